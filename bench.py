@@ -18,17 +18,24 @@ never leave HBM in between; MSD shards the ATOMS, one all-reduce of the S x W
 float64 sums.  ``value`` = 5000 frames / step time, whatever N is.
 ``--scaling weak`` instead gives every rank its own 5000-frame block.
 
-After the RDF+MSD steps the same K steps are repeated with
-``Bad({'Zn-N': 2.5}, dtheta=0.05)`` added (BASELINE configs[3]) and reported
-under ``configs3`` -- never in ``value``, so that the metric means the same
-work at every N.
-
 Rank 0 prints ONE JSON line.  ``roofline`` is computed for the dominant kernel
 (the RDF tile kernel) from HIP events recorded inside the library on the
-launching stream; ``cpu_baseline`` times the CPU oracle on a bounded sample on
-this box's host cores (N = 1 only); ``verified`` says whether the timed results
-themselves were tied to the oracle after the timed region (frames sampled by
-leave-one-out for RDF, an atom slice for MSD).
+launching stream during the timed steps.  A plain run does nothing else: set-up,
+W warm-up steps, K timed steps, the outputs (``--dump-outputs DIR``), the line.
+
+``--full`` adds every other leg, after the timed steps and never in ``value``:
+the same K steps repeated with ``Bad({'Zn-N': 2.5}, dtheta=0.05)`` added
+(BASELINE configs[3], ``configs3``); the MSD class alone (``roofline_msd``);
+``verified``, whether the timed results themselves were tied to the oracle
+(frames sampled by leave-one-out for RDF, an atom slice for MSD);
+``cpu_baseline``, the CPU oracle on a bounded sample on the host's cores, and the
+host-input legs (N = 1 only); coordination numbers on the headline trajectory,
+the realistic cells and the other configs of BASELINE.json (N = 1 only).
+
+``--dump-outputs DIR`` writes what the last timed step computed -- the arrays a
+caller of ``Rdf`` / ``WindowMsd`` receives -- as float64 ``DIR/<name>.npy``
+(rank 0).  The inputs are generated from fixed seeds, so two builds run with the
+same arguments can be compared output for output.
 """
 
 import argparse
@@ -554,6 +561,29 @@ def host_legs(packed, rdf, msd, local_rank, F, N):
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, rdf, msd):
+    """--dump-outputs: the results of the last timed step as a caller receives them (``.data`` of both classes, the
+    integer RDF histogram, the MSD sums), float64, one ``<name>.npy`` each.  Should they exceed DUMP_BYTES_MAX in all
+    (only at sizes far beyond the headline), each array is cut to its share by a fixed-seed sample of its elements."""
+    hist = np.asarray(rdf.hist).view(np.uint64)
+    if hist.size and int(hist.max()) >= 1 << 53:
+        raise ValueError("RDF counts above 2^53 have no exact float64 form")
+    arrays = {"rdf_data": rdf.data.to_numpy(dtype=np.float64),          # [bins][r, every g(r) column]
+              "rdf_hist": hist.astype(np.float64),                       # ordered-pair counts [S][S][bins]
+              "msd_data": msd.data.to_numpy(dtype=np.float64),          # [windows][Time, every MSD column]
+              "msd_sumsq": np.asarray(msd.sumsq, dtype=np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_BYTES_MAX:
+            keep = max(1, int(a.size * DUMP_BYTES_MAX // total))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -563,18 +593,26 @@ def main():
     ap.add_argument("--reps", type=str, default="3,3,4")
     ap.add_argument("--scaling", choices=("strong", "weak"), default="strong",
                     help="N > 1: strong = one shared trajectory sharded over the ranks (default); weak = a block per rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (configs[3], the MSD class alone, the oracle "
+                         "checks, the CPU baseline, host input, CN, realistic cells, configs[1] / configs[4])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 saves the results of the last timed step as float64 DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and host-input legs")
     ap.add_argument("--cpu-rdf-frames", type=int, default=24)
-    ap.add_argument("--no-bad", action="store_true", help="skip the configs[3] leg (RDF+BAD+MSD steps after the timed ones)")
+    ap.add_argument("--no-bad", action="store_true",
+                    help="--full: skip the configs[3] leg (RDF+BAD+MSD steps after the timed ones)")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the realistic-cell and the supplementary configs[1] / configs[4] legs (N = 1)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the oracle spot checks of the timed results")
+                    help="--full: skip the realistic-cell and the supplementary configs[1] / configs[4] legs (N = 1)")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the oracle spot checks of the timed results")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL); gloo only for rehearsals")
     ap.add_argument("--all-on-device", type=int, default=None, help="rehearsal: put every rank on this GPU")
     ap.add_argument("--dump-hist", type=str, default=None, help="rank 0 saves the merged RDF histogram (npy) here")
     ap.add_argument("--rank-probe", type=int, default=None, metavar="CODE",
                     help="launcher check (no GPU needed): every rank prints its RANK / WORLD_SIZE and exits with CODE")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started plainly (`python bench.py --gpus N`): this process becomes the launcher.  It has not touched the
@@ -695,28 +733,32 @@ def main():
         return res, elapsed, mean
 
     (rdf, msd, _), elapsed, mean = timed(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rdf, msd)
     cfg3 = None
-    if not args.no_bad:
+    if args.full and not args.no_bad:
         (rdf3, msd3, bad3), elapsed3, mean3 = timed(True)
         cfg3 = (bad3, elapsed3, mean3)
         assert "N-Zn-N" in bad3.data.columns
 
-    # the MSD pipeline ALONE (nothing else on the GPU): what roofline_msd prices.  Inside the steps above its kernels
-    # share the chip with the RDF launch, and their in-step durations say how well the two overlap, not how fast they are.
-    seq = {"all": [], "dom": [], "wall": []}
-    fence()
-    for rep in range(args.warmup + args.steps):
-        t0 = time.perf_counter()
-        m = WindowMsd.from_trajectory(packed, delta_time=100, timestep=1, device=local_rank, distributed=mode)
-        m.result()
-        if rep >= args.warmup:
-            seq["wall"].append(time.perf_counter() - t0)
-            seq["all"].append(m._stats["kernel_s_all"])
-            seq["dom"].append(m._stats["kernel_s_dominant"])
-    msd_path = m._stats["path"]
-    seq = {k: float(np.mean(v)) for k, v in seq.items()}
-    del m
-    fence()
+    seq = None
+    if args.full:
+        # the MSD pipeline ALONE (nothing else on the GPU): what roofline_msd prices.  Inside the steps above its kernels
+        # share the chip with the RDF launch, and their in-step durations say how well the two overlap, not how fast they are.
+        seq = {"all": [], "dom": [], "wall": []}
+        fence()
+        for rep in range(args.warmup + args.steps):
+            t0 = time.perf_counter()
+            m = WindowMsd.from_trajectory(packed, delta_time=100, timestep=1, device=local_rank, distributed=mode)
+            m.result()
+            if rep >= args.warmup:
+                seq["wall"].append(time.perf_counter() - t0)
+                seq["all"].append(m._stats["kernel_s_all"])
+                seq["dom"].append(m._stats["kernel_s_dominant"])
+        msd_path = m._stats["path"]
+        seq = {k: float(np.mean(v)) for k, v in seq.items()}
+        del m
+        fence()
 
     per_rank = {"rank": rank, "device": local_rank, "rdf_frames": list(_rdf_range(F, rank, world, strong)),
                 "kernel_s": {k: mean[k] for k in ("rdf_dom", "rdf_all", "msd_all")},
@@ -820,18 +862,6 @@ def main():
                                  "to this kernel -- see valu_issue and pair_evals_per_s"},
             "pair_evals_per_s": pairs / t_rdf, "pairs_in_range_per_s": in_range / t_rdf,
             "roofline_valu": roofline_valu, "valu_issue": valu, "counter_files_match_built_sources": counters_current,
-            "roofline_msd": {"kernel": "msd pipeline, fused form (msd_seg: segment sums + tile sums of m p | com_tiles / com_steps / seg_scan | "
-                                       "msd_fused: second pass over pos, products from registers and LDS | colreduce)"
-                                       if world == 1 else "msd pipeline, atom-sharded fused form (shard_begin | all-reduce of the [F][3] sums | shard_finish)",
-                             "bound": "hbm",
-                             "achieved": msd_bytes / seq["all"] / 1e9, "peak": HBM_PEAK_GBPS,
-                             "unit": "GB/s", "frac": msd_bytes / seq["all"] / 1e9 / HBM_PEAK_GBPS,
-                             "traffic": traffic.get("msd_pipeline"), "pipeline_seconds": seq["all"],
-                             "msd_window_kernel_seconds": seq["dom"], "call_wall_seconds": seq["wall"], "path": msd_path,
-                             "algorithmic_bytes": msd_bytes,
-                             "measured": "the MSD class alone, %d calls back to back after the timed steps (in the steps its "
-                                         "kernels run BESIDE the RDF launch on the second lane: in_step_seconds)" % args.steps,
-                             "in_step_seconds": mean["msd_all"]},
             "kernel_seconds_per_step": {"rdf_tile": t_rdf, "rdf_all_incl_quantize": mean["rdf_all"],
                                         "msd_all": mean["msd_all"]},
             "wall_seconds_per_step": {"constructors_return_after": mean["submit_wall"], "rdf_data_after": mean["rdf_wall"],
@@ -842,6 +872,20 @@ def main():
             "async": os.environ.get("AMOF_ASYNC", "1") != "0",
             "per_rank": ranks,
         }
+        if seq is not None:
+            out["roofline_msd"] = {
+                "kernel": "msd pipeline, fused form (msd_seg: segment sums + tile sums of m p | com_tiles / com_steps / seg_scan | "
+                          "msd_fused: second pass over pos, products from registers and LDS | colreduce)"
+                          if world == 1 else "msd pipeline, atom-sharded fused form (shard_begin | all-reduce of the [F][3] sums | shard_finish)",
+                "bound": "hbm",
+                "achieved": msd_bytes / seq["all"] / 1e9, "peak": HBM_PEAK_GBPS,
+                "unit": "GB/s", "frac": msd_bytes / seq["all"] / 1e9 / HBM_PEAK_GBPS,
+                "traffic": traffic.get("msd_pipeline"), "pipeline_seconds": seq["all"],
+                "msd_window_kernel_seconds": seq["dom"], "call_wall_seconds": seq["wall"], "path": msd_path,
+                "algorithmic_bytes": msd_bytes,
+                "measured": "the MSD class alone, %d calls back to back after the timed steps (in the steps its "
+                            "kernels run BESIDE the RDF launch on the second lane: in_step_seconds)" % args.steps,
+                "in_step_seconds": mean["msd_all"]}
         if cfg3:
             bad3, elapsed3, mean3 = cfg3
             out["configs3"] = {
@@ -859,7 +903,7 @@ def main():
             }
         if args.dump_hist:
             np.save(args.dump_hist, np.asarray(rdf.hist).view(np.uint64))
-        if not args.no_verify and strong:
+        if args.full and not args.no_verify and strong:
             try:
                 out["verification"] = verify(packed, ctx, rdf, msd, [0, F // 3 + 1, F - 1][:3 if F > 2 else 1])
                 out["verified"] = out["verification"]["ok"]
@@ -868,7 +912,7 @@ def main():
                 out["verified"] = False
         else:
             out["verified"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             window = np.arange(0, (F // 2), 100)
             out["cpu_baseline"] = cpu_baseline(packed, rmax, nbins, window, args.cpu_rdf_frames)
             out["cpu_baseline"]["host_cpus"] = os.cpu_count()
@@ -877,7 +921,7 @@ def main():
                 out.update(host_legs(packed, rdf, msd, local_rank, F, N))
             except Exception as exc:
                 out["host_legs_error"] = repr(exc)
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             # coordination numbers on the headline trajectory (never `value`): the one kernel of the path that is HBM bound as
             # north_star pictures it -- the Zn / N rows of every frame are fetched once and searched inside LDS
             try:

@@ -103,7 +103,7 @@ def test_bench_starts_its_own_ranks_from_a_plain_shell():
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--all-on-device", "0", "--backend", "gloo",
-           "--frames", "96", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-bad"]
+           "--frames", "96", "--steps", "1", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra", "--no-bad"]
     run = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-3000:]
     rows = [json.loads(l) for l in run.stdout.splitlines() if l.startswith('{"metric"')]

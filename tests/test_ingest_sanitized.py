@@ -34,9 +34,20 @@ def tsan_driver(tmp_path_factory):
     return _build(tmp_path_factory, ["-fsanitize=thread"])
 
 
-def _run(driver, paths):
+def _no_aslr():
+    """ThreadSanitizer of gcc 11 places its shadow memory for a 28-bit address-space randomisation; under the 32 bits
+    recent kernels default to (vm.mmap_rnd_bits) libraries can land inside it and the driver dies before main with
+    "unexpected memory mapping".  Newer runtimes re-execute themselves without randomisation; here the driver is
+    started that way (`setarch -R`: this one process, no system setting)."""
+    import platform
+    import shutil
+    setarch = shutil.which("setarch")
+    return [setarch, platform.machine(), "-R"] if setarch else []
+
+
+def _run(driver, paths, prefix=()):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([driver] + paths, capture_output=True, text=True, env=env, timeout=300)
+    r = subprocess.run(list(prefix) + [driver] + paths, capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
     assert "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-2000:]
@@ -89,5 +100,5 @@ def test_threaded_read_clean_under_tsan(tsan_driver, tmp_path):
             fh.write("7\nframe %d\n" % f)
             for k in range(7):
                 fh.write("C %.8f %.8f %.8f\n" % tuple(rng.normal(size=3)))
-    out = _run(tsan_driver, [str(tmp_path / "many.xyz"), os.path.join(GOLD, "ZIF-4.xyz")])
+    out = _run(tsan_driver, [str(tmp_path / "many.xyz"), os.path.join(GOLD, "ZIF-4.xyz")], prefix=_no_aslr())
     assert "rc=0 F=64 N=7" in out
