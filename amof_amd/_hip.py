@@ -35,6 +35,7 @@ EXPORTS = [
     "amof_rdf_accumulate", "amof_rdf_accumulate_dev", "amof_cn_count", "amof_bad_hist", "amof_bad_hist_dev",
     "amof_bad_hist_by_cn",
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
+    "amof_vanhove_window", "amof_vanhove_window_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
 ]
@@ -127,6 +128,10 @@ def load_library():
         lib.amof_msd_shard_begin.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, P]
         lib.amof_msd_shard_finish.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, P, P]
         lib.amof_msd_direct.argtypes = [P, TP, P]
+        lib.amof_vanhove_window.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P]
+        lib.amof_vanhove_window_dev.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P]
         lib.amof_xyz_scan.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
         lib.amof_xyz_read.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                       P, P, P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
@@ -603,6 +608,44 @@ class Context(Lane):
 
 
     @_locked
+    def vanhove_window(self, packed, windows, dr, nbins, unwrap=False, remove_com=True, atom_range=None, com=None, out=None):
+        """``(counts [S][W][nbins] u64, overflow [S][W] u64, moments [S][W][2] f64, kinds)``: the raw self Van Hove
+        histograms of ``amof_vanhove_window`` (moments: sum of r^2, sum of r^4 over every sample).
+
+        ``out``: optional ``(counts, overflow, moments)`` torch CUDA tensors (int64 ``[S][W][nbins]``, int64 ``[S][W]``, f64
+        ``[S][W][2]``) the results are ADDED into on the device (they stay resident for the ranks' all-reduce); ``com``:
+        optional torch CUDA f64 ``[F][3]`` precomputed centre of mass (``msd_com``)."""
+        th = self._traj(packed)
+        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        a0, a1 = (0, th.n_atoms) if atom_range is None else atom_range
+        S, W, nbins = th.S, len(windows), int(nbins)
+        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), W, 1 if unwrap else 0,
+                1 if remove_com else 0, int(a0), int(a1), float(dr), nbins)
+        if out is not None or com is not None:
+            import torch
+            dev = torch.device("cuda", self.device)
+            if out is None:
+                out = (torch.zeros((S, W, nbins), dtype=torch.int64, device=dev), torch.zeros((S, W), dtype=torch.int64, device=dev),
+                       torch.zeros((S, W, 2), dtype=torch.float64, device=dev))
+            for x, n in zip(out, (S * W * nbins, S * W, S * W * 2)):
+                assert x.is_cuda and x.is_contiguous() and x.numel() == n and x.element_size() == 8
+                assert x.device.index == self.device
+            if com is not None:
+                assert com.is_cuda and com.is_contiguous() and com.numel() == 3 * th.n_frames and com.element_size() == 8
+                assert com.device.index == self.device
+            self._order_after_torch()
+            self._check(self._lib.amof_vanhove_window_dev(*(args + (ctypes.c_void_p(com.data_ptr()) if com is not None else None,) +
+                                                           tuple(ctypes.c_void_p(x.data_ptr()) for x in out))))
+            return out + (th.kinds,)
+        counts = np.zeros((S, W, nbins), dtype=np.uint64)
+        overflow = np.zeros((S, W), dtype=np.uint64)
+        moments = np.zeros((S, W, 2), dtype=np.float64)
+        self._check(self._lib.amof_vanhove_window(*(args + (ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(overflow.ctypes.data),
+                                                            ctypes.c_void_p(moments.ctypes.data)))))
+        return counts, overflow, moments, th.kinds
+
+
+    @_locked
     def msd_shard_begin(self, packed, windows, atom_range, csum):
         """first half of an atom-sharded window MSD (``amof_msd_shard_begin``): ``csum`` (torch CUDA f64 ``[F][3]``) receives
         the mass-weighted coordinate sums of the atoms ``[a0, a1)`` per frame -- the caller all-reduces it over the ranks.
@@ -739,6 +782,18 @@ class MultiContext(object):
             jobs.append(job)
         res = self._run(jobs)
         return sum(r[0] for r in res), res[0][1]
+
+    def vanhove_window(self, packed, windows, dr, nbins, unwrap=False, remove_com=True, atom_range=None):
+        """atoms sharded over the devices; the integer counts add up exactly, the moments up to float64 summation order"""
+        lo, hi = (0, packed.n_atoms) if atom_range is None else atom_range
+        jobs = []
+        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
+            def job(ctx=ctx, a=a, b=b):
+                tr, _ = self._for_device(packed, ctx)
+                return ctx.vanhove_window(tr, windows, dr, nbins, unwrap=unwrap, remove_com=remove_com, atom_range=(a, b))
+            jobs.append(job)
+        res = self._run(jobs)
+        return sum(r[0] for r in res), sum(r[1] for r in res), sum(r[2] for r in res), res[0][3]
 
     def msd_direct(self, packed):
         return self.ctxs[0].msd_direct(self._for_device(packed, self.ctxs[0])[0])

@@ -137,7 +137,9 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *   MSD  "msd_fused" (no transposed copy: diagonal cells, evenly spaced windows), "msd_stream" (register-ring comb, window
  *        spacing 64..256), "msd_comb" (block comb kernels incl. the
  *        double-buffered and > 32-window passes), "msd_group" (arbitrary window lists), "msd_comb_global" /
- *        "msd_global" (series too long for LDS), "msd_direct", "msd_com" (amof_msd_com_dev alone) */
+ *        "msd_global" (series too long for LDS), "msd_direct", "msd_com" (amof_msd_com_dev alone)
+ *   Van Hove "msd_vanhove" (u32 counters in LDS, lag tiles), "msd_vanhove_global" (u64 counters in global memory: more than
+ *        AMOF_MAX_LDS_BINS bins, or AMOF_VANHOVE_GLOBAL=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -255,6 +257,36 @@ int amof_msd_shard_begin(amof_ctx *ctx, const amof_traj *traj, const int32_t *wi
 int amof_msd_shard_finish(amof_ctx *ctx, const amof_traj *traj, const int32_t *windows, int32_t n_windows,
                           int64_t atom_begin, int64_t atom_end, const double *csum_dev /* device [F][3], summed over the ranks */,
                           double *sumsq_dev /* device [S][W], += */);
+
+/*
+ * Self Van Hove function and the moments of the non-Gaussian parameter (window form).
+ * Replaces nothing the reference computes: the same displacements as amof_msd_window (amof.trajectory.get_delta_pos,
+ * amof/trajectory.py:285-303; the centre-of-mass removal and optional unwrap of amof/msd.py:222-237; the time origins
+ * k = 1 .. F-m-1 that WindowMsd.compute_msd_of_m visits, amof/msd.py:185-205), binned instead of summed.
+ *   u_i(k): the running sum of wrapped frame-to-frame displacements, as amof_msd_window defines it.
+ *   one sample per atom i of [atom_begin, atom_end), window m = windows[w] and origin k = 1 .. F-m-1:
+ *       D = u_i(k+m) - u_i(k),  r2 = (Dx*Dx + Dy*Dy) + Dz*Dz (float64, no fma),  r = sqrt(r2) (correctly rounded)
+ *       bin b = (int)(r / dr); b >= nbins goes to overflow.  n_s(m) = N_s (F-m-1) samples per species and window.
+ *   counts[(s*W + w)*nbins + b]   samples of species s (library order) at window w in bin b
+ *   overflow[s*W + w]             samples with b >= nbins
+ *   moments[(s*W + w)*2 + 0] = sum of r2,  [.. + 1] = sum of r2*r2 -- over every sample, overflow included
+ *       (sum of r2 is amof_msd_window's sumsq up to float64 rounding; the alpha_2 of the host is
+ *        3 n sum4 / (5 sum2^2) - 1).  Two identical calls give identical bits: fixed-order reductions, integer atomics.
+ *   unwrap, remove_com, atom_begin, atom_end: as amof_msd_window.  dr > 0, nbins >= 0 (no capacity limit on nbins, W,
+ *   F or N: histograms beyond the LDS take the global-counter kernel).
+ * The host form overwrites its outputs.  Errors: AMOF_EINVAL (bad window, range, dr, nbins, NULL argument),
+ * AMOF_ENOMEM, AMOF_EHIP, AMOF_ENODEVICE.
+ */
+int amof_vanhove_window(amof_ctx *ctx, const amof_traj *traj, const int32_t *windows, int32_t n_windows, int32_t unwrap,
+                        int32_t remove_com, int64_t atom_begin, int64_t atom_end, double dr, int32_t nbins,
+                        uint64_t *counts /* host [S][W][nbins] */, uint64_t *overflow /* host [S][W] */,
+                        double *moments /* host [S][W][2] */);
+/* The same with the results ADDED into device buffers (atom-sharded ranks all-reduce them next) and, optionally, the
+ * per-frame centre of mass handed in (com_dev: device [F][3] from amof_msd_com_dev, NULL = computed here; not with unwrap). */
+int amof_vanhove_window_dev(amof_ctx *ctx, const amof_traj *traj, const int32_t *windows, int32_t n_windows, int32_t unwrap,
+                            int32_t remove_com, int64_t atom_begin, int64_t atom_end, double dr, int32_t nbins,
+                            const double *com_dev /* device [F][3] or NULL */, uint64_t *counts_dev /* device [S][W][nbins], += */,
+                            uint64_t *overflow_dev /* device [S][W], += */, double *moments_dev /* device [S][W][2], += */);
 
 /*
  * Direct MSD with running unwrap, orthogonal cells only (deprecated in the reference).
