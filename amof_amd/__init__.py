@@ -7,6 +7,12 @@ Drop-in mirrors of the reference's hot-path classes (coudertlab/amof v1.1.0):
     amof.bad.Bad                  -> amof_amd.bad.Bad
     amof.cn.CoordinationNumber    -> amof_amd.cn.CoordinationNumber
 
+Analyses beyond the reference:
+
+    amof_amd.vanhove.WindowVanHove                self Van Hove function, non-Gaussian parameter
+    amof_amd.structure_factor.StructureFactor     static structure factor S(q) by direct summation over the
+                                                  reciprocal lattice (density_modes: rho_a(k) of one frame)
+
 All distance arithmetic runs in hand-written HIP kernels (gfx950) behind the C
 ABI of ``include/amof_hip.h``; there is no CPU fallback.
 """

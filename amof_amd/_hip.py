@@ -36,6 +36,7 @@ EXPORTS = [
     "amof_bad_hist_by_cn",
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev",
+    "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
 ]
@@ -132,6 +133,11 @@ def load_library():
                                             ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P]
         lib.amof_vanhove_window_dev.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P]
+        lib.amof_sq_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_double, ctypes.c_int32, P, P, P]
+        lib.amof_sq_accumulate_dev.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.c_double, ctypes.c_int32, P, P, P, P]
+        lib.amof_sq_modes.argtypes = [P, TP, ctypes.c_int64, P, ctypes.c_int32, P]
         lib.amof_xyz_scan.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
         lib.amof_xyz_read.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                       P, P, P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
@@ -149,6 +155,12 @@ def load_library():
             raise RuntimeError("libamofhip.so ABI version %d, expected %d" % (lib.amof_abi_version(), ABI_VERSION))
         _lib = lib
         return lib
+
+
+def reciprocal(cell):
+    """``2 pi inv(cell).T`` of every cell (``[..][3][3]``, rows = cell vectors): rows = reciprocal vectors (amof_sq_*)"""
+    cell = np.asarray(cell, dtype=np.float64)
+    return 2.0 * np.pi * np.swapaxes(np.linalg.inv(cell), -1, -2)
 
 
 def device_count():
@@ -646,6 +658,53 @@ class Context(Lane):
 
 
     @_locked
+    def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None, out=None):
+        """``(counts [nbins] u64, sums [P][nbins] f64, beyond, kinds)`` of ``amof_sq_accumulate``: the vectors ``hkl``
+        (int ``[K][3]``) of the frames ``frame_range[0], + frame_stride, ... < frame_range[1]``, P = S(S+1)/2 species
+        pairs a <= b in ``kinds`` order.  ``recip``: ``[n_cells][3][3]`` (default ``reciprocal(packed.cell)``).
+
+        ``out``: optional ``(counts, sums)`` torch CUDA int64 tensors (``[nbins + 1]``: the counts, then beyond;
+        ``[P][nbins]``: fixed-point sums) the results are ADDED into on the device; returns ``(counts, sums, scale_log2,
+        kinds)`` then, with sums = ``sums * 2**-scale_log2[p]``."""
+        th = self._traj(packed)
+        hkl = np.ascontiguousarray(hkl, dtype=np.int32).reshape(-1, 3)
+        recip = np.ascontiguousarray(reciprocal(packed.cell) if recip is None else recip, dtype=np.float64)
+        assert recip.shape == (packed.cell.shape[0], 3, 3)
+        f0, f1 = (0, th.n_frames) if frame_range is None else frame_range
+        S, nbins = th.S, int(nbins)
+        P = S * (S + 1) // 2
+        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(recip.ctypes.data), ctypes.c_void_p(hkl.ctypes.data), len(hkl),
+                int(f0), int(f1), int(frame_stride), float(dq), nbins)
+        if out is not None:
+            counts, sums = out
+            assert counts.is_cuda and counts.is_contiguous() and counts.numel() == nbins + 1 and counts.element_size() == 8
+            assert sums.is_cuda and sums.is_contiguous() and sums.numel() == P * nbins and sums.element_size() == 8
+            assert counts.device.index == self.device and sums.device.index == self.device
+            scale = np.zeros(P, dtype=np.int32)
+            self._order_after_torch()
+            self._check(self._lib.amof_sq_accumulate_dev(*(args + (ctypes.c_void_p(counts.data_ptr()),
+                                                                   ctypes.c_void_p(sums.data_ptr()),
+                                                                   ctypes.c_void_p(counts.data_ptr() + 8 * nbins),
+                                                                   ctypes.c_void_p(scale.ctypes.data)))))
+            return counts, sums, scale, th.kinds
+        counts = np.zeros(nbins, dtype=np.uint64)
+        sums = np.zeros((P, nbins), dtype=np.float64)
+        beyond = np.zeros(1, dtype=np.uint64)
+        self._check(self._lib.amof_sq_accumulate(*(args + (ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(sums.ctypes.data),
+                                                           ctypes.c_void_p(beyond.ctypes.data)))))
+        return counts, sums, int(beyond[0]), th.kinds
+
+    @_locked
+    def sq_modes(self, packed, hkl, frame=0):
+        """``(rho [K][S] complex128, kinds)``: rho_a(k) of one frame for the vectors ``hkl`` (``amof_sq_modes``)"""
+        th = self._traj(packed)
+        hkl = np.ascontiguousarray(hkl, dtype=np.int32).reshape(-1, 3)
+        rho = np.zeros((len(hkl), th.S, 2), dtype=np.float64)
+        self._check(self._lib.amof_sq_modes(self._h, ctypes.byref(th.c), int(frame), ctypes.c_void_p(hkl.ctypes.data), len(hkl),
+                                            ctypes.c_void_p(rho.ctypes.data)))
+        return rho[:, :, 0] + 1j * rho[:, :, 1], th.kinds
+
+    @_locked
     def msd_shard_begin(self, packed, windows, atom_range, csum):
         """first half of an atom-sharded window MSD (``amof_msd_shard_begin``): ``csum`` (torch CUDA f64 ``[F][3]``) receives
         the mass-weighted coordinate sums of the atoms ``[a0, a1)`` per frame -- the caller all-reduces it over the ranks.
@@ -791,6 +850,24 @@ class MultiContext(object):
             def job(ctx=ctx, a=a, b=b):
                 tr, _ = self._for_device(packed, ctx)
                 return ctx.vanhove_window(tr, windows, dr, nbins, unwrap=unwrap, remove_com=remove_com, atom_range=(a, b))
+            jobs.append(job)
+        res = self._run(jobs)
+        return sum(r[0] for r in res), sum(r[1] for r in res), sum(r[2] for r in res), res[0][3]
+
+    def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None):
+        """frames sharded over the devices (whole strides per device; a device trajectory on another GPU is copied for the
+        shard's frames only): counts add up exactly, the sums to float64 order"""
+        lo, hi = (0, packed.n_frames) if frame_range is None else frame_range
+        stride = int(frame_stride)
+        n_sel = max(0, (hi - lo + stride - 1) // stride)
+        recip = reciprocal(packed.cell) if recip is None else np.asarray(recip, dtype=np.float64)
+        jobs = []
+        for ctx, (a, b) in zip(self.ctxs, self._shards(0, n_sel)):
+            def job(ctx=ctx, a=a, b=b):
+                f0, f1 = lo + a * stride, min(hi, lo + b * stride)
+                tr, fr = self._for_device(packed, ctx, (f0, max(f0, f1)))
+                rc = recip if tr.cell.shape[0] == recip.shape[0] else recip[f0:max(f0, f1)]
+                return ctx.sq_accumulate(tr, hkl, dq, nbins, frame_range=fr, frame_stride=stride, recip=rc)
             jobs.append(job)
         res = self._run(jobs)
         return sum(r[0] for r in res), sum(r[1] for r in res), sum(r[2] for r in res), res[0][3]

@@ -139,7 +139,9 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        double-buffered and > 32-window passes), "msd_group" (arbitrary window lists), "msd_comb_global" /
  *        "msd_global" (series too long for LDS), "msd_direct", "msd_com" (amof_msd_com_dev alone)
  *   Van Hove "msd_vanhove" (u32 counters in LDS, lag tiles), "msd_vanhove_global" (u64 counters in global memory: more than
- *        AMOF_MAX_LDS_BINS bins, or AMOF_VANHOVE_GLOBAL=1) */
+ *        AMOF_MAX_LDS_BINS bins, or AMOF_VANHOVE_GLOBAL=1)
+ *   S(q) "sq" (counters in LDS), "sq_bin_global" (counters in global memory: (P + 1) nbins beyond the LDS budget, or
+ *        AMOF_SQ_GLOBAL=1), "sq_modes" (amof_sq_modes) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -287,6 +289,49 @@ int amof_vanhove_window_dev(amof_ctx *ctx, const amof_traj *traj, const int32_t 
                             int32_t remove_com, int64_t atom_begin, int64_t atom_end, double dr, int32_t nbins,
                             const double *com_dev /* device [F][3] or NULL */, uint64_t *counts_dev /* device [S][W][nbins], += */,
                             uint64_t *overflow_dev /* device [S][W], += */, double *moments_dev /* device [S][W][2], += */);
+
+/*
+ * Static structure factor by direct summation over reciprocal-lattice vectors.
+ * Replaces nothing the reference computes (the structure of an amorphous MOF is compared with total-scattering data; the
+ * reference stops at g(r), amof/rdf.py).  Cells must be periodic on all three axes.
+ *   For every selected frame f = frame_begin, frame_begin + frame_stride, ... < frame_end and every vector m of hkl
+ *   (integer triples, not (0, 0, 0); the caller passes half a space: rho(-k) = conj rho(k)):
+ *     R = recip[cell of f] ([3][3], 2 pi inv(cell).T, computed by the caller),
+ *     qx = (h*R[0][0] + k*R[1][0]) + l*R[2][0] (likewise y, z; float64, no fma), q2 = (qx*qx + qy*qy) + qz*qz,
+ *     q = sqrt(q2) (correctly rounded), bin b = (int)(q / dq); b >= nbins: one more in *beyond, nothing else.
+ *     rho_a = sum over the atoms j of species a of exp(2 pi i phi_j / 2^32), phi_j = h ux_j + k uy_j + l uz_j (mod 2^32)
+ *       with u = the atom's fractional coordinates * 2^32, folded into the cell (the fast paths' quantisation): the
+ *       phase is exact for any cell and for unwrapped input; one f32 v_sin / v_cos per term, f32 partials over <= 64
+ *       atoms folded into f64 (the tests hold every S column within 1e-5 max(1, |S|) of a float64 restatement; no
+ *       separate ulp measurement of v_sin / v_cos was made).
+ *     counts[b] += 1;  for every unordered pair p = (a, c), a <= c, in the order (0,0), (0,1) .. (0,S-1), (1,1) ..:
+ *     sums[p][b] += t_ac = Re rho_a Re rho_c + Im rho_a Im rho_c.
+ *   Each t is rounded to an integer multiple of 2^-s_p and added as int64 (integer atomics: the result is independent of
+ *   the launch and of how frames are split); s_p is the largest exponent with F * C * (N_a N_c + 1/2) * 2^s_p < 2^62.
+ *   F = traj->n_frames; C = the largest number of vectors of hkl that can fall into one bin in one frame of any of the
+ *   trajectory's cells (|q| within delta |hkl| of its value on the mean reciprocal matrix, delta the largest Frobenius
+ *   norm of a cell's deviation from that mean): every frame range of one trajectory has the same scale, and ranges add
+ *   up bit for bit.  When 2^-s_p / sqrt(N_a N_c) would exceed 2^-20: AMOF_ECAPACITY (the caller passes shorter
+ *   trajectories: StructureFactor then accumulates chunks of frames).  Two identical calls give identical bits (the
+ *   atoms are summed in species order, in a fixed order).
+ *   Errors: AMOF_EINVAL (pbc not all set, hkl (0, 0, 0), bad frame range, dq, nbins < 1, positions beyond 10^4 cells,
+ *   NULL argument), AMOF_ECAPACITY, AMOF_ESINGULAR, AMOF_ENOMEM, AMOF_EHIP, AMOF_ENODEVICE.
+ * The host form overwrites counts, sums (float64: int64 * 2^-s_p) and *beyond.
+ */
+int amof_sq_accumulate(amof_ctx *ctx, const amof_traj *traj, const double *recip /* host [n_cells][3][3] */,
+                       const int32_t *hkl /* host [K][3] */, int32_t K, int64_t frame_begin, int64_t frame_end,
+                       int64_t frame_stride, double dq, int32_t nbins, uint64_t *counts /* host [nbins] */,
+                       double *sums /* host [P][nbins], P = S(S+1)/2 */, uint64_t *beyond /* host [1] */);
+/* The same with the results ADDED into device buffers (frame-sharded ranks all-reduce them next): sums_dev holds the
+ * int64 fixed-point sums (sums = sums_dev * 2^-scale_log2[p]); scale_log2 (host [P]) receives the exponents. */
+int amof_sq_accumulate_dev(amof_ctx *ctx, const amof_traj *traj, const double *recip, const int32_t *hkl, int32_t K,
+                           int64_t frame_begin, int64_t frame_end, int64_t frame_stride, double dq, int32_t nbins,
+                           uint64_t *counts_dev /* device [nbins], += */, int64_t *sums_dev /* device [P][nbins], += */,
+                           uint64_t *beyond_dev /* device [1], += */, int32_t *scale_log2 /* host [P] */);
+/* rho_a(k) of one frame: rho[(m*S + a)*2 + 0 / 1] = Re / Im rho_a of vector m of hkl (the kernel of amof_sq_accumulate,
+ * written out instead of binned; any hkl but (0, 0, 0), no half-space rule).  Errors as amof_sq_accumulate. */
+int amof_sq_modes(amof_ctx *ctx, const amof_traj *traj, int64_t frame, const int32_t *hkl /* host [K][3] */, int32_t K,
+                  double *rho /* host [K][S][2] */);
 
 /*
  * Direct MSD with running unwrap, orthogonal cells only (deprecated in the reference).
