@@ -183,17 +183,7 @@ inline double fast_guard_rel(const HostGeom &g, int64_t n_cells, bool sq_scaled 
     double kappa = 1.0;
     for (int64_t k = 0; k < n_cells; k++) {
         const double *c = g.rec.data() + (size_t)k * GEOM_STRIDE, *inv = c + 9;
-        double P[3][3], n1 = 0.0, ninf = 0.0;
-        for (int r = 0; r < 3; r++)
-            for (int x = 0; x < 3; x++) {
-                P[r][x] = 0.0;
-                for (int m = 0; m < 3; m++) P[r][x] += fabs(inv[3 * r + m]) * fabs(c[3 * m + x]);
-            }
-        for (int r = 0; r < 3; r++) {
-            ninf = std::max(ninf, P[r][0] + P[r][1] + P[r][2]);
-            n1 = std::max(n1, P[0][r] + P[1][r] + P[2][r]);
-        }
-        kappa = std::max(kappa, sqrt(n1 * ninf));
+        kappa = std::max(kappa, kappa_cell(c, inv));
     }
     return 1.1 * (5.0 * kappa + 3.06) * u;
 }
@@ -204,18 +194,7 @@ inline double fast_guard_rel_rdf(const HostGeom &g, const double *cells, int64_t
 {
     const double u = 1.0 / 16777216.0;
     if (g.all_ortho) return 1.1 * (3.5 + 1.56) * u;
-    double kappa = 1.0;
-    static const int perms[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {1, 0, 2}, {2, 1, 0}};
-    for (int64_t k = 0; k < n_cells; k++)
-        for (int pm = 0; pm < 6; pm++) {
-            const int *ord = perms[pm];
-            double rows[9], L[9];
-            for (int q = 0; q < 3; q++)
-                for (int x = 0; x < 3; x++) rows[3 * q + x] = cells[9 * k + 3 * ord[q] + x];
-            lower_factor(rows, L);
-            kappa = std::max(kappa, kappa_lower(L));
-        }
-    return 1.1 * (5.0 * kappa + 3.06) * u;
+    return 1.1 * (5.0 * kappa_rdf(cells, n_cells) + 3.06) * u;
 }
 
 // species-sorted tiling of the atoms

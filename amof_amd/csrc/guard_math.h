@@ -47,6 +47,39 @@ inline double kappa_lower(const double L[9])
     }
     return sqrt(n1 * ninf);
 }
+// kappa of the RDF fast paths' chain for general cells: the largest kappa_lower over the six stored axis orders a kernel
+// may pick, over every cell of the trajectory (cells: [n_cells][9], rows = lattice vectors)
+inline double kappa_rdf(const double *cells, long long n_cells)
+{
+    double kappa = 1.0;
+    static const int perms[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {1, 0, 2}, {2, 1, 0}};
+    for (long long k = 0; k < n_cells; k++)
+        for (int pm = 0; pm < 6; pm++) {
+            const int *ord = perms[pm];
+            double rows[9], L[9];
+            for (int q = 0; q < 3; q++)
+                for (int x = 0; x < 3; x++) rows[3 * q + x] = cells[9 * k + 3 * ord[q] + x];
+            lower_factor(rows, L);
+            kappa = std::max(kappa, kappa_lower(L));
+        }
+    return kappa;
+}
+// kappa of the neighbour kernels' chain (the cell itself as the scale matrix): P = |C^-1| |C|, sqrt(||P||_1 ||P||_inf)
+// c: cell rows, inv: its inverse (non-periodic columns zeroed)
+inline double kappa_cell(const double c[9], const double inv[9])
+{
+    double P[3][3], n1 = 0.0, ninf = 0.0;
+    for (int r = 0; r < 3; r++)
+        for (int x = 0; x < 3; x++) {
+            P[r][x] = 0.0;
+            for (int m = 0; m < 3; m++) P[r][x] += fabs(inv[3 * r + m]) * fabs(c[3 * m + x]);
+        }
+    for (int r = 0; r < 3; r++) {
+        ninf = std::max(ninf, P[r][0] + P[r][1] + P[r][2]);
+        n1 = std::max(n1, P[0][r] + P[1][r] + P[2][r]);
+    }
+    return sqrt(n1 * ninf);
+}
 // ZF form of the diagonal-cell tile kernel (rdf.hip fast_q_zf): the slab-axis difference is the difference of two f32
 // coordinates in bins, Z_j' = fl(c (z_j - z0)), Z_i' = fl(c (z_i - z0)), one rounding each (f64 product -> f32):
 //   |dz - Z| <= A + u |Z|,  A = u (|Z_j'| + |Z_i'|) <= u Hb (G / 2^32 + 1/16 + 1/256)
