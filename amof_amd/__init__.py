@@ -10,6 +10,7 @@ Drop-in mirrors of the reference's hot-path classes (coudertlab/amof v1.1.0):
 Analyses beyond the reference:
 
     amof_amd.vanhove.WindowVanHove                self Van Hove function, non-Gaussian parameter
+    amof_amd.vanhove_distinct.DistinctVanHove     distinct Van Hove function G_d(r, t) on the same lags
     amof_amd.structure_factor.StructureFactor     static structure factor S(q) by direct summation over the
                                                   reciprocal lattice (density_modes: rho_a(k) of one frame)
 

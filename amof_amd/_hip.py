@@ -35,7 +35,7 @@ EXPORTS = [
     "amof_rdf_accumulate", "amof_rdf_accumulate_dev", "amof_cn_count", "amof_bad_hist", "amof_bad_hist_dev",
     "amof_bad_hist_by_cn",
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
-    "amof_vanhove_window", "amof_vanhove_window_dev",
+    "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
@@ -133,6 +133,9 @@ def load_library():
                                             ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P]
         lib.amof_vanhove_window_dev.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P]
+        lib.amof_vanhove_distinct.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_double, ctypes.c_int32, P]
+        lib.amof_vanhove_distinct_dev.argtypes = lib.amof_vanhove_distinct.argtypes
         lib.amof_sq_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_double, ctypes.c_int32, P, P, P]
         lib.amof_sq_accumulate_dev.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -658,6 +661,32 @@ class Context(Lane):
 
 
     @_locked
+    def vanhove_distinct(self, packed, windows, rmax, nbins, origin_stride=1, work_range=None, out=None):
+        """``(hist [S][S][W][nbins] u64, kinds)``: the distinct Van Hove counts of ``amof_vanhove_distinct`` for the entries
+        ``work_range`` (default: all) of the lag-major (lag, origin) work list (amof_amd.vanhove_distinct.work_list).
+
+        ``out``: optional torch CUDA int64 tensor ``[S][S][W][nbins]`` the counts are ADDED into on the device (stays
+        resident for an RCCL merge)."""
+        th = self._traj(packed)
+        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        W, nbins = len(windows), int(nbins)
+        if work_range is None:
+            m = windows.astype(np.int64)
+            F, s = th.n_frames, max(1, int(origin_stride))
+            work_range = (0, int(np.where(F - m - 2 >= 0, (F - m - 2) // s + 1, 0).sum()))
+        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), W, int(origin_stride), int(work_range[0]),
+                int(work_range[1]), float(rmax), nbins)
+        if out is not None:
+            assert out.is_cuda and out.is_contiguous() and out.numel() == th.S * th.S * W * nbins and out.element_size() == 8
+            assert out.device.index == self.device
+            self._order_after_torch()
+            self._check(self._lib.amof_vanhove_distinct_dev(*(args + (ctypes.c_void_p(out.data_ptr()),))))
+            return out, th.kinds
+        hist = np.zeros((th.S, th.S, W, nbins), dtype=np.uint64)
+        self._check(self._lib.amof_vanhove_distinct(*(args + (ctypes.c_void_p(hist.ctypes.data),))))
+        return hist, th.kinds
+
+    @_locked
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None, out=None):
         """``(counts [nbins] u64, sums [P][nbins] f64, beyond, kinds)`` of ``amof_sq_accumulate``: the vectors ``hkl``
         (int ``[K][3]``) of the frames ``frame_range[0], + frame_stride, ... < frame_range[1]``, P = S(S+1)/2 species
@@ -853,6 +882,22 @@ class MultiContext(object):
             jobs.append(job)
         res = self._run(jobs)
         return sum(r[0] for r in res), sum(r[1] for r in res), sum(r[2] for r in res), res[0][3]
+
+    def vanhove_distinct(self, packed, windows, rmax, nbins, origin_stride=1, work_range=None):
+        """the (lag, origin) work list sharded over the devices: the integer counts add up exactly"""
+        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        if work_range is None:
+            m = windows.astype(np.int64)
+            F, s = packed.n_frames, max(1, int(origin_stride))
+            work_range = (0, int(np.where(F - m - 2 >= 0, (F - m - 2) // s + 1, 0).sum()))
+        jobs = []
+        for ctx, (a, b) in zip(self.ctxs, self._shards(*work_range)):
+            def job(ctx=ctx, a=a, b=b):
+                tr, _ = self._for_device(packed, ctx)
+                return ctx.vanhove_distinct(tr, windows, rmax, nbins, origin_stride=origin_stride, work_range=(a, b))
+            jobs.append(job)
+        res = self._run(jobs)
+        return sum(r[0] for r in res), res[0][1]
 
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None):
         """frames sharded over the devices (whole strides per device; a device trajectory on another GPU is copied for the

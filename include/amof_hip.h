@@ -141,7 +141,11 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *   Van Hove "msd_vanhove" (u32 counters in LDS, lag tiles), "msd_vanhove_global" (u64 counters in global memory: more than
  *        AMOF_MAX_LDS_BINS bins, or AMOF_VANHOVE_GLOBAL=1)
  *   S(q) "sq" (counters in LDS), "sq_bin_global" (counters in global memory: (P + 1) nbins beyond the LDS budget, or
- *        AMOF_SQ_GLOBAL=1), "sq_modes" (amof_sq_modes) */
+ *        AMOF_SQ_GLOBAL=1), "sq_modes" (amof_sq_modes)
+ *   distinct Van Hove "rdf_distinct_tile" (constant diagonal cell, all axes periodic, one image in reach: quantised frames,
+ *        guarded f32 candidates), "rdf_distinct_exact" (canonical float64 arithmetic per pair, any cell; also
+ *        AMOF_VANHOVE_DISTINCT_EXACT=1), "rdf_distinct_exact_global" (the same with u64 counters in global memory: S nbins
+ *        beyond AMOF_MAX_LDS_BINS, or AMOF_VANHOVE_DISTINCT_GLOBAL=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -289,6 +293,29 @@ int amof_vanhove_window_dev(amof_ctx *ctx, const amof_traj *traj, const int32_t 
                             int32_t remove_com, int64_t atom_begin, int64_t atom_end, double dr, int32_t nbins,
                             const double *com_dev /* device [F][3] or NULL */, uint64_t *counts_dev /* device [S][W][nbins], += */,
                             uint64_t *overflow_dev /* device [S][W], += */, double *moments_dev /* device [S][W][2], += */);
+
+/*
+ * Distinct Van Hove function: pair-distance histograms between two frames of a trajectory.
+ * Replaces nothing the reference computes (the reference has no dynamic pair analysis).
+ *   Lags m = windows[w] (0 <= m < F), origins k = 1, 1 + s, 1 + 2s, ... <= F - m - 1 (s = origin_stride >= 1); the work
+ *   list is every (w, k) in lag-major order (w, then k), n_w = floor((F - m - 2) / s) + 1 entries for lag w (0 if m > F - 2).
+ *   A call handles the entries [work_begin, work_end) of that list: ranges add up bit for bit.
+ *   For every entry and every ordered pair (i, j), i != j: d0 = r_j(k + m) - r_i(k) on the raw float64 positions, the
+ *   canonical minimum image with frame k's cell and pbc (pair_base, plus every further image in reach of
+ *   rmax), counted iff d2 < rmax^2 and b = (int)(sqrt(d2) / (rmax / nbins)) < nbins:
+ *     hist[((a*S + c)*W + w)*nbins + b] += 1,  a = species of i (the centre, at the origin), c = species of j (at k + m),
+ *     library species order.  At m = 0 the counts are the RDF's (amof_rdf_accumulate) over the same frames.
+ *   No centre-of-mass removal, no unwrap: pair distances are periodic.  rmax > 0, nbins >= 1.
+ * The host form overwrites hist.  Errors: AMOF_EINVAL (bad window, stride, work range, rmax, nbins, NULL argument),
+ * AMOF_ENOMEM, AMOF_EHIP, AMOF_ENODEVICE.
+ */
+int amof_vanhove_distinct(amof_ctx *ctx, const amof_traj *traj, const int32_t *windows /* host [W] */, int32_t n_windows,
+                          int64_t origin_stride, int64_t work_begin, int64_t work_end, double rmax, int32_t nbins,
+                          uint64_t *hist /* host [S][S][W][nbins] */);
+/* The same with the counts ADDED into a device buffer (ranks that share the work list all-reduce it next). */
+int amof_vanhove_distinct_dev(amof_ctx *ctx, const amof_traj *traj, const int32_t *windows, int32_t n_windows,
+                              int64_t origin_stride, int64_t work_begin, int64_t work_end, double rmax, int32_t nbins,
+                              uint64_t *hist_dev /* device [S][S][W][nbins], += */);
 
 /*
  * Static structure factor by direct summation over reciprocal-lattice vectors.
