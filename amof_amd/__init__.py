@@ -13,6 +13,8 @@ Analyses beyond the reference:
     amof_amd.vanhove_distinct.DistinctVanHove     distinct Van Hove function G_d(r, t) on the same lags
     amof_amd.structure_factor.StructureFactor     static structure factor S(q) by direct summation over the
                                                   reciprocal lattice (density_modes: rho_a(k) of one frame)
+    amof_amd.intermediate_scattering.IntermediateScattering
+                                                  intermediate scattering function F(q, t), coherent and self
 
 All distance arithmetic runs in hand-written HIP kernels (gfx950) behind the C
 ABI of ``include/amof_hip.h``; there is no CPU fallback.

@@ -36,7 +36,7 @@ EXPORTS = [
     "amof_bad_hist_by_cn",
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
-    "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes",
+    "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
 ]
@@ -141,6 +141,10 @@ def load_library():
         lib.amof_sq_accumulate_dev.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                                ctypes.c_double, ctypes.c_int32, P, P, P, P]
         lib.amof_sq_modes.argtypes = [P, TP, ctypes.c_int64, P, ctypes.c_int32, P]
+        lib.amof_isf_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P]
+        lib.amof_isf_accumulate_dev.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P, P]
         lib.amof_xyz_scan.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
         lib.amof_xyz_read.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                       P, P, P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
@@ -158,6 +162,15 @@ def load_library():
             raise RuntimeError("libamofhip.so ABI version %d, expected %d" % (lib.amof_abi_version(), ABI_VERSION))
         _lib = lib
         return lib
+
+
+def isf_layout(S, W, nbins, self_part=True):
+    """word offsets of the one int64 tensor ``Context.isf_accumulate(out=...)`` adds into: ``counts [W][nbins]``, ``beyond
+    [W]``, ``coh [S][S][W][nbins]``, ``self [S][W][nbins]`` (absent without ``self_part``), and its ``size``"""
+    n = W * nbins
+    lay = {"counts": 0, "beyond": n, "coh": n + W, "self": n + W + S * S * n}
+    lay["size"] = lay["self"] + (S * n if self_part else 0)
+    return lay
 
 
 def reciprocal(cell):
@@ -722,6 +735,58 @@ class Context(Lane):
         self._check(self._lib.amof_sq_accumulate(*(args + (ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(sums.ctypes.data),
                                                            ctypes.c_void_p(beyond.ctypes.data)))))
         return counts, sums, int(beyond[0]), th.kinds
+
+    @_locked
+    def isf_accumulate(self, packed, hkl, windows, dq, nbins, origin_stride=1, work_range=None, self_part=True, recip=None,
+                       out=None):
+        """``(counts [W][nbins] u64, coh [S][S][W][nbins] f64, self [S][W][nbins] f64 or None, beyond [W] u64, kinds)`` of
+        ``amof_isf_accumulate``: the vectors ``hkl`` (int ``[K][3]``) correlated over the entries ``work_range`` (default:
+        all) of the lag-major (lag, origin) work list (amof_amd.vanhove_distinct.work_list); ``coh[a][c]``: species a at the
+        origin, c at the origin + lag.  ``recip``: ``[n_cells][3][3]`` (default ``reciprocal(packed.cell)``).
+
+        ``out``: optional torch CUDA int64 tensor of ``isf_layout(S, W, nbins, self_part)["size"]`` words (counts, beyond,
+        fixed-point coh, fixed-point self) the results are ADDED into on the device; returns ``(out, scale_log2, kinds)``
+        then, with coh[a][c] = ``coh * 2**-scale_log2[p]``, p the unordered pair of ``sq_accumulate``'s order."""
+        th = self._traj(packed)
+        hkl = np.ascontiguousarray(hkl, dtype=np.int32).reshape(-1, 3)
+        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        recip = np.ascontiguousarray(reciprocal(packed.cell) if recip is None else recip, dtype=np.float64)
+        assert recip.shape == (packed.cell.shape[0], 3, 3)
+        S, W, nbins = th.S, len(windows), int(nbins)
+        if work_range is None:
+            m = windows.astype(np.int64)
+            F, s = th.n_frames, max(1, int(origin_stride))
+            work_range = (0, int(np.where(F - m - 2 >= 0, (F - m - 2) // s + 1, 0).sum()))
+        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(recip.ctypes.data), ctypes.c_void_p(hkl.ctypes.data), len(hkl),
+                ctypes.c_void_p(windows.ctypes.data), W, int(origin_stride), int(work_range[0]), int(work_range[1]), float(dq),
+                nbins)
+        if out is not None:
+            lay = isf_layout(S, W, nbins, self_part)
+            assert out.is_cuda and out.is_contiguous() and out.numel() == lay["size"] and out.element_size() == 8
+            assert out.device.index == self.device
+            scale = np.zeros(S * (S + 1) // 2, dtype=np.int32)
+            base = out.data_ptr()
+            self._order_after_torch()
+            self._check(self._lib.amof_isf_accumulate_dev(*(args + (
+                ctypes.c_void_p(base + 8 * lay["counts"]), ctypes.c_void_p(base + 8 * lay["coh"]),
+                ctypes.c_void_p(base + 8 * lay["self"]) if self_part else None, ctypes.c_void_p(base + 8 * lay["beyond"]),
+                ctypes.c_void_p(scale.ctypes.data)))))
+            return out, scale, th.kinds
+        counts = np.zeros((W, nbins), dtype=np.uint64)
+        coh = np.zeros((S, S, W, nbins), dtype=np.float64)
+        selfs = np.zeros((S, W, nbins), dtype=np.float64) if self_part else None
+        beyond = np.zeros(W, dtype=np.uint64)
+        self._check(self._lib.amof_isf_accumulate(*(args + (
+            ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(coh.ctypes.data),
+            ctypes.c_void_p(selfs.ctypes.data) if self_part else None, ctypes.c_void_p(beyond.ctypes.data)))))
+        return counts, coh, selfs, beyond, th.kinds
+
+    def last_stage_seconds(self):
+        """``{"rho", "corr", "self"}``: kernel seconds of the stages of the last ``isf_accumulate`` (amof_last_kernel_seconds
+        2 .. 4; negative: the last call was not one)"""
+        self.drain()
+        with self._lock:
+            return {name: self._lib.amof_last_kernel_seconds(self._h, 2 + i) for i, name in enumerate(("rho", "corr", "self"))}
 
     @_locked
     def sq_modes(self, packed, hkl, frame=0):

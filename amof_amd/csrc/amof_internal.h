@@ -80,6 +80,8 @@ struct amof_ctx {
     int64_t progress = 0;         // 2 calls + (the call's dominant kernel is queued): read by OTHER threads (amof_ctx_follow), atomically
     int64_t shard_ticket = 0;     // `calls` right after a begin; 0 = none pending
     int64_t shard_key[7] = {0, 0, 0, 0, 0, 0, 0};
+    // kernel seconds of the stages of the last amof_isf_accumulate[_dev]: rho table (with the quantisation), correlation, self
+    double stage_seconds[3] = {-1.0, -1.0, -1.0};
 };
 
 namespace amof {

@@ -160,6 +160,7 @@ void timing_begin(amof_ctx *ctx)
 {
     ctx->ev_valid = false;
     ctx->dom_launches = 0;
+    for (double &x : ctx->stage_seconds) x = -1.0;
     ctx->calls++;
     __atomic_store_n(&ctx->progress, 2 * ctx->calls, __ATOMIC_RELEASE);
     (void)hipEventRecord(ctx->ev_all0, ctx->stream);
@@ -503,6 +504,7 @@ int amof_ctx_synchronize(amof_ctx *ctx)
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which)
 {
     if (!ctx || !ctx->ev_valid) return -1.0;
+    if (which >= 2 && which <= 4) return ctx->stage_seconds[which - 2];
     float ms = 0.f;
     hipEvent_t a = which == 1 ? ctx->ev_dom0 : ctx->ev_all0;
     hipEvent_t b = which == 1 ? ctx->ev_dom1 : ctx->ev_all1;

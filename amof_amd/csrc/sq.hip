@@ -20,6 +20,8 @@
 // memory (sq_bin_global) when (P + 1) nbins counters do not fit the LDS budget, or on request (AMOF_SQ_GLOBAL=1).  Integer
 // sums are independent of the order of the atomics, of the batching and of how frames are split across ranks.
 #include <math.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <numeric>
@@ -65,8 +67,9 @@ __global__ __launch_bounds__(SQ_THREADS) void sq_rho_kernel(const uint4 *__restr
                                                             double *__restrict__ rho)
 {
     const int ri = blockIdx.x * SQ_THREADS + threadIdx.x;
+    if (blockIdx.x * SQ_THREADS + (int)(threadIdx.x & ~63u) >= n_runs) return;     // a wave without a live lane (no barrier below)
     const bool live = ri < n_runs;
-    const SqRun run = runs[live ? ri : n_runs - 1];     // (idle lanes compute a copy of the last run and write nothing)
+    const SqRun run = runs[live ? ri : n_runs - 1];     // (idle lanes of a live wave compute a copy of the last run and write nothing)
     const uint4 *__restrict__ q = Q + (size_t)blockIdx.y * N;
     double *__restrict__ out = rho + (size_t)blockIdx.y * K * S * 2;
     const uint32_t h = (uint32_t)run.h, k = (uint32_t)run.k, l0 = (uint32_t)run.l0;
@@ -205,6 +208,40 @@ int64_t sq_bin_capacity(const double *recip, int64_t n_cells, const int32_t *hkl
     return best;
 }
 
+// Per-pair fixed-point scale 2^s: the sum over the trajectory's frames (ANY selection of them) of |t_ab| + 1/2 in one bin
+// stays below 2^62 -- |t_ab| <= N_a N_b, and a bin receives at most F * sq_bin_capacity samples.  The scale depends on
+// the trajectory's frame count and cells, the vectors, the bins and the species counts only: frame ranges of one
+// trajectory add up exactly (and F(q, t) -- at most F samples of a vector per lag -- shares S(q)'s scale).
+int sq_scales(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K, double dq, int32_t nbins,
+              std::vector<int32_t> &sexp, std::vector<double> &scale)
+{
+    const int S = t->n_species, P = S * (S + 1) / 2;
+    const int64_t N = t->n_atoms, F = t->n_frames;
+    std::vector<int64_t> nsp(S, 0);
+    for (int64_t i = 0; i < N; i++) nsp[t->species[i]]++;
+    const int64_t cap = sq_bin_capacity(recip, t->n_cells, hkl, K, dq, nbins);
+    sexp.assign(P, 0);
+    scale.assign(P, 0.0);
+    int p = 0;
+    for (int a = 0; a < S; a++)
+        for (int c = a; c < S; c++, p++) {
+            const double bound = (double)std::max<int64_t>(F, 1) * (double)std::max<int64_t>(cap, 1) *
+                                 ((double)std::max<int64_t>(nsp[a], 1) * (double)std::max<int64_t>(nsp[c], 1) + 0.5);
+            int e;
+            frexp(bound, &e);               // bound < 2^e
+            sexp[p] = std::min(62 - e, 60);
+            scale[p] = ldexp(1.0, sexp[p]);
+            // the quantum 2^-s in S units (divided by sqrt(N_a N_b)) must not exceed 2^-20
+            const double nab = sqrt((double)std::max<int64_t>(nsp[a], 1) * (double)std::max<int64_t>(nsp[c], 1));
+            if (ldexp(1.0, -sexp[p]) / nab > ldexp(1.0, -20))
+                return fail(ctx, AMOF_ECAPACITY, "S(q): %lld frames x %lld vectors per bin x %lld x %lld atoms exceed the "
+                                                 "fixed-point range (quantum above 2^-20): use fewer frames per call, a "
+                                                 "smaller dq or fewer vectors per bin (max_points)",
+                            (long long)F, (long long)cap, (long long)nsp[a], (long long)nsp[c]);
+        }
+    return AMOF_OK;
+}
+
 struct SqPlan {
     std::vector<int32_t> perm;          // atoms in species order (stable)
     std::vector<int64_t> sp_first;      // [S + 1]
@@ -292,34 +329,9 @@ int sq_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t
     for (int64_t c = 0; c < 9 * t->n_cells; c++)
         if (!isfinite(recip[c])) return fail(ctx, AMOF_EINVAL, "recip is not finite");
     if ((size_t)(P + 1) * (size_t)nbins > ((size_t)1 << 36)) return fail(ctx, AMOF_EINVAL, "histogram too large");
-    // per-pair fixed-point scale 2^s: the sum over the trajectory's frames (ANY selection of them) of |t_ab| + 1/2 in one bin
-    // stays below 2^62 -- |t_ab| <= N_a N_b, and a bin receives at most F * sq_bin_capacity samples.  The scale depends on
-    // the trajectory's frame count and cells, the vectors, the bins and the species counts only: frame ranges of one
-    // trajectory add up exactly.
-    std::vector<int64_t> nsp(S, 0);
-    for (int64_t i = 0; i < N; i++) nsp[t->species[i]]++;
-    const int64_t cap = sq_bin_capacity(recip, t->n_cells, hkl, K, dq, nbins);
-    std::vector<int32_t> sexp(P);
-    std::vector<double> scale(P);
-    {
-        int p = 0;
-        for (int a = 0; a < S; a++)
-            for (int c = a; c < S; c++, p++) {
-                const double bound = (double)std::max<int64_t>(F, 1) * (double)std::max<int64_t>(cap, 1) *
-                                     ((double)std::max<int64_t>(nsp[a], 1) * (double)std::max<int64_t>(nsp[c], 1) + 0.5);
-                int e;
-                frexp(bound, &e);               // bound < 2^e
-                sexp[p] = std::min(62 - e, 60);
-                scale[p] = ldexp(1.0, sexp[p]);
-                // the quantum 2^-s in S units (divided by sqrt(N_a N_b)) must not exceed 2^-20
-                const double nab = sqrt((double)std::max<int64_t>(nsp[a], 1) * (double)std::max<int64_t>(nsp[c], 1));
-                if (ldexp(1.0, -sexp[p]) / nab > ldexp(1.0, -20))
-                    return fail(ctx, AMOF_ECAPACITY, "S(q): %lld frames x %lld vectors per bin x %lld x %lld atoms exceed the "
-                                                     "fixed-point range (quantum above 2^-20): use fewer frames per call, a "
-                                                     "smaller dq or fewer vectors per bin (max_points)",
-                                (long long)F, (long long)cap, (long long)nsp[a], (long long)nsp[c]);
-            }
-    }
+    std::vector<int32_t> sexp;
+    std::vector<double> scale;
+    AMOF_TRY(sq_scales(ctx, t, recip, hkl, K, dq, nbins, sexp, scale));
     if (scale_log2) std::copy(sexp.begin(), sexp.end(), scale_log2);
     if (counts) {
         std::fill(counts, counts + nbins, (uint64_t)0);
@@ -409,6 +421,580 @@ int sq_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t
     return AMOF_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ F(q, t) --
+// Intermediate scattering function: the time correlation of the rho table (amof_isf_accumulate[_dev]).
+//
+// Data path, per call:
+//   pos --sq_quantize_kernel--> Q[slots][N]: every frame the work range touches, quantised ONCE
+//   per chunk of K_c vectors (whole runs of the sorted list; the table [slots][K_c][S][2] f64 stays inside the budget):
+//     Q --sq_rho_kernel--> rho[slot][v][s][2]                    (the kernel and atom order of amof_sq_modes: same bits)
+//     rho --isf_corr_kernel--> counts[W][nbins], coh[S][S][W][nbins] (int64 fixed point, S(q)'s scales), beyond[W]
+//   self part, per batch of (lag, origin) entries:
+//     Q --isf_diff_kernel--> D[e][N] = Q[k + m] - Q[k] (u32 wrap-around: the exact phase of the displacement)
+//     D --sq_rho_kernel--> rho_d[e][K][S][2];  Re rho_d --isf_self_bin_kernel--> self[S][W][nbins]
+//
+// isf_corr_kernel: a lane owns a vector of the chunk (consecutive lanes: consecutive 16 S-byte records of one frame's row),
+// a workgroup a range of origin indices.  Origins are taken ISF_TILE at a time: their rows rho(k) and their bins are loaded
+// into registers once and serve every lag of the pass; per lag the S^2 products of the tile's origins are rounded to int64
+// and summed in registers while the bin stays the same (always, for a constant cell), then added with one atomic per
+// (lane, lag, pair) and tile -- into per-lag LDS counter tiles ((1 + S^2) nbins u64 each; as many lags per pass as fit
+// ISF_LDS_BUDGET, flushed to global memory after each pass) or straight into global memory ("isf_global").  S > ISF_SMAX
+// takes a generic form of the same kernel (one atomic per sample, rows re-read through the caches).
+constexpr int ISF_THREADS = 256;
+constexpr int ISF_TILE = 4;                 // origins whose rows a lane holds in registers
+constexpr int ISF_SMAX = 4;                 // species counts with a register form
+constexpr int ISF_OPW = 64;                 // at most this many origins per workgroup
+constexpr size_t ISF_LDS_BUDGET = 64 * 1024;
+// rho table of one vector chunk: 1 GiB, twice S(q)'s batch.  The table is streamed (1 + W) times whatever its size, but a
+// thread of sq_rho_kernel owns a run of up to 16 vectors and a chunk is cut to whole waves of runs: on the headline shape
+// (5000 frames, 4 species: 320 KB per vector) 512 MB hold ~126 runs -- one whole wave, 13 launches with a tail each, the
+// table 14 % slower than S(q)'s -- where 1 GiB holds three.  Next to Q (16 N bytes per frame) a rank's scratch stays near
+// 2 GB there.  AMOF_ISF_RHO_BUDGET (bytes) overrides it (tests: several chunks on a small case).
+constexpr size_t ISF_RHO_BUDGET = (size_t)1 << 30;
+
+struct IsfEntry {
+    int32_t w, k;           // lag index, origin frame
+    int32_t sk, skm;        // slots of frames k and k + m in Q
+};
+
+struct IsfArgs {
+    const double *rho;          // [slots][Kc][S][2]
+    const int32_t *slot_of;     // [F]: slot of a frame in Q / rho (-1: not touched)
+    const int32_t *vec;         // [Kc]: the caller's index of the chunk's vectors
+    const int32_t *hkl;         // [K][3]
+    const double *recip;        // [n_cells][9]
+    const double *scale2;       // [S][S]: 2^s of the unordered pair {a, c}
+    const int32_t *windows;     // [W]
+    const int2 *lagiv;          // [W]: origin indices [x, y) of lag w in this call's work range
+    unsigned long long *counts, *coh, *beyond;
+    int64_t n_cells, stride;
+    int32_t Kc, S, W, nbins, omin, omax, opw, lags_per_pass;
+    double dq;
+};
+
+// the bin of amof_sq_accumulate (f64, no fma), -1 = beyond
+__device__ __forceinline__ int isf_bin(const double *__restrict__ R, const int32_t *__restrict__ v, double dq, int nbins)
+{
+    const double h = (double)v[0], k = (double)v[1], l = (double)v[2];
+    const double qx = (h * R[0] + k * R[3]) + l * R[6];
+    const double qy = (h * R[1] + k * R[4]) + l * R[7];
+    const double qz = (h * R[2] + k * R[5]) + l * R[8];
+    const double qq = sqrt((qx * qx + qy * qy) + qz * qz) / dq;
+    if (!(qq < (double)nbins)) return -1;
+    return (int)qq;
+}
+
+template <int ST, bool GLOBAL>
+__global__ __launch_bounds__(ISF_THREADS) void isf_corr_kernel(IsfArgs a)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    unsigned long long *lc = reinterpret_cast<unsigned long long *>(lds_raw);
+    const int tid = threadIdx.x;
+    const int S = ST ? ST : a.S;
+    constexpr int SR = ST ? ST : 1;
+    const int W = a.W, nbins = a.nbins, Kc = a.Kc;
+    const int v = blockIdx.x * ISF_THREADS + tid;
+    const bool live = v < Kc;
+    const int ob = a.omin + (int)blockIdx.y * a.opw, oe = min(ob + a.opw, a.omax);
+    const int tile = (1 + S * S) * nbins;
+    const int L = GLOBAL ? W : a.lags_per_pass;
+    const size_t row = (size_t)S * 2;
+    const int32_t *hv = a.hkl + 3 * (size_t)a.vec[live ? v : 0];
+
+    for (int w0 = 0; w0 < W; w0 += L) {
+        const int w1 = min(w0 + L, W);
+        if (!GLOBAL) {
+            for (int i = tid; i < (w1 - w0) * tile; i += ISF_THREADS) lc[i] = 0ull;
+            __syncthreads();
+        }
+        if (live) {
+            for (int os = ob; os < oe; os += ISF_TILE) {
+                // the tile's origin rows and bins: loaded once, used by every lag of the pass
+                int bins[ISF_TILE];
+                const double *orow[ISF_TILE];
+                double ore[ISF_TILE][SR], oim[ISF_TILE][SR];
+#pragma unroll
+                for (int t = 0; t < ISF_TILE; t++) {
+                    bins[t] = -1;
+                    orow[t] = a.rho;
+                    if (os + t < oe) {
+                        const int64_t k = 1 + a.stride * (int64_t)(os + t);
+                        bins[t] = isf_bin(a.recip + (a.n_cells == 1 ? 0 : (size_t)k * 9), hv, a.dq, nbins);
+                        orow[t] = a.rho + ((size_t)a.slot_of[k] * Kc + v) * row;
+                        if (ST) {
+#pragma unroll
+                            for (int s = 0; s < SR; s++) { ore[t][s] = orow[t][2 * s]; oim[t][s] = orow[t][2 * s + 1]; }
+                        }
+                    }
+                }
+                for (int w = w0; w < w1; w++) {
+                    const int2 iv = a.lagiv[w];
+                    const int lo = max(os, iv.x), hi = min(min(os + ISF_TILE, oe), iv.y);
+                    if (lo >= hi) continue;
+                    const int64_t m = a.windows[w];
+                    unsigned long long *cw = GLOBAL ? a.counts + (size_t)w * nbins : lc + (size_t)(w - w0) * tile;
+                    // coh of (a, c): cg + (a S + c) cstep
+                    unsigned long long *cg = GLOBAL ? a.coh + (size_t)w * nbins : cw + nbins;
+                    const size_t cstep = GLOBAL ? (size_t)W * nbins : (size_t)nbins;
+                    unsigned long long nbey = 0;
+                    if (ST) {
+                        unsigned long long acc[SR * SR], cnt = 0;
+                        int cur = -1;
+#pragma unroll
+                        for (int i = 0; i < SR * SR; i++) acc[i] = 0ull;
+                        auto flush = [&]() {
+                            if (!cnt) return;
+                            atomicAdd(&cw[cur], cnt);
+#pragma unroll
+                            for (int i = 0; i < SR * SR; i++) {
+                                if (acc[i]) atomicAdd(&cg[(size_t)i * cstep + cur], acc[i]);
+                                acc[i] = 0ull;
+                            }
+                            cnt = 0;
+                        };
+#pragma unroll
+                        for (int t = 0; t < ISF_TILE; t++) {
+                            const int o = os + t;
+                            if (o < lo || o >= hi) continue;
+                            if (bins[t] < 0) { nbey++; continue; }
+                            if (bins[t] != cur) { flush(); cur = bins[t]; }
+                            const int64_t km = 1 + a.stride * (int64_t)o + m;
+                            const double *__restrict__ pr = a.rho + ((size_t)a.slot_of[km] * Kc + v) * row;
+                            double pre[SR], pim[SR];
+#pragma unroll
+                            for (int s = 0; s < SR; s++) { pre[s] = pr[2 * s]; pim[s] = pr[2 * s + 1]; }
+                            cnt++;
+#pragma unroll
+                            for (int x = 0; x < SR; x++)
+#pragma unroll
+                                for (int c = 0; c < SR; c++) {
+                                    const double tt = ore[t][x] * pre[c] + oim[t][x] * pim[c];
+                                    acc[x * SR + c] += (unsigned long long)(long long)rint(tt * a.scale2[x * SR + c]);
+                                }
+                        }
+                        flush();
+                    } else {
+#pragma unroll
+                        for (int t = 0; t < ISF_TILE; t++) {
+                            const int o = os + t;
+                            if (o < lo || o >= hi) continue;
+                            const int bin = bins[t];
+                            if (bin < 0) { nbey++; continue; }
+                            const int64_t km = 1 + a.stride * (int64_t)o + m;
+                            const double *__restrict__ po = orow[t];
+                            const double *__restrict__ pr = a.rho + ((size_t)a.slot_of[km] * Kc + v) * row;
+                            atomicAdd(&cw[bin], 1ull);
+                            for (int x = 0; x < S; x++) {
+                                const double ra = po[2 * x], ia = po[2 * x + 1];
+                                for (int c = 0; c < S; c++) {
+                                    const double tt = ra * pr[2 * c] + ia * pr[2 * c + 1];
+                                    atomicAdd(&cg[(size_t)(x * S + c) * cstep + bin],
+                                              (unsigned long long)(long long)rint(tt * a.scale2[x * S + c]));
+                                }
+                            }
+                        }
+                    }
+                    if (nbey) atomicAdd(&a.beyond[w], nbey);
+                }
+            }
+        }
+        if (!GLOBAL) {
+            __syncthreads();
+            for (int i = tid; i < (w1 - w0) * tile; i += ISF_THREADS) {
+                const unsigned long long val = lc[i];
+                if (!val) continue;
+                const int w = w0 + i / tile, r = i % tile, j = r / nbins, b = r % nbins;
+                atomicAdd(j == 0 ? &a.counts[(size_t)w * nbins + b] : &a.coh[((size_t)(j - 1) * W + w) * nbins + b], val);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// D[e][i] = Q[slot of k + m][i] - Q[slot of k][i], component by component in u32 wrap-around arithmetic
+__global__ __launch_bounds__(256) void isf_diff_kernel(const uint4 *__restrict__ Q, int64_t N, const IsfEntry *__restrict__ ent,
+                                                       uint4 *__restrict__ D)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const IsfEntry e = ent[blockIdx.y];
+    const uint4 q0 = Q[(size_t)e.sk * N + i], q1 = Q[(size_t)e.skm * N + i];
+    D[(size_t)blockIdx.y * N + i] = make_uint4(q1.x - q0.x, q1.y - q0.y, q1.z - q0.z, 0u);
+}
+
+// self[a][w][bin] += rint(Re rho_d_a 2^s_aa): one (entry, vector) sample per thread, bin from the origin frame
+__global__ __launch_bounds__(SQ_THREADS) void isf_self_bin_kernel(const double *__restrict__ rho, int nb, int K, int S, int W,
+                                                                  const IsfEntry *__restrict__ ent, const int32_t *__restrict__ hkl,
+                                                                  const double *__restrict__ recip, int64_t n_cells, double dq,
+                                                                  int nbins, const double *__restrict__ scale2,
+                                                                  unsigned long long *__restrict__ selfs)
+{
+    const int64_t total = (int64_t)nb * K;
+    for (int64_t it = (int64_t)blockIdx.x * SQ_THREADS + threadIdx.x; it < total; it += (int64_t)gridDim.x * SQ_THREADS) {
+        const int b = (int)(it / K), m = (int)(it % K);
+        const IsfEntry e = ent[b];
+        const int bin = isf_bin(recip + (n_cells == 1 ? 0 : (size_t)e.k * 9), hkl + 3 * (size_t)m, dq, nbins);
+        if (bin < 0) continue;      // (counted in beyond by the coherent part)
+        const double *r = rho + (size_t)it * S * 2;
+        for (int s = 0; s < S; s++)
+            atomicAdd(&selfs[((size_t)s * W + e.w) * nbins + bin],
+                      (unsigned long long)(long long)rint(r[2 * s] * scale2[s * S + s]));
+    }
+}
+
+__global__ void isf_add_kernel(unsigned long long *dst, const unsigned long long *src, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] += src[i];
+}
+
+// a pair of events around a stage; seconds() after the stream has been synchronised
+struct IsfSpan {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int stage = 0;
+};
+
+struct IsfSpans {
+    amof_ctx *ctx;
+    std::vector<IsfSpan> spans;
+    explicit IsfSpans(amof_ctx *c) : ctx(c) {}
+    ~IsfSpans()
+    {
+        for (IsfSpan &s : spans) {
+            if (s.e0) (void)hipEventDestroy(s.e0);
+            if (s.e1) (void)hipEventDestroy(s.e1);
+        }
+    }
+    void begin(int stage)
+    {
+        IsfSpan s;
+        s.stage = stage;
+        if (hipEventCreate(&s.e0) != hipSuccess || hipEventCreate(&s.e1) != hipSuccess) {
+            spans.push_back(s);
+            return;
+        }
+        (void)hipEventRecord(s.e0, ctx->stream);
+        spans.push_back(s);
+    }
+    void end()
+    {
+        if (!spans.empty() && spans.back().e1) (void)hipEventRecord(spans.back().e1, ctx->stream);
+    }
+    void collect()      // (stream synchronised)
+    {
+        for (int i = 0; i < 3; i++) ctx->stage_seconds[i] = 0.0;
+        for (IsfSpan &s : spans) {
+            float ms = 0.f;
+            if (s.e0 && s.e1 && hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess) ctx->stage_seconds[s.stage] += (double)ms * 1e-3;
+        }
+    }
+};
+
+template <bool GLOBAL>
+hipError_t isf_launch_corr(amof_ctx *ctx, const IsfArgs &a, dim3 grid, size_t lds)
+{
+    auto go = [&](auto kern) -> hipError_t {
+        if (!GLOBAL) {
+            hipError_t e = allow_max_lds((const void *)kern);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(kern, grid, dim3(ISF_THREADS), GLOBAL ? 0 : lds, ctx->stream, a);
+        return hipGetLastError();
+    };
+    switch (a.S <= ISF_SMAX ? a.S : 0) {
+    case 1: return go(isf_corr_kernel<1, GLOBAL>);
+    case 2: return go(isf_corr_kernel<2, GLOBAL>);
+    case 3: return go(isf_corr_kernel<3, GLOBAL>);
+    case 4: return go(isf_corr_kernel<4, GLOBAL>);
+    default: return go(isf_corr_kernel<0, GLOBAL>);
+    }
+}
+
+// host outputs (counts, coh, selfs: f64, beyond -- overwritten) or device outputs (int64 fixed point / u64, added into;
+// scale_log2 receives the pairs' exponents).  want_self: the self part is computed (selfs / self_dev given)
+int isf_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K, const int32_t *windows,
+            int32_t W, int64_t stride, int64_t wb, int64_t we, double dq, int32_t nbins, bool want_self, uint64_t *counts,
+            double *coh, double *selfs, uint64_t *beyond, uint64_t *counts_dev, int64_t *coh_dev, int64_t *self_dev,
+            uint64_t *beyond_dev, int32_t *scale_log2)
+{
+    AMOF_TRY(sq_check_traj(ctx, t, hkl, K));
+    const int S = t->n_species, P = S * (S + 1) / 2;
+    const int64_t N = t->n_atoms, F = t->n_frames;
+    if (!recip && t->n_cells > 0) return fail(ctx, AMOF_EINVAL, "NULL recip");
+    if (W < 0 || (W > 0 && !windows)) return fail(ctx, AMOF_EINVAL, "NULL argument");
+    if (stride < 1) return fail(ctx, AMOF_EINVAL, "origin_stride must be >= 1");
+    if (!(dq > 0.0) || !isfinite(dq)) return fail(ctx, AMOF_EINVAL, "dq must be positive and finite");
+    if (nbins < 1) return fail(ctx, AMOF_EINVAL, "nbins must be >= 1");
+    if (F > 0x7fffffffLL || N > 0x7fffffffLL) return fail(ctx, AMOF_EINVAL, "too many frames or atoms");
+    for (int w = 0; w < W; w++)
+        if (windows[w] < 0 || windows[w] >= std::max<int64_t>(F, 1)) return fail(ctx, AMOF_EINVAL, "window %d out of range", windows[w]);
+    for (int64_t c = 0; c < 9 * t->n_cells; c++)
+        if (!isfinite(recip[c])) return fail(ctx, AMOF_EINVAL, "recip is not finite");
+    // this call's origin indices [o0, o1) of every lag (the lag-major work list of amof_vanhove_distinct)
+    std::vector<int2> lagiv(std::max(W, 1), make_int2(0, 0));
+    int64_t total = 0, n_entries = 0;
+    for (int w = 0; w < W; w++) {
+        const int64_t m = windows[w];
+        const int64_t n = F - m - 2 >= 0 ? (F - m - 2) / stride + 1 : 0;      // k = 1 + stride o <= F - m - 1
+        const int64_t o0 = std::max<int64_t>(wb - total, 0), o1 = std::min<int64_t>(we - total, n);
+        if (o0 < o1) {
+            lagiv[w] = make_int2((int)o0, (int)o1);
+            n_entries += o1 - o0;
+        }
+        total += n;
+    }
+    if (wb < 0 || we > total || wb > we) return fail(ctx, AMOF_EINVAL, "work range [%lld, %lld) outside [0, %lld)", (long long)wb,
+                                                     (long long)we, (long long)total);
+    const size_t n_cnt = (size_t)W * nbins, n_coh = (size_t)S * S * n_cnt, n_self = want_self ? (size_t)S * n_cnt : 0;
+    if (n_coh > ((size_t)1 << 36)) return fail(ctx, AMOF_EINVAL, "histogram too large");
+    std::vector<int32_t> sexp;
+    std::vector<double> scale;
+    AMOF_TRY(sq_scales(ctx, t, recip, hkl, K, dq, nbins, sexp, scale));
+    if (scale_log2) std::copy(sexp.begin(), sexp.end(), scale_log2);
+    std::vector<double> scale2((size_t)S * S);
+    std::vector<int32_t> sexp2((size_t)S * S);
+    {
+        int p = 0;
+        for (int a = 0; a < S; a++)
+            for (int c = a; c < S; c++, p++) {
+                scale2[a * S + c] = scale2[c * S + a] = scale[p];
+                sexp2[a * S + c] = sexp2[c * S + a] = sexp[p];
+            }
+    }
+    if (counts) {
+        std::fill(counts, counts + n_cnt, (uint64_t)0);
+        std::fill(coh, coh + n_coh, 0.0);
+        if (selfs) std::fill(selfs, selfs + n_self, 0.0);
+        std::fill(beyond, beyond + W, (uint64_t)0);
+    }
+    if (n_entries == 0 || K == 0) return AMOF_OK;
+
+    // the frames the range touches, ascending: slot s of Q and of the rho table holds frame fsel[s]
+    std::vector<int32_t> slot_of(F, -1), fsel;
+    int omin = 0x7fffffff, omax = 0;
+    for (int w = 0; w < W; w++) {
+        if (lagiv[w].x >= lagiv[w].y) continue;
+        omin = std::min(omin, lagiv[w].x);
+        omax = std::max(omax, lagiv[w].y);
+        for (int64_t o = lagiv[w].x; o < lagiv[w].y; o++) {
+            const int64_t k = 1 + stride * o;
+            slot_of[k] = 0;
+            slot_of[k + windows[w]] = 0;
+        }
+    }
+    for (int64_t f = 0; f < F; f++)
+        if (slot_of[f] == 0) {
+            slot_of[f] = (int32_t)fsel.size();
+            fsel.push_back((int32_t)f);
+        }
+    const size_t slots = fsel.size();
+
+    HostGeom hg;
+    AMOF_TRY(build_geometry(ctx, t, hg));
+    SqPlan pl;
+    AMOF_TRY(sq_plan(ctx, t, hkl, K, pl));
+    // vector chunks: whole runs of the sorted list, at most kc_max vectors (at least one run)
+    size_t budget = ISF_RHO_BUDGET;
+    if (const char *e = getenv("AMOF_ISF_RHO_BUDGET")) {
+        const long long b = atoll(e);
+        if (b > 0) budget = (size_t)b;
+    }
+    const size_t vec_bytes = slots * (size_t)S * 2 * sizeof(double);
+    const size_t kc_max = std::max<size_t>(1, budget / vec_bytes);
+    struct Chunk { int r0, r1, v0, nv; };
+    std::vector<Chunk> chunks;
+    std::vector<int32_t> order_local(K);
+    const int n_runs_all = (int)pl.runs.size();
+    for (int r0 = 0; r0 < n_runs_all;) {
+        int r1 = r0, nv = 0;
+        while (r1 < n_runs_all && (r1 == r0 || (size_t)(nv + pl.runs[r1].n) <= kc_max)) nv += pl.runs[r1++].n;
+        // a thread of sq_rho_kernel owns a run: whole waves of runs, so that a chunk leaves no lane of its last wave idle
+        if (r1 < n_runs_all && r1 - r0 > 64)
+            while ((r1 - r0) % 64) nv -= pl.runs[--r1].n;
+        chunks.push_back(Chunk{r0, r1, pl.runs[r0].start, nv});
+        for (int i = 0; i < nv; i++) order_local[pl.runs[r0].start + i] = i;
+        r0 = r1;
+    }
+    int kc_top = 0;
+    for (const Chunk &c : chunks) kc_top = std::max(kc_top, c.nv);
+
+    const size_t tile_ctr = (size_t)(1 + S * S) * nbins;
+    const bool global = tile_ctr * sizeof(uint64_t) > ISF_LDS_BUDGET || getenv("AMOF_ISF_GLOBAL");
+    const int lags_per_pass = global ? W : (int)std::min<size_t>(W, ISF_LDS_BUDGET / (tile_ctr * sizeof(uint64_t)));
+
+    std::vector<IsfEntry> entries;
+    if (want_self) {
+        entries.reserve(n_entries);
+        for (int w = 0; w < W; w++)
+            for (int64_t o = lagiv[w].x; o < lagiv[w].y; o++) {
+                const int64_t k = 1 + stride * o;
+                entries.push_back(IsfEntry{w, (int32_t)k, slot_of[k], slot_of[k + windows[w]]});
+            }
+    }
+
+    AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    timing_begin(ctx);
+    IsfSpans spans(ctx);
+    const double *pos_dev = nullptr;
+    AMOF_TRY(stage_positions(ctx, t, &pos_dev));
+    UploadPack pk;
+    const int i_geom = pk.add(hg.rec.data(), hg.rec.size() * sizeof(double));
+    const int i_perm = pk.add(pl.perm.data(), pl.perm.size() * sizeof(int32_t));
+    const int i_spf = pk.add(pl.sp_first.data(), pl.sp_first.size() * sizeof(int64_t));
+    const int i_runs = pk.add(pl.runs.data(), pl.runs.size() * sizeof(SqRun));
+    const int i_order = pk.add(pl.order.data(), pl.order.size() * sizeof(int32_t));
+    const int i_olocal = pk.add(order_local.data(), order_local.size() * sizeof(int32_t));
+    const int i_hkl = pk.add(hkl, (size_t)K * 3 * sizeof(int32_t));
+    const int i_recip = pk.add(recip, (size_t)t->n_cells * 9 * sizeof(double));
+    const int i_frames = pk.add(fsel.data(), fsel.size() * sizeof(int32_t));
+    const int i_slot = pk.add(slot_of.data(), slot_of.size() * sizeof(int32_t));
+    const int i_scale2 = pk.add(scale2.data(), scale2.size() * sizeof(double));
+    const int i_win = pk.add(windows, (size_t)W * sizeof(int32_t));
+    const int i_iv = pk.add(lagiv.data(), lagiv.size() * sizeof(int2));
+    const int i_ent = pk.add(entries.data(), entries.size() * sizeof(IsfEntry));
+    AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
+    void *d_Q = nullptr, *d_rho = nullptr, *d_flag = nullptr, *d_ctr = nullptr;
+    AMOF_TRY(ensure(ctx, SLOT_AUX0, slots * (size_t)std::max<int64_t>(N, 1) * sizeof(uint4), &d_Q));
+    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)kc_top * vec_bytes, &d_rho));
+    AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), ctx->stream));
+    // the call's own counters, zeroed: [counts | coh | self | beyond]; the device form adds them into the caller's at the end
+    const size_t n_ctr = n_cnt + n_coh + n_self + (size_t)W;
+    AMOF_TRY(ensure(ctx, SLOT_OUT1, n_ctr * sizeof(uint64_t), &d_ctr));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, n_ctr * sizeof(uint64_t), ctx->stream));
+    unsigned long long *cnt = (unsigned long long *)d_ctr, *co = cnt + n_cnt, *se = co + n_coh, *bey = se + n_self;
+
+    // every touched frame is quantised once
+    spans.begin(0);
+    if (N > 0)
+        for (size_t s0 = 0; s0 < slots; s0 += 65535) {
+            const unsigned nb = (unsigned)std::min<size_t>(65535, slots - s0);
+            hipLaunchKernelGGL(sq_quantize_kernel, dim3((unsigned)((N + 255) / 256), nb), dim3(256), 0, ctx->stream, pos_dev,
+                               pk.ptr<double>(i_geom), t->n_cells, pk.ptr<int32_t>(i_perm), N, pk.ptr<int32_t>(i_frames) + s0,
+                               (uint4 *)d_Q + s0 * (size_t)N, (int32_t *)d_flag);
+            AMOF_HIP_TRY(ctx, hipGetLastError());
+        }
+    spans.end();
+
+    IsfArgs a;
+    memset(&a, 0, sizeof a);
+    a.rho = (const double *)d_rho;
+    a.slot_of = pk.ptr<int32_t>(i_slot);
+    a.hkl = pk.ptr<int32_t>(i_hkl);
+    a.recip = pk.ptr<double>(i_recip);
+    a.scale2 = pk.ptr<double>(i_scale2);
+    a.windows = pk.ptr<int32_t>(i_win);
+    a.lagiv = pk.ptr<int2>(i_iv);
+    a.counts = cnt;
+    a.coh = co;
+    a.beyond = bey;
+    a.n_cells = t->n_cells;
+    a.stride = stride;
+    a.S = S;
+    a.W = W;
+    a.nbins = nbins;
+    a.omin = omin;
+    a.omax = omax;
+    a.lags_per_pass = lags_per_pass;
+    a.dq = dq;
+    const size_t lds = (size_t)lags_per_pass * tile_ctr * sizeof(uint64_t);
+
+    timing_dom_begin(ctx, global ? "isf_global" : "isf");
+    int64_t launches = 0;
+    for (const Chunk &c : chunks) {
+        spans.begin(0);
+        const int n_runs = c.r1 - c.r0;
+        for (size_t s0 = 0; s0 < slots; s0 += 65535) {
+            const unsigned nb = (unsigned)std::min<size_t>(65535, slots - s0);
+            hipLaunchKernelGGL(sq_rho_kernel, dim3((unsigned)((n_runs + SQ_THREADS - 1) / SQ_THREADS), nb), dim3(SQ_THREADS), 0,
+                               ctx->stream, (const uint4 *)d_Q + s0 * (size_t)N, N, pk.ptr<int64_t>(i_spf), S,
+                               pk.ptr<SqRun>(i_runs) + c.r0, n_runs, pk.ptr<int32_t>(i_olocal), c.nv,
+                               (double *)d_rho + s0 * (size_t)c.nv * S * 2);
+            AMOF_HIP_TRY(ctx, hipGetLastError());
+            launches++;
+        }
+        spans.end();
+        spans.begin(1);
+        a.Kc = c.nv;
+        a.vec = pk.ptr<int32_t>(i_order) + c.v0;
+        const int vblocks = (c.nv + ISF_THREADS - 1) / ISF_THREADS;
+        const int64_t range = (int64_t)omax - omin;
+        // origins per workgroup: a multiple of the tile, enough workgroups to fill the GPU several times over
+        int64_t opw = std::min<int64_t>(ISF_OPW, std::max<int64_t>(ISF_TILE, range * vblocks / 2048 / ISF_TILE * ISF_TILE));
+        opw = std::max<int64_t>(opw, ((range + 65534) / 65535 + ISF_TILE - 1) / ISF_TILE * ISF_TILE);
+        a.opw = (int32_t)opw;
+        const dim3 grid((unsigned)vblocks, (unsigned)((range + opw - 1) / opw));
+        AMOF_HIP_TRY(ctx, global ? isf_launch_corr<true>(ctx, a, grid, 0) : isf_launch_corr<false>(ctx, a, grid, lds));
+        launches++;
+        spans.end();
+    }
+    timing_dom_end(ctx, launches);
+
+    if (want_self) {
+        // batches of entries inside the same budget: D (16 N bytes) and rho_d (16 K S bytes) per entry
+        const size_t ent_bytes = (size_t)std::max<int64_t>(N, 1) * sizeof(uint4) + (size_t)K * S * 2 * sizeof(double);
+        const size_t nb_max = std::max<size_t>(1, std::min<size_t>({budget / ent_bytes, entries.size(), (size_t)65535}));
+        void *d_D = nullptr, *d_rd = nullptr;
+        AMOF_TRY(ensure(ctx, SLOT_AUX2, nb_max * (size_t)std::max<int64_t>(N, 1) * sizeof(uint4), &d_D));
+        AMOF_TRY(ensure(ctx, SLOT_AUX3, nb_max * (size_t)K * S * 2 * sizeof(double), &d_rd));
+        const int n_runs = (int)pl.runs.size();
+        spans.begin(2);
+        for (size_t e0 = 0; e0 < entries.size(); e0 += nb_max) {
+            const int nb = (int)std::min<size_t>(nb_max, entries.size() - e0);
+            const IsfEntry *d_ent = pk.ptr<IsfEntry>(i_ent) + e0;
+            if (N > 0)
+                hipLaunchKernelGGL(isf_diff_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream,
+                                   (const uint4 *)d_Q, N, d_ent, (uint4 *)d_D);
+            AMOF_HIP_TRY(ctx, hipGetLastError());
+            hipLaunchKernelGGL(sq_rho_kernel, dim3((unsigned)((n_runs + SQ_THREADS - 1) / SQ_THREADS), (unsigned)nb), dim3(SQ_THREADS),
+                               0, ctx->stream, (const uint4 *)d_D, N, pk.ptr<int64_t>(i_spf), S, pk.ptr<SqRun>(i_runs), n_runs,
+                               pk.ptr<int32_t>(i_order), K, (double *)d_rd);
+            AMOF_HIP_TRY(ctx, hipGetLastError());
+            const int64_t samples = (int64_t)nb * K;
+            const unsigned blocks = (unsigned)std::min<int64_t>(SQ_BIN_BLOCKS, (samples + SQ_THREADS - 1) / SQ_THREADS);
+            hipLaunchKernelGGL(isf_self_bin_kernel, dim3(blocks), dim3(SQ_THREADS), 0, ctx->stream, (const double *)d_rd, nb, K, S, W,
+                               d_ent, pk.ptr<int32_t>(i_hkl), pk.ptr<double>(i_recip), t->n_cells, dq, (int)nbins,
+                               pk.ptr<double>(i_scale2), se);
+            AMOF_HIP_TRY(ctx, hipGetLastError());
+        }
+        spans.end();
+    }
+    int32_t flag = 0;
+    AMOF_TRY(fetch(ctx, &flag, d_flag, sizeof(int32_t)));
+    if (flag) {
+        timing_end(ctx);
+        return fail(ctx, AMOF_EINVAL, "positions lie more than 10^4 cells from the cell, or are not finite");
+    }
+    if (counts_dev) {
+        auto add = [&](void *dst, const unsigned long long *src, size_t n) -> hipError_t {
+            if (!n) return hipSuccess;
+            hipLaunchKernelGGL(isf_add_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
+                               (unsigned long long *)dst, src, n);
+            return hipGetLastError();
+        };
+        AMOF_HIP_TRY(ctx, add(counts_dev, cnt, n_cnt));
+        AMOF_HIP_TRY(ctx, add(coh_dev, co, n_coh));
+        if (want_self) AMOF_HIP_TRY(ctx, add(self_dev, se, n_self));
+        AMOF_HIP_TRY(ctx, add(beyond_dev, bey, (size_t)W));
+    }
+    timing_end(ctx);
+    if (counts) {
+        std::vector<int64_t> raw(n_coh + n_self);
+        AMOF_TRY(fetch(ctx, counts, cnt, n_cnt * sizeof(uint64_t)));
+        AMOF_TRY(fetch(ctx, raw.data(), co, raw.size() * sizeof(int64_t)));
+        AMOF_TRY(fetch(ctx, beyond, bey, (size_t)W * sizeof(uint64_t)));
+        for (int x = 0; x < S * S; x++)
+            for (size_t i = 0; i < n_cnt; i++) coh[(size_t)x * n_cnt + i] = ldexp((double)raw[(size_t)x * n_cnt + i], -sexp2[x]);
+        if (want_self)
+            for (int s = 0; s < S; s++)
+                for (size_t i = 0; i < n_cnt; i++)
+                    selfs[(size_t)s * n_cnt + i] = ldexp((double)raw[n_coh + (size_t)s * n_cnt + i], -sexp2[s * S + s]);
+    }
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
+    spans.collect();
+    (void)P;
+    return AMOF_OK;
+}
+
 }  // namespace
 }  // namespace amof
 
@@ -481,4 +1067,26 @@ extern "C" int amof_sq_modes(amof_ctx *ctx, const amof_traj *t, int64_t frame, c
     AMOF_TRY(fetch(ctx, rho, d_rho, (size_t)K * S * 2 * sizeof(double)));
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     return AMOF_OK;
+}
+
+extern "C" int amof_isf_accumulate(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K,
+                                   const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t work_begin,
+                                   int64_t work_end, double dq, int32_t nbins, uint64_t *counts, double *coh, double *self_sums,
+                                   uint64_t *beyond)
+{
+    if (!ctx) return AMOF_EINVAL;
+    if (!counts || !coh || !beyond) return fail(ctx, AMOF_EINVAL, "NULL argument");
+    return isf_run(ctx, t, recip, hkl, K, windows, n_windows, origin_stride, work_begin, work_end, dq, nbins, self_sums != nullptr,
+                   counts, coh, self_sums, beyond, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int amof_isf_accumulate_dev(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K,
+                                       const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t work_begin,
+                                       int64_t work_end, double dq, int32_t nbins, uint64_t *counts_dev, int64_t *coh_dev,
+                                       int64_t *self_dev, uint64_t *beyond_dev, int32_t *scale_log2)
+{
+    if (!ctx) return AMOF_EINVAL;
+    if (!counts_dev || !coh_dev || !beyond_dev || !scale_log2) return fail(ctx, AMOF_EINVAL, "NULL argument");
+    return isf_run(ctx, t, recip, hkl, K, windows, n_windows, origin_stride, work_begin, work_end, dq, nbins, self_dev != nullptr,
+                   nullptr, nullptr, nullptr, nullptr, counts_dev, coh_dev, self_dev, beyond_dev, scale_log2);
 }

@@ -121,7 +121,9 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
 
 /* Seconds spent inside kernels of the last call, measured with HIP events on
  * the context's stream around the dominant kernel's launches:
- * which = 0 total, 1 dominant kernel only. Returns < 0 if unavailable. */
+ * which = 0 total, 1 dominant kernel only.  After amof_isf_accumulate[_dev] also the sums over the call's launches of
+ * which = 2 the rho table (quantisation included), 3 the correlation kernel, 4 the self part (0 if not asked for).
+ * Returns < 0 if unavailable. */
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which);
 /* number of launches of the dominant kernel in the last call */
 int64_t amof_last_kernel_launches(const amof_ctx *ctx);
@@ -145,7 +147,9 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *   distinct Van Hove "rdf_distinct_tile" (constant diagonal cell, all axes periodic, one image in reach: quantised frames,
  *        guarded f32 candidates), "rdf_distinct_exact" (canonical float64 arithmetic per pair, any cell; also
  *        AMOF_VANHOVE_DISTINCT_EXACT=1), "rdf_distinct_exact_global" (the same with u64 counters in global memory: S nbins
- *        beyond AMOF_MAX_LDS_BINS, or AMOF_VANHOVE_DISTINCT_GLOBAL=1) */
+ *        beyond AMOF_MAX_LDS_BINS, or AMOF_VANHOVE_DISTINCT_GLOBAL=1)
+ *   F(q, t) "isf" (per-lag counter tiles in LDS), "isf_global" (u64 counters in global memory: (1 + S^2) nbins counters
+ *        beyond the LDS budget, or AMOF_ISF_GLOBAL=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -359,6 +363,53 @@ int amof_sq_accumulate_dev(amof_ctx *ctx, const amof_traj *traj, const double *r
  * written out instead of binned; any hkl but (0, 0, 0), no half-space rule).  Errors as amof_sq_accumulate. */
 int amof_sq_modes(amof_ctx *ctx, const amof_traj *traj, int64_t frame, const int32_t *hkl /* host [K][3] */, int32_t K,
                   double *rho /* host [K][S][2] */);
+
+/*
+ * Intermediate scattering function F(q, t): the time correlation of rho_a(k) on reciprocal-lattice vectors, coherent and self.
+ * Replaces nothing the reference computes (the reference has no dynamic analysis in reciprocal space).  Cells must be
+ * periodic on all three axes.  recip, hkl (half a space, no (0, 0, 0)), dq, nbins: as amof_sq_accumulate.
+ *   Work list: amof_vanhove_distinct's -- lags m = windows[w] (0 <= m < F), origins k = 1, 1 + s, ... <= F - m - 1
+ *   (s = origin_stride >= 1), every (w, k) in lag-major order, n_w = floor((F - m - 2) / s) + 1 entries for lag w (0 if
+ *   m > F - 2).  A call handles the entries [work_begin, work_end): ranges of one trajectory add up bit for bit.
+ *   rho_a(f; hkl) is what amof_sq_modes returns for frame f and that vector, bit for bit (the same kernel and atom order;
+ *   it does not depend on how the vectors are grouped into runs or chunks).
+ *   For every entry (w, k) and every vector: the bin b from frame k's (the ORIGIN's) reciprocal matrix in
+ *   amof_sq_accumulate's operation order (float64, no fma, b = (int)(q / dq)); !(q / dq < nbins): beyond[w] += 1 and
+ *   nothing else.  Otherwise counts[w][b] += 1 and
+ *     coherent, every ORDERED species pair (a at the origin, c at the origin + lag -- amof_vanhove_distinct's order):
+ *       t_ac = Re rho_a(k) * Re rho_c(k + m) + Im rho_a(k) * Im rho_c(k + m)   (float64, two products and one add, no fma)
+ *       coh[a][c][w][b] += rint(t_ac * 2^s_p) as int64 (integer atomics), p the unordered pair {a, c};
+ *     self, every species a (only when the self output is given):
+ *       u_a = sum over the atoms j of a of cos(2 pi phi_j / 2^32), phi_j = h dx + k dy + l dz (mod 2^32),
+ *       d = Q_j(k + m) - Q_j(k) in u32 wrap-around arithmetic on the quantised fractional coordinates: on reciprocal-LATTICE
+ *       vectors the phase of a displacement is periodic in the cell, so no unwrapping and no centre-of-mass convention
+ *       enters.  This is rho's real part on a "difference frame" (the same kernel: f32 partials over <= 64 atoms folded
+ *       into f64 in a fixed order);  self[a][w][b] += rint(u_a * 2^s_(a,a)).
+ *   s_p is amof_sq_accumulate's scale for the same trajectory, vectors, dq and nbins (a counter receives at most n_w C <=
+ *   F C samples, so that bound holds unchanged; it does not depend on windows, stride or work range), with the same
+ *   AMOF_ECAPACITY rule.  At lag 0, coh[a][c] == coh[c][a] == amof_sq_accumulate's sums[p] over the origin frames, and
+ *   self[a] = N_a counts up to the fixed-point quantum.  Integer sums: the result is independent of tiling, vector
+ *   chunking, launch order and rank split; two identical calls give identical bits.
+ *   The rho table of a chunk of vectors ([frames touched][K_c][S][2] float64) is kept within 1 GiB (AMOF_ISF_RHO_BUDGET,
+ *   bytes, overrides); every touched frame is quantised once per call (16 N bytes per frame of scratch).
+ *   No capacity limit on W, nbins, K, F or N other than the fixed-point rule.
+ * The host form overwrites counts, coh, self_sums (float64: int64 * 2^-s; self_sums == NULL: no self part) and beyond.
+ * Errors: as amof_sq_accumulate, plus AMOF_EINVAL for a bad window, origin_stride or work range.
+ */
+int amof_isf_accumulate(amof_ctx *ctx, const amof_traj *traj, const double *recip /* host [n_cells][3][3] */,
+                        const int32_t *hkl /* host [K][3] */, int32_t K, const int32_t *windows /* host [W] */,
+                        int32_t n_windows, int64_t origin_stride, int64_t work_begin, int64_t work_end, double dq, int32_t nbins,
+                        uint64_t *counts /* host [W][nbins] */, double *coh /* host [S][S][W][nbins] */,
+                        double *self_sums /* host [S][W][nbins] or NULL */, uint64_t *beyond /* host [W] */);
+/* The same with the results ADDED into device buffers (ranks that share the work list all-reduce them next): coh_dev and
+ * self_dev (NULL: no self part) hold the int64 fixed-point sums (value = sum * 2^-scale_log2[p], p = the unordered pair
+ * of amof_sq_accumulate's order; self of species a uses the pair (a, a)); scale_log2 (host [P]) receives the exponents. */
+int amof_isf_accumulate_dev(amof_ctx *ctx, const amof_traj *traj, const double *recip, const int32_t *hkl, int32_t K,
+                            const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t work_begin,
+                            int64_t work_end, double dq, int32_t nbins, uint64_t *counts_dev /* device [W][nbins], += */,
+                            int64_t *coh_dev /* device [S][S][W][nbins], += */,
+                            int64_t *self_dev /* device [S][W][nbins] or NULL, += */, uint64_t *beyond_dev /* device [W], += */,
+                            int32_t *scale_log2 /* host [P] */);
 
 /*
  * Direct MSD with running unwrap, orthogonal cells only (deprecated in the reference).
