@@ -15,6 +15,7 @@ Analyses beyond the reference:
                                                   reciprocal lattice (density_modes: rho_a(k) of one frame)
     amof_amd.intermediate_scattering.IntermediateScattering
                                                   intermediate scattering function F(q, t), coherent and self
+    amof_amd.bond_lifetime.BondLifetime           bond survival correlations C(t), S(t) for CoordinationNumber's sets
 
 All distance arithmetic runs in hand-written HIP kernels (gfx950) behind the C
 ABI of ``include/amof_hip.h``; there is no CPU fallback.

@@ -122,7 +122,8 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
 /* Seconds spent inside kernels of the last call, measured with HIP events on
  * the context's stream around the dominant kernel's launches:
  * which = 0 total, 1 dominant kernel only.  After amof_isf_accumulate[_dev] also the sums over the call's launches of
- * which = 2 the rho table (quantisation included), 3 the correlation kernel, 4 the self part (0 if not asked for).
+ * which = 2 the rho table (quantisation included), 3 the correlation kernel, 4 the self part (0 if not asked for);
+ * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations.
  * Returns < 0 if unavailable. */
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which);
 /* number of launches of the dominant kernel in the last call */
@@ -149,7 +150,10 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        AMOF_VANHOVE_DISTINCT_EXACT=1), "rdf_distinct_exact_global" (the same with u64 counters in global memory: S nbins
  *        beyond AMOF_MAX_LDS_BINS, or AMOF_VANHOVE_DISTINCT_GLOBAL=1)
  *   F(q, t) "isf" (per-lag counter tiles in LDS), "isf_global" (u64 counters in global memory: (1 + S^2) nbins counters
- *        beyond the LDS budget, or AMOF_ISF_GLOBAL=1) */
+ *        beyond the LDS budget, or AMOF_ISF_GLOBAL=1)
+ *   bond survival "bond_series" (constant diagonal cell, all axes periodic: f32 distance of the fixed-point differences,
+ *        the guard band re-decided exactly), "bond_series_exact" (canonical float64 arithmetic per pair and frame: general
+ *        and per-frame cells, open axes; also AMOF_BOND_EXACT=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -320,6 +324,39 @@ int amof_vanhove_distinct(amof_ctx *ctx, const amof_traj *traj, const int32_t *w
 int amof_vanhove_distinct_dev(amof_ctx *ctx, const amof_traj *traj, const int32_t *windows, int32_t n_windows,
                               int64_t origin_stride, int64_t work_begin, int64_t work_end, double rmax, int32_t nbins,
                               uint64_t *hist_dev /* device [S][S][W][nbins], += */);
+
+/*
+ * Bond survival correlations: does the SAME pair stay bonded?
+ * Replaces the per-frame neighbour-list loop a user writes around amof.atom.get_neighborlist (amof/atom.py:72-87; the
+ * search amof/cn.py:65 profiles at "92 % of computation time") to follow individual bonds through a trajectory; the
+ * reference itself has no dynamic neighbour analysis.
+ *   cutoff, sets: as amof_cn_count.  h_ij(f) = 1 iff atom j (species B) is a neighbour of atom i (species A), i != j, in
+ *   frame f -- amof_cn_count's decision for that frame, pair and cutoff: strict sqrt(d2) < rc on the canonical minimum
+ *   image in frame f's cell and pbc.  For h to be 0 or 1, a cutoff of a set above half the smallest
+ *   perpendicular cell height over all frames on a periodic axis is refused (AMOF_EINVAL).
+ *   Lags m = windows[w] (0 <= m < F), origins k = 1, 1 + s, ... <= F - m - 1 (s = origin_stride >= 1): amof_vanhove_distinct's.
+ *   Per set s and lag w, summed over the lag's origins k and the ordered pairs (i, j) with atom_begin <= i < atom_end:
+ *     counts[(s*W + w)*3 + 0] = sum h_ij(k)                              bonds present at the origins
+ *     counts[(s*W + w)*3 + 1] = sum h_ij(k) h_ij(k + m)                  intermittent: bonded at both ends
+ *     counts[(s*W + w)*3 + 2] = sum prod_{f = k .. k + m} h_ij(f)        continuous: bonded at EVERY frame from k to k + m
+ *   The host forms C(t) = [1] / [0] and S(t) = [2] / [0].  counts[(s*W + w)*3] of a lag m = 0 is amof_cn_count's sums[f][s]
+ *   added over the frames f = 1, 1 + s, ... <= F - 1.  Integer counters: ranges of centres add up bit for bit, and the
+ *   result does not depend on launch order or on how the library chunks pairs, centres and lags.
+ *   No capacity limit on the number of pairs, F, W or N: scratch is bounded -- a piece of centres (bitmap <= 256 MB), inside
+ *   it groups of centres of at most 2^25 pairs (pair table <= 256 MB; AMOF_BOND_PAIR_BUDGET, in pairs, overrides), a chunk of
+ *   pairs (series words <= 256 MB) and 2048 lags at a time.  amof_last_kernel_seconds: which = 2 the bond lists of the origin frames, 3 the bit series, 4 the
+ *   correlations; 1 spans the series launches.
+ * The host form overwrites counts.  Errors: AMOF_EINVAL (bad window, stride, atom range, set, cutoff, NULL argument),
+ * AMOF_ESINGULAR, AMOF_ENOMEM, AMOF_EHIP, AMOF_ENODEVICE.
+ */
+int amof_bond_survival(amof_ctx *ctx, const amof_traj *traj, const double *cutoff /* [S][S], as amof_cn_count */,
+                       const int32_t *sets /* [n_sets][2] */, int32_t n_sets, const int32_t *windows /* host [W] */,
+                       int32_t n_windows, int64_t origin_stride, int64_t atom_begin, int64_t atom_end,
+                       uint64_t *counts /* host [n_sets][W][3] */);
+/* The same with the counters ADDED into a device buffer (ranks that share the centres all-reduce it next). */
+int amof_bond_survival_dev(amof_ctx *ctx, const amof_traj *traj, const double *cutoff, const int32_t *sets, int32_t n_sets,
+                           const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t atom_begin,
+                           int64_t atom_end, uint64_t *counts_dev /* device [n_sets][W][3], += */);
 
 /*
  * Static structure factor by direct summation over reciprocal-lattice vectors.
