@@ -348,6 +348,12 @@ class Lane(object):
             self._lane = None
 
 
+def _whole_work_list(n_frames, windows, origin_stride):
+    """``work_range`` of every (lag, origin) pair (a stride below 1 is the library's to refuse)"""
+    from . import lags
+    return 0, lags.total_work(n_frames, windows, max(1, int(origin_stride)))
+
+
 class Context(Lane):
     """One ``amof_ctx``: a device, a stream and its scratch memory -- and, for the analysis classes, a LANE: one worker
     thread that runs the (synchronous) entry points of this context in submission order, so that a class constructor
@@ -475,6 +481,11 @@ class Context(Lane):
         points are synchronous like all others, so torch work queued afterwards needs no further ordering."""
         self.wait_stream(self._torch_stream())
 
+    def _check_out(self, tensor, numel):
+        """an ``out=`` / ``com=`` tensor: contiguous, on this context's GPU, ``numel`` 8-byte words"""
+        assert tensor.is_cuda and tensor.is_contiguous() and tensor.numel() == numel and tensor.element_size() == 8
+        assert tensor.device.index == self.device
+
     def _traj(self, packed, frame_range=None):
         """``_TrajHandle`` of a trajectory this context may read.  A device-resident ``pos`` must live on this
         context's GPU, and the context's (non-blocking) stream is ordered after torch's current stream on that
@@ -522,8 +533,7 @@ class Context(Lane):
         th = self._traj(packed, frame_range)
         vol = ctypes.c_double(0.0)
         if out is not None:
-            assert out.is_cuda and out.is_contiguous() and out.numel() == th.S * th.S * nbins
-            assert out.device.index == self.device and out.element_size() == 8
+            self._check_out(out, th.S * th.S * nbins)
             self._order_after_torch()
             rc = self._lib.amof_rdf_accumulate_dev(self._h, ctypes.byref(th.c), float(rmax), int(nbins),
                                                    ctypes.c_void_p(out.data_ptr()), ctypes.byref(vol))
@@ -559,8 +569,7 @@ class Context(Lane):
         if out is not None:
             hist_t, nang_t = out
             for x, n in ((hist_t, len(triples) * nb), (nang_t, len(triples))):
-                assert x.is_cuda and x.is_contiguous() and x.numel() == n and x.element_size() == 8
-                assert x.device.index == self.device
+                self._check_out(x, n)
             self._order_after_torch()
             rc = self._lib.amof_bad_hist_dev(self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data),
                                              ctypes.c_void_p(triples.ctypes.data), len(triples),
@@ -599,8 +608,7 @@ class Context(Lane):
         """centre of mass of frames ``[f0, f1)`` into rows ``f0 .. f1`` of ``out`` (torch CUDA f64 ``[F][3]``); the other
         rows are left alone (an atom-sharded run: every rank its frame share, then one sum of the zero-filled tables)."""
         th = self._traj(packed)
-        assert out.is_cuda and out.is_contiguous() and out.numel() == 3 * th.n_frames and out.element_size() == 8
-        assert out.device.index == self.device
+        self._check_out(out, 3 * th.n_frames)
         self._order_after_torch()
         self._check(self._lib.amof_msd_com_dev(self._h, ctypes.byref(th.c), int(frame_range[0]), int(frame_range[1]),
                                                ctypes.c_void_p(out.data_ptr())))
@@ -619,11 +627,9 @@ class Context(Lane):
             import torch
             if out is None:
                 out = torch.zeros((th.S, len(windows)), dtype=torch.float64, device=torch.device("cuda", self.device))
-            assert out.is_cuda and out.is_contiguous() and out.numel() == th.S * len(windows) and out.element_size() == 8
-            assert out.device.index == self.device
+            self._check_out(out, th.S * len(windows))
             if com is not None:
-                assert com.is_cuda and com.is_contiguous() and com.numel() == 3 * th.n_frames and com.element_size() == 8
-                assert com.device.index == self.device
+                self._check_out(com, 3 * th.n_frames)
             self._order_after_torch()
             rc = self._lib.amof_msd_window_dev(self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data),
                                                len(windows), 1 if unwrap else 0, 1 if remove_com else 0, int(a0), int(a1),
@@ -660,11 +666,9 @@ class Context(Lane):
                 out = (torch.zeros((S, W, nbins), dtype=torch.int64, device=dev), torch.zeros((S, W), dtype=torch.int64, device=dev),
                        torch.zeros((S, W, 2), dtype=torch.float64, device=dev))
             for x, n in zip(out, (S * W * nbins, S * W, S * W * 2)):
-                assert x.is_cuda and x.is_contiguous() and x.numel() == n and x.element_size() == 8
-                assert x.device.index == self.device
+                self._check_out(x, n)
             if com is not None:
-                assert com.is_cuda and com.is_contiguous() and com.numel() == 3 * th.n_frames and com.element_size() == 8
-                assert com.device.index == self.device
+                self._check_out(com, 3 * th.n_frames)
             self._order_after_torch()
             self._check(self._lib.amof_vanhove_window_dev(*(args + (ctypes.c_void_p(com.data_ptr()) if com is not None else None,) +
                                                            tuple(ctypes.c_void_p(x.data_ptr()) for x in out))))
@@ -680,7 +684,7 @@ class Context(Lane):
     @_locked
     def vanhove_distinct(self, packed, windows, rmax, nbins, origin_stride=1, work_range=None, out=None):
         """``(hist [S][S][W][nbins] u64, kinds)``: the distinct Van Hove counts of ``amof_vanhove_distinct`` for the entries
-        ``work_range`` (default: all) of the lag-major (lag, origin) work list (amof_amd.vanhove_distinct.work_list).
+        ``work_range`` (default: all) of the lag-major (lag, origin) work list (amof_amd.lags.work_list).
 
         ``out``: optional torch CUDA int64 tensor ``[S][S][W][nbins]`` the counts are ADDED into on the device (stays
         resident for an RCCL merge)."""
@@ -688,14 +692,11 @@ class Context(Lane):
         windows = np.ascontiguousarray(windows, dtype=np.int32)
         W, nbins = len(windows), int(nbins)
         if work_range is None:
-            m = windows.astype(np.int64)
-            F, s = th.n_frames, max(1, int(origin_stride))
-            work_range = (0, int(np.where(F - m - 2 >= 0, (F - m - 2) // s + 1, 0).sum()))
+            work_range = _whole_work_list(th.n_frames, windows, origin_stride)
         args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), W, int(origin_stride), int(work_range[0]),
                 int(work_range[1]), float(rmax), nbins)
         if out is not None:
-            assert out.is_cuda and out.is_contiguous() and out.numel() == th.S * th.S * W * nbins and out.element_size() == 8
-            assert out.device.index == self.device
+            self._check_out(out, th.S * th.S * W * nbins)
             self._order_after_torch()
             self._check(self._lib.amof_vanhove_distinct_dev(*(args + (ctypes.c_void_p(out.data_ptr()),))))
             return out, th.kinds
@@ -719,8 +720,7 @@ class Context(Lane):
         args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data), ctypes.c_void_p(sets.ctypes.data), len(sets),
                 ctypes.c_void_p(windows.ctypes.data), len(windows), int(origin_stride), int(a0), int(a1))
         if out is not None:
-            assert out.is_cuda and out.is_contiguous() and out.numel() == len(sets) * len(windows) * 3 and out.element_size() == 8
-            assert out.device.index == self.device
+            self._check_out(out, len(sets) * len(windows) * 3)
             self._order_after_torch()
             self._check(self._lib.amof_bond_survival_dev(*(args + (ctypes.c_void_p(out.data_ptr()),))))
             return out
@@ -748,9 +748,8 @@ class Context(Lane):
                 int(f0), int(f1), int(frame_stride), float(dq), nbins)
         if out is not None:
             counts, sums = out
-            assert counts.is_cuda and counts.is_contiguous() and counts.numel() == nbins + 1 and counts.element_size() == 8
-            assert sums.is_cuda and sums.is_contiguous() and sums.numel() == P * nbins and sums.element_size() == 8
-            assert counts.device.index == self.device and sums.device.index == self.device
+            self._check_out(counts, nbins + 1)
+            self._check_out(sums, P * nbins)
             scale = np.zeros(P, dtype=np.int32)
             self._order_after_torch()
             self._check(self._lib.amof_sq_accumulate_dev(*(args + (ctypes.c_void_p(counts.data_ptr()),
@@ -770,7 +769,7 @@ class Context(Lane):
                        out=None):
         """``(counts [W][nbins] u64, coh [S][S][W][nbins] f64, self [S][W][nbins] f64 or None, beyond [W] u64, kinds)`` of
         ``amof_isf_accumulate``: the vectors ``hkl`` (int ``[K][3]``) correlated over the entries ``work_range`` (default:
-        all) of the lag-major (lag, origin) work list (amof_amd.vanhove_distinct.work_list); ``coh[a][c]``: species a at the
+        all) of the lag-major (lag, origin) work list (amof_amd.lags.work_list); ``coh[a][c]``: species a at the
         origin, c at the origin + lag.  ``recip``: ``[n_cells][3][3]`` (default ``reciprocal(packed.cell)``).
 
         ``out``: optional torch CUDA int64 tensor of ``isf_layout(S, W, nbins, self_part)["size"]`` words (counts, beyond,
@@ -783,16 +782,13 @@ class Context(Lane):
         assert recip.shape == (packed.cell.shape[0], 3, 3)
         S, W, nbins = th.S, len(windows), int(nbins)
         if work_range is None:
-            m = windows.astype(np.int64)
-            F, s = th.n_frames, max(1, int(origin_stride))
-            work_range = (0, int(np.where(F - m - 2 >= 0, (F - m - 2) // s + 1, 0).sum()))
+            work_range = _whole_work_list(th.n_frames, windows, origin_stride)
         args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(recip.ctypes.data), ctypes.c_void_p(hkl.ctypes.data), len(hkl),
                 ctypes.c_void_p(windows.ctypes.data), W, int(origin_stride), int(work_range[0]), int(work_range[1]), float(dq),
                 nbins)
         if out is not None:
             lay = isf_layout(S, W, nbins, self_part)
-            assert out.is_cuda and out.is_contiguous() and out.numel() == lay["size"] and out.element_size() == 8
-            assert out.device.index == self.device
+            self._check_out(out, lay["size"])
             scale = np.zeros(S * (S + 1) // 2, dtype=np.int32)
             base = out.data_ptr()
             self._order_after_torch()
@@ -835,8 +831,7 @@ class Context(Lane):
         Raises :class:`Unsupported` where the fused form does not apply (the caller then takes ``msd_com`` + ``msd_window``)."""
         th = self._traj(packed)
         windows = np.ascontiguousarray(windows, dtype=np.int32)
-        assert csum.is_cuda and csum.is_contiguous() and csum.numel() == 3 * th.n_frames and csum.element_size() == 8
-        assert csum.device.index == self.device
+        self._check_out(csum, 3 * th.n_frames)
         self._order_after_torch()
         self._check(self._lib.amof_msd_shard_begin(self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), len(windows),
                                                    int(atom_range[0]), int(atom_range[1]), ctypes.c_void_p(csum.data_ptr())))
@@ -848,9 +843,8 @@ class Context(Lane):
         atoms ``[a0, a1)`` into ``out`` (torch CUDA f64 ``[S][W]``); ``csum`` = the table summed over the ranks"""
         th = self._traj(packed)
         windows = np.ascontiguousarray(windows, dtype=np.int32)
-        assert csum.is_cuda and csum.is_contiguous() and csum.numel() == 3 * th.n_frames and csum.element_size() == 8
-        assert out.is_cuda and out.is_contiguous() and out.numel() == th.S * len(windows) and out.element_size() == 8
-        assert csum.device.index == self.device and out.device.index == self.device
+        self._check_out(csum, 3 * th.n_frames)
+        self._check_out(out, th.S * len(windows))
         self._order_after_torch()
         self._check(self._lib.amof_msd_shard_finish(self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), len(windows),
                                                     int(atom_range[0]), int(atom_range[1]), ctypes.c_void_p(csum.data_ptr()),
@@ -982,9 +976,7 @@ class MultiContext(object):
         """the (lag, origin) work list sharded over the devices: the integer counts add up exactly"""
         windows = np.ascontiguousarray(windows, dtype=np.int32)
         if work_range is None:
-            m = windows.astype(np.int64)
-            F, s = packed.n_frames, max(1, int(origin_stride))
-            work_range = (0, int(np.where(F - m - 2 >= 0, (F - m - 2) // s + 1, 0).sum()))
+            work_range = _whole_work_list(packed.n_frames, windows, origin_stride)
         jobs = []
         for ctx, (a, b) in zip(self.ctxs, self._shards(*work_range)):
             def job(ctx=ctx, a=a, b=b):

@@ -18,10 +18,8 @@ from . import _hip
 from . import atom as amatom
 from . import data as _data
 from . import dist as _dist
+from . import lags
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
-from .vanhove import window_setup
-from .vanhove_distinct import n_origins
 
 logger = logging.getLogger(__name__)
 
@@ -104,17 +102,13 @@ class BondLifetime(Deferred):
                 take contiguous shares of the centre atoms and all-reduce the counters once; False -> single process
         """
         bl = cls()
-        window, time = window_setup(len(trajectory), delta_time, max_time, timestep)
+        window, time = lags.window_setup(len(trajectory), delta_time, max_time, timestep)
         bl.compute_survival(trajectory, nb_set_and_cutoff, window, time, origin_stride, device=device, distributed=distributed)
         return bl
 
     def compute_survival(self, trajectory, nb_set_and_cutoff, window, time, origin_stride=1, device=None, distributed=None):
-        if int(origin_stride) != origin_stride or origin_stride < 1:
-            raise ValueError("origin_stride must be an integer >= 1")
-        origin_stride = int(origin_stride)
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
-        if getattr(packed, "is_stream", False):
-            packed = packed.read_all()      # a lag couples frames half a trajectory apart: nothing to stream
+        origin_stride = lags.check_origin_stride(origin_stride)
+        packed = lags.pack(trajectory, device)
         window = np.asarray(window, dtype=np.int32)
         kinds, _ = _hip.packed_species(packed)
         lut = {z: k for k, z in enumerate(kinds)}
@@ -131,39 +125,30 @@ class BondLifetime(Deferred):
             if rcm[a, b] > half:
                 raise ValueError("cutoff %s exceeds half the smallest perpendicular cell height (%s): a pair could be bonded "
                                  "through two images" % (rcm[a, b], half))
-        F = len(packed)
-        n_orig = n_origins(F, window, origin_stride)
+        n_orig = lags.n_origins(len(packed), window, origin_stride)
         logger.info("Start computing bond survival at %s times for %s sets", len(window), len(live))
 
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        atoms = _dist.shard_range(packed.n_atoms, rank, world) if merge else (0, packed.n_atoms)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 0)
-        on_device = merge and _dist.device_collectives()
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
+        st = lags.setup(packed, device, distributed)
+        ctx, merge = st.ctx, st.merge
+        atoms = _dist.shard_range(packed.n_atoms, st.rank, st.world) if merge else (0, packed.n_atoms)
         W = len(window)
 
         def local():
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
-            if getattr(source, "is_stream", False):
-                source.read_all()
+            lags.begin_local(st.source)
             if not live:
                 return np.zeros((0, W, 3), dtype=np.uint64)
-            if on_device:
+            out = None
+            if st.on_device:
                 # the counters stay in HBM from the kernels through the RCCL all-reduce (amof_bond_survival_dev)
                 import torch
                 out = torch.zeros((len(live), W, 3), dtype=torch.int64, device=torch.device("cuda", ctx.device))
-                return ctx.bond_survival(packed, rcm, live, window, origin_stride=origin_stride, atom_range=atoms, out=out)
-            return ctx.bond_survival(packed, rcm, live, window, origin_stride=origin_stride, atom_range=atoms)
+            return ctx.bond_survival(packed, rcm, live, window, origin_stride=origin_stride, atom_range=atoms, out=out)
 
         def finish(counts):
             # the ranks' merge (the calling thread: collectives in program order): ONE all-reduce of the integer counters
-            if live and on_device:
-                _dist.all_reduce_sum(counts)
-                counts = counts.cpu().numpy().view(np.uint64)
-            elif live and merge:
-                counts = _dist.all_reduce_sum(counts, device=ctx.device)
+            if live:
+                counts = _dist.all_reduce_counts(counts, st.on_device, merge, ctx.device)
             self._assemble(counts, names, live, n_orig, time)
 
         self._defer(ctx, local, finish, collective=merge and bool(live))

@@ -14,6 +14,7 @@
 
 #include "../../include/amof_hip.h"
 #include "guard_math.h"
+#include "lag_work.h"
 
 namespace amof {
 
@@ -80,7 +81,8 @@ struct amof_ctx {
     int64_t progress = 0;         // 2 calls + (the call's dominant kernel is queued): read by OTHER threads (amof_ctx_follow), atomically
     int64_t shard_ticket = 0;     // `calls` right after a begin; 0 = none pending
     int64_t shard_key[7] = {0, 0, 0, 0, 0, 0, 0};
-    // kernel seconds of the stages of the last amof_isf_accumulate[_dev]: rho table (with the quantisation), correlation, self
+    // kernel seconds of the stages of the last amof_isf_accumulate[_dev]: rho table (with the quantisation), correlation, self;
+    // of the last amof_bond_survival[_dev]: lists, series, correlations (StageSpans)
     double stage_seconds[3] = {-1.0, -1.0, -1.0};
 };
 
@@ -90,6 +92,11 @@ int fail(amof_ctx *ctx, int code, const char *fmt, ...);
 // hipStreamSynchronize(ctx->stream) + reuse of the pinned staging ring
 hipError_t sync_stream(amof_ctx *ctx);
 int ensure(amof_ctx *ctx, Slot s, size_t bytes, void **out);
+// the arguments every entry point of the lag/origin family takes (lag_work.h): windows[W], each in [0, max(F, 1)), stride >= 1
+int check_lag_args(amof_ctx *ctx, const int32_t *windows, int32_t W, int64_t F, int64_t stride);
+// dst[i] += src[i] on the context's stream: a call's own counters into the caller's device buffer ("_dev" entry points)
+int add_into(amof_ctx *ctx, uint64_t *dst, const uint64_t *src, size_t n);
+int add_into(amof_ctx *ctx, double *dst, const double *src, size_t n);
 
 #define AMOF_HIP_TRY(ctx, expr)                                                              \
     do {                                                                                     \
@@ -210,6 +217,7 @@ struct HostTiles {
     std::vector<int32_t> perm;     // atoms sorted by species (stable)
     std::vector<Tile> tiles;
     std::vector<int64_t> nsp;      // atoms per species
+    std::vector<int64_t> sp_first; // [S + 1] species s owns perm[sp_first[s] .. sp_first[s + 1])
     std::vector<int32_t> sp_first_tile, sp_ntiles;
 };
 void build_tiles(const amof_traj *t, int tile, HostTiles &out, int granule = 0);
@@ -330,6 +338,46 @@ void timing_begin(amof_ctx *ctx);
 void timing_end(amof_ctx *ctx);
 void timing_dom_begin(amof_ctx *ctx, const char *path);
 void timing_dom_end(amof_ctx *ctx, int64_t launches);
+
+// Event pairs around the stages of a call, for amof_last_kernel_seconds 2 .. 4 (ctx->stage_seconds).  A stage may be
+// begun many times; end() closes the span begun last.  An event that cannot be created leaves its span out, silently.
+struct StageSpans {
+    struct Span {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        int stage = 0;
+    };
+    amof_ctx *ctx;
+    std::vector<Span> spans;
+    explicit StageSpans(amof_ctx *c) : ctx(c) {}
+    StageSpans(const StageSpans &) = delete;
+    StageSpans &operator=(const StageSpans &) = delete;
+    ~StageSpans()
+    {
+        for (Span &s : spans) {
+            if (s.e0) (void)hipEventDestroy(s.e0);
+            if (s.e1) (void)hipEventDestroy(s.e1);
+        }
+    }
+    void begin(int stage)
+    {
+        Span s;
+        s.stage = stage;
+        if (hipEventCreate(&s.e0) == hipSuccess && hipEventCreate(&s.e1) == hipSuccess) (void)hipEventRecord(s.e0, ctx->stream);
+        spans.push_back(s);
+    }
+    void end()
+    {
+        if (!spans.empty() && spans.back().e1) (void)hipEventRecord(spans.back().e1, ctx->stream);
+    }
+    void collect()      // (the stream has been synchronised)
+    {
+        for (double &x : ctx->stage_seconds) x = 0.0;
+        for (Span &s : spans) {
+            float ms = 0.f;
+            if (s.e0 && s.e1 && hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess) ctx->stage_seconds[s.stage] += (double)ms * 1e-3;
+        }
+    }
+};
 
 // ---------------------------------------------------------------- LDS-DMA --
 typedef __attribute__((address_space(1))) const void *gptr_t;

@@ -351,42 +351,6 @@ __global__ __launch_bounds__(256) void bond_final_kernel(const unsigned long lon
     }
 }
 
-// a pair of events around a stage (amof_last_kernel_seconds 2, 3, 4: list, series, correlation)
-struct BondSpans {
-    amof_ctx *ctx;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev[3];
-    explicit BondSpans(amof_ctx *c) : ctx(c) {}
-    ~BondSpans()
-    {
-        for (auto &v : ev)
-            for (auto &e : v) {
-                if (e.first) (void)hipEventDestroy(e.first);
-                if (e.second) (void)hipEventDestroy(e.second);
-            }
-    }
-    void begin(int stage)
-    {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess) (void)hipEventRecord(e0, ctx->stream);
-        ev[stage].push_back(std::make_pair(e0, e1));
-    }
-    void end(int stage)
-    {
-        if (ev[stage].back().second) (void)hipEventRecord(ev[stage].back().second, ctx->stream);
-    }
-    void collect()      // (stream synchronised)
-    {
-        for (int i = 0; i < 3; i++) {
-            ctx->stage_seconds[i] = 0.0;
-            for (auto &e : ev[i]) {
-                float ms = 0.f;
-                if (e.first && e.second && hipEventElapsedTime(&ms, e.first, e.second) == hipSuccess)
-                    ctx->stage_seconds[i] += (double)ms * 1e-3;
-            }
-        }
-    }
-};
-
 // counts (host, overwritten) or counts_dev (device, added into)
 int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets, const int32_t *windows,
              int32_t W, int64_t stride, int64_t atom_begin, int64_t atom_end, uint64_t *counts, uint64_t *counts_dev)
@@ -394,13 +358,11 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
     AMOF_TRY(validate_traj(ctx, t, false));
     const int S = t->n_species;
     const int64_t N = t->n_atoms, F = t->n_frames;
-    if (!cutoff || n_sets < 0 || (n_sets > 0 && !sets) || W < 0 || (W > 0 && !windows)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (stride < 1) return fail(ctx, AMOF_EINVAL, "origin_stride must be >= 1");
+    if (!cutoff || n_sets < 0 || (n_sets > 0 && !sets)) return fail(ctx, AMOF_EINVAL, "NULL argument");
+    AMOF_TRY(check_lag_args(ctx, windows, W, F, stride));
     if (atom_begin < 0 || atom_end > N || atom_begin > atom_end)
         return fail(ctx, AMOF_EINVAL, "atom range [%lld, %lld) outside [0, %lld)", (long long)atom_begin, (long long)atom_end, (long long)N);
     if (F > 0x7fffff00LL - 64) return fail(ctx, AMOF_EINVAL, "too many frames");
-    for (int w = 0; w < W; w++)
-        if (windows[w] < 0 || windows[w] >= std::max<int64_t>(F, 1)) return fail(ctx, AMOF_EINVAL, "window %d out of range", windows[w]);
     for (int s = 0; s < n_sets; s++) {
         if (sets[2 * s] < 0 || sets[2 * s] >= S || sets[2 * s + 1] < 0 || sets[2 * s + 1] >= S)
             return fail(ctx, AMOF_EINVAL, "set %d names a species outside 0..%d", s, S - 1);
@@ -425,8 +387,7 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
     }
     HostTiles tiles;
     build_tiles(t, BL_THREADS, tiles);
-    std::vector<int64_t> sp_first((size_t)S + 1, 0);
-    for (int s = 0; s < S; s++) sp_first[(size_t)s + 1] = sp_first[(size_t)s] + tiles.nsp[(size_t)s];
+    const std::vector<int64_t> &sp_first = tiles.sp_first;
 
     // sorted distinct lags and where every window finds its own
     std::vector<int32_t> lags(windows, windows + W);
@@ -436,10 +397,13 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
     std::vector<int32_t> map((size_t)W);
     for (int w = 0; w < W; w++) map[(size_t)w] = (int32_t)(std::lower_bound(lags.begin(), lags.end(), windows[w]) - lags.begin());
     const int nwords = (int)((F + 63) / 64);
-    const int64_t n_origins = (F - 2) / stride + 1;         // of lag 0: k = 1 + stride o <= F - 1
+    const int64_t n_origins = lag_origin_count(F, 0, stride);      // lag 0's origins: a superset of every lag's
     if (n_origins > 0x7fffffffLL) return fail(ctx, AMOF_EINVAL, "too many frames");
     std::vector<unsigned long long> obase((size_t)nwords, 0ull);
-    for (int64_t k = 1; k < F; k += stride) obase[(size_t)(k >> 6)] |= 1ull << (k & 63);
+    for (int64_t o = 0; o < n_origins; o++) {
+        const int64_t k = lag_origin_frame(o, stride);
+        obase[(size_t)(k >> 6)] |= 1ull << (k & 63);
+    }
 
     // ---- path selection ----
     const char *env_exact = getenv("AMOF_BOND_EXACT");
@@ -456,7 +420,7 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
 
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
-    BondSpans spans(ctx);
+    StageSpans spans(ctx);      // list, series, correlation
     const double *pos_dev = nullptr;
     AMOF_TRY(stage_positions(ctx, t, &pos_dev));
     UploadPack pk;
@@ -555,7 +519,7 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
             AMOF_HIP_TRY(ctx, hipGetLastError());
             std::vector<unsigned> rowcnt((size_t)rows);
             AMOF_TRY(fetch(ctx, rowcnt.data(), d_rowcnt, (size_t)rows * sizeof(unsigned)));
-            spans.end(0);
+            spans.end();
             if (getenv("AMOF_BOND_REPORT")) {
                 size_t total = 0;
                 for (unsigned n : rowcnt) total += n;
@@ -583,7 +547,7 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
                                    (const unsigned *)d_bitmap, gr0, grows, wpr, (const unsigned *)d_rowoff, pk.ptr<int32_t>(i_perm),
                                    la.seg_a, la.seg_b, (int2 *)d_pairs);
                 AMOF_HIP_TRY(ctx, hipGetLastError());
-                spans.end(0);
+                spans.end();
                 // rowoff dies with this iteration: a copy too big for the staging ring has consumed it when upload returns, one
                 // through the ring was copied there at once
 
@@ -612,7 +576,7 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
                     AMOF_HIP_TRY(ctx, hipGetLastError());
                     series_launches++;
                     timing_dom_end(ctx, series_launches);
-                    spans.end(1);
+                    spans.end();
 
                     spans.begin(2);
                     BondCorrArgs ca;
@@ -636,7 +600,7 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
                         hipLaunchKernelGGL(bond_corr_kernel, dim3((unsigned)pblocks, (unsigned)ysplit), dim3(BC_THREADS), lds, ctx->stream, ca);
                         AMOF_HIP_TRY(ctx, hipGetLastError());
                     }
-                    spans.end(2);
+                    spans.end();
                 }
             }
         }

@@ -24,6 +24,33 @@ int fail(amof_ctx *ctx, int code, const char *fmt, ...)
     return code;
 }
 
+int check_lag_args(amof_ctx *ctx, const int32_t *windows, int32_t W, int64_t F, int64_t stride)
+{
+    if (W < 0 || (W > 0 && !windows)) return fail(ctx, AMOF_EINVAL, "NULL argument");
+    if (stride < 1) return fail(ctx, AMOF_EINVAL, "origin_stride must be >= 1");
+    for (int w = 0; w < W; w++)
+        if (windows[w] < 0 || windows[w] >= std::max<int64_t>(F, 1)) return fail(ctx, AMOF_EINVAL, "window %d out of range", windows[w]);
+    return AMOF_OK;
+}
+
+template <typename T> __global__ void add_into_kernel(T *dst, const T *src, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] += src[i];
+}
+
+template <typename T> static int add_into_t(amof_ctx *ctx, T *dst, const T *src, size_t n)
+{
+    if (!n) return AMOF_OK;
+    hipLaunchKernelGGL(add_into_kernel<T>, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->stream, dst, src, n);
+    AMOF_HIP_TRY(ctx, hipGetLastError());
+    return AMOF_OK;
+}
+int add_into(amof_ctx *ctx, uint64_t *dst, const uint64_t *src, size_t n)
+{
+    return add_into_t(ctx, (unsigned long long *)dst, (const unsigned long long *)src, n);
+}
+int add_into(amof_ctx *ctx, double *dst, const double *src, size_t n) { return add_into_t(ctx, dst, src, n); }
+
 int ensure(amof_ctx *ctx, Slot s, size_t bytes, void **out)
 {
     DevBuf &b = ctx->buf[s];
@@ -312,7 +339,8 @@ void build_tiles(const amof_traj *t, int tile, HostTiles &out, int granule)
     int64_t N = t->n_atoms;
     out.nsp.assign(S, 0);
     for (int64_t i = 0; i < N; i++) out.nsp[t->species[i]]++;
-    std::vector<int64_t> first(S + 1, 0);
+    std::vector<int64_t> &first = out.sp_first;
+    first.assign(S + 1, 0);
     for (int s = 0; s < S; s++) first[s + 1] = first[s] + out.nsp[s];
     out.perm.assign((size_t)N, 0);
     std::vector<int64_t> fill(first.begin(), first.end() - 1);

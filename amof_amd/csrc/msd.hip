@@ -1311,12 +1311,6 @@ __global__ __launch_bounds__(MSD_THREADS) void direct_reduce_kernel(const double
 
 using namespace amof;
 
-__global__ void add_f64_kernel(double *dst, const double *src, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] += src[i];
-}
-
 
 // ---- host side of the fused form ----
 namespace {
@@ -1730,11 +1724,7 @@ static int msd_window_run(amof_ctx *ctx, const amof_traj *t, const int32_t *wind
                        (const double *)d_part, (const int32_t *)d_sgf, (int)W, (double *)d_out);
     AMOF_HIP_TRY(ctx, hipGetLastError());
     }   // (!done: the transposed forms)
-    if (sumsq_dev) {
-        hipLaunchKernelGGL(add_f64_kernel, dim3((unsigned)((S * W + 255) / 256)), dim3(256), 0, ctx->stream, sumsq_dev,
-                           (const double *)d_out, S * (int)W);
-        AMOF_HIP_TRY(ctx, hipGetLastError());
-    }
+    if (sumsq_dev) AMOF_TRY(add_into(ctx, sumsq_dev, (const double *)d_out, (size_t)S * W));
     timing_end(ctx);
     if (sumsq)
         AMOF_TRY(fetch(ctx, sumsq, d_out, (size_t)S * W * sizeof(double)));
@@ -1902,9 +1892,7 @@ extern "C" int amof_msd_shard_finish(amof_ctx *ctx, const amof_traj *t, const in
         AMOF_HIP_TRY(ctx, sync_stream(ctx));
         return msd_window_run(ctx, t, windows, W, 0, 1, a0, a1, (const double *)d_com, nullptr, sumsq_dev);
     }
-    hipLaunchKernelGGL(add_f64_kernel, dim3((unsigned)((S * W + 255) / 256)), dim3(256), 0, ctx->stream, sumsq_dev, (const double *)d_out,
-                       S * (int)W);
-    AMOF_HIP_TRY(ctx, hipGetLastError());
+    AMOF_TRY(add_into(ctx, sumsq_dev, (const double *)d_out, (size_t)S * W));
     timing_end(ctx);
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     return AMOF_OK;
@@ -1957,8 +1945,6 @@ extern "C" int amof_msd_direct(amof_ctx *ctx, const amof_traj *t, double *msd)
             if (!(t->cell[9 * k + 4 * j] > 0.0)) return fail(ctx, AMOF_EINVAL, "DirectMsd needs positive cell diagonals");
     HostTiles tiles;
     build_tiles(t, 256, tiles);
-    std::vector<int64_t> sp_first(S + 1, 0);
-    for (int x = 0; x < S; x++) sp_first[x + 1] = sp_first[x] + tiles.nsp[x];
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
     const double *pos_dev = nullptr;
@@ -1966,7 +1952,7 @@ extern "C" int amof_msd_direct(amof_ctx *ctx, const amof_traj *t, double *msd)
     void *d_cell, *d_perm, *d_spf, *d_sq, *d_out;
     AMOF_TRY(upload(ctx, SLOT_GEOM, t->cell, (size_t)t->n_cells * 9 * sizeof(double), &d_cell));
     AMOF_TRY(upload(ctx, SLOT_PERM, tiles.perm.data(), tiles.perm.size() * sizeof(int32_t), &d_perm));
-    AMOF_TRY(upload(ctx, SLOT_AUX0, sp_first.data(), sp_first.size() * sizeof(int64_t), &d_spf));
+    AMOF_TRY(upload(ctx, SLOT_AUX0, tiles.sp_first.data(), tiles.sp_first.size() * sizeof(int64_t), &d_spf));
     AMOF_TRY(ensure(ctx, SLOT_AUX3, (size_t)F * 3 * N * sizeof(double), &d_sq));
     AMOF_TRY(ensure(ctx, SLOT_OUT0, (size_t)F * (S + 1) * sizeof(double), &d_out));
     if (N > 0) {

@@ -1773,12 +1773,6 @@ static void pick_chunks(int64_t F, size_t nwork, int32_t &fpc, unsigned &chunks)
     chunks = (unsigned)c;
 }
 
-__global__ void add_u64_kernel(unsigned long long *dst, const unsigned long long *src, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        dst[i] += src[i];
-}
-
 // ---- fast-path preparation shared by CN and BAD ----
 struct NbrFast {
     bool ok = false;
@@ -1853,8 +1847,7 @@ static int nbr_fast_prepare(amof_ctx *ctx, const amof_traj *t, const double *cut
         r._pad = 0.f;
         r.gap_per_len = 4294967296.0 / st.geom.rec[(size_t)k * GEOM_STRIDE + 18 + nf.axis] * (1.0 + 1e-6);
     }
-    nf.sp_first.assign(S + 1, 0);
-    for (int x = 0; x < S; x++) nf.sp_first[x + 1] = nf.sp_first[x] + st.tiles.nsp[x];
+    nf.sp_first = st.tiles.sp_first;
     // species without a cutoff to any species are neither centres nor partners: the cell sort skips them
     nf.used_mask = 0ull;
     nf.max_used_atoms = 1;
@@ -2165,8 +2158,7 @@ static int nbr_frame_prepare(const amof_traj *t, const double *cutoff, NbrSetup 
         r._pad = 0.f;
         r.gap_per_len = 0.0;
     }
-    nw.sp_first.assign((size_t)S + 1, 0);
-    for (int x = 0; x < S; x++) nw.sp_first[(size_t)x + 1] = nw.sp_first[(size_t)x] + st.tiles.nsp[(size_t)x];
+    nw.sp_first = st.tiles.sp_first;
     FrameArgs &fr = nw.fr;
     {
         const double want = grel + 3.0 / 16777216.0;     // (+ 3u: see nbr_fast_prepare)
@@ -2915,11 +2907,8 @@ static int bad_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, cons
     }
     // complete and valid: add to the caller's (device) buffers
     if (T > 0 && t->n_frames > 0) {
-        hipLaunchKernelGGL(add_u64_kernel, dim3(64), dim3(256), 0, ctx->stream, hist_dev,
-                           (const unsigned long long *)d_hs, (size_t)T * KC * nb);
-        hipLaunchKernelGGL(add_u64_kernel, dim3(1), dim3(64), 0, ctx->stream, nang_dev,
-                           (const unsigned long long *)d_ns, (size_t)T * KC);
-        AMOF_HIP_TRY(ctx, hipGetLastError());
+        AMOF_TRY(add_into(ctx, (uint64_t *)hist_dev, (const uint64_t *)d_hs, (size_t)T * KC * nb));
+        AMOF_TRY(add_into(ctx, (uint64_t *)nang_dev, (const uint64_t *)d_ns, (size_t)T * KC));
     }
     timing_end(ctx);
     AMOF_HIP_TRY(ctx, sync_stream(ctx));

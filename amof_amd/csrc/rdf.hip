@@ -2073,10 +2073,8 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
                 if (hmin[x] > hmin[axis]) axis = x;
             const char *nocull = getenv("AMOF_RDF_NOCULL");
             const bool cull = !(nocull && nocull[0] == '1') && 2.0 * rmax * 1.05 < hmin[axis];
-            std::vector<int64_t> sp_first(S + 1, 0);
-            for (int sidx = 0; sidx < S; sidx++) sp_first[sidx + 1] = sp_first[sidx] + ftiles.nsp[sidx];
             void *d_spfirst;
-            AMOF_TRY(upload(ctx, SLOT_AUX4, sp_first.data(), sp_first.size() * sizeof(int64_t), &d_spfirst));
+            AMOF_TRY(upload(ctx, SLOT_AUX4, ftiles.sp_first.data(), ftiles.sp_first.size() * sizeof(int64_t), &d_spfirst));
             // per-cell records; fixed-point components are stored in the order (ax0, ax1, axis)
             std::vector<FrameScale> fsv((size_t)nc);
             const int ord[3] = {(axis + 1) % 3, (axis + 2) % 3, axis};

@@ -642,53 +642,6 @@ __global__ __launch_bounds__(SQ_THREADS) void isf_self_bin_kernel(const double *
     }
 }
 
-__global__ void isf_add_kernel(unsigned long long *dst, const unsigned long long *src, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] += src[i];
-}
-
-// a pair of events around a stage; seconds() after the stream has been synchronised
-struct IsfSpan {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int stage = 0;
-};
-
-struct IsfSpans {
-    amof_ctx *ctx;
-    std::vector<IsfSpan> spans;
-    explicit IsfSpans(amof_ctx *c) : ctx(c) {}
-    ~IsfSpans()
-    {
-        for (IsfSpan &s : spans) {
-            if (s.e0) (void)hipEventDestroy(s.e0);
-            if (s.e1) (void)hipEventDestroy(s.e1);
-        }
-    }
-    void begin(int stage)
-    {
-        IsfSpan s;
-        s.stage = stage;
-        if (hipEventCreate(&s.e0) != hipSuccess || hipEventCreate(&s.e1) != hipSuccess) {
-            spans.push_back(s);
-            return;
-        }
-        (void)hipEventRecord(s.e0, ctx->stream);
-        spans.push_back(s);
-    }
-    void end()
-    {
-        if (!spans.empty() && spans.back().e1) (void)hipEventRecord(spans.back().e1, ctx->stream);
-    }
-    void collect()      // (stream synchronised)
-    {
-        for (int i = 0; i < 3; i++) ctx->stage_seconds[i] = 0.0;
-        for (IsfSpan &s : spans) {
-            float ms = 0.f;
-            if (s.e0 && s.e1 && hipEventElapsedTime(&ms, s.e0, s.e1) == hipSuccess) ctx->stage_seconds[s.stage] += (double)ms * 1e-3;
-        }
-    }
-};
-
 template <bool GLOBAL>
 hipError_t isf_launch_corr(amof_ctx *ctx, const IsfArgs &a, dim3 grid, size_t lds)
 {
@@ -720,28 +673,18 @@ int isf_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_
     const int S = t->n_species, P = S * (S + 1) / 2;
     const int64_t N = t->n_atoms, F = t->n_frames;
     if (!recip && t->n_cells > 0) return fail(ctx, AMOF_EINVAL, "NULL recip");
-    if (W < 0 || (W > 0 && !windows)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (stride < 1) return fail(ctx, AMOF_EINVAL, "origin_stride must be >= 1");
+    AMOF_TRY(check_lag_args(ctx, windows, W, F, stride));
     if (!(dq > 0.0) || !isfinite(dq)) return fail(ctx, AMOF_EINVAL, "dq must be positive and finite");
     if (nbins < 1) return fail(ctx, AMOF_EINVAL, "nbins must be >= 1");
     if (F > 0x7fffffffLL || N > 0x7fffffffLL) return fail(ctx, AMOF_EINVAL, "too many frames or atoms");
-    for (int w = 0; w < W; w++)
-        if (windows[w] < 0 || windows[w] >= std::max<int64_t>(F, 1)) return fail(ctx, AMOF_EINVAL, "window %d out of range", windows[w]);
     for (int64_t c = 0; c < 9 * t->n_cells; c++)
         if (!isfinite(recip[c])) return fail(ctx, AMOF_EINVAL, "recip is not finite");
     // this call's origin indices [o0, o1) of every lag (the lag-major work list of amof_vanhove_distinct)
-    std::vector<int2> lagiv(std::max(W, 1), make_int2(0, 0));
-    int64_t total = 0, n_entries = 0;
-    for (int w = 0; w < W; w++) {
-        const int64_t m = windows[w];
-        const int64_t n = F - m - 2 >= 0 ? (F - m - 2) / stride + 1 : 0;      // k = 1 + stride o <= F - m - 1
-        const int64_t o0 = std::max<int64_t>(wb - total, 0), o1 = std::min<int64_t>(we - total, n);
-        if (o0 < o1) {
-            lagiv[w] = make_int2((int)o0, (int)o1);
-            n_entries += o1 - o0;
-        }
-        total += n;
-    }
+    static_assert(sizeof(LagRange) == sizeof(int2), "the kernels read the table as int2");
+    std::vector<LagRange> lagiv(std::max(W, 1), LagRange{0, 0});
+    const int64_t total = lag_work_ranges(windows, W, F, stride, wb, we, lagiv.data());
+    int64_t n_entries = 0;
+    for (int w = 0; w < W; w++) n_entries += lagiv[w].o1 - lagiv[w].o0;
     if (wb < 0 || we > total || wb > we) return fail(ctx, AMOF_EINVAL, "work range [%lld, %lld) outside [0, %lld)", (long long)wb,
                                                      (long long)we, (long long)total);
     const size_t n_cnt = (size_t)W * nbins, n_coh = (size_t)S * S * n_cnt, n_self = want_self ? (size_t)S * n_cnt : 0;
@@ -772,11 +715,11 @@ int isf_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_
     std::vector<int32_t> slot_of(F, -1), fsel;
     int omin = 0x7fffffff, omax = 0;
     for (int w = 0; w < W; w++) {
-        if (lagiv[w].x >= lagiv[w].y) continue;
-        omin = std::min(omin, lagiv[w].x);
-        omax = std::max(omax, lagiv[w].y);
-        for (int64_t o = lagiv[w].x; o < lagiv[w].y; o++) {
-            const int64_t k = 1 + stride * o;
+        if (lagiv[w].o0 >= lagiv[w].o1) continue;
+        omin = std::min(omin, lagiv[w].o0);
+        omax = std::max(omax, lagiv[w].o1);
+        for (int64_t o = lagiv[w].o0; o < lagiv[w].o1; o++) {
+            const int64_t k = lag_origin_frame(o, stride);
             slot_of[k] = 0;
             slot_of[k + windows[w]] = 0;
         }
@@ -825,15 +768,15 @@ int isf_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_
     if (want_self) {
         entries.reserve(n_entries);
         for (int w = 0; w < W; w++)
-            for (int64_t o = lagiv[w].x; o < lagiv[w].y; o++) {
-                const int64_t k = 1 + stride * o;
+            for (int64_t o = lagiv[w].o0; o < lagiv[w].o1; o++) {
+                const int64_t k = lag_origin_frame(o, stride);
                 entries.push_back(IsfEntry{w, (int32_t)k, slot_of[k], slot_of[k + windows[w]]});
             }
     }
 
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
-    IsfSpans spans(ctx);
+    StageSpans spans(ctx);      // rho table (with the quantisation), correlation, self
     const double *pos_dev = nullptr;
     AMOF_TRY(stage_positions(ctx, t, &pos_dev));
     UploadPack pk;
@@ -849,7 +792,7 @@ int isf_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_
     const int i_slot = pk.add(slot_of.data(), slot_of.size() * sizeof(int32_t));
     const int i_scale2 = pk.add(scale2.data(), scale2.size() * sizeof(double));
     const int i_win = pk.add(windows, (size_t)W * sizeof(int32_t));
-    const int i_iv = pk.add(lagiv.data(), lagiv.size() * sizeof(int2));
+    const int i_iv = pk.add(lagiv.data(), lagiv.size() * sizeof(LagRange));
     const int i_ent = pk.add(entries.data(), entries.size() * sizeof(IsfEntry));
     AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
     void *d_Q = nullptr, *d_rho = nullptr, *d_flag = nullptr, *d_ctr = nullptr;
@@ -965,16 +908,11 @@ int isf_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_
         return fail(ctx, AMOF_EINVAL, "positions lie more than 10^4 cells from the cell, or are not finite");
     }
     if (counts_dev) {
-        auto add = [&](void *dst, const unsigned long long *src, size_t n) -> hipError_t {
-            if (!n) return hipSuccess;
-            hipLaunchKernelGGL(isf_add_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
-                               (unsigned long long *)dst, src, n);
-            return hipGetLastError();
-        };
-        AMOF_HIP_TRY(ctx, add(counts_dev, cnt, n_cnt));
-        AMOF_HIP_TRY(ctx, add(coh_dev, co, n_coh));
-        if (want_self) AMOF_HIP_TRY(ctx, add(self_dev, se, n_self));
-        AMOF_HIP_TRY(ctx, add(beyond_dev, bey, (size_t)W));
+        // (the fixed-point sums are int64: two's complement, the same addition)
+        AMOF_TRY(add_into(ctx, counts_dev, (const uint64_t *)cnt, n_cnt));
+        AMOF_TRY(add_into(ctx, (uint64_t *)coh_dev, (const uint64_t *)co, n_coh));
+        if (want_self) AMOF_TRY(add_into(ctx, (uint64_t *)self_dev, (const uint64_t *)se, n_self));
+        AMOF_TRY(add_into(ctx, beyond_dev, (const uint64_t *)bey, (size_t)W));
     }
     timing_end(ctx);
     if (counts) {

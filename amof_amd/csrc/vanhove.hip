@@ -152,12 +152,6 @@ __global__ __launch_bounds__(MSD_THREADS) void vanhove_reduce_kernel(const doubl
     }
 }
 
-__global__ void vanhove_add_f64_kernel(double *dst, const double *src, int n)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] += src[i];
-}
-
 // host outputs (counts, overflow, moments: overwritten) or device outputs (counts_dev, overflow_dev, moments_dev: added into)
 int vanhove_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W, int32_t unwrap, int32_t remove_com,
                 int64_t atom_begin, int64_t atom_end, double dr, int32_t nbins, const double *com_ext, uint64_t *counts,
@@ -310,11 +304,7 @@ int vanhove_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32
     hipLaunchKernelGGL(vanhove_reduce_kernel, dim3((unsigned)(S * W)), dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_part,
                        n_chunks, n_groups, d_sgf, (int)W, (double *)d_mom);
     AMOF_HIP_TRY(ctx, hipGetLastError());
-    if (moments_dev) {
-        hipLaunchKernelGGL(vanhove_add_f64_kernel, dim3((unsigned)((2 * S * W + 255) / 256)), dim3(256), 0, ctx->stream, moments_dev,
-                           (const double *)d_mom, 2 * S * (int)W);
-        AMOF_HIP_TRY(ctx, hipGetLastError());
-    }
+    if (moments_dev) AMOF_TRY(add_into(ctx, moments_dev, (const double *)d_mom, (size_t)2 * S * W));
     timing_end(ctx);
     if (counts) {
         AMOF_TRY(fetch(ctx, counts, cnt, (size_t)S * W * nbins * sizeof(uint64_t)));

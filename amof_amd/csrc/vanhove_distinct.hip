@@ -212,27 +212,18 @@ __global__ __launch_bounds__(VHD_THREADS) void rdf_distinct_tile_kernel(VhdArgs 
     }
 }
 
-__global__ void vhd_add_kernel(unsigned long long *dst, const unsigned long long *src, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) dst[i] += src[i];
-}
-
 // items of [wb, we) of the lag-major work list, with their lag index
 void vhd_items(const int32_t *windows, int W, int64_t F, int64_t stride, int64_t wb, int64_t we, std::vector<VhdItem> &items,
                std::vector<int32_t> &lag_of)
 {
-    int64_t first = 0;
-    for (int w = 0; w < W; w++) {
-        const int64_t m = windows[w];
-        const int64_t n = F - m - 2 >= 0 ? (F - m - 2) / stride + 1 : 0;      // k = 1 + stride o <= F - m - 1
-        const int64_t o0 = std::max<int64_t>(wb - first, 0), o1 = std::min<int64_t>(we - first, n);
-        for (int64_t o = o0; o < o1; o++) {
-            const int64_t k = 1 + stride * o;
-            items.push_back(VhdItem{(int32_t)k, (int32_t)(k + m), 0, 0});
+    std::vector<LagRange> iv((size_t)W);
+    lag_work_ranges(windows, W, F, stride, wb, we, iv.data());
+    for (int w = 0; w < W; w++)
+        for (int64_t o = iv[w].o0; o < iv[w].o1; o++) {
+            const int64_t k = lag_origin_frame(o, stride);
+            items.push_back(VhdItem{(int32_t)k, (int32_t)(k + windows[w]), 0, 0});
             lag_of.push_back(w);
         }
-        first += n;
-    }
 }
 
 // consecutive items of one lag, at most opc per chunk
@@ -247,16 +238,6 @@ void vhd_chunks(const std::vector<int32_t> &lag_of, size_t i0, size_t i1, int op
     }
 }
 
-int64_t vhd_total(const int32_t *windows, int W, int64_t F, int64_t stride)
-{
-    int64_t total = 0;
-    for (int w = 0; w < W; w++) {
-        const int64_t m = windows[w];
-        total += F - m - 2 >= 0 ? (F - m - 2) / stride + 1 : 0;
-    }
-    return total;
-}
-
 // hist (host, overwritten) or hist_dev (device, added into)
 int vhd_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W, int64_t stride, int64_t wb, int64_t we,
             double rmax, int32_t nbins, uint64_t *hist, uint64_t *hist_dev)
@@ -264,14 +245,11 @@ int vhd_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W
     AMOF_TRY(validate_traj(ctx, t, false));
     const int S = t->n_species;
     const int64_t N = t->n_atoms, F = t->n_frames;
-    if (W < 0 || (W > 0 && !windows)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (stride < 1) return fail(ctx, AMOF_EINVAL, "origin_stride must be >= 1");
+    AMOF_TRY(check_lag_args(ctx, windows, W, F, stride));
     if (!(rmax > 0.0) || !isfinite(rmax)) return fail(ctx, AMOF_EINVAL, "rmax must be positive and finite");
     if (nbins <= 0) return fail(ctx, AMOF_EINVAL, "nbins must be positive");
     if (F > 0x7fffffffLL || N > 0x7fffffffLL) return fail(ctx, AMOF_EINVAL, "too many frames or atoms");
-    for (int w = 0; w < W; w++)
-        if (windows[w] < 0 || windows[w] >= std::max<int64_t>(F, 1)) return fail(ctx, AMOF_EINVAL, "window %d out of range", windows[w]);
-    const int64_t total = vhd_total(windows, W, F, stride);
+    const int64_t total = lag_work_total(windows, W, F, stride);
     if (wb < 0 || we > total || wb > we) return fail(ctx, AMOF_EINVAL, "work range [%lld, %lld) outside [0, %lld)", (long long)wb,
                                                      (long long)we, (long long)total);
     const size_t hsize = (size_t)S * S * W * nbins;
@@ -290,8 +268,6 @@ int vhd_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W
     HostTiles tiles;
     build_tiles(t, VHD_THREADS, tiles);
     const int n_tiles = (int)tiles.tiles.size();
-    std::vector<int64_t> sp_first(S + 1, 0);
-    for (int s = 0; s < S; s++) sp_first[s + 1] = sp_first[s] + tiles.nsp[s];
 
     std::vector<VhdItem> items;
     std::vector<int32_t> lag_of;
@@ -379,7 +355,7 @@ int vhd_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W
         const int i_geom = pk.add(geom.rec.data(), geom.rec.size() * sizeof(double));
         const int i_perm = pk.add(tiles.perm.data(), tiles.perm.size() * sizeof(int32_t));
         const int i_tiles = pk.add(tiles.tiles.data(), tiles.tiles.size() * sizeof(Tile));
-        const int i_spf = pk.add(sp_first.data(), sp_first.size() * sizeof(int64_t));
+        const int i_spf = pk.add(tiles.sp_first.data(), tiles.sp_first.size() * sizeof(int64_t));
         const int i_items = pk.add(items.data(), items.size() * sizeof(VhdItem));
         const int i_chunks = pk.add(chunks.data(), chunks.size() * sizeof(VhdChunk));
         AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
@@ -474,11 +450,7 @@ int vhd_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W
         AMOF_HIP_TRY(ctx, e);
         timing_dom_end(ctx, 1);
     }
-    if (hist_dev) {
-        hipLaunchKernelGGL(vhd_add_kernel, dim3((unsigned)std::min<size_t>((hsize + 255) / 256, 4096)), dim3(256), 0, ctx->stream,
-                           (unsigned long long *)hist_dev, (const unsigned long long *)d_H, hsize);
-        AMOF_HIP_TRY(ctx, hipGetLastError());
-    }
+    if (hist_dev) AMOF_TRY(add_into(ctx, hist_dev, (const uint64_t *)d_H, hsize));
     timing_end(ctx);
     if (hist) AMOF_TRY(fetch(ctx, hist, d_H, hsize * sizeof(uint64_t)));
     // host tables above live on this stack frame: finish before returning

@@ -79,6 +79,18 @@ def all_reduce_sum(x, group=None, device=None):
     return x
 
 
+def all_reduce_counts(x, on_device, merge, device):
+    """The ranks' ONE all-reduce of integer counters, as a numpy u64 array: ``x`` is the CUDA int64 tensor a "_dev" entry
+    point added into (``on_device``: summed in HBM, then read back) or the host array of the plain one (``merge``: through
+    ``all_reduce_sum`` on ``device``; neither: returned as it is)."""
+    if on_device:
+        all_reduce_sum(x)
+        return x.cpu().numpy().view(np.uint64)
+    if merge:
+        return all_reduce_sum(x, device=device)
+    return x
+
+
 def all_reduce_min(value, group=None, device=None):
     d = _dist()
     if d is None:

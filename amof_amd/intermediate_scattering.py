@@ -19,11 +19,9 @@ from ._lazy import Deferred, EmptyUntilComputed
 from . import _hip
 from . import data as _data
 from . import dist as _dist
+from . import lags
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
 from .structure_factor import enumerate_hkl, n_bins, pair_index
-from .vanhove import window_setup
-from .vanhove_distinct import n_origins
 
 logger = logging.getLogger(__name__)
 
@@ -129,7 +127,7 @@ class IntermediateScattering(Deferred):
                 process
         """
         isf = cls()
-        window, time = window_setup(len(trajectory), delta_time, max_time, timestep)
+        window, time = lags.window_setup(len(trajectory), delta_time, max_time, timestep)
         isf.compute_isf(trajectory, window, time, dq, qmax, max_points, seed, origin_stride, self_part, device=device,
                         distributed=distributed)
         return isf
@@ -142,12 +140,8 @@ class IntermediateScattering(Deferred):
         nbins = n_bins(qmax, dq)
         if nbins < 1:
             raise ValueError("qmax // dq gives no bin")
-        if int(origin_stride) != origin_stride or origin_stride < 1:
-            raise ValueError("origin_stride must be an integer >= 1")
-        origin_stride = int(origin_stride)
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
-        if getattr(packed, "is_stream", False):
-            packed = packed.read_all()      # a lag couples frames half a trajectory apart: nothing to stream
+        origin_stride = lags.check_origin_stride(origin_stride)
+        packed = lags.pack(trajectory, device)
         if not all(bool(x) for x in packed.pbc):
             raise ValueError("F(q, t) needs a cell periodic on all three axes")
         window = np.asarray(window, dtype=np.int32)
@@ -159,36 +153,30 @@ class IntermediateScattering(Deferred):
         cells = packed.cell if packed.cell.shape[0] == 1 else packed.cell[frames]
         hkl = enumerate_hkl(cells, qmax, dq=dq, max_points=max_points, seed=seed)
         elements = packed.unique_numbers()
-        n_orig = n_origins(F, window, origin_stride)
+        n_orig = lags.n_origins(F, window, origin_stride)
         total = int(n_orig.sum())
         logger.info("Start computing F(q, t) at %s times, %s vectors, %s bins, %s (lag, origin) pairs", len(window), len(hkl),
                     nbins, total)
 
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        work = _dist.shard_range(total, rank, world) if merge else (0, total)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 0)
-        on_device = merge and _dist.device_collectives()
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
+        st = lags.setup(packed, device, distributed)
+        ctx, merge = st.ctx, st.merge
+        work = _dist.shard_range(total, st.rank, st.world) if merge else (0, total)
         S = len(_hip.packed_species(packed)[0])
         W = len(window)
         lay = _hip.isf_layout(S, W, nbins, self_part)
 
         def local():
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
-            if getattr(source, "is_stream", False):
-                source.read_all()
+            lags.begin_local(st.source)
+            flat = None
+            if merge:
+                # integer fixed-point sums: the ranks' shares add up exactly, whatever the split.  Counts, beyond, coh
+                # and self in ONE int64 tensor: one all-reduce
+                import torch
+                flat = torch.zeros(lay["size"], dtype=torch.int64, device=torch.device("cuda", ctx.device))
             try:
-                if merge:
-                    # integer fixed-point sums: the ranks' shares add up exactly, whatever the split.  Counts, beyond, coh
-                    # and self in ONE int64 tensor: one all-reduce
-                    import torch
-                    flat = torch.zeros(lay["size"], dtype=torch.int64, device=torch.device("cuda", ctx.device))
-                    return ctx.isf_accumulate(packed, hkl, window, dq, nbins, origin_stride=origin_stride, work_range=work,
-                                              self_part=self_part, out=flat)
                 return ctx.isf_accumulate(packed, hkl, window, dq, nbins, origin_stride=origin_stride, work_range=work,
-                                          self_part=self_part)
+                                          self_part=self_part, out=flat)
             except _hip.AmofError as e:
                 if e.code != _hip.AMOF_ECAPACITY:
                     raise
@@ -199,7 +187,7 @@ class IntermediateScattering(Deferred):
         def finish(raw):
             if merge:
                 flat, scale, kinds = raw
-                if on_device:
+                if st.on_device:
                     _dist.all_reduce_sum(flat)          # (in HBM)
                     flat = flat.cpu().numpy()
                 else:

@@ -1,0 +1,93 @@
+"""The lag/origin family's shared host side: ``DistinctVanHove``, ``IntermediateScattering``, ``BondLifetime`` (and the
+windows of ``WindowVanHove``).
+
+Lags m are the windows of ``WindowMsd``; the origins of lag m are the frames k = 1, 1 + s, 1 + 2s, ... <= F - m - 1 (s =
+``origin_stride``).  The work list is every (lag, origin) pair, lag-major, origins ascending; ranks and devices take
+contiguous index ranges of it.  The library states the same rule once, in amof_amd/csrc/lag_work.h ("The
+lag/origin family: shared pieces"); tests/test_lag_work_cpu.py holds the two against each other.
+"""
+
+import collections
+import logging
+
+import numpy as np
+
+from . import _hip
+from . import dist as _dist
+from .frames import pack_trajectory, resident_source
+
+logger = logging.getLogger(__name__)
+
+
+def window_setup(n_frames, delta_time=100, max_time="half", timestep=1):
+    """windows (frames) and times (fs) of ``WindowMsd.from_trajectory`` (amof/msd.py:173-181)"""
+    half_time = (n_frames // 2) * timestep
+    if (isinstance(max_time, str) and max_time == "half") or max_time > half_time:
+        max_time = half_time
+    if delta_time < timestep:
+        logger.exception("Delta_time should be larger than timestep")
+    delta_m = delta_time // timestep
+    window = np.arange(0, max_time // timestep, delta_m)
+    return window, timestep * window
+
+
+def check_origin_stride(x):
+    """``origin_stride`` as an int; ValueError unless it is an integer >= 1"""
+    if int(x) != x or x < 1:
+        raise ValueError("origin_stride must be an integer >= 1")
+    return int(x)
+
+
+def origins(n_frames, lag, origin_stride=1):
+    """origin frames k = 1, 1 + s, 1 + 2s, ... <= F - m - 1 of lag m (s = 1: ``WindowVanHove``'s origins)"""
+    return np.arange(1, max(int(n_frames) - int(lag), 1), int(origin_stride), dtype=np.int64)
+
+
+def n_origins(n_frames, windows, origin_stride=1):
+    """``[W]`` number of origins of every lag (the library's n_w = floor((F - m - 2) / s) + 1, 0 for m > F - 2)"""
+    m = np.asarray(windows, dtype=np.int64)
+    return np.where(n_frames - m - 2 >= 0, (n_frames - m - 2) // int(origin_stride) + 1, 0).astype(np.int64)
+
+
+def total_work(n_frames, windows, origin_stride=1):
+    """length of the work list"""
+    return int(n_origins(n_frames, windows, origin_stride).sum())
+
+
+def work_list(n_frames, windows, origin_stride=1):
+    """``(lag index, origin)`` arrays of the flattened work list in the library's order: lag-major, origins ascending"""
+    w = [np.full(len(origins(n_frames, m, origin_stride)), i, dtype=np.int64) for i, m in enumerate(windows)]
+    k = [origins(n_frames, m, origin_stride) for m in windows]
+    return (np.concatenate(w) if w else np.zeros(0, np.int64)), (np.concatenate(k) if k else np.zeros(0, np.int64))
+
+
+Setup = collections.namedtuple("Setup", "packed rank world merge ctx on_device source")
+
+
+def pack(trajectory, device):
+    """the packed trajectory, a stream fully read (a lag couples frames half a trajectory apart: nothing to stream)"""
+    packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
+    if getattr(packed, "is_stream", False):
+        packed = packed.read_all()
+    return packed
+
+
+def setup(trajectory, device, distributed, lane=0):
+    """What every class of the family decides before it shards its work: the packed trajectory (``pack``; one packed
+    already -- a class that has checked its arguments against it, which needs no GPU -- passes through), this process's
+    rank and world, whether the ranks merge, the lane's context (created here), whether the merge stays in HBM, and
+    the source ``begin_local`` makes resident."""
+    packed = pack(trajectory, device)
+    rank, world = (0, 1) if distributed is False else _dist.world()
+    merge = distributed is not False and _dist.merging(world)
+    dev = device if device is not None else getattr(packed, "device_index", None)
+    ctx = _hip.lane_context(dev, lane)
+    on_device = merge and _dist.device_collectives()
+    source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
+    return Setup(packed, rank, world, merge, ctx, on_device, source)
+
+
+def begin_local(source):
+    """first thing of a ``local()`` (the lane job of amof_amd/_lazy.py): the frames are there before the kernels start"""
+    if getattr(source, "is_stream", False):
+        source.read_all()

@@ -19,20 +19,9 @@ from . import data as _data
 from . import dist as _dist
 from .files import path as _path
 from .frames import pack_trajectory, resident_source
+from .lags import window_setup      # (defined there for the whole family; callers also find it here)
 
 logger = logging.getLogger(__name__)
-
-
-def window_setup(n_frames, delta_time=100, max_time="half", timestep=1):
-    """windows (frames) and times (fs) of ``WindowMsd.from_trajectory`` (amof/msd.py:173-181)"""
-    half_time = (n_frames // 2) * timestep
-    if (isinstance(max_time, str) and max_time == "half") or max_time > half_time:
-        max_time = half_time
-    if delta_time < timestep:
-        logger.exception("Delta_time should be larger than timestep")
-    delta_m = delta_time // timestep
-    window = np.arange(0, max_time // timestep, delta_m)
-    return window, timestep * window
 
 
 def assemble(counts, overflow, moments, kinds, elements, species_counts, n_frames, window, time, dr):

@@ -17,30 +17,13 @@ from ._lazy import Deferred, EmptyUntilComputed
 from . import _hip
 from . import data as _data
 from . import dist as _dist
+from . import lags
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
+# (the origin bookkeeping is defined in lags.py for the whole family; callers also find it here)
+from .lags import n_origins, origins, window_setup, work_list      # noqa: F401
 from .rdf import normalize_rdf
-from .vanhove import window_setup
 
 logger = logging.getLogger(__name__)
-
-
-def origins(n_frames, lag, origin_stride=1):
-    """origin frames k = 1, 1 + s, 1 + 2s, ... <= F - m - 1 of lag m (s = 1: ``WindowVanHove``'s origins)"""
-    return np.arange(1, max(int(n_frames) - int(lag), 1), int(origin_stride), dtype=np.int64)
-
-
-def n_origins(n_frames, windows, origin_stride=1):
-    """``[W]`` number of origins of every lag (the library's n_w = floor((F - m - 2) / s) + 1, 0 for m > F - 2)"""
-    m = np.asarray(windows, dtype=np.int64)
-    return np.where(n_frames - m - 2 >= 0, (n_frames - m - 2) // int(origin_stride) + 1, 0).astype(np.int64)
-
-
-def work_list(n_frames, windows, origin_stride=1):
-    """``(lag index, origin)`` arrays of the flattened work list in the library's order: lag-major, origins ascending"""
-    w = [np.full(len(origins(n_frames, m, origin_stride)), i, dtype=np.int64) for i, m in enumerate(windows)]
-    k = [origins(n_frames, m, origin_stride) for m in windows]
-    return (np.concatenate(w) if w else np.zeros(0, np.int64)), (np.concatenate(k) if k else np.zeros(0, np.int64))
 
 
 def clamp_rmax(cell_lengths, rmax):
@@ -146,54 +129,40 @@ class DistinctVanHove(Deferred):
         dr = float(dr)
         if not dr > 0:
             raise ValueError("dr must be positive")
-        if int(origin_stride) != origin_stride or origin_stride < 1:
-            raise ValueError("origin_stride must be an integer >= 1")
-        origin_stride = int(origin_stride)
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
-        if getattr(packed, "is_stream", False):
-            packed = packed.read_all()      # a lag couples frames half a trajectory apart: nothing to stream
+        origin_stride = lags.check_origin_stride(origin_stride)
+        packed = lags.pack(trajectory, device)
         rmax = clamp_rmax(packed.cell_lengths(), rmax)
         nbins = int(rmax // dr)             # Python float floor-division, as Rdf
         if nbins <= 0:
             raise ValueError("rmax // dr gives no bin")
         window = np.asarray(window, dtype=np.int32)
         elements = packed.unique_numbers()
-        F = len(packed)
-        n_orig = n_origins(F, window, origin_stride)
+        n_orig = n_origins(len(packed), window, origin_stride)
         total = int(n_orig.sum())
         logger.info("Start computing the distinct Van Hove function at %s times, %s bins, %s (lag, origin) pairs", len(window),
                     nbins, total)
 
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        work = _dist.shard_range(total, rank, world) if merge else (0, total)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 0)
-        on_device = merge and _dist.device_collectives()
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
+        st = lags.setup(packed, device, distributed)
+        ctx, merge = st.ctx, st.merge
+        work = _dist.shard_range(total, st.rank, st.world) if merge else (0, total)
         S = len(_hip.packed_species(packed)[0])
         W = len(window)
 
         def local():
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
-            if getattr(source, "is_stream", False):
-                source.read_all()
-            if on_device:
+            lags.begin_local(st.source)
+            out = None
+            if st.on_device:
                 # the counts stay in HBM from the kernels through the RCCL all-reduce (amof_vanhove_distinct_dev)
                 import torch
                 out = torch.zeros((S, S, W, nbins), dtype=torch.int64, device=torch.device("cuda", ctx.device))
-                return ctx.vanhove_distinct(packed, window, rmax, nbins, origin_stride=origin_stride, work_range=work, out=out)
-            return ctx.vanhove_distinct(packed, window, rmax, nbins, origin_stride=origin_stride, work_range=work)
+            return ctx.vanhove_distinct(packed, window, rmax, nbins, origin_stride=origin_stride, work_range=work, out=out)
 
         def finish(raw):
             # the ranks' merge (the calling thread: collectives in program order): ONE all-reduce of the integer counts;
             # the volumes come from the host's cells, so no float reduction is needed
             hist, kinds = raw
-            if on_device:
-                _dist.all_reduce_sum(hist)
-                hist = hist.cpu().numpy().view(np.uint64)
-            elif merge:
-                hist = _dist.all_reduce_sum(hist, device=ctx.device)
+            hist = _dist.all_reduce_counts(hist, st.on_device, merge, ctx.device)
             self._assemble(hist, kinds, packed, elements, n_orig, window, time, rmax, nbins, dr, origin_stride)
 
         self._defer(ctx, local, finish, collective=merge)

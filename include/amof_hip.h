@@ -334,7 +334,7 @@ int amof_vanhove_distinct_dev(amof_ctx *ctx, const amof_traj *traj, const int32_
  *   frame f -- amof_cn_count's decision for that frame, pair and cutoff: strict sqrt(d2) < rc on the canonical minimum
  *   image in frame f's cell and pbc.  For h to be 0 or 1, a cutoff of a set above half the smallest
  *   perpendicular cell height over all frames on a periodic axis is refused (AMOF_EINVAL).
- *   Lags m = windows[w] (0 <= m < F), origins k = 1, 1 + s, ... <= F - m - 1 (s = origin_stride >= 1): amof_vanhove_distinct's.
+ *   Lags m = windows[w] and their origins (s = origin_stride >= 1): amof_vanhove_distinct's (stated there).
  *   Per set s and lag w, summed over the lag's origins k and the ordered pairs (i, j) with atom_begin <= i < atom_end:
  *     counts[(s*W + w)*3 + 0] = sum h_ij(k)                              bonds present at the origins
  *     counts[(s*W + w)*3 + 1] = sum h_ij(k) h_ij(k + m)                  intermittent: bonded at both ends
@@ -405,9 +405,8 @@ int amof_sq_modes(amof_ctx *ctx, const amof_traj *traj, int64_t frame, const int
  * Intermediate scattering function F(q, t): the time correlation of rho_a(k) on reciprocal-lattice vectors, coherent and self.
  * Replaces nothing the reference computes (the reference has no dynamic analysis in reciprocal space).  Cells must be
  * periodic on all three axes.  recip, hkl (half a space, no (0, 0, 0)), dq, nbins: as amof_sq_accumulate.
- *   Work list: amof_vanhove_distinct's -- lags m = windows[w] (0 <= m < F), origins k = 1, 1 + s, ... <= F - m - 1
- *   (s = origin_stride >= 1), every (w, k) in lag-major order, n_w = floor((F - m - 2) / s) + 1 entries for lag w (0 if
- *   m > F - 2).  A call handles the entries [work_begin, work_end): ranges of one trajectory add up bit for bit.
+ *   Lags, origins and work list: amof_vanhove_distinct's (stated there).  A call handles the entries
+ *   [work_begin, work_end): ranges of one trajectory add up bit for bit.
  *   rho_a(f; hkl) is what amof_sq_modes returns for frame f and that vector, bit for bit (the same kernel and atom order;
  *   it does not depend on how the vectors are grouped into runs or chunks).
  *   For every entry (w, k) and every vector: the bin b from frame k's (the ORIGIN's) reciprocal matrix in

@@ -28,7 +28,7 @@ def main():
     import torch
     from amof_amd import _hip
     from amof_amd import atom as amatom
-    from amof_amd.vanhove import window_setup
+    from amof_amd.lags import window_setup
     from tests import helpers as H
 
     frames = int(os.environ.get("BOND_TIMING_FRAMES", "5000"))

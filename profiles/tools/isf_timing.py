@@ -24,8 +24,7 @@ def main():
     import torch
     from amof_amd import _hip
     from amof_amd import structure_factor as sf
-    from amof_amd.vanhove import window_setup
-    from amof_amd.vanhove_distinct import n_origins
+    from amof_amd.lags import n_origins, window_setup
     from tests import helpers as H
 
     F = args.frames

@@ -18,7 +18,7 @@ os.environ.setdefault("AMOF_ASYNC", "0")
 import torch                                                # noqa: E402
 from amof_amd import _hip                                   # noqa: E402
 from amof_amd import vanhove_distinct as vd                 # noqa: E402
-from amof_amd.vanhove import window_setup                   # noqa: E402
+from amof_amd.lags import n_origins, window_setup           # noqa: E402
 from tests import helpers as H                              # noqa: E402
 
 F = int(sys.argv[1]) if len(sys.argv) > 1 else 5000
@@ -32,7 +32,7 @@ rmax = float(np.min(packed.cell_lengths()) / 2)
 nbins = int(rmax // 0.01)
 windows, _ = window_setup(F, 100)
 windows = windows.astype(np.int32)
-items = int(vd.n_origins(F, windows, stride).sum())
+items = int(n_origins(F, windows, stride).sum())
 rec = {"atoms": packed.n_atoms, "frames": F, "lags": len(windows), "origin_stride": stride, "nbins": nbins, "pairs": items,
        "calls": []}
 

@@ -10,7 +10,7 @@ import pytest
 from amof_amd import _hip
 from amof_amd import bond_lifetime as bl
 from amof_amd.frames import PackedTrajectory
-from amof_amd.vanhove_distinct import n_origins
+from amof_amd.lags import n_origins
 from tests import bond_ref as ref
 from tests import helpers as H
 from tests.conftest import ROOT

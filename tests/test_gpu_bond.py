@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from amof_amd.frames import PackedTrajectory
-from amof_amd.vanhove import window_setup
+from amof_amd.lags import window_setup
 from tests import bond_ref as ref
 from tests import edge_plant as E
 from tests import helpers as H
@@ -205,6 +205,17 @@ def test_tie_to_cn_atom_ranges_and_dev(hip_ctx):
     # scratch left by one call means nothing to the next
     hip_ctx.debug_poison(0xA5)
     assert np.array_equal(hip_ctx.bond_survival(packed, rcm, sets, windows, origin_stride=4), full)
+
+
+def test_stage_seconds_after_a_call_and_after_one_without_sets(hip_ctx):
+    packed = _walk(DIAG, _numbers4(64), 10, 23)
+    rcm, sets = _abi(packed, [(30, 7, 3.0)])
+    assert hip_ctx.bond_survival(packed, rcm, sets, [0, 1]).sum() > 0
+    stages = hip_ctx.last_stage_seconds()
+    assert sorted(stages) == ["corr", "rho", "self"] and all(v >= 0 for v in stages.values())      # lists, series, correlations
+    # without a set the call returns before it starts device work: the record of the call before it stays as it was
+    assert hip_ctx.bond_survival(packed, rcm, [], [0, 1]).shape == (0, 2, 3)
+    assert hip_ctx.last_stage_seconds() == stages
 
 
 def test_abi_refuses_cutoff_above_half_height_and_bad_arguments(hip_ctx):

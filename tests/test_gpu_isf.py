@@ -270,6 +270,37 @@ def test_invariances_bit_for_bit(hip_ctx):
     assert np.array_equal(whole["counts"].view(np.uint64), host[0]) and np.array_equal(whole["beyond"].view(np.uint64), host[3])
 
 
+@pytest.mark.parametrize("F", [11, 12])
+def test_work_list_cut_at_lag_boundaries(hip_ctx, F):
+    """three species, 71 atoms, lags [0, 2, 5], every second origin (F = 11: 5, 4 and 3 origins per lag; F = 12: 6, 5 and
+    3): the work list cut exactly on the first lag boundary, an empty piece there (it must add nothing to the device
+    tensor), a cut inside the second lag, the rest -- added into one tensor, equal to the single full call bit for bit"""
+    from amof_amd import lags
+    windows, stride, dq, qmax = [0, 2, 5], 2, 0.1, 1.3
+    numbers = np.repeat([1, 6, 30], [31, 24, 16])
+    gas = H.random_gas(len(numbers), [11.3, 12.1, 13.7], numbers, 51)
+    packed = H.random_walk(Frame(numbers, gas.pos[0], gas.cell[0], (True, True, True)), F, 0.2, 52, ortho=True)
+    hkl = sf.enumerate_hkl(packed.cell, qmax)
+    assert 24 <= len(hkl) <= 60
+    nbins = sf.n_bins(qmax, dq)
+    n = lags.n_origins(F, windows, stride)
+    total = int(n.sum())
+    cuts = [(0, int(n[0])), (int(n[0]), int(n[0])), (int(n[0]), int(n[0]) + 2), (int(n[0]) + 2, total)]
+    if F == 11:
+        assert n.tolist() == [5, 4, 3] and cuts == [(0, 5), (5, 5), (5, 7), (7, 12)]
+    whole, scale, _ = _dev_call(hip_ctx, packed, hkl, windows, dq, nbins, origin_stride=stride)
+    assert whole["counts"].sum() > 0 and np.abs(whole["coh"]).sum() > 0 and np.abs(whole["self"]).sum() > 0
+    flat, snap = None, []
+    for c in cuts:
+        pieces, scale_c, flat = _dev_call(hip_ctx, packed, hkl, windows, dq, nbins, flat=flat, origin_stride=stride, work_range=c)
+        assert np.array_equal(scale_c, scale)
+        snap.append(flat.cpu().numpy().copy())
+    assert np.array_equal(snap[1], snap[0]) and not np.array_equal(snap[2], snap[1])        # the empty piece added nothing
+    assert pieces["counts"][1:].sum() > 0 and snap[0].reshape(-1)[nbins:3 * nbins].sum() == 0   # piece 0 ends with lag 0
+    for k in whole:
+        assert np.array_equal(whole[k], pieces[k]), k
+
+
 def test_more_bins_than_the_lds_budget_take_global_counters(hip_ctx):
     packed = H.random_walk(H.zif4_frame(), 6, 0.05, 38)
     hkl = sf.enumerate_hkl(packed.cell, 2.4)

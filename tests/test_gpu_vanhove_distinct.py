@@ -7,9 +7,10 @@ import sys
 import numpy as np
 import pytest
 
+from amof_amd import lags
 from amof_amd import vanhove_distinct as vd
-from amof_amd.frames import PackedTrajectory
-from amof_amd.vanhove import window_setup
+from amof_amd.frames import Frame, PackedTrajectory
+from amof_amd.lags import window_setup
 from tests import edge_plant as E
 from tests import helpers as H
 from tests import vanhove_distinct_ref as ref
@@ -85,7 +86,7 @@ def test_rectangular_cell_all_paths(hip_ctx, S):
     F = 14
     packed = _walk(DIAG, numbers, F, seed=10 + S)
     windows, _ = window_setup(F, 2)
-    wl, kl = vd.work_list(F, windows)
+    wl, kl = lags.work_list(F, windows)
     assert (len(windows) - 1, F - windows[-1] - 1) in set(zip(wl.tolist(), kl.tolist()))
     rmax, nbins = 8.6, 430
     _case(hip_ctx, packed, windows, rmax, nbins, [({}, "rdf_distinct_tile"), (EXACT, "rdf_distinct_exact"),
@@ -150,7 +151,7 @@ def test_guard_band_across_frames(hip_ctx, nbins):
 def test_work_halves_add_up_and_calls_are_deterministic(hip_ctx):
     packed = _walk(DIAG, _numbers4(517), 16, seed=31)
     windows, _ = window_setup(16, 3)
-    n = int(vd.n_origins(16, windows, 2).sum())
+    n = int(lags.n_origins(16, windows, 2).sum())
     for env, path in (({}, "rdf_distinct_tile"), (EXACT, "rdf_distinct_exact")):
         with _env(**env):
             whole, _ = hip_ctx.vanhove_distinct(packed, windows, 8.0, 800, origin_stride=2)
@@ -175,6 +176,44 @@ def test_work_halves_add_up_and_calls_are_deterministic(hip_ctx):
     finally:
         multi.close()
     assert np.array_equal(m, whole)
+
+
+def _lag_cuts(F, windows, stride):
+    """the work list cut exactly on the first lag boundary, an empty piece there, a cut inside the second lag, the rest"""
+    n = lags.n_origins(F, windows, stride)
+    total = int(n.sum())
+    assert len(n) == 3 and n[1] > 2
+    return [(0, int(n[0])), (int(n[0]), int(n[0])), (int(n[0]), int(n[0]) + 2), (int(n[0]) + 2, total)], total
+
+
+@pytest.mark.parametrize("F", [11, 12])
+@pytest.mark.parametrize("exact", [False, True])
+def test_work_list_cut_at_lag_boundaries(hip_ctx, monkeypatch, F, exact):
+    """three species, 71 atoms, lags [0, 2, 5], every second origin: F = 11 has 5, 4 and 3 origins per lag, F = 12 has 6, 5
+    and 3.  The pieces -- into host arrays (zeroed by every call) and into one device tensor (added into) -- sum to the
+    single full call bit for bit."""
+    import torch
+    windows, stride, rmax, nbins = np.array([0, 2, 5], dtype=np.int32), 2, 5.0, 40
+    numbers = np.repeat([1, 6, 30], [31, 24, 16])
+    gas = H.random_gas(len(numbers), [11.3, 12.1, 13.7], numbers, 51)
+    packed = H.random_walk(Frame(numbers, gas.pos[0], gas.cell[0], (True, True, True)), F, 0.2, 52, ortho=True)
+    cuts, total = _lag_cuts(F, windows, stride)
+    if F == 11:
+        assert lags.n_origins(F, windows, stride).tolist() == [5, 4, 3] and cuts == [(0, 5), (5, 5), (5, 7), (7, 12)]
+    if exact:
+        monkeypatch.setenv("AMOF_VANHOVE_DISTINCT_EXACT", "1")      # (read per call)
+    whole, _ = hip_ctx.vanhove_distinct(packed, windows, rmax, nbins, origin_stride=stride)
+    assert hip_ctx.last_path() == ("rdf_distinct_exact" if exact else "rdf_distinct_tile")
+    assert whole.sum() > 0 and whole.shape == (3, 3, 3, nbins)
+    assert np.array_equal(whole, hip_ctx.vanhove_distinct(packed, windows, rmax, nbins, origin_stride=stride, work_range=(0, total))[0])
+    parts = [hip_ctx.vanhove_distinct(packed, windows, rmax, nbins, origin_stride=stride, work_range=c)[0] for c in cuts]
+    assert parts[1].sum() == 0 and all(parts[k].sum() > 0 for k in (0, 2, 3))
+    assert parts[0][:, :, 1:].sum() == 0 and parts[2][:, :, 0].sum() == 0      # the cut sits exactly on the lag boundary
+    assert np.array_equal(sum(parts), whole)
+    out = torch.zeros(whole.shape, dtype=torch.int64, device="cuda:0")
+    for c in cuts:
+        hip_ctx.vanhove_distinct(packed, windows, rmax, nbins, origin_stride=stride, work_range=c, out=out)
+    assert np.array_equal(out.cpu().numpy().view(np.uint64), whole)
 
 
 def test_lag0_ties_to_the_rdf_at_the_headline_geometry(hip_ctx):

@@ -8,10 +8,11 @@ import numpy as np
 import pytest
 
 from amof_amd import dist
+from amof_amd import lags
 from amof_amd import vanhove_distinct as vd
 from amof_amd.frames import PackedTrajectory
+from amof_amd.lags import window_setup
 from amof_amd.rdf import Rdf
-from amof_amd.vanhove import window_setup
 from tests import vanhove_distinct_ref as ref
 
 
@@ -19,29 +20,29 @@ def test_origins_and_counts_per_lag():
     F = 11
     windows = [0, 1, 4, 9, 10]
     for s in (1, 2, 3, 7):
-        n = vd.n_origins(F, windows, s)
+        n = lags.n_origins(F, windows, s)
         for w, m in enumerate(windows):
             want = [k for k in range(1, F) if k <= F - m - 1 and (k - 1) % s == 0]
-            assert list(vd.origins(F, m, s)) == want
+            assert list(lags.origins(F, m, s)) == want
             assert n[w] == len(want)
-    assert vd.n_origins(F, [10], 1)[0] == 0 and vd.n_origins(F, [9], 1)[0] == 1
+    assert lags.n_origins(F, [10], 1)[0] == 0 and lags.n_origins(F, [9], 1)[0] == 1
     # stride 1: WindowVanHove's origins k = 1 .. F - m - 1
-    assert list(vd.n_origins(F, windows)) == [F - m - 1 for m in windows]
+    assert list(lags.n_origins(F, windows)) == [F - m - 1 for m in windows]
 
 
 @pytest.mark.parametrize("world", [1, 2, 3, 5, 8])
 def test_work_shards_cover_every_pair_once(world):
     F = 23
     windows, _ = window_setup(F, 3)
-    wl, kl = vd.work_list(F, windows, 2)
-    assert len(wl) == vd.n_origins(F, windows, 2).sum()
+    wl, kl = lags.work_list(F, windows, 2)
+    assert len(wl) == lags.n_origins(F, windows, 2).sum()
     assert np.all(np.diff(wl) >= 0)                                    # lag-major
     seen = []
     for r in range(world):
         lo, hi = dist.shard_range(len(wl), r, world)
         seen += list(zip(wl[lo:hi], kl[lo:hi]))
     assert len(seen) == len(set(seen)) == len(wl)
-    assert set(seen) == {(w, k) for w, m in enumerate(windows) for k in vd.origins(F, m, 2)}
+    assert set(seen) == {(w, k) for w, m in enumerate(windows) for k in lags.origins(F, m, 2)}
 
 
 def test_rmax_clamp_and_bins():
@@ -71,7 +72,7 @@ def test_assembly_at_t0_equals_rdf_and_schema():
     rmax = 5.0
     rng = np.random.default_rng(1)
     hist = rng.integers(0, 1000, (S, S, W, nbins)).astype(np.uint64)
-    n_orig = vd.n_origins(F, windows)
+    n_orig = lags.n_origins(F, windows)
     vol = vd.mean_volumes(packed.cell, F, windows)
     elements = packed.unique_numbers()
     df = vd.assemble(hist, kinds, elements, packed.species_counts(), N, n_orig, vol, time, rmax, nbins, 0.12)
@@ -91,7 +92,7 @@ def test_assembly_at_t0_equals_rdf_and_schema():
     w = W - 1
     a, b = kinds.index(30), kinds.index(7)
     from amof_amd.rdf import normalize_rdf
-    k = vd.origins(F, windows[w])
+    k = lags.origins(F, windows[w])
     want = normalize_rdf(hist[a, b, w], len(k) * 5, N, np.mean(packed.volumes()[k]), rmax, nbins)
     np.testing.assert_allclose(df["Zn-N"].values[w * nbins:], want, rtol=1e-14)
     # a lag without origins: NaN volume, rows still there
@@ -104,13 +105,13 @@ def test_feather_round_trip(tmp_path):
     kinds = sorted(set(int(z) for z in packed.numbers))
     hist = np.ones((len(kinds), len(kinds), len(windows), 30), dtype=np.uint64)
     vh = vd.DistinctVanHove()
-    vh._assemble(hist, kinds, packed, packed.unique_numbers(), vd.n_origins(len(packed), windows), windows, time, 4.0, 30, 0.13, 1)
+    vh._assemble(hist, kinds, packed, packed.unique_numbers(), lags.n_origins(len(packed), windows), windows, time, 4.0, 30, 0.13, 1)
     p = os.path.join(str(tmp_path), "gd")
     vh.write_to_file(p)
     assert os.path.exists(p + ".vanhove_distinct")
     back = vd.DistinctVanHove.from_file(p)
     assert back.data.equals(vh.data)
-    assert list(vh.n_origins) == list(vd.n_origins(len(packed), windows)) and vh.rmax == 4.0 and vh.kinds == kinds
+    assert list(vh.n_origins) == list(lags.n_origins(len(packed), windows)) and vh.rmax == 4.0 and vh.kinds == kinds
 
 
 @pytest.mark.parametrize("kw", [dict(origin_stride=0), dict(origin_stride=-2), dict(origin_stride=1.5), dict(dr=0.0),
@@ -136,7 +137,7 @@ def test_reference_construction_equals_a_numpy_double_loop(stride):
         rdf, _ = clib.rdf_hist(packed.pos[1:], packed.cell[1:], sp, len(kinds), rmax, nbins)
         assert np.array_equal(got[:, :, 0], rdf)
     # a work range is a slice of the whole
-    n = int(vd.n_origins(len(packed), windows, stride).sum())
+    n = int(lags.n_origins(len(packed), windows, stride).sum())
     a = ref.distinct_hist(packed.pos, packed.cell, packed.numbers, windows, rmax, nbins, stride, work_range=(0, n // 2))
     b = ref.distinct_hist(packed.pos, packed.cell, packed.numbers, windows, rmax, nbins, stride, work_range=(n // 2, n))
     assert np.array_equal(a + b, got)

@@ -9,6 +9,7 @@ import pandas as pd
 import pytest
 
 from amof_amd import _hip
+from amof_amd import lags
 from amof_amd import vanhove as vh
 from amof_amd.frames import PackedTrajectory
 from oracle import numpy_oracle as no
@@ -45,10 +46,10 @@ def test_restatement_second_moment_is_the_window_msd(unwrap):
 def test_windows_follow_window_msd():
     for F, kw in [(5000, dict(delta_time=100)), (37, dict(delta_time=4, timestep=2)), (100, dict(delta_time=5, max_time=30)),
                   (9, dict(delta_time=1, max_time=1000))]:
-        w, t = vh.window_setup(F, **kw)
+        w, t = lags.window_setup(F, **kw)
         w_ref, t_ref = no.msd_window_setup(F, **kw)
         assert np.array_equal(w, w_ref) and np.array_equal(t, t_ref)
-    assert len(vh.window_setup(5000)[0]) == 25
+    assert len(lags.window_setup(5000)[0]) == 25
 
 
 def _synthetic(seed=1, W=4, nbins=50, dr=0.1):

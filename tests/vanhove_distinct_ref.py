@@ -4,11 +4,11 @@ Built on the C oracle's RDF (``oracle.clib.rdf_hist``) alone: frame k and frame 
 frame k's cell and pbc, the second copy's species shifted by S.  The oracle's cross partial [a][S + b] then holds every pair
 (i at k, j at k + m) through the canonical arithmetic, every image in reach included, and the atom's own pairs (i, i) too.
 Those are taken back exactly with a batch of 2-atom frames (r_i(k), r_i(k + m)) through the same oracle.  Lag-major over
-the work list of ``amof_amd.vanhove_distinct.work_list``; ``work_range`` selects entries of it."""
+the work list of ``amof_amd.lags.work_list``; ``work_range`` selects entries of it."""
 
 import numpy as np
 
-from amof_amd.vanhove_distinct import work_list
+from amof_amd.lags import work_list
 from oracle import clib
 
 
