@@ -36,7 +36,7 @@ EXPORTS = [
     "amof_bad_hist_by_cn",
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
-    "amof_bond_survival", "amof_bond_survival_dev",
+    "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
@@ -140,6 +140,8 @@ def load_library():
         lib.amof_bond_survival.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_int64, P]
         lib.amof_bond_survival_dev.argtypes = lib.amof_bond_survival.argtypes
+        lib.amof_bond_reorientation.argtypes = lib.amof_bond_survival.argtypes + [P]
+        lib.amof_bond_reorientation_dev.argtypes = lib.amof_bond_reorientation.argtypes
         lib.amof_sq_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_double, ctypes.c_int32, P, P, P]
         lib.amof_sq_accumulate_dev.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -729,6 +731,34 @@ class Context(Lane):
         return counts
 
     @_locked
+    def bond_reorientation(self, packed, cutoff, sets, windows, origin_stride=1, atom_range=None, out=None):
+        """``(out [n_sets][W][3] int64, scale_log2 [n_sets] int32)`` of ``amof_bond_reorientation``: per set (A, B) and lag,
+        the pairs bonded at the origin and at origin + lag, and the sums over them of ``rint(P1 2^e)`` and ``rint(P2 2^e)`` of
+        the cosine between the pair's vectors at both ends, for the centres ``atom_range`` (default: all); e =
+        ``scale_log2[set]``.  ``cutoff``, ``sets``: as ``cn_count``.  A zero-length vector raises ``ZeroDivisionError``.
+
+        ``out``: optional torch CUDA int64 tensor ``[n_sets][W][3]`` the sums are ADDED into on the device (stays resident
+        for an RCCL merge)."""
+        th = self._traj(packed)
+        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64).reshape(th.S, th.S)
+        sets = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 2)
+        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        a0, a1 = (0, th.n_atoms) if atom_range is None else atom_range
+        scale = np.zeros(len(sets), dtype=np.int32)
+        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data), ctypes.c_void_p(sets.ctypes.data), len(sets),
+                ctypes.c_void_p(windows.ctypes.data), len(windows), int(origin_stride), int(a0), int(a1))
+        if out is not None:
+            self._check_out(out, len(sets) * len(windows) * 3)
+            self._order_after_torch()
+            self._check(self._lib.amof_bond_reorientation_dev(*(args + (ctypes.c_void_p(out.data_ptr()),
+                                                                        ctypes.c_void_p(scale.ctypes.data)))))
+            return out, scale
+        sums = np.zeros((len(sets), len(windows), 3), dtype=np.int64)
+        self._check(self._lib.amof_bond_reorientation(*(args + (ctypes.c_void_p(sums.ctypes.data),
+                                                                ctypes.c_void_p(scale.ctypes.data)))))
+        return sums, scale
+
+    @_locked
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None, out=None):
         """``(counts [nbins] u64, sums [P][nbins] f64, beyond, kinds)`` of ``amof_sq_accumulate``: the vectors ``hkl``
         (int ``[K][3]``) of the frames ``frame_range[0], + frame_stride, ... < frame_range[1]``, P = S(S+1)/2 species
@@ -809,7 +839,8 @@ class Context(Lane):
     def last_stage_seconds(self):
         """``{"rho", "corr", "self"}``: kernel seconds of the stages of the last ``isf_accumulate`` (amof_last_kernel_seconds
         2 .. 4; negative: the last call was not one).  After ``bond_survival`` the same three slots hold the bond lists, the
-        bit series and the correlations."""
+        bit series and the correlations; after ``bond_reorientation`` the bond lists, the bit series, and the vector table
+        with the reorientation sums."""
         self.drain()
         with self._lock:
             return {name: self._lib.amof_last_kernel_seconds(self._h, 2 + i) for i, name in enumerate(("rho", "corr", "self"))}
@@ -996,6 +1027,18 @@ class MultiContext(object):
                 return ctx.bond_survival(tr, cutoff, sets, windows, origin_stride=origin_stride, atom_range=(a, b))
             jobs.append(job)
         return sum(self._run(jobs))
+
+    def bond_reorientation(self, packed, cutoff, sets, windows, origin_stride=1, atom_range=None):
+        """the centre atoms sharded over the devices: the integer sums add up exactly; the scale is the same on all"""
+        lo, hi = (0, packed.n_atoms) if atom_range is None else atom_range
+        jobs = []
+        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
+            def job(ctx=ctx, a=a, b=b):
+                tr, _ = self._for_device(packed, ctx)
+                return ctx.bond_reorientation(tr, cutoff, sets, windows, origin_stride=origin_stride, atom_range=(a, b))
+            jobs.append(job)
+        res = self._run(jobs)
+        return sum(r[0] for r in res), res[0][1]
 
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None):
         """frames sharded over the devices (whole strides per device; a device trajectory on another GPU is copied for the

@@ -14,9 +14,6 @@ import pandas as pd
 
 from ._lazy import Deferred, EmptyUntilComputed
 
-from . import _hip
-from . import atom as amatom
-from . import data as _data
 from . import dist as _dist
 from . import lags
 from .files import path as _path
@@ -24,18 +21,7 @@ from .files import path as _path
 logger = logging.getLogger(__name__)
 
 
-def min_periodic_height(cells, pbc):
-    """smallest perpendicular cell height over all cells (``[..][3][3]``, rows = cell vectors) on a periodic axis; inf
-    without a periodic axis"""
-    cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
-    vol = np.abs(np.linalg.det(cells))
-    best = np.inf
-    for x in range(3):
-        if not pbc[x]:
-            continue
-        area = np.linalg.norm(np.cross(cells[:, (x + 1) % 3], cells[:, (x + 2) % 3]), axis=1)
-        best = min(best, float(np.min(vol / area)))
-    return best
+min_periodic_height = lags.min_periodic_height      # (its home is the family's shared module)
 
 
 def assemble(counts, names, time):
@@ -110,21 +96,7 @@ class BondLifetime(Deferred):
         origin_stride = lags.check_origin_stride(origin_stride)
         packed = lags.pack(trajectory, device)
         window = np.asarray(window, dtype=np.int32)
-        kinds, _ = _hip.packed_species(packed)
-        lut = {z: k for k, z in enumerate(kinds)}
-        rcm = amatom.cutoff_matrix(amatom.format_cutoff(nb_set_and_cutoff), kinds)
-        names, live = [], []
-        for nb_set in nb_set_and_cutoff.keys():
-            a, b = tuple(_data.atomic_numbers[i] for i in nb_set.split('-'))
-            ok = a in lut and b in lut
-            names.append((nb_set, ok))
-            if ok:
-                live.append((lut[a], lut[b]))
-        half = 0.5 * min_periodic_height(packed.cell, packed.pbc)
-        for a, b in live:
-            if rcm[a, b] > half:
-                raise ValueError("cutoff %s exceeds half the smallest perpendicular cell height (%s): a pair could be bonded "
-                                 "through two images" % (rcm[a, b], half))
+        rcm, names, live = lags.neighbour_sets(packed, nb_set_and_cutoff)
         n_orig = lags.n_origins(len(packed), window, origin_stride)
         logger.info("Start computing bond survival at %s times for %s sets", len(window), len(live))
 

@@ -28,8 +28,23 @@
 //                        in LDS, one global u64 atomic per counter and workgroup.
 //   bond_final_kernel    sorted-lag counters -> counts[n_sets][W][3] (suffix sums of the survival histogram)
 // AMOF_BOND_REPORT=1 prints the number of pairs of every piece to stderr (profiles/tools/bond_timing.py).
-// LDS: bond_list_kernel 6 KB static; bond_corr_kernel 28 B per lag of a launch (<= BC_LAGS = 2048 lags: 56 KB); the series
-// kernels use none.  No kernel spills (checked with -Rpass-analysis=kernel-resource-usage).
+//
+// Bond reorientation (amof_bond_reorientation[_dev]) shares the list, compaction and series stages -- unchanged, launched as
+// above -- and replaces bond_corr_kernel / bond_final_kernel by
+//   bond_vector_kernel   a lane owns a pair, a wave 64 frames (the series kernel's shape): the canonical float64 vector
+//                        d_ij(f) of pair_base<ORTHO>, every path, into the table [F][3][Pc] (SLOT_AUX5); the chunk of pairs is
+//                        sized so that the table stays within 256 MB (64 pairs at least).  The f32 fast form decides h only.
+//   bond_reorient_kernel bond_corr_kernel's lanes and word ranges; per lag it walks the set bits of h & (h >> m) & origin
+//                        mask, reads d(k) and d(k + m) (consecutive pairs: coalesced), cos = dot / sqrt(dot dot) clamped,
+//                        P1 = cos, P2 = fma(1.5 cos, cos, -0.5), both as rint(P 2^e) in int64; n, sum P1, sum P2 reduced
+//                        over the wave by shuffles into u64 LDS counters, one global u64 atomic per counter and workgroup.
+//                        A term with a zero-length vector raises a flag: AMOF_EANGLE (host out: zeros; device out: untouched).
+//   bond_reorient_final_kernel  sorted-lag counters -> out[n_sets][W][3]
+// "bond_reorient" / "bond_reorient_exact" name the h decision that ran ("bond_series" / "bond_series_exact").  Stage spans:
+// 0 the lists, 1 the series (both as the survival call), 2 the vector table and the reorientation correlations.
+// LDS: bond_list_kernel 6 KB static; bond_corr_kernel and bond_reorient_kernel 28 B per lag of a launch (<= BC_LAGS = 2048
+// lags: 56 KB); the series and vector kernels use none.  No kernel spills (checked with
+// -Rpass-analysis=kernel-resource-usage).
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -50,6 +65,7 @@ constexpr int BC_LAGS = 2048;           // lags per launch of bond_corr_kernel
 constexpr size_t BOND_BITMAP_BYTES = (size_t)256 << 20;     // bitmap of a piece (2^31 bits: a piece has < 2^31 pairs)
 constexpr size_t BOND_WORDS_BYTES = (size_t)256 << 20;      // series words of a chunk of pairs
 constexpr size_t BOND_PAIR_BYTES = (size_t)256 << 20;       // pair table of a group of rows (AMOF_BOND_PAIR_BUDGET, in pairs, overrides)
+constexpr size_t BOND_VEC_BYTES = (size_t)256 << 20;        // reorientation: vector table of a chunk of pairs
 
 struct BondListArgs {
     const double *pos;
@@ -351,9 +367,177 @@ __global__ __launch_bounds__(256) void bond_final_kernel(const unsigned long lon
     }
 }
 
-// counts (host, overwritten) or counts_dev (device, added into)
+// ---- reorientation ----
+struct BondVecArgs {
+    const double *pos;
+    const double *geom;
+    const int2 *pairs;                  // this chunk's pairs
+    double *tab;                        // [F][3][P]
+    int64_t N;
+    int32_t F, P, nwords, n_cells;
+};
+
+// the series kernel's shape: a lane owns a pair, the wave frames 64 q .. 64 q + 63
+template <bool ORTHO>
+__global__ __launch_bounds__(BS_THREADS) void bond_vector_kernel(BondVecArgs a)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int q = blockIdx.x * (BS_THREADS / 64) + wave;
+    const int p = blockIdx.y * 64 + lane;
+    if (q >= a.nwords || p >= a.P) return;
+    const int2 ij = a.pairs[p];
+    const int f0 = q * 64, nf = min(64, a.F - f0);
+    const size_t P = (size_t)a.P;
+    for (int b = 0; b < nf; b++) {
+        const int f = f0 + b;
+        const double *__restrict__ pi = a.pos + ((size_t)f * (size_t)a.N + (size_t)ij.x) * 3;
+        const double *__restrict__ pj = a.pos + ((size_t)f * (size_t)a.N + (size_t)ij.y) * 3;
+        const double *__restrict__ g = a.geom + (size_t)(a.n_cells == 1 ? 0 : f) * GEOM_STRIDE;
+        double dx, dy, dz;
+        pair_base<ORTHO>(g, pj[0] - pi[0], pj[1] - pi[1], pj[2] - pi[2], dx, dy, dz);
+        double *__restrict__ o = a.tab + (size_t)f * 3 * P + p;
+        o[0] = dx;
+        o[P] = dy;
+        o[2 * P] = dz;
+    }
+}
+
+struct BondReorArgs {
+    const unsigned long long *words;    // [nwords][P]
+    const unsigned long long *obase;    // [nwords]
+    const int32_t *lags;                // sorted, distinct [Wu]
+    const double *tab;                  // [F][3][P]
+    unsigned long long *G;              // this set's counters [3][Wu]: n, sum rint(P1 2^e), sum rint(P2 2^e)
+    int32_t *flag;                      // a contributing term had a zero-length vector
+    int32_t F, P, nwords, Wu, w0, w1;
+    double scale;                       // 2^e
+};
+
+__device__ __forceinline__ double bond_dot(double ax, double ay, double az, double bx, double by, double bz)
+{
+    return fma(az, bz, fma(ay, by, ax * bx));       // norm2's chain
+}
+
+__global__ __launch_bounds__(BC_THREADS) void bond_reorient_kernel(BondReorArgs a)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    const int nl = a.w1 - a.w0;
+    unsigned long long *c_n = reinterpret_cast<unsigned long long *>(lds_raw);       // [nl] pairs bonded at both ends
+    unsigned long long *c_p1 = c_n + nl;                                              // [nl]
+    unsigned long long *c_p2 = c_p1 + nl;                                             // [nl]
+    int32_t *lag = reinterpret_cast<int32_t *>(c_p2 + nl);                            // [nl]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int k = tid; k < 3 * nl; k += BC_THREADS) c_n[k] = 0ull;
+    for (int k = tid; k < nl; k += BC_THREADS) lag[k] = a.lags[a.w0 + k];
+    __syncthreads();
+
+    const int p = blockIdx.x * 64 + lane;
+    const bool has = p < a.P;
+    const int R = gridDim.y * (BC_THREADS / 64), r = blockIdx.y * (BC_THREADS / 64) + wave;
+    const int qa = (int)((long long)a.nwords * r / R), qb = (int)((long long)a.nwords * (r + 1) / R);
+    const unsigned long long *__restrict__ hw = a.words + (has ? p : 0);
+    const double *__restrict__ tab = a.tab + (has ? p : 0);
+    const size_t P = (size_t)a.P;
+    const int nwords = a.nwords;
+    bool bad = false;
+
+    for (int w = 0; w < nl; w++) {
+        const int m = lag[w];
+        const int lim = a.F - m - 1;            // the last origin frame of this lag
+        unsigned n = 0;
+        long long s1 = 0, s2 = 0;
+        if (has && lim >= 1) {
+            const int mq = m >> 6, mr = m & 63;
+            for (int q = qa; q < qb && q * 64 <= lim; q++) {
+                unsigned long long om = a.obase[q];
+                const int top = lim - q * 64;   // bits 0 .. top of this word are origins of the lag
+                if (top < 63) om &= (2ull << top) - 1ull;
+                unsigned long long x = hw[(size_t)q * P] & om;
+                if (!x) continue;
+                const int q2 = q + mq;
+                const unsigned long long lo = q2 < nwords ? hw[(size_t)q2 * P] : 0ull;
+                unsigned long long sh = lo;
+                if (mr) {
+                    const unsigned long long hi = q2 + 1 < nwords ? hw[(size_t)(q2 + 1) * P] : 0ull;
+                    sh = (lo >> mr) | (hi << (64 - mr));
+                }
+                x &= sh;
+                n += __popcll(x);
+                while (x) {
+                    const int k = q * 64 + __ffsll(x) - 1;      // h(k) h(k + m) = 1: k + m <= F - 1
+                    x &= x - 1;
+                    const double *__restrict__ da = tab + (size_t)k * 3 * P;
+                    const double *__restrict__ db = tab + (size_t)(k + m) * 3 * P;
+                    const double ax = da[0], ay = da[P], az = da[2 * P];
+                    const double bx = db[0], by = db[P], bz = db[2 * P];
+                    const double den = bond_dot(ax, ay, az, ax, ay, az) * bond_dot(bx, by, bz, bx, by, bz);
+                    if (!(den > 0.0)) {
+                        bad = true;
+                        continue;
+                    }
+                    double c = bond_dot(ax, ay, az, bx, by, bz) / sqrt(den);
+                    c = fmin(fmax(c, -1.0), 1.0);
+                    const double p2 = fma(1.5 * c, c, -0.5);
+                    s1 += (long long)rint(c * a.scale);
+                    s2 += (long long)rint(p2 * a.scale);
+                }
+            }
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            n += __shfl_down(n, off, 64);
+            s1 += __shfl_down(s1, off, 64);
+            s2 += __shfl_down(s2, off, 64);
+        }
+        if (lane == 0 && n) {
+            atomicAdd(&c_n[w], (unsigned long long)n);
+            atomicAdd(&c_p1[w], (unsigned long long)s1);
+            atomicAdd(&c_p2[w], (unsigned long long)s2);
+        }
+    }
+    if (bad) *a.flag = 1;
+    __syncthreads();
+    for (int k = tid; k < 3 * nl; k += BC_THREADS) {
+        const unsigned long long v = c_n[k];
+        if (v) atomicAdd(&a.G[(size_t)(k / nl) * a.Wu + a.w0 + (k % nl)], v);
+    }
+}
+
+// out[s][w][c] (+)= the sorted-lag counters
+__global__ __launch_bounds__(256) void bond_reorient_final_kernel(const unsigned long long *__restrict__ G, const int32_t *__restrict__ map,
+                                                                  int n_sets, int W, int Wu, int add, unsigned long long *__restrict__ out)
+{
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_sets * W) return;
+    const int s = k / W, u = map[k % W];
+    const unsigned long long *__restrict__ g = G + (size_t)s * 3 * Wu;
+    unsigned long long *__restrict__ o = out + (size_t)k * 3;
+    for (int c = 0; c < 3; c++) {
+        const unsigned long long v = g[(size_t)c * Wu + u];
+        o[c] = add ? o[c] + v : v;
+    }
+}
+
+// e_s = min(40, 62 - bit_length(n_a n_b n_0)); < 20 (a product of 2^43 and more, or one beyond u64): refused by the caller
+int reorient_scale_log2(int64_t n_a, int64_t n_b, int64_t n_0)
+{
+    unsigned long long ab = 0, abo = 0;
+    if (__builtin_mul_overflow((unsigned long long)n_a, (unsigned long long)n_b, &ab) ||
+        __builtin_mul_overflow(ab, (unsigned long long)n_0, &abo))
+        return -1;
+    const int bits = abo ? 64 - __builtin_clzll(abo) : 0;
+    return std::min(40, 62 - bits);
+}
+
+// what a reorientation call adds to bond_run's arguments
+struct Reorient {
+    int64_t *out;           // host [n_sets][W][3], overwritten, or NULL
+    int64_t *out_dev;       // device, added into, or NULL
+    int32_t *scale_log2;    // host [n_sets]
+};
+
+// counts (host, overwritten) or counts_dev (device, added into); ro: the reorientation sums instead
 int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets, const int32_t *windows,
-             int32_t W, int64_t stride, int64_t atom_begin, int64_t atom_end, uint64_t *counts, uint64_t *counts_dev)
+             int32_t W, int64_t stride, int64_t atom_begin, int64_t atom_end, uint64_t *counts, uint64_t *counts_dev, const Reorient *ro = nullptr)
 {
     AMOF_TRY(validate_traj(ctx, t, false));
     const int S = t->n_species;
@@ -371,6 +555,22 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
     }
     const size_t csize = (size_t)n_sets * W * 3;
     if (counts) std::fill(counts, counts + csize, (uint64_t)0);
+    if (ro) {
+        // the scale depends on the trajectory, the set and the stride alone: never on the atom range or the chunking.  (Counted
+        // here and not taken from build_tiles below: a call that returns early -- no windows, one frame -- still reports it.)
+        std::vector<int64_t> nsp((size_t)S, 0);
+        for (int64_t i = 0; i < N; i++) nsp[(size_t)t->species[i]]++;
+        const int64_t n0 = lag_origin_count(F, 0, stride);
+        for (int s = 0; s < n_sets; s++) {
+            const int e = reorient_scale_log2(nsp[(size_t)sets[2 * s]], nsp[(size_t)sets[2 * s + 1]], n0);
+            if (e < 20)
+                return fail(ctx, AMOF_EINVAL, "set %d: %lld x %lld pairs x %lld origins leave a fixed-point quantum above 2^-20: use a "
+                                              "larger origin stride or fewer frames per call",
+                            s, (long long)nsp[(size_t)sets[2 * s]], (long long)nsp[(size_t)sets[2 * s + 1]], (long long)n0);
+            ro->scale_log2[s] = e;
+        }
+        if (ro->out) std::fill(ro->out, ro->out + csize, (int64_t)0);
+    }
     if (csize == 0 || F < 2 || N < 2) return AMOF_OK;
 
     HostGeom geom;
@@ -455,7 +655,12 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
             sa.sc[x] = (float)(c0[4 * x] * (1.0 / 4294967296.0));
         }
     }
-    const char *series_path = fast ? "bond_series" : "bond_series_exact";
+    const char *series_path = ro ? (fast ? "bond_reorient" : "bond_reorient_exact") : (fast ? "bond_series" : "bond_series_exact");
+    void *d_flag = nullptr;
+    if (ro) {
+        AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag));
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), ctx->stream));
+    }
     int64_t series_launches = 0;
     ctx->last_path = series_path;
 
@@ -552,7 +757,8 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
                 // through the ring was copied there at once
 
                 // ---- series and correlations, a chunk of pairs at a time ----
-                const size_t pc_max = std::max<size_t>(64, std::min<size_t>((size_t)65535 * 4, BOND_WORDS_BYTES / 8 / (size_t)nwords) / 64 * 64);
+                size_t pc_max = std::max<size_t>(64, std::min<size_t>((size_t)65535 * 4, BOND_WORDS_BYTES / 8 / (size_t)nwords) / 64 * 64);
+                if (ro) pc_max = std::max<size_t>(64, std::min<size_t>(pc_max, BOND_VEC_BYTES / 24 / (size_t)F) / 64 * 64);
                 for (size_t p0 = 0; p0 < P; p0 += pc_max) {
                     const int Pc = (int)std::min(pc_max, P - p0);
                     void *d_words = nullptr;
@@ -578,32 +784,90 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
                     timing_dom_end(ctx, series_launches);
                     spans.end();
 
+                    // ---- correlations of the chunk: the survival counters, or the vector table and the reorientation sums ----
                     spans.begin(2);
-                    BondCorrArgs ca;
-                    memset(&ca, 0, sizeof ca);
-                    ca.words = (const unsigned long long *)d_words;
-                    ca.obase = pk.ptr<unsigned long long>(i_obase);
-                    ca.lags = pk.ptr<int32_t>(i_lags);
-                    ca.G = (unsigned long long *)d_G + (size_t)s * 3 * Wu;
-                    ca.F = (int32_t)F;
-                    ca.P = Pc;
-                    ca.nwords = nwords;
-                    ca.Wu = Wu;
-                    // word ranges: four per workgroup; more workgroups while the pairs alone do not fill the GPU
-                    const int pblocks = (Pc + 63) / 64;
-                    const int ysplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((nwords + 3) / 4, 64), 2048 / pblocks));
-                    AMOF_HIP_TRY(ctx, allow_max_lds((const void *)bond_corr_kernel));
-                    for (int w0 = 0; w0 < Wu; w0 += BC_LAGS) {
-                        ca.w0 = w0;
-                        ca.w1 = std::min(w0 + BC_LAGS, Wu);
-                        const size_t lds = (size_t)(ca.w1 - ca.w0) * (3 * sizeof(uint64_t) + sizeof(int32_t));
-                        hipLaunchKernelGGL(bond_corr_kernel, dim3((unsigned)pblocks, (unsigned)ysplit), dim3(BC_THREADS), lds, ctx->stream, ca);
+                    // word ranges: four per workgroup; more workgroups while the pairs alone do not fill the GPU; BC_LAGS lags
+                    // per launch (both kernels: 28 B of LDS per lag)
+                    auto launch_lags = [&](auto kernel, auto &args) -> int {
+                        const int pblocks = (Pc + 63) / 64;
+                        const int ysplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((nwords + 3) / 4, 64), 2048 / pblocks));
+                        AMOF_HIP_TRY(ctx, allow_max_lds((const void *)kernel));
+                        for (int w0 = 0; w0 < Wu; w0 += BC_LAGS) {
+                            args.w0 = w0;
+                            args.w1 = std::min(w0 + BC_LAGS, Wu);
+                            const size_t lds = (size_t)(args.w1 - args.w0) * (3 * sizeof(uint64_t) + sizeof(int32_t));
+                            hipLaunchKernelGGL(kernel, dim3((unsigned)pblocks, (unsigned)ysplit), dim3(BC_THREADS), lds, ctx->stream, args);
+                            AMOF_HIP_TRY(ctx, hipGetLastError());
+                        }
+                        return AMOF_OK;
+                    };
+                    if (ro) {
+                        void *d_tab = nullptr;
+                        AMOF_TRY(ensure(ctx, SLOT_AUX5, (size_t)F * 3 * Pc * sizeof(double), &d_tab));
+                        BondVecArgs va;
+                        memset(&va, 0, sizeof va);
+                        va.pos = pos_dev;
+                        va.geom = sa.geom;
+                        va.pairs = sa.pairs;
+                        va.tab = (double *)d_tab;
+                        va.N = N;
+                        va.F = (int32_t)F;
+                        va.P = Pc;
+                        va.nwords = nwords;
+                        va.n_cells = (int32_t)t->n_cells;
+                        const dim3 vgrid((unsigned)((nwords + 3) / 4), (unsigned)((Pc + 63) / 64));
+                        if (ortho) hipLaunchKernelGGL(bond_vector_kernel<true>, vgrid, dim3(BS_THREADS), 0, ctx->stream, va);
+                        else hipLaunchKernelGGL(bond_vector_kernel<false>, vgrid, dim3(BS_THREADS), 0, ctx->stream, va);
                         AMOF_HIP_TRY(ctx, hipGetLastError());
+                        BondReorArgs ra;
+                        memset(&ra, 0, sizeof ra);
+                        ra.words = (const unsigned long long *)d_words;
+                        ra.obase = pk.ptr<unsigned long long>(i_obase);
+                        ra.lags = pk.ptr<int32_t>(i_lags);
+                        ra.tab = (const double *)d_tab;
+                        ra.G = (unsigned long long *)d_G + (size_t)s * 3 * Wu;
+                        ra.flag = (int32_t *)d_flag;
+                        ra.F = (int32_t)F;
+                        ra.P = Pc;
+                        ra.nwords = nwords;
+                        ra.Wu = Wu;
+                        ra.scale = ldexp(1.0, ro->scale_log2[s]);
+                        AMOF_TRY(launch_lags(bond_reorient_kernel, ra));
+                    } else {
+                        BondCorrArgs ca;
+                        memset(&ca, 0, sizeof ca);
+                        ca.words = (const unsigned long long *)d_words;
+                        ca.obase = pk.ptr<unsigned long long>(i_obase);
+                        ca.lags = pk.ptr<int32_t>(i_lags);
+                        ca.G = (unsigned long long *)d_G + (size_t)s * 3 * Wu;
+                        ca.F = (int32_t)F;
+                        ca.P = Pc;
+                        ca.nwords = nwords;
+                        ca.Wu = Wu;
+                        AMOF_TRY(launch_lags(bond_corr_kernel, ca));
                     }
                     spans.end();
                 }
             }
         }
+    }
+    if (ro) {
+        // a zero-length vector among the terms: an error return; the host out holds the zeros it was given above, the device
+        // buffer is untouched
+        int32_t flag = 0;
+        timing_end(ctx);
+        AMOF_TRY(fetch(ctx, &flag, d_flag, sizeof flag));
+        spans.collect();
+        if (flag) return fail(ctx, AMOF_EANGLE, "a bonded pair has a zero-length vector: the angle is undefined");
+        void *d_ro = ro->out_dev;
+        if (!d_ro) AMOF_TRY(ensure(ctx, SLOT_OUT0, csize * sizeof(int64_t), &d_ro));
+        hipLaunchKernelGGL(bond_reorient_final_kernel, dim3((unsigned)(((size_t)n_sets * W + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const unsigned long long *)d_G, pk.ptr<int32_t>(i_map), (int)n_sets, (int)W, Wu, ro->out_dev ? 1 : 0,
+                           (unsigned long long *)d_ro);
+        AMOF_HIP_TRY(ctx, hipGetLastError());
+        if (ro->out) AMOF_TRY(fetch(ctx, ro->out, d_ro, csize * sizeof(int64_t)));
+        AMOF_HIP_TRY(ctx, sync_stream(ctx));
+        return AMOF_OK;
     }
     void *d_out = counts_dev;
     if (!counts_dev) AMOF_TRY(ensure(ctx, SLOT_OUT0, csize * sizeof(uint64_t), &d_out));
@@ -640,4 +904,24 @@ extern "C" int amof_bond_survival_dev(amof_ctx *ctx, const amof_traj *traj, cons
     if (!ctx) return AMOF_EINVAL;
     if (!counts_dev) return fail(ctx, AMOF_EINVAL, "counts is NULL");
     return bond_run(ctx, traj, cutoff, sets, n_sets, windows, n_windows, origin_stride, atom_begin, atom_end, nullptr, counts_dev);
+}
+
+extern "C" int amof_bond_reorientation(amof_ctx *ctx, const amof_traj *traj, const double *cutoff, const int32_t *sets, int32_t n_sets,
+                                       const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t atom_begin,
+                                       int64_t atom_end, int64_t *out, int32_t *scale_log2)
+{
+    if (!ctx) return AMOF_EINVAL;
+    if (!out || !scale_log2) return fail(ctx, AMOF_EINVAL, "out or scale_log2 is NULL");
+    const Reorient ro = {out, nullptr, scale_log2};
+    return bond_run(ctx, traj, cutoff, sets, n_sets, windows, n_windows, origin_stride, atom_begin, atom_end, nullptr, nullptr, &ro);
+}
+
+extern "C" int amof_bond_reorientation_dev(amof_ctx *ctx, const amof_traj *traj, const double *cutoff, const int32_t *sets, int32_t n_sets,
+                                           const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t atom_begin,
+                                           int64_t atom_end, int64_t *out_dev, int32_t *scale_log2)
+{
+    if (!ctx) return AMOF_EINVAL;
+    if (!out_dev || !scale_log2) return fail(ctx, AMOF_EINVAL, "out or scale_log2 is NULL");
+    const Reorient ro = {nullptr, out_dev, scale_log2};
+    return bond_run(ctx, traj, cutoff, sets, n_sets, windows, n_windows, origin_stride, atom_begin, atom_end, nullptr, nullptr, &ro);
 }

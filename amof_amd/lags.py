@@ -1,5 +1,5 @@
-"""The lag/origin family's shared host side: ``DistinctVanHove``, ``IntermediateScattering``, ``BondLifetime`` (and the
-windows of ``WindowVanHove``).
+"""The lag/origin family's shared host side: ``DistinctVanHove``, ``IntermediateScattering``, ``BondLifetime``,
+``BondReorientation`` (and the windows of ``WindowVanHove``).
 
 Lags m are the windows of ``WindowMsd``; the origins of lag m are the frames k = 1, 1 + s, 1 + 2s, ... <= F - m - 1 (s =
 ``origin_stride``).  The work list is every (lag, origin) pair, lag-major, origins ascending; ranks and devices take
@@ -13,6 +13,8 @@ import logging
 import numpy as np
 
 from . import _hip
+from . import atom as amatom
+from . import data as _data
 from . import dist as _dist
 from .frames import pack_trajectory, resident_source
 
@@ -91,3 +93,40 @@ def begin_local(source):
     """first thing of a ``local()`` (the lane job of amof_amd/_lazy.py): the frames are there before the kernels start"""
     if getattr(source, "is_stream", False):
         source.read_all()
+
+
+def min_periodic_height(cells, pbc):
+    """smallest perpendicular cell height over all cells (``[..][3][3]``, rows = cell vectors) on a periodic axis; inf
+    without a periodic axis"""
+    cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
+    vol = np.abs(np.linalg.det(cells))
+    best = np.inf
+    for x in range(3):
+        if not pbc[x]:
+            continue
+        area = np.linalg.norm(np.cross(cells[:, (x + 1) % 3], cells[:, (x + 2) % 3]), axis=1)
+        best = min(best, float(np.min(vol / area)))
+    return best
+
+
+def neighbour_sets(packed, nb_set_and_cutoff):
+    """What the bond analyses (``BondLifetime``, ``BondReorientation``) make of ``CoordinationNumber``'s dictionary:
+    ``(cutoff matrix [S][S], names, live)`` -- names = [(set name, both species present)] in dictionary order, live = the
+    (centre, neighbour) species indices of the present ones.  ValueError for a cutoff above half the smallest
+    perpendicular cell height on a periodic axis (a pair could be bonded through two images)."""
+    kinds, _ = _hip.packed_species(packed)
+    lut = {z: k for k, z in enumerate(kinds)}
+    rcm = amatom.cutoff_matrix(amatom.format_cutoff(nb_set_and_cutoff), kinds)
+    names, live = [], []
+    for nb_set in nb_set_and_cutoff.keys():
+        a, b = tuple(_data.atomic_numbers[i] for i in nb_set.split('-'))
+        ok = a in lut and b in lut
+        names.append((nb_set, ok))
+        if ok:
+            live.append((lut[a], lut[b]))
+    half = 0.5 * min_periodic_height(packed.cell, packed.pbc)
+    for a, b in live:
+        if rcm[a, b] > half:
+            raise ValueError("cutoff %s exceeds half the smallest perpendicular cell height (%s): a pair could be bonded "
+                             "through two images" % (rcm[a, b], half))
+    return rcm, names, live

@@ -123,7 +123,8 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * the context's stream around the dominant kernel's launches:
  * which = 0 total, 1 dominant kernel only.  After amof_isf_accumulate[_dev] also the sums over the call's launches of
  * which = 2 the rho table (quantisation included), 3 the correlation kernel, 4 the self part (0 if not asked for);
- * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations.
+ * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations;
+ * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
  * Returns < 0 if unavailable. */
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which);
 /* number of launches of the dominant kernel in the last call */
@@ -153,7 +154,9 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        beyond the LDS budget, or AMOF_ISF_GLOBAL=1)
  *   bond survival "bond_series" (constant diagonal cell, all axes periodic: f32 distance of the fixed-point differences,
  *        the guard band re-decided exactly), "bond_series_exact" (canonical float64 arithmetic per pair and frame: general
- *        and per-frame cells, open axes; also AMOF_BOND_EXACT=1) */
+ *        and per-frame cells, open axes; also AMOF_BOND_EXACT=1)
+ *   bond reorientation "bond_reorient" (the bond indicator decided as "bond_series"), "bond_reorient_exact" (as
+ *        "bond_series_exact"); the bond vectors are the canonical float64 ones on both */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -357,6 +360,38 @@ int amof_bond_survival(amof_ctx *ctx, const amof_traj *traj, const double *cutof
 int amof_bond_survival_dev(amof_ctx *ctx, const amof_traj *traj, const double *cutoff, const int32_t *sets, int32_t n_sets,
                            const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t atom_begin,
                            int64_t atom_end, uint64_t *counts_dev /* device [n_sets][W][3], += */);
+
+/*
+ * Bond reorientation: first- and second-rank correlations C_l(t) = <P_l(u(0) . u(t))> of the bond vectors.
+ * Replaces the same per-frame neighbour-list loop (amof/cn.py:65) with a minimum-image call per pair.
+ *   Arguments, bond indicator h_ij(f), lags, origins, the refusal of a cutoff above half the smallest height: as
+ *   amof_bond_survival.  d_ij(f): the canonical float64 minimum-image vector r_j - r_i in frame f's cell, on every
+ *   path.  With dot(a, b) = fma(az, bz, fma(ay, by, ax bx)):
+ *     cos = dot(d(k), d(k + m)) / sqrt(dot(d(k), d(k)) * dot(d(k + m), d(k + m))), clamped to [-1, 1]
+ *     P1 = cos,  P2 = fma(1.5 cos, cos, -0.5)              (a lag of 0 gives cos = P1 = P2 = 1 exactly)
+ *   Per set s and lag w, summed over the lag's origins k and the ordered pairs (i, j) with atom_begin <= i < atom_end:
+ *     out[(s*W + w)*3 + 0] = sum h(k) h(k + m)                             (amof_bond_survival's counts[..][1], bit for bit)
+ *     out[(s*W + w)*3 + 1] = sum h(k) h(k + m) rint(P1 2^e_s)              int64, two's complement
+ *     out[(s*W + w)*3 + 2] = sum h(k) h(k + m) rint(P2 2^e_s)
+ *   scale_log2[s] = e_s = min(40, 62 - bit_length(n_A n_B n_0)), n_A and n_B the atoms of the set's species in the whole
+ *   trajectory, n_0 the origins of lag 0: it depends on the trajectory, the set and the stride only.  e_s < 20 is refused
+ *   (AMOF_EINVAL).  The host forms C_l(t) = out[l] 2^-e_s / out[0].  Integer sums: ranges of centres add up bit for bit, and
+ *   the result does not depend on launch order, chunking or the path.
+ *   A contributing term with a zero-length vector returns AMOF_EANGLE; the host form's out holds zeros then, the _dev form's
+ *   buffer is untouched.
+ *   Scratch as amof_bond_survival, plus the vector table of a chunk of pairs (<= 256 MB, 64 pairs at least).
+ *   amof_last_kernel_seconds: which = 2 the bond lists, 3 the bit series, 4 the vector table and the sums.
+ * The host form overwrites out.  Errors: amof_bond_survival's, and AMOF_EANGLE.
+ */
+int amof_bond_reorientation(amof_ctx *ctx, const amof_traj *traj, const double *cutoff /* [S][S], as amof_cn_count */,
+                            const int32_t *sets /* [n_sets][2] */, int32_t n_sets, const int32_t *windows /* host [W] */,
+                            int32_t n_windows, int64_t origin_stride, int64_t atom_begin, int64_t atom_end,
+                            int64_t *out /* host [n_sets][W][3] */, int32_t *scale_log2 /* host [n_sets] */);
+/* The same with the sums ADDED into a device buffer (ranks that share the centres all-reduce it next). */
+int amof_bond_reorientation_dev(amof_ctx *ctx, const amof_traj *traj, const double *cutoff, const int32_t *sets, int32_t n_sets,
+                                const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t atom_begin,
+                                int64_t atom_end, int64_t *out_dev /* device [n_sets][W][3], += */,
+                                int32_t *scale_log2 /* host [n_sets] */);
 
 /*
  * Static structure factor by direct summation over reciprocal-lattice vectors.
