@@ -241,6 +241,7 @@ struct RdfFastArgs {
     int32_t img_queue;       // IMG variant: capacity of one parking buffer
     int32_t img_defer;       // 1: two small buffers, a step's parked pairs are evaluated at the start of the next step
                              // (no extra barrier); 0: one large buffer, evaluated at the end of the step
+    int32_t noreach;         // rdf_tile_zf with slab culling: 1 = every quad of a diagonal tile pair masked (AMOF_RDF_NOREACH)
 };
 
 constexpr int FAST_THREADS = 256;
@@ -443,7 +444,11 @@ struct LaneQueue {
 };
 constexpr unsigned QUEUE_EMPTY = 0xffffffffu;
 
-template <bool ORTHO, bool DIAG, bool TAIL, bool IMG = false, bool ZF = false, bool ZFK = false, bool AA = false, bool PARK = false>
+// SLIM (with PARK): the pairs that find their lane's queue full share ONE refinement body, reached by a loop over the eight
+// pair slots with the partner's record from LDS again, instead of eight inlined ones per quad loop -- the culled ZF kernel
+// 10 423 -> 4 989 instructions, no scratch, 0.25 ms of the headline launch (profiles/r06/tile_reach.txt)
+template <bool ORTHO, bool DIAG, bool TAIL, bool IMG = false, bool ZF = false, bool ZFK = false, bool AA = false, bool PARK = false,
+          bool SLIM = false>
 __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa, const double *sc64,
                                           const double *__restrict__ g, const float *sc, const uint4 *tq,
                                           int j0, int cntj, bool has_a, bool has_b, int ia, int ib,
@@ -495,7 +500,21 @@ __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa,
                     else { lq->pk1 = lq->pk0; lq->pq1 = lq->pq0; lq->pk0 = ((unsigned)(j0 + u) << 1) | 1u; lq->pq0 = qb[u]; }
                 }
             }
-            if (ovf) {
+            if (SLIM) {
+                if (ovf) {
+#pragma unroll 1
+                    for (int k = 0; k < 8; k++) {       // bit k of ovf: partner j0 + k / 2, centre b when k is odd
+                        if (ovf & (1u << k)) {
+                            const int u = k >> 1;
+                            const bool cb = (k & 1) != 0;
+                            const float qv = cb ? (u == 0 ? qb[0] : u == 1 ? qb[1] : u == 2 ? qb[2] : qb[3])
+                                                : (u == 0 ? qa[0] : u == 1 ? qa[1] : u == 2 ? qa[2] : qa[3]);
+                            rdf_pair_refine<ORTHO, ZFK, AA>(hist, fa, sc64, g, qv, cb ? ubx : uax, cb ? uby : uay, cb ? ubz : uaz,
+                                                            tq[j0 + u], p, cb ? idb : ida, qseg, j0 + u);
+                        }
+                    }
+                }
+            } else if (ovf) {
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     if (ovf & (1u << (2 * u))) rdf_pair_refine<ORTHO, ZFK, AA>(hist, fa, sc64, g, qa[u], uax, uay, uaz, qj[u], p, ida, qseg, j0 + u);
@@ -796,6 +815,10 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
     // flagged pairs wait in per-lane register queues for the end of the step (fast_quad): the diagonal-cell kernels.  68.6 ->
     // 67.0 ms per headline launch -- the first parking scheme that pays (seven with LDS queues lost: profiles/r04/rdf_tile_stop.txt)
     constexpr bool PARK = ORTHO && ZFK && !IMG && TRI < 0 && AA;
+    // REACH (rdf_tile_zf with slab culling): of a diagonal tile pair only the sub-tile's own 128-partner block runs the masked
+    // body -- partners behind it satisfy j > ia and j > ib always and go through the unmasked loop and the ragged tail quad,
+    // like an off-diagonal pair (fa.noreach: every quad masked, as before).  Its quad loops use the SLIM form of fast_quad.
+    constexpr bool REACH = ORTHO && CULL && ZFK && !IMG && TRI < 0;
     // TRI = 10 / 11: near mode 4 with the exact-half x wrap, c10 = + 1/2 / - 1/2 (tri_q_twin)
     constexpr int NEAR = TRI >= 10 ? 4 : (TRI >= 0 ? TRI % 5 : 0);
     constexpr bool XW = TRI >= 5;
@@ -1124,6 +1147,29 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
                                                                  cax, cay, uaz, ida, cbx, cby, ubz, idb,
                                                                  nq, nqc, nq_cap, g, p, gi, zaf, zbf, qseg, clampv);
                     }
+                    continue;
+                }
+                if constexpr (REACH) {
+                    // (a piece starts at or behind the own block's first quad, and a wave keeps its residue across the cut:
+                    //  the quads whose slab coordinates it converted)
+                    const int own_end = !diag ? 0 : (fa.noreach ? qe : min(qe, (sub + 1) * FAST_SUB));
+                    const int qe_plain = min(qe, full);
+                    int j0 = qb + 4 * wave;
+                    for (; j0 < own_end; j0 += 16)
+                        fast_quad<ORTHO, true, true, IMG, ZF, ZFK, AA, PARK, true>(hist, fa, sc64, g, sc, tq, j0, cntj, has_a, has_b, ia, ib,
+                                                                         half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
+                                                                         idb, p, near_f, gi, nq, nullptr, nq_cap, zaf,
+                                                                         zbf, qseg, clampv, &lq);
+                    for (; j0 < qe_plain; j0 += 16)
+                        fast_quad<ORTHO, false, false, IMG, ZF, ZFK, AA, PARK, true>(hist, fa, sc64, g, sc, tq, j0, cntj, has_a, has_b, ia, ib,
+                                                                           half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
+                                                                           idb, p, near_f, gi, nq, nullptr, nq_cap,
+                                                                           zaf, zbf, qseg, clampv, &lq);
+                    if (j0 == full && j0 < qe && full < cntj)
+                        fast_quad<ORTHO, false, true, IMG, ZF, ZFK, AA, PARK, true>(hist, fa, sc64, g, sc, tq, full, cntj, has_a, has_b, ia, ib,
+                                                                          half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
+                                                                          idb, p, near_f, gi, nq, nullptr, nq_cap, zaf,
+                                                                          zbf, qseg, clampv, &lq);
                     continue;
                 }
                 if (diag) {
@@ -2104,6 +2150,10 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
             AMOF_TRY(upload(ctx, SLOT_AUX5, fsv.data(), fsv.size() * sizeof(FrameScale), &d_fs));
             RdfFastArgs fa;
             fa.a = a;
+            {
+                const char *noreach = getenv("AMOF_RDF_NOREACH");    // tests / measurements: see rdf_tile_kernel_fast, REACH
+                fa.noreach = noreach && noreach[0] == '1' ? 1 : 0;
+            }
             fa.a.tiles = (const Tile *)d_ftiles;
             fa.a.pairs = (const int2 *)d_fpairs;
             fa.fs = (const FrameScale *)d_fs;
