@@ -14,6 +14,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 #include "amof_internal.h"
@@ -1773,6 +1774,90 @@ static void pick_chunks(int64_t F, size_t nwork, int32_t &fpc, unsigned &chunks)
     chunks = (unsigned)c;
 }
 
+// ---- run-time switches to template arguments ----
+// Every kernel family here is instantiated over a few switches.  The helpers below call f once with the run-time
+// switches as std::integral_constant tags, so a family's ladder is one call: with_flags(ortho, cell, [&](auto O, auto C)
+// { return launch_lds(kernel<O(), C()>, ...); }).
+template <bool V> using Flag = std::integral_constant<bool, V>;
+template <int V> using Count = std::integral_constant<int, V>;
+template <typename F>
+static hipError_t with_flag(bool a, F &&f)
+{
+    return a ? f(Flag<true>{}) : f(Flag<false>{});
+}
+template <typename F>
+static hipError_t with_flags(bool a, bool b, F &&f)
+{
+    return with_flag(a, [&](auto A) { return with_flag(b, [&](auto B) { return f(A, B); }); });
+}
+// allow_max_lds + launch + the launch's own error (kernels without dynamic LDS take lds = 0: the cap is then a no-op)
+template <typename Kernel, typename... Args>
+static hipError_t launch_lds(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args)
+{
+    const hipError_t e = allow_max_lds((const void *)kern);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
+// ---- constants the two tiers' preparation shares ----
+struct NbrGuard {
+    double hmin[3];         // smallest perpendicular height of any cell, per axis
+    float guard_rel, guard_abs;
+    double csum;            // largest sum of a cell's vector lengths
+    double R;               // largest cutoff
+    bool sheared_ok;        // false: a sheared cell too small for R (the exact kernels answer)
+};
+static NbrGuard nbr_guard(const amof_traj *t, const double *cutoff, const NbrSetup &st)
+{
+    const int64_t nc = t->n_cells;
+    NbrGuard g;
+    g.csum = g.R = 0.0;
+    for (int k = 0; k < t->n_species * t->n_species; k++) g.R = std::max(g.R, cutoff[k]);
+    for (int x = 0; x < 3; x++) g.hmin[x] = 1e300;
+    for (int64_t k = 0; k < nc; k++) {
+        const double *c = t->cell + 9 * k;
+        for (int x = 0; x < 3; x++) g.hmin[x] = std::min(g.hmin[x], st.geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
+        g.csum = std::max(g.csum, sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) +
+                                      sqrt(c[3] * c[3] + c[4] * c[4] + c[5] * c[5]) +
+                                      sqrt(c[6] * c[6] + c[7] * c[7] + c[8] * c[8]));
+    }
+    // f32 chain error: fast_guard_rel (amof_internal.h); the fixed-point grid moves a distance by
+    // < csum * 2^-32 (x2 margin)
+    const double grel = fast_guard_rel(st.geom, nc);
+    // + 3u: the cutoff rounded to f32 (1u) and the roundings of r_in / r_out = rc -+ g in the kernels
+    const double want = grel + 3.0 / 16777216.0;
+    float fg = (float)want;
+    if ((double)fg < want) fg = nextafterf(fg, INFINITY);
+    g.guard_rel = fg;
+    g.guard_abs = (float)(g.csum * (1.0 / 2147483648.0));
+    // sheared cells: wrapped and canonical images may differ at |s_k| = 1/2 -- both must then be
+    // decisively beyond every cutoff (see rdf.hip)
+    g.sheared_ok = true;
+    if (!st.geom.all_ortho)
+        for (int x = 0; x < 3; x++)
+            if (g.R * (1.0 + 4.0 * grel + 1e-6) >= 0.5 * g.hmin[x]) g.sheared_ok = false;
+    return g;
+}
+
+// the f32 scale of the fixed-point components in every cell's table entry: component q of a record lies along cell
+// vector ord[q] (gap_per_len is the caller's)
+static void fill_cell_scales(const amof_traj *t, bool ortho, const int ord[3], std::vector<NbrCell> &cells)
+{
+    const double two32 = 1.0 / 4294967296.0;
+    for (int64_t k = 0; k < t->n_cells; k++) {
+        const double *c = t->cell + 9 * k;
+        NbrCell &r = cells[(size_t)k];
+        for (int q = 0; q < 9; q++) r.sc[q] = 0.f;
+        if (ortho) {
+            for (int q = 0; q < 3; q++) r.sc[q] = (float)(c[4 * ord[q]] * two32);
+        } else {
+            for (int q = 0; q < 3; q++)
+                for (int x = 0; x < 3; x++) r.sc[3 * q + x] = (float)(c[3 * ord[q] + x] * two32);
+        }
+    }
+}
+
 // ---- fast-path preparation shared by CN and BAD ----
 struct NbrFast {
     bool ok = false;
@@ -1780,7 +1865,6 @@ struct NbrFast {
     bool ortho = false;
     int64_t FB = 0, FB0 = 0;     // frames per batch (largest, first)
     void *d_Q = nullptr, *d_slab = nullptr, *d_cells = nullptr, *d_spfirst = nullptr, *d_qflag = nullptr;
-    std::vector<int64_t> sp_first;
     NbrFastArgs fa;
     // 3-D cell list (cutoffs far below the cell size): frames sorted by (species, cell) instead of slabs
     bool cell = false;
@@ -1790,64 +1874,26 @@ struct NbrFast {
     int64_t max_used_atoms = 0;             // (its LDS record cache is sized for the largest of them)
 };
 
-// quantise + sort one frame batch for the neighbour kernels (slab list or cell list) and point fa at it
-static int nbr_fast_batch(amof_ctx *ctx, const amof_traj *t, NbrSetup &st, NbrFast &nf, int64_t fb, int64_t nfr)
-{
-    const NbrArgs &a = st.a;
-    if (nf.cell)
-        AMOF_TRY(launch_quantize_cells(ctx, a.pos, a.geom, (int)t->n_cells, a.perm, (const int64_t *)nf.d_spfirst,
-                                       t->n_species, t->n_atoms, (int)fb, (int)nfr, nf.nk[0], nf.nk[1], nf.nk[2],
-                                       (QAtom *)nf.d_Q, (uint32_t *)nf.d_start3, (int32_t *)nf.d_qflag, nf.max_used_atoms,
-                                       nf.used_mask));
-    else
-        AMOF_TRY(launch_quantize(ctx, a.pos, a.geom, (int)t->n_cells, a.perm, (const int64_t *)nf.d_spfirst, t->n_species,
-                                 t->n_atoms, (int)fb, (int)nfr, nf.axis, (QAtom *)nf.d_Q, (uint32_t *)nf.d_slab,
-                                 (int32_t *)nf.d_qflag));
-    nf.fa.f_base = (int32_t)fb;
-    nf.fa.nf = (int32_t)nfr;
-    return AMOF_OK;
-}
-
 static int nbr_fast_prepare(amof_ctx *ctx, const amof_traj *t, const double *cutoff, NbrSetup &st, NbrFast &nf,
                             unsigned long long centre_mask = 0ull)
 {
     const int S = t->n_species;
     const int64_t nc = t->n_cells;
     const char *force = getenv("AMOF_NBR_KERNEL");
-    double R = 0.0;
-    for (int k = 0; k < S * S; k++) R = std::max(R, cutoff[k]);
+    const NbrGuard g = nbr_guard(t, cutoff, st);
+    const double R = g.R, *hmin = g.hmin;
     nf.ok = st.max_img == 0 && t->pbc[0] && t->pbc[1] && t->pbc[2] && R > 0.0 && t->n_atoms > 0 &&
             !(force && strcmp(force, "v1") == 0);
     if (!nf.ok) return AMOF_OK;
     nf.ortho = st.geom.all_ortho;
-    double hmin[3] = {1e300, 1e300, 1e300}, csum = 0.0;
-    for (int64_t k = 0; k < nc; k++) {
-        const double *c = t->cell + 9 * k;
-        for (int x = 0; x < 3; x++) hmin[x] = std::min(hmin[x], st.geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-        csum = std::max(csum, sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) +
-                                  sqrt(c[3] * c[3] + c[4] * c[4] + c[5] * c[5]) +
-                                  sqrt(c[6] * c[6] + c[7] * c[7] + c[8] * c[8]));
-    }
     nf.axis = 0;
     for (int x = 1; x < 3; x++)
         if (hmin[x] > hmin[nf.axis]) nf.axis = x;
     const int ord[3] = {(nf.axis + 1) % 3, (nf.axis + 2) % 3, nf.axis};
-    const double two32 = 1.0 / 4294967296.0;
     std::vector<NbrCell> cells((size_t)nc);
-    for (int64_t k = 0; k < nc; k++) {
-        const double *c = t->cell + 9 * k;
-        NbrCell &r = cells[(size_t)k];
-        for (int q = 0; q < 9; q++) r.sc[q] = 0.f;
-        if (nf.ortho) {
-            for (int q = 0; q < 3; q++) r.sc[q] = (float)(c[4 * ord[q]] * two32);
-        } else {
-            for (int q = 0; q < 3; q++)
-                for (int x = 0; x < 3; x++) r.sc[3 * q + x] = (float)(c[3 * ord[q] + x] * two32);
-        }
-        r._pad = 0.f;
-        r.gap_per_len = 4294967296.0 / st.geom.rec[(size_t)k * GEOM_STRIDE + 18 + nf.axis] * (1.0 + 1e-6);
-    }
-    nf.sp_first = st.tiles.sp_first;
+    fill_cell_scales(t, nf.ortho, ord, cells);
+    for (int64_t k = 0; k < nc; k++)
+        cells[(size_t)k].gap_per_len = 4294967296.0 / st.geom.rec[(size_t)k * GEOM_STRIDE + 18 + nf.axis] * (1.0 + 1e-6);
     // species without a cutoff to any species are neither centres nor partners: the cell sort skips them
     nf.used_mask = 0ull;
     nf.max_used_atoms = 1;
@@ -1897,19 +1943,11 @@ static int nbr_fast_prepare(amof_ctx *ctx, const amof_traj *t, const double *cut
     nf.FB0 = st.stage.lazy ? std::min<int64_t>(nf.FB, 512) : nf.FB;
     if (nf.cell) {
         // the cell kernels read the fixed-point components in the cell's own axis order
-        for (int64_t k = 0; k < nc; k++) {
-            const double *c = t->cell + 9 * k;
-            NbrCell &r = cells[(size_t)k];
-            for (int q = 0; q < 9; q++) r.sc[q] = 0.f;
-            if (nf.ortho) {
-                for (int q = 0; q < 3; q++) r.sc[q] = (float)(c[4 * q] * two32);
-            } else {
-                for (int q = 0; q < 9; q++) r.sc[q] = (float)(c[q] * two32);
-            }
-        }
+        const int own[3] = {0, 1, 2};
+        fill_cell_scales(t, nf.ortho, own, cells);
     }
     AMOF_TRY(upload(ctx, SLOT_AUX4, cells.data(), cells.size() * sizeof(NbrCell), &nf.d_cells));
-    AMOF_TRY(upload(ctx, SLOT_AUX5, nf.sp_first.data(), nf.sp_first.size() * sizeof(int64_t), &nf.d_spfirst));
+    AMOF_TRY(upload(ctx, SLOT_AUX5, st.tiles.sp_first.data(), st.tiles.sp_first.size() * sizeof(int64_t), &nf.d_spfirst));
     AMOF_TRY(ensure(ctx, SLOT_HISTU, (size_t)nf.FB * t->n_atoms * sizeof(QAtom), &nf.d_Q));
     if (nf.cell) {
         AMOF_TRY(ensure(ctx, SLOT_SELF, (size_t)nf.FB * (nkeys + 1) * sizeof(uint32_t), &nf.d_start3));
@@ -1926,41 +1964,85 @@ static int nbr_fast_prepare(amof_ctx *ctx, const amof_traj *t, const double *cut
     fa.nx = nf.nk[0]; fa.ny = nf.nk[1]; fa.nz = nf.nk[2];
     fa.cells = (const NbrCell *)nf.d_cells;
     fa.sp_first = (const int64_t *)nf.d_spfirst;
-    // f32 chain error: fast_guard_rel (amof_internal.h); the fixed-point grid moves a distance by
-    // < csum * 2^-32 (x2 margin)
-    const double grel = fast_guard_rel(st.geom, nc);
-    // + 3u: the cutoff rounded to f32 (1u) and the roundings of r_in / r_out = rc -+ g in the kernels
-    {
-        const double want = grel + 3.0 / 16777216.0;
-        float fg = (float)want;
-        if ((double)fg < want) fg = nextafterf(fg, INFINITY);
-        fa.guard_rel = fg;
+    fa.guard_rel = g.guard_rel;
+    if (!g.sheared_ok) {
+        nf.ok = false;
+        return AMOF_OK;
     }
-    if (!nf.ortho) {
-        // sheared cells: wrapped and canonical images may differ at |s_k| = 1/2 -- both must then be
-        // decisively beyond every cutoff (see rdf.hip)
-        for (int x = 0; x < 3; x++)
-            if (R * (1.0 + 4.0 * grel + 1e-6) >= 0.5 * hmin[x]) nf.ok = false;
-        if (!nf.ok) return AMOF_OK;
-    }
-    fa.guard_abs = (float)(csum * (1.0 / 2147483648.0));
+    fa.guard_abs = g.guard_abs;
     return AMOF_OK;
+}
+
+// The gather tiers' frame batches (CN and BAD): FB0 frames first when the input is staged lazily, doubling up to FB.  A batch
+// is quantised + sorted (slab list or cell list), fa pointed at it and its transposed lists emptied (BAD, when it keeps
+// any); launch(nfr, grid) then queues its kernels over nwork work items.  qflag: an atom absurdly far from the cell.
+template <typename Launch>
+static int nbr_fast_batches(amof_ctx *ctx, const amof_traj *t, NbrSetup &st, NbrFast &nf, size_t nwork, bool bad, Launch &&launch,
+                            int32_t &qflag)
+{
+    const NbrArgs &a = st.a;
+    int64_t launches = 0;
+    for (int64_t fb = 0, cur = nf.FB0; fb < t->n_frames && nwork > 0; fb += cur, cur = std::min<int64_t>(2 * cur, nf.FB)) {
+        const int64_t nfr = std::min<int64_t>(cur, t->n_frames - fb);
+        AMOF_TRY(stager_need(st.stage, fb + nfr));
+        if (nf.cell)
+            AMOF_TRY(launch_quantize_cells(ctx, a.pos, a.geom, (int)t->n_cells, a.perm, (const int64_t *)nf.d_spfirst,
+                                           t->n_species, t->n_atoms, (int)fb, (int)nfr, nf.nk[0], nf.nk[1], nf.nk[2],
+                                           (QAtom *)nf.d_Q, (uint32_t *)nf.d_start3, (int32_t *)nf.d_qflag, nf.max_used_atoms,
+                                           nf.used_mask));
+        else
+            AMOF_TRY(launch_quantize(ctx, a.pos, a.geom, (int)t->n_cells, a.perm, (const int64_t *)nf.d_spfirst, t->n_species,
+                                     t->n_atoms, (int)fb, (int)nfr, nf.axis, (QAtom *)nf.d_Q, (uint32_t *)nf.d_slab,
+                                     (int32_t *)nf.d_qflag));
+        nf.fa.f_base = (int32_t)fb;
+        nf.fa.nf = (int32_t)nfr;
+        if (nf.fa.a.tr_total > 0)
+            AMOF_HIP_TRY(ctx, hipMemsetAsync(nf.fa.a.tcount, 0, (size_t)nfr * nf.fa.a.tr_total * sizeof(uint32_t), ctx->stream));
+        unsigned chunks;
+        pick_chunks(nfr, nwork, nf.fa.a.frames_per_chunk, chunks);
+        if (launches == 0) timing_dom_begin(ctx, bad ? (nf.cell ? "bad_cell" : "bad_fast") : (nf.cell ? "cn_cell" : "cn_fast"));
+        AMOF_TRY(launch(nfr, dim3((unsigned)nwork, chunks)));
+        launches++;
+    }
+    timing_dom_end(ctx, launches);
+    qflag = 0;
+    return fetch(ctx, &qflag, nf.d_qflag, sizeof qflag);
 }
 
 // ---- whole-frame-in-LDS tier: per-item grids and the few constants the kernels need ----
 struct NbrFrame {
     bool ok = false;
     bool ortho = false;
+    double hmin[3] = {0.0, 0.0, 0.0};
     std::vector<FrameItem> items;
     size_t lds = 0;
     bool compact = false;   // 8-byte records + (atom, rank) in global scratch: pairs that 16-byte records leave one workgroup per CU
+    bool slabs = false;     // every pair in z-slabs, the streaming kernels (PT = 0)
+    int64_t most = 0;       // atoms of the largest pair
     FrameArgs fr;
     std::vector<NbrCell> cells;
-    std::vector<int64_t> sp_first;
     UploadPack pk;          // cells | sp_first | items (| whatever the caller adds first): one copy (nbr_frame_commit)
     const int64_t *d_spfirst = nullptr;
     void *d_qflag = nullptr;
 };
+
+// the finest grid a cutoff allows -- cells at least rc (+ trunc of the axis) thick, >= 3 and <= 1024 per axis -- made
+// coarser along its longest axis until it has at most `want` cells (or is 3 cells long everywhere)
+static bool frame_grid(const double hmin[3], double rc, double trunc, int64_t want, int nk[3])
+{
+    for (int x = 0; x < 3; x++) {
+        nk[x] = (int)std::min(1024.0, floor(1.0 / (rc * (1.0 + 1e-5) / hmin[x] + trunc)));
+        if (nk[x] < 3) return false;
+    }
+    while ((int64_t)nk[0] * nk[1] * nk[2] > want) {
+        int big = 0;
+        for (int x = 1; x < 3; x++)
+            if (nk[x] > nk[big]) big = x;
+        if (nk[big] <= 3) break;
+        nk[big]--;
+    }
+    return true;
+}
 
 // a grid for one species pair: cells at least rc thick, >= 3 per axis, as fine as the LDS left beside n records allows
 static bool frame_item_grid(const double hmin[3], double rc, int64_t n, int slots, int64_t densest, FrameItem &it, size_t &lds,
@@ -1973,10 +2055,6 @@ static bool frame_item_grid(const double hmin[3], double rc, int64_t n, int slot
     // 8-byte records key the coordinate TRUNCATED to 16 bits, which moves a centre against its partner by up to 2^-16 of the
     // cell vector -- far more than 1e-5 * rc / h -- so their cells are 2^-15 (twice that, in fractions of the axis) thicker.
     const double trunc = rec_size < sizeof(uint4) ? 1.0 / 32768.0 : 0.0;
-    for (int x = 0; x < 3; x++) {
-        nk[x] = (int)std::min(1024.0, floor(1.0 / (rc * (1.0 + 1e-5) / hmin[x] + trunc)));
-        if (nk[x] < 3) return false;
-    }
     const size_t rec_bytes = (size_t)n * rec_size + extra_bytes;           // (+ whatever else the kernel keeps per atom)
     // two workgroups per CU when the records leave room for a useful table, one otherwise
     size_t budget = 76 * 1024;
@@ -1986,13 +2064,7 @@ static bool frame_item_grid(const double hmin[3], double rc, int64_t n, int slot
     // as fine as the budget allows (the cutoff bounds it from the other side): a centre walks 27 cells whatever their size,
     // so emptier cells are fewer candidates, and clearing + scanning 8k counters costs a thousand lanes eight steps
     const int64_t want = std::max<int64_t>(27, std::min<int64_t>(cells_budget, std::max<int64_t>(4 * densest, 4096)));
-    while ((int64_t)nk[0] * nk[1] * nk[2] > want) {
-        int big = 0;
-        for (int x = 1; x < 3; x++)
-            if (nk[x] > nk[big]) big = x;
-        if (nk[big] <= 3) break;
-        nk[big]--;
-    }
+    if (!frame_grid(hmin, rc, trunc, want, nk)) return false;
     if ((int64_t)nk[0] * nk[1] * nk[2] > cells_budget) return false;
     it.nx = nk[0]; it.ny = nk[1]; it.nz = nk[2];
     it.zoff = 0; it.nzg = nk[2]; it.c0 = 0; it.cn = nk[2]; it.cap = (int32_t)n;
@@ -2008,21 +2080,9 @@ static bool frame_item_slabs(const double hmin[3], double rc, int64_t nA, int64_
                              size_t &lds, size_t budget, size_t fixed, size_t per_atom, bool thin)
 {
     int nk0[3];
-    for (int x = 0; x < 3; x++) {
-        nk0[x] = (int)std::min(1024.0, floor(1.0 / (rc * (1.0 + 1e-5) / hmin[x])));
-        if (nk0[x] < 3) return false;
-    }
     const int64_t partners = nB > 0 ? nB : nA;
-    {   // the whole frame's granularity first, as frame_item_grid: about four cells per partner
-        const int64_t want = std::max<int64_t>(27, std::max<int64_t>(4 * partners, 4096));
-        while ((int64_t)nk0[0] * nk0[1] * nk0[2] > want) {
-            int big = 0;
-            for (int x = 1; x < 3; x++)
-                if (nk0[x] > nk0[big]) big = x;
-            if (nk0[big] <= 3) break;
-            nk0[big]--;
-        }
-    }
+    // the whole frame's granularity first, as frame_item_grid: about four cells per partner
+    if (!frame_grid(hmin, rc, 0.0, std::max<int64_t>(27, std::max<int64_t>(4 * partners, 4096)), nk0)) return false;
     const size_t rec = sizeof(uint4) + per_atom;
     for (int nsl = 1; nsl == 1 || (nk0[2] >= 4 && nsl <= nk0[2] / 2); nsl++) {
         int nk[3] = {nk0[0], nk0[1], nk0[2]};
@@ -2078,106 +2138,88 @@ static bool frame_slab_passes(Build &&build, std::vector<FrameItem> &items, size
     }
     return false;
 }
-static bool frame_slabs_forced() { const char *e = getenv("AMOF_NBR_SLABS"); return e && e[0] == '1'; }
-static bool frame_slabs_forbidden() { const char *e = getenv("AMOF_NBR_SLABS"); return e && e[0] == '0'; }
 
-// the slab kernels' input: room for FB frames of records (at most 2 GiB: FB shrinks) and their bin tables
-static int frame_slab_buffers(amof_ctx *ctx, const amof_traj *t, NbrFrame &nw, int64_t &FB)
+// The tier's plan.  A prototype is one species pair of the call: its FrameItem with sa, sb, set, reg_ab, reg_ba filled, the
+// pair's cutoff and the atoms of sa and sb.  Beside its records a workgroup keeps, per call, `per_atom` bytes per atom
+// (rounded up to a word for a whole frame) and `extra` bytes for a whole frame, `slab_fixed` for a slab.
+struct FrameProto {
+    FrameItem it;
+    double rc;
+    int64_t nA, nB;
+};
+// nw.ok on entry: the tier may take the call at all.  On return nw.ok, items, lds, compact, slabs and most are the plan.
+static void frame_plan(const std::vector<FrameProto> &protos, size_t extra, size_t slab_fixed, size_t per_atom, NbrFrame &nw)
 {
-    FB = std::max<int64_t>(1, std::min<int64_t>(FB, (int64_t)(((size_t)2 << 30) / ((size_t)t->n_atoms * sizeof(QAtom)))));
-    void *d_Q, *d_z;
-    AMOF_TRY(ensure(ctx, SLOT_HISTU, (size_t)FB * (size_t)t->n_atoms * sizeof(QAtom), &d_Q));
-    AMOF_TRY(ensure(ctx, SLOT_SELF, (size_t)FB * (size_t)t->n_species * (QSLABS + 1) * sizeof(uint32_t), &d_z));
-    nw.fr.Q = (const QAtom *)d_Q;
-    nw.fr.zstart = (const uint32_t *)d_z;
-    return AMOF_OK;
-}
-static int frame_slab_quantize(amof_ctx *ctx, const amof_traj *t, const NbrArgs &a, NbrFrame &nw, int64_t fb, int64_t nfr)
-{
-    unsigned long long used = 0ull;         // only the species some pair of the call reads
-    for (const FrameItem &it : nw.items) {
-        used |= it.sa < 64 ? 1ull << it.sa : 0ull;
-        used |= it.sb < 64 ? 1ull << it.sb : 0ull;
+    if (!nw.ok) return;
+    auto atoms_of = [](const FrameProto &p) { return p.it.sa == p.it.sb ? p.nA : p.nA + p.nB; };
+    nw.most = 0;
+    for (const FrameProto &p : protos) nw.most = std::max(nw.most, atoms_of(p));
+    // Record size of the tier, three passes: 0 = 16-byte records, 1 = COMPACT 8-byte ones, 2 = 16-byte again.  AMOF_NBR_COMPACT=1
+    // starts at (and keeps) the compact pass -- tests of the 16-bit cell keys; =0 never leaves pass 0.
+    const char *e_compact = getenv("AMOF_NBR_COMPACT"), *e_slabs = getenv("AMOF_NBR_SLABS");
+    const bool compact_forced = e_compact && (e_compact[0] == '1' || e_compact[0] == '0');
+    const bool slabs_forced = e_slabs && e_slabs[0] == '1', slabs_forbidden = e_slabs && e_slabs[0] == '0';
+    bool ok16 = false;
+    for (int pass = e_compact && e_compact[0] == '1' ? 1 : 0; pass < 3; pass++) {
+        // 16-byte records first; if a pair then needs a whole CU's LDS, everything again with the 8-byte ones; if that
+        // does not bring two workgroups per CU either, the 16-byte ones stay -- unless they did not fit at all
+        nw.ok = true; nw.items.clear(); nw.lds = 0; nw.compact = pass == 1;
+        for (size_t k = 0; k < protos.size() && nw.ok; k++) {
+            const FrameProto &p = protos[k];
+            const int64_t n = atoms_of(p);
+            FrameItem it = p.it;
+            nw.ok = frame_item_grid(nw.hmin, p.rc, n, 1, p.nB, it, nw.lds, nw.compact ? sizeof(uint2) : sizeof(uint4),
+                                    ((size_t)n * per_atom + 3) / 4 * 4 + extra);
+            if (nw.ok) nw.items.push_back(it);
+        }
+        if (pass == 0) ok16 = nw.ok;
+        if (compact_forced) break;                              // whatever this pass gave
+        if (nw.ok && nw.lds <= 76 * 1024) break;                // two workgroups per CU: nothing to gain
+        if (pass == 1 && nw.ok && !ok16) break;                 // only the compact records fit at all: keep them (pass 2 would fail again)
     }
-    return launch_quantize(ctx, a.pos, a.geom, (int)t->n_cells, a.perm, nw.d_spfirst, t->n_species, t->n_atoms, (int)fb, (int)nfr, 2,
-                           (QAtom *)nw.fr.Q, (uint32_t *)nw.fr.zstart, (int32_t *)nw.d_qflag, 0, 1, nullptr, used);
-}
-
-// Record size of the tier, three passes: 0 = 16-byte records, 1 = COMPACT 8-byte ones, 2 = 16-byte again.  AMOF_NBR_COMPACT=1
-// starts at (and keeps) the compact pass -- tests of the 16-bit cell keys; =0 never leaves pass 0.
-static int frame_first_pass()
-{
-    const char *e = getenv("AMOF_NBR_COMPACT");
-    return e && e[0] == '1' ? 1 : 0;
-}
-static bool frame_pass_done(int pass, bool ok, size_t lds, bool ok16)
-{
-    const char *e = getenv("AMOF_NBR_COMPACT");
-    if (e && (e[0] == '1' || e[0] == '0')) return true;     // forced: whatever this pass gave
-    if (ok && lds <= 76 * 1024) return true;                // two workgroups per CU: nothing to gain
-    if (pass == 1 && ok && !ok16) return true;              // only the compact records fit at all: keep them (pass 2 would fail again)
-    return pass == 2;
+    // pairs too big for one workgroup (or AMOF_NBR_SLABS=1): every pair in z-slabs, the streaming kernels
+    nw.slabs = false;
+    if (!slabs_forbidden && (slabs_forced || !nw.ok)) {
+        nw.slabs = frame_slab_passes([&](size_t budget, bool thin, std::vector<FrameItem> &out, size_t &lds) {
+            for (const FrameProto &p : protos)
+                if (!frame_item_slabs(nw.hmin, p.rc, p.nA, p.it.sa == p.it.sb ? 0 : p.nB, p.it, out, lds, budget, slab_fixed,
+                                      per_atom, thin)) return false;
+            return true;
+        }, nw.items, nw.lds);
+        if (nw.slabs) { nw.ok = true; nw.compact = false; }
+        else if (slabs_forced) { nw.ok = false; }
+    }
 }
 
 // host-side constants of the tier (nothing is uploaded before nbr_frame_commit); ok stays false when the tier cannot take the call
-static int nbr_frame_prepare(const amof_traj *t, const double *cutoff, NbrSetup &st, NbrFrame &nw, double hmin[3])
+static int nbr_frame_prepare(const amof_traj *t, const double *cutoff, NbrSetup &st, NbrFrame &nw)
 {
-    const int S = t->n_species;
-    const int64_t nc = t->n_cells;
-    double R = 0.0, csum = 0.0;
-    for (int k = 0; k < S * S; k++) R = std::max(R, cutoff[k]);
-    nw.ok = st.max_img == 0 && t->pbc[0] && t->pbc[1] && t->pbc[2] && R > 0.0 && t->n_atoms > 0 &&
+    const NbrGuard g = nbr_guard(t, cutoff, st);
+    nw.ok = st.max_img == 0 && t->pbc[0] && t->pbc[1] && t->pbc[2] && g.R > 0.0 && t->n_atoms > 0 &&
             t->n_atoms < (1ll << CELL_SPECIES_SHIFT) && !getenv("AMOF_NBR_NOFRAME") &&
             !getenv("AMOF_NBR_NOCELL") && !getenv("AMOF_NBR_FORCE_CELL") &&      // (those name the gather kernels)
             !(getenv("AMOF_NBR_KERNEL") && strcmp(getenv("AMOF_NBR_KERNEL"), "v1") == 0);
-    for (int x = 0; x < 3; x++) hmin[x] = 1e300;
-    for (int64_t k = 0; k < nc; k++) {
-        const double *c = t->cell + 9 * k;
-        for (int x = 0; x < 3; x++) hmin[x] = std::min(hmin[x], st.geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-        csum = std::max(csum, sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) + sqrt(c[3] * c[3] + c[4] * c[4] + c[5] * c[5]) +
-                                  sqrt(c[6] * c[6] + c[7] * c[7] + c[8] * c[8]));
-    }
+    for (int x = 0; x < 3; x++) nw.hmin[x] = g.hmin[x];
+    if (!g.sheared_ok) nw.ok = false;
     if (!nw.ok) return AMOF_OK;
     nw.ortho = st.geom.all_ortho;
-    const double grel = fast_guard_rel(st.geom, nc);
-    if (!nw.ortho)
-        for (int x = 0; x < 3; x++)
-            if (R * (1.0 + 4.0 * grel + 1e-6) >= 0.5 * hmin[x]) nw.ok = false;     // (as in nbr_fast_prepare)
-    if (!nw.ok) return AMOF_OK;
-    const double two32 = 1.0 / 4294967296.0;
-    nw.cells.assign((size_t)nc, NbrCell{});
-    for (int64_t k = 0; k < nc; k++) {
-        const double *c = t->cell + 9 * k;
-        NbrCell &r = nw.cells[(size_t)k];
-        for (int q = 0; q < 9; q++) r.sc[q] = 0.f;
-        if (nw.ortho) {
-            for (int q = 0; q < 3; q++) r.sc[q] = (float)(c[4 * q] * two32);
-        } else {
-            for (int q = 0; q < 9; q++) r.sc[q] = (float)(c[q] * two32);
-        }
-        r._pad = 0.f;
-        r.gap_per_len = 0.0;
-    }
-    nw.sp_first = st.tiles.sp_first;
+    const int own[3] = {0, 1, 2};
+    nw.cells.assign((size_t)t->n_cells, NbrCell{});
+    fill_cell_scales(t, nw.ortho, own, nw.cells);
     FrameArgs &fr = nw.fr;
-    {
-        const double want = grel + 3.0 / 16777216.0;     // (+ 3u: see nbr_fast_prepare)
-        float fg = (float)want;
-        if ((double)fg < want) fg = nextafterf(fg, INFINITY);
-        fr.guard_rel = fg;
-    }
-    fr.guard_abs = (float)(csum * (1.0 / 2147483648.0));
-    fr.guard_abs16 = (float)(csum * (1.0 / 32768.0));      // (16-bit coordinates: one unit is 2^-16 of a cell vector; x2 margin as above)
+    fr.guard_rel = g.guard_rel;
+    fr.guard_abs = g.guard_abs;
+    fr.guard_abs16 = (float)(g.csum * (1.0 / 32768.0));    // (16-bit coordinates: one unit is 2^-16 of a cell vector; x2 margin as above)
     fr.sidx = nullptr;
     fr.sidx_stride = 0;
     return AMOF_OK;
 }
 
 // the tier takes the call: its tables (and whatever the caller added to nw.pk before) to the device in one copy
-static int nbr_frame_commit(amof_ctx *ctx, NbrFrame &nw)
+static int nbr_frame_commit(amof_ctx *ctx, const NbrSetup &st, NbrFrame &nw)
 {
     const int i_cells = nw.pk.add(nw.cells.data(), nw.cells.size() * sizeof(NbrCell));
-    const int i_sp = nw.pk.add(nw.sp_first.data(), nw.sp_first.size() * sizeof(int64_t));
+    const int i_sp = nw.pk.add(st.tiles.sp_first.data(), st.tiles.sp_first.size() * sizeof(int64_t));
     const int i_items = nw.pk.add(nw.items.data(), nw.items.size() * sizeof(FrameItem));
     AMOF_TRY(upload_pack(ctx, SLOT_AUX4, nw.pk));
     AMOF_TRY(ensure(ctx, SLOT_SPEC, sizeof(int32_t), &nw.d_qflag));
@@ -2186,6 +2228,651 @@ static int nbr_frame_commit(amof_ctx *ctx, NbrFrame &nw)
     nw.fr.sp_first = nw.d_spfirst = nw.pk.ptr<int64_t>(i_sp);
     nw.fr.items = nw.pk.ptr<FrameItem>(i_items);
     nw.fr.qflag = (int32_t *)nw.d_qflag;
+    return AMOF_OK;
+}
+
+// frames per batch that the compact records' (atom, rank) of every sorted position allow: at most 256 MB a batch
+static int64_t frame_sidx_frames(const NbrFrame &nw, int64_t FB)
+{
+    if (!nw.compact) return FB;
+    const size_t per_frame = nw.items.size() * (size_t)nw.most * sizeof(uint2);
+    return std::max<int64_t>(1, std::min<int64_t>(FB, (int64_t)(((size_t)256 << 20) / per_frame)));
+}
+
+// The planned tier's per-batch buffers; FB shrinks to what they allow.  Slabs: room for FB frames of records (at most
+// 2 GiB) and their bin tables, the slab kernels' input.  Compact records: the (atom, rank) table.
+static int frame_batch_buffers(amof_ctx *ctx, const amof_traj *t, NbrFrame &nw, int64_t &FB)
+{
+    if (nw.slabs) {
+        FB = std::max<int64_t>(1, std::min<int64_t>(FB, (int64_t)(((size_t)2 << 30) / ((size_t)t->n_atoms * sizeof(QAtom)))));
+        void *d_Q, *d_z;
+        AMOF_TRY(ensure(ctx, SLOT_HISTU, (size_t)FB * (size_t)t->n_atoms * sizeof(QAtom), &d_Q));
+        AMOF_TRY(ensure(ctx, SLOT_SELF, (size_t)FB * (size_t)t->n_species * (QSLABS + 1) * sizeof(uint32_t), &d_z));
+        nw.fr.Q = (const QAtom *)d_Q;
+        nw.fr.zstart = (const uint32_t *)d_z;
+    }
+    if (nw.compact) {
+        FB = frame_sidx_frames(nw, FB);
+        void *d_sidx;
+        AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)FB * nw.items.size() * (size_t)nw.most * sizeof(uint2), &d_sidx));
+        nw.fr.sidx = (uint2 *)d_sidx;
+        nw.fr.sidx_stride = (int32_t)nw.most;
+    }
+    return AMOF_OK;
+}
+
+// The frame tier's batches (CN and BAD), after frame_batch_buffers: FB0 frames first when the input is staged lazily,
+// doubling up to FB.  launch(nfr) queues one batch's kernels; qflag says whether an atom lay absurdly far from the cell.
+template <typename Launch>
+static int frame_batches(amof_ctx *ctx, const amof_traj *t, NbrSetup &st, NbrFrame &nw, int64_t FB, bool bad, Launch &&launch,
+                         int32_t &qflag)
+{
+    const NbrArgs &a = st.a;
+    unsigned long long used = 0ull;         // slabs quantise only the species some pair of the call reads
+    for (const FrameItem &it : nw.items) {
+        used |= it.sa < 64 ? 1ull << it.sa : 0ull;
+        used |= it.sb < 64 ? 1ull << it.sb : 0ull;
+    }
+    const int64_t FB0 = st.stage.lazy ? std::min<int64_t>(FB, 512) : FB;
+    int64_t launches = 0;
+    for (int64_t fb = 0, cur = FB0; fb < t->n_frames; fb += cur, cur = std::min<int64_t>(2 * cur, FB)) {
+        const int64_t nfr = std::min<int64_t>(cur, t->n_frames - fb);
+        AMOF_TRY(stager_need(st.stage, fb + nfr));
+        nw.fr.f_base = (int32_t)fb;
+        nw.fr.nf = (int32_t)nfr;
+        if (launches == 0)
+            timing_dom_begin(ctx, bad ? (nw.slabs ? "bad_frame_slabs" : "bad_frame") : (nw.slabs ? "cn_frame_slabs" : "cn_frame"));
+        if (nw.slabs)
+            AMOF_TRY(launch_quantize(ctx, a.pos, a.geom, (int)t->n_cells, a.perm, nw.d_spfirst, t->n_species, t->n_atoms, (int)fb,
+                                     (int)nfr, 2, (QAtom *)nw.fr.Q, (uint32_t *)nw.fr.zstart, (int32_t *)nw.d_qflag, 0, 1, nullptr, used));
+        AMOF_TRY(launch(nfr));
+        launches++;
+    }
+    timing_dom_end(ctx, launches);
+    qflag = 0;
+    return fetch(ctx, &qflag, nw.d_qflag, sizeof qflag);
+}
+
+// the <ORTHO, PT, COMPACT> of a frame-tier kernel: slabs stream 16-byte records (PT = 0); a whole frame takes 4 atoms per
+// thread, 8 when a pair has more than 4096, with either record size
+template <typename F>
+static hipError_t frame_dispatch(const NbrFrame &nw, F &&f)
+{
+    return with_flag(nw.ortho, [&](auto O) {
+        if (nw.slabs) return f(O, Count<0>{}, Flag<false>{});
+        return with_flags(nw.most > 4 * NBRW_THREADS, nw.compact,
+                          [&](auto WIDE, auto C) { return f(O, Count<(decltype(WIDE)::value ? 8 : 4)>{}, C); });
+    });
+}
+
+// ---- what the tiers of one call share: first tier to last, each runs unless one before it is done ----
+struct NbrCall {
+    amof_ctx *ctx;
+    const amof_traj *t;
+    const double *cutoff;
+    NbrSetup st;
+    bool done = false;
+};
+struct CnCall : NbrCall {
+    const int32_t *sets;
+    int32_t n_sets;
+    bool per_atom;
+    void *d_sums = nullptr, *d_pa = nullptr;
+    size_t sums_bytes = 0, pa_bytes = 0;
+    int reset_outputs()         // the outputs as before the first tier: sums zero, per-atom counts unset
+    {
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_sums, 0, sums_bytes, ctx->stream));
+        if (per_atom) AMOF_HIP_TRY(ctx, hipMemsetAsync(d_pa, 0xFF, pa_bytes, ctx->stream));
+        return AMOF_OK;
+    }
+};
+
+// whole-frame-in-LDS tier: every set with a cutoff is one item (a zero-cutoff set with per-atom output keeps the
+// gather kernels: its centres still want their zeros)
+static int cn_frame_tier(CnCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const int S = t->n_species;
+    NbrFrame nw;
+    AMOF_TRY(nbr_frame_prepare(t, c.cutoff, c.st, nw));
+    std::vector<FrameProto> protos;
+    bool zero_set = false;
+    for (int s2 = 0; s2 < c.n_sets; s2++) {
+        const int A = c.sets[2 * s2], B = c.sets[2 * s2 + 1];
+        FrameProto p{FrameItem{}, c.cutoff[A * S + B], c.st.tiles.nsp[A], c.st.tiles.nsp[B]};
+        if (!(p.rc > 0.0) || p.nA == 0 || p.nB == 0) { zero_set = true; continue; }
+        p.it.sa = A; p.it.sb = B; p.it.set = s2; p.it.reg_ab = p.it.reg_ba = -1;
+        protos.push_back(p);
+    }
+    if (zero_set && c.per_atom) nw.ok = false;
+    frame_plan(protos, 0, 0, 0, nw);
+    if (!nw.ok) return AMOF_OK;
+    if (nw.items.empty()) {
+        c.done = true;          // no set has a cutoff and both species: every count is zero
+        return AMOF_OK;
+    }
+    AMOF_TRY(nbr_frame_commit(ctx, c.st, nw));
+    int64_t FB = std::min<int64_t>(t->n_frames, 32768);
+    AMOF_TRY(frame_batch_buffers(ctx, t, nw, FB));
+    auto batch = [&](int64_t nfr) -> int {
+        const dim3 grid((unsigned)nw.items.size(), (unsigned)nfr);
+        const hipError_t e = frame_dispatch(nw, [&](auto O, auto PT, auto C) {
+            return launch_lds(cn_frame_kernel<O(), PT(), C()>, grid, dim3(NBRW_THREADS), nw.lds, ctx->stream, c.st.a, nw.fr);
+        });
+        AMOF_HIP_TRY(ctx, e);
+        return AMOF_OK;
+    };
+    int32_t qflag;
+    AMOF_TRY(frame_batches(ctx, t, c.st, nw, FB, false, batch, qflag));
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
+    if (qflag) return c.reset_outputs();    // atoms absurdly far from the cell: the exact kernel answers (via the fast path's own check)
+    c.done = true;
+    return AMOF_OK;
+}
+
+// gathered cell list or slab list: one work item per tile of centres of a set
+static int cn_gather_tier(CnCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const int S = t->n_species;
+    NbrFast nf;
+    unsigned long long centre_mask = 0ull;
+    if (c.per_atom)
+        for (int s2 = 0; s2 < c.n_sets; s2++)
+            if (c.sets[2 * s2] < 64) centre_mask |= 1ull << c.sets[2 * s2];
+    AMOF_TRY(nbr_fast_prepare(ctx, t, c.cutoff, c.st, nf, centre_mask));
+    if (!nf.ok) return AMOF_OK;
+    std::vector<int4> fwork;
+    for (int s2 = 0; s2 < c.n_sets; s2++) {
+        int A = c.sets[2 * s2], B = c.sets[2 * s2 + 1];
+        if (!(c.cutoff[A * S + B] > 0.0) && !c.per_atom) continue;      // counts stay zero (per_atom still wants its zeros)
+        for (int64_t c0 = 0; c0 < c.st.tiles.nsp[A]; c0 += NBRF_TILE) fwork.push_back(make_int4(s2, (int)c0, A, B));
+    }
+    void *d_fwork;
+    AMOF_TRY(upload(ctx, SLOT_AUX3, fwork.data(), fwork.size() * sizeof(int4), &d_fwork));
+    nf.fa.a = c.st.a;
+    nf.fa.a.work = (const int4 *)d_fwork;
+    auto batch = [&](int64_t, dim3 grid) -> int {
+        const hipError_t e = with_flags(nf.ortho, nf.cell, [&](auto O, auto CELL) {
+            return launch_lds(cn_fast_kernel<O(), CELL()>, grid, dim3(NBRF_TILE), 0, ctx->stream, nf.fa);
+        });
+        AMOF_HIP_TRY(ctx, e);
+        return AMOF_OK;
+    };
+    int32_t qflag;
+    AMOF_TRY(nbr_fast_batches(ctx, t, c.st, nf, fwork.size(), false, batch, qflag));
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
+    if (qflag) return c.reset_outputs();    // atoms absurdly far from the cell: redo with the exact kernel
+    c.done = true;
+    return AMOF_OK;
+}
+
+// exact kernel: every tile of centres of a set against every partner and image
+static int cn_exact_tier(CnCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    NbrSetup &st = c.st;
+    std::vector<int4> work;
+    for (int s = 0; s < c.n_sets; s++) {
+        int A = c.sets[2 * s], B = c.sets[2 * s + 1];
+        for (int k = 0; k < st.tiles.sp_ntiles[A]; k++)
+            work.push_back(make_int4(s, st.tiles.sp_first_tile[A] + k, A, B));
+    }
+    if (work.empty()) return AMOF_OK;
+    NbrArgs &a = st.a;
+    void *d_work;       // (the exact kernel's work list: uploaded only when it runs)
+    AMOF_TRY(upload(ctx, SLOT_PAIRS, work.data(), work.size() * sizeof(int4), &d_work));
+    a.work = (const int4 *)d_work;
+    unsigned chunks;
+    pick_chunks(t->n_frames, work.size(), a.frames_per_chunk, chunks);
+    const dim3 grid((unsigned)work.size(), chunks);
+    timing_dom_begin(ctx, "cn_exact");
+    const hipError_t e = with_flags(st.geom.all_ortho, st.max_img > 0, [&](auto O, auto EXTRA) {
+        return launch_lds(cn_kernel<O(), EXTRA()>, grid, dim3(CN_TILE), 0, ctx->stream, a);
+    });
+    AMOF_HIP_TRY(ctx, e);
+    timing_dom_end(ctx, 1);
+    return AMOF_OK;
+}
+
+struct BadCall : NbrCall {
+    const int32_t *triples;
+    int32_t T, nb, cn_max;
+    // every pass accumulates into scratch; the caller's buffers only ever receive a complete, valid result
+    void *d_hs = nullptr, *d_flags = nullptr;
+    size_t hs_words = 0;
+    size_t lds_bins = 0;        // histogram bins a workgroup keeps in LDS (0: more bins than LDS holds, global atomics)
+    size_t KC = 1;              // histogram slots per triple
+    int read_flags(int32_t (&fl)[4])
+    {
+        AMOF_TRY(fetch(ctx, fl, d_flags, sizeof fl));
+        AMOF_HIP_TRY(ctx, sync_stream(ctx));
+        return AMOF_OK;
+    }
+    int clear_scratch()
+    {
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_hs, 0, hs_words * sizeof(unsigned long long), ctx->stream));
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
+        return AMOF_OK;
+    }
+};
+
+// whole-frame-in-LDS tier: one sort + LDS search per species pair into neighbour rows, every triple from the rows
+static int bad_frame_tier(BadCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const double *cutoff = c.cutoff;
+    NbrSetup &st = c.st;
+    NbrArgs &a = st.a;
+    const int S = t->n_species, T = c.T;
+    NbrFrame nw;
+    AMOF_TRY(nbr_frame_prepare(t, cutoff, st, nw));
+    if (getenv("AMOF_BAD_NOTRANSPOSE")) nw.ok = false;      // (names the two-search gather kernels)
+    auto live_pair = [&](int x, int y) { return cutoff[x * S + y] > 0.0 && st.tiles.nsp[x] > 0 && st.tiles.nsp[y] > 0; };
+    std::vector<char> needed((size_t)S * S, 0);
+    std::vector<int4> awork;
+    for (int k = 0; k < T && nw.ok; k++) {
+        const int A = c.triples[2 * k], B = c.triples[2 * k + 1];
+        for (int sa = 0; sa < S; sa++) {
+            if (!(A < 0 || sa == A)) continue;
+            bool live = false;
+            for (int sb = 0; sb < S; sb++)
+                if ((B < 0 || sb == B) && live_pair(sa, sb)) { needed[(size_t)sa * S + sb] = 1; live = true; }
+            if (live) awork.push_back(make_int4(k, sa, B, 0));
+        }
+    }
+    std::vector<int32_t> region_of((size_t)S * S, -1);
+    int64_t R = 0;
+    for (int x = 0; x < S * S && nw.ok; x++)
+        if (needed[(size_t)x]) { region_of[(size_t)x] = (int32_t)R; R += st.tiles.nsp[(size_t)(x / S)]; }
+    std::vector<FrameProto> protos;
+    for (int x = 0; x < S; x++)
+        for (int y = x; y < S; y++) {
+            if (!needed[(size_t)x * S + y] && !needed[(size_t)y * S + x]) continue;
+            FrameProto p{FrameItem{}, cutoff[x * S + y], 0, 0};
+            p.it.sa = st.tiles.nsp[y] < st.tiles.nsp[x] ? y : x;      // the species with fewer atoms searches
+            p.it.sb = p.it.sa == x ? y : x;
+            p.it.set = 0;
+            p.it.reg_ab = region_of[(size_t)p.it.sa * S + p.it.sb];
+            p.it.reg_ba = x == y ? -1 : region_of[(size_t)p.it.sb * S + p.it.sa];
+            p.nA = st.tiles.nsp[p.it.sa];
+            p.nB = st.tiles.nsp[p.it.sb];
+            protos.push_back(p);
+        }
+    // beside the records: a byte per atom (its row's count) and the hit buffer
+    frame_plan(protos, (size_t)NBRW_HITS * sizeof(uint32_t), (size_t)NBRW_HITS * sizeof(uint32_t) + 4, 1, nw);
+    bool shared_rows = false;
+    if (nw.slabs)
+        for (const FrameItem &it : nw.items) shared_rows = shared_rows || (it.cn != it.nzg && it.reg_ba >= 0);
+    if (nw.ok && awork.empty()) {
+        c.done = true;          // no triple has a centre with a cutoff to any of its partners: no angle
+        return AMOF_OK;
+    }
+    if (!(nw.ok && R > 0 && R < (1ll << 30) && t->n_frames > 0)) return AMOF_OK;
+    // merged angle passes: one per centre species, every angle computed once (histograms in LDS; BadByCn keys, more
+    // bins than LDS holds, a centre species with more than three partner species or a triple named twice keep
+    // the pass per triple)
+    std::vector<MergedItem> merged;
+    size_t lds_merged = 0;
+    if (c.cn_max == 0 && !a.global_hist && !getenv("AMOF_BAD_NOMERGE")) {
+        auto find_triple = [&](int A, int B, bool &twice) {
+            int found = -1;
+            for (int k = 0; k < T; k++)
+                if (c.triples[2 * k] == A && c.triples[2 * k + 1] == B) { if (found >= 0) twice = true; else found = k; }
+            return found;
+        };
+        bool usable = true, twice = false;
+        for (int sa = 0; sa < S && usable; sa++) {
+            MergedItem mi{};
+            mi.sa = sa;
+            for (int q = 0; q < 3; q++) { mi.reg[q] = 0; mi.tb[q][0] = mi.tb[q][1] = -1; }
+            for (int sb = 0; sb < S && usable; sb++) {
+                if (region_of[(size_t)sa * S + sb] < 0) continue;
+                if (mi.n_reg == 3) { usable = false; break; }
+                mi.reg[mi.n_reg] = region_of[(size_t)sa * S + sb];
+                mi.tb[mi.n_reg][0] = find_triple(sa, sb, twice);
+                mi.tb[mi.n_reg][1] = find_triple(-1, sb, twice);
+                mi.n_reg++;
+            }
+            mi.tx[0] = find_triple(sa, -1, twice);
+            mi.tx[1] = find_triple(-1, -1, twice);
+            if (mi.n_reg == 0) continue;
+            bool any = mi.tx[0] >= 0 || mi.tx[1] >= 0;
+            for (int q = 0; q < mi.n_reg; q++) any = any || mi.tb[q][0] >= 0 || mi.tb[q][1] >= 0;
+            if (!any) continue;
+            lds_merged = std::max(lds_merged, (size_t)(mi.n_reg + (mi.n_reg > 1 ? 1 : 0)) * c.lds_bins * sizeof(unsigned));
+            merged.push_back(mi);
+        }
+        // (worth it when it saves passes: two triples over one species pair are two passes either way, and the pass
+        //  per triple keeps a centre's vectors in registers)
+        if (!usable || twice || lds_merged > 60 * 1024 || merged.size() >= awork.size()) merged.clear();
+    }
+    // one small table: angle work | region_of[S*S] | inv_rank[N]; the items beside it
+    std::vector<int32_t> tab(4 * awork.size() + (size_t)S * S + (size_t)t->n_atoms);
+    memcpy(tab.data(), awork.data(), awork.size() * sizeof(int4));
+    memcpy(&tab[4 * awork.size()], region_of.data(), region_of.size() * sizeof(int32_t));
+    for (int64_t x = 0; x < t->n_atoms; x++) {
+        const int32_t atom = st.tiles.perm[(size_t)x];
+        tab[4 * awork.size() + (size_t)S * S + (size_t)atom] = (int32_t)(x - st.tiles.sp_first[(size_t)t->species[atom]]);
+    }
+    void *d_lists;
+    const int i_tab = nw.pk.add(tab.data(), tab.size() * sizeof(int32_t));
+    const int i_merged = nw.pk.add(merged.data(), merged.size() * sizeof(MergedItem));
+    AMOF_TRY(nbr_frame_commit(ctx, c.st, nw));
+    const int32_t *d_tab = nw.pk.ptr<int32_t>(i_tab);
+    const MergedItem *d_merged = nw.pk.ptr<MergedItem>(i_merged);
+    const size_t per_frame = (size_t)R * (sizeof(uint32_t) + (size_t)NBRL_CAP * NBRL_EW * sizeof(double));
+    size_t rows_budget = (size_t)4 << 30;                          // <= 4 GiB of rows
+    if (const char *mb = getenv("AMOF_BAD_ROWS_MB")) rows_budget = (size_t)std::max(1, atoi(mb)) << 20;     // tests: many batches
+    int64_t FB = std::max<int64_t>(1, (int64_t)rows_budget / (int64_t)per_frame);
+    FB = std::min<int64_t>(FB, std::max<int64_t>(1, 0x7fffff00ll / std::max<int64_t>(1, t->n_atoms)));    // flat (frame, centre) index
+    FB = std::min<int64_t>(std::min<int64_t>(FB, 32768), t->n_frames);
+    FB = frame_sidx_frames(nw, FB);         // (the rows are not sized for more frames than a batch will hold)
+    // (a device short of memory gets smaller batches, not an error)
+    for (;;) {
+        const int rc_rows = ensure(ctx, SLOT_AUX9, (size_t)FB * per_frame, &d_lists);
+        if (rc_rows == AMOF_OK) break;
+        if (rc_rows != AMOF_ENOMEM || FB == 1) return rc_rows;
+        FB = std::max<int64_t>(1, FB / 4);
+    }
+    AMOF_TRY(frame_batch_buffers(ctx, t, nw, FB));
+    NbrListArgs la;
+    const int4 *d_aw = (const int4 *)d_tab;
+    la.region_of = (const int32_t *)d_tab + 4 * awork.size();
+    la.inv_rank = la.region_of + (size_t)S * S;
+    la.rows = (double *)d_lists;                                   // (doubles first: 8-byte aligned)
+    la.count = (uint32_t *)(la.rows + (size_t)FB * R * NBRL_CAP * NBRL_EW);
+    la.R = (int32_t)R;
+    la.plane = (size_t)FB * (size_t)R;
+    const size_t lds_rows = c.lds_bins * sizeof(unsigned);
+    auto batch = [&](int64_t nfr) -> int {
+        if (shared_rows)    // (partners of several slabs claim their rows' slots with global atomics: the counts start at zero)
+            AMOF_HIP_TRY(ctx, hipMemsetAsync(la.count, 0, (size_t)FB * (size_t)R * sizeof(uint32_t), ctx->stream));
+        const dim3 sgrid((unsigned)nw.items.size(), (unsigned)nfr);
+        hipError_t e = frame_dispatch(nw, [&](auto O, auto PT, auto C) {
+            return launch_lds(lists_frame_kernel<O(), PT(), C()>, sgrid, dim3(NBRW_THREADS), nw.lds, ctx->stream, a, nw.fr, la);
+        });
+        AMOF_HIP_TRY(ctx, e);
+        if (!merged.empty()) {
+            // one pass per centre species: about 1024 workgroups of 512 lanes in all
+            int64_t widest_m = 0;
+            for (const MergedItem &mi : merged)
+                widest_m = std::max<int64_t>(widest_m, (nfr * st.tiles.nsp[(size_t)mi.sa] + NBRM_THREADS - 1) / NBRM_THREADS);
+            const int64_t gm = std::max<int64_t>(1, std::min<int64_t>(widest_m, (1024 + (int64_t)merged.size() - 1) / (int64_t)merged.size()));
+            const dim3 mgrid((unsigned)gm, (unsigned)merged.size());
+            e = with_flag(nw.ortho, [&](auto O) {
+                return launch_lds(bad_rows_merged_kernel<O()>, mgrid, dim3(NBRM_THREADS), lds_merged, ctx->stream, a, la, d_merged,
+                                  nw.d_spfirst, (int)nfr);
+            });
+            AMOF_HIP_TRY(ctx, e);
+            return AMOF_OK;
+        }
+        // angle kernel: about eight workgroups per CU in all work items together, each striding over the tiles of its own
+        int64_t widest = 0;
+        for (const int4 &w : awork) widest = std::max<int64_t>(widest, (nfr * st.tiles.nsp[(size_t)w.y] + NBRF_TILE - 1) / NBRF_TILE);
+        // (every workgroup ends with one global atomic per non-empty bin of its histogram, all on the same few
+        //  addresses: 16 384 workgroups spent more time there than on the angles)
+        const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(widest, (2048 + (int64_t)awork.size() - 1) / (int64_t)awork.size()));
+        const dim3 agrid((unsigned)gx, (unsigned)awork.size());
+        e = with_flag(nw.ortho, [&](auto O) {
+            return launch_lds(bad_rows_kernel<O()>, agrid, dim3(NBRF_TILE), lds_rows, ctx->stream, a, la, d_aw, nw.d_spfirst, (int)nfr);
+        });
+        AMOF_HIP_TRY(ctx, e);
+        return AMOF_OK;
+    };
+    int32_t qflag;
+    AMOF_TRY(frame_batches(ctx, t, st, nw, FB, true, batch, qflag));
+#ifdef NBR_PHASE_STAMPS
+    {
+        unsigned long long ph[16][5];
+        hipDeviceSynchronize();
+        hipMemcpyFromSymbol(ph, HIP_SYMBOL(nbr_phase_ticks), sizeof ph);
+        for (size_t e = 0; e < nw.items.size() && e < 16; e++)
+            if (ph[e][4])
+                fprintf(stderr, "lists entry %zu (species %d+%d, layers %d of %d, grid %dx%dx%d): us per workgroup: sort %.1f search + unit vectors (wave 0) %.1f (-) %.1f counts %.1f\n",
+                        e, nw.items[e].sa, nw.items[e].sb, nw.items[e].cn, nw.items[e].nzg, nw.items[e].nx, nw.items[e].ny, nw.items[e].nz,
+                        0.01 * ph[e][0] / ph[e][4], 0.01 * ph[e][1] / ph[e][4], 0.01 * ph[e][2] / ph[e][4], 0.01 * ph[e][3] / ph[e][4]);
+        memset(ph, 0, sizeof ph);
+        hipMemcpyToSymbol(HIP_SYMBOL(nbr_phase_ticks), ph, sizeof ph);
+    }
+#endif
+    int32_t flags[4];
+    AMOF_TRY(c.read_flags(flags));
+    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
+    // atoms absurdly far from the cell, or a centre with more than NBRL_CAP neighbours: the gather / exact kernels
+    if (qflag || flags[1]) return c.clear_scratch();
+    c.done = true;
+    return AMOF_OK;
+}
+
+// gathered cell list or slab list, one search per centre tile of a triple; of two triples B-A-B / A-B-A over one species
+// pair only the side with fewer centres searches, the other's angles come from the transposed lists
+static int bad_gather_tier(BadCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const double *cutoff = c.cutoff;
+    const int32_t *triples = c.triples;
+    NbrSetup &st = c.st;
+    const int S = t->n_species, T = c.T;
+    NbrFast nf;
+    AMOF_TRY(nbr_fast_prepare(ctx, t, cutoff, st, nf));
+    if (!nf.ok || t->n_frames <= 0) return AMOF_OK;
+    std::vector<int32_t> derived_from((size_t)T, -1), tr_off((size_t)T, -1);
+    std::vector<TrDerived> der;
+    int32_t tr_total = 0;
+    if (!getenv("AMOF_BAD_NOTRANSPOSE")) {
+        for (int k = 0; k < T; k++) {
+            const int A = triples[2 * k], B = triples[2 * k + 1];
+            if (A < 0 || B < 0 || A == B || !(cutoff[A * S + B] > 0.0) || !(st.tiles.nsp[A] > st.tiles.nsp[B])) continue;
+            for (int k2 = 0; k2 < T && derived_from[(size_t)k] < 0; k2++)
+                if (triples[2 * k2] == B && triples[2 * k2 + 1] == A && tr_off[(size_t)k2] < 0) {
+                    derived_from[(size_t)k] = k2;
+                    tr_off[(size_t)k2] = tr_total;
+                    der.push_back(TrDerived{k, A, tr_total, (int32_t)st.tiles.nsp[A]});
+                    tr_total += (int32_t)st.tiles.nsp[A];
+                }
+        }
+    }
+    std::vector<int4> fwork;
+    for (int k = 0; k < T; k++) {
+        int A = triples[2 * k], B = triples[2 * k + 1];
+        if (derived_from[(size_t)k] >= 0) continue;      // (its angles come from the lists of the triple searched from the other side)
+        for (int sa = 0; sa < S; sa++) {
+            if (!(A < 0 || sa == A)) continue;
+            // centres of a species that has no cutoff with any partner species of this triple find nothing
+            bool live = false;
+            for (int sb = 0; sb < S; sb++)
+                if ((B < 0 || sb == B) && cutoff[sa * S + sb] > 0.0 && st.tiles.nsp[sb] > 0) live = true;
+            if (!live) continue;
+            for (int64_t c0 = 0; c0 < st.tiles.nsp[sa]; c0 += NBRF_TILE) fwork.push_back(make_int4(k, (int)c0, sa, B));
+        }
+    }
+    void *d_fwork;
+    AMOF_TRY(upload(ctx, SLOT_AUX6, fwork.data(), fwork.size() * sizeof(int4), &d_fwork));
+    void *d_trtab = nullptr, *d_trlists = nullptr;
+    int n_twork = 0;
+    if (tr_total > 0) {
+        // one small table: tr_off[T] | inv_rank[N] | derived records | their work list; the lists shrink the frame
+        // batch if they must
+        std::vector<int2> twork;
+        for (size_t dd = 0; dd < der.size(); dd++)
+            for (int32_t c0 = 0; c0 < der[dd].count; c0 += 256) twork.push_back(make_int2((int)dd, c0));
+        n_twork = (int)twork.size();
+        std::vector<int32_t> tab((size_t)T + (size_t)t->n_atoms + 4 * der.size() + 2 * twork.size());
+        for (int k = 0; k < T; k++) tab[(size_t)k] = tr_off[(size_t)k];
+        for (int64_t x = 0; x < t->n_atoms; x++) {
+            const int32_t atom = st.tiles.perm[(size_t)x];
+            tab[(size_t)T + (size_t)atom] = (int32_t)(x - st.tiles.sp_first[t->species[atom]]);
+        }
+        memcpy(&tab[(size_t)T + (size_t)t->n_atoms], der.data(), der.size() * sizeof(TrDerived));
+        memcpy(&tab[(size_t)T + (size_t)t->n_atoms + 4 * der.size()], twork.data(), twork.size() * sizeof(int2));
+        AMOF_TRY(upload(ctx, SLOT_AUX8, tab.data(), tab.size() * sizeof(int32_t), &d_trtab));
+        const size_t per_frame = (size_t)tr_total * (1 + TR_CAP) * sizeof(uint32_t);
+        const int64_t fit = std::max<int64_t>(1, (int64_t)((size_t)1 << 30) / (int64_t)per_frame);
+        nf.FB = std::min<int64_t>(nf.FB, fit);
+        nf.FB0 = std::min<int64_t>(nf.FB0, nf.FB);
+        AMOF_TRY(ensure(ctx, SLOT_AUX9, (size_t)nf.FB * per_frame, &d_trlists));
+    }
+    nf.fa.a = st.a;
+    nf.fa.a.work = (const int4 *)d_fwork;
+    nf.fa.a.tr_total = tr_total;
+    if (tr_total > 0) {
+        nf.fa.a.tr_off = (const int32_t *)d_trtab;
+        nf.fa.a.inv_rank = (const int32_t *)d_trtab + T;
+        nf.fa.a.tcount = (uint32_t *)d_trlists;
+        nf.fa.a.tlist = (uint32_t *)d_trlists + (size_t)nf.FB * tr_total;
+    }
+    const size_t lds = 3 * (size_t)NBRF_UVCAP * sizeof(double) +
+                       (size_t)NBRF_NLIST * NBRF_TILE * sizeof(uint32_t) + NBRF_TILE * sizeof(uint32_t) +
+                       (NBRF_TILE + 4) * sizeof(int) + NBRF_UVCAP * sizeof(unsigned short) + c.lds_bins * sizeof(unsigned);
+    auto batch = [&](int64_t nfr, dim3 grid) -> int {
+        hipError_t e = with_flags(nf.ortho, nf.cell, [&](auto O, auto CELL) {
+            return launch_lds(bad_fast_kernel<O(), CELL()>, grid, dim3(NBRF_TILE), lds, ctx->stream, nf.fa);
+        });
+        AMOF_HIP_TRY(ctx, e);
+        if (tr_total > 0) {     // the angles of the triples that were not searched, from the lists just written
+            const TrDerived *d_der = reinterpret_cast<const TrDerived *>((const int32_t *)d_trtab + T + t->n_atoms);
+            const int2 *d_twork = reinterpret_cast<const int2 *>((const int32_t *)d_trtab + T + t->n_atoms + 4 * der.size());
+            NbrFastArgs ta = nf.fa;
+            unsigned tchunks;
+            pick_chunks(nfr, (size_t)n_twork, ta.a.frames_per_chunk, tchunks);
+            const dim3 tgrid((unsigned)n_twork, tchunks);
+            const size_t tlds = c.lds_bins * sizeof(unsigned);
+            e = with_flag(nf.ortho, [&](auto O) {
+                return launch_lds(bad_transposed_kernel<O()>, tgrid, dim3(256), tlds, ctx->stream, ta, d_der, d_twork);
+            });
+            AMOF_HIP_TRY(ctx, e);
+        }
+        return AMOF_OK;
+    };
+    int32_t qflag;
+    AMOF_TRY(nbr_fast_batches(ctx, t, st, nf, fwork.size(), true, batch, qflag));
+    int32_t flags[4];
+    AMOF_TRY(c.read_flags(flags));
+    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
+    // atoms absurdly far from the cell: redo with the exact kernel.  A centre with more than NBRF_NLIST neighbours: the
+    // exact kernel with its AMOF_MAX_NEIGHBOURS-deep LDS lists comes next (dense systems with 17..32 neighbours stay in
+    // LDS); only if that overflows too, the big-list pass
+    if (qflag || flags[1]) return c.clear_scratch();
+    c.done = true;
+    return AMOF_OK;
+}
+
+// exact kernel with its AMOF_MAX_NEIGHBOURS-deep LDS lists and, if a centre has more neighbours still, the big-list pass
+static int bad_exact_tier(BadCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    NbrSetup &st = c.st;
+    NbrArgs &a = st.a;
+    std::vector<int4> work;
+    for (int k = 0; k < c.T; k++) {
+        int A = c.triples[2 * k], B = c.triples[2 * k + 1];
+        for (int tl = 0; tl < (int)st.tiles.tiles.size(); tl++)
+            if (A < 0 || st.tiles.tiles[tl].species == A) work.push_back(make_int4(k, tl, A, B));
+    }
+    if (work.empty() || t->n_frames <= 0) return AMOF_OK;
+    void *d_work;       // (the exact kernels' work list: uploaded only when they run)
+    AMOF_TRY(upload(ctx, SLOT_PAIRS, work.data(), work.size() * sizeof(int4), &d_work));
+    a.work = (const int4 *)d_work;
+    const size_t lds_exact = (size_t)(3 * AMOF_MAX_NEIGHBOURS * BAD_TILE + 3 * BAD_TILE) * sizeof(double) +
+                             BAD_TILE * sizeof(int) + c.lds_bins * sizeof(unsigned);
+    auto launch_exact = [&](dim3 grid) -> hipError_t {
+        return with_flags(st.geom.all_ortho, st.max_img > 0, [&](auto O, auto EXTRA) {
+            return launch_lds(bad_kernel<O(), EXTRA()>, grid, dim3(BAD_TILE), lds_exact, ctx->stream, a);
+        });
+    };
+    int32_t flags[4];
+    unsigned chunks;
+    pick_chunks(t->n_frames, work.size(), a.frames_per_chunk, chunks);
+    timing_dom_begin(ctx, "bad_exact");
+    AMOF_HIP_TRY(ctx, launch_exact(dim3((unsigned)work.size(), chunks)));
+    timing_dom_end(ctx, 1);
+    AMOF_TRY(c.read_flags(flags));
+    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
+    if (!flags[1]) return AMOF_OK;
+    AMOF_TRY(c.clear_scratch());
+    // Big-list pass.  The reference has no limit on the neighbours of a centre (amof/bad.py:87-100): find the
+    // largest neighbour count with a counting pass of the exact kernel, then run that kernel once more with its
+    // per-centre lists of unit vectors in global scratch, [workgroup][3][cap][BAD_TILE] doubles.
+    a.count_only = 1;
+    AMOF_HIP_TRY(ctx, launch_exact(dim3((unsigned)work.size(), chunks)));
+    AMOF_TRY(c.read_flags(flags));
+    a.count_only = 0;
+    const int64_t cap = std::max<int64_t>(flags[2], 1);
+    const size_t per_wg = (size_t)3 * (size_t)cap * BAD_TILE * sizeof(double);
+    const size_t budget = (size_t)2 << 30;
+    // fewer, longer frame chunks until the scratch of all workgroups fits the budget
+    int64_t max_wg = std::max<int64_t>(1, (int64_t)(budget / per_wg));
+    int64_t nchunks = std::max<int64_t>(1, std::min<int64_t>(chunks, max_wg / (int64_t)work.size()));
+    a.frames_per_chunk = (int32_t)((t->n_frames + nchunks - 1) / nchunks);
+    nchunks = (t->n_frames + a.frames_per_chunk - 1) / a.frames_per_chunk;
+    void *d_nbuf;
+    AMOF_TRY(ensure(ctx, SLOT_AUX8, per_wg * work.size() * (size_t)nchunks, &d_nbuf));
+    a.nbuf = (double *)d_nbuf;
+    a.ncap = (int32_t)cap;
+    AMOF_TRY(c.clear_scratch());
+    timing_dom_begin(ctx, "bad_exact_biglist");
+    AMOF_HIP_TRY(ctx, launch_exact(dim3((unsigned)work.size(), (unsigned)nchunks)));
+    timing_dom_end(ctx, 1);
+    AMOF_TRY(c.read_flags(flags));
+    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
+    if (flags[1]) return fail(ctx, AMOF_EHIP, "internal error: neighbour list overflow in the big-list pass");
+    return AMOF_OK;
+}
+
+static int bad_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *triples,
+                   int32_t T, const double *edges, int32_t nb, unsigned long long *hist_dev,
+                   unsigned long long *nang_dev, int32_t cn_max = 0)
+{
+    BadCall c{{ctx, t, cutoff}, triples, T, nb, cn_max};
+    AMOF_TRY(nbr_setup(ctx, t, cutoff, BAD_TILE, c.st));
+    void *d_edges;
+    AMOF_TRY(upload(ctx, SLOT_AUX3, edges, (size_t)(nb + 1) * sizeof(double), &d_edges));
+    AMOF_TRY(ensure(ctx, SLOT_FLAGS, 4 * sizeof(int32_t), &c.d_flags));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(c.d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
+    NbrArgs &a = c.st.a;
+    a.edges = (const double *)d_edges;
+    a.nb = nb;
+    a.edge_step = 0.0;
+    if (edges[0] == 0.0 && !getenv("AMOF_BAD_EDGE_TABLE")) {
+        volatile double step = edges[1];
+        bool uniform = true;
+        for (int k = 0; k <= nb && uniform; k++) {
+            volatile double e = (double)k * step;      // (one IEEE multiplication, as numpy and the kernels do it)
+            uniform = e == edges[k];
+        }
+        if (uniform) a.edge_step = step;
+    }
+    a.flags = (int32_t *)c.d_flags;
+    a.cn_max = cn_max;
+    a.nbuf = nullptr;
+    a.ncap = 0;
+    a.count_only = 0;
+    a.global_hist = nb > AMOF_MAX_LDS_BINS - 16384 ? 1 : 0;      // (the reference has no limit on the bin count)
+    c.lds_bins = a.global_hist ? 0 : (size_t)nb;
+    c.KC = (size_t)(cn_max > 0 ? cn_max + 1 : 1);
+    c.hs_words = (size_t)T * c.KC * nb + (size_t)T * c.KC;
+    AMOF_TRY(ensure(ctx, SLOT_AUX7, c.hs_words * sizeof(unsigned long long), &c.d_hs));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(c.d_hs, 0, c.hs_words * sizeof(unsigned long long), ctx->stream));
+    a.hist = (unsigned long long *)c.d_hs;
+    a.n_angles = a.hist + (size_t)T * c.KC * nb;
+    AMOF_TRY(bad_frame_tier(c));
+    if (!c.done) AMOF_TRY(bad_gather_tier(c));
+    AMOF_TRY(stager_need(c.st.stage, t->n_frames));   // (no-op unless the fast path was skipped)
+    if (!c.done) AMOF_TRY(bad_exact_tier(c));
+    // complete and valid: add to the caller's (device) buffers
+    if (T > 0 && t->n_frames > 0) {
+        AMOF_TRY(add_into(ctx, (uint64_t *)hist_dev, (const uint64_t *)a.hist, (size_t)T * c.KC * nb));
+        AMOF_TRY(add_into(ctx, (uint64_t *)nang_dev, (const uint64_t *)a.n_angles, (size_t)T * c.KC));
+    }
+    timing_end(ctx);
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
     return AMOF_OK;
 }
 
@@ -2204,713 +2891,27 @@ extern "C" int amof_cn_count(amof_ctx *ctx, const amof_traj *t, const double *cu
         if (sets[2 * s] < 0 || sets[2 * s] >= S || sets[2 * s + 1] < 0 || sets[2 * s + 1] >= S)
             return fail(ctx, AMOF_EINVAL, "set %d names a species out of range", s);
     if (n_sets == 0 || t->n_frames == 0) return AMOF_OK;
-    NbrSetup st;
-    AMOF_TRY(nbr_setup(ctx, t, cutoff, CN_TILE, st));
-    std::vector<int4> work;
-    for (int s = 0; s < n_sets; s++) {
-        int A = sets[2 * s], B = sets[2 * s + 1];
-        for (int k = 0; k < st.tiles.sp_ntiles[A]; k++)
-            work.push_back(make_int4(s, st.tiles.sp_first_tile[A] + k, A, B));
-    }
-    const size_t F = (size_t)t->n_frames, N = (size_t)t->n_atoms;
-    void *d_sums, *d_pa = nullptr;
-    AMOF_TRY(ensure(ctx, SLOT_OUT0, F * n_sets * sizeof(int64_t), &d_sums));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_sums, 0, F * n_sets * sizeof(int64_t), ctx->stream));
+    CnCall c{{ctx, t, cutoff}, sets, n_sets, per_atom != nullptr};
+    AMOF_TRY(nbr_setup(ctx, t, cutoff, CN_TILE, c.st));
+    c.sums_bytes = (size_t)t->n_frames * n_sets * sizeof(int64_t);
+    AMOF_TRY(ensure(ctx, SLOT_OUT0, c.sums_bytes, &c.d_sums));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(c.d_sums, 0, c.sums_bytes, ctx->stream));
     if (per_atom) {
-        AMOF_TRY(ensure(ctx, SLOT_OUT1, F * n_sets * N * sizeof(int32_t), &d_pa));
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_pa, 0xFF, F * n_sets * N * sizeof(int32_t), ctx->stream));
+        c.pa_bytes = (size_t)t->n_frames * n_sets * (size_t)t->n_atoms * sizeof(int32_t);
+        AMOF_TRY(ensure(ctx, SLOT_OUT1, c.pa_bytes, &c.d_pa));
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(c.d_pa, 0xFF, c.pa_bytes, ctx->stream));
     }
-    NbrArgs &a = st.a;
+    NbrArgs &a = c.st.a;
     a.n_sets = n_sets;
-    a.sums = (unsigned long long *)d_sums;
-    a.per_atom = (int32_t *)d_pa;
-    bool done = false;
-    {
-        // whole-frame-in-LDS tier: every set with a cutoff is one item (a zero-cutoff set with per-atom output keeps the
-        // gather kernels: its centres still want their zeros)
-        NbrFrame nw;
-        double hmin[3];
-        AMOF_TRY(nbr_frame_prepare(t, cutoff, st, nw, hmin));
-        const bool tier_ok = nw.ok;
-        bool ok16 = false;
-        for (int pass = frame_first_pass(); pass < 3 && tier_ok; pass++) {
-            // 16-byte records first; if a pair then needs a whole CU's LDS, everything again with the 8-byte ones; if that
-            // does not bring two workgroups per CU either, the 16-byte ones stay -- unless they did not fit at all
-            nw.ok = true; nw.items.clear(); nw.lds = 0; nw.compact = pass == 1;
-            int64_t biggest = 0;
-            for (int s2 = 0; s2 < n_sets && nw.ok; s2++) {
-                const int A = sets[2 * s2], B = sets[2 * s2 + 1];
-                const int64_t nA = st.tiles.nsp[A], nB = st.tiles.nsp[B];
-                if (!(cutoff[A * S + B] > 0.0) || nA == 0 || nB == 0) { nw.ok = !per_atom; continue; }
-                FrameItem it{};
-                it.sa = A; it.sb = B; it.set = s2; it.reg_ab = it.reg_ba = -1;
-                nw.ok = frame_item_grid(hmin, cutoff[A * S + B], A == B ? nA : nA + nB, 1, nB, it, nw.lds,
-                                        nw.compact ? sizeof(uint2) : sizeof(uint4));
-                if (nw.ok) nw.items.push_back(it);
-                biggest = std::max(biggest, A == B ? nA : nA + nB);
-            }
-            if (pass == 0) ok16 = nw.ok;
-            if (frame_pass_done(pass, nw.ok, nw.lds, ok16)) break;
-        }
-        // pairs too big for one workgroup (or AMOF_NBR_SLABS=1): every pair in z-slabs, the streaming kernels
-        bool slabs = false;
-        if (tier_ok && !frame_slabs_forbidden() && (frame_slabs_forced() || !nw.ok)) {
-            bool zero_set = false;
-            slabs = frame_slab_passes([&](size_t budget, bool thin, std::vector<FrameItem> &out, size_t &lds) {
-                for (int s2 = 0; s2 < n_sets; s2++) {
-                    const int A = sets[2 * s2], B = sets[2 * s2 + 1];
-                    const int64_t nA = st.tiles.nsp[A], nB = st.tiles.nsp[B];
-                    if (!(cutoff[A * S + B] > 0.0) || nA == 0 || nB == 0) { zero_set = true; continue; }
-                    FrameItem it{};
-                    it.sa = A; it.sb = B; it.set = s2; it.reg_ab = it.reg_ba = -1;
-                    if (!frame_item_slabs(hmin, cutoff[A * S + B], nA, A == B ? 0 : nB, it, out, lds, budget, 0, 0, thin)) return false;
-                }
-                return true;
-            }, nw.items, nw.lds);
-            if (zero_set && per_atom) slabs = false;        // (a zero-cutoff set with per-atom output keeps the gather kernels)
-            if (slabs) { nw.ok = true; nw.compact = false; }
-            else if (frame_slabs_forced()) { nw.ok = false; }
-        }
-        if (nw.ok && !nw.items.empty()) {
-            AMOF_TRY(nbr_frame_commit(ctx, nw));
-            int64_t most = 0;
-            for (const FrameItem &it : nw.items)
-                most = std::max<int64_t>(most, st.tiles.nsp[it.sa] + (it.sa == it.sb ? 0 : st.tiles.nsp[it.sb]));
-            int64_t launches = 0;
-            int64_t FB = std::min<int64_t>(t->n_frames, 32768);
-            if (nw.compact) {       // (atom, rank) of every sorted position: at most 256 MB a batch
-                const size_t per_frame = nw.items.size() * (size_t)most * sizeof(uint2);
-                FB = std::max<int64_t>(1, std::min<int64_t>(FB, (int64_t)(((size_t)256 << 20) / per_frame)));
-                void *d_sidx;
-                AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)FB * per_frame, &d_sidx));
-                nw.fr.sidx = (uint2 *)d_sidx;
-                nw.fr.sidx_stride = (int32_t)most;
-            }
-            if (slabs) AMOF_TRY(frame_slab_buffers(ctx, t, nw, FB));
-            const int64_t FB0 = st.stage.lazy ? std::min<int64_t>(FB, 512) : FB;
-            for (int64_t fb = 0, cur = FB0; fb < t->n_frames; fb += cur, cur = std::min<int64_t>(2 * cur, FB)) {
-                const int64_t nfr = std::min<int64_t>(cur, t->n_frames - fb);
-                AMOF_TRY(stager_need(st.stage, fb + nfr));
-                nw.fr.f_base = (int32_t)fb;
-                nw.fr.nf = (int32_t)nfr;
-                if (launches == 0) timing_dom_begin(ctx, slabs ? "cn_frame_slabs" : "cn_frame");
-                if (slabs) AMOF_TRY(frame_slab_quantize(ctx, t, a, nw, fb, nfr));
-                const dim3 grid((unsigned)nw.items.size(), (unsigned)nfr);
-                auto launch = [&](auto kern) -> hipError_t {
-                    hipError_t e2 = allow_max_lds((const void *)kern);
-                    if (e2 == hipSuccess) hipLaunchKernelGGL(kern, grid, dim3(NBRW_THREADS), nw.lds, ctx->stream, a, nw.fr);
-                    return e2;
-                };
-                hipError_t e;
-                if (slabs) e = nw.ortho ? launch(cn_frame_kernel<true, 0, false>) : launch(cn_frame_kernel<false, 0, false>);
-                else if (most > 4 * NBRW_THREADS && nw.compact) e = nw.ortho ? launch(cn_frame_kernel<true, 8, true>) : launch(cn_frame_kernel<false, 8, true>);
-                else if (most > 4 * NBRW_THREADS) e = nw.ortho ? launch(cn_frame_kernel<true, 8, false>) : launch(cn_frame_kernel<false, 8, false>);
-                else if (nw.compact) e = nw.ortho ? launch(cn_frame_kernel<true, 4, true>) : launch(cn_frame_kernel<false, 4, true>);
-                else e = nw.ortho ? launch(cn_frame_kernel<true, 4, false>) : launch(cn_frame_kernel<false, 4, false>);
-                AMOF_HIP_TRY(ctx, e);
-                AMOF_HIP_TRY(ctx, hipGetLastError());
-                launches++;
-            }
-            timing_dom_end(ctx, launches);
-            int32_t qflag = 0;
-            AMOF_TRY(fetch(ctx, &qflag, nw.d_qflag, sizeof qflag));
-            AMOF_HIP_TRY(ctx, sync_stream(ctx));
-            if (qflag) {    // atoms absurdly far from the cell: the exact kernel answers (via the fast path's own check)
-                AMOF_HIP_TRY(ctx, hipMemsetAsync(d_sums, 0, F * n_sets * sizeof(int64_t), ctx->stream));
-                if (per_atom) AMOF_HIP_TRY(ctx, hipMemsetAsync(d_pa, 0xFF, F * n_sets * N * sizeof(int32_t), ctx->stream));
-            } else {
-                done = true;
-            }
-        } else if (nw.ok) {
-            done = true;        // no set has a cutoff and both species: every count is zero
-        }
-    }
-    NbrFast nf;
-    unsigned long long centre_mask = 0ull;
-    if (per_atom)
-        for (int s2 = 0; s2 < n_sets; s2++)
-            if (sets[2 * s2] < 64) centre_mask |= 1ull << sets[2 * s2];
-    if (!done) AMOF_TRY(nbr_fast_prepare(ctx, t, cutoff, st, nf, centre_mask));
-    if (nf.ok && !done) {
-        std::vector<int4> fwork;
-        for (int s2 = 0; s2 < n_sets; s2++) {
-            int A = sets[2 * s2], B = sets[2 * s2 + 1];
-            if (!(cutoff[A * S + B] > 0.0) && !per_atom) continue;      // counts stay zero (per_atom still wants its zeros)
-            for (int64_t c0 = 0; c0 < st.tiles.nsp[A]; c0 += NBRF_TILE) fwork.push_back(make_int4(s2, (int)c0, A, B));
-        }
-        void *d_fwork;
-        AMOF_TRY(upload(ctx, SLOT_AUX3, fwork.data(), fwork.size() * sizeof(int4), &d_fwork));
-        nf.fa.a = a;
-        nf.fa.a.work = (const int4 *)d_fwork;
-        int64_t launches = 0;
-        for (int64_t fb = 0, cur = nf.FB0; fb < t->n_frames && !fwork.empty(); fb += cur, cur = std::min<int64_t>(2 * cur, nf.FB)) {
-            const int64_t nfr = std::min<int64_t>(cur, t->n_frames - fb);
-            AMOF_TRY(stager_need(st.stage, fb + nfr));
-            AMOF_TRY(nbr_fast_batch(ctx, t, st, nf, fb, nfr));
-            unsigned chunks;
-            pick_chunks(nfr, fwork.size(), nf.fa.a.frames_per_chunk, chunks);
-            dim3 grid((unsigned)fwork.size(), chunks);
-            if (launches == 0) timing_dom_begin(ctx, nf.cell ? "cn_cell" : "cn_fast");
-            if (nf.cell && nf.ortho) hipLaunchKernelGGL((cn_fast_kernel<true, true>), grid, dim3(NBRF_TILE), 0, ctx->stream, nf.fa);
-            else if (nf.cell) hipLaunchKernelGGL((cn_fast_kernel<false, true>), grid, dim3(NBRF_TILE), 0, ctx->stream, nf.fa);
-            else if (nf.ortho) hipLaunchKernelGGL((cn_fast_kernel<true, false>), grid, dim3(NBRF_TILE), 0, ctx->stream, nf.fa);
-            else hipLaunchKernelGGL((cn_fast_kernel<false, false>), grid, dim3(NBRF_TILE), 0, ctx->stream, nf.fa);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-            launches++;
-        }
-        timing_dom_end(ctx, launches);
-        int32_t qflag = 0;
-        AMOF_TRY(fetch(ctx, &qflag, nf.d_qflag, sizeof qflag));
-        AMOF_HIP_TRY(ctx, sync_stream(ctx));
-        if (qflag) {   // atoms absurdly far from the cell: redo with the exact kernel
-            AMOF_HIP_TRY(ctx, hipMemsetAsync(d_sums, 0, F * n_sets * sizeof(int64_t), ctx->stream));
-        } else {
-            done = true;
-        }
-    }
-    AMOF_TRY(stager_need(st.stage, t->n_frames));   // (no-op unless the fast path was skipped)
-    if (!done && !work.empty()) {
-        void *d_work;       // (the exact kernel's work list: uploaded only when it runs)
-        AMOF_TRY(upload(ctx, SLOT_PAIRS, work.data(), work.size() * sizeof(int4), &d_work));
-        a.work = (const int4 *)d_work;
-        unsigned chunks;
-        pick_chunks(t->n_frames, work.size(), a.frames_per_chunk, chunks);
-        dim3 grid((unsigned)work.size(), chunks);
-        const bool extra = st.max_img > 0, ortho = st.geom.all_ortho;
-        timing_dom_begin(ctx, "cn_exact");
-        if (ortho && !extra) hipLaunchKernelGGL((cn_kernel<true, false>), grid, dim3(CN_TILE), 0, ctx->stream, a);
-        else if (ortho && extra) hipLaunchKernelGGL((cn_kernel<true, true>), grid, dim3(CN_TILE), 0, ctx->stream, a);
-        else if (!ortho && !extra) hipLaunchKernelGGL((cn_kernel<false, false>), grid, dim3(CN_TILE), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((cn_kernel<false, true>), grid, dim3(CN_TILE), 0, ctx->stream, a);
-        AMOF_HIP_TRY(ctx, hipGetLastError());
-        timing_dom_end(ctx, 1);
-    }
+    a.sums = (unsigned long long *)c.d_sums;
+    a.per_atom = (int32_t *)c.d_pa;
+    AMOF_TRY(cn_frame_tier(c));
+    if (!c.done) AMOF_TRY(cn_gather_tier(c));
+    AMOF_TRY(stager_need(c.st.stage, t->n_frames));   // (no-op unless the fast path was skipped)
+    if (!c.done) AMOF_TRY(cn_exact_tier(c));
     timing_end(ctx);
-    AMOF_TRY(fetch(ctx, sums, d_sums, F * n_sets * sizeof(int64_t)));
-    if (per_atom)
-        AMOF_TRY(fetch(ctx, per_atom, d_pa, F * n_sets * N * sizeof(int32_t)));
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    return AMOF_OK;
-}
-
-static int bad_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *triples,
-                   int32_t T, const double *edges, int32_t nb, unsigned long long *hist_dev,
-                   unsigned long long *nang_dev, int32_t cn_max = 0)
-{
-    NbrSetup st;
-    AMOF_TRY(nbr_setup(ctx, t, cutoff, BAD_TILE, st));
-    std::vector<int4> work;
-    for (int k = 0; k < T; k++) {
-        int A = triples[2 * k], B = triples[2 * k + 1];
-        for (int tl = 0; tl < (int)st.tiles.tiles.size(); tl++)
-            if (A < 0 || st.tiles.tiles[tl].species == A) work.push_back(make_int4(k, tl, A, B));
-    }
-    void *d_edges, *d_flags;
-    AMOF_TRY(upload(ctx, SLOT_AUX3, edges, (size_t)(nb + 1) * sizeof(double), &d_edges));
-    AMOF_TRY(ensure(ctx, SLOT_FLAGS, 4 * sizeof(int32_t), &d_flags));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
-    NbrArgs &a = st.a;
-    a.edges = (const double *)d_edges;
-    a.nb = nb;
-    a.edge_step = 0.0;
-    if (edges[0] == 0.0 && !getenv("AMOF_BAD_EDGE_TABLE")) {
-        volatile double step = edges[1];
-        bool uniform = true;
-        for (int k = 0; k <= nb && uniform; k++) {
-            volatile double e = (double)k * step;      // (one IEEE multiplication, as numpy and the kernels do it)
-            uniform = e == edges[k];
-        }
-        if (uniform) a.edge_step = step;
-    }
-    a.flags = (int32_t *)d_flags;
-    a.cn_max = cn_max;
-    a.nbuf = nullptr;
-    a.ncap = 0;
-    a.count_only = 0;
-    a.global_hist = nb > AMOF_MAX_LDS_BINS - 16384 ? 1 : 0;      // (the reference has no limit on the bin count)
-    const size_t lds_bins = a.global_hist ? 0 : (size_t)nb;
-    const size_t KC = (size_t)(cn_max > 0 ? cn_max + 1 : 1);   // histogram slots per triple
-    // every pass accumulates into scratch; the caller's buffers only ever receive a complete, valid result
-    const size_t hs_words = (size_t)T * KC * nb + (size_t)T * KC;
-    void *d_hs, *d_ns;
-    AMOF_TRY(ensure(ctx, SLOT_AUX7, hs_words * sizeof(unsigned long long), &d_hs));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_hs, 0, hs_words * sizeof(unsigned long long), ctx->stream));
-    d_ns = (unsigned long long *)d_hs + (size_t)T * KC * nb;
-    a.hist = (unsigned long long *)d_hs;
-    a.n_angles = (unsigned long long *)d_ns;
-    auto read_flags = [&](int32_t (&fl)[4]) -> int {
-        AMOF_TRY(fetch(ctx, fl, d_flags, sizeof fl));
-        AMOF_HIP_TRY(ctx, sync_stream(ctx));
-        return AMOF_OK;
-    };
-    auto clear_scratch = [&]() -> int {
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_hs, 0, hs_words * sizeof(unsigned long long), ctx->stream));
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
-        return AMOF_OK;
-    };
-    bool done = false, overflow = false;
-    int32_t flags[4] = {0, 0, 0, 0};
-    {
-        // ---- whole-frame-in-LDS tier: one sort + LDS search per species pair into neighbour rows, every triple from the rows
-        const int S = t->n_species;
-        NbrFrame nw;
-        double hmin[3];
-        AMOF_TRY(nbr_frame_prepare(t, cutoff, st, nw, hmin));
-        if (getenv("AMOF_BAD_NOTRANSPOSE")) nw.ok = false;      // (names the two-search gather kernels)
-        auto live_pair = [&](int x, int y) { return cutoff[x * S + y] > 0.0 && st.tiles.nsp[x] > 0 && st.tiles.nsp[y] > 0; };
-        std::vector<char> needed((size_t)S * S, 0);
-        std::vector<int4> awork;
-        for (int k = 0; k < T && nw.ok; k++) {
-            const int A = triples[2 * k], B = triples[2 * k + 1];
-            for (int sa = 0; sa < S; sa++) {
-                if (!(A < 0 || sa == A)) continue;
-                bool live = false;
-                for (int sb = 0; sb < S; sb++)
-                    if ((B < 0 || sb == B) && live_pair(sa, sb)) { needed[(size_t)sa * S + sb] = 1; live = true; }
-                if (live) awork.push_back(make_int4(k, sa, B, 0));
-            }
-        }
-        std::vector<int32_t> region_of((size_t)S * S, -1);
-        int64_t R = 0;
-        for (int x = 0; x < S * S && nw.ok; x++)
-            if (needed[(size_t)x]) { region_of[(size_t)x] = (int32_t)R; R += st.tiles.nsp[(size_t)(x / S)]; }
-        int64_t most = 0;
-        const bool tier_ok = nw.ok;
-        bool ok16 = false;
-        for (int pass = frame_first_pass(); pass < 3 && tier_ok; pass++) {
-            // 16-byte records first; if a pair then needs a whole CU's LDS, everything again with the 8-byte ones; if that
-            // does not bring two workgroups per CU either, the 16-byte ones stay -- unless they did not fit at all
-            nw.ok = true; nw.items.clear(); nw.lds = 0; nw.compact = pass == 1; most = 0;
-            for (int x = 0; x < S && nw.ok; x++)
-                for (int y = x; y < S && nw.ok; y++) {
-                    if (!needed[(size_t)x * S + y] && !needed[(size_t)y * S + x]) continue;
-                    FrameItem it{};
-                    it.sa = st.tiles.nsp[y] < st.tiles.nsp[x] ? y : x;      // the species with fewer atoms searches
-                    it.sb = it.sa == x ? y : x;
-                    it.set = 0;
-                    it.reg_ab = region_of[(size_t)it.sa * S + it.sb];
-                    it.reg_ba = x == y ? -1 : region_of[(size_t)it.sb * S + it.sa];
-                    const int64_t n = st.tiles.nsp[x] + (x == y ? 0 : st.tiles.nsp[y]);
-                    size_t lds_it = 0;
-                    nw.ok = frame_item_grid(hmin, cutoff[x * S + y], n, 1, st.tiles.nsp[it.sb], it, lds_it,
-                                            nw.compact ? sizeof(uint2) : sizeof(uint4),
-                                            (size_t)((n + 3) / 4) * 4 + (size_t)NBRW_HITS * sizeof(uint32_t));
-                    nw.lds = std::max(nw.lds, lds_it);
-                    most = std::max(most, n);
-                    if (nw.ok) nw.items.push_back(it);
-                }
-            if (pass == 0) ok16 = nw.ok;
-            if (frame_pass_done(pass, nw.ok, nw.lds, ok16)) break;
-        }
-        // pairs too big for one workgroup (or AMOF_NBR_SLABS=1): every pair in z-slabs, the streaming kernels
-        bool slabs = false, shared_rows = false;
-        if (tier_ok && !frame_slabs_forbidden() && (frame_slabs_forced() || !nw.ok)) {
-            slabs = frame_slab_passes([&](size_t budget, bool thin, std::vector<FrameItem> &out, size_t &lds) {
-                for (int x = 0; x < S; x++)
-                    for (int y = x; y < S; y++) {
-                        if (!needed[(size_t)x * S + y] && !needed[(size_t)y * S + x]) continue;
-                        FrameItem it{};
-                        it.sa = st.tiles.nsp[y] < st.tiles.nsp[x] ? y : x;      // the species with fewer atoms searches
-                        it.sb = it.sa == x ? y : x;
-                        it.set = 0;
-                        it.reg_ab = region_of[(size_t)it.sa * S + it.sb];
-                        it.reg_ba = x == y ? -1 : region_of[(size_t)it.sb * S + it.sa];
-                        if (!frame_item_slabs(hmin, cutoff[x * S + y], st.tiles.nsp[it.sa], x == y ? 0 : st.tiles.nsp[it.sb], it, out, lds,
-                                              budget, (size_t)NBRW_HITS * sizeof(uint32_t) + 4, 1, thin)) return false;
-                    }
-                return true;
-            }, nw.items, nw.lds);
-            if (slabs) {
-                nw.ok = true; nw.compact = false;
-                for (const FrameItem &it : nw.items) shared_rows = shared_rows || (it.cn != it.nzg && it.reg_ba >= 0);
-            } else if (frame_slabs_forced()) {
-                nw.ok = false;
-            }
-        }
-        if (nw.ok && !awork.empty() && R > 0 && R < (1ll << 30) && t->n_frames > 0) {
-            // merged angle passes: one per centre species, every angle computed once (histograms in LDS; BadByCn keys, more
-            // bins than LDS holds, a centre species with more than three partner species or a triple named twice keep
-            // the pass per triple)
-            std::vector<MergedItem> merged;
-            size_t lds_merged = 0;
-            if (cn_max == 0 && !a.global_hist && !getenv("AMOF_BAD_NOMERGE")) {
-                auto find_triple = [&](int A, int B, bool &twice) {
-                    int found = -1;
-                    for (int k = 0; k < T; k++)
-                        if (triples[2 * k] == A && triples[2 * k + 1] == B) { if (found >= 0) twice = true; else found = k; }
-                    return found;
-                };
-                bool usable = true, twice = false;
-                for (int sa = 0; sa < S && usable; sa++) {
-                    MergedItem mi{};
-                    mi.sa = sa;
-                    for (int q = 0; q < 3; q++) { mi.reg[q] = 0; mi.tb[q][0] = mi.tb[q][1] = -1; }
-                    for (int sb = 0; sb < S && usable; sb++) {
-                        if (region_of[(size_t)sa * S + sb] < 0) continue;
-                        if (mi.n_reg == 3) { usable = false; break; }
-                        mi.reg[mi.n_reg] = region_of[(size_t)sa * S + sb];
-                        mi.tb[mi.n_reg][0] = find_triple(sa, sb, twice);
-                        mi.tb[mi.n_reg][1] = find_triple(-1, sb, twice);
-                        mi.n_reg++;
-                    }
-                    mi.tx[0] = find_triple(sa, -1, twice);
-                    mi.tx[1] = find_triple(-1, -1, twice);
-                    if (mi.n_reg == 0) continue;
-                    bool any = mi.tx[0] >= 0 || mi.tx[1] >= 0;
-                    for (int q = 0; q < mi.n_reg; q++) any = any || mi.tb[q][0] >= 0 || mi.tb[q][1] >= 0;
-                    if (!any) continue;
-                    lds_merged = std::max(lds_merged, (size_t)(mi.n_reg + (mi.n_reg > 1 ? 1 : 0)) * lds_bins * sizeof(unsigned));
-                    merged.push_back(mi);
-                }
-                // (worth it when it saves passes: two triples over one species pair are two passes either way, and the pass
-                //  per triple keeps a centre's vectors in registers)
-                if (!usable || twice || lds_merged > 60 * 1024 || merged.size() >= awork.size()) merged.clear();
-            }
-            // one small table: angle work | region_of[S*S] | inv_rank[N]; the items beside it
-            std::vector<int32_t> tab(4 * awork.size() + (size_t)S * S + (size_t)t->n_atoms);
-            memcpy(tab.data(), awork.data(), awork.size() * sizeof(int4));
-            memcpy(&tab[4 * awork.size()], region_of.data(), region_of.size() * sizeof(int32_t));
-            for (int64_t x = 0; x < t->n_atoms; x++) {
-                const int32_t atom = st.tiles.perm[(size_t)x];
-                tab[4 * awork.size() + (size_t)S * S + (size_t)atom] = (int32_t)(x - nw.sp_first[(size_t)t->species[atom]]);
-            }
-            void *d_lists;
-            const int i_tab = nw.pk.add(tab.data(), tab.size() * sizeof(int32_t));
-            const int i_merged = nw.pk.add(merged.data(), merged.size() * sizeof(MergedItem));
-            AMOF_TRY(nbr_frame_commit(ctx, nw));
-            const int32_t *d_tab = nw.pk.ptr<int32_t>(i_tab);
-            const size_t per_frame = (size_t)R * (sizeof(uint32_t) + (size_t)NBRL_CAP * NBRL_EW * sizeof(double));
-            size_t rows_budget = (size_t)4 << 30;                          // <= 4 GiB of rows
-            if (const char *mb = getenv("AMOF_BAD_ROWS_MB")) rows_budget = (size_t)std::max(1, atoi(mb)) << 20;     // tests: many batches
-            int64_t FB = std::max<int64_t>(1, (int64_t)rows_budget / (int64_t)per_frame);
-            FB = std::min<int64_t>(FB, std::max<int64_t>(1, 0x7fffff00ll / std::max<int64_t>(1, t->n_atoms)));    // flat (frame, centre) index
-            FB = std::min<int64_t>(std::min<int64_t>(FB, 32768), t->n_frames);
-            size_t sidx_per_frame = 0;
-            if (nw.compact) {       // (atom, rank) of every sorted position: at most 256 MB a batch
-                sidx_per_frame = nw.items.size() * (size_t)most * sizeof(uint2);
-                FB = std::max<int64_t>(1, std::min<int64_t>(FB, (int64_t)(((size_t)256 << 20) / sidx_per_frame)));
-            }
-            // (a device short of memory gets smaller batches, not an error)
-            for (;;) {
-                const int rc_rows = ensure(ctx, SLOT_AUX9, (size_t)FB * per_frame, &d_lists);
-                if (rc_rows == AMOF_OK) break;
-                if (rc_rows != AMOF_ENOMEM || FB == 1) return rc_rows;
-                FB = std::max<int64_t>(1, FB / 4);
-            }
-            if (slabs) AMOF_TRY(frame_slab_buffers(ctx, t, nw, FB));
-            const int64_t FB0 = st.stage.lazy ? std::min<int64_t>(FB, 512) : FB;
-            if (nw.compact) {
-                void *d_sidx;
-                AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)FB * sidx_per_frame, &d_sidx));
-                nw.fr.sidx = (uint2 *)d_sidx;
-                nw.fr.sidx_stride = (int32_t)most;
-            }
-            NbrListArgs la;
-            const int4 *d_aw = (const int4 *)d_tab;
-            la.region_of = (const int32_t *)d_tab + 4 * awork.size();
-            la.inv_rank = la.region_of + (size_t)S * S;
-            la.rows = (double *)d_lists;                                   // (doubles first: 8-byte aligned)
-            la.count = (uint32_t *)(la.rows + (size_t)FB * R * NBRL_CAP * NBRL_EW);
-            la.R = (int32_t)R;
-            la.plane = (size_t)FB * (size_t)R;
-            const size_t lds_rows = lds_bins * sizeof(unsigned);
-            int64_t launches = 0;
-            for (int64_t fb = 0, cur = FB0; fb < t->n_frames; fb += cur, cur = std::min<int64_t>(2 * cur, FB)) {
-                const int64_t nfr = std::min<int64_t>(cur, t->n_frames - fb);
-                AMOF_TRY(stager_need(st.stage, fb + nfr));
-                nw.fr.f_base = (int32_t)fb;
-                nw.fr.nf = (int32_t)nfr;
-                if (launches == 0) timing_dom_begin(ctx, slabs ? "bad_frame_slabs" : "bad_frame");
-                if (slabs) AMOF_TRY(frame_slab_quantize(ctx, t, a, nw, fb, nfr));
-                if (shared_rows)    // (partners of several slabs claim their rows' slots with global atomics: the counts start at zero)
-                    AMOF_HIP_TRY(ctx, hipMemsetAsync(la.count, 0, (size_t)FB * (size_t)R * sizeof(uint32_t), ctx->stream));
-                const dim3 sgrid((unsigned)nw.items.size(), (unsigned)nfr);
-                auto launch = [&](auto kern) -> hipError_t {
-                    hipError_t e2 = allow_max_lds((const void *)kern);
-                    if (e2 == hipSuccess) hipLaunchKernelGGL(kern, sgrid, dim3(NBRW_THREADS), nw.lds, ctx->stream, a, nw.fr, la);
-                    return e2;
-                };
-                hipError_t e;
-                if (slabs) e = nw.ortho ? launch(lists_frame_kernel<true, 0, false>) : launch(lists_frame_kernel<false, 0, false>);
-                else if (most > 4 * NBRW_THREADS && nw.compact) e = nw.ortho ? launch(lists_frame_kernel<true, 8, true>) : launch(lists_frame_kernel<false, 8, true>);
-                else if (most > 4 * NBRW_THREADS) e = nw.ortho ? launch(lists_frame_kernel<true, 8, false>) : launch(lists_frame_kernel<false, 8, false>);
-                else if (nw.compact) e = nw.ortho ? launch(lists_frame_kernel<true, 4, true>) : launch(lists_frame_kernel<false, 4, true>);
-                else e = nw.ortho ? launch(lists_frame_kernel<true, 4, false>) : launch(lists_frame_kernel<false, 4, false>);
-                AMOF_HIP_TRY(ctx, e);
-                AMOF_HIP_TRY(ctx, hipGetLastError());
-                if (!merged.empty()) {
-                    // one pass per centre species: about 1024 workgroups of 512 lanes in all
-                    int64_t widest_m = 0;
-                    for (const MergedItem &mi : merged)
-                        widest_m = std::max<int64_t>(widest_m, (nfr * st.tiles.nsp[(size_t)mi.sa] + NBRM_THREADS - 1) / NBRM_THREADS);
-                    const int64_t gm = std::max<int64_t>(1, std::min<int64_t>(widest_m, (1024 + (int64_t)merged.size() - 1) / (int64_t)merged.size()));
-                    const dim3 mgrid((unsigned)gm, (unsigned)merged.size());
-                    const MergedItem *d_merged = nw.pk.ptr<MergedItem>(i_merged);
-                    if (nw.ortho) {
-                        e = allow_max_lds((const void *)bad_rows_merged_kernel<true>);
-                        if (e == hipSuccess) hipLaunchKernelGGL(bad_rows_merged_kernel<true>, mgrid, dim3(NBRM_THREADS), lds_merged, ctx->stream, a, la,
-                                                                d_merged, nw.d_spfirst, (int)nfr);
-                    } else {
-                        e = allow_max_lds((const void *)bad_rows_merged_kernel<false>);
-                        if (e == hipSuccess) hipLaunchKernelGGL(bad_rows_merged_kernel<false>, mgrid, dim3(NBRM_THREADS), lds_merged, ctx->stream, a, la,
-                                                                d_merged, nw.d_spfirst, (int)nfr);
-                    }
-                    AMOF_HIP_TRY(ctx, e);
-                    AMOF_HIP_TRY(ctx, hipGetLastError());
-                    launches++;
-                    continue;
-                }
-                // angle kernel: about eight workgroups per CU in all work items together, each striding over the tiles of its own
-                int64_t widest = 0;
-                for (const int4 &w : awork) widest = std::max<int64_t>(widest, (nfr * st.tiles.nsp[(size_t)w.y] + NBRF_TILE - 1) / NBRF_TILE);
-                // (every workgroup ends with one global atomic per non-empty bin of its histogram, all on the same few
-                //  addresses: 16 384 workgroups spent more time there than on the angles)
-                const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(widest, (2048 + (int64_t)awork.size() - 1) / (int64_t)awork.size()));
-                const dim3 agrid((unsigned)gx, (unsigned)awork.size());
-                if (nw.ortho) {
-                    e = allow_max_lds((const void *)bad_rows_kernel<true>);
-                    if (e == hipSuccess) hipLaunchKernelGGL(bad_rows_kernel<true>, agrid, dim3(NBRF_TILE), lds_rows, ctx->stream, a, la, d_aw,
-                                                            nw.d_spfirst, (int)nfr);
-                } else {
-                    e = allow_max_lds((const void *)bad_rows_kernel<false>);
-                    if (e == hipSuccess) hipLaunchKernelGGL(bad_rows_kernel<false>, agrid, dim3(NBRF_TILE), lds_rows, ctx->stream, a, la, d_aw,
-                                                            nw.d_spfirst, (int)nfr);
-                }
-                AMOF_HIP_TRY(ctx, e);
-                AMOF_HIP_TRY(ctx, hipGetLastError());
-                launches++;
-            }
-            timing_dom_end(ctx, launches);
-#ifdef NBR_PHASE_STAMPS
-            {
-                unsigned long long ph[16][5];
-                hipDeviceSynchronize();
-                hipMemcpyFromSymbol(ph, HIP_SYMBOL(nbr_phase_ticks), sizeof ph);
-                for (size_t e = 0; e < nw.items.size() && e < 16; e++)
-                    if (ph[e][4])
-                        fprintf(stderr, "lists entry %zu (species %d+%d, layers %d of %d, grid %dx%dx%d): us per workgroup: sort %.1f search + unit vectors (wave 0) %.1f (-) %.1f counts %.1f\n",
-                                e, nw.items[e].sa, nw.items[e].sb, nw.items[e].cn, nw.items[e].nzg, nw.items[e].nx, nw.items[e].ny, nw.items[e].nz,
-                                0.01 * ph[e][0] / ph[e][4], 0.01 * ph[e][1] / ph[e][4], 0.01 * ph[e][2] / ph[e][4], 0.01 * ph[e][3] / ph[e][4]);
-                memset(ph, 0, sizeof ph);
-                hipMemcpyToSymbol(HIP_SYMBOL(nbr_phase_ticks), ph, sizeof ph);
-            }
-#endif
-            int32_t qflag = 0;
-            AMOF_TRY(fetch(ctx, &qflag, nw.d_qflag, sizeof qflag));
-            AMOF_TRY(read_flags(flags));
-            if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-            if (qflag || flags[1]) {
-                // atoms absurdly far from the cell, or a centre with more than NBRL_CAP neighbours: the gather / exact kernels
-                AMOF_TRY(clear_scratch());
-            } else {
-                done = true;
-            }
-        } else if (nw.ok && awork.empty()) {
-            done = true;            // no triple has a centre with a cutoff to any of its partners: no angle
-        }
-    }
-    NbrFast nf;
-    if (!done) AMOF_TRY(nbr_fast_prepare(ctx, t, cutoff, st, nf));
-    if (nf.ok && !done && t->n_frames > 0) {
-        const int S = t->n_species;
-        // transposed lists: of two triples B-A-B / A-B-A over one species pair, only the side with fewer centres searches
-        std::vector<int32_t> derived_from((size_t)T, -1), tr_off((size_t)T, -1);
-        std::vector<TrDerived> der;
-        int32_t tr_total = 0;
-        if (!getenv("AMOF_BAD_NOTRANSPOSE")) {
-            for (int k = 0; k < T; k++) {
-                const int A = triples[2 * k], B = triples[2 * k + 1];
-                if (A < 0 || B < 0 || A == B || !(cutoff[A * S + B] > 0.0) || !(st.tiles.nsp[A] > st.tiles.nsp[B])) continue;
-                for (int k2 = 0; k2 < T && derived_from[(size_t)k] < 0; k2++)
-                    if (triples[2 * k2] == B && triples[2 * k2 + 1] == A && tr_off[(size_t)k2] < 0) {
-                        derived_from[(size_t)k] = k2;
-                        tr_off[(size_t)k2] = tr_total;
-                        der.push_back(TrDerived{k, A, tr_total, (int32_t)st.tiles.nsp[A]});
-                        tr_total += (int32_t)st.tiles.nsp[A];
-                    }
-            }
-        }
-        std::vector<int4> fwork;
-        for (int k = 0; k < T; k++) {
-            int A = triples[2 * k], B = triples[2 * k + 1];
-            if (derived_from[(size_t)k] >= 0) continue;      // (its angles come from the lists of the triple searched from the other side)
-            for (int sa = 0; sa < S; sa++) {
-                if (!(A < 0 || sa == A)) continue;
-                // centres of a species that has no cutoff with any partner species of this triple find nothing
-                bool live = false;
-                for (int sb = 0; sb < S; sb++)
-                    if ((B < 0 || sb == B) && cutoff[sa * S + sb] > 0.0 && st.tiles.nsp[sb] > 0) live = true;
-                if (!live) continue;
-                for (int64_t c0 = 0; c0 < st.tiles.nsp[sa]; c0 += NBRF_TILE) fwork.push_back(make_int4(k, (int)c0, sa, B));
-            }
-        }
-        void *d_fwork;
-        AMOF_TRY(upload(ctx, SLOT_AUX6, fwork.data(), fwork.size() * sizeof(int4), &d_fwork));
-        void *d_trtab = nullptr, *d_trlists = nullptr;
-        int n_twork = 0;
-        if (tr_total > 0) {
-            // one small table: tr_off[T] | inv_rank[N] | derived records | their work list; the lists shrink the frame
-            // batch if they must
-            std::vector<int2> twork;
-            for (size_t dd = 0; dd < der.size(); dd++)
-                for (int32_t c0 = 0; c0 < der[dd].count; c0 += 256) twork.push_back(make_int2((int)dd, c0));
-            n_twork = (int)twork.size();
-            std::vector<int32_t> tab((size_t)T + (size_t)t->n_atoms + 4 * der.size() + 2 * twork.size());
-            for (int k = 0; k < T; k++) tab[(size_t)k] = tr_off[(size_t)k];
-            for (int64_t x = 0; x < t->n_atoms; x++) {
-                const int32_t atom = st.tiles.perm[(size_t)x];
-                tab[(size_t)T + (size_t)atom] = (int32_t)(x - nf.sp_first[t->species[atom]]);
-            }
-            memcpy(&tab[(size_t)T + (size_t)t->n_atoms], der.data(), der.size() * sizeof(TrDerived));
-            memcpy(&tab[(size_t)T + (size_t)t->n_atoms + 4 * der.size()], twork.data(), twork.size() * sizeof(int2));
-            AMOF_TRY(upload(ctx, SLOT_AUX8, tab.data(), tab.size() * sizeof(int32_t), &d_trtab));
-            const size_t per_frame = (size_t)tr_total * (1 + TR_CAP) * sizeof(uint32_t);
-            const int64_t fit = std::max<int64_t>(1, (int64_t)((size_t)1 << 30) / (int64_t)per_frame);
-            nf.FB = std::min<int64_t>(nf.FB, fit);
-            nf.FB0 = std::min<int64_t>(nf.FB0, nf.FB);
-            AMOF_TRY(ensure(ctx, SLOT_AUX9, (size_t)nf.FB * per_frame, &d_trlists));
-        }
-        nf.fa.a = a;
-        nf.fa.a.work = (const int4 *)d_fwork;
-        nf.fa.a.tr_total = tr_total;
-        if (tr_total > 0) {
-            nf.fa.a.tr_off = (const int32_t *)d_trtab;
-            nf.fa.a.inv_rank = (const int32_t *)d_trtab + T;
-            nf.fa.a.tcount = (uint32_t *)d_trlists;
-            nf.fa.a.tlist = (uint32_t *)d_trlists + (size_t)nf.FB * tr_total;
-        }
-        size_t lds = 3 * (size_t)NBRF_UVCAP * sizeof(double) +
-                     (size_t)NBRF_NLIST * NBRF_TILE * sizeof(uint32_t) + NBRF_TILE * sizeof(uint32_t) +
-                     (NBRF_TILE + 4) * sizeof(int) + NBRF_UVCAP * sizeof(unsigned short) + lds_bins * sizeof(unsigned);
-        int64_t launches = 0;
-        for (int64_t fb = 0, cur = nf.FB0; fb < t->n_frames && !fwork.empty(); fb += cur, cur = std::min<int64_t>(2 * cur, nf.FB)) {
-            const int64_t nfr = std::min<int64_t>(cur, t->n_frames - fb);
-            AMOF_TRY(stager_need(st.stage, fb + nfr));
-            AMOF_TRY(nbr_fast_batch(ctx, t, st, nf, fb, nfr));
-            if (tr_total > 0)
-                AMOF_HIP_TRY(ctx, hipMemsetAsync(nf.fa.a.tcount, 0, (size_t)nfr * tr_total * sizeof(uint32_t), ctx->stream));
-            unsigned chunks;
-            pick_chunks(nfr, fwork.size(), nf.fa.a.frames_per_chunk, chunks);
-            dim3 grid((unsigned)fwork.size(), chunks);
-            if (launches == 0) timing_dom_begin(ctx, nf.cell ? "bad_cell" : "bad_fast");
-            auto launch = [&](auto kern) -> hipError_t {
-                hipError_t e2 = allow_max_lds((const void *)kern);
-                if (e2 == hipSuccess) hipLaunchKernelGGL(kern, grid, dim3(NBRF_TILE), lds, ctx->stream, nf.fa);
-                return e2;
-            };
-            hipError_t e;
-            if (nf.cell && nf.ortho) e = launch(bad_fast_kernel<true, true>);
-            else if (nf.cell) e = launch(bad_fast_kernel<false, true>);
-            else if (nf.ortho) e = launch(bad_fast_kernel<true, false>);
-            else e = launch(bad_fast_kernel<false, false>);
-            AMOF_HIP_TRY(ctx, e);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-            if (tr_total > 0) {     // the angles of the triples that were not searched, from the lists just written
-                const TrDerived *d_der = reinterpret_cast<const TrDerived *>((const int32_t *)d_trtab + T + t->n_atoms);
-                const int2 *d_twork = reinterpret_cast<const int2 *>((const int32_t *)d_trtab + T + t->n_atoms + 4 * der.size());
-                NbrFastArgs ta = nf.fa;
-                unsigned tchunks;
-                pick_chunks(nfr, (size_t)n_twork, ta.a.frames_per_chunk, tchunks);
-                dim3 tgrid((unsigned)n_twork, tchunks);
-                const size_t tlds = lds_bins * sizeof(unsigned);
-                hipError_t e3;
-                if (nf.ortho) {
-                    e3 = allow_max_lds((const void *)bad_transposed_kernel<true>);
-                    if (e3 == hipSuccess) hipLaunchKernelGGL(bad_transposed_kernel<true>, tgrid, dim3(256), tlds, ctx->stream, ta, d_der, d_twork);
-                } else {
-                    e3 = allow_max_lds((const void *)bad_transposed_kernel<false>);
-                    if (e3 == hipSuccess) hipLaunchKernelGGL(bad_transposed_kernel<false>, tgrid, dim3(256), tlds, ctx->stream, ta, d_der, d_twork);
-                }
-                AMOF_HIP_TRY(ctx, e3);
-                AMOF_HIP_TRY(ctx, hipGetLastError());
-            }
-            launches++;
-        }
-        timing_dom_end(ctx, launches);
-        int32_t qflag = 0;
-        AMOF_TRY(fetch(ctx, &qflag, nf.d_qflag, sizeof qflag));
-        AMOF_TRY(read_flags(flags));
-        if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-        if (qflag) {           // atoms absurdly far from the cell: redo with the exact kernel
-            AMOF_TRY(clear_scratch());
-        } else if (flags[1]) {
-            // a centre has more than NBRF_NLIST neighbours: the exact kernel with its AMOF_MAX_NEIGHBOURS-deep LDS lists
-            // comes next (dense systems with 17..32 neighbours stay in LDS); only if that overflows too, the big-list pass
-            AMOF_TRY(clear_scratch());
-        } else {
-            done = true;
-        }
-    }
-    AMOF_TRY(stager_need(st.stage, t->n_frames));   // (no-op unless the fast path was skipped)
-    const bool extra = st.max_img > 0, ortho = st.geom.all_ortho;
-    const size_t lds_exact = (size_t)(3 * AMOF_MAX_NEIGHBOURS * BAD_TILE + 3 * BAD_TILE) * sizeof(double) +
-                             BAD_TILE * sizeof(int) + lds_bins * sizeof(unsigned);
-    if (!done && !work.empty() && t->n_frames > 0) {      // (the exact kernels' work list: uploaded only when they run)
-        void *d_work;
-        AMOF_TRY(upload(ctx, SLOT_PAIRS, work.data(), work.size() * sizeof(int4), &d_work));
-        a.work = (const int4 *)d_work;
-    }
-    auto launch_exact = [&](dim3 grid) -> hipError_t {
-        auto launch = [&](auto kern) -> hipError_t {
-            hipError_t e = allow_max_lds((const void *)kern);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid, dim3(BAD_TILE), lds_exact, ctx->stream, a);
-            return hipGetLastError();
-        };
-        if (ortho && !extra) return launch(bad_kernel<true, false>);
-        if (ortho && extra) return launch(bad_kernel<true, true>);
-        if (!ortho && !extra) return launch(bad_kernel<false, false>);
-        return launch(bad_kernel<false, true>);
-    };
-    if (!done && !overflow && !work.empty() && t->n_frames > 0) {
-        unsigned chunks;
-        pick_chunks(t->n_frames, work.size(), a.frames_per_chunk, chunks);
-        timing_dom_begin(ctx, "bad_exact");
-        AMOF_HIP_TRY(ctx, launch_exact(dim3((unsigned)work.size(), chunks)));
-        timing_dom_end(ctx, 1);
-        AMOF_TRY(read_flags(flags));
-        if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-        if (flags[1]) {
-            overflow = true;
-            AMOF_TRY(clear_scratch());
-        }
-    }
-    if (overflow && !work.empty() && t->n_frames > 0) {
-        // Big-list pass.  The reference has no limit on the neighbours of a centre (amof/bad.py:87-100): find the
-        // largest neighbour count with a counting pass of the exact kernel, then run that kernel once more with its
-        // per-centre lists of unit vectors in global scratch, [workgroup][3][cap][BAD_TILE] doubles.
-        unsigned chunks;
-        pick_chunks(t->n_frames, work.size(), a.frames_per_chunk, chunks);
-        a.count_only = 1;
-        AMOF_HIP_TRY(ctx, launch_exact(dim3((unsigned)work.size(), chunks)));
-        AMOF_TRY(read_flags(flags));
-        a.count_only = 0;
-        const int64_t cap = std::max<int64_t>(flags[2], 1);
-        const size_t per_wg = (size_t)3 * (size_t)cap * BAD_TILE * sizeof(double);
-        const size_t budget = (size_t)2 << 30;
-        // fewer, longer frame chunks until the scratch of all workgroups fits the budget
-        int64_t max_wg = std::max<int64_t>(1, (int64_t)(budget / per_wg));
-        int64_t nchunks = std::max<int64_t>(1, std::min<int64_t>(chunks, max_wg / (int64_t)work.size()));
-        a.frames_per_chunk = (int32_t)((t->n_frames + nchunks - 1) / nchunks);
-        nchunks = (t->n_frames + a.frames_per_chunk - 1) / a.frames_per_chunk;
-        void *d_nbuf;
-        AMOF_TRY(ensure(ctx, SLOT_AUX8, per_wg * work.size() * (size_t)nchunks, &d_nbuf));
-        a.nbuf = (double *)d_nbuf;
-        a.ncap = (int32_t)cap;
-        AMOF_TRY(clear_scratch());
-        timing_dom_begin(ctx, "bad_exact_biglist");
-        AMOF_HIP_TRY(ctx, launch_exact(dim3((unsigned)work.size(), (unsigned)nchunks)));
-        timing_dom_end(ctx, 1);
-        AMOF_TRY(read_flags(flags));
-        if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-        if (flags[1]) return fail(ctx, AMOF_EHIP, "internal error: neighbour list overflow in the big-list pass");
-    }
-    // complete and valid: add to the caller's (device) buffers
-    if (T > 0 && t->n_frames > 0) {
-        AMOF_TRY(add_into(ctx, (uint64_t *)hist_dev, (const uint64_t *)d_hs, (size_t)T * KC * nb));
-        AMOF_TRY(add_into(ctx, (uint64_t *)nang_dev, (const uint64_t *)d_ns, (size_t)T * KC));
-    }
-    timing_end(ctx);
+    AMOF_TRY(fetch(ctx, sums, c.d_sums, c.sums_bytes));
+    if (per_atom) AMOF_TRY(fetch(ctx, per_atom, c.d_pa, c.pa_bytes));
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     return AMOF_OK;
 }
@@ -2941,23 +2942,31 @@ extern "C" int amof_bad_hist_dev(amof_ctx *ctx, const amof_traj *t, const double
                    (unsigned long long *)n_angles_dev);
 }
 
+// the host-array entry points: the caller's counters to the device, bad_run adds into them, back again
+// (cn_max = 0: one histogram per triple; BadByCn: cn_max + 1 of them)
+static int bad_hist_host(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *triples, int32_t T,
+                         const double *edges, int32_t nb, int32_t cn_max, uint64_t *hist, uint64_t *n_angles)
+{
+    if (T == 0) return AMOF_OK;
+    AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    void *d_hist, *d_nang;
+    const size_t KC = (size_t)(cn_max > 0 ? cn_max + 1 : 1);
+    const size_t hb = (size_t)T * KC * nb * sizeof(uint64_t), nbts = (size_t)T * KC * sizeof(uint64_t);
+    AMOF_TRY(upload(ctx, SLOT_OUT0, hist, hb, &d_hist));
+    AMOF_TRY(upload(ctx, SLOT_OUT1, n_angles, nbts, &d_nang));
+    AMOF_TRY(bad_run(ctx, t, cutoff, triples, T, edges, nb, (unsigned long long *)d_hist, (unsigned long long *)d_nang, cn_max));
+    AMOF_TRY(fetch(ctx, hist, d_hist, hb));
+    AMOF_TRY(fetch(ctx, n_angles, d_nang, nbts));
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
+    return AMOF_OK;
+}
+
 extern "C" int amof_bad_hist(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *triples,
                              int32_t T, const double *edges, int32_t nb, uint64_t *hist, uint64_t *n_angles)
 {
     if (!ctx) return AMOF_EINVAL;
     AMOF_TRY(bad_check(ctx, t, cutoff, triples, T, edges, nb, hist, n_angles));
-    if (T == 0) return AMOF_OK;
-    AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void *d_hist, *d_nang;
-    size_t hb = (size_t)T * nb * sizeof(uint64_t), nbts = (size_t)T * sizeof(uint64_t);
-    AMOF_TRY(upload(ctx, SLOT_OUT0, hist, hb, &d_hist));
-    AMOF_TRY(upload(ctx, SLOT_OUT1, n_angles, nbts, &d_nang));
-    int rc = bad_run(ctx, t, cutoff, triples, T, edges, nb, (unsigned long long *)d_hist, (unsigned long long *)d_nang);
-    if (rc) return rc;
-    AMOF_TRY(fetch(ctx, hist, d_hist, hb));
-    AMOF_TRY(fetch(ctx, n_angles, d_nang, nbts));
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    return AMOF_OK;
+    return bad_hist_host(ctx, t, cutoff, triples, T, edges, nb, 0, hist, n_angles);
 }
 
 extern "C" int amof_bad_hist_by_cn(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *triples,
@@ -2967,17 +2976,5 @@ extern "C" int amof_bad_hist_by_cn(amof_ctx *ctx, const amof_traj *t, const doub
     if (!ctx) return AMOF_EINVAL;
     AMOF_TRY(bad_check(ctx, t, cutoff, triples, T, edges, nb, hist, n_angles));
     if (cn_max < 1 || cn_max > 65535) return fail(ctx, AMOF_EINVAL, "cn_max must be 1..65535");
-    if (T == 0) return AMOF_OK;
-    AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    void *d_hist, *d_nang;
-    const size_t KC = (size_t)cn_max + 1;
-    size_t hb = (size_t)T * KC * nb * sizeof(uint64_t), nbts = (size_t)T * KC * sizeof(uint64_t);
-    AMOF_TRY(upload(ctx, SLOT_OUT0, hist, hb, &d_hist));
-    AMOF_TRY(upload(ctx, SLOT_OUT1, n_angles, nbts, &d_nang));
-    int rc = bad_run(ctx, t, cutoff, triples, T, edges, nb, (unsigned long long *)d_hist, (unsigned long long *)d_nang, cn_max);
-    if (rc) return rc;
-    AMOF_TRY(fetch(ctx, hist, d_hist, hb));
-    AMOF_TRY(fetch(ctx, n_angles, d_nang, nbts));
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    return AMOF_OK;
+    return bad_hist_host(ctx, t, cutoff, triples, T, edges, nb, cn_max, hist, n_angles);
 }

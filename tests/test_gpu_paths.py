@@ -760,6 +760,38 @@ def test_frame_tier_atom_count_boundaries(hip_ctx, n_pair):
         assert np.array_equal(hg[0], hr[0]) and np.array_equal(hg[1], hr[1]), (n_pair, split)
 
 
+@pytest.mark.parametrize("compact", ["0", "1"])
+@pytest.mark.parametrize("cell", ["diagonal", "sheared"])
+def test_frame_tier_eight_atoms_per_thread_forced_record_size(hip_ctx, monkeypatch, cell, compact):
+    """More than 4096 atoms in a pair (the 8-atoms-per-thread kernels) with the record size forced either way
+    (AMOF_NBR_COMPACT), on a diagonal and on a sheared cell: one species of 4097 atoms, and 4100 atoms split one third /
+    two thirds, where the mixed pair is past 4096 and the smaller same-species pair is not"""
+    monkeypatch.setenv("AMOF_NBR_COMPACT", compact)
+    edges = np.arange(182) * 1.0
+    for n_atoms, split in ((4097, 4097), (4100, 4100 // 3)):
+        rng = np.random.default_rng(n_atoms)
+        L = (n_atoms / 0.06) ** (1 / 3)
+        c = np.diag([L, 1.1 * L, 0.9 * L])
+        if cell == "sheared":
+            c = c + np.array([[0, 0, 0], [3.1, 0, 0], [-2.3, 2.9, 0]])
+        numbers = np.where(np.arange(n_atoms) < split, 30, 7)
+        pos = rng.uniform(0, 1, (2, n_atoms, 3)) @ c
+        packed = PackedTrajectory(pos, c, numbers)
+        kinds, sp = H.species_of(packed.numbers)
+        S = len(kinds)
+        rcm = np.full((S, S), 2.2)
+        sets = [(a, b) for a in range(S) for b in range(S)]
+        got = hip_ctx.cn_count(packed, rcm, sets, per_atom=True)
+        assert hip_ctx.last_path() == "cn_frame", (n_atoms, hip_ctx.last_path())
+        ref = clib.cn_counts(packed.pos, packed.cell, sp, S, rcm, sets, per_atom=True)
+        assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]), n_atoms
+        triples = [(0, 0), (0, -1), (-1, -1)] if S == 1 else [(0, 1), (1, 0), (1, -1), (-1, -1)]
+        hg = hip_ctx.bad_hist(packed, rcm, triples, edges)
+        assert hip_ctx.last_path() == "bad_frame", (n_atoms, hip_ctx.last_path())
+        hr = clib.bad_hist(packed.pos, packed.cell, sp, S, rcm, triples, edges)
+        assert np.array_equal(hg[0], hr[0]) and np.array_equal(hg[1], hr[1]), n_atoms
+
+
 @pytest.mark.parametrize("ortho", [True, False])
 def test_frame_tier_in_slabs_forced_on_small_frames(hip_ctx, monkeypatch, ortho):
     """AMOF_NBR_SLABS=1 sends pairs that fit one workgroup through the streaming slab kernels (one or several z-slabs per
