@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "amof_internal.h"
+#include "tile_plan.h"
 
 namespace amof {
 
@@ -242,6 +243,8 @@ struct RdfFastArgs {
     int32_t img_defer;       // 1: two small buffers, a step's parked pairs are evaluated at the start of the next step
                              // (no extra barrier); 0: one large buffer, evaluated at the end of the step
     int32_t noreach;         // rdf_tile_zf with slab culling: 1 = every quad of a diagonal tile pair masked (AMOF_RDF_NOREACH)
+    int32_t plan_noskip;     // PLAN: 1 = steps without a quad to visit are run all the same (AMOF_RDF_PLAN_NOSKIP: measurements)
+    const uint4 *plan;       // PLAN: [pairs][nf][4] one TilePlanRecord per step, pair-major (rdf_tile_plan_kernel, tile_plan.h)
 };
 
 constexpr int FAST_THREADS = 256;
@@ -790,6 +793,7 @@ __device__ __forceinline__ void fast_quad_tri(unsigned *hist, const RdfFastArgs 
 // share the quads of tile J round-robin, so the slab culling -- which depends only on the
 // centre atoms' slab range -- removes the same share of work from every wave.
 constexpr int FAST_SUB = 128;
+static_assert(FAST_SUB == TILE_PLAN_SUB && FAST_TILE == TILE_PLAN_MAX_SUBS * TILE_PLAN_SUB && QSLABS == TILE_PLAN_SLABS, "tile_plan.h");
 
 // One wave copies 64 x 16 B from per-lane global addresses to 1 KiB of LDS at `dst`
 // (wave-uniform), without passing through registers (LDS-DMA, global_load_lds_dwordx4).
@@ -798,7 +802,7 @@ __device__ __forceinline__ void dma_1k(const QAtom *src_lane, uint4 *dst_wave)
     dma16(src_lane, dst_wave);
 }
 
-template <bool ORTHO, bool CULL, bool IMG = false, bool ZFK = false, int TRI = -1>
+template <bool ORTHO, bool CULL, bool IMG = false, bool ZFK = false, int TRI = -1, bool PLAN = false>
 // (five workgroups per CU, 96 VGPRs.  The TRI variants once spilled 136 - 240 bytes per lane at that budget -- 7x the vector-
 //  memory instructions of the diagonal kernel -- and the ones with near tests in the fast path ran better at four workgroups
 //  and 128 VGPRs; since their slow path reads the partner's record from LDS again and the canonical fallback of a full queue
@@ -819,6 +823,12 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
     // body -- partners behind it satisfy j > ia and j > ib always and go through the unmasked loop and the ragged tail quad,
     // like an off-diagonal pair (fa.noreach: every quad masked, as before).  Its quad loops use the SLIM form of fast_quad.
     constexpr bool REACH = ORTHO && CULL && ZFK && !IMG && TRI < 0;
+    // PLAN (REACH only): a step's partner window comes from its record of fa.plan (rdf_tile_plan_kernel: the window arithmetic
+    // of tile_plan.h over the quantiser's slab table, once per step instead of ballots over sampled quads in every wave), and a
+    // step without a quad to visit is not run at all: no centres staged, no barrier; a frame without a live step stages no
+    // tile J, a work item without one returns at once.  Chunks of at most 16 frames (the host launches the kernel without
+    // a plan otherwise): the live steps of the chunk are one 64-bit mask.
+    static_assert(!PLAN || REACH, "PLAN: the slab-culled diagonal-cell kernel on f32 slab coordinates");
     // TRI = 10 / 11: near mode 4 with the exact-half x wrap, c10 = + 1/2 / - 1/2 (tri_q_twin)
     constexpr int NEAR = TRI >= 10 ? 4 : (TRI >= 0 ? TRI % 5 : 0);
     constexpr bool XW = TRI >= 5;
@@ -862,7 +872,8 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
     const Tile tj = a.tiles[pr.y];
     const bool diag = pr.x == pr.y;
     const int nbins = a.nbins;
-    for (int k = tid; k < nbins; k += FAST_THREADS) hist[k] = 0u;
+    if constexpr (!PLAN)
+        for (int k = tid; k < nbins; k += FAST_THREADS) hist[k] = 0u;
 
     // equal shares (+-1 frame): with the XCD mapping n_chunks is a multiple of 8, so every XCD gets the same work
     // (with the XCD mapping, XCD x owns the contiguous frame range [x nf/8, (x+1) nf/8), cut into n_chunks/8 shares)
@@ -900,18 +911,50 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
             dma_1k(Qf + ti.start + sub * FAST_SUB + min(wave * 64 + lane, cnt - 1), tcb + cb * FAST_SUB + wave * 64);
     };
 
-    const int nsteps = (f1 - f0) * nsub;
+    // PLAN: bit 4 (fl - f0) + sub of `live` = that step is still to run; the records of this work item's chunk
+    // (read through the constant address space, so that a step's record arrives by one scalar load that the step before
+    //  issued: as an ordinary load it is a vector load, a wait and three v_readfirstlane behind every barrier)
+    typedef uint32_t plan_rec_t __attribute__((ext_vector_type(4)));
+    typedef const plan_rec_t __attribute__((address_space(4))) *plan_ptr_t;
+    unsigned long long live = 0ull;
+    const uint4 *__restrict__ plan_wg = nullptr;
+    plan_ptr_t plan_c = nullptr;
+    if constexpr (PLAN) {
+        plan_wg = fa.plan + ((size_t)bx * (size_t)fa.nf + (size_t)f0) * TILE_PLAN_MAX_SUBS;
+        plan_c = (plan_ptr_t)(uintptr_t)plan_wg;
+        bool lv = false;
+        if (f0 + (lane >> 2) < f1 && (lane & 3) < nsub)
+            lv = fa.plan_noskip || ((plan_wg[lane].z >> 16) & TILE_PLAN_LIVE) != 0u;
+        live = __ballot(lv);
+        if (live == 0ull) return;       // (nothing to zero, nothing to flush)
+        for (int k = tid; k < nbins; k += FAST_THREADS) hist[k] = 0u;
+    }
+    const int nsteps = PLAN ? __popcll(live) : (f1 - f0) * nsub;
     if (QUEUE && tid < 3) nq_count[tid] = 0u;
     const double *p_prev = nullptr, *g_prev = nullptr;
     int gi_prev = 0;
-    if (nsteps > 0) { stage_j(f0, 0); stage_c(f0, 0, 0); }
+    int fl = f0, sub = 0;
+    int jbp = 0, fl_j = -1;         // PLAN: the J buffer in use and the frame it holds
+    plan_rec_t rec_next = {0u, 0u, 0u, 0u};
+    if constexpr (PLAN) {
+        const int bit = __builtin_amdgcn_readfirstlane(__ffsll((long long)live) - 1);
+        fl = f0 + (bit >> 2); sub = bit & 3;
+        rec_next = plan_c[bit];
+    }
+    if (nsteps > 0) { stage_j(fl, 0); stage_c(fl, sub, 0); }
     float sc[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     double sc64r[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     TriConst trc = {0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u};
     float near_f[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
     uint32_t cull_gap = 0u;
-    for (int step = 0, fl = f0, sub = 0; step < nsteps; step++) {
-        const int jb = (fl - f0) & 1, cbuf = step & 1;
+    for (int step = 0; step < nsteps; step++) {
+        // PLAN: steps count the live ones; the first live step of a frame turns to the other J buffer
+        const bool new_frame = PLAN && fl != fl_j;
+        if (PLAN && new_frame) { if (fl_j >= 0) jbp = __builtin_amdgcn_readfirstlane(jbp ^ 1); fl_j = fl; }
+        const unsigned long long rest = live & (live - 1ull);          // PLAN: the live steps behind this one
+        const int bit_next = PLAN && rest ? __builtin_amdgcn_readfirstlane(__ffsll((long long)rest) - 1) : 0;
+        const plan_rec_t rec = rec_next;
+        const int jb = PLAN ? jbp : (fl - f0) & 1, cbuf = step & 1;
         const int cnti = min(FAST_SUB, ti.count - sub * FAST_SUB);     // centre atoms of this sub-tile
         const int ia = sub * FAST_SUB + la, ib = ia + 1;               // indices in tile I
         const bool has_a = la < cnti, has_b = lb < cnti;
@@ -953,6 +996,9 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
             }
         }
         const double *sc64 = (ORTHO || TRI >= 0) ? sc64r : fs->sc64;
+        if constexpr (PLAN) {      // (the next step's record: its latency passes in the wait below)
+            if (rest) rec_next = plan_c[bit_next];
+        }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA for this step has landed
         __syncthreads();                                    // everyone's has; the previous step is fully consumed
         if (QUEUE) {
@@ -971,7 +1017,12 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
         }
         uint2 *nq = nq_base + (fa.img_defer ? (size_t)(step & 1) * nq_cap : 0);
         // what the next step needs streams in behind the arithmetic
-        {
+        if constexpr (PLAN) {
+            if (rest) stage_c(f0 + (bit_next >> 2), bit_next & 3, cbuf ^ 1);
+            // the next frame with a live step (buffer jb^1: the frame before this one, consumed before this barrier)
+            const unsigned long long later = rest & ~(0xfull << (4 * (fl - f0)));
+            if (new_frame && later) stage_j(f0 + ((__ffsll((long long)later) - 1) >> 2), jb ^ 1);
+        } else {
             const int nsub_next = sub + 1 < nsub ? sub + 1 : 0;
             const int fl_next = sub + 1 < nsub ? fl : fl + 1;
             if (step + 1 < nsteps) stage_c(fl_next, nsub_next, cbuf ^ 1);
@@ -992,7 +1043,15 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
         // quad ranges [b, e) of this step, quads dealt round-robin to the four waves: zq on f32 slab coordinates,
         // iq on the integer slab differences
         int zqb[2] = {0, 0}, zqe[2] = {0, 0}, iqb[2] = {0, 0}, iqe[2] = {0, 0};
-        if (CULL || ZFK) {
+        if constexpr (PLAN) {
+            // the step's record: quad ranges as tile_plan_window made them, the centres' slab range, the ZF flag
+            const uint32_t s_first = rec.z & 255u, s_last = (rec.z >> 8) & 255u;
+            const uint32_t wlo = s_first << 24, whi = (s_last << 24) | 0xffffffu;
+            zf = ((rec.z >> 16) & TILE_PLAN_ZF) != 0u;
+            z0 = wlo + ((whi - wlo) >> 1);
+            (zf ? zqb : iqb)[0] = (int)(rec.x & 0xffffu); (zf ? zqe : iqe)[0] = (int)(rec.x >> 16);
+            (zf ? zqb : iqb)[1] = (int)(rec.y & 0xffffu); (zf ? zqe : iqe)[1] = (int)(rec.y >> 16);
+        } else if (CULL || ZFK) {
             // the sub-tile is slab-sorted: its first / last atoms give its slab range
             const uint32_t s_first = tc[0].z >> 24, s_last = tc[cnti - 1].z >> 24;
             const uint32_t wlo = s_first << 24, whi = (s_last << 24) | 0xffffffu;
@@ -1220,7 +1279,12 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
                 rdf_pair_images<ORTHO>(hist, fa, g, p, pr2.x, pr2.y, gi);
             }
         }
-        if (++sub == nsub) { sub = 0; fl++; }
+        if constexpr (PLAN) {
+            live = rest;
+            fl = f0 + (bit_next >> 2); sub = bit_next & 3;
+        } else {
+            if (++sub == nsub) { sub = 0; fl++; }
+        }
     }
     if (QUEUE && fa.img_defer && nsteps > 0) {   // the last step's parked pairs
         __syncthreads();
@@ -1236,6 +1300,64 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
     for (int k = tid; k < nbins; k += FAST_THREADS) {
         unsigned v = hist[k];
         if (v) atomicAdd(&U[k], (unsigned long long)v);
+    }
+}
+
+// Plan of the tile kernel's steps (PLAN), once per frame batch behind the quantiser: one workgroup per frame, the frame's
+// slab table [S][257] in LDS.  First the slab range of every centre sub-tile (its first and last atom, by search in the
+// table), then one thread per tile pair: the records of its (up to four) steps, plan[(pair nf + frame) 4 + sub] -- a work
+// item of the tile kernel reads the records of its chunk as one contiguous run.
+struct TilePlanArgs {
+    const uint32_t *slab_start;     // [nf][S][257]
+    const Tile *tiles;
+    const int2 *pairs;
+    const int64_t *sp_first;        // [S + 1]
+    const FrameScale *fs;           // [n_cells]
+    uint4 *plan;                    // [npairs][nf][4]
+    int32_t S, ntiles, npairs, nf, f_base, n_cells;
+};
+
+constexpr int PLAN_THREADS = 256;
+
+__global__ __launch_bounds__(PLAN_THREADS) void rdf_tile_plan_kernel(TilePlanArgs pa)
+{
+    extern __shared__ __align__(16) unsigned char plan_raw[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(plan_raw);                  // [S][257]
+    uint32_t *cslab = tab + (size_t)pa.S * (QSLABS + 1);                     // [ntiles][4]: s_first | s_last << 8
+    const int fl = blockIdx.x, tid = threadIdx.x;
+    const uint32_t *__restrict__ src = pa.slab_start + (size_t)fl * pa.S * (QSLABS + 1);
+    for (int i = tid; i < pa.S * (QSLABS + 1); i += PLAN_THREADS) tab[i] = src[i];
+    __syncthreads();
+    for (int i = tid; i < pa.ntiles * TILE_PLAN_MAX_SUBS; i += PLAN_THREADS) {
+        const Tile t = pa.tiles[i / TILE_PLAN_MAX_SUBS];
+        const int sub = i % TILE_PLAN_MAX_SUBS;
+        uint32_t v = 0u;
+        if (sub * FAST_SUB < t.count) {
+            const uint32_t *st = tab + (size_t)t.species * (QSLABS + 1);
+            const uint32_t k0 = (uint32_t)(t.start - pa.sp_first[t.species]) + (uint32_t)(sub * FAST_SUB);
+            const uint32_t k1 = k0 + (uint32_t)min(FAST_SUB, t.count - sub * FAST_SUB) - 1u;
+            v = tile_plan_slab_of(st, k0) | tile_plan_slab_of(st, k1) << 8;
+        }
+        cslab[i] = v;
+    }
+    __syncthreads();
+    const uint32_t G = pa.fs[pa.n_cells == 1 ? 0 : pa.f_base + fl].cull_gap;
+    for (int p = tid; p < pa.npairs; p += PLAN_THREADS) {
+        const int2 pr = pa.pairs[p];
+        const Tile ti = pa.tiles[pr.x], tj = pa.tiles[pr.y];
+        const uint32_t *st = tab + (size_t)tj.species * (QSLABS + 1);
+        const int toff = (int)(tj.start - pa.sp_first[tj.species]);
+        uint4 *out = pa.plan + ((size_t)p * (size_t)pa.nf + (size_t)fl) * TILE_PLAN_MAX_SUBS;
+#pragma unroll 1
+        for (int sub = 0; sub < TILE_PLAN_MAX_SUBS; sub++) {
+            TilePlanRecord r = {0u, 0u, 0u, 0u};
+            if (sub * FAST_SUB < ti.count) {
+                const uint32_t c = cslab[pr.x * TILE_PLAN_MAX_SUBS + sub];
+                const uint32_t s_first = c & 255u, s_last = (c >> 8) & 255u;
+                r = tile_plan_pack(tile_plan_window(st, toff, tj.count, s_first, s_last, G, pr.x == pr.y, sub), s_first, s_last);
+            }
+            out[sub] = make_uint4(r.x, r.y, r.z, r.w);
+        }
     }
 }
 
@@ -2153,6 +2275,9 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
             {
                 const char *noreach = getenv("AMOF_RDF_NOREACH");    // tests / measurements: see rdf_tile_kernel_fast, REACH
                 fa.noreach = noreach && noreach[0] == '1' ? 1 : 0;
+                const char *noskip = getenv("AMOF_RDF_PLAN_NOSKIP");
+                fa.plan_noskip = noskip && noskip[0] == '1' ? 1 : 0;
+                fa.plan = nullptr;
             }
             fa.a.tiles = (const Tile *)d_ftiles;
             fa.a.pairs = (const int2 *)d_fpairs;
@@ -2525,13 +2650,27 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
                 lds = 2 * (FAST_TILE + FAST_SUB) * sizeof(uint4) + (size_t)((nbins + FAST_TRASH + 2 + 3) & ~3) * sizeof(unsigned) +
                       (fa.img_defer ? 2 : 1) * (size_t)fa.img_queue * sizeof(uint2) + 16;
             }
+            // rdf_tile_zf with slab culling runs from a plan of its steps (rdf_tile_kernel_fast, PLAN): the quantiser writes
+            // its slab table, rdf_tile_plan_kernel the records.  AMOF_RDF_NOPLAN=1: the search over sampled quads in every
+            // step, as the other variants have it (tests / measurements).  Not for tables beyond the plan kernel's LDS or
+            // plans beyond 256 MiB (systems far larger than a tile kernel's share).
+            const char *noplan = getenv("AMOF_RDF_NOPLAN");
+            const size_t plan_lds = (size_t)S * (QSLABS + 1) * sizeof(uint32_t) + ftiles.tiles.size() * TILE_PLAN_MAX_SUBS * sizeof(uint32_t);
+            const size_t plan_bytes = fpairs.size() * (size_t)FB * TILE_PLAN_MAX_SUBS * sizeof(uint4);
+            const bool plan_ok = use_zf && cull && !tri && !fast_img && !(noplan && noplan[0] == '1') && plan_lds <= 64 * 1024 &&
+                                 plan_bytes <= ((size_t)256 << 20);
+            void *d_slab = nullptr, *d_plan = nullptr;
+            if (plan_ok) {
+                AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)FB * S * (QSLABS + 1) * sizeof(uint32_t), &d_slab));
+                AMOF_TRY(ensure(ctx, SLOT_AUX9, plan_bytes, &d_plan));
+            }
             int64_t launches = 0;
             for (int64_t fb = 0; fb < t->n_frames; fb += cur, cur = std::min<int64_t>(2 * cur, FB)) {
                 const int64_t nf = std::min<int64_t>(cur, t->n_frames - fb);
                 AMOF_TRY(stager_need(stage, fb + nf));
                 AMOF_TRY(launch_quantize(ctx, pos_dev, (const double *)d_geom, (int)t->n_cells, (const int32_t *)d_perm,
                                          (const int64_t *)d_spfirst, S, t->n_atoms, (int)fb, (int)nf, axis, (QAtom *)d_Q,
-                                         nullptr, (int32_t *)d_flag, tri ? tri_ax0 : -1, tri ? tri_ax1 : -1, d_fold));
+                                         (uint32_t *)d_slab, (int32_t *)d_flag, tri ? tri_ax0 : -1, tri ? tri_ax1 : -1, d_fold));
                 fa.f_base = (int32_t)fb;
                 fa.nf = (int32_t)nf;
                 // frames per workgroup chunk: ~80k workgroups per launch (1280 run at a time: > 60 rounds, so that
@@ -2554,6 +2693,24 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
                 fa.n_chunks = (int32_t)chunks;
                 fa.nf_main = (int32_t)(nf - nf_tail);
                 dim3 grid((unsigned)fpairs.size(), (unsigned)(chunks + nf_tail));
+                // (a work item keeps the live steps of its chunk in 64 bits: four per frame)
+                const bool plan = plan_ok && (fa.nf_main + chunks - 1) / chunks <= 64 / TILE_PLAN_MAX_SUBS;
+                fa.plan = nullptr;
+                if (plan) {
+                    TilePlanArgs pa;
+                    pa.slab_start = (const uint32_t *)d_slab;
+                    pa.tiles = (const Tile *)d_ftiles;
+                    pa.pairs = (const int2 *)d_fpairs;
+                    pa.sp_first = (const int64_t *)d_spfirst;
+                    pa.fs = (const FrameScale *)d_fs;
+                    pa.plan = (uint4 *)d_plan;
+                    pa.S = S; pa.ntiles = (int32_t)ftiles.tiles.size(); pa.npairs = (int32_t)fpairs.size();
+                    pa.nf = (int32_t)nf; pa.f_base = (int32_t)fb; pa.n_cells = (int32_t)t->n_cells;
+                    AMOF_HIP_TRY(ctx, allow_max_lds((const void *)rdf_tile_plan_kernel));
+                    hipLaunchKernelGGL(rdf_tile_plan_kernel, dim3((unsigned)nf), dim3(PLAN_THREADS), plan_lds, ctx->stream, pa);
+                    AMOF_HIP_TRY(ctx, hipGetLastError());
+                    fa.plan = (const uint4 *)d_plan;
+                }
                 if (launches == 0) timing_dom_begin(ctx, tri ? "rdf_tile_tri" : fast_img ? "rdf_tile_img" : use_zf ? "rdf_tile_zf" : "rdf_tile");
                 auto launch = [&](auto kern) -> hipError_t {
                     hipError_t e2 = allow_max_lds_from_zero((const void *)kern);
@@ -2599,9 +2756,13 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
                     RdfFastArgs fz = fa;
                     fz.nb_hi = zf_nb_hi;
                     fz.half_m_guard = zf_half_m_guard;
-                    hipError_t e2 = cull ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true>)
-                                         : allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, false, false, true>);
-                    if (e2 == hipSuccess && cull)
+                    hipError_t e2 = plan   ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true, -1, true>)
+                                    : cull ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true>)
+                                           : allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, false, false, true>);
+                    if (e2 == hipSuccess && plan)
+                        hipLaunchKernelGGL((rdf_tile_kernel_fast<true, true, false, true, -1, true>), grid, dim3(FAST_THREADS), lds,
+                                           ctx->stream, fz);
+                    else if (e2 == hipSuccess && cull)
                         hipLaunchKernelGGL((rdf_tile_kernel_fast<true, true, false, true>), grid, dim3(FAST_THREADS), lds,
                                            ctx->stream, fz);
                     else if (e2 == hipSuccess)
