@@ -31,6 +31,7 @@
 
 #include "amof_internal.h"
 #include "tile_plan.h"
+#include "tri_select.h"
 
 namespace amof {
 
@@ -2087,12 +2088,7 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
             fast_img = true;
             near_thr.assign((size_t)nc * 3, 0x7fffffffu);
         }
-        // ---- TRI: general cells in the orthogonalised lattice frame (see fast_quad_tri) ----
-        // Stored order (x, y, z = slab axis): of the two orders of the other axes the one that leaves the x wrap the
-        // larger slack.  Conditions per cell, with R = rmax (1 + guards) and the lower factor L in Angstrom:
-        //   X: R / L00 + |L10| / (2 L00) < 1/2 - 1e-6     (the x wrap, decided without the c10 iy term, cannot lose an in-range image)
-        //   Y: tau_y = R / L11 - 1/2 <= 0: unique; else pairs with |iy| > 1/2 - tau_y are flagged near (<= 1.5 % of them)
-        //   Z: likewise with L22 (= the slab axis's perpendicular height)
+        // ---- TRI: general cells in the orthogonalised lattice frame (see fast_quad_tri; the selection: tri_select.h) ----
         bool tri = false;
         int tri_code = 0, tri_ax0 = -1, tri_ax1 = -1, tri_axis = 0;       // code: near tests (0 none, 1 slow path only, 2 fast path y, 3 y + z, 4 y with its twin image) + 5 x (x wrap with the y term)
         double tri_share = 0.0, tri_l10_bins = 0.0, tri_c10 = 0.0, tri_tau = 0.0;
@@ -2101,106 +2097,13 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
         const double two32_ = 1.0 / 4294967296.0;
         if (!ortho && max_img <= 124 && t->pbc[0] && t->pbc[1] && t->pbc[2] && nbins <= AMOF_MAX_LDS_BINS - 5120 &&
             guard_f < 0.25 && !(force && strcmp(force, "v1") == 0) && !getenv("AMOF_RDF_NOTRI") && !getenv("AMOF_RDF_FORCE_IMG")) {
-            double hmin3[3] = {1e300, 1e300, 1e300};
+            std::vector<double> heights((size_t)nc * 3);
             for (int64_t k = 0; k < nc; k++)
-                for (int x = 0; x < 3; x++) hmin3[x] = std::min(hmin3[x], geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-            tri_axis = 0;
-            for (int x = 1; x < 3; x++)
-                if (hmin3[x] > hmin3[tri_axis]) tri_axis = x;
-            const double R = rmax * (1.0 + 4.0 * guard_f / (double)nbins + 1e-6);
-            double best_cost = 1e300;
-            for (int sw = 0; sw < 2; sw++) {
-                const int a0 = sw ? (tri_axis + 2) % 3 : (tri_axis + 1) % 3, a1 = sw ? (tri_axis + 1) % 3 : (tri_axis + 2) % 3;
-                const int ordt[3] = {a0, a1, tri_axis};
-                bool ok = true;
-                double slack = 1e300, share = 0.0, l10b = 0.0, c10max = 0.0, tau_max = 0.0;
-                int near = 0;
-                bool twin = false, xw_wraps = false, twin_wraps = false, twin_short = false, half_p = true, half_m = true;
-                std::vector<double> fold((size_t)nc * 2), rec((size_t)nc * 9);
-                for (int64_t k = 0; k < nc && ok; k++) {
-                    const double *c = t->cell + 9 * k;
-                    double rows[9], L[9];
-                    for (int q = 0; q < 3; q++)
-                        for (int x = 0; x < 3; x++) rows[3 * q + x] = c[3 * ordt[q] + x];
-                    lower_factor(rows, L);
-                    if (!(L[0] > 0.0 && L[4] > 0.0 && L[8] > 0.0)) { ok = false; break; }
-                    // (no slack: the x wrap takes the c10 iy term along, XW -- two instructions more per pair)
-                    slack = std::min(slack, 0.5 - 1e-6 - (R / L[0] + 0.5 * fabs(L[3]) / L[0]));
-                    c10max = std::max(c10max, fabs(L[3]) / L[0]);
-                    double tau_y = R / L[4] - 0.5 + 1e-9, tau_z = R / L[8] - 0.5 + 1e-9;
-                    // (a second image along y up to 9 % of the pairs either side -- hexagonal cells: 7.7 % -- is evaluated by the
-                    //  slow path itself, near mode 4; along z only what the canonical queue can take)
-                    if (tau_y > 0.09 || tau_z > 0.0075) { ok = false; break; }
-                    if (tau_y > 0.0075) twin = true;
-                    // (near mode 4 counts the nearer of two candidates that differ by a lattice vector +-(B - k A), x wrapped:
-                    //  only where every such vector is at least 2 rmax long can the other one never be in range as well)
-                    {
-                        const double xr = L[3] - L[0] * rint(L[3] / L[0]);
-                        if (sqrt(L[4] * L[4] + xr * xr) * (1.0 + 1e-12) < 2.0 * rmax) twin_short = true;
-                    }
-                    tau_max = std::max(tau_max, std::max(tau_y, 0.0));
-                    // The x wrap of XW and of the twin image forms (int)(fy * c10), fy = the y difference in units of 2^-32 of the
-                    // cell: modular arithmetic only while |fy c10| < 2^31 (the conversion saturates beyond).  In range means
-                    // |fy| <= R / L11 cells (the twin: 1/2 + tau_y), so a skewed, non-reduced cell with |L10| >~ L00 cannot take
-                    // these variants: rdf_tile_img / rdf_exact answer it.
-                    if (fabs(L[3]) / L[0] * (R / L[4] + 1e-3) >= 0.5 - 1e-3) xw_wraps = true;
-                    if (fabs(L[3]) / L[0] * (0.5 + std::max(tau_y, 0.0) + 1e-3) >= 0.5 - 1e-3) twin_wraps = true;
-                    // A second image along y (z) can only be in range when L11 / 2 < R0 (canonical rmax with rounding slack);
-                    // then its in-plane components are below rho = sqrt(R0^2 - (L/2)^2), the evaluated image's differ from them
-                    // by at most the lattice offsets, so it lies between L - R0 and sqrt(D2max) from the origin.  When that
-                    // whole interval is within g_m / 2 of the cutoff the pair is flagged by the guard band of the last bin
-                    // edge anyway: no compare in the fast path (the slow path tests, and parks it).
-                    const double R0 = rmax * (1.0 + 1e-12), gband = 0.5 * (2.0 * quant / dr + (double)nbins * 1e-12);
-                    auto covered = [&](double Lk, double off_a, double off_b) {
-                        const double rho = sqrt(std::max(0.0, R0 * R0 - 0.25 * Lk * Lk));
-                        const double d2max = 0.25 * Lk * Lk + (rho + off_a) * (rho + off_a) + (rho + off_b) * (rho + off_b);
-                        return (Lk - R0) / dr >= (double)nbins - gband && sqrt(d2max) / dr <= (double)nbins + gband;
-                    };
-                    if (0.5 * L[4] >= R0) tau_y = -1.0;       // no second image along y at all
-                    else near = std::max(near, covered(L[4], fabs(L[3]), 0.0) ? 1 : 2);
-                    if (0.5 * L[8] >= R0) tau_z = -1.0;
-                    else near = std::max(near, covered(L[8], fabs(L[7]), fabs(L[6]) + fabs(L[3])) ? 1 : 3);
-                    // x: |A| >= 2 rmax whenever rmax is the reference's half shortest length; a larger rmax (the C ABI
-                    // takes any) would need a near test on x in the fast path: not this variant
-                    double tau_x = R / L[0] - 0.5 + 1e-9;
-                    if (0.5 * L[0] >= R0) tau_x = -1.0;
-                    else if (covered(L[0], 0.0, 0.0)) near = std::max(near, 1);
-                    else { ok = false; break; }
-                    share = std::max(share, tau_y > 0.0075 ? 0.012 : 2.0 * std::max(tau_y, 0.0) + 2.0 * std::max(tau_z, 0.0));
-                    l10b = std::max(l10b, fabs(L[3]) / dr);
-                    const double c10 = L[3] / L[0], r20 = L[6] / L[0], r21 = L[7] / L[4];
-                    // (c10 = +-1/2 to 2^-33: the exact-half x wrap of near mode 4, tri_q_twin<HALF>, is then right to one grid unit)
-                    if (fabs(c10 - 0.5) > 1e-10) half_p = false;
-                    if (fabs(c10 + 0.5) > 1e-10) half_m = false;
-                    fold[(size_t)k * 2] = r20 - c10 * r21;
-                    fold[(size_t)k * 2 + 1] = r21;
-                    double *r = &rec[(size_t)k * 9];
-                    r[0] = L[0] * two32_ / dr; r[1] = L[3] * two32_ / dr; r[2] = L[4] * two32_ / dr; r[3] = L[8] * two32_ / dr;
-                    // thresholds with room for the f32 conversions / coordinates of the fast path (flag a few more, never fewer)
-                    r[4] = tau_y > 0.0 ? (0.5 - tau_y) * 4294967296.0 * (1.0 - 1e-6) - 8.0 : INFINITY;
-                    r[5] = tau_z > 0.0 ? (L[8] - R) / dr * (1.0 - 1e-6) - 0.02 : INFINITY;
-                    r[6] = fold[(size_t)k * 2]; r[7] = fold[(size_t)k * 2 + 1];
-                    r[8] = tau_x > 0.0 ? (0.5 - tau_x) * 4294967296.0 * (1.0 - 1e-6) - 1024.0 : INFINITY;     // (f32 sum: 2^-23 of 2^31)
-                }
-                // cheaper order first: a near test costs a compare per pair, the x wrap two instructions in the chain
-                // (measured: + 8 % per compare, + 24 % for the wrap, profiles/r04/tri_experiments.txt)
-                if (twin) {
-                    if (near == 3) ok = false;      // (a common twin along y AND near tests along z: the image-aware / exact kernels)
-                    if (twin_wraps || twin_short) ok = false;
-                    near = 4;
-                }
-                if (!(slack > 0.0) && xw_wraps) ok = false;
-                int code = near + (slack > 0.0 ? 0 : 5);
-                if (near == 4 && (half_p || half_m) && !getenv("AMOF_RDF_NOHALF")) code = half_p ? 10 : 11;
-                const double cost = (near == 0 ? 0.0 : near == 1 ? 0.5 : near == 4 ? 6.0 : (double)(near - 1) * 1.5) +
-                                    (slack > 0.0 ? 0.0 : 2.5);
-                if (ok && (!tri || cost < best_cost)) {
-                    best_cost = cost;
-                    tri = true; tri_code = code; tri_ax0 = a0; tri_ax1 = a1; tri_share = share; tri_l10_bins = l10b; tri_c10 = c10max;
-                    tri_tau = tau_max;
-                    tri_fold.swap(fold); tri_rec.swap(rec);
-                }
-            }
+                for (int x = 0; x < 3; x++) heights[(size_t)k * 3 + x] = geom.rec[(size_t)k * GEOM_STRIDE + 18 + x];
+            TriSelect sel = tri_select(t->cell, heights.data(), nc, rmax, nbins, guard_f, quant, dr, getenv("AMOF_RDF_NOHALF") != nullptr);
+            tri = sel.ok; tri_code = sel.code; tri_ax0 = sel.ax0; tri_ax1 = sel.ax1; tri_axis = sel.axis;
+            tri_share = sel.share; tri_l10_bins = sel.l10_bins; tri_c10 = sel.c10; tri_tau = sel.tau;
+            tri_fold.swap(sel.fold); tri_rec.swap(sel.rec);
         }
         if (tri) {      // (the guard of its candidate at the widest reach must leave room between the bin edges)
             double hb = 0.0;

@@ -976,9 +976,15 @@ def test_rdf_hexagonal_cells_take_the_exact_half_x_wrap(hip_ctx, kind, capfd):
         assert np.array_equal(got, ref) and np.array_equal(plain, ref)
 
 
+# kind -> the variant's code at the default cutoff and at 0.8 of it (csrc/tri_select.h: near mode + 5 with the y term in the
+# x wrap; 10 / 11 the exact-half forms): fixture near 1; equal_ab near 1 + the y term; short_c near 2; cubic near 3 + the y
+# term; the hexagonal cells 11 / 10, and at the shorter cutoff still without slack along x
+_TRI_CODE = {"fixture": (1, 0), "equal_ab": (6, 0), "short_c": (2, 0), "cubic": (8, 0), "hexagonal": (11, 5), "hexagonal60": (10, 5)}
+
+
 @pytest.mark.parametrize("kind", ["fixture", "equal_ab", "short_c", "cubic", "hexagonal", "hexagonal60"])
 @pytest.mark.parametrize("jitter", [0.0, 0.004])
-def test_rdf_triangular_frame_kernel(hip_ctx, kind, jitter):
+def test_rdf_triangular_frame_kernel(hip_ctx, kind, jitter, capfd):
     """General cells at the reference's default cutoff (half the shortest cell LENGTH, amof/rdf.py:74): the tile kernel in
     the orthogonalised lattice frame against the oracle, with the image-aware / exact kernels it replaces beside it; a
     cutoff beyond half the x axis (only the C ABI allows it) is refused by the variant"""
@@ -987,8 +993,13 @@ def test_rdf_triangular_frame_kernel(hip_ctx, kind, jitter):
     rmax = float(np.min(packed.cell_lengths()) / 2)
     for rm, nb in ((rmax, 1540), (rmax, 257), (0.8 * rmax, 500)):
         with _env(AMOF_RDF_NOCELL="1", AMOF_RDF_NORANGE="1"):
-            got, _, _ = hip_ctx.rdf_accumulate(packed, rm, nb)
+            with _env(AMOF_RDF_DEBUG="1"):
+                capfd.readouterr()
+                got, _, _ = hip_ctx.rdf_accumulate(packed, rm, nb)
+                err = capfd.readouterr().err
             assert hip_ctx.last_path() == "rdf_tile_tri", (kind, rm)
+            # the variant each kind is built for (see _tri_cell), and the plain ones at the shorter cutoff
+            assert "rdf_tile_tri: code %d " % _TRI_CODE[kind][0 if rm == rmax else 1] in err, (kind, rm, nb, err)
             with _env(AMOF_RDF_NOCULL="1"):
                 nocull, _, _ = hip_ctx.rdf_accumulate(packed, rm, nb)
                 assert hip_ctx.last_path() == "rdf_tile_tri"
