@@ -17,6 +17,7 @@ Analyses beyond the reference:
                                                   intermediate scattering function F(q, t), coherent and self
     amof_amd.bond_lifetime.BondLifetime           bond survival correlations C(t), S(t) for CoordinationNumber's sets
     amof_amd.bond_reorientation.BondReorientation reorientational correlations C1(t), C2(t) of the same sets' bond vectors
+    amof_amd.bond_order.BondOrder                 Steinhardt q_l and tetrahedral order parameter of the same sets' shells
 
 All distance arithmetic runs in hand-written HIP kernels (gfx950) behind the C
 ABI of ``include/amof_hip.h``; there is no CPU fallback.

@@ -37,6 +37,7 @@ EXPORTS = [
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
+    "amof_bond_order", "amof_bond_order_dev",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
@@ -142,6 +143,8 @@ def load_library():
         lib.amof_bond_survival_dev.argtypes = lib.amof_bond_survival.argtypes
         lib.amof_bond_reorientation.argtypes = lib.amof_bond_survival.argtypes + [P]
         lib.amof_bond_reorientation_dev.argtypes = lib.amof_bond_reorientation.argtypes
+        lib.amof_bond_order.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P]
+        lib.amof_bond_order_dev.argtypes = lib.amof_bond_order.argtypes
         lib.amof_sq_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_double, ctypes.c_int32, P, P, P]
         lib.amof_sq_accumulate_dev.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -759,6 +762,41 @@ class Context(Lane):
         return sums, scale
 
     @_locked
+    def bond_order(self, packed, cutoff, sets, l, nbins, nbins_tet, frame_range=None, per_atom=False, out=None):
+        """``(hist u64 [n_sets][n_l][nbins], hist_tet u64 [n_sets][nbins_tet], frame_sums int64 [F][n_sets][4 + n_l + 1]
+        [, per_atom int64 [F][n_sets][N][2 + n_l]])`` of ``amof_bond_order``: the Steinhardt q_l (``l``: up to four values in
+        1 .. 12) and the tetrahedral order parameter of every centre of the sets (A, B), binned over the frames of
+        ``frame_range``; per frame and set the sums of n, of the centres with n >= 1 and n == 4, of n (n - 1) / 2, of
+        ``llrint(q_l 2^30)`` per l and of ``llrint(q_tet 2^30)``; per atom ``(n, T_l ..., U)`` (include/amof_hip.h).
+        ``cutoff``, ``sets``: as ``cn_count``.  A zero-length bond vector raises ``ZeroDivisionError``.
+
+        ``out``: optional pair of torch CUDA int64 tensors ``([n_sets][n_l][nbins], [n_sets][nbins_tet])`` the histograms
+        are ADDED into on the device (they stay resident for an RCCL merge); they are returned in place of the arrays."""
+        th = self._traj(packed, frame_range)
+        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64).reshape(th.S, th.S)
+        sets = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 2)
+        l = np.ascontiguousarray(l, dtype=np.int32).reshape(-1)
+        nbins, nbins_tet = int(nbins), int(nbins_tet)
+        sums = np.zeros((th.n_frames, len(sets), 4 + len(l) + 1), dtype=np.int64)
+        pa = np.zeros((th.n_frames, len(sets), th.n_atoms, 2 + len(l)), dtype=np.int64) if per_atom else None
+        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data), ctypes.c_void_p(sets.ctypes.data), len(sets),
+                ctypes.c_void_p(l.ctypes.data), len(l), nbins, nbins_tet)
+        tail = (ctypes.c_void_p(sums.ctypes.data), ctypes.c_void_p(pa.ctypes.data) if per_atom else None)
+        if out is not None:
+            hist, hist_tet = out
+            self._check_out(hist, len(sets) * len(l) * nbins)
+            self._check_out(hist_tet, len(sets) * nbins_tet)
+            self._order_after_torch()
+            self._check(self._lib.amof_bond_order_dev(*(args + (ctypes.c_void_p(hist.data_ptr()),
+                                                                ctypes.c_void_p(hist_tet.data_ptr())) + tail)))
+        else:
+            hist = np.zeros((len(sets), len(l), nbins), dtype=np.uint64)
+            hist_tet = np.zeros((len(sets), nbins_tet), dtype=np.uint64)
+            self._check(self._lib.amof_bond_order(*(args + (ctypes.c_void_p(hist.ctypes.data),
+                                                            ctypes.c_void_p(hist_tet.ctypes.data)) + tail)))
+        return (hist, hist_tet, sums, pa) if per_atom else (hist, hist_tet, sums)
+
+    @_locked
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None, out=None):
         """``(counts [nbins] u64, sums [P][nbins] f64, beyond, kinds)`` of ``amof_sq_accumulate``: the vectors ``hkl``
         (int ``[K][3]``) of the frames ``frame_range[0], + frame_stride, ... < frame_range[1]``, P = S(S+1)/2 species
@@ -840,7 +878,7 @@ class Context(Lane):
         """``{"rho", "corr", "self"}``: kernel seconds of the stages of the last ``isf_accumulate`` (amof_last_kernel_seconds
         2 .. 4; negative: the last call was not one).  After ``bond_survival`` the same three slots hold the bond lists, the
         bit series and the correlations; after ``bond_reorientation`` the bond lists, the bit series, and the vector table
-        with the reorientation sums."""
+        with the reorientation sums; after ``bond_order`` the list stage and the order kernels (the third is 0)."""
         self.drain()
         with self._lock:
             return {name: self._lib.amof_last_kernel_seconds(self._h, 2 + i) for i, name in enumerate(("rho", "corr", "self"))}
@@ -1039,6 +1077,20 @@ class MultiContext(object):
             jobs.append(job)
         res = self._run(jobs)
         return sum(r[0] for r in res), res[0][1]
+
+    def bond_order(self, packed, cutoff, sets, l, nbins, nbins_tet, frame_range=None, per_atom=False, out=None):
+        """frames sharded over the devices as ``cn_count``'s: the rows concatenate, the histograms add up exactly"""
+        assert out is None, "device-resident accumulation is a single-context feature"
+        lo, hi = (0, packed.n_frames) if frame_range is None else frame_range
+        jobs = []
+        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
+            def job(ctx=ctx, a=a, b=b):
+                tr, fr = self._for_device(packed, ctx, (a, b))
+                return ctx.bond_order(tr, cutoff, sets, l, nbins, nbins_tet, frame_range=fr, per_atom=per_atom)
+            jobs.append(job)
+        res = self._run(jobs)
+        merged = (sum(r[0] for r in res), sum(r[1] for r in res), np.concatenate([r[2] for r in res], axis=0))
+        return merged + (np.concatenate([r[3] for r in res], axis=0),) if per_atom else merged
 
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None):
         """frames sharded over the devices (whole strides per device; a device trajectory on another GPU is copied for the

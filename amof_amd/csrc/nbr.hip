@@ -1702,6 +1702,313 @@ __global__ __launch_bounds__(NBRM_THREADS) void bad_rows_merged_kernel(NbrArgs a
     else flush(hist_x, nangx, it.tx[0], it.tx[1]);
 }
 
+// --------------------------------------------------------------- bond order ----
+// Steinhardt q_l and the tetrahedral order parameter q_tet of every centre of a set (A, B), from the unit vectors to its
+// neighbours alone (include/amof_hip.h, amof_bond_order).  By the addition theorem of the spherical harmonics
+//     q_l^2 = (n + 2 sum_{j<k} P_l(cos theta_jk)) / n^2,
+// so a centre needs the cosines BAD forms and a Legendre recurrence, no spherical harmonic.  Every term is rounded to a
+// fixed-point grid of 2^-40 (ORDER_E) and summed in int64: the sums are exact, order independent and the same on every
+// path.  order_pair and order_centre are the ONE statement of the arithmetic both tiers call.
+// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): order_rows_kernel 95 VGPRs, order_kernel<true / false> 84,
+// 0 bytes of scratch per lane and no VGPR spill in either; the compiler parks 20 / 17 SGPRs in VGPR lanes, as it does for
+// bad_rows_kernel.  No inline assembly.
+constexpr int ORDER_E = 40;
+constexpr int ORDER_MAX_L = 4;              // values of l per call
+constexpr int ORDER_L_TOP = 12;             // each in 1 .. 12
+constexpr int ORDER_CAP = 64;               // neighbours of a centre (more: AMOF_ECAPACITY); n 2^E + 2 T_l < 2^53 up to here
+constexpr int ORDER_EXACT_LDS_BINS = 15360; // u32 bins beside the exact kernel's 96 KB of unit vectors
+
+struct OrderArgs {
+    int32_t n_l, l_top;             // l_top = the largest l asked for
+    int32_t l[ORDER_MAX_L];         // (0: unused)
+    int32_t nbins, nbins_tet;
+    int32_t global_hist;            // 1: more bins than LDS holds -- u64 global atomics
+    int32_t lane_sums;              // 1: per-lane atomics for the frame sums even where a wave shares one frame (measurements)
+    int32_t cols;                   // 4 + n_l + 1 columns of frame_sums
+    unsigned long long *hist;       // [n_sets][n_l][nbins]
+    unsigned long long *hist_tet;   // [n_sets][nbins_tet]
+    unsigned long long *frame_sums; // [F][n_sets][cols] (int64, two's complement)
+    long long *per_atom;            // [F][n_sets][N][2 + n_l] or null
+};
+
+struct OrderSums {
+    long long T[ORDER_MAX_L];       // sum over pairs of llrint(P_l(c) 2^E)
+    long long U;                    // sum over pairs of llrint((c + 1/3)^2 2^E)
+};
+
+// one unordered pair of neighbours: BAD's clipped cosine (same expression, no contraction), the Bonnet recurrence in float64
+__device__ __forceinline__ void order_pair(const OrderArgs &o, double ax, double ay, double az, double bx, double by, double bz,
+                                           OrderSums &s)
+{
+    double c = ax * bx + ay * by + az * bz;
+    if (c > 1.0) c = 1.0;
+    if (c < -1.0) c = -1.0;
+    double pm = 1.0, p = c;
+    for (int m = 1;; m++) {
+#pragma unroll
+        for (int q = 0; q < ORDER_MAX_L; q++)
+            if (o.l[q] == m) s.T[q] += llrint(p * 0x1p40);
+        if (m >= o.l_top) break;
+        const double pn = (((double)(2 * m + 1) * c) * p - (double)m * pm) / (double)(m + 1);
+        pm = p;
+        p = pn;
+    }
+    const double t = c + 1.0 / 3.0;
+    s.U += llrint(t * t * 0x1p40);
+}
+
+// what a centre adds to its frame's sums: v[0..3] = n, n >= 1, n == 4, n (n - 1) / 2; ql[q] = llrint(q_l 2^30); qt = llrint(q_tet 2^30)
+struct OrderRow {
+    long long v[4];
+    long long ql[ORDER_MAX_L];
+    long long qt;
+};
+
+// a centre with n neighbours (0: none, or no centre at all) and its sums: the bins (lh: the workgroup's LDS histogram,
+// [n_l][nbins] then [nbins_tet]; null: global atomics) and its row of the frame sums
+__device__ __forceinline__ OrderRow order_centre(const OrderArgs &o, int set, int n, const OrderSums &s, unsigned *lh)
+{
+    OrderRow r;
+    r.v[0] = n; r.v[1] = n >= 1 ? 1 : 0; r.v[2] = n == 4 ? 1 : 0; r.v[3] = (long long)n * (n - 1) / 2;
+    r.qt = 0;
+#pragma unroll
+    for (int q = 0; q < ORDER_MAX_L; q++) {
+        r.ql[q] = 0;
+        if (n < 1 || q >= o.n_l) continue;
+        long long Q = ((long long)n << ORDER_E) + 2 * s.T[q];
+        if (Q < 0) Q = 0;
+        const double ql = sqrt((double)Q * 0x1p-40) / (double)n;
+        const int b = max(0, min((int)(ql * (double)o.nbins), o.nbins - 1));
+        if (lh) atomicAdd(&lh[q * o.nbins + b], 1u);
+        else atomicAdd(&o.hist[((size_t)set * o.n_l + q) * o.nbins + b], 1ull);
+        r.ql[q] = llrint(ql * 0x1p30);
+    }
+    if (n == 4) {
+        const double qt = 1.0 - 0.375 * ((double)s.U * 0x1p-40);
+        const int b = max(0, min((int)((qt + 3.0) * 0.25 * (double)o.nbins_tet), o.nbins_tet - 1));
+        if (lh) atomicAdd(&lh[o.n_l * o.nbins + b], 1u);
+        else atomicAdd(&o.hist_tet[(size_t)set * o.nbins_tet + b], 1ull);
+        r.qt = llrint(qt * 0x1p30);
+    }
+    return r;
+}
+
+// (n, T_l ..., U) of one centre
+__device__ __forceinline__ void order_per_atom(const NbrArgs &a, const OrderArgs &o, int f, int set, int64_t atom, int n,
+                                               const OrderSums &s)
+{
+    long long *pa = o.per_atom + (((size_t)f * a.n_sets + set) * (size_t)a.N + (size_t)atom) * (size_t)(2 + o.n_l);
+    pa[0] = n;
+#pragma unroll
+    for (int q = 0; q < ORDER_MAX_L; q++)
+        if (q < o.n_l) pa[1 + q] = s.T[q];
+    pa[1 + o.n_l] = s.U;
+}
+
+// The rows of a wave's centres into frame_sums (called by all 64 lanes; f < 0: the lane has no centre).  A wave whose
+// centres share one frame adds them up first -- one atomic per column; otherwise every lane adds its own row.
+__device__ __forceinline__ void order_frame_sums(const OrderArgs &o, int n_sets, int f, int set, const OrderRow &r)
+{
+    const int f0 = __shfl(f, 0, 64);
+    const bool shared = !o.lane_sums && __all(f == f0 || f < 0);
+    const int lane = threadIdx.x & 63;
+    auto column = [&](long long x, int col) {
+        if (shared) {
+            for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+            if (lane == 0 && f0 >= 0 && x) atomicAdd(&o.frame_sums[((size_t)f0 * n_sets + set) * o.cols + col], (unsigned long long)x);
+        } else if (f >= 0 && x) {
+            atomicAdd(&o.frame_sums[((size_t)f * n_sets + set) * o.cols + col], (unsigned long long)x);
+        }
+    };
+#pragma unroll
+    for (int k = 0; k < 4; k++) column(f >= 0 ? r.v[k] : 0, k);
+#pragma unroll
+    for (int q = 0; q < ORDER_MAX_L; q++)
+        if (q < o.n_l) column(f >= 0 ? r.ql[q] : 0, 4 + q);
+    column(f >= 0 ? r.qt : 0, 4 + o.n_l);
+}
+
+// the workgroup's LDS histogram into the global ones: one u64 atomic per non-empty bin
+__device__ __forceinline__ void order_flush_hist(const OrderArgs &o, int set, const unsigned *lh, int threads)
+{
+    const int nq = o.n_l * o.nbins, nh = nq + o.nbins_tet;
+    for (int k = threadIdx.x; k < nh; k += threads) {
+        const unsigned v = lh[k];
+        if (!v) continue;
+        if (k < nq) atomicAdd(&o.hist[(size_t)set * nq + k], (unsigned long long)v);
+        else atomicAdd(&o.hist_tet[(size_t)set * o.nbins_tet + (k - nq)], (unsigned long long)v);
+    }
+}
+
+// per_atom before any kernel: (n, T_l ..., U) = (0, 0 ..., 0) for the atoms of a set's centre species (a set without a
+// cutoff or without partners has no kernel work: its centres keep these), n = -1 for all others
+__global__ __launch_bounds__(256) void order_init_kernel(long long *__restrict__ pa, const int32_t *__restrict__ species,
+                                                         const int32_t *__restrict__ set_a, int n_sets, int64_t N, int width, size_t total)
+{
+    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t)gridDim.x * 256) {
+        const size_t cell = k / (size_t)width;
+        const int col = (int)(k - cell * (size_t)width);
+        const int64_t atom = (int64_t)(cell % (size_t)N);
+        const int set = (int)((cell / (size_t)N) % (size_t)n_sets);
+        pa[k] = (col == 0 && species[atom] != set_a[set]) ? -1ll : 0ll;
+    }
+}
+
+// Frame tier: work item (blockIdx.y) = (set, centre species, partner species, -); blockIdx.x strides over the tiles of 256
+// (frame, centre) pairs of the batch, a lane owns its centre (as bad_rows_kernel); n <= 4 keeps the vectors in registers
+__global__ __launch_bounds__(NBRF_TILE) void order_rows_kernel(NbrArgs a, NbrListArgs la, OrderArgs o, const int4 *__restrict__ aw,
+                                                               const int64_t *__restrict__ sp_first, int f_base, int nf)
+{
+    extern __shared__ unsigned order_lh[];          // [n_l][nbins] | [nbins_tet] unless the counts go straight to global memory
+    const int tid = threadIdx.x;
+    const int4 w = aw[blockIdx.y];
+    const int set = w.x, sa = w.y, sb = w.z;
+    const int reg = la.region_of[sa * a.S + sb];
+    const int64_t seg = sp_first[sa];
+    const uint32_t nA = (uint32_t)(sp_first[sa + 1] - seg);
+    const uint32_t total = (uint32_t)nf * nA;                             // (< 2^31: the host sizes the frame batch)
+    const uint32_t tiles = (total + NBRF_TILE - 1) / NBRF_TILE;
+    unsigned *lh = o.global_hist ? nullptr : order_lh;
+    if (lh)
+        for (int k = tid; k < o.n_l * o.nbins + o.nbins_tet; k += NBRF_TILE) lh[k] = 0u;
+    __syncthreads();
+    const size_t step = la.plane * (NBRL_EW / 2);
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint32_t flat = tile * (uint32_t)NBRF_TILE + tid;
+        const bool has = flat < total;
+        const uint32_t fl = has ? flat / nA : 0u, r = has ? flat - fl * nA : 0u;
+        const size_t cbase = (size_t)fl * la.R + r + (size_t)reg;
+        int n = has ? (int)la.count[cbase] : 0;
+        if (n > NBRL_CAP) { a.flags[1] = 1; n = 0; }        // (as bad_rows_kernel: a fuller centre -> the exact kernel)
+        OrderSums s;
+#pragma unroll
+        for (int q = 0; q < ORDER_MAX_L; q++) s.T[q] = 0;
+        s.U = 0;
+        const double2 *__restrict__ e0 = reinterpret_cast<const double2 *>(la.rows + cbase * NBRL_EW);
+        if (n >= 2 && n <= 4) {
+            const double2 v0a = e0[0], v0b = e0[1], v1a = e0[step], v1b = e0[step + 1];
+            order_pair(o, v0a.x, v0a.y, v0b.x, v1a.x, v1a.y, v1b.x, s);
+            if (n > 2) {
+                const double2 v2a = e0[2 * step], v2b = e0[2 * step + 1];
+                order_pair(o, v0a.x, v0a.y, v0b.x, v2a.x, v2a.y, v2b.x, s);
+                order_pair(o, v1a.x, v1a.y, v1b.x, v2a.x, v2a.y, v2b.x, s);
+                if (n > 3) {
+                    const double2 v3a = e0[3 * step], v3b = e0[3 * step + 1];
+                    order_pair(o, v0a.x, v0a.y, v0b.x, v3a.x, v3a.y, v3b.x, s);
+                    order_pair(o, v1a.x, v1a.y, v1b.x, v3a.x, v3a.y, v3b.x, s);
+                    order_pair(o, v2a.x, v2a.y, v2b.x, v3a.x, v3a.y, v3b.x, s);
+                }
+            }
+        } else if (n > 4) {
+            for (int u = 0; u + 1 < n; u++) {
+                const double2 a01 = e0[u * step], a2 = e0[u * step + 1];
+                for (int v = u + 1; v < n; v++) {
+                    const double2 b01 = e0[v * step], b2 = e0[v * step + 1];
+                    order_pair(o, a01.x, a01.y, a2.x, b01.x, b01.y, b2.x, s);
+                }
+            }
+        }
+        const int f = has ? f_base + (int)fl : -1;
+        const OrderRow row = order_centre(o, set, n, s, lh);
+        if (o.per_atom && has) order_per_atom(a, o, f, set, a.perm[seg + r], n, s);
+        order_frame_sums(o, a.n_sets, f, set, row);
+    }
+    __syncthreads();
+    if (lh) order_flush_hist(o, set, lh, NBRF_TILE);
+}
+
+// Exact tier: bad_kernel<ORTHO, false>'s structure -- a lane per centre of a tile of 64, partner tiles staged through LDS,
+// the canonical minimum image (pair_base) and the strict sqrt(d2) < rc of amof_cn_count, the unit vectors [slot][lane] in
+// LDS, ORDER_CAP slots (96 KB).  Any cell, open axes, atoms anywhere.
+template <bool ORTHO>
+__global__ __launch_bounds__(BAD_TILE) void order_kernel(NbrArgs a, OrderArgs o)
+{
+    extern __shared__ __align__(16) unsigned char lds_raw[];
+    double *ux = reinterpret_cast<double *>(lds_raw);
+    double *uy = ux + ORDER_CAP * BAD_TILE;
+    double *uz = uy + ORDER_CAP * BAD_TILE;
+    double *tjx = uz + ORDER_CAP * BAD_TILE;
+    double *tjy = tjx + BAD_TILE;
+    double *tjz = tjy + BAD_TILE;
+    int *tja = reinterpret_cast<int *>(tjz + BAD_TILE);
+    unsigned *lh = o.global_hist ? nullptr : reinterpret_cast<unsigned *>(tja + BAD_TILE);
+
+    const int tid = threadIdx.x;
+    const int4 w = a.work[blockIdx.x];          // (set, centre tile, A, B)
+    const int set = w.x, A = w.z, B = w.w;
+    const Tile ti = a.tiles[w.y];
+    const double rc = a.cutoff[A * a.S + B];
+    const int64_t ai = tid < ti.count ? a.perm[ti.start + tid] : -1;
+    const int f0 = blockIdx.y * a.frames_per_chunk;
+    const int f1 = min(f0 + a.frames_per_chunk, a.F);
+    const int tb0 = a.sp_first_tile[B], tb1 = tb0 + a.sp_ntiles[B];
+    if (lh)
+        for (int k = tid; k < o.n_l * o.nbins + o.nbins_tet; k += BAD_TILE) lh[k] = 0u;
+    __syncthreads();
+
+    for (int f = f0; f < f1; f++) {
+        const double *__restrict__ p = a.pos + (size_t)f * (size_t)a.N * 3;
+        const double *__restrict__ g = a.geom + (size_t)(a.n_cells == 1 ? 0 : f) * GEOM_STRIDE;
+        double xi = 0.0, yi = 0.0, zi = 0.0;
+        if (ai >= 0) {
+            xi = p[ai * 3 + 0];
+            yi = p[ai * 3 + 1];
+            zi = p[ai * 3 + 2];
+        }
+        int n = 0;
+        if (rc > 0.0) {
+            for (int tb = tb0; tb < tb1; tb++) {
+                // partner tiles hold up to 256 atoms: stage them 64 at a time
+                const Tile tj = a.tiles[tb];
+                for (int base = 0; base < tj.count; base += BAD_TILE) {
+                    const int cntj = min(BAD_TILE, tj.count - base);
+                    __syncthreads();
+                    if (tid < cntj) {
+                        const int64_t aj = a.perm[tj.start + base + tid];
+                        tjx[tid] = p[aj * 3 + 0];
+                        tjy[tid] = p[aj * 3 + 1];
+                        tjz[tid] = p[aj * 3 + 2];
+                        tja[tid] = (int)aj;
+                    }
+                    __syncthreads();
+                    if (ai < 0) continue;
+                    for (int j = 0; j < cntj; j++) {
+                        if (tja[j] == (int)ai) continue;
+                        double dx, dy, dz;
+                        pair_base<ORTHO>(g, tjx[j] - xi, tjy[j] - yi, tjz[j] - zi, dx, dy, dz);
+                        if (!(sqrt(norm2(dx, dy, dz)) < rc)) continue;
+                        double qx = 0.0, qy = 0.0, qz = 0.0;
+                        if (!unit_vec(dx, dy, dz, qx, qy, qz)) a.flags[0] = 1;       // (the call fails: results are discarded)
+                        if (n < ORDER_CAP) {
+                            ux[n * BAD_TILE + tid] = qx;
+                            uy[n * BAD_TILE + tid] = qy;
+                            uz[n * BAD_TILE + tid] = qz;
+                        } else {
+                            a.flags[1] = 1;                                          // (AMOF_ECAPACITY)
+                        }
+                        n++;
+                    }
+                }
+            }
+        }
+        const int nn = min(n, ORDER_CAP);
+        OrderSums s;
+#pragma unroll
+        for (int q = 0; q < ORDER_MAX_L; q++) s.T[q] = 0;
+        s.U = 0;
+        for (int u = 0; u + 1 < nn; u++) {
+            const double ax = ux[u * BAD_TILE + tid], ay = uy[u * BAD_TILE + tid], az = uz[u * BAD_TILE + tid];
+            for (int v = u + 1; v < nn; v++)
+                order_pair(o, ax, ay, az, ux[v * BAD_TILE + tid], uy[v * BAD_TILE + tid], uz[v * BAD_TILE + tid], s);
+        }
+        const OrderRow row = order_centre(o, set, ai >= 0 ? nn : 0, s, lh);
+        if (o.per_atom && ai >= 0) order_per_atom(a, o, f, set, ai, nn, s);
+        order_frame_sums(o, a.n_sets, ai >= 0 ? f : -1, set, row);
+    }
+    __syncthreads();
+    if (lh) order_flush_hist(o, set, lh, BAD_TILE);
+}
+
 // ------------------------------------------------------------ host side ----
 struct NbrSetup {
     HostGeom geom;
@@ -2261,10 +2568,12 @@ static int frame_batch_buffers(amof_ctx *ctx, const amof_traj *t, NbrFrame &nw, 
     return AMOF_OK;
 }
 
-// The frame tier's batches (CN and BAD), after frame_batch_buffers: FB0 frames first when the input is staged lazily,
-// doubling up to FB.  launch(nfr) queues one batch's kernels; qflag says whether an atom lay absurdly far from the cell.
+// The frame tier's batches (CN, BAD and the bond order parameters), after frame_batch_buffers: FB0 frames first when the
+// input is staged lazily, doubling up to FB.  launch(nfr) queues one batch's kernels; qflag says whether an atom lay absurdly
+// far from the cell.  user: whose path name amof_last_path reports.
+enum FrameUser { FRAME_CN, FRAME_BAD, FRAME_ORDER };
 template <typename Launch>
-static int frame_batches(amof_ctx *ctx, const amof_traj *t, NbrSetup &st, NbrFrame &nw, int64_t FB, bool bad, Launch &&launch,
+static int frame_batches(amof_ctx *ctx, const amof_traj *t, NbrSetup &st, NbrFrame &nw, int64_t FB, FrameUser user, Launch &&launch,
                          int32_t &qflag)
 {
     const NbrArgs &a = st.a;
@@ -2281,7 +2590,9 @@ static int frame_batches(amof_ctx *ctx, const amof_traj *t, NbrSetup &st, NbrFra
         nw.fr.f_base = (int32_t)fb;
         nw.fr.nf = (int32_t)nfr;
         if (launches == 0)
-            timing_dom_begin(ctx, bad ? (nw.slabs ? "bad_frame_slabs" : "bad_frame") : (nw.slabs ? "cn_frame_slabs" : "cn_frame"));
+            timing_dom_begin(ctx, user == FRAME_ORDER ? "order_frame"
+                                  : user == FRAME_BAD ? (nw.slabs ? "bad_frame_slabs" : "bad_frame")
+                                                      : (nw.slabs ? "cn_frame_slabs" : "cn_frame"));
         if (nw.slabs)
             AMOF_TRY(launch_quantize(ctx, a.pos, a.geom, (int)t->n_cells, a.perm, nw.d_spfirst, t->n_species, t->n_atoms, (int)fb,
                                      (int)nfr, 2, (QAtom *)nw.fr.Q, (uint32_t *)nw.fr.zstart, (int32_t *)nw.d_qflag, 0, 1, nullptr, used));
@@ -2364,7 +2675,7 @@ static int cn_frame_tier(CnCall &c)
         return AMOF_OK;
     };
     int32_t qflag;
-    AMOF_TRY(frame_batches(ctx, t, c.st, nw, FB, false, batch, qflag));
+    AMOF_TRY(frame_batches(ctx, t, c.st, nw, FB, FRAME_CN, batch, qflag));
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     if (qflag) return c.reset_outputs();    // atoms absurdly far from the cell: the exact kernel answers (via the fast path's own check)
     c.done = true;
@@ -2438,6 +2749,127 @@ static int cn_exact_tier(CnCall &c)
     return AMOF_OK;
 }
 
+// ---- the list stage of the frame tier: one sort + LDS search per species pair into neighbour rows (lists_frame_kernel).
+// BAD forms its angles from the rows, the bond order parameters their Legendre sums: both plan, commit and run it here.
+struct FrameLists {
+    NbrFrame nw;
+    std::vector<int32_t> region_of;     // [S][S] first row of the ordered pair (centre species, partner species); -1: not kept
+    int64_t R = 0;                      // rows per frame
+    bool shared_rows = false;           // partners of several slabs claim their rows' slots with global atomics
+    int64_t FB = 0;                     // frames per batch
+    NbrListArgs la;
+    const int32_t *d_head = nullptr;    // the caller's words at the head of the table (frame_lists_commit)
+};
+
+// regions of the ordered pairs in `needed` [S][S], one item per unordered pair, the tier's plan (after nbr_frame_prepare:
+// nothing happens unless L.nw.ok)
+static void frame_lists_plan(const NbrCall &c, const std::vector<char> &needed, FrameLists &L)
+{
+    const NbrSetup &st = c.st;
+    const int S = c.t->n_species;
+    NbrFrame &nw = L.nw;
+    L.region_of.assign((size_t)S * S, -1);
+    L.R = 0;
+    for (int x = 0; x < S * S && nw.ok; x++)
+        if (needed[(size_t)x]) { L.region_of[(size_t)x] = (int32_t)L.R; L.R += st.tiles.nsp[(size_t)(x / S)]; }
+    std::vector<FrameProto> protos;
+    for (int x = 0; x < S; x++)
+        for (int y = x; y < S; y++) {
+            if (!needed[(size_t)x * S + y] && !needed[(size_t)y * S + x]) continue;
+            FrameProto p{FrameItem{}, c.cutoff[x * S + y], 0, 0};
+            p.it.sa = st.tiles.nsp[y] < st.tiles.nsp[x] ? y : x;      // the species with fewer atoms searches
+            p.it.sb = p.it.sa == x ? y : x;
+            p.it.set = 0;
+            p.it.reg_ab = L.region_of[(size_t)p.it.sa * S + p.it.sb];
+            p.it.reg_ba = x == y ? -1 : L.region_of[(size_t)p.it.sb * S + p.it.sa];
+            p.nA = st.tiles.nsp[p.it.sa];
+            p.nB = st.tiles.nsp[p.it.sb];
+            protos.push_back(p);
+        }
+    // beside the records: a byte per atom (its row's count) and the hit buffer
+    frame_plan(protos, (size_t)NBRW_HITS * sizeof(uint32_t), (size_t)NBRW_HITS * sizeof(uint32_t) + 4, 1, nw);
+    L.shared_rows = false;
+    if (nw.slabs)
+        for (const FrameItem &it : nw.items) L.shared_rows = L.shared_rows || (it.cn != it.nzg && it.reg_ba >= 0);
+}
+
+// the tier takes the call: one small table -- the caller's head words | region_of[S*S] | inv_rank[N] -- and whatever the
+// caller added to nw.pk to the device, the rows (at most 4 GiB, or rows_env megabytes: tests force many batches; with
+// zero_is_one_frame a value of 0 means one frame per batch) and the per-batch buffers
+static int frame_lists_commit(NbrCall &c, FrameLists &L, const int32_t *head, size_t head_words, const char *rows_env,
+                              bool zero_is_one_frame = false)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const NbrSetup &st = c.st;
+    NbrFrame &nw = L.nw;
+    const int S = t->n_species;
+    const int64_t R = L.R;
+    std::vector<int32_t> tab(head_words + (size_t)S * S + (size_t)t->n_atoms);
+    if (head_words) memcpy(tab.data(), head, head_words * sizeof(int32_t));
+    memcpy(&tab[head_words], L.region_of.data(), L.region_of.size() * sizeof(int32_t));
+    for (int64_t x = 0; x < t->n_atoms; x++) {
+        const int32_t atom = st.tiles.perm[(size_t)x];
+        tab[head_words + (size_t)S * S + (size_t)atom] = (int32_t)(x - st.tiles.sp_first[(size_t)t->species[atom]]);
+    }
+    void *d_lists;
+    const int i_tab = nw.pk.add(tab.data(), tab.size() * sizeof(int32_t));
+    AMOF_TRY(nbr_frame_commit(ctx, st, nw));
+    const int32_t *d_tab = nw.pk.ptr<int32_t>(i_tab);
+    const size_t per_frame = (size_t)R * (sizeof(uint32_t) + (size_t)NBRL_CAP * NBRL_EW * sizeof(double));
+    size_t rows_budget = (size_t)4 << 30;                          // <= 4 GiB of rows
+    if (const char *mb = getenv(rows_env)) rows_budget = (size_t)std::max(1, atoi(mb)) << 20;     // tests: many batches
+    if (zero_is_one_frame && getenv(rows_env) && atoi(getenv(rows_env)) <= 0) rows_budget = 1;    // (a frame per batch)
+    int64_t FB = std::max<int64_t>(1, (int64_t)rows_budget / (int64_t)per_frame);
+    FB = std::min<int64_t>(FB, std::max<int64_t>(1, 0x7fffff00ll / std::max<int64_t>(1, t->n_atoms)));    // flat (frame, centre) index
+    FB = std::min<int64_t>(std::min<int64_t>(FB, 32768), t->n_frames);
+    FB = frame_sidx_frames(nw, FB);         // (the rows are not sized for more frames than a batch will hold)
+    // (a device short of memory gets smaller batches, not an error)
+    for (;;) {
+        const int rc_rows = ensure(ctx, SLOT_AUX9, (size_t)FB * per_frame, &d_lists);
+        if (rc_rows == AMOF_OK) break;
+        if (rc_rows != AMOF_ENOMEM || FB == 1) return rc_rows;
+        FB = std::max<int64_t>(1, FB / 4);
+    }
+    AMOF_TRY(frame_batch_buffers(ctx, t, nw, FB));
+    L.FB = FB;
+    L.d_head = d_tab;
+    NbrListArgs &la = L.la;
+    la.region_of = d_tab + head_words;
+    la.inv_rank = la.region_of + (size_t)S * S;
+    la.rows = (double *)d_lists;                                   // (doubles first: 8-byte aligned)
+    la.count = (uint32_t *)(la.rows + (size_t)FB * R * NBRL_CAP * NBRL_EW);
+    la.R = (int32_t)R;
+    la.plane = (size_t)FB * (size_t)R;
+    return AMOF_OK;
+}
+
+// every batch: the rows of its frames (lists_frame_kernel), then consume(nfr) queues the kernels that read them.  spans:
+// stage 0 around the list kernels, stage 1 around the consumer's (or null)
+template <typename Consume>
+static int frame_lists_run(NbrCall &c, FrameLists &L, FrameUser user, StageSpans *spans, Consume &&consume, int32_t &qflag)
+{
+    amof_ctx *ctx = c.ctx;
+    NbrFrame &nw = L.nw;
+    const NbrArgs &a = c.st.a;
+    const NbrListArgs &la = L.la;
+    auto batch = [&](int64_t nfr) -> int {
+        if (spans) spans->begin(0);
+        if (L.shared_rows)  // (partners of several slabs claim their rows' slots with global atomics: the counts start at zero)
+            AMOF_HIP_TRY(ctx, hipMemsetAsync(la.count, 0, (size_t)L.FB * (size_t)L.R * sizeof(uint32_t), ctx->stream));
+        const dim3 sgrid((unsigned)nw.items.size(), (unsigned)nfr);
+        const hipError_t e = frame_dispatch(nw, [&](auto O, auto PT, auto C) {
+            return launch_lds(lists_frame_kernel<O(), PT(), C()>, sgrid, dim3(NBRW_THREADS), nw.lds, ctx->stream, a, nw.fr, la);
+        });
+        AMOF_HIP_TRY(ctx, e);
+        if (spans) { spans->end(); spans->begin(1); }
+        AMOF_TRY(consume(nfr));
+        if (spans) spans->end();
+        return AMOF_OK;
+    };
+    return frame_batches(ctx, c.t, c.st, nw, L.FB, user, batch, qflag);
+}
+
 struct BadCall : NbrCall {
     const int32_t *triples;
     int32_t T, nb, cn_max;
@@ -2469,7 +2901,8 @@ static int bad_frame_tier(BadCall &c)
     NbrSetup &st = c.st;
     NbrArgs &a = st.a;
     const int S = t->n_species, T = c.T;
-    NbrFrame nw;
+    FrameLists L;
+    NbrFrame &nw = L.nw;
     AMOF_TRY(nbr_frame_prepare(t, cutoff, st, nw));
     if (getenv("AMOF_BAD_NOTRANSPOSE")) nw.ok = false;      // (names the two-search gather kernels)
     auto live_pair = [&](int x, int y) { return cutoff[x * S + y] > 0.0 && st.tiles.nsp[x] > 0 && st.tiles.nsp[y] > 0; };
@@ -2485,29 +2918,9 @@ static int bad_frame_tier(BadCall &c)
             if (live) awork.push_back(make_int4(k, sa, B, 0));
         }
     }
-    std::vector<int32_t> region_of((size_t)S * S, -1);
-    int64_t R = 0;
-    for (int x = 0; x < S * S && nw.ok; x++)
-        if (needed[(size_t)x]) { region_of[(size_t)x] = (int32_t)R; R += st.tiles.nsp[(size_t)(x / S)]; }
-    std::vector<FrameProto> protos;
-    for (int x = 0; x < S; x++)
-        for (int y = x; y < S; y++) {
-            if (!needed[(size_t)x * S + y] && !needed[(size_t)y * S + x]) continue;
-            FrameProto p{FrameItem{}, cutoff[x * S + y], 0, 0};
-            p.it.sa = st.tiles.nsp[y] < st.tiles.nsp[x] ? y : x;      // the species with fewer atoms searches
-            p.it.sb = p.it.sa == x ? y : x;
-            p.it.set = 0;
-            p.it.reg_ab = region_of[(size_t)p.it.sa * S + p.it.sb];
-            p.it.reg_ba = x == y ? -1 : region_of[(size_t)p.it.sb * S + p.it.sa];
-            p.nA = st.tiles.nsp[p.it.sa];
-            p.nB = st.tiles.nsp[p.it.sb];
-            protos.push_back(p);
-        }
-    // beside the records: a byte per atom (its row's count) and the hit buffer
-    frame_plan(protos, (size_t)NBRW_HITS * sizeof(uint32_t), (size_t)NBRW_HITS * sizeof(uint32_t) + 4, 1, nw);
-    bool shared_rows = false;
-    if (nw.slabs)
-        for (const FrameItem &it : nw.items) shared_rows = shared_rows || (it.cn != it.nzg && it.reg_ba >= 0);
+    frame_lists_plan(c, needed, L);
+    const std::vector<int32_t> &region_of = L.region_of;
+    const int64_t R = L.R;
     if (nw.ok && awork.empty()) {
         c.done = true;          // no triple has a centre with a cutoff to any of its partners: no angle
         return AMOF_OK;
@@ -2551,52 +2964,15 @@ static int bad_frame_tier(BadCall &c)
         //  per triple keeps a centre's vectors in registers)
         if (!usable || twice || lds_merged > 60 * 1024 || merged.size() >= awork.size()) merged.clear();
     }
-    // one small table: angle work | region_of[S*S] | inv_rank[N]; the items beside it
-    std::vector<int32_t> tab(4 * awork.size() + (size_t)S * S + (size_t)t->n_atoms);
-    memcpy(tab.data(), awork.data(), awork.size() * sizeof(int4));
-    memcpy(&tab[4 * awork.size()], region_of.data(), region_of.size() * sizeof(int32_t));
-    for (int64_t x = 0; x < t->n_atoms; x++) {
-        const int32_t atom = st.tiles.perm[(size_t)x];
-        tab[4 * awork.size() + (size_t)S * S + (size_t)atom] = (int32_t)(x - st.tiles.sp_first[(size_t)t->species[atom]]);
-    }
-    void *d_lists;
-    const int i_tab = nw.pk.add(tab.data(), tab.size() * sizeof(int32_t));
+    // the angle work at the head of the list stage's table; the merged items beside it
     const int i_merged = nw.pk.add(merged.data(), merged.size() * sizeof(MergedItem));
-    AMOF_TRY(nbr_frame_commit(ctx, c.st, nw));
-    const int32_t *d_tab = nw.pk.ptr<int32_t>(i_tab);
+    AMOF_TRY(frame_lists_commit(c, L, reinterpret_cast<const int32_t *>(awork.data()), 4 * awork.size(), "AMOF_BAD_ROWS_MB"));
     const MergedItem *d_merged = nw.pk.ptr<MergedItem>(i_merged);
-    const size_t per_frame = (size_t)R * (sizeof(uint32_t) + (size_t)NBRL_CAP * NBRL_EW * sizeof(double));
-    size_t rows_budget = (size_t)4 << 30;                          // <= 4 GiB of rows
-    if (const char *mb = getenv("AMOF_BAD_ROWS_MB")) rows_budget = (size_t)std::max(1, atoi(mb)) << 20;     // tests: many batches
-    int64_t FB = std::max<int64_t>(1, (int64_t)rows_budget / (int64_t)per_frame);
-    FB = std::min<int64_t>(FB, std::max<int64_t>(1, 0x7fffff00ll / std::max<int64_t>(1, t->n_atoms)));    // flat (frame, centre) index
-    FB = std::min<int64_t>(std::min<int64_t>(FB, 32768), t->n_frames);
-    FB = frame_sidx_frames(nw, FB);         // (the rows are not sized for more frames than a batch will hold)
-    // (a device short of memory gets smaller batches, not an error)
-    for (;;) {
-        const int rc_rows = ensure(ctx, SLOT_AUX9, (size_t)FB * per_frame, &d_lists);
-        if (rc_rows == AMOF_OK) break;
-        if (rc_rows != AMOF_ENOMEM || FB == 1) return rc_rows;
-        FB = std::max<int64_t>(1, FB / 4);
-    }
-    AMOF_TRY(frame_batch_buffers(ctx, t, nw, FB));
-    NbrListArgs la;
-    const int4 *d_aw = (const int4 *)d_tab;
-    la.region_of = (const int32_t *)d_tab + 4 * awork.size();
-    la.inv_rank = la.region_of + (size_t)S * S;
-    la.rows = (double *)d_lists;                                   // (doubles first: 8-byte aligned)
-    la.count = (uint32_t *)(la.rows + (size_t)FB * R * NBRL_CAP * NBRL_EW);
-    la.R = (int32_t)R;
-    la.plane = (size_t)FB * (size_t)R;
+    const int4 *d_aw = (const int4 *)L.d_head;
+    const NbrListArgs &la = L.la;
     const size_t lds_rows = c.lds_bins * sizeof(unsigned);
-    auto batch = [&](int64_t nfr) -> int {
-        if (shared_rows)    // (partners of several slabs claim their rows' slots with global atomics: the counts start at zero)
-            AMOF_HIP_TRY(ctx, hipMemsetAsync(la.count, 0, (size_t)FB * (size_t)R * sizeof(uint32_t), ctx->stream));
-        const dim3 sgrid((unsigned)nw.items.size(), (unsigned)nfr);
-        hipError_t e = frame_dispatch(nw, [&](auto O, auto PT, auto C) {
-            return launch_lds(lists_frame_kernel<O(), PT(), C()>, sgrid, dim3(NBRW_THREADS), nw.lds, ctx->stream, a, nw.fr, la);
-        });
-        AMOF_HIP_TRY(ctx, e);
+    auto angles = [&](int64_t nfr) -> int {
+        hipError_t e;
         if (!merged.empty()) {
             // one pass per centre species: about 1024 workgroups of 512 lanes in all
             int64_t widest_m = 0;
@@ -2625,7 +3001,7 @@ static int bad_frame_tier(BadCall &c)
         return AMOF_OK;
     };
     int32_t qflag;
-    AMOF_TRY(frame_batches(ctx, t, st, nw, FB, true, batch, qflag));
+    AMOF_TRY(frame_lists_run(c, L, FRAME_BAD, nullptr, angles, qflag));
 #ifdef NBR_PHASE_STAMPS
     {
         unsigned long long ph[16][5];
@@ -2876,6 +3252,228 @@ static int bad_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, cons
     return AMOF_OK;
 }
 
+// ------------------------------------------------------------ bond order: host side ----
+struct OrderCall : NbrCall {
+    const int32_t *sets;
+    int32_t n_sets;
+    OrderArgs o;
+    size_t words = 0;           // histogram words of a set: n_l nbins + nbins_tet
+    // every tier accumulates into the call's own buffers; the caller's only ever receive a complete, valid result
+    void *d_hs = nullptr, *d_flags = nullptr, *d_fs = nullptr, *d_pa = nullptr;
+    size_t hs_words = 0, fs_bytes = 0, pa_words = 0;
+    const int32_t *d_species = nullptr, *d_set_a = nullptr;
+    StageSpans *spans = nullptr;
+    int read_flags(int32_t (&fl)[4])
+    {
+        AMOF_TRY(fetch(ctx, fl, d_flags, sizeof fl));
+        AMOF_HIP_TRY(ctx, sync_stream(ctx));
+        return AMOF_OK;
+    }
+    int reset_outputs()         // the outputs as before the first tier
+    {
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_hs, 0, hs_words * sizeof(unsigned long long), ctx->stream));
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_fs, 0, fs_bytes, ctx->stream));
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
+        if (d_pa) {
+            const unsigned blocks = (unsigned)std::min<size_t>((pa_words + 255) / 256, 8192);
+            hipLaunchKernelGGL(order_init_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (long long *)d_pa, d_species, d_set_a,
+                               (int)n_sets, (int64_t)t->n_atoms, 2 + o.n_l, pa_words);
+            AMOF_HIP_TRY(ctx, hipGetLastError());
+        }
+        return AMOF_OK;
+    }
+};
+
+// whole-frame-in-LDS tier: BAD's list stage (one sort + LDS search per species pair into neighbour rows), every set from its rows
+static int order_frame_tier(OrderCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    NbrSetup &st = c.st;
+    const int S = t->n_species;
+    FrameLists L;
+    NbrFrame &nw = L.nw;
+    AMOF_TRY(nbr_frame_prepare(t, c.cutoff, st, nw));
+    std::vector<char> needed((size_t)S * S, 0);
+    std::vector<int4> awork;
+    for (int s2 = 0; s2 < c.n_sets && nw.ok; s2++) {
+        const int A = c.sets[2 * s2], B = c.sets[2 * s2 + 1];
+        if (!(c.cutoff[A * S + B] > 0.0) || st.tiles.nsp[A] == 0 || st.tiles.nsp[B] == 0) continue;     // (no centre has a neighbour)
+        needed[(size_t)A * S + B] = 1;
+        awork.push_back(make_int4(s2, A, B, 0));
+    }
+    frame_lists_plan(c, needed, L);
+    if (nw.ok && awork.empty()) {
+        c.done = true;
+        return AMOF_OK;
+    }
+    if (!(nw.ok && L.R > 0 && L.R < (1ll << 30) && t->n_frames > 0)) return AMOF_OK;
+    AMOF_TRY(frame_lists_commit(c, L, reinterpret_cast<const int32_t *>(awork.data()), 4 * awork.size(), "AMOF_ORDER_ROWS_MB", true));
+    const int4 *d_aw = (const int4 *)L.d_head;
+    c.o.global_hist = c.words > (size_t)AMOF_MAX_LDS_BINS ? 1 : 0;
+    const size_t lds = c.o.global_hist ? 0 : c.words * sizeof(unsigned);
+    auto order = [&](int64_t nfr) -> int {
+        // about eight workgroups per CU in all work items together, each striding over the tiles of its own (as bad_rows_kernel)
+        int64_t widest = 0;
+        for (const int4 &w : awork) widest = std::max<int64_t>(widest, (nfr * st.tiles.nsp[(size_t)w.y] + NBRF_TILE - 1) / NBRF_TILE);
+        const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(widest, (2048 + (int64_t)awork.size() - 1) / (int64_t)awork.size()));
+        const dim3 grid((unsigned)gx, (unsigned)awork.size());
+        AMOF_HIP_TRY(ctx, launch_lds(order_rows_kernel, grid, dim3(NBRF_TILE), lds, ctx->stream, st.a, L.la, c.o, d_aw, nw.d_spfirst,
+                                     (int)nw.fr.f_base, (int)nfr));
+        return AMOF_OK;
+    };
+    int32_t qflag;
+    AMOF_TRY(frame_lists_run(c, L, FRAME_ORDER, c.spans, order, qflag));
+    int32_t flags[4];
+    AMOF_TRY(c.read_flags(flags));
+    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
+    // atoms absurdly far from the cell, or a centre with more than NBRL_CAP neighbours: the exact kernel
+    if (qflag || flags[1]) return c.reset_outputs();
+    c.done = true;
+    return AMOF_OK;
+}
+
+// exact kernel: every tile of centres of a set against every partner, canonical float64 arithmetic
+static int order_exact_tier(OrderCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    NbrSetup &st = c.st;
+    NbrArgs &a = st.a;
+    std::vector<int4> work;
+    for (int s = 0; s < c.n_sets; s++) {
+        const int A = c.sets[2 * s], B = c.sets[2 * s + 1];
+        for (int k = 0; k < st.tiles.sp_ntiles[A]; k++) work.push_back(make_int4(s, st.tiles.sp_first_tile[A] + k, A, B));
+    }
+    if (work.empty() || t->n_frames <= 0) return AMOF_OK;
+    void *d_work;
+    AMOF_TRY(upload(ctx, SLOT_PAIRS, work.data(), work.size() * sizeof(int4), &d_work));
+    a.work = (const int4 *)d_work;
+    c.o.global_hist = c.words > (size_t)ORDER_EXACT_LDS_BINS ? 1 : 0;
+    const size_t lds = (size_t)(3 * ORDER_CAP * BAD_TILE + 3 * BAD_TILE) * sizeof(double) + BAD_TILE * sizeof(int) +
+                       (c.o.global_hist ? 0 : c.words * sizeof(unsigned));
+    unsigned chunks;
+    pick_chunks(t->n_frames, work.size(), a.frames_per_chunk, chunks);
+    timing_dom_begin(ctx, "order_exact");
+    if (c.spans) c.spans->begin(1);
+    const hipError_t e = with_flag(st.geom.all_ortho, [&](auto O) {
+        return launch_lds(order_kernel<O()>, dim3((unsigned)work.size(), chunks), dim3(BAD_TILE), lds, ctx->stream, a, c.o);
+    });
+    AMOF_HIP_TRY(ctx, e);
+    if (c.spans) c.spans->end();
+    timing_dom_end(ctx, 1);
+    int32_t flags[4];
+    AMOF_TRY(c.read_flags(flags));
+    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
+    if (flags[1]) return fail(ctx, AMOF_ECAPACITY, "a centre has more than %d neighbours", ORDER_CAP);
+    c.done = true;
+    return AMOF_OK;
+}
+
+static int order_check(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets, const int32_t *l,
+                       int32_t n_l, int32_t nbins, int32_t nbins_tet, const void *hist, const void *hist_tet, const void *frame_sums)
+{
+    AMOF_TRY(validate_traj(ctx, t, false));
+    if (!cutoff || n_sets < 0 || (n_sets > 0 && !sets) || !l) return fail(ctx, AMOF_EINVAL, "NULL argument");
+    if (n_l < 1 || n_l > ORDER_MAX_L) return fail(ctx, AMOF_EINVAL, "n_l must be 1..%d", ORDER_MAX_L);
+    for (int q = 0; q < n_l; q++)
+        if (l[q] < 1 || l[q] > ORDER_L_TOP) return fail(ctx, AMOF_EINVAL, "l must be 1..%d", ORDER_L_TOP);
+    if (nbins < 1 || nbins > (1 << 24) || nbins_tet < 1 || nbins_tet > (1 << 24)) return fail(ctx, AMOF_EINVAL, "nbins, nbins_tet must be 1..2^24");
+    if (n_sets > 0 && (!hist || !hist_tet || (t->n_frames > 0 && !frame_sums))) return fail(ctx, AMOF_EINVAL, "NULL argument");
+    const int S = t->n_species;
+    for (int s = 0; s < n_sets; s++)
+        if (sets[2 * s] < 0 || sets[2 * s] >= S || sets[2 * s + 1] < 0 || sets[2 * s + 1] >= S)
+            return fail(ctx, AMOF_EINVAL, "set %d names a species out of range", s);
+    for (int k = 0; k < S * S; k++)
+        if (!(cutoff[k] >= 0.0) || !isfinite(cutoff[k])) return fail(ctx, AMOF_EINVAL, "cutoff must be finite and >= 0");
+    if (n_sets == 0 || t->n_frames == 0) return AMOF_OK;
+    HostGeom geom;
+    AMOF_TRY(build_geometry(ctx, t, geom));
+    double hmin = INFINITY;         // smallest perpendicular height on a periodic axis
+    for (int64_t k = 0; k < t->n_cells; k++)
+        for (int x = 0; x < 3; x++)
+            if (t->pbc[x]) hmin = std::min(hmin, geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
+    for (int s = 0; s < n_sets; s++) {
+        const double rc = cutoff[sets[2 * s] * S + sets[2 * s + 1]];
+        if (rc > 0.5 * hmin)
+            return fail(ctx, AMOF_EINVAL, "cutoff %g of set %d exceeds half the smallest cell height %g: a neighbour could be counted twice",
+                        rc, s, hmin);
+    }
+    return AMOF_OK;
+}
+
+// hist_dev / hist_tet_dev: device buffers to add into, or null (the call's own device buffers are then read back into
+// hist_host / hist_tet_host); frame_sums and per_atom: host
+static int order_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets, const int32_t *l,
+                     int32_t n_l, int32_t nbins, int32_t nbins_tet, uint64_t *hist_dev, uint64_t *hist_tet_dev, uint64_t *hist_host,
+                     uint64_t *hist_tet_host, int64_t *frame_sums, int64_t *per_atom)
+{
+    if (n_sets == 0 || t->n_frames == 0) return AMOF_OK;
+    OrderCall c{{ctx, t, cutoff}, sets, n_sets};
+    AMOF_TRY(nbr_setup(ctx, t, cutoff, BAD_TILE, c.st));
+    StageSpans spans(ctx);      // list stage, order kernels
+    c.spans = &spans;
+    OrderArgs &o = c.o;
+    memset(&o, 0, sizeof o);
+    o.n_l = n_l;
+    for (int q = 0; q < n_l; q++) {
+        o.l[q] = l[q];
+        o.l_top = std::max(o.l_top, l[q]);
+    }
+    o.nbins = nbins;
+    o.nbins_tet = nbins_tet;
+    o.cols = 4 + n_l + 1;
+    const char *sv = getenv("AMOF_ORDER_SUMS");
+    o.lane_sums = sv && !strcmp(sv, "lane") ? 1 : 0;
+    c.words = (size_t)n_l * nbins + (size_t)nbins_tet;
+    const size_t hq = (size_t)n_sets * n_l * nbins, ht = (size_t)n_sets * nbins_tet;
+    c.hs_words = hq + ht;
+    c.fs_bytes = (size_t)t->n_frames * n_sets * o.cols * sizeof(int64_t);
+    AMOF_TRY(ensure(ctx, SLOT_FLAGS, 4 * sizeof(int32_t), &c.d_flags));
+    AMOF_TRY(ensure(ctx, SLOT_AUX7, c.hs_words * sizeof(unsigned long long), &c.d_hs));
+    AMOF_TRY(ensure(ctx, SLOT_OUT0, c.fs_bytes, &c.d_fs));
+    if (per_atom) {
+        c.pa_words = (size_t)t->n_frames * n_sets * (size_t)t->n_atoms * (size_t)(2 + n_l);
+        AMOF_TRY(ensure(ctx, SLOT_OUT1, c.pa_words * sizeof(int64_t), &c.d_pa));
+        std::vector<int32_t> set_a((size_t)n_sets);
+        for (int s = 0; s < n_sets; s++) set_a[(size_t)s] = sets[2 * s];
+        UploadPack pk;
+        const int i_sp = pk.add(t->species, (size_t)t->n_atoms * sizeof(int32_t));
+        const int i_sa = pk.add(set_a.data(), set_a.size() * sizeof(int32_t));
+        AMOF_TRY(upload_pack(ctx, SLOT_AUX3, pk));
+        AMOF_HIP_TRY(ctx, sync_stream(ctx));        // (set_a leaves scope)
+        c.d_species = pk.ptr<int32_t>(i_sp);
+        c.d_set_a = pk.ptr<int32_t>(i_sa);
+    }
+    o.hist = (unsigned long long *)c.d_hs;
+    o.hist_tet = o.hist + hq;
+    o.frame_sums = (unsigned long long *)c.d_fs;
+    o.per_atom = (long long *)c.d_pa;
+    NbrArgs &a = c.st.a;
+    a.n_sets = n_sets;
+    a.flags = (int32_t *)c.d_flags;
+    AMOF_TRY(c.reset_outputs());
+    const char *ex = getenv("AMOF_ORDER_EXACT");
+    if (!(ex && ex[0] == '1')) AMOF_TRY(order_frame_tier(c));
+    AMOF_TRY(stager_need(c.st.stage, t->n_frames));   // (no-op unless the frame tier was skipped)
+    if (!c.done) AMOF_TRY(order_exact_tier(c));
+    // complete and valid: to the caller
+    if (hist_dev) {
+        AMOF_TRY(add_into(ctx, hist_dev, (const uint64_t *)o.hist, hq));
+        AMOF_TRY(add_into(ctx, hist_tet_dev, (const uint64_t *)o.hist_tet, ht));
+    }
+    timing_end(ctx);
+    if (!hist_dev) {
+        AMOF_TRY(fetch(ctx, hist_host, o.hist, hq * sizeof(uint64_t)));
+        AMOF_TRY(fetch(ctx, hist_tet_host, o.hist_tet, ht * sizeof(uint64_t)));
+    }
+    AMOF_TRY(fetch(ctx, frame_sums, c.d_fs, c.fs_bytes));
+    if (per_atom) AMOF_TRY(fetch(ctx, per_atom, c.d_pa, c.pa_words * sizeof(int64_t)));
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
+    spans.collect();
+    return AMOF_OK;
+}
+
 }  // namespace amof
 
 using namespace amof;
@@ -2977,4 +3575,33 @@ extern "C" int amof_bad_hist_by_cn(amof_ctx *ctx, const amof_traj *t, const doub
     AMOF_TRY(bad_check(ctx, t, cutoff, triples, T, edges, nb, hist, n_angles));
     if (cn_max < 1 || cn_max > 65535) return fail(ctx, AMOF_EINVAL, "cn_max must be 1..65535");
     return bad_hist_host(ctx, t, cutoff, triples, T, edges, nb, cn_max, hist, n_angles);
+}
+
+extern "C" int amof_bond_order(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets,
+                               const int32_t *l, int32_t n_l, int32_t nbins, int32_t nbins_tet, uint64_t *hist, uint64_t *hist_tet,
+                               int64_t *frame_sums, int64_t *per_atom)
+{
+    if (!ctx) return AMOF_EINVAL;
+    AMOF_TRY(order_check(ctx, t, cutoff, sets, n_sets, l, n_l, nbins, nbins_tet, hist, hist_tet, frame_sums));
+    // the host form overwrites: zeros first, so that a failing call leaves zeros
+    if (n_sets > 0) {
+        std::fill(hist, hist + (size_t)n_sets * n_l * nbins, (uint64_t)0);
+        std::fill(hist_tet, hist_tet + (size_t)n_sets * nbins_tet, (uint64_t)0);
+        if (t->n_frames > 0) std::fill(frame_sums, frame_sums + (size_t)t->n_frames * n_sets * (4 + n_l + 1), (int64_t)0);
+        if (per_atom) std::fill(per_atom, per_atom + (size_t)t->n_frames * n_sets * (size_t)t->n_atoms * (2 + n_l), (int64_t)0);
+    }
+    return order_run(ctx, t, cutoff, sets, n_sets, l, n_l, nbins, nbins_tet, nullptr, nullptr, hist, hist_tet, frame_sums, per_atom);
+}
+
+extern "C" int amof_bond_order_dev(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets,
+                                   const int32_t *l, int32_t n_l, int32_t nbins, int32_t nbins_tet, uint64_t *hist_dev,
+                                   uint64_t *hist_tet_dev, int64_t *frame_sums, int64_t *per_atom)
+{
+    if (!ctx) return AMOF_EINVAL;
+    AMOF_TRY(order_check(ctx, t, cutoff, sets, n_sets, l, n_l, nbins, nbins_tet, hist_dev, hist_tet_dev, frame_sums));
+    if (n_sets > 0 && t->n_frames > 0) {
+        std::fill(frame_sums, frame_sums + (size_t)t->n_frames * n_sets * (4 + n_l + 1), (int64_t)0);
+        if (per_atom) std::fill(per_atom, per_atom + (size_t)t->n_frames * n_sets * (size_t)t->n_atoms * (2 + n_l), (int64_t)0);
+    }
+    return order_run(ctx, t, cutoff, sets, n_sets, l, n_l, nbins, nbins_tet, hist_dev, hist_tet_dev, nullptr, nullptr, frame_sums, per_atom);
 }

@@ -125,6 +125,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * which = 2 the rho table (quantisation included), 3 the correlation kernel, 4 the self part (0 if not asked for);
  * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations;
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
+ * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
  * Returns < 0 if unavailable. */
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which);
 /* number of launches of the dominant kernel in the last call */
@@ -156,7 +157,10 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        the guard band re-decided exactly), "bond_series_exact" (canonical float64 arithmetic per pair and frame: general
  *        and per-frame cells, open axes; also AMOF_BOND_EXACT=1)
  *   bond reorientation "bond_reorient" (the bond indicator decided as "bond_series"), "bond_reorient_exact" (as
- *        "bond_series_exact"); the bond vectors are the canonical float64 ones on both */
+ *        "bond_series_exact"); the bond vectors are the canonical float64 ones on both
+ *   bond order "order_frame" (the neighbour rows of BAD's frame tier: whole frames or z-slabs in LDS), "order_exact"
+ *        (canonical float64 arithmetic per pair: general and per-frame cells, open axes, centres with 17 .. 64
+ *        neighbours; also AMOF_ORDER_EXACT=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -392,6 +396,53 @@ int amof_bond_reorientation_dev(amof_ctx *ctx, const amof_traj *traj, const doub
                                 const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t atom_begin,
                                 int64_t atom_end, int64_t *out_dev /* device [n_sets][W][3], += */,
                                 int32_t *scale_log2 /* host [n_sets] */);
+
+/*
+ * Bond order parameters of neighbour shells: Steinhardt q_l and the tetrahedral order parameter q_tet per centre atom.
+ * Replaces nothing in the reference (it stops at bond counts and angle histograms, amof/cn.py, amof/bad.py); both are
+ * non-linear functions of ALL the angles of one centre, which a histogram of angles cannot give.
+ *   cutoff, sets: as amof_cn_count, and so is the neighbour decision: strict sqrt(d2) < rc on the canonical minimum image.
+ *   As amof_bond_survival, a cutoff of a set above half the smallest perpendicular cell height on a periodic axis is
+ *   refused (AMOF_EINVAL): a neighbour is then one image, and n is amof_cn_count's per-atom count.
+ *   Centre i (species A) with n neighbours of species B: u_1 .. u_n = v / sqrt(vx vx + vy vy + vz vz) of the canonical
+ *   minimum-image vectors (as BAD; a zero-length vector returns AMOF_EANGLE).  For every unordered pair j < k:
+ *     c = ux*vx + uy*vy + uz*vz, clipped to [-1, 1]                   (BAD's expression and operation order, no fma)
+ *     P_m(c) by the Bonnet recurrence in float64: p0 = 1, p1 = c,
+ *         p_{m+1} = (((double)(2m+1) * c) * p_m - (double)m * p_{m-1}) / (double)(m+1)
+ *     with E = 40:  T_l(i) = sum_{j<k} llrint(P_l(c) * 2^E)                                  (int64)
+ *                   U(i)   = sum_{j<k} llrint((c + 1.0/3.0) * (c + 1.0/3.0) * 2^E)           (used when n == 4)
+ *   By the addition theorem of the spherical harmonics q_l^2 = (n + 2 sum_{j<k} P_l(cos theta_jk)) / n^2, so
+ *     Q_l = max(0, n*2^E + 2*T_l),  q_l = sqrt(ldexp((double)Q_l, -E)) / (double)n          n >= 1 (n = 1: exactly 1)
+ *     q_tet = 1.0 - 0.375 * ldexp((double)U, -E)                                             n == 4 only; in [-3, 1]
+ *   A centre with more than 64 neighbours returns AMOF_ECAPACITY; up to 64, Q_l < 2^53 converts exactly.
+ *   l[n_l]: 1 <= n_l <= 4 values, each in 1 .. 12.
+ *   Bins: q_l:   b = min((int)(q_l * (double)nbins), nbins - 1)
+ *         q_tet: b = min((int)((q_tet + 3.0) * 0.25 * (double)nbins_tet), nbins_tet - 1)     (last bin right-closed: q = 1 counts)
+ *   Outputs, over the frames of the call:
+ *     hist [n_sets][n_l][nbins]: centres with n >= 1;  hist_tet [n_sets][nbins_tet]: centres with n == 4
+ *     frame_sums int64 [F][n_sets][4 + n_l + 1]: sum of n (amof_cn_count's sums[f][s], bit for bit), centres with n >= 1,
+ *       centres with n == 4, sum of n (n - 1) / 2 (amof_bad_hist's n_angles of the triple B-A-B over the same frames),
+ *       sum of llrint(q_l * 2^30) per l, sum of llrint(q_tet * 2^30)
+ *     per_atom (optional, may be NULL) int64 [F][n_sets][N][2 + n_l]: (n, T_l ..., U); n = -1 where the atom is not of species A
+ *   All outputs are integers: frame ranges concatenate / add up bit for bit, and nothing depends on launch geometry,
+ *   batching or the path ("order_frame": the neighbour rows of BAD's frame tier; "order_exact": canonical float64
+ *   arithmetic per pair, any cell, up to 64 neighbours; AMOF_ORDER_EXACT=1 forces it; AMOF_ORDER_ROWS_MB=n caps
+ *   the scratch of the neighbour rows -- more, smaller frame batches; 0: one frame per batch).
+ *   amof_last_kernel_seconds: which = 2 the list stage, 3 the order kernels.
+ * The host form overwrites hist, hist_tet, frame_sums and per_atom (zeros after an error).  The _dev form ADDS hist and
+ * hist_tet into device buffers (frame-sharded ranks all-reduce them next); frame_sums and per_atom stay host buffers, as
+ * amof_cn_count's sums.  Errors: AMOF_EINVAL, AMOF_EANGLE, AMOF_ECAPACITY, AMOF_ESINGULAR, AMOF_ENOMEM, AMOF_EHIP.
+ */
+int amof_bond_order(amof_ctx *ctx, const amof_traj *traj, const double *cutoff /* [S][S], as amof_cn_count */,
+                    const int32_t *sets /* [n_sets][2] */, int32_t n_sets, const int32_t *l /* host [n_l] */, int32_t n_l,
+                    int32_t nbins, int32_t nbins_tet, uint64_t *hist /* host [n_sets][n_l][nbins] */,
+                    uint64_t *hist_tet /* host [n_sets][nbins_tet] */, int64_t *frame_sums /* host [F][n_sets][4 + n_l + 1] */,
+                    int64_t *per_atom /* host [F][n_sets][N][2 + n_l] or NULL */);
+int amof_bond_order_dev(amof_ctx *ctx, const amof_traj *traj, const double *cutoff, const int32_t *sets, int32_t n_sets,
+                        const int32_t *l, int32_t n_l, int32_t nbins, int32_t nbins_tet,
+                        uint64_t *hist_dev /* device [n_sets][n_l][nbins], += */,
+                        uint64_t *hist_tet_dev /* device [n_sets][nbins_tet], += */, int64_t *frame_sums /* host */,
+                        int64_t *per_atom /* host or NULL */);
 
 /*
  * Static structure factor by direct summation over reciprocal-lattice vectors.
