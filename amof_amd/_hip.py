@@ -353,6 +353,46 @@ class Lane(object):
             self._lane = None
 
 
+# -- marshalling: what the entry points of include/amof_hip.h take, from what the callers hand in -------------------------
+def _ptr(x):
+    """``c_void_p`` of a numpy array's or a torch tensor's memory; None (an optional argument) stays None"""
+    if x is None:
+        return None
+    return ctypes.c_void_p(x.ctypes.data if isinstance(x, np.ndarray) else x.data_ptr())
+
+
+def _cutoff(x, S):
+    """cutoff matrix ``[S][S]`` f64"""
+    return np.ascontiguousarray(x, dtype=np.float64).reshape(S, S)
+
+
+def _pairs(x):
+    """``sets`` / ``triples``: species index pairs ``[n][2]`` i32"""
+    return np.ascontiguousarray(x, dtype=np.int32).reshape(-1, 2)
+
+
+def _i32(x):
+    """``windows`` (and other index lists): i32"""
+    return np.ascontiguousarray(x, dtype=np.int32)
+
+
+def _hkl(x):
+    """reciprocal-lattice vectors ``[K][3]`` i32"""
+    return np.ascontiguousarray(x, dtype=np.int32).reshape(-1, 3)
+
+
+def _recip(packed, recip):
+    """``[n_cells][3][3]`` f64 reciprocal cells of a trajectory (default: ``reciprocal(packed.cell)``)"""
+    recip = np.ascontiguousarray(reciprocal(packed.cell) if recip is None else recip, dtype=np.float64)
+    assert recip.shape == (packed.cell.shape[0], 3, 3)
+    return recip
+
+
+def _span(given, n):
+    """a ``frame_range`` / ``atom_range`` argument as ``(lo, hi)``: all ``n`` by default"""
+    return (0, n) if given is None else tuple(given)
+
+
 def _whole_work_list(n_frames, windows, origin_stride):
     """``work_range`` of every (lag, origin) pair (a stride below 1 is the library's to refuse)"""
     from . import lags
@@ -540,72 +580,51 @@ class Context(Lane):
         if out is not None:
             self._check_out(out, th.S * th.S * nbins)
             self._order_after_torch()
-            rc = self._lib.amof_rdf_accumulate_dev(self._h, ctypes.byref(th.c), float(rmax), int(nbins),
-                                                   ctypes.c_void_p(out.data_ptr()), ctypes.byref(vol))
-            self._check(rc)
-            return out, vol.value, th.kinds
-        hist = np.zeros((th.S, th.S, nbins), dtype=np.uint64)
-        rc = self._lib.amof_rdf_accumulate(self._h, ctypes.byref(th.c), float(rmax), int(nbins),
-                                           ctypes.c_void_p(hist.ctypes.data), ctypes.byref(vol))
-        self._check(rc)
+            fn, hist = self._lib.amof_rdf_accumulate_dev, out
+        else:
+            fn, hist = self._lib.amof_rdf_accumulate, np.zeros((th.S, th.S, nbins), dtype=np.uint64)
+        self._check(fn(self._h, ctypes.byref(th.c), float(rmax), int(nbins), _ptr(hist), ctypes.byref(vol)))
         return hist, vol.value, th.kinds
 
     @_locked
     def cn_count(self, packed, cutoff, sets, frame_range=None, per_atom=False):
         th = self._traj(packed, frame_range)
-        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64).reshape(th.S, th.S)
-        sets = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 2)
+        cutoff, sets = _cutoff(cutoff, th.S), _pairs(sets)
         sums = np.zeros((th.n_frames, len(sets)), dtype=np.int64)
         pa = np.zeros((th.n_frames, len(sets), th.n_atoms), dtype=np.int32) if per_atom else None
-        rc = self._lib.amof_cn_count(self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data),
-                                     ctypes.c_void_p(sets.ctypes.data), len(sets),
-                                     ctypes.c_void_p(sums.ctypes.data),
-                                     ctypes.c_void_p(pa.ctypes.data) if per_atom else None)
-        self._check(rc)
+        self._check(self._lib.amof_cn_count(self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(sets), len(sets), _ptr(sums), _ptr(pa)))
         return (sums, pa) if per_atom else sums
 
     @_locked
     def bad_hist(self, packed, cutoff, triples, edges, frame_range=None, out=None):
         th = self._traj(packed, frame_range)
-        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64).reshape(th.S, th.S)
-        triples = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 2)
+        cutoff, triples = _cutoff(cutoff, th.S), _pairs(triples)
         edges = np.ascontiguousarray(edges, dtype=np.float64)
         nb = len(edges) - 1
         if out is not None:
-            hist_t, nang_t = out
-            for x, n in ((hist_t, len(triples) * nb), (nang_t, len(triples))):
+            hist, nang = out
+            for x, n in ((hist, len(triples) * nb), (nang, len(triples))):
                 self._check_out(x, n)
             self._order_after_torch()
-            rc = self._lib.amof_bad_hist_dev(self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data),
-                                             ctypes.c_void_p(triples.ctypes.data), len(triples),
-                                             ctypes.c_void_p(edges.ctypes.data), nb,
-                                             ctypes.c_void_p(hist_t.data_ptr()), ctypes.c_void_p(nang_t.data_ptr()))
-            self._check(rc)
-            return hist_t, nang_t
-        hist = np.zeros((len(triples), nb), dtype=np.uint64)
-        nang = np.zeros(len(triples), dtype=np.uint64)
-        rc = self._lib.amof_bad_hist(self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data),
-                                     ctypes.c_void_p(triples.ctypes.data), len(triples),
-                                     ctypes.c_void_p(edges.ctypes.data), nb,
-                                     ctypes.c_void_p(hist.ctypes.data), ctypes.c_void_p(nang.ctypes.data))
-        self._check(rc)
+            fn = self._lib.amof_bad_hist_dev
+        else:
+            hist, nang = np.zeros((len(triples), nb), dtype=np.uint64), np.zeros(len(triples), dtype=np.uint64)
+            fn = self._lib.amof_bad_hist
+        self._check(fn(self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(triples), len(triples), _ptr(edges), nb, _ptr(hist),
+                       _ptr(nang)))
         return hist, nang
 
     @_locked
     def bad_hist_by_cn(self, packed, cutoff, triples, edges, cn_max=16, frame_range=None):
         """``(hist u64 [T][cn_max+1][nb], n_angles u64 [T][cn_max+1])`` keyed by neighbour count."""
         th = self._traj(packed, frame_range)
-        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64).reshape(th.S, th.S)
-        triples = np.ascontiguousarray(triples, dtype=np.int32).reshape(-1, 2)
+        cutoff, triples = _cutoff(cutoff, th.S), _pairs(triples)
         edges = np.ascontiguousarray(edges, dtype=np.float64)
         nb = len(edges) - 1
         hist = np.zeros((len(triples), cn_max + 1, nb), dtype=np.uint64)
         nang = np.zeros((len(triples), cn_max + 1), dtype=np.uint64)
-        rc = self._lib.amof_bad_hist_by_cn(self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data),
-                                           ctypes.c_void_p(triples.ctypes.data), len(triples),
-                                           ctypes.c_void_p(edges.ctypes.data), nb, int(cn_max),
-                                           ctypes.c_void_p(hist.ctypes.data), ctypes.c_void_p(nang.ctypes.data))
-        self._check(rc)
+        self._check(self._lib.amof_bad_hist_by_cn(self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(triples), len(triples),
+                                                  _ptr(edges), nb, int(cn_max), _ptr(hist), _ptr(nang)))
         return hist, nang
 
     @_locked
@@ -615,8 +634,7 @@ class Context(Lane):
         th = self._traj(packed)
         self._check_out(out, 3 * th.n_frames)
         self._order_after_torch()
-        self._check(self._lib.amof_msd_com_dev(self._h, ctypes.byref(th.c), int(frame_range[0]), int(frame_range[1]),
-                                               ctypes.c_void_p(out.data_ptr())))
+        self._check(self._lib.amof_msd_com_dev(self._h, ctypes.byref(th.c), int(frame_range[0]), int(frame_range[1]), _ptr(out)))
         return out
 
     @_locked
@@ -626,8 +644,9 @@ class Context(Lane):
         ``out``: optional torch CUDA f64 tensor ``[S][W]`` the sums are ADDED into on the device (stays resident for
         the ranks' all-reduce); ``com``: optional torch CUDA f64 ``[F][3]`` precomputed centre of mass (``msd_com``)."""
         th = self._traj(packed)
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
-        a0, a1 = (0, th.n_atoms) if atom_range is None else atom_range
+        windows = _i32(windows)
+        a0, a1 = _span(atom_range, th.n_atoms)
+        args = (self._h, ctypes.byref(th.c), _ptr(windows), len(windows), 1 if unwrap else 0, 1 if remove_com else 0, int(a0), int(a1))
         if out is not None or com is not None:
             import torch
             if out is None:
@@ -636,19 +655,11 @@ class Context(Lane):
             if com is not None:
                 self._check_out(com, 3 * th.n_frames)
             self._order_after_torch()
-            rc = self._lib.amof_msd_window_dev(self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data),
-                                               len(windows), 1 if unwrap else 0, 1 if remove_com else 0, int(a0), int(a1),
-                                               ctypes.c_void_p(com.data_ptr()) if com is not None else None,
-                                               ctypes.c_void_p(out.data_ptr()))
-            self._check(rc)
+            self._check(self._lib.amof_msd_window_dev(*args, _ptr(com), _ptr(out)))
             return out, th.kinds
         out = np.zeros((th.S, len(windows)), dtype=np.float64)
-        rc = self._lib.amof_msd_window(self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data),
-                                       len(windows), 1 if unwrap else 0, 1 if remove_com else 0,
-                                       int(a0), int(a1), ctypes.c_void_p(out.ctypes.data))
-        self._check(rc)
+        self._check(self._lib.amof_msd_window(*args, _ptr(out)))
         return out, th.kinds
-
 
     @_locked
     def vanhove_window(self, packed, windows, dr, nbins, unwrap=False, remove_com=True, atom_range=None, com=None, out=None):
@@ -659,11 +670,11 @@ class Context(Lane):
         ``[S][W][2]``) the results are ADDED into on the device (they stay resident for the ranks' all-reduce); ``com``:
         optional torch CUDA f64 ``[F][3]`` precomputed centre of mass (``msd_com``)."""
         th = self._traj(packed)
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
-        a0, a1 = (0, th.n_atoms) if atom_range is None else atom_range
+        windows = _i32(windows)
+        a0, a1 = _span(atom_range, th.n_atoms)
         S, W, nbins = th.S, len(windows), int(nbins)
-        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), W, 1 if unwrap else 0,
-                1 if remove_com else 0, int(a0), int(a1), float(dr), nbins)
+        args = (self._h, ctypes.byref(th.c), _ptr(windows), W, 1 if unwrap else 0, 1 if remove_com else 0, int(a0), int(a1),
+                float(dr), nbins)
         if out is not None or com is not None:
             import torch
             dev = torch.device("cuda", self.device)
@@ -675,16 +686,11 @@ class Context(Lane):
             if com is not None:
                 self._check_out(com, 3 * th.n_frames)
             self._order_after_torch()
-            self._check(self._lib.amof_vanhove_window_dev(*(args + (ctypes.c_void_p(com.data_ptr()) if com is not None else None,) +
-                                                           tuple(ctypes.c_void_p(x.data_ptr()) for x in out))))
+            self._check(self._lib.amof_vanhove_window_dev(*args, _ptr(com), *[_ptr(x) for x in out]))
             return out + (th.kinds,)
-        counts = np.zeros((S, W, nbins), dtype=np.uint64)
-        overflow = np.zeros((S, W), dtype=np.uint64)
-        moments = np.zeros((S, W, 2), dtype=np.float64)
-        self._check(self._lib.amof_vanhove_window(*(args + (ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(overflow.ctypes.data),
-                                                            ctypes.c_void_p(moments.ctypes.data)))))
-        return counts, overflow, moments, th.kinds
-
+        out = (np.zeros((S, W, nbins), dtype=np.uint64), np.zeros((S, W), dtype=np.uint64), np.zeros((S, W, 2), dtype=np.float64))
+        self._check(self._lib.amof_vanhove_window(*args, *[_ptr(x) for x in out]))
+        return out + (th.kinds,)
 
     @_locked
     def vanhove_distinct(self, packed, windows, rmax, nbins, origin_stride=1, work_range=None, out=None):
@@ -694,19 +700,18 @@ class Context(Lane):
         ``out``: optional torch CUDA int64 tensor ``[S][S][W][nbins]`` the counts are ADDED into on the device (stays
         resident for an RCCL merge)."""
         th = self._traj(packed)
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        windows = _i32(windows)
         W, nbins = len(windows), int(nbins)
         if work_range is None:
             work_range = _whole_work_list(th.n_frames, windows, origin_stride)
-        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), W, int(origin_stride), int(work_range[0]),
-                int(work_range[1]), float(rmax), nbins)
         if out is not None:
             self._check_out(out, th.S * th.S * W * nbins)
             self._order_after_torch()
-            self._check(self._lib.amof_vanhove_distinct_dev(*(args + (ctypes.c_void_p(out.data_ptr()),))))
-            return out, th.kinds
-        hist = np.zeros((th.S, th.S, W, nbins), dtype=np.uint64)
-        self._check(self._lib.amof_vanhove_distinct(*(args + (ctypes.c_void_p(hist.ctypes.data),))))
+            fn, hist = self._lib.amof_vanhove_distinct_dev, out
+        else:
+            fn, hist = self._lib.amof_vanhove_distinct, np.zeros((th.S, th.S, W, nbins), dtype=np.uint64)
+        self._check(fn(self._h, ctypes.byref(th.c), _ptr(windows), W, int(origin_stride), int(work_range[0]), int(work_range[1]),
+                       float(rmax), nbins, _ptr(hist)))
         return hist, th.kinds
 
     @_locked
@@ -718,19 +723,17 @@ class Context(Lane):
         ``out``: optional torch CUDA int64 tensor ``[n_sets][W][3]`` the counters are ADDED into on the device (stays
         resident for an RCCL merge)."""
         th = self._traj(packed)
-        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64).reshape(th.S, th.S)
-        sets = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 2)
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
-        a0, a1 = (0, th.n_atoms) if atom_range is None else atom_range
-        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data), ctypes.c_void_p(sets.ctypes.data), len(sets),
-                ctypes.c_void_p(windows.ctypes.data), len(windows), int(origin_stride), int(a0), int(a1))
+        cutoff, sets, windows = _cutoff(cutoff, th.S), _pairs(sets), _i32(windows)
+        a0, a1 = _span(atom_range, th.n_atoms)
+        n_sets, W = len(sets), len(windows)
+        args = (self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(sets), n_sets, _ptr(windows), W, int(origin_stride), int(a0), int(a1))
         if out is not None:
-            self._check_out(out, len(sets) * len(windows) * 3)
+            self._check_out(out, n_sets * W * 3)
             self._order_after_torch()
-            self._check(self._lib.amof_bond_survival_dev(*(args + (ctypes.c_void_p(out.data_ptr()),))))
-            return out
-        counts = np.zeros((len(sets), len(windows), 3), dtype=np.uint64)
-        self._check(self._lib.amof_bond_survival(*(args + (ctypes.c_void_p(counts.ctypes.data),))))
+            fn, counts = self._lib.amof_bond_survival_dev, out
+        else:
+            fn, counts = self._lib.amof_bond_survival, np.zeros((n_sets, W, 3), dtype=np.uint64)
+        self._check(fn(*args, _ptr(counts)))
         return counts
 
     @_locked
@@ -743,22 +746,18 @@ class Context(Lane):
         ``out``: optional torch CUDA int64 tensor ``[n_sets][W][3]`` the sums are ADDED into on the device (stays resident
         for an RCCL merge)."""
         th = self._traj(packed)
-        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64).reshape(th.S, th.S)
-        sets = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 2)
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
-        a0, a1 = (0, th.n_atoms) if atom_range is None else atom_range
-        scale = np.zeros(len(sets), dtype=np.int32)
-        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data), ctypes.c_void_p(sets.ctypes.data), len(sets),
-                ctypes.c_void_p(windows.ctypes.data), len(windows), int(origin_stride), int(a0), int(a1))
+        cutoff, sets, windows = _cutoff(cutoff, th.S), _pairs(sets), _i32(windows)
+        a0, a1 = _span(atom_range, th.n_atoms)
+        n_sets, W = len(sets), len(windows)
+        args = (self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(sets), n_sets, _ptr(windows), W, int(origin_stride), int(a0), int(a1))
+        scale = np.zeros(n_sets, dtype=np.int32)
         if out is not None:
-            self._check_out(out, len(sets) * len(windows) * 3)
+            self._check_out(out, n_sets * W * 3)
             self._order_after_torch()
-            self._check(self._lib.amof_bond_reorientation_dev(*(args + (ctypes.c_void_p(out.data_ptr()),
-                                                                        ctypes.c_void_p(scale.ctypes.data)))))
-            return out, scale
-        sums = np.zeros((len(sets), len(windows), 3), dtype=np.int64)
-        self._check(self._lib.amof_bond_reorientation(*(args + (ctypes.c_void_p(sums.ctypes.data),
-                                                                ctypes.c_void_p(scale.ctypes.data)))))
+            fn, sums = self._lib.amof_bond_reorientation_dev, out
+        else:
+            fn, sums = self._lib.amof_bond_reorientation, np.zeros((n_sets, W, 3), dtype=np.int64)
+        self._check(fn(*args, _ptr(sums), _ptr(scale)))
         return sums, scale
 
     @_locked
@@ -773,27 +772,23 @@ class Context(Lane):
         ``out``: optional pair of torch CUDA int64 tensors ``([n_sets][n_l][nbins], [n_sets][nbins_tet])`` the histograms
         are ADDED into on the device (they stay resident for an RCCL merge); they are returned in place of the arrays."""
         th = self._traj(packed, frame_range)
-        cutoff = np.ascontiguousarray(cutoff, dtype=np.float64).reshape(th.S, th.S)
-        sets = np.ascontiguousarray(sets, dtype=np.int32).reshape(-1, 2)
-        l = np.ascontiguousarray(l, dtype=np.int32).reshape(-1)
+        cutoff, sets = _cutoff(cutoff, th.S), _pairs(sets)
+        l = _i32(l).reshape(-1)
         nbins, nbins_tet = int(nbins), int(nbins_tet)
         sums = np.zeros((th.n_frames, len(sets), 4 + len(l) + 1), dtype=np.int64)
         pa = np.zeros((th.n_frames, len(sets), th.n_atoms, 2 + len(l)), dtype=np.int64) if per_atom else None
-        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(cutoff.ctypes.data), ctypes.c_void_p(sets.ctypes.data), len(sets),
-                ctypes.c_void_p(l.ctypes.data), len(l), nbins, nbins_tet)
-        tail = (ctypes.c_void_p(sums.ctypes.data), ctypes.c_void_p(pa.ctypes.data) if per_atom else None)
         if out is not None:
             hist, hist_tet = out
             self._check_out(hist, len(sets) * len(l) * nbins)
             self._check_out(hist_tet, len(sets) * nbins_tet)
             self._order_after_torch()
-            self._check(self._lib.amof_bond_order_dev(*(args + (ctypes.c_void_p(hist.data_ptr()),
-                                                                ctypes.c_void_p(hist_tet.data_ptr())) + tail)))
+            fn = self._lib.amof_bond_order_dev
         else:
             hist = np.zeros((len(sets), len(l), nbins), dtype=np.uint64)
             hist_tet = np.zeros((len(sets), nbins_tet), dtype=np.uint64)
-            self._check(self._lib.amof_bond_order(*(args + (ctypes.c_void_p(hist.ctypes.data),
-                                                            ctypes.c_void_p(hist_tet.ctypes.data)) + tail)))
+            fn = self._lib.amof_bond_order
+        self._check(fn(self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(sets), len(sets), _ptr(l), len(l), nbins, nbins_tet,
+                       _ptr(hist), _ptr(hist_tet), _ptr(sums), _ptr(pa)))
         return (hist, hist_tet, sums, pa) if per_atom else (hist, hist_tet, sums)
 
     @_locked
@@ -806,30 +801,24 @@ class Context(Lane):
         ``[P][nbins]``: fixed-point sums) the results are ADDED into on the device; returns ``(counts, sums, scale_log2,
         kinds)`` then, with sums = ``sums * 2**-scale_log2[p]``."""
         th = self._traj(packed)
-        hkl = np.ascontiguousarray(hkl, dtype=np.int32).reshape(-1, 3)
-        recip = np.ascontiguousarray(reciprocal(packed.cell) if recip is None else recip, dtype=np.float64)
-        assert recip.shape == (packed.cell.shape[0], 3, 3)
-        f0, f1 = (0, th.n_frames) if frame_range is None else frame_range
+        hkl, recip = _hkl(hkl), _recip(packed, recip)
+        f0, f1 = _span(frame_range, th.n_frames)
         S, nbins = th.S, int(nbins)
         P = S * (S + 1) // 2
-        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(recip.ctypes.data), ctypes.c_void_p(hkl.ctypes.data), len(hkl),
-                int(f0), int(f1), int(frame_stride), float(dq), nbins)
+        args = (self._h, ctypes.byref(th.c), _ptr(recip), _ptr(hkl), len(hkl), int(f0), int(f1), int(frame_stride), float(dq), nbins)
         if out is not None:
             counts, sums = out
             self._check_out(counts, nbins + 1)
             self._check_out(sums, P * nbins)
             scale = np.zeros(P, dtype=np.int32)
             self._order_after_torch()
-            self._check(self._lib.amof_sq_accumulate_dev(*(args + (ctypes.c_void_p(counts.data_ptr()),
-                                                                   ctypes.c_void_p(sums.data_ptr()),
-                                                                   ctypes.c_void_p(counts.data_ptr() + 8 * nbins),
-                                                                   ctypes.c_void_p(scale.ctypes.data)))))
+            self._check(self._lib.amof_sq_accumulate_dev(*args, _ptr(counts), _ptr(sums), ctypes.c_void_p(counts.data_ptr() + 8 * nbins),
+                                                         _ptr(scale)))
             return counts, sums, scale, th.kinds
         counts = np.zeros(nbins, dtype=np.uint64)
         sums = np.zeros((P, nbins), dtype=np.float64)
         beyond = np.zeros(1, dtype=np.uint64)
-        self._check(self._lib.amof_sq_accumulate(*(args + (ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(sums.ctypes.data),
-                                                           ctypes.c_void_p(beyond.ctypes.data)))))
+        self._check(self._lib.amof_sq_accumulate(*args, _ptr(counts), _ptr(sums), _ptr(beyond)))
         return counts, sums, int(beyond[0]), th.kinds
 
     @_locked
@@ -844,34 +833,26 @@ class Context(Lane):
         fixed-point coh, fixed-point self) the results are ADDED into on the device; returns ``(out, scale_log2, kinds)``
         then, with coh[a][c] = ``coh * 2**-scale_log2[p]``, p the unordered pair of ``sq_accumulate``'s order."""
         th = self._traj(packed)
-        hkl = np.ascontiguousarray(hkl, dtype=np.int32).reshape(-1, 3)
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
-        recip = np.ascontiguousarray(reciprocal(packed.cell) if recip is None else recip, dtype=np.float64)
-        assert recip.shape == (packed.cell.shape[0], 3, 3)
+        hkl, windows, recip = _hkl(hkl), _i32(windows), _recip(packed, recip)
         S, W, nbins = th.S, len(windows), int(nbins)
         if work_range is None:
             work_range = _whole_work_list(th.n_frames, windows, origin_stride)
-        args = (self._h, ctypes.byref(th.c), ctypes.c_void_p(recip.ctypes.data), ctypes.c_void_p(hkl.ctypes.data), len(hkl),
-                ctypes.c_void_p(windows.ctypes.data), W, int(origin_stride), int(work_range[0]), int(work_range[1]), float(dq),
-                nbins)
+        args = (self._h, ctypes.byref(th.c), _ptr(recip), _ptr(hkl), len(hkl), _ptr(windows), W, int(origin_stride),
+                int(work_range[0]), int(work_range[1]), float(dq), nbins)
         if out is not None:
             lay = isf_layout(S, W, nbins, self_part)
             self._check_out(out, lay["size"])
             scale = np.zeros(S * (S + 1) // 2, dtype=np.int32)
-            base = out.data_ptr()
+            part = [ctypes.c_void_p(out.data_ptr() + 8 * lay[k]) for k in ("counts", "coh", "self", "beyond")]
             self._order_after_torch()
-            self._check(self._lib.amof_isf_accumulate_dev(*(args + (
-                ctypes.c_void_p(base + 8 * lay["counts"]), ctypes.c_void_p(base + 8 * lay["coh"]),
-                ctypes.c_void_p(base + 8 * lay["self"]) if self_part else None, ctypes.c_void_p(base + 8 * lay["beyond"]),
-                ctypes.c_void_p(scale.ctypes.data)))))
+            self._check(self._lib.amof_isf_accumulate_dev(*args, part[0], part[1], part[2] if self_part else None, part[3],
+                                                          _ptr(scale)))
             return out, scale, th.kinds
         counts = np.zeros((W, nbins), dtype=np.uint64)
         coh = np.zeros((S, S, W, nbins), dtype=np.float64)
         selfs = np.zeros((S, W, nbins), dtype=np.float64) if self_part else None
         beyond = np.zeros(W, dtype=np.uint64)
-        self._check(self._lib.amof_isf_accumulate(*(args + (
-            ctypes.c_void_p(counts.ctypes.data), ctypes.c_void_p(coh.ctypes.data),
-            ctypes.c_void_p(selfs.ctypes.data) if self_part else None, ctypes.c_void_p(beyond.ctypes.data)))))
+        self._check(self._lib.amof_isf_accumulate(*args, _ptr(counts), _ptr(coh), _ptr(selfs), _ptr(beyond)))
         return counts, coh, selfs, beyond, th.kinds
 
     def last_stage_seconds(self):
@@ -887,10 +868,9 @@ class Context(Lane):
     def sq_modes(self, packed, hkl, frame=0):
         """``(rho [K][S] complex128, kinds)``: rho_a(k) of one frame for the vectors ``hkl`` (``amof_sq_modes``)"""
         th = self._traj(packed)
-        hkl = np.ascontiguousarray(hkl, dtype=np.int32).reshape(-1, 3)
+        hkl = _hkl(hkl)
         rho = np.zeros((len(hkl), th.S, 2), dtype=np.float64)
-        self._check(self._lib.amof_sq_modes(self._h, ctypes.byref(th.c), int(frame), ctypes.c_void_p(hkl.ctypes.data), len(hkl),
-                                            ctypes.c_void_p(rho.ctypes.data)))
+        self._check(self._lib.amof_sq_modes(self._h, ctypes.byref(th.c), int(frame), _ptr(hkl), len(hkl), _ptr(rho)))
         return rho[:, :, 0] + 1j * rho[:, :, 1], th.kinds
 
     @_locked
@@ -899,11 +879,11 @@ class Context(Lane):
         the mass-weighted coordinate sums of the atoms ``[a0, a1)`` per frame -- the caller all-reduces it over the ranks.
         Raises :class:`Unsupported` where the fused form does not apply (the caller then takes ``msd_com`` + ``msd_window``)."""
         th = self._traj(packed)
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        windows = _i32(windows)
         self._check_out(csum, 3 * th.n_frames)
         self._order_after_torch()
-        self._check(self._lib.amof_msd_shard_begin(self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), len(windows),
-                                                   int(atom_range[0]), int(atom_range[1]), ctypes.c_void_p(csum.data_ptr())))
+        self._check(self._lib.amof_msd_shard_begin(self._h, ctypes.byref(th.c), _ptr(windows), len(windows), int(atom_range[0]),
+                                                   int(atom_range[1]), _ptr(csum)))
         return csum
 
     @_locked
@@ -911,13 +891,12 @@ class Context(Lane):
         """second half (``amof_msd_shard_finish``, the next call on this context after its begin): adds the sums of the
         atoms ``[a0, a1)`` into ``out`` (torch CUDA f64 ``[S][W]``); ``csum`` = the table summed over the ranks"""
         th = self._traj(packed)
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        windows = _i32(windows)
         self._check_out(csum, 3 * th.n_frames)
         self._check_out(out, th.S * len(windows))
         self._order_after_torch()
-        self._check(self._lib.amof_msd_shard_finish(self._h, ctypes.byref(th.c), ctypes.c_void_p(windows.ctypes.data), len(windows),
-                                                    int(atom_range[0]), int(atom_range[1]), ctypes.c_void_p(csum.data_ptr()),
-                                                    ctypes.c_void_p(out.data_ptr())))
+        self._check(self._lib.amof_msd_shard_finish(self._h, ctypes.byref(th.c), _ptr(windows), len(windows), int(atom_range[0]),
+                                                    int(atom_range[1]), _ptr(csum), _ptr(out)))
         return out, th.kinds
 
     @_locked
@@ -925,8 +904,17 @@ class Context(Lane):
         """``(msd [F][S+1] f64, kinds)``: column 0 = all atoms, then one per species."""
         th = self._traj(packed)
         out = np.zeros((th.n_frames, th.S + 1), dtype=np.float64)
-        self._check(self._lib.amof_msd_direct(self._h, ctypes.byref(th.c), ctypes.c_void_p(out.ctypes.data)))
+        self._check(self._lib.amof_msd_direct(self._h, ctypes.byref(th.c), _ptr(out)))
         return out, th.kinds
+
+
+def merge_results(results, rules):
+    """One result from those of the shards of a call (the devices of a ``MultiContext``, the batches of a stream): per
+    returned element ``"sum"``, ``"cat"`` (concatenate along axis 0) or ``"first"``; one rule for a bare result."""
+    if isinstance(rules, str):
+        return merge_results([(r,) for r in results], (rules,))[0]
+    how = {"sum": sum, "cat": lambda xs: np.concatenate(xs, axis=0), "first": lambda xs: xs[0]}
+    return tuple(how[rule]([r[i] for r in results]) for i, rule in enumerate(rules))
 
 
 class MultiContext(object):
@@ -970,145 +958,85 @@ class MultiContext(object):
         with ThreadPoolExecutor(len(jobs)) as ex:
             return [f.result() for f in [ex.submit(j) for j in jobs]]
 
+    def _sharded(self, name, packed, span, key, rules, *args, copy_frames=False, per_shard=None, **kwargs):
+        """``ctx.<name>(trajectory, *args, <key>=shard, **kwargs)`` on every context, merged by ``rules`` (``merge_results``).
+        ``span``: the ``(lo, hi)`` that ``_shards`` cuts, or the shards themselves, one per context; ``key``: the keyword
+        that receives a shard (``frame_range``, ``atom_range``, ``work_range``); ``copy_frames``: the shard is a frame range,
+        and a trajectory on another device is copied for those frames only (``_for_device``: the call then gets the range
+        within the copy); ``per_shard(trajectory, a, b)``: further keywords that depend on the shard."""
+        def job(ctx, a, b):
+            tr, fr = self._for_device(packed, ctx, (a, b) if copy_frames else None)
+            extra = per_shard(tr, a, b) if per_shard is not None else {}
+            return getattr(ctx, name)(tr, *args, **dict(kwargs, **{key: fr if copy_frames else (a, b)}), **extra)
+        shards = self._shards(*span) if isinstance(span, tuple) else span
+        return merge_results(self._run([lambda ctx=ctx, a=a, b=b: job(ctx, a, b) for ctx, (a, b) in zip(self.ctxs, shards)]), rules)
+
     def rdf_accumulate(self, packed, rmax, nbins, frame_range=None, out=None):
         assert out is None, "device-resident accumulation is a single-context feature"
-        lo, hi = (0, packed.n_frames) if frame_range is None else frame_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, fr = self._for_device(packed, ctx, (a, b))
-                return ctx.rdf_accumulate(tr, rmax, nbins, frame_range=fr)
-            jobs.append(job)
-        res = self._run(jobs)
-        return sum(r[0] for r in res), float(sum(r[1] for r in res)), res[0][2]
+        hist, vol, kinds = self._sharded("rdf_accumulate", packed, _span(frame_range, packed.n_frames), "frame_range",
+                                         ("sum", "sum", "first"), rmax, nbins, copy_frames=True)
+        return hist, float(vol), kinds
 
     def cn_count(self, packed, cutoff, sets, frame_range=None, per_atom=False):
-        lo, hi = (0, packed.n_frames) if frame_range is None else frame_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, fr = self._for_device(packed, ctx, (a, b))
-                return ctx.cn_count(tr, cutoff, sets, frame_range=fr, per_atom=per_atom)
-            jobs.append(job)
-        res = self._run(jobs)
-        if per_atom:
-            return np.concatenate([r[0] for r in res], axis=0), np.concatenate([r[1] for r in res], axis=0)
-        return np.concatenate(res, axis=0)
+        return self._sharded("cn_count", packed, _span(frame_range, packed.n_frames), "frame_range",
+                             ("cat", "cat") if per_atom else "cat", cutoff, sets, copy_frames=True, per_atom=per_atom)
 
     def bad_hist(self, packed, cutoff, triples, edges, frame_range=None, out=None):
         assert out is None, "device-resident accumulation is a single-context feature"
-        lo, hi = (0, packed.n_frames) if frame_range is None else frame_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, fr = self._for_device(packed, ctx, (a, b))
-                return ctx.bad_hist(tr, cutoff, triples, edges, frame_range=fr)
-            jobs.append(job)
-        res = self._run(jobs)
-        return sum(r[0] for r in res), sum(r[1] for r in res)
+        return self._sharded("bad_hist", packed, _span(frame_range, packed.n_frames), "frame_range", ("sum", "sum"),
+                             cutoff, triples, edges, copy_frames=True)
 
     def bad_hist_by_cn(self, packed, cutoff, triples, edges, cn_max=16, frame_range=None):
-        lo, hi = (0, packed.n_frames) if frame_range is None else frame_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, fr = self._for_device(packed, ctx, (a, b))
-                return ctx.bad_hist_by_cn(tr, cutoff, triples, edges, cn_max=cn_max, frame_range=fr)
-            jobs.append(job)
-        res = self._run(jobs)
-        return sum(r[0] for r in res), sum(r[1] for r in res)
+        return self._sharded("bad_hist_by_cn", packed, _span(frame_range, packed.n_frames), "frame_range", ("sum", "sum"),
+                             cutoff, triples, edges, copy_frames=True, cn_max=cn_max)
 
     def msd_window(self, packed, windows, unwrap=False, remove_com=True, atom_range=None):
-        lo, hi = (0, packed.n_atoms) if atom_range is None else atom_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, _ = self._for_device(packed, ctx)
-                return ctx.msd_window(tr, windows, unwrap=unwrap, remove_com=remove_com, atom_range=(a, b))
-            jobs.append(job)
-        res = self._run(jobs)
-        return sum(r[0] for r in res), res[0][1]
+        return self._sharded("msd_window", packed, _span(atom_range, packed.n_atoms), "atom_range", ("sum", "first"),
+                             windows, unwrap=unwrap, remove_com=remove_com)
 
     def vanhove_window(self, packed, windows, dr, nbins, unwrap=False, remove_com=True, atom_range=None):
         """atoms sharded over the devices; the integer counts add up exactly, the moments up to float64 summation order"""
-        lo, hi = (0, packed.n_atoms) if atom_range is None else atom_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, _ = self._for_device(packed, ctx)
-                return ctx.vanhove_window(tr, windows, dr, nbins, unwrap=unwrap, remove_com=remove_com, atom_range=(a, b))
-            jobs.append(job)
-        res = self._run(jobs)
-        return sum(r[0] for r in res), sum(r[1] for r in res), sum(r[2] for r in res), res[0][3]
+        return self._sharded("vanhove_window", packed, _span(atom_range, packed.n_atoms), "atom_range",
+                             ("sum", "sum", "sum", "first"), windows, dr, nbins, unwrap=unwrap, remove_com=remove_com)
 
     def vanhove_distinct(self, packed, windows, rmax, nbins, origin_stride=1, work_range=None):
         """the (lag, origin) work list sharded over the devices: the integer counts add up exactly"""
-        windows = np.ascontiguousarray(windows, dtype=np.int32)
+        windows = _i32(windows)
         if work_range is None:
             work_range = _whole_work_list(packed.n_frames, windows, origin_stride)
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(*work_range)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, _ = self._for_device(packed, ctx)
-                return ctx.vanhove_distinct(tr, windows, rmax, nbins, origin_stride=origin_stride, work_range=(a, b))
-            jobs.append(job)
-        res = self._run(jobs)
-        return sum(r[0] for r in res), res[0][1]
+        return self._sharded("vanhove_distinct", packed, tuple(work_range), "work_range", ("sum", "first"), windows, rmax, nbins,
+                             origin_stride=origin_stride)
 
     def bond_survival(self, packed, cutoff, sets, windows, origin_stride=1, atom_range=None):
         """the centre atoms sharded over the devices: the integer counters add up exactly"""
-        lo, hi = (0, packed.n_atoms) if atom_range is None else atom_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, _ = self._for_device(packed, ctx)
-                return ctx.bond_survival(tr, cutoff, sets, windows, origin_stride=origin_stride, atom_range=(a, b))
-            jobs.append(job)
-        return sum(self._run(jobs))
+        return self._sharded("bond_survival", packed, _span(atom_range, packed.n_atoms), "atom_range", "sum", cutoff, sets,
+                             windows, origin_stride=origin_stride)
 
     def bond_reorientation(self, packed, cutoff, sets, windows, origin_stride=1, atom_range=None):
         """the centre atoms sharded over the devices: the integer sums add up exactly; the scale is the same on all"""
-        lo, hi = (0, packed.n_atoms) if atom_range is None else atom_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, _ = self._for_device(packed, ctx)
-                return ctx.bond_reorientation(tr, cutoff, sets, windows, origin_stride=origin_stride, atom_range=(a, b))
-            jobs.append(job)
-        res = self._run(jobs)
-        return sum(r[0] for r in res), res[0][1]
+        return self._sharded("bond_reorientation", packed, _span(atom_range, packed.n_atoms), "atom_range", ("sum", "first"),
+                             cutoff, sets, windows, origin_stride=origin_stride)
 
     def bond_order(self, packed, cutoff, sets, l, nbins, nbins_tet, frame_range=None, per_atom=False, out=None):
         """frames sharded over the devices as ``cn_count``'s: the rows concatenate, the histograms add up exactly"""
         assert out is None, "device-resident accumulation is a single-context feature"
-        lo, hi = (0, packed.n_frames) if frame_range is None else frame_range
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(lo, hi)):
-            def job(ctx=ctx, a=a, b=b):
-                tr, fr = self._for_device(packed, ctx, (a, b))
-                return ctx.bond_order(tr, cutoff, sets, l, nbins, nbins_tet, frame_range=fr, per_atom=per_atom)
-            jobs.append(job)
-        res = self._run(jobs)
-        merged = (sum(r[0] for r in res), sum(r[1] for r in res), np.concatenate([r[2] for r in res], axis=0))
-        return merged + (np.concatenate([r[3] for r in res], axis=0),) if per_atom else merged
+        return self._sharded("bond_order", packed, _span(frame_range, packed.n_frames), "frame_range",
+                             ("sum", "sum", "cat", "cat")[:3 + bool(per_atom)], cutoff, sets, l, nbins, nbins_tet,
+                             copy_frames=True, per_atom=per_atom)
 
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None):
         """frames sharded over the devices (whole strides per device; a device trajectory on another GPU is copied for the
         shard's frames only): counts add up exactly, the sums to float64 order"""
-        lo, hi = (0, packed.n_frames) if frame_range is None else frame_range
+        lo, hi = _span(frame_range, packed.n_frames)
         stride = int(frame_stride)
         n_sel = max(0, (hi - lo + stride - 1) // stride)
         recip = reciprocal(packed.cell) if recip is None else np.asarray(recip, dtype=np.float64)
-        jobs = []
-        for ctx, (a, b) in zip(self.ctxs, self._shards(0, n_sel)):
-            def job(ctx=ctx, a=a, b=b):
-                f0, f1 = lo + a * stride, min(hi, lo + b * stride)
-                tr, fr = self._for_device(packed, ctx, (f0, max(f0, f1)))
-                rc = recip if tr.cell.shape[0] == recip.shape[0] else recip[f0:max(f0, f1)]
-                return ctx.sq_accumulate(tr, hkl, dq, nbins, frame_range=fr, frame_stride=stride, recip=rc)
-            jobs.append(job)
-        res = self._run(jobs)
-        return sum(r[0] for r in res), sum(r[1] for r in res), sum(r[2] for r in res), res[0][3]
+        shards = [(lo + a * stride, max(lo + a * stride, min(hi, lo + b * stride))) for a, b in self._shards(0, n_sel)]
+
+        def shard_recip(tr, f0, f1):
+            return {"recip": recip if tr.cell.shape[0] == recip.shape[0] else recip[f0:f1]}
+        return self._sharded("sq_accumulate", packed, shards, "frame_range", ("sum", "sum", "sum", "first"), hkl, dq, nbins,
+                             copy_frames=True, per_shard=shard_recip, frame_stride=stride)
 
     def msd_direct(self, packed):
         return self.ctxs[0].msd_direct(self._for_device(packed, self.ctxs[0])[0])

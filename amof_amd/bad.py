@@ -21,17 +21,49 @@ import pandas as pd
 from ._lazy import Deferred, EmptyUntilComputed
 
 from . import _hip
+from . import _setup
 from . import atom as amatom
 from . import data as _data
 from . import dist as _dist
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
 
 logger = logging.getLogger(__name__)
 
 
 def _symbol(c):
     return "X" if isinstance(c, str) else _data.chemical_symbols[c]
+
+
+def _plan(packed, nb_set_and_cutoff, dtheta):
+    """``(cutoff matrix, names, triples, theta_bins, theta)`` of ``Bad`` and ``BadByCn``: the B-A-B columns of the elements
+    named in the dictionary (reference amof/bad.py:122-145) and their (centre, neighbour) species indices, -1 = any"""
+    elements_present_unique = list(set([_data.atomic_numbers[i] for nb_set in nb_set_and_cutoff.keys()
+                                        for i in nb_set.split('-')]))
+    if len(elements_present_unique) == len(packed.unique_numbers()):
+        elements_present_unique.append("X")
+    elements = [(a, b) for b in elements_present_unique for a in elements_present_unique
+                if (a not in [b, "X"] or ((a, b) == ("X", "X")))]
+
+    logger.info("Start computing bad for %s frames with dtheta = %s", len(packed), dtheta)
+    bins = int(180 // dtheta)       # Python float floor-division (amof/bad.py:142)
+    theta_bins = np.arange(bins + 2) * dtheta
+    theta = np.arange(bins + 1) * dtheta + dtheta / 2
+
+    kinds, _ = _hip.packed_species(packed)
+    lut = {z: k for k, z in enumerate(kinds)}
+    rcm = amatom.cutoff_matrix(amatom.format_cutoff(nb_set_and_cutoff), kinds)
+
+    def sidx(c):
+        return -1 if isinstance(c, str) else lut.get(c, None)
+
+    names, triples = [], []
+    for A, B in elements:
+        ia, ib = sidx(A), sidx(B)
+        if ia is None or ib is None:
+            continue                # species absent from the trajectory: no angle, column omitted
+        names.append("-".join([_symbol(C) for C in [B, A, B]]))
+        triples.append((ia, ib))
+    return rcm, names, triples, theta_bins, theta
 
 
 class CoreBad(object):
@@ -82,45 +114,16 @@ class Bad(CoreBad, Deferred):
     def compute_bad(self, trajectory, nb_set_and_cutoff, dtheta, normalization='total', parallel=False,
                     device=None, distributed=None):
         """compute bond-angle distributions (reference amof/bad.py:116-160)"""
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
-        atomic_numbers_unique = packed.unique_numbers()
-
-        cutoff_dict = amatom.format_cutoff(nb_set_and_cutoff)
-        elements_present_unique = list(set([_data.atomic_numbers[i] for nb_set in nb_set_and_cutoff.keys()
-                                            for i in nb_set.split('-')]))
-        if len(elements_present_unique) == len(atomic_numbers_unique):
-            elements_present_unique.append("X")
-        elements = [(a, b) for b in elements_present_unique for a in elements_present_unique
-                    if (a not in [b, "X"] or ((a, b) == ("X", "X")))]
-
-        logger.info("Start computing bad for %s frames with dtheta = %s", len(packed), dtheta)
-        bins = int(180 // dtheta)       # Python float floor-division (amof/bad.py:142)
-        theta_bins = np.arange(bins + 2) * dtheta
-        theta = np.arange(bins + 1) * dtheta + dtheta / 2
-
-        kinds, _ = _hip.packed_species(packed)
-        lut = {z: k for k, z in enumerate(kinds)}
-        rcm = amatom.cutoff_matrix(cutoff_dict, kinds)
-
-        def sidx(c):
-            return -1 if isinstance(c, str) else lut.get(c, None)
-
-        names, triples = [], []
-        for A, B in elements:
-            aba_str = "-".join([_symbol(C) for C in [B, A, B]])
-            ia, ib = sidx(A), sidx(B)
-            if ia is None or ib is None:
-                continue                # species absent from the trajectory: no angle, column omitted
-            names.append(aba_str)
-            triples.append((ia, ib))
-
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        F = len(packed)
-        frame_range = _dist.shard_range(F, rank, world) if (merge and distributed != 'local') else (0, F)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 1)
+        packed = _setup.pack(trajectory, device, keep_stream=True)
+        rcm, names, triples, theta_bins, theta = _plan(packed, nb_set_and_cutoff, dtheta)
+        st = _setup.setup(packed, device, distributed, lane=1, keep_stream=True, honour_local=True)
+        ctx, merge, source = st.ctx, st.merge, st.source
+        frame_range = st.shard(len(packed))
         db = np.array(np.diff(theta_bins), float)
+        T, nb = len(triples), len(theta)
+
+        def empty():
+            return np.zeros((T, nb), dtype=np.uint64), np.zeros(T, dtype=np.uint64)
 
         def assemble(hist, nang):
             self.hist = hist
@@ -133,23 +136,15 @@ class Bad(CoreBad, Deferred):
                     cols[aba_str] = n / db / n.sum()      # numpy.histogram(density=True)
             self.data = pd.DataFrame(cols)
 
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
-        if getattr(source, "is_stream", False):
-            if merge:
-                raise ValueError("a streamed trajectory is analysed by one process (distributed=False)")
-
+        if _setup.streamed(st):
             def walk():
-                hist, nang = np.zeros((len(triples), bins + 1), dtype=np.uint64), np.zeros(len(triples), dtype=np.uint64)
-                for batch in source.batches():
-                    if triples:
-                        h, a = ctx.bad_hist(batch, rcm, triples, theta_bins)
-                        hist, nang = hist + h, nang + a
-                return hist, nang
+                if not triples:
+                    return empty()
+                return _setup.walk(source, lambda batch: ctx.bad_hist(batch, rcm, triples, theta_bins), ("sum", "sum"))
 
             self._defer(ctx, walk, lambda raw: assemble(raw[0], raw[1]))
             return
         on_device = bool(triples) and merge and _dist.device_collectives()
-        T, nb = len(triples), bins + 1
 
         def local():
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
@@ -161,7 +156,7 @@ class Bad(CoreBad, Deferred):
                 return both, None
             if triples:
                 return ctx.bad_hist(packed, rcm, triples, theta_bins, frame_range=frame_range)
-            return np.zeros((0, bins + 1), dtype=np.uint64), np.zeros(0, dtype=np.uint64)
+            return empty()
 
         def finish(raw):
             hist, nang = raw
@@ -227,38 +222,12 @@ class BadByCn(CoreBad):
     def compute_bad(self, trajectory, nb_set_and_cutoff, dtheta, normalisation='total', parallel=False,
                     device=None, distributed=None):
         """compute bond-angle distributions by cn (reference amof/bad.py:240-301)"""
-        packed = pack_trajectory(trajectory)
-        if getattr(packed, "is_stream", False):
-            packed = packed.read_all()      # (this analysis does not add up batch by batch)
-        atomic_numbers_unique = packed.unique_numbers()
-        cutoff_dict = amatom.format_cutoff(nb_set_and_cutoff)
-        elements_present_unique = list(set([_data.atomic_numbers[i] for nb_set in nb_set_and_cutoff.keys()
-                                            for i in nb_set.split('-')]))
-        if len(elements_present_unique) == len(atomic_numbers_unique):
-            elements_present_unique.append("X")
-        elements = [(a, b) for b in elements_present_unique for a in elements_present_unique
-                    if (a not in [b, "X"] or ((a, b) == ("X", "X")))]
-        logger.info("Start computing bad for %s frames with dtheta = %s", len(packed), dtheta)
-        bins = int(180 // dtheta)
-        theta_bins = np.arange(bins + 2) * dtheta
-        theta = np.arange(bins + 1) * dtheta + dtheta / 2
-        kinds, _ = _hip.packed_species(packed)
-        lut = {z: k for k, z in enumerate(kinds)}
-        rcm = amatom.cutoff_matrix(cutoff_dict, kinds)
-        names, triples = [], []
-        for A, B in elements:
-            ia = -1 if isinstance(A, str) else lut.get(A, None)
-            ib = -1 if isinstance(B, str) else lut.get(B, None)
-            if ia is None or ib is None:
-                continue
-            names.append("-".join([_symbol(C) for C in [B, A, B]]))
-            triples.append((ia, ib))
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        F = len(packed)
-        frame_range = _dist.shard_range(F, rank, world) if (merge and distributed != 'local') else (0, F)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.get_context(dev)
+        packed = _setup.pack(trajectory, device, upload=False)      # (read whole: this analysis does not add up batch by batch)
+        rcm, names, triples, theta_bins, theta = _plan(packed, nb_set_and_cutoff, dtheta)
+        st = _setup.setup(packed, device, distributed, lane=None, honour_local=True)
+        ctx, merge = st.ctx, st.merge
+        frame_range = st.shard(len(packed))
+        bins = len(theta) - 1
         # the last slot (cn_max) also collects every larger neighbour count -- the reference has no limit on the
         # coordination number (amof/bad.py:190-224).  When it is populated the slots are sized ONCE from a count pass (the
         # CN kernels' per-atom output: the largest number of neighbours any centre has in any frame) and the histogram is

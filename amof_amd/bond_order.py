@@ -20,13 +20,10 @@ import pandas as pd
 
 from ._lazy import Deferred, EmptyUntilComputed
 
-from . import _hip
-from . import atom as amatom
-from . import data as _data
+from . import _setup
 from . import dist as _dist
 from . import trajectory as _trajectory
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
 
 logger = logging.getLogger(__name__)
 
@@ -147,29 +144,17 @@ class BondOrder(Deferred):
         if not 1 <= len(l) <= 4 or any(not 1 <= x <= 12 for x in l):
             raise ValueError("l: one to four degrees, each in 1 .. 12")
         nbins, nbins_tet = int(nbins), int(nbins_tet)
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
+        packed = _setup.pack(trajectory, device, keep_stream=True)
         logger.info("Start computing bond order parameters for %s frames", len(packed))
-        kinds, _ = _hip.packed_species(packed)
-        lut = {z: k for k, z in enumerate(kinds)}
-        rcm = amatom.cutoff_matrix(amatom.format_cutoff(nb_set_and_cutoff), kinds)
-        counts = packed.species_counts()
-        names, live, centres = [], [], []
-        for nb_set in nb_set_and_cutoff.keys():
-            a, b = tuple(_data.atomic_numbers[i] for i in nb_set.split('-'))
-            ok = a in lut and b in lut
-            names.append((nb_set, int(counts.get(a, 0)), ok))
-            centres.append(a)
-            if ok:
-                live.append((lut[a], lut[b]))
+        ns = _setup.neighbour_sets(packed, nb_set_and_cutoff)
+        rcm, live, centres = ns.cutoff, ns.live, ns.centres
+        names = list(zip(ns.names, ns.n_centres, ns.present))
         n_l, cols = len(l), 4 + len(l) + 1
 
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
+        st = _setup.setup(packed, device, distributed, lane=1, keep_stream=True, honour_local=True)
+        ctx, source, sharded = st.ctx, st.source, st.sharded
         F, N = len(packed), packed.n_atoms
-        sharded = merge and distributed != 'local'
-        frame_range = _dist.shard_range(F, rank, world) if sharded else (0, F)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 1)
+        frame_range = st.shard(F)
         numbers = np.asarray(packed.numbers)
 
         def empty(nf):
@@ -181,27 +166,13 @@ class BondOrder(Deferred):
             self._assemble(np.asarray(hist).view(np.uint64), np.asarray(hist_tet).view(np.uint64), sums, pa, names, centres, numbers,
                            l, step)
 
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
-        if getattr(source, "is_stream", False):
-            if merge:
-                raise ValueError("a streamed trajectory is analysed by one process (distributed=False)")
-
+        if _setup.streamed(st):
             def walk():
                 if not live:
                     return empty(F)
-                hist = np.zeros((len(live), n_l, nbins), dtype=np.uint64)
-                hist_tet = np.zeros((len(live), nbins_tet), dtype=np.uint64)
-                rows, atoms = [], []
-                for batch in source.batches():
-                    res = ctx.bond_order(batch, rcm, live, l, nbins, nbins_tet, per_atom=per_atom)
-                    hist += res[0]
-                    hist_tet += res[1]
-                    rows.append(res[2])
-                    if per_atom:
-                        atoms.append(res[3])
-                sums = np.concatenate(rows, axis=0) if rows else np.zeros((0, len(live), cols), dtype=np.int64)
-                pa = (np.concatenate(atoms, axis=0) if atoms else empty(0)[3]) if per_atom else None
-                return hist, hist_tet, sums, pa
+                res = _setup.walk(source, lambda batch: ctx.bond_order(batch, rcm, live, l, nbins, nbins_tet, per_atom=per_atom),
+                                  ("sum", "sum", "cat", "cat")[:3 + bool(per_atom)])
+                return res if per_atom else res + (None,)
 
             self._defer(ctx, walk, finish_host)
             return

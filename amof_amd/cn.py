@@ -13,13 +13,10 @@ import pandas as pd
 
 from ._lazy import Deferred, EmptyUntilComputed
 
-from . import _hip
-from . import atom as amatom
-from . import data as _data
+from . import _setup
 from . import dist as _dist
 from . import trajectory as _trajectory
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
 
 logger = logging.getLogger(__name__)
 
@@ -57,36 +54,19 @@ class CoordinationNumber(Deferred):
 
     def compute_cn(self, trajectory, nb_set_and_cutoff, step, parallel=False, device=None, distributed=None):
         """compute coordination numbers (reference amof/cn.py:48-82)"""
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
+        packed = _setup.pack(trajectory, device, keep_stream=True)
         logger.info("Start computing coordination number for %s frames", len(packed))
-        cutoff_dict = amatom.format_cutoff(nb_set_and_cutoff)
-        kinds, _ = _hip.packed_species(packed)
-        lut = {z: k for k, z in enumerate(kinds)}
-        rcm = amatom.cutoff_matrix(cutoff_dict, kinds)
-        names, sets, present = [], [], []
-        for nb_set in nb_set_and_cutoff.keys():
-            a, b = tuple(_data.atomic_numbers[i] for i in nb_set.split('-'))
-            names.append(nb_set)
-            ok = a in lut and b in lut
-            present.append(a in lut)
-            sets.append((lut[a], lut[b]) if ok else None)
-        live = [s for s in sets if s is not None]
-
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        F = len(packed)
-        frame_range = _dist.shard_range(F, rank, world) if (merge and distributed != 'local') else (0, F)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 1)
-        counts = packed.species_counts()
+        ns = _setup.neighbour_sets(packed, nb_set_and_cutoff)
+        rcm, live = ns.cutoff, ns.live
+        st = _setup.setup(packed, device, distributed, lane=1, keep_stream=True, honour_local=True)
+        ctx, source = st.ctx, st.source
+        frame_range = st.shard(len(packed))
 
         def assemble(sums):
             data = {'Step': np.asarray(step)[:len(sums)] if distributed == 'local' else step}
             k = 0
-            for name, s, has_a in zip(names, sets, present):
-                a = _data.atomic_numbers[name.split('-')[0]]
-                n_a = counts.get(a, 0)
-                if s is not None:
+            for name, ok, has_a, n_a in zip(ns.names, ns.present, ns.has_centre, ns.n_centres):
+                if ok:
                     col = sums[:, k].astype(np.float64) / n_a   # np.mean of integer counts (amof/cn.py:73)
                     k += 1
                 elif has_a:
@@ -96,32 +76,22 @@ class CoordinationNumber(Deferred):
                 data[name] = col
             self.data = pd.DataFrame(data)
 
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
-        if getattr(source, "is_stream", False):
-            if merge:
-                raise ValueError("a streamed trajectory is analysed by one process (distributed=False)")
-
-            def walk():
-                rows = [ctx.cn_count(batch, rcm, live) if live else np.zeros((len(batch), 0), dtype=np.int64)
-                        for batch in source.batches()]
-                return np.concatenate(rows, axis=0) if rows else np.zeros((0, len(live)), dtype=np.int64)
-
-            self._defer(ctx, walk, assemble)
-            return
-        sharded = merge and distributed != 'local'
-
-        def local():
-            # this rank's kernels (a lane job: amof_amd/_lazy.py)
+        def count(part, frame_range=None):
             if live:
-                return ctx.cn_count(packed, rcm, live, frame_range=frame_range)
-            return np.zeros((frame_range[1] - frame_range[0], 0), dtype=np.int64)
+                return ctx.cn_count(part, rcm, live, frame_range=frame_range)
+            return np.zeros((len(part) if frame_range is None else frame_range[1] - frame_range[0], 0), dtype=np.int64)
+
+        if _setup.streamed(st):
+            self._defer(ctx, lambda: _setup.walk(source, count, "cat"), assemble)
+            return
 
         def finish(sums):
-            if sharded:
+            if st.sharded:
                 sums = _dist.all_gather_rows(sums, device=ctx.device)
             assemble(sums)
 
-        self._defer(ctx, local, finish, collective=sharded)
+        # (local: this rank's kernels, a lane job -- amof_amd/_lazy.py)
+        self._defer(ctx, lambda: count(packed, frame_range), finish, collective=st.sharded)
 
     @classmethod
     def from_file(cls, filename):

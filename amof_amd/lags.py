@@ -7,16 +7,11 @@ contiguous index ranges of it.  The library states the same rule once, in amof_a
 lag/origin family: shared pieces"); tests/test_lag_work_cpu.py holds the two against each other.
 """
 
-import collections
 import logging
 
 import numpy as np
 
-from . import _hip
-from . import atom as amatom
-from . import data as _data
-from . import dist as _dist
-from .frames import pack_trajectory, resident_source
+from . import _setup
 
 logger = logging.getLogger(__name__)
 
@@ -63,36 +58,8 @@ def work_list(n_frames, windows, origin_stride=1):
     return (np.concatenate(w) if w else np.zeros(0, np.int64)), (np.concatenate(k) if k else np.zeros(0, np.int64))
 
 
-Setup = collections.namedtuple("Setup", "packed rank world merge ctx on_device source")
-
-
-def pack(trajectory, device):
-    """the packed trajectory, a stream fully read (a lag couples frames half a trajectory apart: nothing to stream)"""
-    packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
-    if getattr(packed, "is_stream", False):
-        packed = packed.read_all()
-    return packed
-
-
-def setup(trajectory, device, distributed, lane=0):
-    """What every class of the family decides before it shards its work: the packed trajectory (``pack``; one packed
-    already -- a class that has checked its arguments against it, which needs no GPU -- passes through), this process's
-    rank and world, whether the ranks merge, the lane's context (created here), whether the merge stays in HBM, and
-    the source ``begin_local`` makes resident."""
-    packed = pack(trajectory, device)
-    rank, world = (0, 1) if distributed is False else _dist.world()
-    merge = distributed is not False and _dist.merging(world)
-    dev = device if device is not None else getattr(packed, "device_index", None)
-    ctx = _hip.lane_context(dev, lane)
-    on_device = merge and _dist.device_collectives()
-    source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
-    return Setup(packed, rank, world, merge, ctx, on_device, source)
-
-
-def begin_local(source):
-    """first thing of a ``local()`` (the lane job of amof_amd/_lazy.py): the frames are there before the kernels start"""
-    if getattr(source, "is_stream", False):
-        source.read_all()
+# (what every class decides before it shards its work is stated once, in _setup.py; the family finds it here)
+Setup, pack, setup, begin_local = _setup.Setup, _setup.pack, _setup.setup, _setup.begin_local
 
 
 def min_periodic_height(cells, pbc):
@@ -114,16 +81,8 @@ def neighbour_sets(packed, nb_set_and_cutoff):
     ``(cutoff matrix [S][S], names, live)`` -- names = [(set name, both species present)] in dictionary order, live = the
     (centre, neighbour) species indices of the present ones.  ValueError for a cutoff above half the smallest
     perpendicular cell height on a periodic axis (a pair could be bonded through two images)."""
-    kinds, _ = _hip.packed_species(packed)
-    lut = {z: k for k, z in enumerate(kinds)}
-    rcm = amatom.cutoff_matrix(amatom.format_cutoff(nb_set_and_cutoff), kinds)
-    names, live = [], []
-    for nb_set in nb_set_and_cutoff.keys():
-        a, b = tuple(_data.atomic_numbers[i] for i in nb_set.split('-'))
-        ok = a in lut and b in lut
-        names.append((nb_set, ok))
-        if ok:
-            live.append((lut[a], lut[b]))
+    ns = _setup.neighbour_sets(packed, nb_set_and_cutoff)
+    rcm, names, live = ns.cutoff, list(zip(ns.names, ns.present)), ns.live
     half = 0.5 * min_periodic_height(packed.cell, packed.pbc)
     for a, b in live:
         if rcm[a, b] > half:

@@ -19,10 +19,11 @@ import pandas as pd
 from ._lazy import Deferred, EmptyUntilComputed
 
 from . import _hip
+from . import _setup
 from . import data as _data
 from . import dist as _dist
 from .files import path as _path
-from .frames import pack_trajectory, resident_source, PackedTrajectory
+from .frames import pack_trajectory, PackedTrajectory
 
 logger = logging.getLogger(__name__)
 
@@ -183,21 +184,18 @@ class WindowMsd(Msd, Deferred):
 
     def compute_msd(self, trajectory, window, time, parallel=False, unwrap=False, device=None, distributed=None):
         """compute the window MSD (reference amof/msd.py:207-268)"""
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
-        if getattr(packed, "is_stream", False):
-            packed = packed.read_all()      # a window couples frames half a trajectory apart: nothing to stream
+        packed = _setup.pack(trajectory, device)      # (read whole: a window couples frames half a trajectory apart)
         elements = packed.unique_numbers()
         if unwrap == True:  # noqa: E712  (the reference compares with ==)
             logger.info("Unwrap trajectory before computing msd")
         logger.info("Start computing msd at %s times on a trajectory of %s frames", len(window), len(packed))
 
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        N, F = packed.n_atoms, len(packed)
-        atom_range = _dist.shard_range(N, rank, world) if merge and distributed != 'local' else (0, N)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 1)
-        sharded = merge and distributed != 'local'
+        # (a host trajectory's one device copy, started by whichever analysis came first, must be complete: that wait is part
+        #  of the lane job -- begin_local)
+        st = _setup.setup(packed, device, distributed, lane=1, honour_local=True)
+        rank, world, ctx, source, sharded = st.rank, st.world, st.ctx, st.source, st.sharded
+        F = len(packed)
+        atom_range = st.shard(packed.n_atoms)
         on_device = sharded and _dist.device_collectives()
         com = csum = None
         if on_device and unwrap != True and packed.on_device:  # noqa: E712  (the unwrapped centre of mass is another quantity)
@@ -220,14 +218,9 @@ class WindowMsd(Msd, Deferred):
                 ctx.msd_com(packed, _dist.shard_range(F, rank, world), com)
                 _dist.all_reduce_sum(com)
 
-        # (a host trajectory: its one device copy -- started by whichever analysis came first -- must be complete: the wait is
-        #  part of the lane job)
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
-
         def local():
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
-            if getattr(source, "is_stream", False):
-                source.read_all()
+            _setup.begin_local(source)
             if on_device:
                 # the S x W sums stay in HBM from the kernels through their all-reduce
                 import torch

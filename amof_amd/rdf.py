@@ -18,10 +18,11 @@ import pandas as pd
 from ._lazy import Deferred, EmptyUntilComputed
 
 from . import _hip
+from . import _setup
 from . import data as _data
 from . import dist as _dist
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
+from .frames import pack_trajectory
 
 logger = logging.getLogger(__name__)
 
@@ -121,15 +122,10 @@ class Rdf(Deferred):
 
     def compute_rdf(self, trajectory, dr, rmax, device=None, distributed=None):
         """compute rdf from a trajectory (reference amof/rdf.py:67-114)"""
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
+        packed = _setup.pack(trajectory, device, keep_stream=True)
         atomic_numbers_unique = packed.unique_numbers()
-        N_species = len(atomic_numbers_unique)
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 0)
-        # a host trajectory gets ONE device copy, uploaded while its first analyses walk the part that has arrived
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
+        st = _setup.setup(packed, device, distributed, lane=0, keep_stream=True, honour_local=True)
+        merge, ctx, source, sharded = st.merge, st.ctx, st.source, st.sharded
 
         # min over ALL frames of the three cell lengths, halved (amof/rdf.py:74)
         rmax_half_cell = np.min(packed.cell_lengths()) / 2
@@ -150,18 +146,11 @@ class Rdf(Deferred):
             raise ValueError("rmax // dr gives no bin")
 
         F_local = len(packed)
-        if getattr(source, "is_stream", False):
-            # frames are independent: the integer counts of the batches add up (a file stream parses its next batch in a
-            # background thread, a host trajectory's next frames are on their way over PCIe, while this one is on the GPU)
-            if merge:
-                raise ValueError("a streamed trajectory is analysed by one process (distributed=False)")
-
+        if _setup.streamed(st):
+            # frames are independent: the integer counts of the batches add up
             def walk():
-                hist, vol_sum, kinds = None, 0.0, None
-                for batch in source.batches():
-                    h, v, kinds = ctx.rdf_accumulate(batch, rmax, bins)
-                    hist = h if hist is None else hist + h
-                    vol_sum += v
+                hist, vol_sum, kinds = _setup.walk(source, lambda batch: ctx.rdf_accumulate(batch, rmax, bins),
+                                                   ("sum", "sum", "first"))
                 if source.cell is not None:
                     vol_sum = source.volume_sum()      # (the library's own left-to-right sum: identical to the unstreamed result)
                 return hist, vol_sum, kinds
@@ -169,11 +158,7 @@ class Rdf(Deferred):
             self._defer(ctx, walk, lambda raw: self._finish(packed, raw[0], raw[1], F_local, raw[2], atomic_numbers_unique,
                                                             rmax, bins, r))
             return
-        if merge and distributed != 'local':
-            frame_range = _dist.shard_range(F_local, rank, world)
-        else:
-            frame_range = (0, F_local)
-        sharded = merge and distributed != 'local'
+        frame_range = st.shard(F_local)
         on_device = merge and _dist.device_collectives()
 
         def local():

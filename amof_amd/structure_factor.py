@@ -15,10 +15,11 @@ import pandas as pd
 from ._lazy import Deferred, EmptyUntilComputed
 
 from . import _hip
+from . import _setup
 from . import data as _data
 from . import dist as _dist
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
+from .frames import pack_trajectory
 
 logger = logging.getLogger(__name__)
 
@@ -226,9 +227,7 @@ class StructureFactor(Deferred):
         nbins = n_bins(qmax, dq)
         if nbins < 1:
             raise ValueError("qmax // dq gives no bin")
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
-        if getattr(packed, "is_stream", False):
-            packed = packed.read_all()      # (not walked batch by batch)
+        packed = _setup.pack(trajectory, device)      # (read whole: not walked batch by batch)
         if not all(bool(x) for x in packed.pbc):
             raise ValueError("S(q) needs a cell periodic on all three axes")
         F = len(packed)
@@ -241,21 +240,18 @@ class StructureFactor(Deferred):
         elements = packed.unique_numbers()
         logger.info("Start computing S(q) for %s frames, %s vectors, %s bins", len(frames), len(hkl), nbins)
 
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        a, b = _dist.shard_range(len(frames), rank, world) if merge else (0, len(frames))
+        # (the selected frames are sharded whenever the ranks merge: 'local' has no meaning of its own here)
+        st = _setup.setup(packed, device, distributed, lane=0, honour_local=False)
+        ctx, merge, source = st.ctx, st.merge, st.source
+        a, b = st.shard(len(frames))
         frame_range = (f0 + a * stride, min(f1, f0 + b * stride)) if b > a else (f0, f0)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 0)
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
         S = len(_hip.packed_species(packed)[0])
         P = S * (S + 1) // 2
         on_device = merge and _dist.device_collectives()
 
         def local():
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
-            if getattr(source, "is_stream", False):
-                source.read_all()
+            _setup.begin_local(source)
             try:
                 if merge:
                     # integer fixed-point sums: the ranks' shares add up exactly, whatever the sharding.  Counts, beyond

@@ -15,10 +15,10 @@ import pandas as pd
 from ._lazy import Deferred, EmptyUntilComputed
 
 from . import _hip
+from . import _setup
 from . import data as _data
 from . import dist as _dist
 from .files import path as _path
-from .frames import pack_trajectory, resident_source
 from .lags import window_setup      # (defined there for the whole family; callers also find it here)
 
 logger = logging.getLogger(__name__)
@@ -109,9 +109,7 @@ class WindowVanHove(Deferred):
         return vh
 
     def compute_vanhove(self, trajectory, window, time, dr=0.01, rmax="half_cell", unwrap=False, device=None, distributed=None):
-        packed = pack_trajectory(trajectory, device=device if device is not None else _hip.default_device())
-        if getattr(packed, "is_stream", False):
-            packed = packed.read_all()      # a window couples frames half a trajectory apart: nothing to stream
+        packed = _setup.pack(trajectory, device)      # (read whole: a window couples frames half a trajectory apart)
         if isinstance(rmax, str):
             if rmax != "half_cell":
                 raise ValueError("rmax: 'half_cell' or a number")
@@ -125,13 +123,10 @@ class WindowVanHove(Deferred):
         logger.info("Start computing the self Van Hove function at %s times, %s bins, on a trajectory of %s frames",
                     len(window), nbins, len(packed))
 
-        rank, world = (0, 1) if distributed is False else _dist.world()
-        merge = distributed is not False and _dist.merging(world)
-        N, F = packed.n_atoms, len(packed)
-        sharded = merge and distributed != 'local'
-        atom_range = _dist.shard_range(N, rank, world) if sharded else (0, N)
-        dev = device if device is not None else getattr(packed, "device_index", None)
-        ctx = _hip.lane_context(dev, 1)
+        st = _setup.setup(packed, device, distributed, lane=1, honour_local=True)
+        rank, world, ctx, source, sharded = st.rank, st.world, st.ctx, st.source, st.sharded
+        F = len(packed)
+        atom_range = st.shard(packed.n_atoms)
         on_device = sharded and _dist.device_collectives()
         com = None
         if on_device and not unwrap and packed.on_device:
@@ -148,14 +143,12 @@ class WindowVanHove(Deferred):
                 ctx.msd_com(packed, frames, com)
             _dist.all_reduce_sum(com)
 
-        source = resident_source(packed, ctx.device, allow=not merge and hasattr(ctx, "submit"))
         S = len(_hip.packed_species(packed)[0])
         W = len(window)
 
         def local():
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
-            if getattr(source, "is_stream", False):
-                source.read_all()
+            _setup.begin_local(source)
             if on_device:
                 # counts and overflow in ONE int64 tensor, the moments in another: two all-reduces, results stay in HBM
                 import torch
