@@ -1576,8 +1576,10 @@ __global__ __launch_bounds__(CELL_THREADS, 8) void rdf_cell_kernel(RdfCellArgs c
         const float wx = 4294967296.f / (float)nx, wy = 4294967296.f / (float)ny, wz = 4294967296.f / (float)nz;
         const float ex = wx * 1e-5f + 1024.f, ey = wy * 1e-5f + 1024.f, ez = wz * 1e-5f + 1024.f;
         const float Rq = nb_hi * 1.0001f + 2.f;
-        const float s_xx = sc[0], s_yx = ORTHO ? 0.f : sc[3], s_yy = ORTHO ? sc[1] : sc[4], s_zx = ORTHO ? 0.f : sc[6],
-                    s_zy = ORTHO ? 0.f : sc[7], s_zz = ORTHO ? sc[2] : sc[8];
+        // (a diagonal cell's scales carry the signs of its entries; the bounds below take lengths: the metric's factor has
+        //  a positive diagonal, a diagonal cell |entry|)
+        const float s_xx = ORTHO ? fabsf(sc[0]) : sc[0], s_yx = ORTHO ? 0.f : sc[3], s_yy = ORTHO ? fabsf(sc[1]) : sc[4],
+                    s_zx = ORTHO ? 0.f : sc[6], s_zy = ORTHO ? 0.f : sc[7], s_zz = ORTHO ? fabsf(sc[2]) : sc[8];
 #pragma unroll 1
         for (int row = 0; row < 13; row++) {
             // rows of the positive half shell
@@ -1755,8 +1757,9 @@ __global__ __launch_bounds__(CW_THREADS, CW_MIN_WAVES) void rdf_cellwave_kernel(
             const float wx = 4294967296.f / (float)nx, wy = 4294967296.f / (float)ny, wz = 4294967296.f / (float)nz;
             const float ex = wx * 2e-5f + 2048.f, ey = wy * 2e-5f + 2048.f, ez = wz * 2e-5f + 2048.f;
             const float Rq = nb_hi * 1.0001f + 2.f;
-            const float s_xx = sc[0], s_yx = ORTHO ? 0.f : sc[3], s_yy = ORTHO ? sc[1] : sc[4], s_zx = ORTHO ? 0.f : sc[6],
-                        s_zy = ORTHO ? 0.f : sc[7], s_zz = ORTHO ? sc[2] : sc[8];
+            // (lengths, as in rdf_cell_kernel: a diagonal cell's scales carry the signs of its entries)
+            const float s_xx = ORTHO ? fabsf(sc[0]) : sc[0], s_yx = ORTHO ? 0.f : sc[3], s_yy = ORTHO ? fabsf(sc[1]) : sc[4],
+                        s_zx = ORTHO ? 0.f : sc[6], s_zy = ORTHO ? 0.f : sc[7], s_zz = ORTHO ? fabsf(sc[2]) : sc[8];
             // differences partner - centre in grid units: the partner anywhere in its cell, the centre anywhere in mine
             const float zl = (float)(rdz - 1) * wz - ez, zh = (float)(rdz + 1) * wz + ez;
             const float yl = (float)(rdy - 1) * wy - ey, yh = (float)(rdy + 1) * wy + ey;

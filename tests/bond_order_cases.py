@@ -8,6 +8,7 @@ import numpy as np
 
 from amof_amd.frames import PackedTrajectory
 from tests import bond_order_ref as ref
+from tests import cell_forms
 from tests import helpers as H
 from tests import test_gpu_bond as B
 
@@ -91,6 +92,14 @@ def cluster(counts=CLUSTER_COUNTS, seed=5, radius=2.0):
 
 @functools.lru_cache(maxsize=None)
 def case(name):
+    """the case ``name``; "name@form" is the same case built in the cell cell_forms.apply(cell, form)"""
+    name, _, form = name.partition("@")
+    if form:
+        assert name in ("rect", "four", "sheared", "npt_diag", "npt_sheared"), name
+    return _build(name, cell_forms.apply(B.DIAG, form or None), cell_forms.apply(B.SHEARED, form or None))
+
+
+def _build(name, DIAG, SHEARED):
     if name == "rect":
         # N = 150 and F = 7: neither a multiple of 64; the cutoff gives 0 .. 12 and more neighbours, 4 among them
         return _case(B._walk(DIAG, np.full(150, 30), 7, 13), [(30, 30, 3.9)], (3, 4, 6, 12))

@@ -6,6 +6,7 @@ import functools
 
 import numpy as np
 
+from tests import cell_forms
 from tests import helpers as H
 from tests import reorientation_ref as ref
 from tests import test_gpu_bond as B
@@ -38,7 +39,7 @@ def _npt(base, seed_cells):
     return B._walk(cells, B._numbers4(97), F, 15)
 
 
-def planted(where, seed):
+def planted(where, seed, cell=DIAG):
     """test_gpu_bond.py's ``_planted`` -- four frames, the pairs edge_plant puts across the f32 guard band sit there in frame
     ``where`` and at half the planted vector in the others -- without its atoms thousands of cells away: at that distance
     float64 itself resolves a vector to 1e-10 only, and the restatement's budget (tests/reorientation_ref.py) is to stay
@@ -48,14 +49,14 @@ def planted(where, seed):
     from tests import edge_plant as E
     numbers = np.repeat([7, 30], [160, 140])
     rcm = np.array([[3.1, 3.4], [3.4, 2.9]])
-    pl = E.plant_nbr(DIAG, numbers, rcm, seed, F=1, far=False)
+    pl = E.plant_nbr(cell, numbers, rcm, seed, F=1, far=False)
     p0 = pl.packed.pos[0]
     vec = p0[pl.j] - p0[pl.i]
     near = p0.copy()
-    near[pl.j] = p0[pl.i] + 0.5 * (vec - pl.m @ DIAG) + pl.m @ DIAG
+    near[pl.j] = p0[pl.i] + 0.5 * (vec - pl.m @ cell) + pl.m @ cell
     frames = [near.copy(), near.copy(), near.copy(), near.copy()]
     frames[where] = p0
-    return PackedTrajectory(np.stack(frames), DIAG, numbers), pl
+    return PackedTrajectory(np.stack(frames), cell, numbers), pl
 
 
 def class_windows(F, delta_time):
@@ -63,8 +64,22 @@ def class_windows(F, delta_time):
     return window_setup(F, delta_time, "half", 1)
 
 
+def split(name):
+    """"rect@mirror" -> ("rect", "mirror"): a case whose cell is stored in a form of tests/cell_forms.py"""
+    base, _, form = name.partition("@")
+    return base, form or None
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
+    """the case ``name``; "name@form" is the same case built in the cell cell_forms.apply(cell, form)"""
+    name, form = split(name)
+    if form is not None:
+        assert name in ("rect", "four", "sheared", "npt_diag", "npt_sheared") or name.startswith("planted"), name
+    return _build(name, cell_forms.apply(B.DIAG, form), cell_forms.apply(B.SHEARED, form))
+
+
+def _build(name, DIAG, SHEARED):
     if name == "rect":
         return _case(B._walk(DIAG, np.full(150, 30), 131, 11), [(30, 30, 3.1)], RECT_LAGS, (1, 3))
     if name == "four":
@@ -82,7 +97,7 @@ def case(name):
                      [0, 1, 5])
     if name.startswith("planted"):
         where = int(name[-1])
-        return _case(planted(where, 40 + where)[0], PLANT_SETS, [0, 1, 2])
+        return _case(planted(where, 40 + where, DIAG)[0], PLANT_SETS, [0, 1, 2])
     if name == "composition":
         return _case(B._walk(DIAG, B._numbers4(203), 70, 21), COMP_SETS, COMP_LAGS, (1, 4))
     if name == "class":

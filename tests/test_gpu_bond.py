@@ -143,20 +143,21 @@ def test_zif4_walk_bonds_break_and_reform(hip_ctx):
     _case(hip_ctx, tr, named, windows, [({}, path), (EXACT, "bond_series_exact")], device=True)
 
 
-def _planted(where, seed):
+def _planted(where, seed, cell=DIAG):
     """four frames (0: unused filler, 1: the origin, 2: the intermediate frame, 3: origin + 2): the pairs edge_plant puts
     on both sides of rc inside the f32 guard band sit there in frame `where`; in the two other frames the same pairs are
-    bonded beyond doubt (half the planted vector), so that every counter of lag 2 hangs on the planted decision"""
+    bonded beyond doubt (half the planted vector), so that every counter of lag 2 hangs on the planted decision.
+    cell: the cell the pairs are planted in (tests/test_gpu_cell_forms.py plants them in other forms of it)"""
     numbers = np.repeat([7, 30], [160, 140])
     rcm = np.array([[3.1, 3.4], [3.4, 2.9]])
-    pl = E.plant_nbr(DIAG, numbers, rcm, seed, F=1, far=True)
+    pl = E.plant_nbr(cell, numbers, rcm, seed, F=1, far=True)
     p0 = pl.packed.pos[0]
     vec = p0[pl.j] - p0[pl.i]
     near = p0.copy()
-    near[pl.j] = p0[pl.i] + 0.5 * (vec - pl.m @ DIAG) + pl.m @ DIAG
+    near[pl.j] = p0[pl.i] + 0.5 * (vec - pl.m @ cell) + pl.m @ cell
     frames = [near.copy(), near.copy(), near.copy(), near.copy()]
     frames[where] = p0
-    return PackedTrajectory(np.stack(frames), DIAG, numbers), pl
+    return PackedTrajectory(np.stack(frames), cell, numbers), pl
 
 
 @pytest.mark.parametrize("where", [1, 2, 3])

@@ -26,6 +26,7 @@ asserted by tests/test_tri_select_cpu.py."""
 import numpy as np
 
 from amof_amd.frames import PackedTrajectory
+from tests import cell_forms
 from tests import edge_plant as E
 
 TWO32 = 4294967296.0
@@ -87,18 +88,49 @@ CASES = {
 NBINS = (7, 999, 2310)
 NBINS_BIG = {"c2_on": 31744, "c9_on": 31744}          # two cases at the LDS limit of the tile kernels
 DEVICE_INPUT = ("c3_off", "c7_on", "c11_on")
+# the cases that also run in a form of tests/cell_forms.py (tests/test_gpu_cell_forms.py): every case rotated, the per-frame
+# cases rotated and mirrored, and the exact-half cells with the second row negated (the sign of c10, on which codes 10 and
+# 11 key, changes); (name, form, nbins)
+NPT_CASES = ("npt2_on", "npt7_on", "npt3_off")
+HALF_CASES = ("c10_off", "c10_on", "c11_off", "c11_on", "c9_nohalf")
 
 
-def case_cells(name):
+def form_params():
+    return ([(n, "rot", 999) for n in CASES] + [("c2_on", "rot", 2310), ("c9_on", "rot", 2310)] +
+            [(n, "rotmirror", 999) for n in NPT_CASES] + [(n, "negrow", 999) for n in HALF_CASES])
+
+
+def case_cells(name, form=None):
+    """the cells of a case, [F][3][3]; form: one of tests/cell_forms.py (None: as tabulated)"""
     c = np.asarray(CASES[name]["cell"], dtype=np.float64)
-    return c.reshape(-1, 3, 3)
+    return cell_forms.apply(c.reshape(-1, 3, 3), form)
 
 
-def case_rmax(name):
+def case_rmax(name, form=None):
     r = CASES[name]["rmax"]
-    if r is None:       # the reference's default: half the shortest cell length, float64
-        r = float(min(np.linalg.norm(c, axis=1).min() for c in case_cells(name)) / 2)
+    if r is None:       # the reference's default: half the shortest cell length, float64 (of the cell as stored)
+        r = float(min(np.linalg.norm(c, axis=1).min() for c in case_cells(name, form)) / 2)
     return float(r)
+
+
+def case_expect(name, form=None):
+    """what the selection takes for a case in a form: (code, ax0, ax1, axis, cull).  A rigid motion or a mirror changes
+    nothing; `perm` renames the rows; negating the second row flips the sign of c10 = L10 / L00 wherever exactly one of
+    (ax0, ax1) is that row, on which the exact-half codes key: 10 and 11 change places (no other code reads the sign).
+    tests/test_cell_forms_cpu.py pins this to tri_select.h."""
+    code, cull = CASES[name]["expect"][0], CASES[name]["expect"][4]
+    order = case_order(name, form)
+    if form == "negrow" and code in (10, 11) and (order[0] == 1) != (order[1] == 1):
+        code = 21 - code
+    return (code,) + order + (cull,)
+
+
+def case_order(name, form=None):
+    """the stored axes (ax0, ax1, axis) of a case; they name rows, so they follow the rows of `perm`"""
+    order = CASES[name]["expect"][1:4]
+    if form == "perm":      # new row k is old row (1, 2, 0)[k]
+        order = tuple((2, 0, 1)[o] for o in order)
+    return tuple(order)
 
 
 class Stored(object):
@@ -160,11 +192,11 @@ class Stored(object):
         return fx, fy, fz
 
 
-def stored_frames(name, nbins):
-    cells = case_cells(name)
-    rmax = case_rmax(name)
+def stored_frames(name, nbins, form=None):
+    cells = case_cells(name, form)
+    rmax = case_rmax(name, form)
     g = E.rdf_band(cells, rmax, nbins)
-    order = CASES[name]["expect"][1:4]
+    order = case_order(name, form)
     return [Stored(c, order, rmax, nbins, g) for c in cells], g
 
 
@@ -383,14 +415,15 @@ class TriPlanted(object):
         return out
 
 
-def plant_tri(name, nbins, seed=0, n_atoms=2400, F=2, pair_share=0.92):
+def plant_tri(name, nbins, seed=0, n_atoms=2400, F=2, pair_share=0.92, form=None):
     """the planted trajectory of one case: F frames (per-frame cells: one per cell), most atoms in anchor-partner pairs
-    split evenly over the categories that apply to the case, the rest random filler"""
+    split evenly over the categories that apply to the case, the rest random filler.  form: the case's cell in one of
+    the forms of tests/cell_forms.py; the planting works from the metric of the cell as stored"""
     rng = np.random.default_rng(seed)
-    cells = case_cells(name)
+    cells = case_cells(name, form)
     F = len(cells) if len(cells) > 1 else F
-    rmax = case_rmax(name)
-    sts, g = stored_frames(name, nbins)
+    rmax = case_rmax(name, form)
+    sts, g = stored_frames(name, nbins, form)
     default = CASES[name]["rmax"] is None
     cats = categories(name, sts, default)
     nums = numbers(n_atoms)
