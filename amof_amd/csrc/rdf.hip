@@ -451,8 +451,66 @@ constexpr unsigned QUEUE_EMPTY = 0xffffffffu;
 // SLIM (with PARK): the pairs that find their lane's queue full share ONE refinement body, reached by a loop over the eight
 // pair slots with the partner's record from LDS again, instead of eight inlined ones per quad loop -- the culled ZF kernel
 // 10 423 -> 4 989 instructions, no scratch, 0.25 ms of the headline launch (profiles/r06/tile_reach.txt)
+// PRE (the plan variant's quad loops, AHEAD): a quad's partner records arrive in registers (`pre`: x, y and the slab word --
+// the f32 slab coordinate .w of a ZF quad, .z otherwise), read from LDS a whole quad earlier, and the record of partner u of the
+// wave's next quad of the piece (LDS byte address pre_addr; the piece's last quad names itself) is read into the same registers
+// behind partner u's subtractions -- no register rotation.  The compiler's own wait in front of the quad was lgkmcnt(0): the
+// LDS returns in order, so the quad's reads queued behind the wave's last atomics.  Hence the reads are inline assembly, which
+// the compiler does not count, and each partner waits with lgkmcnt(12): behind the read of partner u and in front of its next
+// wait lie three more reads of two instructions and the six atomics of three partners, held there by the reads' "memory"
+// clobbers, so at most 12 outstanding operations mean that it has arrived (more operations in between, the slow path's, only
+// make the wait longer).  PRE = 2, the ragged tail quad: always the piece's last, it reads nothing and drains first.  The
+// destination registers belong to the reads until pre_drain (rdf_tile_kernel_fast) at the end of the piece.
+// (profiles/r09/tile_ahead.txt)
+typedef uint32_t pre_u32x2 __attribute__((ext_vector_type(2)));
+struct PreRec {
+    pre_u32x2 xy;
+    uint32_t s;
+};
+template <int U, bool ZF>
+__device__ __forceinline__ void pre_read(PreRec &r, unsigned addr)
+{
+    asm volatile("ds_read_b64 %[xy], %[a] offset:%[o0]\n\tds_read_b32 %[s], %[a] offset:%[o1]"
+                 : [xy] "=&v"(r.xy), [s] "=&v"(r.s)
+                 : [a] "v"(addr), [o0] "n"(16 * U), [o1] "n"(16 * U + (ZF ? 12 : 8))
+                 : "memory");
+}
+template <int N>
+__device__ __forceinline__ void pre_wait(PreRec &r)
+{
+    // (the record is an input of the wait and passes through an empty statement behind it: whatever copy the compiler makes for a
+    //  tied operand reads the registers after the wait, and no consumer is scheduled above it)
+    asm volatile("s_waitcnt lgkmcnt(%[n])" : : "v"(r.xy), "v"(r.s), [n] "n"(N));
+    asm volatile("" : "+v"(r.xy), "+v"(r.s));
+}
+// a piece's first quad: the four records and a full wait in one statement
+// (the centres' records are operands although the text does not name them: the compiler waits for its own LDS reads of them
+//  here, once, and not with an lgkmcnt(0) at their first use inside the quad loop)
+template <bool ZF>
+__device__ __forceinline__ void pre_prime(PreRec *r, unsigned addr, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t c4,
+                                          uint32_t c5)
+{
+    asm volatile("ds_read_b64 %[xy0], %[a]\n\tds_read_b32 %[s0], %[a] offset:%[o]\n\t"
+                 "ds_read_b64 %[xy1], %[a] offset:16\n\tds_read_b32 %[s1], %[a] offset:16+%[o]\n\t"
+                 "ds_read_b64 %[xy2], %[a] offset:32\n\tds_read_b32 %[s2], %[a] offset:32+%[o]\n\t"
+                 "ds_read_b64 %[xy3], %[a] offset:48\n\tds_read_b32 %[s3], %[a] offset:48+%[o]\n\t"
+                 "s_waitcnt lgkmcnt(0)"
+                 : [xy0] "=&v"(r[0].xy), [s0] "=&v"(r[0].s), [xy1] "=&v"(r[1].xy), [s1] "=&v"(r[1].s),
+                   [xy2] "=&v"(r[2].xy), [s2] "=&v"(r[2].s), [xy3] "=&v"(r[3].xy), [s3] "=&v"(r[3].s)
+                 : [a] "v"(addr), [o] "n"(ZF ? 12 : 8), "v"(c0), "v"(c1), "v"(c2), "v"(c3), "v"(c4), "v"(c5)
+                 : "memory");
+}
+// every read of the piece has landed: only now are the registers anyone else's
+__device__ __forceinline__ void pre_drain(PreRec *r)
+{
+    asm volatile("s_waitcnt lgkmcnt(0)"
+                 :
+                 : "v"(r[0].xy), "v"(r[0].s), "v"(r[1].xy), "v"(r[1].s), "v"(r[2].xy), "v"(r[2].s), "v"(r[3].xy), "v"(r[3].s)
+                 : "memory");
+    asm volatile("" : "+v"(r[0].xy), "+v"(r[0].s), "+v"(r[1].xy), "+v"(r[1].s), "+v"(r[2].xy), "+v"(r[2].s), "+v"(r[3].xy), "+v"(r[3].s));
+}
 template <bool ORTHO, bool DIAG, bool TAIL, bool IMG = false, bool ZF = false, bool ZFK = false, bool AA = false, bool PARK = false,
-          bool SLIM = false>
+          bool SLIM = false, int PRE = 0>
 __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa, const double *sc64,
                                           const double *__restrict__ g, const float *sc, const uint4 *tq,
                                           int j0, int cntj, bool has_a, bool has_b, int ia, int ib,
@@ -462,14 +520,18 @@ __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa,
                                           const float *near_f = nullptr, int gi = 0, uint2 *nq = nullptr,
                                           unsigned *nq_count = nullptr, unsigned nq_cap = 0,
                                           float zaf = 0.0f, float zbf = 0.0f, const QAtom *__restrict__ qseg = nullptr,
-                                          float clampv = 0.0f, LaneQueue *lq = nullptr)
+                                          float clampv = 0.0f, LaneQueue *lq = nullptr, PreRec *pre = nullptr, unsigned pre_addr = 0u)
 {
     // ZF: this step uses the f32 slab coordinates; ZFK: the kernel is a ZF kernel (the .w of the LDS copies may have
     // been overwritten by an earlier step of the frame: atom indices always come from the quantised frame)
     // four partner atoms per trip, read by broadcast before any LDS atomic
+    static_assert(PRE == 0 || (SLIM && PARK && !IMG), "PRE: the slow path reads the partner's record from LDS again");
     uint4 qj[4];
+    if constexpr (PRE == 0) {
 #pragma unroll
-    for (int u = 0; u < 4; u++) qj[u] = tq[j0 + u];
+        for (int u = 0; u < 4; u++) qj[u] = tq[j0 + u];
+    }
+    if constexpr (PRE == 2) pre_drain(pre);
     float qa[4], qb[4];
     bool na[4], nb[4];   // per-pair "needs refinement" flags (kept as lane masks)
     bool anynear = false;   // IMG: some pair of this quad lies within reach of a cell face (one mask only: SGPRs are scarce)
@@ -479,6 +541,32 @@ __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa,
         const bool la = has_a && (!TAIL || j < cntj) && (!DIAG || j > ia);
         const bool lb = has_b && (!TAIL || j < cntj) && (!DIAG || j > ib);
         bool ma = false, mb = false;
+        if constexpr (PRE != 0) {
+            // (fast_bin subtracts zeros from the differences: folded away)
+            uint4 da, db;
+            auto diffs = [&](auto uc) {
+                constexpr int U = decltype(uc)::value;
+                if constexpr (PRE == 1) pre_wait<12>(pre[U]);
+                const uint32_t qx = pre[U].xy.x, qy = pre[U].xy.y, qs = pre[U].s;
+                da = make_uint4(qx - uax, qy - uay, ZF ? 0u : qs - uaz, ZF ? __float_as_uint(__uint_as_float(qs) - zaf) : 0u);
+                db = make_uint4(qx - ubx, qy - uby, ZF ? 0u : qs - ubz, ZF ? __float_as_uint(__uint_as_float(qs) - zbf) : 0u);
+                if constexpr (PRE == 1) {
+                    // (the differences exist before the read overwrites the record: volatile statements keep their order)
+                    if constexpr (ZF) asm volatile("" : "+v"(da.x), "+v"(da.y), "+v"(da.w), "+v"(db.x), "+v"(db.y), "+v"(db.w));
+                    else asm volatile("" : "+v"(da.x), "+v"(da.y), "+v"(da.z), "+v"(db.x), "+v"(db.y), "+v"(db.z));
+                    pre_read<U, ZF>(pre[U], pre_addr);
+                }
+            };
+            if (u == 0) diffs(std::integral_constant<int, 0>{});
+            else if (u == 1) diffs(std::integral_constant<int, 1>{});
+            else if (u == 2) diffs(std::integral_constant<int, 2>{});
+            else diffs(std::integral_constant<int, 3>{});
+            na[u] = fast_bin<ORTHO, IMG, ZF, AA>(hist, sc, la, half_m_guard, nb_hi, 0u, 0u, 0u, da, qa[u], near_f, &ma, 0.0f,
+                                                 clampv, ZF && !DIAG && !TAIL);
+            nb[u] = fast_bin<ORTHO, IMG, ZF, AA>(hist, sc, lb, half_m_guard, nb_hi, 0u, 0u, 0u, db, qb[u], near_f, &mb, 0.0f,
+                                                 clampv, ZF && !DIAG && !TAIL);
+            continue;
+        }
         // (ZF: centres that do not exist carry an infinite slab coordinate, so only DIAG / TAIL need a live mask)
         na[u] = fast_bin<ORTHO, IMG, ZF, AA>(hist, sc, la, half_m_guard, nb_hi, uax, uay, uaz, qj[u], qa[u], near_f, &ma, zaf,
                                              clampv, ZF && !DIAG && !TAIL);
@@ -803,7 +891,7 @@ __device__ __forceinline__ void dma_1k(const QAtom *src_lane, uint4 *dst_wave)
     dma16(src_lane, dst_wave);
 }
 
-template <bool ORTHO, bool CULL, bool IMG = false, bool ZFK = false, int TRI = -1, bool PLAN = false>
+template <bool ORTHO, bool CULL, bool IMG = false, bool ZFK = false, int TRI = -1, bool PLAN = false, int AHEAD = 0>
 // (five workgroups per CU, 96 VGPRs.  The TRI variants once spilled 136 - 240 bytes per lane at that budget -- 7x the vector-
 //  memory instructions of the diagonal kernel -- and the ones with near tests in the fast path ran better at four workgroups
 //  and 128 VGPRs; since their slow path reads the partner's record from LDS again and the canonical fallback of a full queue
@@ -830,6 +918,9 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
     // tile J, a work item without one returns at once.  Chunks of at most 16 frames (the host launches the kernel without
     // a plan otherwise): the live steps of the chunk are one 64-bit mask.
     static_assert(!PLAN || REACH, "PLAN: the slab-culled diagonal-cell kernel on f32 slab coordinates");
+    // AHEAD (PLAN only) bit 0: a wave reads the partner records of its next quad of a piece before the arithmetic of the
+    // quad in hand (fast_quad<PRE>); AMOF_RDF_NOAHEAD=1 launches the kernel without it
+    static_assert(AHEAD == 0 || PLAN, "AHEAD: the plan variant");
     // TRI = 10 / 11: near mode 4 with the exact-half x wrap, c10 = + 1/2 / - 1/2 (tri_q_twin)
     constexpr int NEAR = TRI >= 10 ? 4 : (TRI >= 0 ? TRI % 5 : 0);
     constexpr bool XW = TRI >= 5;
@@ -1215,6 +1306,36 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
                     const int own_end = !diag ? 0 : (fa.noreach ? qe : min(qe, (sub + 1) * FAST_SUB));
                     const int qe_plain = min(qe, full);
                     int j0 = qb + 4 * wave;
+                    if constexpr ((AHEAD & 1) != 0) {
+                        // the wave's quads of the piece are j0 = qb + 4 wave + 16 k < qe, whichever of the three loops takes
+                        // them: each reads the records of the next one, the last reads its own again (never past the piece),
+                        // a wave without a quad reads none
+                        // (the kernel has no static LDS: a byte offset into the dynamic part is the LDS address, see bin_count)
+                        const unsigned tq_addr = (unsigned)((const unsigned char *)tq - lds_raw);
+                        PreRec pre[4];
+                        if (j0 >= qe) continue;
+                        pre_prime<ZF>(pre, tq_addr + 16u * (unsigned)j0, uax, uay, uaz, ubx, uby, ubz);
+                        for (; j0 < own_end; j0 += 16)
+                            fast_quad<ORTHO, true, true, IMG, ZF, ZFK, AA, PARK, true, 1>(hist, fa, sc64, g, sc, tq, j0, cntj, has_a, has_b, ia, ib,
+                                                                                half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
+                                                                                idb, p, near_f, gi, nq, nullptr, nq_cap, zaf,
+                                                                                zbf, qseg, clampv, &lq, pre,
+                                                                                tq_addr + 16u * (unsigned)(j0 + 16 < qe ? j0 + 16 : j0));
+                        for (; j0 < qe_plain; j0 += 16)
+                            fast_quad<ORTHO, false, false, IMG, ZF, ZFK, AA, PARK, true, 1>(hist, fa, sc64, g, sc, tq, j0, cntj, has_a, has_b, ia, ib,
+                                                                                  half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
+                                                                                  idb, p, near_f, gi, nq, nullptr, nq_cap,
+                                                                                  zaf, zbf, qseg, clampv, &lq, pre,
+                                                                                  tq_addr + 16u * (unsigned)(j0 + 16 < qe ? j0 + 16 : j0));
+                        if (j0 == full && j0 < qe && full < cntj)
+                            fast_quad<ORTHO, false, true, IMG, ZF, ZFK, AA, PARK, true, 2>(hist, fa, sc64, g, sc, tq, full, cntj, has_a, has_b, ia, ib,
+                                                                                 half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
+                                                                                 idb, p, near_f, gi, nq, nullptr, nq_cap, zaf,
+                                                                                 zbf, qseg, clampv, &lq, pre, 0u);
+                        else
+                            pre_drain(pre);
+                        continue;
+                    }
                     for (; j0 < own_end; j0 += 16)
                         fast_quad<ORTHO, true, true, IMG, ZF, ZFK, AA, PARK, true>(hist, fa, sc64, g, sc, tq, j0, cntj, has_a, has_b, ia, ib,
                                                                          half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
@@ -2560,7 +2681,10 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
             // its slab table, rdf_tile_plan_kernel the records.  AMOF_RDF_NOPLAN=1: the search over sampled quads in every
             // step, as the other variants have it (tests / measurements).  Not for tables beyond the plan kernel's LDS or
             // plans beyond 256 MiB (systems far larger than a tile kernel's share).
+            // AMOF_RDF_NOAHEAD=1: the plan kernel without the partner records read a quad ahead (tests / measurements)
             const char *noplan = getenv("AMOF_RDF_NOPLAN");
+            const char *noahead = getenv("AMOF_RDF_NOAHEAD");
+            const bool ahead = !(noahead && noahead[0] == '1');
             const size_t plan_lds = (size_t)S * (QSLABS + 1) * sizeof(uint32_t) + ftiles.tiles.size() * TILE_PLAN_MAX_SUBS * sizeof(uint32_t);
             const size_t plan_bytes = fpairs.size() * (size_t)FB * TILE_PLAN_MAX_SUBS * sizeof(uint4);
             const bool plan_ok = use_zf && cull && !tri && !fast_img && !(noplan && noplan[0] == '1') && plan_lds <= 64 * 1024 &&
@@ -2662,10 +2786,14 @@ static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins
                     RdfFastArgs fz = fa;
                     fz.nb_hi = zf_nb_hi;
                     fz.half_m_guard = zf_half_m_guard;
-                    hipError_t e2 = plan   ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true, -1, true>)
-                                    : cull ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true>)
-                                           : allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, false, false, true>);
-                    if (e2 == hipSuccess && plan)
+                    hipError_t e2 = plan && ahead ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true, -1, true, 1>)
+                                    : plan        ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true, -1, true>)
+                                    : cull        ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true>)
+                                                  : allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, false, false, true>);
+                    if (e2 == hipSuccess && plan && ahead)
+                        hipLaunchKernelGGL((rdf_tile_kernel_fast<true, true, false, true, -1, true, 1>), grid, dim3(FAST_THREADS), lds,
+                                           ctx->stream, fz);
+                    else if (e2 == hipSuccess && plan)
                         hipLaunchKernelGGL((rdf_tile_kernel_fast<true, true, false, true, -1, true>), grid, dim3(FAST_THREADS), lds,
                                            ctx->stream, fz);
                     else if (e2 == hipSuccess && cull)
