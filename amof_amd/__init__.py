@@ -18,6 +18,8 @@ Analyses beyond the reference:
     amof_amd.bond_lifetime.BondLifetime           bond survival correlations C(t), S(t) for CoordinationNumber's sets
     amof_amd.bond_reorientation.BondReorientation reorientational correlations C1(t), C2(t) of the same sets' bond vectors
     amof_amd.bond_order.BondOrder                 Steinhardt q_l and tetrahedral order parameter of the same sets' shells
+    amof_amd.pore.Pore                            void fraction, cavity-size histogram and largest included sphere on a grid
+                                                  (the reference's Pore wraps the external Zeo++ binary: not its numbers)
 
 All distance arithmetic runs in hand-written HIP kernels (gfx950) behind the C
 ABI of ``include/amof_hip.h``; there is no CPU fallback.

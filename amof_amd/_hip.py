@@ -37,7 +37,7 @@ EXPORTS = [
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
-    "amof_bond_order", "amof_bond_order_dev",
+    "amof_bond_order", "amof_bond_order_dev", "amof_pore_field", "amof_pore_candidate_bound",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
@@ -145,6 +145,9 @@ def load_library():
         lib.amof_bond_reorientation_dev.argtypes = lib.amof_bond_reorientation.argtypes
         lib.amof_bond_order.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P]
         lib.amof_bond_order_dev.argtypes = lib.amof_bond_order.argtypes
+        lib.amof_pore_field.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, P, P, P, P, P]
+        lib.amof_pore_candidate_bound.argtypes = [P, ctypes.c_double]
+        lib.amof_pore_candidate_bound.restype = ctypes.c_double
         lib.amof_sq_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_double, ctypes.c_int32, P, P, P]
         lib.amof_sq_accumulate_dev.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
@@ -190,6 +193,13 @@ def reciprocal(cell):
 
 def device_count():
     return load_library().amof_device_count()
+
+
+def pore_candidate_bound(cell, rcut):
+    """``amof_pore_candidate_bound``: the bound (Angstrom) of the float32 candidate of the "pore_brick" path for one cell
+    ``[3][3]`` and ``rcut = dmax + the largest radius``"""
+    cell = np.ascontiguousarray(cell, dtype=np.float64).reshape(9)
+    return float(load_library().amof_pore_candidate_bound(_ptr(cell), float(rcut)))
 
 
 def species_index(numbers):
@@ -792,6 +802,34 @@ class Context(Lane):
         return (hist, hist_tet, sums, pa) if per_atom else (hist, hist_tet, sums)
 
     @_locked
+    def pore_field(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False):
+        """``(hist u64 [F][nbins + 2], counts int64 [F][n_t], vmax f64 [F], argmax int64 [F][, field f64 [F][nx][ny][nz]])``
+        of ``amof_pore_field`` over the frames of ``frame_range``: per frame the histogram of the distance ``v`` of every
+        point of the grid ``grid = (nx, ny, nz)`` over the cell to the nearest atomic surface (``radii [S]`` in Angstrom,
+        in ``kinds`` order; row: inside an atom, ``nbins = rint(dmax / dr)`` bins of ``[0, dmax)``, overflow), the points
+        with ``v >= thresholds[t]``, the largest ``v`` and its linear grid index; ``per_point``: the field itself
+        (include/amof_hip.h)."""
+        th = self._traj(packed, frame_range)
+        radii = np.ascontiguousarray(radii, dtype=np.float64).reshape(th.S)
+        grid = _i32(grid).reshape(3)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        dr, dmax = float(dr), float(dmax)
+        if not (np.isfinite(dr) and dr > 0 and np.isfinite(dmax) and dmax > 0):
+            raise ValueError("dr and dmax must be finite and > 0")
+        nbins = int(np.rint(dmax / dr))
+        if nbins < 1 or (grid < 1).any() or int(grid[0]) * int(grid[1]) * int(grid[2]) > 2 ** 31 - 1:
+            raise ValueError("dmax / dr rounds to no bin, or a grid that is not 1 .. 2^31 - 1 points")
+        F, G = th.n_frames, int(grid[0]) * int(grid[1]) * int(grid[2])
+        hist = np.zeros((F, nbins + 2), dtype=np.uint64)
+        counts = np.zeros((F, len(thr)), dtype=np.int64)
+        vmax, argmax = np.zeros(F, dtype=np.float64), np.zeros(F, dtype=np.int64)
+        field = np.zeros((F, G), dtype=np.float64) if per_point else None
+        self._check(self._lib.amof_pore_field(self._h, ctypes.byref(th.c), _ptr(radii), _ptr(grid), dr, dmax, _ptr(thr), len(thr),
+                                              _ptr(hist), _ptr(counts), _ptr(vmax), _ptr(argmax), _ptr(field)))
+        res = (hist, counts, vmax, argmax)
+        return res + (field.reshape((F,) + tuple(int(x) for x in grid)),) if per_point else res
+
+    @_locked
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None, out=None):
         """``(counts [nbins] u64, sums [P][nbins] f64, beyond, kinds)`` of ``amof_sq_accumulate``: the vectors ``hkl``
         (int ``[K][3]``) of the frames ``frame_range[0], + frame_stride, ... < frame_range[1]``, P = S(S+1)/2 species
@@ -1023,6 +1061,12 @@ class MultiContext(object):
         return self._sharded("bond_order", packed, _span(frame_range, packed.n_frames), "frame_range",
                              ("sum", "sum", "cat", "cat")[:3 + bool(per_atom)], cutoff, sets, l, nbins, nbins_tet,
                              copy_frames=True, per_atom=per_atom)
+
+    def pore_field(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False):
+        """frames sharded over the devices as ``cn_count``'s: every output is per frame, the rows concatenate"""
+        return self._sharded("pore_field", packed, _span(frame_range, packed.n_frames), "frame_range",
+                             ("cat",) * (4 + bool(per_point)), radii, grid, dr, dmax, thresholds, copy_frames=True,
+                             per_point=per_point)
 
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None):
         """frames sharded over the devices (whole strides per device; a device trajectory on another GPU is copied for the

@@ -1,0 +1,327 @@
+"""Pore geometry of a trajectory on MI355X: void fraction, cavity-size histogram and largest included sphere per frame.
+
+``Pore`` lays a grid over the cell of every frame and gives each grid point its distance to the nearest atomic surface,
+
+    v(p) = min_j |r_j - p| - R_j            (minimum image; R_j: the van der Waals radius of atom j's element)
+
+which the HIP kernels behind ``amof_pore_field`` (amof_amd/csrc/pore.hip) evaluate in the library's canonical float64
+arithmetic.  A probe of radius rp fits with its CENTRE at p where v(p) >= rp, so per frame
+
+    probe-centre volume fraction(rp) = #{v >= rp} / G,      Di = 2 max_p v(p)   (largest included sphere)
+
+and the histogram of v over the void is a cavity-size distribution.  The kernels return integers and the largest value;
+the host keeps the divisions and the DataFrames.
+
+The reference's ``Pore`` (amof/pore/core.py) writes one CIF per frame and starts the external Zeo++ binary on it.  This
+class takes the reference's four arguments and Zeo++'s column names for the quantities it has, but it is NOT Zeo++: that
+uses a Voronoi network, Monte-Carlo sampling and an accessibility test; this is the deterministic grid version of the same
+geometric quantities, converging with the grid spacing.  Not computed: accessibility / percolation of the void (the volumes
+are accessible plus non-accessible), the probe-occupiable volume, surface areas, the Gelb-Gubbins pore size distribution.
+"""
+
+import logging
+
+import numpy as np
+import pandas as pd
+
+from ._lazy import Deferred, EmptyUntilComputed
+
+from . import _hip
+from . import _setup
+from . import data as _data
+from . import dist as _dist
+from . import trajectory as _trajectory
+from .files import path as _path
+
+logger = logging.getLogger(__name__)
+
+# van der Waals radii in Angstrom (A. Bondi, J. Phys. Chem. 68 (1964) 441, and the later values commonly tabulated with them)
+BONDI = {"H": 1.20, "He": 1.40, "Li": 1.82, "C": 1.70, "N": 1.55, "O": 1.52, "F": 1.47, "Ne": 1.54, "Na": 2.27, "Mg": 1.73,
+         "Si": 2.10, "P": 1.80, "S": 1.80, "Cl": 1.75, "Ar": 1.88, "K": 2.75, "Ni": 1.63, "Cu": 1.40, "Zn": 1.39, "Ga": 1.87,
+         "As": 1.85, "Se": 1.90, "Br": 1.85, "Kr": 2.02, "Pd": 1.63, "Ag": 1.72, "Cd": 1.58, "In": 1.93, "Sn": 2.17,
+         "Te": 2.06, "I": 1.98, "Xe": 2.16, "Pt": 1.75, "Au": 1.66, "Hg": 1.55, "Tl": 1.96, "Pb": 2.02, "U": 1.86}
+AVOGADRO_A3 = 0.602214076       # N_A * 1e-24: Angstrom^3 per atom and g/mol  ->  cm^3/g
+DMAX_CAP = 8.0
+
+
+def grid_points(cell, n):
+    """Cartesian grid points ``[nx][ny][nz][3]`` of one cell ``[3][3]`` (rows = cell vectors): the point (i, j, k) has the
+    fractional coordinates ``((i + 0.5) / nx, (j + 0.5) / ny, (k + 0.5) / nz)`` and ``p_c = (f_x C[0][c] + f_y C[1][c]) +
+    f_z C[2][c]`` -- float64 products and sums in this order, the kernels' own bits.  Linear index: ``(i ny + j) nz + k``."""
+    cell = np.asarray(cell, dtype=np.float64).reshape(3, 3)
+    nx, ny, nz = (int(x) for x in n)
+    fx = ((np.arange(nx, dtype=np.float64) + 0.5) / np.float64(nx))[:, None, None, None]
+    fy = ((np.arange(ny, dtype=np.float64) + 0.5) / np.float64(ny))[None, :, None, None]
+    fz = ((np.arange(nz, dtype=np.float64) + 0.5) / np.float64(nz))[None, None, :, None]
+    return (fx * cell[0] + fy * cell[1]) + fz * cell[2]
+
+
+def default_grid(cell, spacing):
+    """``n_k = max(1, ceil(|a_k| / spacing))`` from the lattice-vector lengths of one cell"""
+    spacing = float(spacing)
+    if not (np.isfinite(spacing) and spacing > 0):
+        raise ValueError("spacing must be finite and > 0")
+    lengths = np.sqrt((np.asarray(cell, dtype=np.float64).reshape(3, 3) ** 2).sum(axis=1))
+    return tuple(max(1, int(np.ceil(x / spacing))) for x in lengths)
+
+
+def cell_heights(cells):
+    """perpendicular heights ``[..][3]`` of cells ``[..][3][3]``: volume / area of the face spanned by the other two vectors"""
+    cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
+    faces = np.stack([np.cross(cells[:, 1], cells[:, 2]), np.cross(cells[:, 2], cells[:, 0]), np.cross(cells[:, 0], cells[:, 1])], axis=1)
+    vol = np.abs((cells[:, 0] * faces[:, 0]).sum(axis=1))
+    return vol[:, None] / np.sqrt((faces ** 2).sum(axis=2))
+
+
+def half_height(cells, pbc):
+    """half the smallest perpendicular height of any cell on a periodic axis (inf without one)"""
+    h = cell_heights(cells)[:, np.asarray(pbc, dtype=bool)]
+    return 0.5 * float(h.min()) if h.size else np.inf
+
+
+def default_dmax(cells, pbc, rmax, dr):
+    """the largest multiple of ``dr`` not above ``min(8 A, min over frames of h_min / 2 - rmax)``"""
+    limit = min(DMAX_CAP, half_height(cells, pbc) - rmax)
+    k = int(np.floor(limit / dr)) if limit > 0 else 0
+    while k > 0 and k * dr > limit:
+        k -= 1
+    if k < 1:
+        raise ValueError("no multiple of dr = %g fits below half the smallest cell height minus the largest radius (%g): the cell "
+                         "is too small for these radii" % (dr, limit))
+    return k * dr
+
+
+def species_radii(numbers, radii=None):
+    """van der Waals radius (Angstrom) per atomic number of ``numbers``: ``radii`` (element symbol -> Angstrom) over the
+    built-in ``BONDI`` table; an element in neither raises ValueError"""
+    table = dict(BONDI)
+    for sym, r in (radii or {}).items():
+        r = float(r)
+        if not (np.isfinite(r) and r >= 0):
+            raise ValueError("radius of %s must be finite and >= 0" % sym)
+        table[str(sym).capitalize()] = r
+    out = []
+    for z in numbers:
+        sym = _data.chemical_symbols[int(z)]
+        if sym not in table:
+            raise ValueError("no van der Waals radius for element %s: pass radii={'%s': ...}" % (sym, sym))
+        out.append(table[sym])
+    return np.array(out, dtype=np.float64)
+
+
+def probe_label(rp):
+    return "%g" % rp
+
+
+def positions(argmax, cells, grid):
+    """``[F][3]`` grid points of the linear indices ``argmax [F]`` in the cells ``[1 or F][3][3]`` (``grid_points``' rule)"""
+    am = np.asarray(argmax, dtype=np.int64)
+    cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
+    if cells.shape[0] == 1:
+        cells = np.broadcast_to(cells, (len(am), 3, 3))
+    nx, ny, nz = (int(x) for x in grid)
+    i, j, k = am // (ny * nz), (am // nz) % ny, am % nz
+    f = np.stack([(i + 0.5) / np.float64(nx), (j + 0.5) / np.float64(ny), (k + 0.5) / np.float64(nz)], axis=1)
+    return (f[:, 0:1] * cells[:, 0] + f[:, 1:2] * cells[:, 1]) + f[:, 2:3] * cells[:, 2]
+
+
+def assemble(counts, probe_counts, vmax, step, volume, mass, probes, grid, dr):
+    """``(data, hist)`` from the library's per-frame results: ``counts`` u64 ``[F][nbins + 2]`` (inside an atom, the bins of
+    [0, dmax), overflow), ``probe_counts [F][n_probes]`` (points with v >= rp), ``vmax [F]``; ``volume [F]``: the cell
+    volumes (A^3), ``mass``: the sum of the atomic masses (g/mol).
+      data   Step, Unitcell_volume (A^3), Density (g/cm^3) = M / (V 0.602214076), per probe rp (``%g``)
+             PCV_Volume_fraction-rp = count / G, PCV_A^3-rp, PCV_cm^3/g-rp = V 0.602214076 / M (probe-centre volume:
+             accessible plus non-accessible), and Di = 2 vmax (inf where the frame has an overflow point: the largest sphere
+             is not resolved, raise dmax)
+      hist   r (bin centres) and density: the trajectory mean of count / (G dr) over the non-negative bins"""
+    counts = np.asarray(counts, dtype=np.uint64)
+    F = counts.shape[0]
+    nbins = counts.shape[1] - 2
+    G = int(grid[0]) * int(grid[1]) * int(grid[2])
+    volume = np.asarray(volume, dtype=np.float64).reshape(F)
+    step = np.asarray(step)
+    data = {"Step": step[:F] if len(step) >= F else np.arange(F), "Unitcell_volume": volume,
+            "Density": float(mass) / (volume * AVOGADRO_A3)}
+    probe_counts = np.asarray(probe_counts, dtype=np.int64).reshape(F, len(probes))
+    for k, rp in enumerate(probes):
+        frac = probe_counts[:, k].astype(np.float64) / G
+        data["PCV_Volume_fraction-" + probe_label(rp)] = frac
+        data["PCV_A^3-" + probe_label(rp)] = frac * volume
+        data["PCV_cm^3/g-" + probe_label(rp)] = frac * volume * AVOGADRO_A3 / float(mass)
+    overflow = counts[:, nbins + 1] > 0
+    data["Di"] = np.where(overflow, np.inf, 2.0 * np.asarray(vmax, dtype=np.float64).reshape(F))
+    per_frame = counts[:, 1:nbins + 1].astype(np.float64) / (G * float(dr))
+    hist = pd.DataFrame({"r": (np.arange(nbins) + 0.5) * float(dr),
+                         "density": per_frame.mean(axis=0) if F else np.full(nbins, np.nan)})
+    return pd.DataFrame(data), hist
+
+
+class Pore(Deferred):
+    """
+    Void fraction, cavity-size histogram and largest included sphere of every frame of a trajectory
+
+    ``from_trajectory`` enqueues the analysis on its device's second lane and returns; ``.data`` (and every other result)
+    waits for it (amof_amd/_lazy.py; ``AMOF_ASYNC=0``: synchronous).
+
+      .data         per frame: Step, Unitcell_volume, Density, PCV_Volume_fraction-rp / PCV_A^3-rp / PCV_cm^3/g-rp per probe
+                    radius, Di (``assemble``)
+      .hist         r, density: distribution of the distance to the nearest atomic surface over the void, trajectory mean
+      .counts       u64 [F][nbins + 2]: grid points inside an atom, per bin of [0, dmax), overflow
+      .di_position  [F][3]: where the largest included sphere sits
+      per_point=True: .field float64 [F][nx][ny][nz], the distance itself (dmax where it is not below dmax)
+    These are grid estimates of geometric quantities, not Zeo++'s numbers (see the module's docstring).
+    """
+
+    data = EmptyUntilComputed("Step")
+
+    def __init__(self):
+        """default constructor"""
+        self.data = None
+
+    @classmethod
+    def from_trajectory(cls, trajectory, delta_Step=1, first_frame=0, parallel=False, *, probe_radius=(0.0, 1.2), spacing=0.2,
+                        grid=None, dr=0.05, dmax=None, radii=None, per_point=False, device=None, distributed=None):
+        """
+        Args:
+            trajectory: list of ase.Atoms-like frames, a PackedTrajectory or an XyzStream
+            parallel: accepted for the reference's signature and ignored
+            probe_radius: probe radii in Angstrom (0: the void itself)
+            spacing: grid spacing in Angstrom: ``n_k = max(1, ceil(|a_k| / spacing))`` from frame 0's cell, the same grid for
+                all frames; grid: ``(nx, ny, nz)`` instead (required, as is dmax, with ``distributed='local'``)
+            dr: bin width of the histogram; dmax: its upper end and the largest distance resolved (default: the largest
+                multiple of dr not above min(8, half the smallest cell height - the largest radius)); dmax + the largest
+                radius above half the smallest perpendicular cell height raises ValueError
+            radii: dict element -> Angstrom over the built-in Bondi table; an element in neither raises ValueError
+            per_point: keep the field
+            device: GPU index or list of indices (default: LOCAL_RANK or 0)
+            distributed: None -> the ranks of an initialised torch.distributed group take contiguous shares of the frames;
+                False -> single process; 'local' -> the trajectory is this rank's own block of frames
+        """
+        pore = cls()
+        step = _trajectory.construct_step(delta_Step=delta_Step, first_frame=first_frame, number_of_frames=len(trajectory))
+        pore.compute_pore(trajectory, step, probe_radius, spacing, grid, dr, dmax, radii, per_point, device=device,
+                          distributed=distributed)
+        return pore
+
+    def compute_pore(self, trajectory, step, probe_radius=(0.0, 1.2), spacing=0.2, grid=None, dr=0.05, dmax=None, radii=None,
+                     per_point=False, device=None, distributed=None):
+        packed = _setup.pack(trajectory, device, keep_stream=True)
+        logger.info("Start pore analysis for %s frames", len(packed))
+        kinds, _ = _hip.packed_species(packed)
+        rs = species_radii(kinds, radii)
+        probes = [float(x) for x in np.atleast_1d(np.asarray(probe_radius, dtype=np.float64))]
+        if any(not (np.isfinite(x) and x >= 0) for x in probes):
+            raise ValueError("probe radii must be finite and >= 0")
+        dr = float(dr)
+        if not (np.isfinite(dr) and dr > 0):
+            raise ValueError("dr must be finite and > 0")
+        cells = packed._cells_known() if hasattr(packed, "_cells_known") else packed.cell
+        cells = np.asarray(cells, dtype=np.float64).reshape(-1, 3, 3)
+        if distributed == 'local' and (grid is None or dmax is None):
+            # the defaults come from the cells a rank sees: ranks with blocks of their own would not agree on the grid, on
+            # dmax or on the number of bins of the rows they gather
+            raise ValueError("distributed='local': every rank sees its own frames only, pass grid=(nx, ny, nz) and dmax=")
+        if grid is None:
+            grid = default_grid(cells[0], spacing)
+        grid = tuple(int(x) for x in grid)
+        if len(grid) != 3 or min(grid) < 1 or grid[0] * grid[1] * grid[2] > 2 ** 31 - 1:
+            raise ValueError("grid must be three counts >= 1 with at most 2^31 - 1 points")
+        rmax = float(rs.max()) if len(rs) else 0.0
+        F = len(packed)
+        if F:
+            if dmax is None:
+                dmax = default_dmax(cells, packed.pbc, rmax, dr)
+            dmax = float(dmax)
+            if not (np.isfinite(dmax) and dmax > 0) or int(np.rint(dmax / dr)) < 1:
+                raise ValueError("dmax must be finite, > 0 and at least one bin of dr")
+            # (the library's own check, with its relative slack: the default dmax may land on half a height exactly)
+            if dmax + rmax > half_height(cells, packed.pbc) * (1.0 + 1e-12):
+                raise ValueError("dmax + the largest radius = %g exceeds half the smallest cell height %g: one minimum image "
+                                 "would not do" % (dmax + rmax, 2.0 * half_height(cells, packed.pbc)))
+        else:
+            dmax = float(dmax) if dmax is not None else dr
+        nbins, n_t = int(np.rint(dmax / dr)), len(probes)
+        mass = float(np.asarray(packed.masses, dtype=np.float64).sum())
+
+        st = _setup.setup(packed, device, distributed, lane=1, keep_stream=True, honour_local=True)
+        ctx, source, sharded = st.ctx, st.source, st.sharded
+        frame_range = st.shard(F)
+        G = grid[0] * grid[1] * grid[2]
+
+        cols = nbins + 2 + n_t + 6
+
+        def finish_host(raw):
+            rows, field = raw
+            rows = np.asarray(rows, dtype=np.int64).reshape(-1, cols)
+            tail = rows[:, nbins + 2 + n_t:].copy()
+            self._assemble(rows[:, :nbins + 2].copy().view(np.uint64), rows[:, nbins + 2:nbins + 2 + n_t].copy(),
+                           tail[:, 0].copy().view(np.float64), tail[:, 1].copy(), tail[:, 2].copy().view(np.float64),
+                           tail[:, 3:].copy().view(np.float64), field, step, mass, probes, grid, dr, dmax, rs, kinds)
+
+        def call(tr, frame_range=None):
+            # one int64 row per frame -- histogram, probe counts, the bits of vmax, argmax, the bits of the cell volume and of
+            # the position of vmax -- so that one gather merges the ranks
+            res = ctx.pore_field(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point)
+            hist, counts, vmax, argmax = res[:4]
+            f0, f1 = (0, len(vmax)) if frame_range is None else frame_range
+            c = np.asarray(tr.cell, dtype=np.float64).reshape(-1, 3, 3)
+            c = np.broadcast_to(c, (f1 - f0, 3, 3)) if c.shape[0] == 1 else c[f0:f1]
+            volume = np.ascontiguousarray(np.abs(np.linalg.det(c)), dtype=np.float64).reshape(-1)
+            where = np.ascontiguousarray(positions(argmax, c, grid), dtype=np.float64).reshape(-1, 3)
+            rows = np.concatenate([hist.view(np.int64), counts, vmax.view(np.int64)[:, None], argmax[:, None],
+                                   volume.view(np.int64)[:, None], where.view(np.int64)], axis=1)
+            return rows, (res[4] if per_point else None)
+
+        if _setup.streamed(st):
+            def walk():
+                if per_point:
+                    return _setup.walk(source, call, ("cat", "cat"))
+                return _setup.walk(source, lambda batch: call(batch)[:1], ("cat",)) + (None,)
+
+            self._defer(ctx, walk, finish_host)
+            return
+
+        def local():
+            # this rank's kernels (a lane job: amof_amd/_lazy.py)
+            if F == 0:
+                return np.zeros((0, cols), dtype=np.int64), (np.zeros((0,) + grid) if per_point else None)
+            return call(packed, frame_range)
+
+        def finish(raw):
+            rows, field = raw
+            if sharded:
+                rows = _dist.all_gather_rows(rows, device=ctx.device)
+                if per_point:
+                    field = _dist.all_gather_rows(field.reshape(-1, G).view(np.int64), device=ctx.device).view(np.float64)
+                    field = field.reshape((-1,) + grid)
+            finish_host((rows, field))
+
+        self._defer(ctx, local, finish, collective=sharded)
+
+    def _assemble(self, counts, probe_counts, vmax, argmax, volume, where, field, step, mass, probes, grid, dr, dmax, radii, kinds):
+        self.counts = counts
+        self.probe_counts = probe_counts
+        self.vmax = vmax
+        self.argmax = argmax
+        self.di_position = where
+        self.grid, self.dr, self.dmax, self.probe_radius = tuple(grid), dr, dmax, list(probes)
+        self.radii = {_data.chemical_symbols[int(z)]: float(r) for z, r in zip(kinds, radii)}
+        if field is not None:
+            self.field = field
+        self.data, self.hist = assemble(counts, probe_counts, vmax, step, volume, mass, probes, grid, dr)
+        nbins = counts.shape[1] - 2
+        over = np.nonzero(counts[:, nbins + 1] > 0)[0]
+        if len(over):
+            logger.warning("Pore: %d frame(s) have grid points farther than dmax = %g from every atomic surface (first: frame %d); "
+                           "Di is inf there -- raise dmax", len(over), dmax, int(over[0]))
+
+    def write_to_file(self, path_to_output):
+        """writes ``.data`` to ``<path>.pore`` (feather)"""
+        self.data.to_feather(_path.append_suffix(path_to_output, 'pore'))
+
+    @classmethod
+    def from_file(cls, path_to_file):
+        """constructor from the file ``write_to_file`` wrote"""
+        pore = cls()
+        pore.data = pd.read_feather(_path.append_suffix(path_to_file, 'pore'))
+        return pore

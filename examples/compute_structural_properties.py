@@ -21,6 +21,7 @@ from amof_amd.rdf import Rdf                             # noqa: E402
 from amof_amd.bad import Bad                             # noqa: E402
 from amof_amd.cn import CoordinationNumber               # noqa: E402
 from amof_amd.msd import WindowMsd                       # noqa: E402
+from amof_amd.pore import Pore                           # noqa: E402
 
 
 def main(out_dir):
@@ -47,6 +48,9 @@ def main(out_dir):
         mock[k].positions = mock[k - 1].positions + rng.normal(scale=0.5, size=mock[k].positions.shape)
     msd = WindowMsd.from_trajectory(mock, delta_time=1, timestep=1)
     print(msd.data.to_string())
+
+    pore = Pore.from_trajectory(traj, spacing=0.25)      # (the reference runs Zeo++ here, :131; this is the grid estimate)
+    print(pore.data[["Step", "Density", "PCV_Volume_fraction-0", "PCV_Volume_fraction-1.2", "Di"]].to_string())
 
 
 if __name__ == "__main__":

@@ -49,6 +49,7 @@ extern "C" {
                                        16 and hand a call with a fuller centre to the exact kernel); a centre with more
                                        sends the call through a further pass with lists in global memory (no error) */
 #define AMOF_MAX_IMAGES 4096        /* extra periodic images per frame (AMOF_ECAPACITY when exceeded) */
+#define AMOF_PORE_MAX_WORDS 2048    /* amof_pore_field: nbins + 2 + n_thresholds counters per frame (AMOF_ECAPACITY beyond) */
 
 typedef struct amof_ctx amof_ctx;
 
@@ -126,6 +127,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations;
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
+ * after amof_pore_field: 2 the cell sort (0 on "pore_exact"), 3 the field kernels.
  * Returns < 0 if unavailable. */
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which);
 /* number of launches of the dominant kernel in the last call */
@@ -160,7 +162,10 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        "bond_series_exact"); the bond vectors are the canonical float64 ones on both
  *   bond order "order_frame" (the neighbour rows of BAD's frame tier: whole frames or z-slabs in LDS), "order_exact"
  *        (canonical float64 arithmetic per pair: general and per-frame cells, open axes, centres with 17 .. 64
- *        neighbours; also AMOF_ORDER_EXACT=1) */
+ *        neighbours; also AMOF_ORDER_EXACT=1)
+ *   pore field "pore_brick" (bricks of grid points against a cell list, float32 candidates, the near-minimal atoms
+ *        re-evaluated in canonical float64), "pore_exact" (every atom per grid point in canonical float64: open axes,
+ *        bricks too coarse for the cutoff or too full; also AMOF_PORE_EXACT=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -443,6 +448,40 @@ int amof_bond_order_dev(amof_ctx *ctx, const amof_traj *traj, const double *cuto
                         uint64_t *hist_dev /* device [n_sets][n_l][nbins], += */,
                         uint64_t *hist_tet_dev /* device [n_sets][nbins_tet], += */, int64_t *frame_sums /* host */,
                         int64_t *per_atom /* host or NULL */);
+
+/*
+ * Pore geometry on a grid: the distance of every grid point to the nearest atomic surface, and from it the void
+ * fraction for a set of probe radii, the cavity-size histogram and the largest included sphere, per frame.
+ * The reference's Pore (amof/pore.py) writes one CIF per frame and runs the external Zeo++ binary on it (Voronoi network,
+ * Monte-Carlo sampling, accessibility test); this is the deterministic grid version of the same geometric quantities and
+ * does not reproduce Zeo++'s numbers.  No accessibility / percolation test: the counts are of probe CENTRES that fit.
+ *   grid n = (nx, ny, nz), G = nx ny nz <= 2^31 - 1.  Point (i, j, k), linear index (i ny + j) nz + k:
+ *     f = (((double)i + 0.5) / (double)nx, ...),  p_c = (f_x C[0][c] + f_y C[1][c]) + f_z C[2][c]   (no fma; the grid spans
+ *     the cell parallelepiped, also along non-periodic axes)
+ *   atom j of species s: d0 = r_j - p from the raw positions, the canonical minimum image of it and d2 exactly as
+ *     amof_cn_count forms them, v_j = sqrt(d2) - radii[s]
+ *   field v(p) = min_j v_j if that is < dmax, else dmax (the point then counts as overflow).  The minimum of IEEE numbers
+ *     does not depend on the order: v is bit-identical whatever the path, the batching or the frame range.
+ *   dmax + max_s radii[s] must not exceed half the smallest perpendicular height of any frame's cell on a periodic axis
+ *     (AMOF_EINVAL; the heights are compared with a relative slack of 1e-12): one minimum image then suffices.
+ *   nbins = (int)rint(dmax / dr);  nbins + 2 + n_t <= AMOF_PORE_MAX_WORDS (AMOF_ECAPACITY)
+ *   hist [F][nbins + 2]: [0] points with v < 0 (inside an atom: v < 0 <=> sqrt(d2) < R, amof_cn_count's decision);
+ *     [1 + b] points with b = (int)(v / dr), 0 <= v < dmax, b < nbins;  [nbins + 1] the rest (overflow).  A row sums to G.
+ *   counts [F][n_t]: points with v >= thresholds[t] (float64 compare of the field value)
+ *   vmax [F], argmax [F]: the largest field value and the smallest linear index that has it
+ *   field (optional, may be NULL) host [F][G]: the field itself; at most 4 GiB per frame (AMOF_ECAPACITY)
+ * Paths (amof_last_path): "pore_brick", "pore_exact"; AMOF_PORE_EXACT=1 forces the latter, AMOF_PORE_BATCH=n caps the frames
+ * per launch.  amof_last_kernel_seconds: which = 2 the cell sort, 3 the field kernels.
+ * All outputs are overwritten (zeros after an error).  Errors: AMOF_EINVAL, AMOF_ECAPACITY, AMOF_ESINGULAR, AMOF_ENOMEM, AMOF_EHIP.
+ */
+int amof_pore_field(amof_ctx *ctx, const amof_traj *traj, const double *radii /* host [S], Angstrom */,
+                    const int32_t *grid /* host [3] */, double dr, double dmax, const double *thresholds /* host [n_t] */,
+                    int32_t n_t, uint64_t *hist /* host [F][nbins + 2] */, int64_t *counts /* host [F][n_t] */,
+                    double *vmax /* host [F] */, int64_t *argmax /* host [F] */, double *field /* host [F][G] or NULL */);
+/* the bound eps_c (Angstrom) on |candidate - v| that "pore_brick" uses for a cell (rows = cell vectors) and
+ * rcut = dmax + max_s radii[s] (amof_amd/csrc/pore_math.h): atoms whose float32 candidate is within 2 eps_c of the
+ * candidate minimum are re-evaluated in float64.  Tests plant decisions inside it. */
+double amof_pore_candidate_bound(const double *cell /* host [9] */, double rcut);
 
 /*
  * Static structure factor by direct summation over reciprocal-lattice vectors.
