@@ -9,6 +9,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -155,6 +156,40 @@ inline hipError_t allow_max_lds_from_zero(const void *kern)
     return static_bytes == 0 ? hipSuccess : hipErrorInvalidValue;
 }
 
+// ---- run-time switches to template arguments ----
+// Every kernel family is instantiated over a few switches.  The helpers below call f once with the run-time
+// switches as std::integral_constant tags, so a family's ladder is one call: with_flags(ortho, cell, [&](auto O, auto C)
+// { return launch_lds(kernel<O(), C()>, ...); }).
+template <bool V> using Flag = std::integral_constant<bool, V>;
+template <int V> using Count = std::integral_constant<int, V>;
+template <typename F>
+static hipError_t with_flag(bool a, F &&f)
+{
+    return a ? f(Flag<true>{}) : f(Flag<false>{});
+}
+template <typename F>
+static hipError_t with_flags(bool a, bool b, F &&f)
+{
+    return with_flag(a, [&](auto A) { return with_flag(b, [&](auto B) { return f(A, B); }); });
+}
+// v in [0, N) as a Count tag (values beyond N - 1 take the last)
+template <int N, typename F>
+static hipError_t with_count(int v, F &&f)
+{
+    if constexpr (N == 1) return f(Count<0>{});
+    else return v >= N - 1 ? f(Count<N - 1>{}) : with_count<N - 1>(v, f);
+}
+// allow_max_lds + launch + the launch's own error (kernels without dynamic LDS take lds = 0: the cap is then a no-op)
+// FROM_ZERO: allow_max_lds_from_zero
+template <bool FROM_ZERO = false, typename Kernel, typename... Args>
+static hipError_t launch_lds(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args)
+{
+    const hipError_t e = FROM_ZERO ? allow_max_lds_from_zero((const void *)kern) : allow_max_lds((const void *)kern);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
+    return hipGetLastError();
+}
+
 // --------------------------------------------------------------- geometry --
 // One record per distinct cell: 24 doubles.
 //   [0..8]  cell rows          [9..17] cell^-1 with non-periodic columns zeroed
@@ -195,15 +230,6 @@ inline double fast_guard_rel(const HostGeom &g, int64_t n_cells, bool sq_scaled 
         kappa = std::max(kappa, kappa_cell(c, inv));
     }
     return 1.1 * (5.0 * kappa + 3.06) * u;
-}
-
-// relative error bound of the RDF fast paths' f32 chain: diagonal cells as fast_guard_rel(sq_scaled); general cells
-// (5 kappa + 3.06) u with kappa of the lower factor, the largest over the six stored axis orders a kernel may pick
-inline double fast_guard_rel_rdf(const HostGeom &g, const double *cells, int64_t n_cells)
-{
-    const double u = 1.0 / 16777216.0;
-    if (g.all_ortho) return 1.1 * (3.5 + 1.56) * u;
-    return 1.1 * (5.0 * kappa_rdf(cells, n_cells) + 3.06) * u;
 }
 
 // species-sorted tiling of the atoms

@@ -64,6 +64,14 @@ inline double kappa_rdf(const double *cells, long long n_cells)
         }
     return kappa;
 }
+// relative error bound of the RDF fast paths' f32 chain: diagonal cells as fast_guard_rel(sq_scaled) (amof_internal.h);
+// general cells (5 kappa + 3.06) u with kappa of the lower factor, the largest over the six stored axis orders a kernel may pick
+inline double fast_guard_rel_rdf(bool all_ortho, const double *cells, long long n_cells)
+{
+    const double u = 1.0 / 16777216.0;
+    if (all_ortho) return 1.1 * (3.5 + 1.56) * u;
+    return 1.1 * (5.0 * kappa_rdf(cells, n_cells) + 3.06) * u;
+}
 // kappa of the neighbour kernels' chain (the cell itself as the scale matrix): P = |C^-1| |C|, sqrt(||P||_1 ||P||_inf)
 // c: cell rows, inv: its inverse (non-periodic columns zeroed)
 inline double kappa_cell(const double c[9], const double inv[9])

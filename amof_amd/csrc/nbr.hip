@@ -2081,32 +2081,6 @@ static void pick_chunks(int64_t F, size_t nwork, int32_t &fpc, unsigned &chunks)
     chunks = (unsigned)c;
 }
 
-// ---- run-time switches to template arguments ----
-// Every kernel family here is instantiated over a few switches.  The helpers below call f once with the run-time
-// switches as std::integral_constant tags, so a family's ladder is one call: with_flags(ortho, cell, [&](auto O, auto C)
-// { return launch_lds(kernel<O(), C()>, ...); }).
-template <bool V> using Flag = std::integral_constant<bool, V>;
-template <int V> using Count = std::integral_constant<int, V>;
-template <typename F>
-static hipError_t with_flag(bool a, F &&f)
-{
-    return a ? f(Flag<true>{}) : f(Flag<false>{});
-}
-template <typename F>
-static hipError_t with_flags(bool a, bool b, F &&f)
-{
-    return with_flag(a, [&](auto A) { return with_flag(b, [&](auto B) { return f(A, B); }); });
-}
-// allow_max_lds + launch + the launch's own error (kernels without dynamic LDS take lds = 0: the cap is then a no-op)
-template <typename Kernel, typename... Args>
-static hipError_t launch_lds(Kernel kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args)
-{
-    const hipError_t e = allow_max_lds((const void *)kern);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kern, grid, block, lds, stream, args...);
-    return hipGetLastError();
-}
-
 // ---- constants the two tiers' preparation shares ----
 struct NbrGuard {
     double hmin[3];         // smallest perpendicular height of any cell, per axis

@@ -30,8 +30,7 @@
 #include <vector>
 
 #include "amof_internal.h"
-#include "tile_plan.h"
-#include "tri_select.h"
+#include "rdf_select.h"
 
 namespace amof {
 
@@ -209,21 +208,7 @@ __global__ __launch_bounds__(RDF_TILE) void rdf_tile_kernel_global(RdfArgs a)
 // |s_k| = 1/2 the wrapped image and the canonical one may differ: in a diagonal cell both have the
 // same length; sheared cells take the fast path only when the cutoff stays clear of every half
 // height, so both images are out of range there.
-// per-cell record of the fast path (one per frame when the cell changes)
-struct FrameScale {
-    float sc[9];        // ORTHO: sc[0..2] = L_k * 2^-32 / dr, sc[3..5] their squares ; else the lower-triangular factor of the
-                        // metric of cell * 2^-32 / dr (rows in stored order): sc[0], sc[3], sc[4], sc[6..8]; the others 0
-    uint32_t cull_gap;  // slab-gap threshold of this cell (0 = culling off)
-    uint32_t near_t[3]; // IMG variant: a pair with |i_k| > near_t[k] (stored axis order) is evaluated canonically
-    uint32_t _pad;
-    double sc64[9];     // the same factors in f64 (level-2 refinement)
-    // TRI variant (see RdfTri below): sc[3..5] = L00^2, L11^2, L22^2, sc[8] = L22 (units: bins per 2^-32 of the axis)
-    uint32_t tri_kx, tri_ky;    // round(kx 2^32), round(ky 2^32) mod 2^32: what one cell of slab wrap adds to the folded x'', y'
-    float tri_c10;              // L10 / L00
-    float tri_near_y;           // a pair with |fl(iy)| > tri_near_y may have a second image in range (+inf: never)
-    float tri_near_z;           // likewise |dz| (bins) > tri_near_z
-    float tri_near_x;           // likewise |fl(ix + c10 iy)| (slow path only: the variant is refused when the fast path would need it)
-};
+// (the per-cell record of the fast path, FrameScale, and the sizes of the tile kernel: rdf_select.h)
 
 struct RdfFastArgs {
     RdfArgs a;
@@ -249,9 +234,6 @@ struct RdfFastArgs {
 };
 
 constexpr int FAST_THREADS = 256;
-constexpr int IMG_QUEUE_MAX = 1024; // IMG variant: parked near-face pairs per step and buffer (capacity chosen by the host)
-constexpr int FAST_TILE = 512;      // two centre atoms per thread
-constexpr int FAST_TRASH = 32;      // tile kernel: words behind the LDS histogram that take the out-of-range pairs (fast_bin<AA>)
 
 // a wave-uniform double, moved to scalar registers
 __device__ __forceinline__ double uniform_f64(double v)
@@ -881,8 +863,7 @@ __device__ __forceinline__ void fast_quad_tri(unsigned *hist, const RdfFastArgs 
 // waves of the workgroup hold the SAME 128 centre atoms (two adjacent ones per lane) and
 // share the quads of tile J round-robin, so the slab culling -- which depends only on the
 // centre atoms' slab range -- removes the same share of work from every wave.
-constexpr int FAST_SUB = 128;
-static_assert(FAST_SUB == TILE_PLAN_SUB && FAST_TILE == TILE_PLAN_MAX_SUBS * TILE_PLAN_SUB && QSLABS == TILE_PLAN_SLABS, "tile_plan.h");
+static_assert(QSLABS == TILE_PLAN_SLABS && CELL_SPECIES_SHIFT == RDF_CELL_ATOM_BITS, "tile_plan.h, rdf_select.h");
 
 // One wave copies 64 x 16 B from per-lane global addresses to 1 KiB of LDS at `dst`
 // (wave-uniform), without passing through registers (LDS-DMA, global_load_lds_dwordx4).
@@ -2057,815 +2038,496 @@ __global__ void rdf_finalize_kernel(const unsigned long long *U, const unsigned 
     }
 }
 
-static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins,
-                   unsigned long long *hist_dev, double *volume_sum)
-{
-    const int S = t->n_species;
+// ---- host side: a call record and one function per tier; every decision and record fill is in rdf_select.h ----
+struct RdfCall {
+    amof_ctx *ctx;
+    const amof_traj *t;
+    double rmax, dr;
+    int32_t nbins;
     HostGeom geom;
-    AMOF_TRY(build_geometry(ctx, t, geom));
     std::vector<double> img;
     std::vector<int32_t> nimg;
     int max_img = 0;
-    AMOF_TRY(build_images(ctx, t, geom, rmax, img, nimg, max_img));
-    const double dr = rmax / nbins;
-    const double rmax2 = rmax * rmax;
+    std::vector<unsigned long long> selfh;
+    HostTiles tiles, ftiles;            // tiles of the exact kernels (RDF_TILE) | of the fast tiers (FAST_TILE)
+    std::vector<int2> pairs, fpairs;
+    std::vector<FrameScale> fsv;        // per-cell records in the tile kernel's axis order
+    RdfSwitches sw;
+    RdfSelect sel;
+    Stager stage;
+    void *d_geom, *d_perm, *d_U, *d_self, *d_nsp;
+    void *d_ftiles, *d_fpairs, *d_spfirst, *d_fs;       // fast tiers (rdf_fast_prepare)
+    size_t U_bytes;
+    RdfArgs a;
+    RdfFastArgs fa = {};
+    bool done = false;                  // a fast tier has answered: no exact kernels
+};
+
+// The quantiser's far-atom flag (some atom lies > 1e4 cells away from the origin) behind a fast tier's launches: set, U is
+// cleared and the exact kernels take over; clear, the call is done.
+static int rdf_take_flag(RdfCall &c, const void *d_flag)
+{
+    int32_t flag = 0;
+    AMOF_TRY(fetch(c.ctx, &flag, d_flag, sizeof flag));
+    AMOF_HIP_TRY(c.ctx, sync_stream(c.ctx));
+    if (flag) AMOF_HIP_TRY(c.ctx, hipMemsetAsync(c.d_U, 0, c.U_bytes, c.ctx->stream));
+    else c.done = true;
+    return AMOF_OK;
+}
+
+// geometry, images, the exact kernels' tiles; staging, the uploads every tier shares, U cleared
+static int rdf_prepare(RdfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const int S = t->n_species, nbins = c.nbins;
+    AMOF_TRY(build_geometry(ctx, t, c.geom));
+    AMOF_TRY(build_images(ctx, t, c.geom, c.rmax, c.img, c.nimg, c.max_img));
+    const double dr = c.dr, rmax2 = c.rmax * c.rmax;
 
     // self-image pairs (i, i, E): position independent, histogrammed on the host
-    std::vector<unsigned long long> selfh((size_t)nbins, 0ull);
+    c.selfh.assign((size_t)nbins, 0ull);
     for (int64_t f = 0; f < t->n_frames; f++) {
         size_t gi = t->n_cells == 1 ? 0 : (size_t)f;
-        for (int m = 0; m < nimg[gi]; m++) {
-            const double *E = &img[(gi * max_img + m) * 3];
+        for (int m = 0; m < c.nimg[gi]; m++) {
+            const double *E = &c.img[(gi * c.max_img + m) * 3];
             double d2 = fma(E[2], E[2], fma(E[1], E[1], E[0] * E[0]));
             if (d2 < rmax2) {
                 int b = (int)(sqrt(d2) / dr);
-                if (b < nbins) selfh[(size_t)b]++;
+                if (b < nbins) c.selfh[(size_t)b]++;
             }
         }
     }
 
-    HostTiles tiles;
-    build_tiles(t, RDF_TILE, tiles);
-    std::vector<int2> pairs;
-    for (int i = 0; i < (int)tiles.tiles.size(); i++)
-        for (int j = i; j < (int)tiles.tiles.size(); j++) pairs.push_back(make_int2(i, j));
+    build_tiles(t, RDF_TILE, c.tiles);
+    for (int i = 0; i < (int)c.tiles.tiles.size(); i++)
+        for (int j = i; j < (int)c.tiles.tiles.size(); j++) c.pairs.push_back(make_int2(i, j));
 
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
-    Stager stage;
-    AMOF_TRY(stager_begin(ctx, t, true, stage));
-    const double *pos_dev = stage.dev;
-    void *d_geom, *d_img, *d_nimg, *d_perm, *d_tiles, *d_pairs, *d_U, *d_self, *d_nsp;
-    AMOF_TRY(upload(ctx, SLOT_GEOM, geom.rec.data(), geom.rec.size() * sizeof(double), &d_geom));
-    AMOF_TRY(upload(ctx, SLOT_IMG, img.data(), img.size() * sizeof(double), &d_img));
-    AMOF_TRY(upload(ctx, SLOT_NIMG, nimg.data(), nimg.size() * sizeof(int32_t), &d_nimg));
-    AMOF_TRY(upload(ctx, SLOT_PERM, tiles.perm.data(), tiles.perm.size() * sizeof(int32_t), &d_perm));
-    AMOF_TRY(upload(ctx, SLOT_TILES, tiles.tiles.data(), tiles.tiles.size() * sizeof(Tile), &d_tiles));
-    AMOF_TRY(upload(ctx, SLOT_PAIRS, pairs.data(), pairs.size() * sizeof(int2), &d_pairs));
-    AMOF_TRY(upload(ctx, SLOT_SELF, selfh.data(), selfh.size() * sizeof(unsigned long long), &d_self));
-    AMOF_TRY(upload(ctx, SLOT_AUX0, tiles.nsp.data(), tiles.nsp.size() * sizeof(int64_t), &d_nsp));
-    size_t U_bytes = (size_t)S * S * nbins * sizeof(unsigned long long);
-    AMOF_TRY(ensure(ctx, SLOT_HISTU, U_bytes, &d_U));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_U, 0, U_bytes, ctx->stream));
+    AMOF_TRY(stager_begin(ctx, t, true, c.stage));
+    void *d_img, *d_nimg, *d_tiles, *d_pairs;
+    AMOF_TRY(upload(ctx, SLOT_GEOM, c.geom.rec.data(), c.geom.rec.size() * sizeof(double), &c.d_geom));
+    AMOF_TRY(upload(ctx, SLOT_IMG, c.img.data(), c.img.size() * sizeof(double), &d_img));
+    AMOF_TRY(upload(ctx, SLOT_NIMG, c.nimg.data(), c.nimg.size() * sizeof(int32_t), &d_nimg));
+    AMOF_TRY(upload(ctx, SLOT_PERM, c.tiles.perm.data(), c.tiles.perm.size() * sizeof(int32_t), &c.d_perm));
+    AMOF_TRY(upload(ctx, SLOT_TILES, c.tiles.tiles.data(), c.tiles.tiles.size() * sizeof(Tile), &d_tiles));
+    AMOF_TRY(upload(ctx, SLOT_PAIRS, c.pairs.data(), c.pairs.size() * sizeof(int2), &d_pairs));
+    AMOF_TRY(upload(ctx, SLOT_SELF, c.selfh.data(), c.selfh.size() * sizeof(unsigned long long), &c.d_self));
+    AMOF_TRY(upload(ctx, SLOT_AUX0, c.tiles.nsp.data(), c.tiles.nsp.size() * sizeof(int64_t), &c.d_nsp));
+    c.U_bytes = (size_t)S * S * nbins * sizeof(unsigned long long);
+    AMOF_TRY(ensure(ctx, SLOT_HISTU, c.U_bytes, &c.d_U));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(c.d_U, 0, c.U_bytes, ctx->stream));
 
-    if (!pairs.empty() && t->n_frames > 0) {
-        RdfArgs a;
-        a.pos = pos_dev;
-        a.geom = (const double *)d_geom;
-        a.img = (const double *)d_img;
-        a.nimg = (const int32_t *)d_nimg;
-        a.perm = (const int32_t *)d_perm;
-        a.tiles = (const Tile *)d_tiles;
-        a.pairs = (const int2 *)d_pairs;
-        a.U = (unsigned long long *)d_U;
-        a.N = t->n_atoms;
-        a.F = (int32_t)t->n_frames;
-        a.n_cells = (int32_t)t->n_cells;
-        a.nbins = nbins;
-        a.S = S;
-        a.max_img = max_img;
-        a.rmax2 = rmax2;
-        a.dr = dr;
-        const bool extra = max_img > 0;
-        const bool ortho = geom.all_ortho;
-        auto pick_chunks = [&](int64_t nframes, int32_t &fpc_out, unsigned &chunks_out) {
-            // enough workgroups to fill 256 CUs several times over, few enough
-            // flushes that the u64 global atomics stay negligible
-            int64_t want_chunks = (8 * 2048 + (int64_t)pairs.size() - 1) / (int64_t)pairs.size();
-            int64_t fpc = std::max<int64_t>(1, nframes / std::max<int64_t>(1, want_chunks));
-            fpc = std::min<int64_t>(fpc, 64);
-            int64_t chunks = (nframes + fpc - 1) / fpc;
-            if (chunks > 65535) {
-                fpc = (nframes + 65534) / 65535;
-                chunks = (nframes + fpc - 1) / fpc;
-            }
-            fpc_out = (int32_t)fpc;
-            chunks_out = (unsigned)chunks;
-        };
+    RdfArgs &a = c.a;
+    a.pos = c.stage.dev;
+    a.geom = (const double *)c.d_geom;
+    a.img = (const double *)d_img;
+    a.nimg = (const int32_t *)d_nimg;
+    a.perm = (const int32_t *)c.d_perm;
+    a.tiles = (const Tile *)d_tiles;
+    a.pairs = (const int2 *)d_pairs;
+    a.U = (unsigned long long *)c.d_U;
+    a.N = t->n_atoms;
+    a.F = (int32_t)t->n_frames;
+    a.n_cells = (int32_t)t->n_cells;
+    a.frames_per_chunk = 1;
+    a.nbins = nbins;
+    a.S = S;
+    a.max_img = c.max_img;
+    a.rmax2 = rmax2;
+    a.dr = dr;
+    return AMOF_OK;
+}
 
-        // ---- fast path: fixed-point minimum image + guarded candidate bins ----
-        const int64_t nc = t->n_cells;
-        double csum = 0.0;   // largest sum of cell-vector lengths: bounds the fixed-point grid error
-        for (int64_t k = 0; k < nc; k++) {
-            const double *c = t->cell + 9 * k;
-            csum = std::max(csum, sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]) +
-                                      sqrt(c[3] * c[3] + c[4] * c[4] + c[5] * c[5]) +
-                                      sqrt(c[6] * c[6] + c[7] * c[7] + c[8] * c[8]));
-        }
-        // fractional coordinates are truncated to 2^-32: a pair vector moves by < csum * 2^-32;
-        // quant carries a factor 2 of margin (it also covers the f64 rounding of the fold, |s| < 1e4)
-        const double quant = csum * (1.0 / 2147483648.0);
-        const double guard_m = quant / dr + (double)nbins * 1e-12;
-        // f32 candidate: relative error bound of the chain, see fast_guard_rel (amof_internal.h)
-        const double guard_f = (double)nbins * fast_guard_rel_rdf(geom, t->cell, nc) + guard_m;
-        const char *force = getenv("AMOF_RDF_KERNEL");
-        bool fast = !extra && t->pbc[0] && t->pbc[1] && t->pbc[2] && nbins <= AMOF_MAX_LDS_BINS - 5120 &&
-                    guard_f < 0.25 && !(force && strcmp(force, "v1") == 0);
-        if (fast && !ortho) {
-            // At |s_k| = 1/2 the wrapped fixed-point image and the canonical rint() image can be different
-            // lattice images of unequal length in a sheared cell (equal in a diagonal one): keep both
-            // decisively out of range, i.e. the cutoff clear of every half height by more than the guards.
-            for (int64_t k = 0; k < nc && fast; k++)
-                for (int x = 0; x < 3; x++)
-                    if (rmax * (1.0 + 4.0 * guard_f / (double)nbins + 1e-6) >= 0.5 * geom.rec[(size_t)k * GEOM_STRIDE + 18 + x])
-                        fast = false;
-        }
-        // Image-aware variant of the tile kernel: the cutoff reaches beyond half a cell height (further periodic
-        // images count) or comes too close to it.  Pairs whose fractional difference lies within reach of a cell
-        // face are evaluated canonically (base + every listed image); all others can only have their base image
-        // in range, and that base is unambiguous.  near_thr[cell][axis]: fixed-point threshold on |i_k|.
-        bool fast_img = false;
-        double img_share = 0.0;
-        std::vector<uint32_t> near_thr;
-        if (!fast && t->pbc[0] && t->pbc[1] && t->pbc[2] && nbins <= AMOF_MAX_LDS_BINS - 5120 && guard_f < 0.25 &&
-            !(force && strcmp(force, "v1") == 0) && max_img <= 124 && !getenv("AMOF_RDF_NOIMG")) {
-            fast_img = true;
-            near_thr.assign((size_t)nc * 3, 0x7fffffffu);
-            for (int64_t k = 0; k < nc && fast_img; k++) {
-                double share = 0.0;      // expected share of the pairs that go the canonical way
-                for (int x = 0; x < 3; x++) {
-                    const double h = geom.rec[(size_t)k * GEOM_STRIDE + 18 + x];
-                    share += 2.0 * std::max(0.0, rmax / h - 0.5);
-                }
-                // the parking queue holds 1024 of a step's 65 536 pairs; beyond that the exact kernels are the better choice
-                if (share > 0.03) fast_img = false;
-                img_share = std::max(img_share, share);
+// what the cell, range and tile tiers share: tiles of FAST_TILE atoms, their pairs, the per-cell records and the guards
+// ---- fast path: fixed-point minimum image + guarded candidate bins ----
+static int rdf_fast_prepare(RdfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const RdfSelect &sel = c.sel;
+    HostTiles &ftiles = c.ftiles;
+    build_tiles(t, FAST_TILE, ftiles, FAST_SUB);
+    for (int i = 0; i < (int)ftiles.tiles.size(); i++)
+        for (int j = i; j < (int)ftiles.tiles.size(); j++) c.fpairs.push_back(make_int2(i, j));
+    // heavy tile pairs first: the drain tail of the launch is filled with the light ones
+    auto cost = [&](const int2 &pr) {
+        const double w = (double)ftiles.tiles[pr.x].count * (double)ftiles.tiles[pr.y].count;
+        return pr.x == pr.y ? 0.5 * w : w;
+    };
+    std::stable_sort(c.fpairs.begin(), c.fpairs.end(), [&](const int2 &u, const int2 &v) { return cost(u) > cost(v); });
+    AMOF_TRY(upload(ctx, SLOT_AUX2, ftiles.tiles.data(), ftiles.tiles.size() * sizeof(Tile), &c.d_ftiles));
+    AMOF_TRY(upload(ctx, SLOT_AUX3, c.fpairs.data(), c.fpairs.size() * sizeof(int2), &c.d_fpairs));
+    AMOF_TRY(upload(ctx, SLOT_AUX4, ftiles.sp_first.data(), ftiles.sp_first.size() * sizeof(int64_t), &c.d_spfirst));
+    // per-cell records; fixed-point components are stored in the order (ax0, ax1, axis)
+    const int ord[3] = {(sel.axis + 1) % 3, (sel.axis + 2) % 3, sel.axis};
+    c.fsv.assign((size_t)t->n_cells, FrameScale{});
+    fill_frame_scales(t->cell, t->n_cells, c.geom.all_ortho, ord, c.dr, sel.cull_gap.data(), sel.img ? sel.near_thr.data() : nullptr,
+                      c.fsv.data());
+    AMOF_TRY(upload(ctx, SLOT_AUX5, c.fsv.data(), c.fsv.size() * sizeof(FrameScale), &c.d_fs));
+    RdfFastArgs &fa = c.fa;
+    fa.a = c.a;
+    fa.noreach = c.sw.noreach ? 1 : 0;
+    fa.plan_noskip = c.sw.plan_noskip ? 1 : 0;
+    fa.plan = nullptr;
+    fa.a.tiles = (const Tile *)c.d_ftiles;
+    fa.a.pairs = (const int2 *)c.d_fpairs;
+    fa.fs = (const FrameScale *)c.d_fs;
+    fa.nb_hi = sel.thr.nb_hi;
+    fa.half_m_guard = sel.thr.half_m_guard;
+    fa.guard64 = sel.guard_m;
+    fa.guard64_2 = 2.0 * sel.guard_m * (1.0 + 1e-9);
+    fa.guard64_sq = sel.guard_m * sel.guard_m * (1.0 + 1e-9);
+    return AMOF_OK;
+}
+
+// ---- 3-D cell list for cutoffs far below the cell size (cell kernel) ----
+static int rdf_cell_tier(RdfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const int S = t->n_species, nbins = c.nbins;
+    const int *nk = c.sel.nk;
+    const bool ortho = c.geom.all_ortho;
+    const int npk = S * (S + 1) / 2;
+    const size_t lds3 = ((size_t)npk * nbins + (size_t)S * S) * sizeof(unsigned);
+    const int nkeys = nk[0] * nk[1] * nk[2] * S;
+    AMOF_TRY(stager_need(c.stage, t->n_frames));
+    std::vector<FrameScale> fs3((size_t)t->n_cells);
+    const int ord[3] = {0, 1, 2};
+    fill_frame_scales(t->cell, t->n_cells, ortho, ord, c.dr, nullptr, nullptr, fs3.data());
+    std::vector<uint32_t> ktab((size_t)S * S + npk);
+    {
+        int key = 0;
+        for (int lo = 0; lo < S; lo++)
+            for (int hi = lo; hi < S; hi++, key++) {
+                ktab[(size_t)lo * S + hi] = ktab[(size_t)hi * S + lo] = (uint32_t)(key * nbins);
+                ktab[(size_t)S * S + key] = (uint32_t)(((size_t)lo * S + hi) * nbins);
             }
-            for (int64_t k = 0; k < nc && fast_img; k++)
-                for (int x = 0; x < 3; x++) {
-                    const double h = geom.rec[(size_t)k * GEOM_STRIDE + 18 + x];
-                    // beyond |s| = 1/2 - tau an image shifted along this axis could come within the cutoff
-                    const double tau = rmax * (1.0 + 4.0 * guard_f / (double)nbins + 1e-6) / h - 0.5 + 1e-9;
-                    const double thr = 0.5 - std::max(tau, 0.0) - 1e-9;
-                    if (tau <= 0.0) {
-                        // clear of this half height by more than the guards: only an exact tie is ambiguous
-                        near_thr[(size_t)k * 3 + x] = 0x7fffffffu;
-                    } else if (thr < 0.3) {
-                        fast_img = false;      // two fifths of the pairs or more would go the canonical way
-                    } else {
-                        near_thr[(size_t)k * 3 + x] = (uint32_t)floor(thr * 4294967296.0) - 2u;
-                    }
-                }
-        }
-        if (fast && getenv("AMOF_RDF_FORCE_IMG")) {   // tests / measurements: the image-aware variant on a plain case
-            fast = false;
-            fast_img = true;
-            near_thr.assign((size_t)nc * 3, 0x7fffffffu);
-        }
-        // ---- TRI: general cells in the orthogonalised lattice frame (see fast_quad_tri; the selection: tri_select.h) ----
-        bool tri = false;
-        int tri_code = 0, tri_ax0 = -1, tri_ax1 = -1, tri_axis = 0;       // code: near tests (0 none, 1 slow path only, 2 fast path y, 3 y + z, 4 y with its twin image) + 5 x (x wrap with the y term)
-        double tri_share = 0.0, tri_l10_bins = 0.0, tri_c10 = 0.0, tri_tau = 0.0;
-        std::vector<double> tri_fold;       // [nc][2] kx, ky
-        std::vector<double> tri_rec;        // [nc][9] L00 L10 L11 L22 (bins per 2^-32), thr_y (units), thr_z (bins), kx, ky, thr_x (units)
-        const double two32_ = 1.0 / 4294967296.0;
-        if (!ortho && max_img <= 124 && t->pbc[0] && t->pbc[1] && t->pbc[2] && nbins <= AMOF_MAX_LDS_BINS - 5120 &&
-            guard_f < 0.25 && !(force && strcmp(force, "v1") == 0) && !getenv("AMOF_RDF_NOTRI") && !getenv("AMOF_RDF_FORCE_IMG")) {
-            std::vector<double> heights((size_t)nc * 3);
-            for (int64_t k = 0; k < nc; k++)
-                for (int x = 0; x < 3; x++) heights[(size_t)k * 3 + x] = geom.rec[(size_t)k * GEOM_STRIDE + 18 + x];
-            TriSelect sel = tri_select(t->cell, heights.data(), nc, rmax, nbins, guard_f, quant, dr, getenv("AMOF_RDF_NOHALF") != nullptr);
-            tri = sel.ok; tri_code = sel.code; tri_ax0 = sel.ax0; tri_ax1 = sel.ax1; tri_axis = sel.axis;
-            tri_share = sel.share; tri_l10_bins = sel.l10_bins; tri_c10 = sel.c10; tri_tau = sel.tau;
-            tri_fold.swap(sel.fold); tri_rec.swap(sel.rec);
-        }
-        if (tri) {      // (the guard of its candidate at the widest reach must leave room between the bin edges)
-            double hb = 0.0;
-            for (int64_t k = 0; k < nc; k++) hb = std::max(hb, geom.rec[(size_t)k * GEOM_STRIDE + 18 + tri_axis] / dr);
-            if (!(fast_guard_tri(nbins, hb, 0.5, tri_l10_bins) * (1.0 + 4.0 * tri_tau) + 2.0 * quant / dr +
-                  (1.0 + 256.0 * tri_c10) * 1.5 * csum * two32_ / dr + (double)nbins * 1e-12 < 0.25)) tri = false;
-        }
-        if (tri && getenv("AMOF_RDF_DEBUG"))
-            fprintf(stderr, "rdf_tile_tri: code %d (near mode %d, x wrap %d) axes (%d, %d | %d) parked share %.4f tau %.5f c10 %.5f\n", tri_code,
-                    tri_code >= 10 ? 4 : tri_code % 5, tri_code >= 10 ? 2 : tri_code / 5, tri_ax0, tri_ax1, tri_axis, tri_share, tri_tau, tri_c10);
-        bool done = false;
-        const bool fast_plain = fast;      // the cell-list / range kernels below rest on the plain criterion (cutoff clear of every half height)
-        if (tri) { fast = true; fast_img = false; }
-        if (fast || fast_img) {
-            HostTiles ftiles;
-            build_tiles(t, FAST_TILE, ftiles, FAST_SUB);
-            std::vector<int2> fpairs;
-            for (int i = 0; i < (int)ftiles.tiles.size(); i++)
-                for (int j = i; j < (int)ftiles.tiles.size(); j++) fpairs.push_back(make_int2(i, j));
-            // heavy tile pairs first: the drain tail of the launch is filled with the light ones
-            {
-                auto cost = [&](const int2 &pr) {
-                    const double c = (double)ftiles.tiles[pr.x].count * (double)ftiles.tiles[pr.y].count;
-                    return pr.x == pr.y ? 0.5 * c : c;
-                };
-                std::stable_sort(fpairs.begin(), fpairs.end(), [&](const int2 &u, const int2 &v) { return cost(u) > cost(v); });
-            }
-            void *d_ftiles, *d_fpairs;
-            AMOF_TRY(upload(ctx, SLOT_AUX2, ftiles.tiles.data(), ftiles.tiles.size() * sizeof(Tile), &d_ftiles));
-            AMOF_TRY(upload(ctx, SLOT_AUX3, fpairs.data(), fpairs.size() * sizeof(int2), &d_fpairs));
-            // slab axis = the axis whose smallest perpendicular height over the trajectory is largest;
-            // culling only pays when 2 rmax < h
-            int axis = 0;
-            double hmin[3] = {1e300, 1e300, 1e300};
-            for (int64_t k = 0; k < nc; k++)
-                for (int x = 0; x < 3; x++) hmin[x] = std::min(hmin[x], geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-            for (int x = 1; x < 3; x++)
-                if (hmin[x] > hmin[axis]) axis = x;
-            const char *nocull = getenv("AMOF_RDF_NOCULL");
-            const bool cull = !(nocull && nocull[0] == '1') && 2.0 * rmax * 1.05 < hmin[axis];
-            void *d_spfirst;
-            AMOF_TRY(upload(ctx, SLOT_AUX4, ftiles.sp_first.data(), ftiles.sp_first.size() * sizeof(int64_t), &d_spfirst));
-            // per-cell records; fixed-point components are stored in the order (ax0, ax1, axis)
-            std::vector<FrameScale> fsv((size_t)nc);
-            const int ord[3] = {(axis + 1) % 3, (axis + 2) % 3, axis};
-            const double two32 = 1.0 / 4294967296.0;
-            for (int64_t k = 0; k < nc; k++) {
-                const double *c = t->cell + 9 * k;
-                FrameScale &r = fsv[(size_t)k];
-                for (int q = 0; q < 9; q++) r.sc64[q] = 0.0;
-                if (ortho) {
-                    for (int q = 0; q < 3; q++) r.sc64[q] = c[4 * ord[q]] * two32 / dr;
-                } else {
-                    double rows[9];
-                    for (int q = 0; q < 3; q++)
-                        for (int x = 0; x < 3; x++) rows[3 * q + x] = c[3 * ord[q] + x] * two32 / dr;
-                    lower_factor(rows, r.sc64);
-                }
-                for (int q = 0; q < 9; q++) r.sc[q] = (float)r.sc64[q];
-                if (ortho)
-                    for (int q = 0; q < 3; q++) r.sc[3 + q] = (float)(r.sc64[q] * r.sc64[q]);
-                // a block is skipped when the slab gap alone exceeds rmax (1e-6 relative and 4 grid units of slack)
-                const double hax = geom.rec[(size_t)k * GEOM_STRIDE + 18 + axis];
-                r.cull_gap = cull ? (uint32_t)std::min(4294967295.0, ceil(rmax / hax * 4294967296.0 * (1.0 + 1e-6)) + 4.0) : 0u;
-                for (int q = 0; q < 3; q++) r.near_t[q] = fast_img ? near_thr[(size_t)k * 3 + ord[q]] : 0x7fffffffu;
-                r._pad = 0u;
-            }
-            void *d_fs;
-            AMOF_TRY(upload(ctx, SLOT_AUX5, fsv.data(), fsv.size() * sizeof(FrameScale), &d_fs));
-            RdfFastArgs fa;
-            fa.a = a;
-            {
-                const char *noreach = getenv("AMOF_RDF_NOREACH");    // tests / measurements: see rdf_tile_kernel_fast, REACH
-                fa.noreach = noreach && noreach[0] == '1' ? 1 : 0;
-                const char *noskip = getenv("AMOF_RDF_PLAN_NOSKIP");
-                fa.plan_noskip = noskip && noskip[0] == '1' ? 1 : 0;
-                fa.plan = nullptr;
-            }
-            fa.a.tiles = (const Tile *)d_ftiles;
-            fa.a.pairs = (const int2 *)d_fpairs;
-            fa.fs = (const FrameScale *)d_fs;
-            // thresholds in f32 with directed rounding, so that the f64 bound g_f is never undercut
-            {
-                const double hi = (double)nbins + guard_f, half = 0.5 - guard_f;
-                float fhi = (float)hi, fhalf = (float)half;
-                if ((double)fhi < hi) fhi = nextafterf(fhi, INFINITY);
-                if ((double)fhalf > half) fhalf = nextafterf(fhalf, -INFINITY);
-                fa.nb_hi = fhi;
-                fa.half_m_guard = fhalf;
-            }
-            fa.guard64 = guard_m;
-            fa.guard64_2 = 2.0 * guard_m * (1.0 + 1e-9);
-            fa.guard64_sq = guard_m * guard_m * (1.0 + 1e-9);
-            // Diagonal cells: the tile kernel takes the slab-axis difference from f32 coordinates (ZF, see fast_q_zf) --
-            // with slab culling for every visited partner, without it for all but a band around the sub-tile's antipode;
-            // its candidate carries one more absolute term, hence its own (slightly wider) guard.
-            const char *nozf = getenv("AMOF_RDF_NOZF");
-            bool use_zf = fast && !fast_img && ortho && !(nozf && nozf[0] == '1');
-            float zf_nb_hi = fa.nb_hi, zf_half_m_guard = fa.half_m_guard;
-            if (use_zf) {
-                double hb = 0.0, gfrac = 0.0;
-                for (int64_t k = 0; k < nc; k++) {
-                    hb = std::max(hb, geom.rec[(size_t)k * GEOM_STRIDE + 18 + axis] / dr);
-                    gfrac = std::max(gfrac, cull ? (double)fsv[(size_t)k].cull_gap / 4294967296.0 : 0.5);   // (no culling: reach 2^31)
-                }
-                const double guard_zf = fast_guard_zf(nbins, hb, gfrac) + guard_m;
-                if (!(guard_zf < 0.25)) use_zf = false;
-                const double hi = (double)nbins + guard_zf, half = 0.5 - guard_zf;
-                float fhi = (float)hi, fhalf = (float)half;
-                if ((double)fhi < hi) fhi = nextafterf(fhi, INFINITY);
-                if ((double)fhalf > half) fhalf = nextafterf(fhalf, -INFINITY);
-                zf_nb_hi = fhi;
-                zf_half_m_guard = fhalf;
-            }
-            // ---- 3-D cell list for cutoffs far below the cell size (cell kernel) ----
-            bool cell_taken = false;
-            {
-                int nk[3];
-                bool cell_ok = fast_plain && S <= 16 && t->n_atoms < (1ll << CELL_SPECIES_SHIFT) && t->n_atoms >= 64 &&
-                               !getenv("AMOF_RDF_NOCELL");
-                for (int x = 0; x < 3; x++) {
-                    nk[x] = (int)std::min(1024.0, floor(hmin[x] / (0.5 * rmax * (1.0 + 1e-5))));
-                    if (nk[x] < 5) cell_ok = false;
-                }
-                const int npk = S * (S + 1) / 2;
-                const size_t lds3 = ((size_t)npk * nbins + (size_t)S * S) * sizeof(unsigned);
-                if (lds3 > 96 * 1024) cell_ok = false;
-                if (cell_ok) {
-                    // no point in cells emptier than ~2 atoms: thicker cells are still correct (reach stays 2)
-                    while ((int64_t)nk[0] * nk[1] * nk[2] > std::max<int64_t>(125, t->n_atoms / 2)) {
-                        int big = 0;
-                        for (int x = 1; x < 3; x++)
-                            if (nk[x] > nk[big]) big = x;
-                        if (nk[big] <= 5) break;
-                        nk[big]--;
-                    }
-                    // visited share of all pairs: half shell of 5x5x5 cells (lane utilisation ~0.8) vs the slab list's
-                    // f1c / 2; a gathered pair costs ~1.8x a broadcast one and the sort is a fixed cost per frame
-                    // (crossovers measured with profiles/tools/sweep_cell.py)
-                    const double f3 = 62.5 / ((double)nk[0] * nk[1] * nk[2]) / 0.8;
-                    const double f1c = std::min(1.0, 2.0 * rmax / hmin[axis] + 2.0 / 256 + 0.02);
-                    if (!(f3 < 0.32 * f1c && t->n_atoms >= 4000) && !getenv("AMOF_RDF_FORCE_CELL")) cell_ok = false;
-                }
-                if (cell_ok) {
-                    const int nkeys = nk[0] * nk[1] * nk[2] * S;
-                    AMOF_TRY(stager_need(stage, t->n_frames));
-                    std::vector<FrameScale> fs3((size_t)nc);
-                    for (int64_t k = 0; k < nc; k++) {
-                        const double *c = t->cell + 9 * k;
-                        FrameScale &r = fs3[(size_t)k];
-                        for (int q = 0; q < 9; q++) r.sc64[q] = 0.0;
-                        if (ortho) {
-                            for (int q = 0; q < 3; q++) r.sc64[q] = c[4 * q] * two32 / dr;
-                        } else {
-                            double rows[9];
-                            for (int q = 0; q < 9; q++) rows[q] = c[q] * two32 / dr;
-                            lower_factor(rows, r.sc64);
-                        }
-                        for (int q = 0; q < 9; q++) r.sc[q] = (float)r.sc64[q];
-                        if (ortho)
-                            for (int q = 0; q < 3; q++) r.sc[3 + q] = (float)(r.sc64[q] * r.sc64[q]);
-                        r.cull_gap = 0u;
-                        r.near_t[0] = r.near_t[1] = r.near_t[2] = 0x7fffffffu;
-                        r._pad = 0u;
-                    }
-                    std::vector<uint32_t> ktab((size_t)S * S + npk);
-                    {
-                        int key = 0;
-                        for (int lo = 0; lo < S; lo++)
-                            for (int hi = lo; hi < S; hi++, key++) {
-                                ktab[(size_t)lo * S + hi] = ktab[(size_t)hi * S + lo] = (uint32_t)(key * nbins);
-                                ktab[(size_t)S * S + key] = (uint32_t)(((size_t)lo * S + hi) * nbins);
-                            }
-                    }
-                    void *d_fs3, *d_ktab, *d_spec, *d_Q3, *d_start3, *d_keys, *d_cursor, *d_flag3;
-                    AMOF_TRY(upload(ctx, SLOT_AUX5, fs3.data(), fs3.size() * sizeof(FrameScale), &d_fs3));
-                    AMOF_TRY(upload(ctx, SLOT_AUX8, ktab.data(), ktab.size() * sizeof(uint32_t), &d_ktab));
-                    AMOF_TRY(upload(ctx, SLOT_SPEC, t->species, (size_t)t->n_atoms * sizeof(int32_t), &d_spec));
-                    const size_t per_frame = (size_t)t->n_atoms * (sizeof(QAtom) + sizeof(uint32_t)) +
-                                             (size_t)(2 * nkeys + 1) * sizeof(uint32_t);
-                    int64_t FB3 = std::max<int64_t>(1, (int64_t)(1ll << 30) / (int64_t)per_frame);
-                    FB3 = std::min<int64_t>(std::min<int64_t>(FB3, 32768), t->n_frames);
-                    // (tests cross a frame-batch boundary without gigabytes of frames)
-                    if (const char *be = getenv("AMOF_RDF_BATCH")) FB3 = std::min<int64_t>(FB3, std::max(1, atoi(be)));
-                    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)FB3 * t->n_atoms * sizeof(QAtom), &d_Q3));
-                    AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)FB3 * (nkeys + 1) * sizeof(uint32_t), &d_start3));
-                    AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)FB3 * t->n_atoms * sizeof(uint32_t), &d_keys));
-                    AMOF_TRY(ensure(ctx, SLOT_AUX9, (size_t)FB3 * nkeys * sizeof(uint32_t), &d_cursor));
-                    AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag3));
-                    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag3, 0, sizeof(int32_t), ctx->stream));
-                    RdfCellArgs ca;
-                    ca.f = fa;
-                    ca.f.fs = (const FrameScale *)d_fs3;
-                    ca.f.Q = (const QAtom *)d_Q3;
-                    ca.start3 = (const uint32_t *)d_start3;
-                    ca.keyoff = (const uint32_t *)d_ktab;
-                    ca.keyU = (const uint32_t *)d_ktab + (size_t)S * S;
-                    ca.nx = nk[0]; ca.ny = nk[1]; ca.nz = nk[2];
-                    ca.npk = npk;
-                    ca.cpt = 1;
-                    ca.trim = getenv("AMOF_RDF_NOTRIM") ? 0 : 1;
-                    // round 5: one wave per cell (rdf_cellwave_kernel) unless AMOF_RDF_CELL_GATHER=1 asks for the per-lane gather form
-                    const bool wavecell = !getenv("AMOF_RDF_CELL_GATHER");
-                    const int64_t ncell3 = (int64_t)nk[0] * nk[1] * nk[2];
-                    const size_t lds3w = lds3 + ((size_t)CW_WAVES * CW_WAVE_WORDS + 1) * sizeof(unsigned);
-                    unsigned gx = (unsigned)((t->n_atoms + (int64_t)CELL_THREADS * ca.cpt - 1) / ((int64_t)CELL_THREADS * ca.cpt));
-                    if (wavecell) gx = (unsigned)((ncell3 + CW_WAVES - 1) / CW_WAVES);
-                    int64_t launches = 0;
-                    for (int64_t fb = 0; fb < t->n_frames; fb += FB3) {
-                        const int64_t nf = std::min<int64_t>(FB3, t->n_frames - fb);
-                        AMOF_TRY(launch_cell_sort(ctx, pos_dev, (const double *)d_geom, (int)t->n_cells, (const int32_t *)d_spec, S,
-                                                  t->n_atoms, (int)fb, (int)nf, nk[0], nk[1], nk[2], (QAtom *)d_Q3,
-                                                  (uint32_t *)d_start3, (uint32_t *)d_keys, (uint32_t *)d_cursor,
-                                                  (int32_t *)d_flag3));
-                        ca.f.f_base = (int32_t)fb;
-                        ca.f.nf = (int32_t)nf;
-                        ca.f.xcd_map = nf >= 16 ? 1 : 0;
-                        ca.frames_grid = (int32_t)(ca.f.xcd_map ? (nf + 7) / 8 * 8 : nf);
-                        // frames per workgroup: >= ~8k workgroups per launch (32 per CU), at most 8 frames (the u32 counters of
-                        // a chunk: 8 frames x 512 atoms x ~300 partners stay far below 2^32)
-                        {
-                            const int64_t slots = ca.f.xcd_map ? ca.frames_grid / 8 : ca.frames_grid;       // per XCD
-                            int64_t fpc = std::max<int64_t>(1, std::min<int64_t>(8, (int64_t)gx * ca.frames_grid / 8192));
-                            if (const char *fe = getenv("AMOF_RDF_CELL_FPC")) fpc = std::max(1, atoi(fe));      // experiments / tests
-                            fpc = std::min<int64_t>(fpc, slots);
-                            ca.fpc = (int32_t)fpc;
-                            const int64_t chunks = (slots + fpc - 1) / fpc;
-                            ca.frames_grid = (int32_t)(ca.f.xcd_map ? chunks * 8 : chunks);
-                        }
-                        if (wavecell) {
-                            // cell groups per workgroup: the histogram flush (npk x nbins u64 atomics) is paid per workgroup and
-                            // chunk, a cell and frame bring ~1e3 pairs -- keep >= ~8k workgroups per launch, at most 8 groups
-                            const int64_t groups = (ncell3 + CW_WAVES - 1) / CW_WAVES;
-                            int64_t cpw = std::max<int64_t>(1, std::min<int64_t>(8, groups * ca.frames_grid / 8192));
-                            if (const char *ce = getenv("AMOF_RDF_CELL_CPW")) cpw = std::max(1, atoi(ce));            // experiments / tests
-                            cpw = std::min<int64_t>(cpw, groups);
-                            ca.cpt = (int32_t)cpw;
-                            gx = (unsigned)((groups + cpw - 1) / cpw);
-                        }
-                        dim3 grid(gx, (unsigned)ca.frames_grid);
-                        if (launches == 0) timing_dom_begin(ctx, "rdf_cell");
-                        if (wavecell) {
-                            hipError_t e = ortho ? allow_max_lds((const void *)rdf_cellwave_kernel<true>)
-                                                 : allow_max_lds((const void *)rdf_cellwave_kernel<false>);
-                            AMOF_HIP_TRY(ctx, e);
-                            if (ortho) hipLaunchKernelGGL(rdf_cellwave_kernel<true>, grid, dim3(CW_THREADS), lds3w, ctx->stream, ca);
-                            else hipLaunchKernelGGL(rdf_cellwave_kernel<false>, grid, dim3(CW_THREADS), lds3w, ctx->stream, ca);
-                        } else {
-                            hipError_t e = ortho ? allow_max_lds((const void *)rdf_cell_kernel<true>)
-                                                 : allow_max_lds((const void *)rdf_cell_kernel<false>);
-                            AMOF_HIP_TRY(ctx, e);
-                            if (ortho) hipLaunchKernelGGL(rdf_cell_kernel<true>, grid, dim3(CELL_THREADS), lds3, ctx->stream, ca);
-                            else hipLaunchKernelGGL(rdf_cell_kernel<false>, grid, dim3(CELL_THREADS), lds3, ctx->stream, ca);
-                        }
-                        AMOF_HIP_TRY(ctx, hipGetLastError());
-                        launches++;
-                    }
-                    timing_dom_end(ctx, launches);
-                    int32_t flag3 = 0;
-                    AMOF_TRY(fetch(ctx, &flag3, d_flag3, sizeof flag3));
-                    AMOF_HIP_TRY(ctx, sync_stream(ctx));
-                    if (flag3) AMOF_HIP_TRY(ctx, hipMemsetAsync(d_U, 0, U_bytes, ctx->stream));   // far-away atoms: exact kernels
-                    else done = true;
-                    cell_taken = true;    // (either done, or the exact kernels take over)
-                }
-            }
-            // ---- two-level cell list for small cutoffs (range kernel) ----
-            int axis_y = (axis + 1) % 3;
-            if (hmin[(axis + 2) % 3] > hmin[axis_y]) axis_y = (axis + 2) % 3;
-            const int nz2 = (int)std::min(64.0, floor(hmin[axis] / (rmax * (1.0 + 1e-5))));
-            bool use_range = false;
-            if (fast_plain && nz2 >= 3 && t->n_cells == 1 && !cell_taken && !(getenv("AMOF_RDF_NORANGE"))) {
-                // visited share of the partners: 1-D slab list vs (3 slabs) x (y strip + 2 rmax)
-                int64_t nmax = 0;
-                for (int x = 0; x < S; x++) nmax = std::max<int64_t>(nmax, ftiles.nsp[x]);
-                const double strip = std::min(1.0, (double)FAST_SUB * nz2 / std::max<double>(1.0, (double)nmax));
-                const double f1 = std::min(1.0, 2.0 * rmax / hmin[axis] + 2.0 / 256 + 0.02);
-                const double f2 = std::min(1.0, 3.0 / nz2) * std::min(1.0, 2.0 * rmax / hmin[axis_y] + strip + 2.0 / 256);
-                use_range = f2 < 0.6 * f1 || getenv("AMOF_RDF_FORCE_RANGE") != nullptr;   // (forced: tests)
-            }
-            if (use_range) {
-                AMOF_TRY(stager_need(stage, t->n_frames));
-                const int gy = (int)ceil(rmax * (1.0 + 1e-5) / hmin[axis_y] * 256.0) + 1;
-                // scale records: stored component order is (remaining axis, axis_y, axis)
-                const int ax_x = 3 - axis - axis_y;
-                const int ord2[3] = {ax_x, axis_y, axis};
-                for (int64_t k = 0; k < nc; k++) {
-                    const double *c = t->cell + 9 * k;
-                    FrameScale &r = fsv[(size_t)k];
-                    for (int q = 0; q < 9; q++) r.sc64[q] = 0.0;
-                    if (ortho) {
-                        for (int q = 0; q < 3; q++) r.sc64[q] = c[4 * ord2[q]] * two32 / dr;
-                    } else {
-                        double rows[9];
-                        for (int q = 0; q < 3; q++)
-                            for (int x = 0; x < 3; x++) rows[3 * q + x] = c[3 * ord2[q] + x] * two32 / dr;
-                        lower_factor(rows, r.sc64);
-                    }
-                    for (int q = 0; q < 9; q++) r.sc[q] = (float)r.sc64[q];
-                    if (ortho)
-                        for (int q = 0; q < 3; q++) r.sc[3 + q] = (float)(r.sc64[q] * r.sc64[q]);
-                    r.cull_gap = 0u;
-                    r.near_t[0] = r.near_t[1] = r.near_t[2] = 0x7fffffffu;
-                    r._pad = 0u;
-                }
-                AMOF_TRY(upload(ctx, SLOT_AUX5, fsv.data(), fsv.size() * sizeof(FrameScale), &d_fs));
-                fa.fs = (const FrameScale *)d_fs;
-                std::vector<int4> rwork;
-                for (int sa2 = 0; sa2 < S; sa2++)
-                    for (int64_t c0 = 0; c0 < ftiles.nsp[sa2]; c0 += FAST_SUB)
-                        for (int sb2 = sa2; sb2 < S; sb2++)
-                            if (ftiles.nsp[sb2] > 0) rwork.push_back(make_int4(sa2, (int)c0, sb2, 0));
-                void *d_rwork, *d_start2, *d_Q2, *d_flag2;
-                AMOF_TRY(upload(ctx, SLOT_AUX6, rwork.data(), rwork.size() * sizeof(int4), &d_rwork));
-                const size_t per_frame = (size_t)t->n_atoms * sizeof(QAtom) + (size_t)S * (nz2 * 256 + 1) * sizeof(uint32_t);
-                int64_t FB2 = std::max<int64_t>(1, (int64_t)(1ll << 30) / (int64_t)per_frame);
-                FB2 = std::min<int64_t>(std::min<int64_t>(FB2, 32768), t->n_frames);
-                AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)FB2 * t->n_atoms * sizeof(QAtom), &d_Q2));
-                AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)FB2 * S * (nz2 * 256 + 1) * sizeof(uint32_t), &d_start2));
-                AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag2));
-                AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag2, 0, sizeof(int32_t), ctx->stream));
-                RdfRangeArgs ra;
-                ra.f = fa;
-                ra.f.Q = (const QAtom *)d_Q2;
-                ra.f.xcd_map = 0;
-                ra.start2 = (const uint32_t *)d_start2;
-                ra.sp_first = (const int64_t *)d_spfirst;
-                ra.work = (const int4 *)d_rwork;
-                ra.nz = nz2;
-                ra.gy_bins = gy;
-                size_t lds2 = FAST_TILE * sizeof(uint4) + (size_t)nbins * sizeof(unsigned);
-                int64_t launches = 0;
-                for (int64_t fb = 0; fb < t->n_frames && !rwork.empty(); fb += FB2) {
-                    const int64_t nf = std::min<int64_t>(FB2, t->n_frames - fb);
-                    AMOF_TRY(launch_quantize2(ctx, pos_dev, (const double *)d_geom, (int)t->n_cells, (const int32_t *)d_perm,
-                                              (const int64_t *)d_spfirst, S, t->n_atoms, (int)fb, (int)nf, axis, axis_y, nz2,
-                                              (QAtom *)d_Q2, (uint32_t *)d_start2, (int32_t *)d_flag2));
-                    ra.f.f_base = (int32_t)fb;
-                    ra.f.nf = (int32_t)nf;
-                    int64_t want_chunks = (8 * 2048 + (int64_t)rwork.size() - 1) / (int64_t)rwork.size();
-                    int64_t fpc = std::max<int64_t>(1, nf / std::max<int64_t>(1, want_chunks));
-                    fpc = std::min<int64_t>(fpc, 16);
-                    int64_t chunks = (nf + fpc - 1) / fpc;
-                    ra.f.a.frames_per_chunk = (int32_t)fpc;
-                    dim3 grid((unsigned)rwork.size(), (unsigned)chunks);
-                    if (launches == 0) timing_dom_begin(ctx, "rdf_range");
-                    hipError_t e;
-                    if (ortho) {
-                        e = allow_max_lds((const void *)rdf_range_kernel_fast<true>);
-                        if (e == hipSuccess) hipLaunchKernelGGL(rdf_range_kernel_fast<true>, grid, dim3(FAST_THREADS), lds2, ctx->stream, ra);
-                    } else {
-                        e = allow_max_lds((const void *)rdf_range_kernel_fast<false>);
-                        if (e == hipSuccess) hipLaunchKernelGGL(rdf_range_kernel_fast<false>, grid, dim3(FAST_THREADS), lds2, ctx->stream, ra);
-                    }
-                    AMOF_HIP_TRY(ctx, e);
-                    AMOF_HIP_TRY(ctx, hipGetLastError());
-                    launches++;
-                }
-                timing_dom_end(ctx, launches);
-                int32_t flag2 = 0;
-                AMOF_TRY(fetch(ctx, &flag2, d_flag2, sizeof flag2));
-                AMOF_HIP_TRY(ctx, sync_stream(ctx));
-                if (flag2) AMOF_HIP_TRY(ctx, hipMemsetAsync(d_U, 0, U_bytes, ctx->stream));
-                else done = true;
-            }
-            if (!done && !use_range && !cell_taken) {
-            int64_t FB = std::max<int64_t>(1, (int64_t)(1ll << 30) / std::max<int64_t>(1, t->n_atoms * 16));
-            FB = std::min<int64_t>(std::min<int64_t>(FB, 32768), t->n_frames);
-            // host-resident input: batches of 512, 1024, 2048 ... frames (each >= 32 chunks of 16 frames); the copy
-            // of batch k+1 overlaps the kernels of batch k, and only the first, small copy is exposed
-            int64_t cur = stage.lazy ? std::min<int64_t>(FB, 512) : FB;
-            if (const char *be = getenv("AMOF_RDF_BATCH")) cur = std::min<int64_t>(FB, std::max(1, atoi(be)));   // experiments
-            void *d_Q, *d_flag;
-            AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)FB * t->n_atoms * sizeof(QAtom), &d_Q));
-            AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag));
-            AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), ctx->stream));
-            fa.Q = (const QAtom *)d_Q;
-            size_t lds = 2 * (FAST_TILE + FAST_SUB) * sizeof(uint4) + (size_t)((nbins + FAST_TRASH + 2 + 3) & ~3) * sizeof(unsigned);
-            fa.img_queue = 0;
-            fa.img_defer = 0;
-            const double *d_fold = nullptr;
-            RdfFastArgs ft = fa;        // TRI: its own per-cell records, guards and queue
-            if (tri) {
-                std::vector<FrameScale> fst((size_t)nc);
-                double hb = 0.0, gfrac = 0.0;
-                for (int64_t k = 0; k < nc; k++) {
-                    FrameScale &r = fst[(size_t)k];
-                    memset(&r, 0, sizeof r);
-                    const double *tr = &tri_rec[(size_t)k * 9];
-                    r.sc64[0] = tr[0]; r.sc64[3] = tr[1]; r.sc64[4] = tr[2]; r.sc64[8] = tr[3];
-                    r.sc[3] = (float)(tr[0] * tr[0]); r.sc[4] = (float)(tr[2] * tr[2]); r.sc[5] = (float)(tr[3] * tr[3]);
-                    r.sc[8] = (float)tr[3];
-                    r.tri_c10 = (float)(tr[1] / tr[0]);
-                    auto down = [](double v) {      // largest float <= v
-                        if (!(v < INFINITY)) return (float)INFINITY;
-                        float f = (float)v;
-                        if ((double)f > v) f = nextafterf(f, -INFINITY);
-                        return f;
-                    };
-                    r.tri_near_y = down(tr[4]);
-                    r.tri_near_z = down(tr[5]);
-                    r.tri_near_x = down(tr[8]);
-                    r.tri_kx = (uint32_t)(long long)rint(tr[6] * 4294967296.0);
-                    r.tri_ky = (uint32_t)(long long)rint(tr[7] * 4294967296.0);
-                    r.cull_gap = fsv[(size_t)k].cull_gap;           // (same slab axis, same height)
-                    for (int q = 0; q < 3; q++) r.near_t[q] = 0x7fffffffu;
-                    hb = std::max(hb, geom.rec[(size_t)k * GEOM_STRIDE + 18 + axis] / dr);
-                    gfrac = std::max(gfrac, cull ? (double)r.cull_gap / 4294967296.0 : 0.5);
-                }
-                void *d_fst, *d_foldv;
-                AMOF_TRY(upload(ctx, SLOT_AUX5, fst.data(), fst.size() * sizeof(FrameScale), &d_fst));
-                AMOF_TRY(upload(ctx, SLOT_AUX6, tri_fold.data(), tri_fold.size() * sizeof(double), &d_foldv));
-                d_fold = (const double *)d_foldv;
-                ft.fs = (const FrameScale *)d_fst;
-                // folded coordinates: two fold roundings and the wrap constant on top of the truncation (2.5 grid units per
-                // axis instead of 1): twice the grid term; XW: the truncated f32 product c10 iy moves the x wrap and the
-                // candidate by < 1 + 256 |c10| units more (quant = 2 units of csum)
-                // (in units of the x axis: |A| <= csum; 1.5 for margin)
-                const double guard_m_tri = 2.0 * quant / dr + (tri_code >= 5 || tri_code % 5 == 4 ? (1.0 + 256.0 * tri_c10) * 1.5 * csum * two32_ / dr : 0.0) +
-                                           (double)nbins * 1e-12;
-                // (the twin image of near mode 4 has |iy| up to 2^31 (1 + 2 tau): its candidate's error bound grows with it)
-                const double guard_tri = fast_guard_tri(nbins, hb, gfrac, tri_l10_bins) * (1.0 + 4.0 * tri_tau) + guard_m_tri;
-                if (!(guard_tri < 0.25)) return fail(ctx, AMOF_ECAPACITY, "TRI guard out of range");      // (checked at selection)
-                const double half = 0.5 - guard_tri;
-                float fhalf = (float)half;
-                if ((double)fhalf > half) fhalf = nextafterf(fhalf, -INFINITY);
-                ft.half_m_guard = fhalf;
-                ft.guard64 = guard_m_tri;
-                ft.guard64_2 = 2.0 * guard_m_tri * (1.0 + 1e-9);
-                ft.guard64_sq = guard_m_tri * guard_m_tri * (1.0 + 1e-9);
-                // queue: the near pairs (share of all pairs) and the level-3 pairs of a step
-                const double expect = tri_share * (double)FAST_SUB * FAST_TILE;
-                const double want = std::max(96.0, ceil(4.0 * expect / 32.0) * 32.0);
-                ft.img_defer = want <= 256.0 ? 1 : 0;
-                ft.img_queue = ft.img_defer ? (int32_t)want : IMG_QUEUE_MAX;
-                lds = 2 * (FAST_TILE + FAST_SUB) * sizeof(uint4) + (size_t)((nbins + FAST_TRASH + 2 + 3) & ~3) * sizeof(unsigned) +
-                      (ft.img_defer ? 2 : 1) * (size_t)ft.img_queue * sizeof(uint2) + 16;
-            }
-            if (fast_img) {
-                // expected number of parked pairs per step (a step is 128 x 512 pairs).  Slightly sheared cells: two
-                // buffers of >= 96 entries, evaluated a step later -- small enough for five workgroups per CU and no
-                // extra barrier; larger shares: one buffer of 1024, evaluated at the end of the step.
-                const double expect = img_share * (double)FAST_SUB * FAST_TILE;
-                const double want = std::max(96.0, ceil(4.0 * expect / 32.0) * 32.0);
-                fa.img_defer = want <= 256.0 ? 1 : 0;
-                fa.img_queue = fa.img_defer ? (int32_t)want : IMG_QUEUE_MAX;
-                lds = 2 * (FAST_TILE + FAST_SUB) * sizeof(uint4) + (size_t)((nbins + FAST_TRASH + 2 + 3) & ~3) * sizeof(unsigned) +
-                      (fa.img_defer ? 2 : 1) * (size_t)fa.img_queue * sizeof(uint2) + 16;
-            }
-            // rdf_tile_zf with slab culling runs from a plan of its steps (rdf_tile_kernel_fast, PLAN): the quantiser writes
-            // its slab table, rdf_tile_plan_kernel the records.  AMOF_RDF_NOPLAN=1: the search over sampled quads in every
-            // step, as the other variants have it (tests / measurements).  Not for tables beyond the plan kernel's LDS or
-            // plans beyond 256 MiB (systems far larger than a tile kernel's share).
-            // AMOF_RDF_NOAHEAD=1: the plan kernel without the partner records read a quad ahead (tests / measurements)
-            const char *noplan = getenv("AMOF_RDF_NOPLAN");
-            const char *noahead = getenv("AMOF_RDF_NOAHEAD");
-            const bool ahead = !(noahead && noahead[0] == '1');
-            const size_t plan_lds = (size_t)S * (QSLABS + 1) * sizeof(uint32_t) + ftiles.tiles.size() * TILE_PLAN_MAX_SUBS * sizeof(uint32_t);
-            const size_t plan_bytes = fpairs.size() * (size_t)FB * TILE_PLAN_MAX_SUBS * sizeof(uint4);
-            const bool plan_ok = use_zf && cull && !tri && !fast_img && !(noplan && noplan[0] == '1') && plan_lds <= 64 * 1024 &&
-                                 plan_bytes <= ((size_t)256 << 20);
-            void *d_slab = nullptr, *d_plan = nullptr;
-            if (plan_ok) {
-                AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)FB * S * (QSLABS + 1) * sizeof(uint32_t), &d_slab));
-                AMOF_TRY(ensure(ctx, SLOT_AUX9, plan_bytes, &d_plan));
-            }
-            int64_t launches = 0;
-            for (int64_t fb = 0; fb < t->n_frames; fb += cur, cur = std::min<int64_t>(2 * cur, FB)) {
-                const int64_t nf = std::min<int64_t>(cur, t->n_frames - fb);
-                AMOF_TRY(stager_need(stage, fb + nf));
-                AMOF_TRY(launch_quantize(ctx, pos_dev, (const double *)d_geom, (int)t->n_cells, (const int32_t *)d_perm,
-                                         (const int64_t *)d_spfirst, S, t->n_atoms, (int)fb, (int)nf, axis, (QAtom *)d_Q,
-                                         (uint32_t *)d_slab, (int32_t *)d_flag, tri ? tri_ax0 : -1, tri ? tri_ax1 : -1, d_fold));
-                fa.f_base = (int32_t)fb;
-                fa.nf = (int32_t)nf;
-                // frames per workgroup chunk: ~80k workgroups per launch (1280 run at a time: > 60 rounds, so that
-                // ramp-up and drain stay around 1-2 %), between 2 and 16 frames -- fewer frames flush the LDS histogram
-                // more often (u64 global atomics: HBM-side write traffic), more do not fit the 4 MiB L2 of an XCD.
-                // Measured on cfg3 (profiles/r02/rdf_fpc_sweep.txt): a 625-frame shard 11.33 (10 frames) -> 11.08 ms (2);
-                // 5000 frames stay at 16 (8 would be 0.5 % faster for 38 % more traffic).
-                int64_t fpc = (nf * (int64_t)fpairs.size() + 40000) / 80000;
-                fpc = std::max<int64_t>(2, std::min<int64_t>(fpc, 16));
-                if (const char *fpc_env = getenv("AMOF_RDF_FPC")) fpc = std::max(1, atoi(fpc_env));     // experiments
-                fpc = std::min<int64_t>(fpc, std::max<int64_t>(1, nf));
-                if (nf >= 64) fpc = std::min<int64_t>(fpc, nf / 32);   // >= 32 chunks: every XCD gets >= 4
-                int64_t chunks = (nf + fpc - 1) / fpc;
-                fa.xcd_map = chunks >= 32 ? 1 : 0;
-                // the XCD mapping deals chunks in groups of 8, over a number of frames that divides by 8; the rest: one grid
-                // row per frame behind the chunks (rdf_tile_kernel_fast)
-                const int64_t nf_tail = fa.xcd_map && !getenv("AMOF_RDF_NOTAIL") ? nf % 8 : 0;
-                if (fa.xcd_map) chunks = ((nf - nf_tail + fpc - 1) / fpc + 7) / 8 * 8;
-                fa.a.frames_per_chunk = (int32_t)fpc;
-                fa.n_chunks = (int32_t)chunks;
-                fa.nf_main = (int32_t)(nf - nf_tail);
-                dim3 grid((unsigned)fpairs.size(), (unsigned)(chunks + nf_tail));
-                // (a work item keeps the live steps of its chunk in 64 bits: four per frame)
-                const bool plan = plan_ok && (fa.nf_main + chunks - 1) / chunks <= 64 / TILE_PLAN_MAX_SUBS;
-                fa.plan = nullptr;
-                if (plan) {
-                    TilePlanArgs pa;
-                    pa.slab_start = (const uint32_t *)d_slab;
-                    pa.tiles = (const Tile *)d_ftiles;
-                    pa.pairs = (const int2 *)d_fpairs;
-                    pa.sp_first = (const int64_t *)d_spfirst;
-                    pa.fs = (const FrameScale *)d_fs;
-                    pa.plan = (uint4 *)d_plan;
-                    pa.S = S; pa.ntiles = (int32_t)ftiles.tiles.size(); pa.npairs = (int32_t)fpairs.size();
-                    pa.nf = (int32_t)nf; pa.f_base = (int32_t)fb; pa.n_cells = (int32_t)t->n_cells;
-                    AMOF_HIP_TRY(ctx, allow_max_lds((const void *)rdf_tile_plan_kernel));
-                    hipLaunchKernelGGL(rdf_tile_plan_kernel, dim3((unsigned)nf), dim3(PLAN_THREADS), plan_lds, ctx->stream, pa);
-                    AMOF_HIP_TRY(ctx, hipGetLastError());
-                    fa.plan = (const uint4 *)d_plan;
-                }
-                if (launches == 0) timing_dom_begin(ctx, tri ? "rdf_tile_tri" : fast_img ? "rdf_tile_img" : use_zf ? "rdf_tile_zf" : "rdf_tile");
-                auto launch = [&](auto kern) -> hipError_t {
-                    hipError_t e2 = allow_max_lds_from_zero((const void *)kern);
-                    if (e2 != hipSuccess) return e2;
-                    hipLaunchKernelGGL(kern, grid, dim3(FAST_THREADS), lds, ctx->stream, fa);
-                    return hipSuccess;
-                };
-                hipError_t e;
-                if (tri) {
-                    ft.Q = fa.Q; ft.f_base = fa.f_base; ft.nf = fa.nf; ft.xcd_map = fa.xcd_map; ft.n_chunks = fa.n_chunks; ft.nf_main = fa.nf_main;
-                    ft.a.frames_per_chunk = fa.a.frames_per_chunk;
-                    auto launch_tri = [&](auto kern) -> hipError_t {
-                        hipError_t e2 = allow_max_lds_from_zero((const void *)kern);
-                        if (e2 != hipSuccess) return e2;
-                        hipLaunchKernelGGL(kern, grid, dim3(FAST_THREADS), lds, ctx->stream, ft);
-                        return hipSuccess;
-                    };
-                    // (one instantiation per code: near tests x x wrap)
-#define AMOF_TRI(C) (cull ? launch_tri(rdf_tile_kernel_fast<false, true, false, true, C>) : launch_tri(rdf_tile_kernel_fast<false, false, false, true, C>))
-                    switch (tri_code) {
-                    case 0: e = AMOF_TRI(0); break;
-                    case 1: e = AMOF_TRI(1); break;
-                    case 2: e = AMOF_TRI(2); break;
-                    case 3: e = AMOF_TRI(3); break;
-                    case 4: e = AMOF_TRI(4); break;
-                    case 5: e = AMOF_TRI(5); break;
-                    case 6: e = AMOF_TRI(6); break;
-                    case 7: e = AMOF_TRI(7); break;
-                    case 8: e = AMOF_TRI(8); break;
-                    case 9: e = AMOF_TRI(9); break;
-                    case 10: e = AMOF_TRI(10); break;
-                    default: e = AMOF_TRI(11); break;
-                    }
-#undef AMOF_TRI
-                }
-                else if (fast_img) {
-                    if (ortho && cull) e = launch(rdf_tile_kernel_fast<true, true, true>);
-                    else if (ortho) e = launch(rdf_tile_kernel_fast<true, false, true>);
-                    else if (cull) e = launch(rdf_tile_kernel_fast<false, true, true>);
-                    else e = launch(rdf_tile_kernel_fast<false, false, true>);
-                }
-                else if (use_zf) {
-                    RdfFastArgs fz = fa;
-                    fz.nb_hi = zf_nb_hi;
-                    fz.half_m_guard = zf_half_m_guard;
-                    hipError_t e2 = plan && ahead ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true, -1, true, 1>)
-                                    : plan        ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true, -1, true>)
-                                    : cull        ? allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, true, false, true>)
-                                                  : allow_max_lds_from_zero((const void *)rdf_tile_kernel_fast<true, false, false, true>);
-                    if (e2 == hipSuccess && plan && ahead)
-                        hipLaunchKernelGGL((rdf_tile_kernel_fast<true, true, false, true, -1, true, 1>), grid, dim3(FAST_THREADS), lds,
-                                           ctx->stream, fz);
-                    else if (e2 == hipSuccess && plan)
-                        hipLaunchKernelGGL((rdf_tile_kernel_fast<true, true, false, true, -1, true>), grid, dim3(FAST_THREADS), lds,
-                                           ctx->stream, fz);
-                    else if (e2 == hipSuccess && cull)
-                        hipLaunchKernelGGL((rdf_tile_kernel_fast<true, true, false, true>), grid, dim3(FAST_THREADS), lds,
-                                           ctx->stream, fz);
-                    else if (e2 == hipSuccess)
-                        hipLaunchKernelGGL((rdf_tile_kernel_fast<true, false, false, true>), grid, dim3(FAST_THREADS), lds,
-                                           ctx->stream, fz);
-                    e = e2;
-                }
-                else if (ortho && cull) e = launch(rdf_tile_kernel_fast<true, true>);
-                else if (ortho) e = launch(rdf_tile_kernel_fast<true, false>);
-                else if (cull) e = launch(rdf_tile_kernel_fast<false, true>);
-                else e = launch(rdf_tile_kernel_fast<false, false>);
-                AMOF_HIP_TRY(ctx, e);
-                AMOF_HIP_TRY(ctx, hipGetLastError());
-                launches++;
-            }
-            timing_dom_end(ctx, launches);
-            int32_t flag = 0;
-            AMOF_TRY(fetch(ctx, &flag, d_flag, sizeof flag));
-            AMOF_HIP_TRY(ctx, sync_stream(ctx));
-            if (flag) {
-                // some atom lies > 1e4 cells away from the origin: redo with the exact kernel
-                AMOF_HIP_TRY(ctx, hipMemsetAsync(d_U, 0, U_bytes, ctx->stream));
-            } else {
-                done = true;
-            }
-            }   // tile kernel (not the range kernel)
-        }
-        if (!done) {
-        AMOF_TRY(stager_need(stage, t->n_frames));
+    }
+    void *d_fs3, *d_ktab, *d_spec, *d_Q3, *d_start3, *d_keys, *d_cursor, *d_flag3;
+    AMOF_TRY(upload(ctx, SLOT_AUX5, fs3.data(), fs3.size() * sizeof(FrameScale), &d_fs3));
+    AMOF_TRY(upload(ctx, SLOT_AUX8, ktab.data(), ktab.size() * sizeof(uint32_t), &d_ktab));
+    AMOF_TRY(upload(ctx, SLOT_SPEC, t->species, (size_t)t->n_atoms * sizeof(int32_t), &d_spec));
+    const size_t per_frame = (size_t)t->n_atoms * (sizeof(QAtom) + sizeof(uint32_t)) + (size_t)(2 * nkeys + 1) * sizeof(uint32_t);
+    int64_t FB3 = frame_batch((int64_t)per_frame, t->n_frames);
+    if (c.sw.batch) FB3 = std::min<int64_t>(FB3, c.sw.batch);   // (tests cross a frame-batch boundary without gigabytes of frames)
+    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)FB3 * t->n_atoms * sizeof(QAtom), &d_Q3));
+    AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)FB3 * (nkeys + 1) * sizeof(uint32_t), &d_start3));
+    AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)FB3 * t->n_atoms * sizeof(uint32_t), &d_keys));
+    AMOF_TRY(ensure(ctx, SLOT_AUX9, (size_t)FB3 * nkeys * sizeof(uint32_t), &d_cursor));
+    AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag3));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag3, 0, sizeof(int32_t), ctx->stream));
+    RdfCellArgs ca;
+    ca.f = c.fa;
+    ca.f.fs = (const FrameScale *)d_fs3;
+    ca.f.Q = (const QAtom *)d_Q3;
+    ca.start3 = (const uint32_t *)d_start3;
+    ca.keyoff = (const uint32_t *)d_ktab;
+    ca.keyU = (const uint32_t *)d_ktab + (size_t)S * S;
+    ca.nx = nk[0]; ca.ny = nk[1]; ca.nz = nk[2];
+    ca.npk = npk;
+    ca.trim = c.sw.notrim ? 0 : 1;
+    // round 5: one wave per cell (rdf_cellwave_kernel) unless AMOF_RDF_CELL_GATHER=1 asks for the per-lane gather form
+    const bool wavecell = !c.sw.cell_gather;
+    const int64_t groups = ((int64_t)nk[0] * nk[1] * nk[2] + CW_WAVES - 1) / CW_WAVES;
+    const size_t lds3w = lds3 + ((size_t)CW_WAVES * CW_WAVE_WORDS + 1) * sizeof(unsigned);
+    // (the x extent a batch's frame rule starts from is the one its predecessor launched with)
+    unsigned gx = wavecell ? (unsigned)groups : (unsigned)((t->n_atoms + (int64_t)CELL_THREADS - 1) / (int64_t)CELL_THREADS);
+    int64_t launches = 0;
+    for (int64_t fb = 0; fb < t->n_frames; fb += FB3) {
+        const int64_t nf = std::min<int64_t>(FB3, t->n_frames - fb);
+        AMOF_TRY(launch_cell_sort(ctx, c.stage.dev, (const double *)c.d_geom, (int)t->n_cells, (const int32_t *)d_spec, S,
+                                  t->n_atoms, (int)fb, (int)nf, nk[0], nk[1], nk[2], (QAtom *)d_Q3,
+                                  (uint32_t *)d_start3, (uint32_t *)d_keys, (uint32_t *)d_cursor, (int32_t *)d_flag3));
+        const CellChunks ch = cell_chunks(nf, gx, wavecell ? groups : 0, c.sw);
+        gx = ch.gx;
+        ca.f.f_base = (int32_t)fb;
+        ca.f.nf = (int32_t)nf;
+        ca.f.xcd_map = ch.xcd_map;
+        ca.frames_grid = ch.frames_grid;
+        ca.fpc = ch.fpc;
+        ca.cpt = ch.cpw;
+        dim3 grid(gx, (unsigned)ca.frames_grid);
+        if (launches == 0) timing_dom_begin(ctx, "rdf_cell");
+        AMOF_HIP_TRY(ctx, with_flag(ortho, [&](auto O) {
+            return wavecell ? launch_lds(rdf_cellwave_kernel<O()>, grid, dim3(CW_THREADS), lds3w, ctx->stream, ca)
+                            : launch_lds(rdf_cell_kernel<O()>, grid, dim3(CELL_THREADS), lds3, ctx->stream, ca);
+        }));
+        launches++;
+    }
+    timing_dom_end(ctx, launches);
+    return rdf_take_flag(c, d_flag3);     // (either done, or the exact kernels take over)
+}
+
+// ---- two-level cell list for small cutoffs (range kernel) ----
+static int rdf_range_tier(RdfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const RdfSelect &sel = c.sel;
+    const HostTiles &ftiles = c.ftiles;
+    const int S = t->n_species, nbins = c.nbins, nz2 = sel.nz2;
+    AMOF_TRY(stager_need(c.stage, t->n_frames));
+    // scale records: stored component order is (remaining axis, axis_y, axis)
+    const int ord2[3] = {3 - sel.axis - sel.axis_y, sel.axis_y, sel.axis};
+    fill_frame_scales(t->cell, t->n_cells, c.geom.all_ortho, ord2, c.dr, nullptr, nullptr, c.fsv.data());
+    AMOF_TRY(upload(ctx, SLOT_AUX5, c.fsv.data(), c.fsv.size() * sizeof(FrameScale), &c.d_fs));
+    std::vector<int4> rwork;
+    for (int sa2 = 0; sa2 < S; sa2++)
+        for (int64_t c0 = 0; c0 < ftiles.nsp[sa2]; c0 += FAST_SUB)
+            for (int sb2 = sa2; sb2 < S; sb2++)
+                if (ftiles.nsp[sb2] > 0) rwork.push_back(make_int4(sa2, (int)c0, sb2, 0));
+    void *d_rwork, *d_start2, *d_Q2, *d_flag2;
+    AMOF_TRY(upload(ctx, SLOT_AUX6, rwork.data(), rwork.size() * sizeof(int4), &d_rwork));
+    const size_t per_frame = (size_t)t->n_atoms * sizeof(QAtom) + (size_t)S * (nz2 * 256 + 1) * sizeof(uint32_t);
+    const int64_t FB2 = frame_batch((int64_t)per_frame, t->n_frames);
+    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)FB2 * t->n_atoms * sizeof(QAtom), &d_Q2));
+    AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)FB2 * S * (nz2 * 256 + 1) * sizeof(uint32_t), &d_start2));
+    AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag2));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag2, 0, sizeof(int32_t), ctx->stream));
+    RdfRangeArgs ra;
+    ra.f = c.fa;
+    ra.f.fs = (const FrameScale *)c.d_fs;
+    ra.f.Q = (const QAtom *)d_Q2;
+    ra.f.xcd_map = 0;
+    ra.start2 = (const uint32_t *)d_start2;
+    ra.sp_first = (const int64_t *)c.d_spfirst;
+    ra.work = (const int4 *)d_rwork;
+    ra.nz = nz2;
+    ra.gy_bins = sel.gy;
+    const size_t lds2 = FAST_TILE * sizeof(uint4) + (size_t)nbins * sizeof(unsigned);
+    int64_t launches = 0;
+    for (int64_t fb = 0; fb < t->n_frames && !rwork.empty(); fb += FB2) {
+        const int64_t nf = std::min<int64_t>(FB2, t->n_frames - fb);
+        AMOF_TRY(launch_quantize2(ctx, c.stage.dev, (const double *)c.d_geom, (int)t->n_cells, (const int32_t *)c.d_perm,
+                                  (const int64_t *)c.d_spfirst, S, t->n_atoms, (int)fb, (int)nf, sel.axis, sel.axis_y, nz2,
+                                  (QAtom *)d_Q2, (uint32_t *)d_start2, (int32_t *)d_flag2));
+        ra.f.f_base = (int32_t)fb;
+        ra.f.nf = (int32_t)nf;
         unsigned chunks;
-        pick_chunks(t->n_frames, a.frames_per_chunk, chunks);
-        dim3 grid((unsigned)pairs.size(), chunks);
-        timing_dom_begin(ctx, "rdf_exact");
-        if (nbins <= AMOF_MAX_LDS_BINS) {
-            size_t lds = 3 * RDF_TILE * sizeof(double) + (size_t)nbins * sizeof(unsigned);
-            auto launch = [&](auto kern) -> hipError_t {
-                hipError_t e = allow_max_lds((const void *)kern);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, grid, dim3(RDF_TILE), lds, ctx->stream, a);
-                return hipGetLastError();
-            };
-            hipError_t e;
-            if (ortho && !extra) e = launch(rdf_tile_kernel<true, false>);
-            else if (ortho && extra) e = launch(rdf_tile_kernel<true, true>);
-            else if (!ortho && !extra) e = launch(rdf_tile_kernel<false, false>);
-            else e = launch(rdf_tile_kernel<false, true>);
-            AMOF_HIP_TRY(ctx, e);
-        } else {
-            if (ortho && !extra) hipLaunchKernelGGL((rdf_tile_kernel_global<true, false>), grid, dim3(RDF_TILE), 0, ctx->stream, a);
-            else if (ortho && extra) hipLaunchKernelGGL((rdf_tile_kernel_global<true, true>), grid, dim3(RDF_TILE), 0, ctx->stream, a);
-            else if (!ortho && !extra) hipLaunchKernelGGL((rdf_tile_kernel_global<false, false>), grid, dim3(RDF_TILE), 0, ctx->stream, a);
-            else hipLaunchKernelGGL((rdf_tile_kernel_global<false, true>), grid, dim3(RDF_TILE), 0, ctx->stream, a);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
+        pick_chunks(nf, (int64_t)rwork.size(), 16, ra.f.a.frames_per_chunk, chunks);
+        dim3 grid((unsigned)rwork.size(), chunks);
+        if (launches == 0) timing_dom_begin(ctx, "rdf_range");
+        AMOF_HIP_TRY(ctx, with_flag(c.geom.all_ortho, [&](auto O) {
+            return launch_lds(rdf_range_kernel_fast<O()>, grid, dim3(FAST_THREADS), lds2, ctx->stream, ra);
+        }));
+        launches++;
+    }
+    timing_dom_end(ctx, launches);
+    return rdf_take_flag(c, d_flag2);
+}
+
+// TRI: the variant's own per-cell records, fold table, guards and queue into k; *d_fold: the fold table for the quantiser
+static int rdf_tri_args(RdfCall &c, RdfFastArgs &k, const double **d_fold)
+{
+    amof_ctx *ctx = c.ctx;
+    const RdfSelect &sel = c.sel;
+    const TriSelect &tri = sel.tri;
+    const int64_t nc = c.t->n_cells;
+    const int nbins = c.nbins;
+    const double dr = c.dr;
+    std::vector<FrameScale> fst((size_t)nc);
+    fill_frame_scales_tri(tri.rec.data(), nc, sel.cull_gap.data(), fst.data());      // (same slab axis, same height)
+    double hb = 0.0, gfrac = 0.0;
+    for (int64_t q = 0; q < nc; q++) {
+        hb = std::max(hb, c.geom.rec[(size_t)q * GEOM_STRIDE + 18 + sel.axis] / dr);
+        gfrac = std::max(gfrac, sel.cull ? (double)sel.cull_gap[(size_t)q] / 4294967296.0 : 0.5);
+    }
+    void *d_fst, *d_foldv;
+    AMOF_TRY(upload(ctx, SLOT_AUX5, fst.data(), fst.size() * sizeof(FrameScale), &d_fst));
+    AMOF_TRY(upload(ctx, SLOT_AUX6, tri.fold.data(), tri.fold.size() * sizeof(double), &d_foldv));
+    *d_fold = (const double *)d_foldv;
+    k.fs = (const FrameScale *)d_fst;
+    // folded coordinates: two fold roundings and the wrap constant on top of the truncation (2.5 grid units per
+    // axis instead of 1): twice the grid term; XW: the truncated f32 product c10 iy moves the x wrap and the
+    // candidate by < 1 + 256 |c10| units more (quant = 2 units of csum)
+    // (in units of the x axis: |A| <= csum; 1.5 for margin)
+    const double guard_m_tri = 2.0 * sel.quant / dr +
+                               (tri.code >= 5 || tri.code % 5 == 4 ? (1.0 + 256.0 * tri.c10) * 1.5 * sel.csum * (1.0 / 4294967296.0) / dr : 0.0) +
+                               (double)nbins * 1e-12;
+    // (the twin image of near mode 4 has |iy| up to 2^31 (1 + 2 tau): its candidate's error bound grows with it)
+    const double guard_tri = fast_guard_tri(nbins, hb, gfrac, tri.l10_bins) * (1.0 + 4.0 * tri.tau) + guard_m_tri;
+    if (!(guard_tri < 0.25)) return fail(ctx, AMOF_ECAPACITY, "TRI guard out of range");      // (checked at selection)
+    k.half_m_guard = guard_thresholds(nbins, guard_tri).half_m_guard;
+    k.guard64 = guard_m_tri;
+    k.guard64_2 = 2.0 * guard_m_tri * (1.0 + 1e-9);
+    k.guard64_sq = guard_m_tri * guard_m_tri * (1.0 + 1e-9);
+    // queue: the near pairs (share of all pairs) and the level-3 pairs of a step
+    const ParkedQueue pq = parked_queue(tri.share);
+    k.img_queue = pq.img_queue;
+    k.img_defer = pq.img_defer;
+    return AMOF_OK;
+}
+
+// one launch of the tile kernel's selected variant.  TRI: one instantiation per code (near tests x x wrap); ZF: a list of
+// four (planned with / without the records read a quad ahead, culled, unculled)
+static hipError_t rdf_tile_launch(RdfCall &c, const RdfFastArgs &k, dim3 grid, size_t lds, bool plan)
+{
+    const RdfSelect &sel = c.sel;
+    const bool ortho = c.geom.all_ortho, cull = sel.cull;
+    auto launch = [&](auto kern) { return launch_lds<true>(kern, grid, dim3(FAST_THREADS), lds, c.ctx->stream, k); };
+    if (sel.tri.ok)
+        return with_flag(cull, [&](auto C) {
+            return with_count<12>(sel.tri.code, [&](auto K) { return launch(rdf_tile_kernel_fast<false, C(), false, true, K()>); });
+        });
+    if (sel.img) return with_flags(ortho, cull, [&](auto O, auto C) { return launch(rdf_tile_kernel_fast<O(), C(), true>); });
+    if (sel.zf)
+        return plan && !c.sw.noahead ? launch(rdf_tile_kernel_fast<true, true, false, true, -1, true, 1>)
+               : plan                ? launch(rdf_tile_kernel_fast<true, true, false, true, -1, true>)
+               : cull                ? launch(rdf_tile_kernel_fast<true, true, false, true>)
+                                     : launch(rdf_tile_kernel_fast<true, false, false, true>);
+    return with_flags(ortho, cull, [&](auto O, auto C) { return launch(rdf_tile_kernel_fast<O(), C()>); });
+}
+
+// ---- slab list (tile kernel): rdf_tile, rdf_tile_zf, rdf_tile_img, rdf_tile_tri ----
+static int rdf_tile_tier(RdfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const RdfSelect &sel = c.sel;
+    const int S = t->n_species, nbins = c.nbins;
+    const bool tri = sel.tri.ok;
+    const int64_t FB = frame_batch(t->n_atoms * 16, t->n_frames);
+    // host-resident input: batches of 512, 1024, 2048 ... frames (each >= 32 chunks of 16 frames); the copy
+    // of batch k+1 overlaps the kernels of batch k, and only the first, small copy is exposed
+    int64_t cur = c.stage.lazy ? std::min<int64_t>(FB, 512) : FB;
+    if (c.sw.batch) cur = std::min<int64_t>(FB, c.sw.batch);   // experiments
+    void *d_Q, *d_flag;
+    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)FB * t->n_atoms * sizeof(QAtom), &d_Q));
+    AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), ctx->stream));
+    RdfFastArgs k = c.fa;       // the selected variant's arguments
+    k.Q = (const QAtom *)d_Q;
+    k.img_queue = 0;
+    k.img_defer = 0;
+    const double *d_fold = nullptr;
+    if (tri) {
+        AMOF_TRY(rdf_tri_args(c, k, &d_fold));
+    } else if (sel.img) {
+        const ParkedQueue pq = parked_queue(sel.img_share);
+        k.img_queue = pq.img_queue;
+        k.img_defer = pq.img_defer;
+    } else if (sel.zf) {
+        k.nb_hi = sel.zf_thr.nb_hi;
+        k.half_m_guard = sel.zf_thr.half_m_guard;
+    }
+    const size_t lds = tile_lds(nbins, k.img_queue, k.img_defer);
+    // rdf_tile_zf with slab culling runs from a plan of its steps (rdf_tile_kernel_fast, PLAN): the quantiser writes
+    // its slab table, rdf_tile_plan_kernel the records.  Not for tables beyond the plan kernel's LDS or plans beyond
+    // 256 MiB (systems far larger than a tile kernel's share).
+    const size_t plan_lds = (size_t)S * (QSLABS + 1) * sizeof(uint32_t) + c.ftiles.tiles.size() * TILE_PLAN_MAX_SUBS * sizeof(uint32_t);
+    const size_t plan_bytes = c.fpairs.size() * (size_t)FB * TILE_PLAN_MAX_SUBS * sizeof(uint4);
+    const bool plan_ok = sel.zf && sel.cull && !tri && !sel.img && !c.sw.noplan && plan_lds <= 64 * 1024 &&
+                         plan_bytes <= ((size_t)256 << 20);
+    void *d_slab = nullptr, *d_plan = nullptr;
+    if (plan_ok) {
+        AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)FB * S * (QSLABS + 1) * sizeof(uint32_t), &d_slab));
+        AMOF_TRY(ensure(ctx, SLOT_AUX9, plan_bytes, &d_plan));
+    }
+    int64_t launches = 0;
+    for (int64_t fb = 0; fb < t->n_frames; fb += cur, cur = std::min<int64_t>(2 * cur, FB)) {
+        const int64_t nf = std::min<int64_t>(cur, t->n_frames - fb);
+        AMOF_TRY(stager_need(c.stage, fb + nf));
+        AMOF_TRY(launch_quantize(ctx, c.stage.dev, (const double *)c.d_geom, (int)t->n_cells, (const int32_t *)c.d_perm,
+                                 (const int64_t *)c.d_spfirst, S, t->n_atoms, (int)fb, (int)nf, sel.axis, (QAtom *)d_Q,
+                                 (uint32_t *)d_slab, (int32_t *)d_flag, tri ? sel.tri.ax0 : -1, tri ? sel.tri.ax1 : -1, d_fold));
+        const TileChunks ch = tile_chunks(nf, (int64_t)c.fpairs.size(), c.sw);
+        k.f_base = (int32_t)fb;
+        k.nf = (int32_t)nf;
+        k.xcd_map = ch.xcd_map;
+        k.a.frames_per_chunk = ch.fpc;
+        k.n_chunks = ch.chunks;
+        k.nf_main = ch.nf_main;
+        dim3 grid((unsigned)c.fpairs.size(), (unsigned)(ch.chunks + ch.nf_tail));
+        const bool plan = plan_ok && ch.plan_fits;
+        k.plan = nullptr;
+        if (plan) {
+            TilePlanArgs pa;
+            pa.slab_start = (const uint32_t *)d_slab;
+            pa.tiles = (const Tile *)c.d_ftiles;
+            pa.pairs = (const int2 *)c.d_fpairs;
+            pa.sp_first = (const int64_t *)c.d_spfirst;
+            pa.fs = (const FrameScale *)c.d_fs;
+            pa.plan = (uint4 *)d_plan;
+            pa.S = S; pa.ntiles = (int32_t)c.ftiles.tiles.size(); pa.npairs = (int32_t)c.fpairs.size();
+            pa.nf = (int32_t)nf; pa.f_base = (int32_t)fb; pa.n_cells = (int32_t)t->n_cells;
+            AMOF_HIP_TRY(ctx, launch_lds(rdf_tile_plan_kernel, dim3((unsigned)nf), dim3(PLAN_THREADS), plan_lds, ctx->stream, pa));
+            k.plan = (const uint4 *)d_plan;
         }
-        timing_dom_end(ctx, 1);
+        if (launches == 0) timing_dom_begin(ctx, tri ? "rdf_tile_tri" : sel.img ? "rdf_tile_img" : sel.zf ? "rdf_tile_zf" : "rdf_tile");
+        AMOF_HIP_TRY(ctx, rdf_tile_launch(c, k, grid, lds, plan));
+        launches++;
+    }
+    timing_dom_end(ctx, launches);
+    return rdf_take_flag(c, d_flag);
+}
+
+// ---- exact kernels: canonical f64 arithmetic, every image ----
+static int rdf_exact_tier(RdfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    RdfArgs &a = c.a;
+    AMOF_TRY(stager_need(c.stage, c.t->n_frames));
+    unsigned chunks;
+    pick_chunks(c.t->n_frames, (int64_t)c.pairs.size(), 64, a.frames_per_chunk, chunks);
+    dim3 grid((unsigned)c.pairs.size(), chunks);
+    timing_dom_begin(ctx, "rdf_exact");
+    const hipError_t e = with_flags(c.geom.all_ortho, c.max_img > 0, [&](auto O, auto EXTRA) {
+        if (c.nbins <= AMOF_MAX_LDS_BINS)
+            return launch_lds(rdf_tile_kernel<O(), EXTRA()>, grid, dim3(RDF_TILE),
+                              3 * RDF_TILE * sizeof(double) + (size_t)c.nbins * sizeof(unsigned), ctx->stream, a);
+        hipLaunchKernelGGL((rdf_tile_kernel_global<O(), EXTRA()>), grid, dim3(RDF_TILE), 0, ctx->stream, a);
+        return hipGetLastError();
+    });
+    AMOF_HIP_TRY(ctx, e);
+    timing_dom_end(ctx, 1);
+    return AMOF_OK;
+}
+
+static int rdf_run(amof_ctx *ctx, const amof_traj *t, double rmax, int32_t nbins,
+                   unsigned long long *hist_dev, double *volume_sum)
+{
+    RdfCall c;
+    c.ctx = ctx;
+    c.t = t;
+    c.rmax = rmax;
+    c.nbins = nbins;
+    c.dr = rmax / nbins;
+    c.sw = RdfSwitches::from_env();
+    AMOF_TRY(rdf_prepare(c));
+    if (!c.pairs.empty() && t->n_frames > 0) {
+        std::vector<double> heights((size_t)t->n_cells * 3);
+        for (int64_t k = 0; k < t->n_cells; k++)
+            for (int x = 0; x < 3; x++) heights[(size_t)k * 3 + x] = c.geom.rec[(size_t)k * GEOM_STRIDE + 18 + x];
+        c.sel = rdf_select(t->cell, heights.data(), t->n_cells, t->pbc, t->n_species, t->n_atoms, c.tiles.nsp.data(), nbins, rmax,
+                           c.max_img, c.geom.all_ortho, c.sw);
+        const TriSelect &tri = c.sel.tri;
+        if (tri.ok && c.sw.debug)
+            fprintf(stderr, "rdf_tile_tri: code %d (near mode %d, x wrap %d) axes (%d, %d | %d) parked share %.4f tau %.5f c10 %.5f\n", tri.code,
+                    tri.code >= 10 ? 4 : tri.code % 5, tri.code >= 10 ? 2 : tri.code / 5, tri.ax0, tri.ax1, tri.axis, tri.share, tri.tau, tri.c10);
+        // a taken cell tier excludes range and tile; a tier that met far-away atoms hands over to the exact kernels
+        if (c.sel.tile()) {
+            AMOF_TRY(rdf_fast_prepare(c));
+            if (c.sel.cell) AMOF_TRY(rdf_cell_tier(c));
+            else if (c.sel.range) AMOF_TRY(rdf_range_tier(c));
+            else AMOF_TRY(rdf_tile_tier(c));
         }
+        if (!c.done) AMOF_TRY(rdf_exact_tier(c));
     }
     {
-        size_t total = (size_t)S * S * nbins;
+        size_t total = (size_t)t->n_species * t->n_species * nbins;
         int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
         hipLaunchKernelGGL(rdf_finalize_kernel, dim3(blocks), dim3(256), 0, ctx->stream,
-                           (const unsigned long long *)d_U, (const unsigned long long *)d_self,
-                           (const long long *)d_nsp, hist_dev, S, nbins);
+                           (const unsigned long long *)c.d_U, (const unsigned long long *)c.d_self,
+                           (const long long *)c.d_nsp, hist_dev, t->n_species, nbins);
         AMOF_HIP_TRY(ctx, hipGetLastError());
     }
     timing_end(ctx);
     // host metadata above lives on this stack frame: finish before returning
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    if (volume_sum) *volume_sum += geom.volume_sum;
+    if (volume_sum) *volume_sum += c.geom.volume_sum;
     return AMOF_OK;
 }
 

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "amof_internal.h"
+#include "rdf_select.h"
 
 namespace amof {
 namespace {
@@ -285,7 +286,7 @@ int vhd_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W
     const double csum = sqrt(c0[0] * c0[0] + c0[1] * c0[1] + c0[2] * c0[2]) + sqrt(c0[3] * c0[3] + c0[4] * c0[4] + c0[5] * c0[5]) +
                         sqrt(c0[6] * c0[6] + c0[7] * c0[7] + c0[8] * c0[8]);
     const double guard_m = csum * (1.0 / 2147483648.0) / dr + (double)nbins * 1e-12;
-    const double guard_f = (double)nbins * fast_guard_rel_rdf(geom, t->cell, t->n_cells) + guard_m;
+    const double guard_f = (double)nbins * fast_guard_rel_rdf(geom.all_ortho, t->cell, t->n_cells) + guard_m;
     bool tile = !global && !getenv("AMOF_VANHOVE_DISTINCT_EXACT") && t->n_cells == 1 && geom.all_ortho && max_img == 0 &&
                 t->pbc[0] && t->pbc[1] && t->pbc[2] && guard_f < 0.25;
     // origins per workgroup: enough workgroups to fill the GPU several times over
@@ -372,13 +373,9 @@ int vhd_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W
             const double sc = geom.rec[4 * c] * (1.0 / 4294967296.0) / dr;
             a.sc2[c] = (float)(sc * sc);
         }
-        const double half = 0.5 - guard_f;
-        float fh = (float)half;
-        if ((double)fh > half) fh = nextafterf(fh, -INFINITY);
-        float fnb = (float)((double)nbins + guard_f);
-        if ((double)fnb < (double)nbins + guard_f) fnb = nextafterf(fnb, INFINITY);
-        a.half_m_guard = fh;
-        a.nb_hi = fnb;
+        const GuardThresholds thr = guard_thresholds(nbins, guard_f);
+        a.half_m_guard = thr.half_m_guard;
+        a.nb_hi = thr.nb_hi;
         const size_t lds = VHD_THREADS * sizeof(uint4) + (size_t)S * nbins * sizeof(unsigned);
         AMOF_HIP_TRY(ctx, allow_max_lds((const void *)rdf_distinct_tile_kernel));
         int64_t launches = 0;

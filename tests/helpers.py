@@ -99,6 +99,30 @@ def random_gas(N, cell, numbers, seed, F=1):
     return PackedTrajectory(P, cell, numbers)
 
 
+def rdf_path_case(kind):
+    """(PackedTrajectory, rmax, nbins) of the cases whose RDF kernel family the GPU tests assert (tests/test_gpu_paths.py)
+    and the selection is pinned to on the CPU (tests/test_rdf_select_cpu.py)"""
+    z = zif4_frame()
+    if kind == "elongated":       # 2x1x4 supercell: slab culling along z is active (2 rmax < Lz)
+        return random_walk(replicate(z, (2, 1, 4)), 3, 0.05, 31, ortho=True), 6.0, 600
+    if kind == "elongated_tri":
+        return random_walk(replicate(z, (1, 1, 3)), 3, 0.05, 32), 5.0, 417
+    if kind == "npt":
+        return random_walk(replicate(z, (1, 1, 2)), 6, 0.05, 33, cell_jitter=0.01), 7.0, 700
+    if kind == "plain_img":       # the image-aware variant forced on an input that does not need it
+        return random_walk(replicate(z, (2, 1, 2)), 3, 0.05, 98, ortho=True), 7.0, 700
+    if kind == "cell_ortho":      # 3264 atoms, 30.8 x 30.8 x 55.3 A: cutoffs far below the cell size
+        return random_walk(replicate(z, (2, 2, 3)), 3, 0.08, 73, ortho=True), 5.0, 500
+    if kind == "thin_long":       # a slab: thin along x only (no 3-D cell list), many cutoffs long and wide
+        rng = np.random.default_rng(12)
+        cell = np.diag([19.0, 120.0, 150.0])
+        N = 20000
+        numbers = np.where(np.arange(N) % 3 == 0, 8, 1)
+        return PackedTrajectory(rng.uniform(0, 1, (2, N, 3)) @ cell, cell, numbers), 9.0, 900
+    assert kind == "cubicish"
+    return random_walk(z, 4, 0.05, 34), 7.7, 770
+
+
 def device_walk(device, reps, n_frames, sigma, seed, base=None):
     """Synthetic ZIF-4 supercell trajectory generated directly in HBM (torch, float64): Gaussian random walk,
     sigma per frame and axis, wrapped each frame into the constant orthorhombic cell.  The headline workload of

@@ -30,15 +30,7 @@ class _env(object):
                 os.environ[k] = v
 
 
-def _traj(kind):
-    z = H.zif4_frame()
-    if kind == "elongated":       # 2x1x4 supercell: slab culling along z is active (2 rmax < Lz)
-        return H.random_walk(H.replicate(z, (2, 1, 4)), 3, 0.05, 31, ortho=True), 6.0, 600
-    if kind == "elongated_tri":
-        return H.random_walk(H.replicate(z, (1, 1, 3)), 3, 0.05, 32), 5.0, 417
-    if kind == "npt":
-        return H.random_walk(H.replicate(z, (1, 1, 2)), 6, 0.05, 33, cell_jitter=0.01), 7.0, 700
-    return H.random_walk(z, 4, 0.05, 34), 7.7, 770
+_traj = H.rdf_path_case       # (shared with the CPU pin of the selection, tests/test_rdf_select_cpu.py)
 
 
 @pytest.mark.parametrize("kind", ["elongated", "elongated_tri", "npt", "cubicish"])
@@ -336,6 +328,28 @@ def test_far_away_atoms_fall_back(hip_ctx):
     assert np.array_equal(ab, ar) and np.array_equal(hb, hr)
 
 
+def test_far_atom_hands_every_rdf_tier_over_to_the_exact_kernels(hip_ctx):
+    """one atom of the LAST frame 2e5 cell lengths away: the tile, cell-list and range tiers each see the quantiser's flag
+    only after earlier frame batches have added into U (AMOF_RDF_BATCH=1), clear it and hand over -- a missing clear
+    shows as doubled counts.  The unshifted run proves that the tier under test is the one that runs."""
+    packed, rmax, nb = H.rdf_path_case("cell_ortho")        # diagonal cell, one cell record, three frames
+    assert packed.cell.shape[0] == 1 and packed.pos.shape[0] == 3
+    pos = packed.pos.copy()
+    pos[-1, 0, 0] += 2.0e5 * packed.cell[0, 0, 0]
+    far = PackedTrajectory(pos, packed.cell, packed.numbers)
+    kinds, sp = H.species_of(packed.numbers)
+    ref, _ = clib.rdf_hist(far.pos, far.cell, sp, len(kinds), rmax, nb)
+    for env, path in (({"AMOF_RDF_NOCELL": "1", "AMOF_RDF_NORANGE": "1", "AMOF_RDF_BATCH": "1"}, "rdf_tile_zf"),
+                      ({"AMOF_RDF_FORCE_CELL": "1", "AMOF_RDF_BATCH": "1"}, "rdf_cell"),
+                      ({"AMOF_RDF_FORCE_RANGE": "1", "AMOF_RDF_NOCELL": "1"}, "rdf_range")):
+        with _env(**env):
+            hip_ctx.rdf_accumulate(packed, rmax, nb)
+            assert hip_ctx.last_path() == path, (env, hip_ctx.last_path())
+            got, _, _ = hip_ctx.rdf_accumulate(far, rmax, nb)
+            assert hip_ctx.last_path() == "rdf_exact", (env, hip_ctx.last_path())
+        assert np.array_equal(got, ref), (path, int(got.sum()), int(ref.sum()))
+
+
 def test_bad_by_cn(hip_ctx):
     from amof_amd.bad import Bad, BadByCn
     packed = H.random_walk(H.replicate(H.zif4_frame(), (1, 1, 2)), 6, 0.25, 41)     # hot: mixed coordination numbers
@@ -617,7 +631,7 @@ def test_rdf_sheared_cell_default_cutoff_counts_images(hip_ctx, eps, jitter):
 
 def test_rdf_image_aware_variant_on_a_plain_case(hip_ctx):
     # the image-aware variant forced on an input that does not need it: same integers as the plain tile kernel
-    packed = H.random_walk(H.replicate(H.zif4_frame(), (2, 1, 2)), 3, 0.05, 98, ortho=True)
+    packed = H.rdf_path_case("plain_img")[0]
     with _env(AMOF_RDF_NOCELL="1", AMOF_RDF_NORANGE="1"):
         plain, _, _ = hip_ctx.rdf_accumulate(packed, 7.0, 700)
         assert hip_ctx.last_path() in ("rdf_tile", "rdf_tile_zf")
@@ -1085,11 +1099,7 @@ def test_rdf_cell_kernel_frame_chunks(hip_ctx, frames):
 def test_rdf_range_kernel_is_what_a_thin_long_cell_selects(hip_ctx):
     """housekeeping (round-3 review): the 2-level range kernel is not dead code -- a slab-shaped cell, too thin along ONE axis
     for five cells of rmax / 2 (so no 3-D cell list) but many cutoffs long and wide, selects it WITHOUT any switch; the 1-D slab list beside it"""
-    rng = np.random.default_rng(12)
-    cell = np.diag([19.0, 120.0, 150.0])            # a slab: thin along x only
-    N = 20000
-    numbers = np.where(np.arange(N) % 3 == 0, 8, 1)
-    packed = PackedTrajectory(rng.uniform(0, 1, (2, N, 3)) @ cell, cell, numbers)
+    packed = H.rdf_path_case("thin_long")[0]        # a slab: thin along x only
     kinds, sp = H.species_of(packed.numbers)
     got, _, _ = hip_ctx.rdf_accumulate(packed, 9.0, 900)
     assert hip_ctx.last_path() == "rdf_range"
