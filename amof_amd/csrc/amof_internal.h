@@ -179,6 +179,13 @@ static hipError_t with_count(int v, F &&f)
     if constexpr (N == 1) return f(Count<0>{});
     else return v >= N - 1 ? f(Count<N - 1>{}) : with_count<N - 1>(v, f);
 }
+// v out of a list of values as a Count tag (a value that is not in the list takes the last)
+template <int V0, int... Vs, typename F>
+static hipError_t with_value(int v, F &&f)
+{
+    if constexpr (sizeof...(Vs) == 0) return f(Count<V0>{});
+    else return v == V0 ? f(Count<V0>{}) : with_value<Vs...>(v, f);
+}
 // allow_max_lds + launch + the launch's own error (kernels without dynamic LDS take lds = 0: the cap is then a no-op)
 // FROM_ZERO: allow_max_lds_from_zero
 template <bool FROM_ZERO = false, typename Kernel, typename... Args>

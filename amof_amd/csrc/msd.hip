@@ -5,28 +5,39 @@
 // (amof/msd.py:185-205) and the centre-of-mass / unwrap preamble of
 // amof/msd.py:222-237.
 //
-// Data flow (all float64):
-//   frame-major pos[F][N][3]  --com_kernel-->      com[F][3]
-//   pos, com  --delta_transpose_kernel-->          D_T[3N][Fp]   wrapped
-//       frame-to-frame displacements, TRANSPOSED to atom-major through an LDS
-//       tile so that a column (one coordinate of one atom over time) is
-//       contiguous;  Fp = F rounded up to 32
-//   D_T --msd_group_kernel-->  partial[group][W]: per column the whole time
-//       series sits in LDS (F*8 bytes), is prefix-summed in place (running
-//       position u) and every window m reduces sum_k (u[k+m]-u[k])^2 from LDS.
-//   partial --msd_reduce_kernel--> sumsq[S][W]  (fixed order: deterministic)
-// HBM traffic: pos read twice (com + delta), D_T written once and read once.
+// All float64.  Which form answers a call is decided on the host, in one place: msd_select.h (msd_select -> MsdPlan; its
+// rules are pinned on the CPU by tests/test_msd_select_cpu.py).  The forms, in the order they are tried:
 //
-// Round 4, diagonal cells (the 2-pass form): the centre of mass is folded into the transposition.  wrap() is a shift by
-// whole cell vectors, so  wrap((p_k - c_k) - (p_k-1 - c_k-1)) = wrap(wrap(p_k - p_k-1) - (c_k - c_k-1)):  pass 1 reads pos
-// ONCE, writes the wrapped RAW differences to D_T and the mass-weighted coordinate sums of its 64-atom tile per frame
-// (cpart, 1.5 % of the traffic; summed in fixed order by com_finish_kernel into dc[3][Fp] = c_k - c_k-1); the window
-// kernels finish the columns.  Wrapping again changes an entry only when the raw difference lies within |dc| of half the
-// cell (an atom that moves half a box in one frame): for every other column  sum_j wrap(raw_j - dc_j) = U_raw[k] - C[k],
-// C[k] = c_k (up to a constant that cancels in every window) -- the kernels scan the RAW column and subtract C[k] where an entry enters the registers (no extra
-// pass); the scan's first loop checks |raw| against  L/2 - max|dc|,  and a column with such an entry is loaded again,
-// corrected entry by entry with the wrap arithmetic (dcom_column) and scanned once more (C replaced by zeros).
-// pos read once, D_T written once and read once.
+// 1. Fused (windows w d with d >= 16, W <= 32, diagonal cells, the whole system, centre of mass removed, no unwrap): no
+//    transposed copy at all -- msd_seg_kernel, seg_scan_kernel, msd_fused[_general]_kernel, msd_colreduce_kernel; see the
+//    comment in front of them.  pos is read twice.  Pass 2 raises a flag when a raw difference could wrap again under the
+//    centre-of-mass step; the call is then answered by the forms below.
+//
+// Every other form works on wrapped frame-to-frame steps TRANSPOSED to atom-major columns D_T[3N][Fp] (Fp = F rounded up
+// to 32; msd_columns.h: build_step_columns), so that one coordinate of one atom over time is contiguous:
+//
+// 2. 2-pass fold (diagonal cells, the whole system, the series LDS-resident): the centre of mass is folded into the
+//    transposition.  wrap() is a shift by whole cell vectors, so
+//    wrap((p_k - c_k) - (p_k-1 - c_k-1)) = wrap(wrap(p_k - p_k-1) - (c_k - c_k-1)):  pass 1 reads pos ONCE, writes the wrapped
+//    RAW differences to D_T and the mass-weighted coordinate sums of its 64-atom tile per frame (cpart, 1.5 % of the traffic;
+//    summed in fixed order by com_finish_kernel into dc[3][Fp] = c_k - c_k-1); the window kernels finish the columns.
+//    Wrapping again changes an entry only when the raw difference lies within |dc| of half the cell (an atom that moves half
+//    a box in one frame): for every other column  sum_j wrap(raw_j - dc_j) = U_raw[k] - C[k],  C[k] = c_k (up to a constant
+//    that cancels in every window) -- the kernels scan the RAW column and subtract C[k] where an entry enters the registers
+//    (no extra pass); the scan's first loop checks |raw| against  L/2 - max|dc|,  and a column with such an entry is loaded
+//    again, corrected entry by entry with the wrap arithmetic (dcom_column) and scanned once more (C replaced by zeros).
+//    pos read once, D_T written once and read once.
+// 3. 3-pass:  pos --com_kernel--> com[F][3];  pos, com --delta_transpose_kernel--> D_T.  pos read twice.
+// 4. Unwrap: every column is transposed and scanned from frame 0's positions, the centre of mass comes from the unwrapped
+//    columns and delta_T_kernel re-forms the wrapped steps of the call's atoms.
+//
+//    On D_T, one workgroup per group of <= MSD_GROUP atoms of one species holds a whole column in LDS (F * 8 bytes),
+//    prefix-sums it in place (running position u) and reduces sum_k (u[k+m]-u[k])^2 for its windows: msd_stream_kernel
+//    (windows w d, 64 <= d <= 256), msd_comb[_db | _hi]_kernel (windows w d), msd_group_kernel (any windows) -> partial
+//    [group][W];  partial --msd_reduce_kernel--> sumsq[S][W]  (fixed order: deterministic).
+//
+// 5. Long series (F + W beyond the LDS budget): the columns of form 3 or 4 are prefix-summed in global memory
+//    (scan_column_kernel) and the windows reduced from there, msd_comb_global_kernel (windows w d) or msd_group_kernel_global.
 #include <math.h>
 
 #include <algorithm>
@@ -35,10 +46,9 @@
 
 #include "amof_internal.h"
 #include "msd_columns.h"
+#include "msd_select.h"
 
 namespace amof {
-
-constexpr int MSD_GROUP = 4;  // atoms per msd workgroup
 
 // The same sum with the four row totals combined by DPP row broadcasts (row_bcast:15 into rows 1 and 3, row_bcast:31 into
 // rows 2 and 3) instead of readlanes: no scalar round trip (a v_readlane of a value a vector instruction has just written
@@ -180,13 +190,6 @@ __device__ __forceinline__ void scan_column(const Dcom &dc, int comp, double *u,
         __syncthreads();
     }
 }
-
-struct MsdGroup {
-    int32_t start;    // into perm
-    int32_t count;    // atoms
-    int32_t species;
-    int32_t _pad;
-};
 
 // one workgroup = one group of <= MSD_GROUP atoms of one species.
 // WREG > 0: at most WREG windows, per-thread partial sums stay in registers across all the
@@ -528,8 +531,6 @@ __device__ __forceinline__ bool reg_scan(double *u, int F, int chunk, double *wt
     __syncthreads();
     return evt;
 }
-constexpr int STREAM_CH = 42;       // register scan: chunks of up to 42 entries per thread (F <= 41 T: 5248 frames at 128 threads)
-
 template <int L, int T, bool FOLD>
 __global__ __launch_bounds__(T, 2) void msd_stream_kernel(const double *__restrict__ DT, int64_t Fp, int F,
                                                        const int32_t *__restrict__ perm,
@@ -787,14 +788,7 @@ __global__ __launch_bounds__(MSD_THREADS) void msd_reduce_kernel(const double *_
 // cell; pass 2 checks every raw difference and raises a flag, and the call is then answered by the transposed forms.
 // Shape of pass 2's workgroups (256 threads, <= 128 VGPRs, 10 kB of LDS): what ONE retiring workgroup of the RDF tile
 // kernel frees on a CU, so that they are placed beside a running RDF launch (second lane: amof_amd/_lazy.py).
-constexpr int FU_EB = 5;          // comb entries (segments) per thread
-#ifndef AMOF_FU_CPW
-#define AMOF_FU_CPW 24
-#endif
-// columns (= 8 atoms) per workgroup; whole 128-byte lines measured slower: 32 (5-wave workgroups) 0.64, 16 (2.5-wave
-// workgroups) 0.57 against 0.47 ms (-DAMOF_FU_CPW=..: experiments)
-constexpr int FU_CPW = AMOF_FU_CPW;
-constexpr int FU_MAX_TPC = 21;    // threads per column: nq <= 105 (workgroups of <= 512 threads: 168 registers per lane)
+// (FU_EB segments per thread, FU_CPW columns per workgroup, at most FU_MAX_TPC threads per column: msd_select.h)
 
 // TPL atoms per lane (atoms a, a + 64, ...: a "tile" of cpart is 64 TPL atoms): their m p are added in the lane before the
 // wave sum -- the three double sums over the 64 lanes are ~60 of the ~130 instructions of a frame at TPL = 1.
@@ -1311,123 +1305,295 @@ __global__ __launch_bounds__(MSD_THREADS) void direct_reduce_kernel(const double
 
 using namespace amof;
 
-
-// ---- host side of the fused form ----
+// ---- host side: the call record, one function per form (what runs when: msd_select.h) ----
 namespace {
 
-struct FusedDims {
-    int d = 0, nq = 0, TPC = 0, L = 0;
-    int64_t ncols = 0, stride = 0;      // columns of the atom range; row stride of RS / colpart (columns padded to 32)
-    size_t lds = 0;
-    unsigned threads = 0;
+// one window-MSD call: arguments, host tables, the device pointers of its single upload pack, the plan
+struct MsdCall {
+    amof_ctx *ctx;
+    const amof_traj *t;
+    const int32_t *windows;
+    int W;
+    bool unwrap, remove_com;
+    int64_t a0, a1;             // atom range
+    const double *com_ext;      // optional precomputed centre of mass (device [F][3])
+    HostGeom hg;
+    std::vector<double> grec;   // msd_geom_records
+    SpeciesGroups sg;
+    double total_mass = 0.0;
+    UploadPack pk;
+    const double *pos_dev = nullptr, *d_geom = nullptr, *d_mass = nullptr;
+    const int32_t *d_perm = nullptr, *d_win = nullptr, *d_sgf = nullptr, *d_sfa = nullptr;
+    const MsdGroup *d_groups = nullptr;
+    MsdPlan plan;
+    double *d_DT = nullptr;     // step columns (msd_columns_tier)
+    Dcom dcom;                  // what the window kernels need to finish them
+    double *d_out = nullptr;    // [S][W]
+    int64_t F() const { return t->n_frames; }
+    int64_t Fp() const { return (t->n_frames + 31) / 32 * 32; }
+    unsigned n_groups() const { return (unsigned)sg.groups.size(); }
 };
 
-// does the fused form take windows m_w = w * comb_d, w = 0 .. W-1, over F frames?
-bool fused_dims(int64_t F, int W, int comb_d, int64_t a0, int64_t a1, FusedDims &fd)
+// what every window-MSD entry point asks of its arguments
+int msd_check(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W, int64_t a0, int64_t a1, bool need_masses)
 {
-    if (comb_d < 16 || W < 2 || W > 32 || F < 64 || a1 <= a0) return false;
-    fd.d = comb_d;
-    fd.nq = (int)((F + comb_d - 1) / comb_d);
-    fd.TPC = (fd.nq + FU_EB - 1) / FU_EB;
-    if (fd.TPC > FU_MAX_TPC) return false;
-    fd.L = W <= 8 ? 7 : W <= 16 ? 15 : W <= 25 ? 24 : 31;
-    fd.ncols = 3 * (a1 - a0);
-    fd.stride = (fd.ncols + 31) / 32 * 32;
-    fd.threads = (unsigned)((fd.TPC * FU_CPW + 63) / 64 * 64);
-    fd.lds = (size_t)2 * (fd.L + fd.TPC * FU_EB) * FU_CPW * sizeof(double);
-    return true;
+    AMOF_TRY(validate_traj(ctx, t, need_masses));
+    const int64_t N = t->n_atoms, F = t->n_frames;
+    if (W < 0 || (W > 0 && !windows)) return fail(ctx, AMOF_EINVAL, "NULL argument");
+    if (a0 < 0 || a1 > N || a0 > a1) return fail(ctx, AMOF_EINVAL, "bad atom range");
+    for (int w = 0; w < W; w++)
+        if (windows[w] < 0 || (F > 0 && windows[w] >= F)) return fail(ctx, AMOF_EINVAL, "window %d out of range", windows[w]);
+    return AMOF_OK;
 }
 
+// Host tables of the call -- geometry records with the FULL inverse (wrap_positions semantics), the species-sorted groups
+// of the selected atoms, masses -- as the pieces of ONE upload (a copy costs ~5 us of queue time however small: six of them
+// were a tenth of the pipeline); msd_upload sends it
+int msd_tables(MsdCall &c)
+{
+    const amof_traj *t = c.t;
+    AMOF_TRY(build_geometry(c.ctx, t, c.hg));
+    msd_geom_records(t, c.hg, c.grec);
+    species_groups(t->species, c.a0, c.a1, t->n_species, MSD_GROUP, c.sg);
+    if (c.remove_com)
+        for (int64_t i = 0; i < t->n_atoms; i++) c.total_mass += t->masses[i];
+    c.pk.add(c.grec.data(), c.grec.size() * sizeof(double));
+    c.pk.add(c.sg.perm.data(), c.sg.perm.size() * sizeof(int32_t));
+    c.pk.add(c.sg.groups.data(), c.sg.groups.size() * sizeof(MsdGroup));
+    c.pk.add(c.windows, (size_t)c.W * sizeof(int32_t));
+    c.pk.add(c.sg.group_first.data(), c.sg.group_first.size() * sizeof(int32_t));
+    c.pk.add(c.sg.atom_first.data(), c.sg.atom_first.size() * sizeof(int32_t));
+    if (c.remove_com) c.pk.add(t->masses, (size_t)t->n_atoms * sizeof(double));
+    return AMOF_OK;
+}
+
+int msd_upload(MsdCall &c)
+{
+    AMOF_TRY(upload_pack(c.ctx, SLOT_GEOM, c.pk));
+    c.d_geom = c.pk.ptr<double>(0); c.d_perm = c.pk.ptr<int32_t>(1); c.d_groups = c.pk.ptr<MsdGroup>(2);
+    c.d_win = c.pk.ptr<int32_t>(3); c.d_sgf = c.pk.ptr<int32_t>(4); c.d_sfa = c.pk.ptr<int32_t>(5);
+    c.d_mass = c.remove_com ? c.pk.ptr<double>(6) : nullptr;
+    return AMOF_OK;
+}
+
+// SLOT_AUX4 of the fused and the 2-pass forms: dc [3][Fp] | C [4][Fp] (row 3 = zeros) | max |dc| [3] (bits) | flag words
+// (dcmax and the flag words sit next to each other behind C: one fill of `zero_bytes` clears them)
+struct DcomScratch {
+    double *dcT, *CT;
+    unsigned long long *dcmax;
+    int32_t *flag;
+    static constexpr size_t zero_bytes = 3 * sizeof(unsigned long long) + 4 * sizeof(int32_t);
+    static size_t bytes(int64_t Fp) { return (size_t)7 * Fp * sizeof(double) + 64; }
+};
+DcomScratch dcom_carve(void *base, int64_t Fp)
+{
+    DcomScratch s;
+    s.dcT = (double *)base;
+    s.CT = s.dcT + (size_t)3 * Fp;
+    s.dcmax = (unsigned long long *)(s.CT + (size_t)4 * Fp);
+    s.flag = (int32_t *)(s.dcmax + 3);
+    return s;
+}
+Dcom dcom_of(const amof_traj *t, const double *d_geom, int64_t Fp, const DcomScratch *s)
+{
+    Dcom dc = {s ? s->dcT : nullptr, s ? s->CT : nullptr, s ? s->dcmax : nullptr, d_geom, {0.0, 0.0, 0.0}, Fp, (int32_t)t->n_cells, 0};
+    if (s) wrap_half_lengths(t, dc.lhalf);
+    return dc;
+}
+
+// ---- the fused form ----
 // pass 1 over the atoms [a0, a1): RS (SLOT_AUX7) and the tile sums, added up into csum[F][3] (device, overwritten)
 int fused_pass1(amof_ctx *ctx, const amof_traj *t, const double *pos_dev, const double *d_geom, const double *d_mass, int64_t a0,
                 int64_t a1, const FusedDims &fd, double *d_csum, double **d_RS_out)
 {
     const int64_t N = t->n_atoms, F = t->n_frames;
-    // four atoms per lane where that still gives every SIMD a wave, two down to a quarter of that, else one (measured on the
-    // headline shape and its eighth, profiles/r05/msd_fused_experiments.txt: 4 x 2 0.248 / 0.092, 2 x 4 0.256 / 0.067,
-    // 1 x 4 0.273 / 0.073 ms)
-    const int64_t work = (a1 - a0) * (int64_t)fd.nq;
-    int tpl = work >= (int64_t)4 * 64 * 1024 ? 4 : work >= (int64_t)2 * 64 * 256 ? 2 : 1, useg = 4;
-    const int ntiles = (int)((a1 - a0 + 64 * tpl - 1) / (64 * tpl));
+    const SegShape sh = seg_shape(a1 - a0, fd.nq);
     void *d_RS, *d_cpart;
     AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)fd.nq * (size_t)fd.stride * sizeof(double), &d_RS));
-    AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)ntiles * (size_t)F * 3 * sizeof(double), &d_cpart));
-    const dim3 grid((unsigned)ntiles, (unsigned)((fd.nq + 3) / 4));
-#define AMOF_SEG(T, UU)                                                                                                     \
-    do {                                                                                                                    \
-        if (t->n_cells == 1)                                                                                                \
-            hipLaunchKernelGGL((msd_seg_kernel<T, UU, true>), grid, dim3(256), 0, ctx->stream, pos_dev, d_geom, (int)t->n_cells, N, \
-                               (int)F, fd.d, fd.nq, a0, a1, d_mass, (double *)d_RS, fd.stride, (double *)d_cpart);          \
-        else                                                                                                                \
-            hipLaunchKernelGGL((msd_seg_kernel<T, UU, false>), grid, dim3(256), 0, ctx->stream, pos_dev, d_geom, (int)t->n_cells, N, \
-                               (int)F, fd.d, fd.nq, a0, a1, d_mass, (double *)d_RS, fd.stride, (double *)d_cpart);          \
-    } while (0)
-    if (tpl == 4) AMOF_SEG(4, 2);
-    else if (tpl == 2) AMOF_SEG(2, 4);
-    else if (useg == 8) AMOF_SEG(1, 8);
-    else AMOF_SEG(1, 4);
-#undef AMOF_SEG
-    AMOF_HIP_TRY(ctx, hipGetLastError());
+    AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)sh.ntiles * (size_t)F * 3 * sizeof(double), &d_cpart));
+    const dim3 grid((unsigned)sh.ntiles, (unsigned)((fd.nq + 3) / 4));
+    const hipError_t e = with_value<4, 2, 1>(sh.tpl, [&](auto T) {
+        constexpr int TPL = decltype(T)::value, U = TPL == 4 ? 2 : 4;
+        return with_flag(t->n_cells == 1, [&](auto C) {
+            return launch_lds(msd_seg_kernel<TPL, U, decltype(C)::value>, grid, dim3(256), 0, ctx->stream, pos_dev, d_geom,
+                              (int)t->n_cells, N, (int)F, fd.d, fd.nq, a0, a1, d_mass, (double *)d_RS, fd.stride, (double *)d_cpart);
+        });
+    });
+    AMOF_HIP_TRY(ctx, e);
     hipLaunchKernelGGL(com_tiles_kernel, dim3((unsigned)((F + COMF_FRAMES - 1) / COMF_FRAMES)), dim3(MSD_THREADS), 0, ctx->stream,
-                       (const double *)d_cpart, ntiles, (int)F, d_csum);
+                       (const double *)d_cpart, sh.ntiles, (int)F, d_csum);
     AMOF_HIP_TRY(ctx, hipGetLastError());
     *d_RS_out = (double *)d_RS;
     return AMOF_OK;
 }
 
-// centre of mass from the complete csum, prefix of RS, pass 2, column sums -> d_out[S][W]; *d_flag_out: device word that is
-// non-zero when a raw difference could wrap again under the centre-of-mass step (the caller reads it back and then answers
-// the call with the transposed forms)
+// centre of mass from the complete csum, prefix of RS, pass 2 (general: not the lean kernel), column sums -> d_out[S][W];
+// *d_flag_out: device word that is non-zero when a raw difference could wrap again under the centre-of-mass step (the
+// caller reads it back and then answers the call with the transposed forms)
 int fused_pass2(amof_ctx *ctx, const amof_traj *t, const double *pos_dev, const double *d_geom, int64_t a0, const FusedDims &fd,
-                int W, const double *d_csum, double total_mass, double *d_RS, const int32_t *d_perm, const int32_t *d_spfirst,
-                double *d_out, int32_t **d_flag_out)
+                bool general, int W, const double *d_csum, double total_mass, double *d_RS, const int32_t *d_perm,
+                const int32_t *d_spfirst, double *d_out, int32_t **d_flag_out)
 {
     const int64_t N = t->n_atoms, F = t->n_frames;
     const int S = t->n_species;
     const int64_t Fp = (F + 31) / 32 * 32;
-    void *d_dcT, *d_colpart, *d_flag;
-    AMOF_TRY(ensure(ctx, SLOT_AUX4, (size_t)7 * Fp * sizeof(double) + 64, &d_dcT));
+    void *d_aux, *d_colpart;
+    AMOF_TRY(ensure(ctx, SLOT_AUX4, DcomScratch::bytes(Fp), &d_aux));
     AMOF_TRY(ensure(ctx, SLOT_AUX8, (size_t)(fd.L + 1) * (size_t)fd.stride * sizeof(double), &d_colpart));
-    double *d_CT = (double *)d_dcT + (size_t)3 * Fp;
-    unsigned long long *d_dcmax = (unsigned long long *)(d_CT + (size_t)4 * Fp);
-    d_flag = d_dcmax + 3;
-    // (dcmax and the flag word sit next to each other behind C: one fill)
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_dcmax, 0, 3 * sizeof(unsigned long long) + 4 * sizeof(int32_t), ctx->stream));
+    const DcomScratch sc = dcom_carve(d_aux, Fp);
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(sc.dcmax, 0, DcomScratch::zero_bytes, ctx->stream));
     hipLaunchKernelGGL(com_steps_kernel, dim3((unsigned)((F + MSD_THREADS - 1) / MSD_THREADS)), dim3(MSD_THREADS), 0, ctx->stream,
-                       d_csum, (int)F, Fp, total_mass, (double *)d_dcT, d_CT, d_dcmax);
+                       d_csum, (int)F, Fp, total_mass, sc.dcT, sc.CT, sc.dcmax);
     hipLaunchKernelGGL(seg_scan_kernel, dim3((unsigned)((fd.ncols + 255) / 256)), dim3(256), 0, ctx->stream, d_RS, fd.nq, fd.ncols,
                        fd.stride);
     AMOF_HIP_TRY(ctx, hipGetLastError());
-    Dcom dc = {(const double *)d_dcT, d_CT, d_dcmax, d_geom, {0.0, 0.0, 0.0}, Fp, (int32_t)t->n_cells, 0};
-    for (int c = 0; c < 3; c++) {
-        double lmin = 1e300;
-        for (int64_t k = 0; k < t->n_cells; k++) lmin = std::min(lmin, fabs(t->cell[9 * k + 4 * c]));
-        dc.lhalf[c] = t->pbc[c] ? lmin * (0.5 - 1e-6) : 1e300;       // (a non-periodic axis never wraps)
-    }
+    const Dcom dc = dcom_of(t, d_geom, Fp, &sc);
     timing_dom_begin(ctx, "msd_fused");
-    auto go = [&](auto kern) -> hipError_t {
-        hipError_t e = allow_max_lds((const void *)kern);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((unsigned)((fd.ncols + FU_CPW - 1) / FU_CPW)), dim3(fd.threads), fd.lds, ctx->stream, pos_dev,
-                           (const double *)d_RS, fd.stride, d_geom, (int)t->n_cells, dc, N, (int)F, fd.d, fd.nq, fd.TPC, a0, fd.ncols,
-                           (double *)d_colpart, fd.stride, W, (int32_t *)d_flag);
-        return hipGetLastError();
+    auto go = [&](auto kern) {
+        return launch_lds(kern, dim3((unsigned)((fd.ncols + FU_CPW - 1) / FU_CPW)), dim3(fd.threads), fd.lds, ctx->stream, pos_dev,
+                          (const double *)d_RS, fd.stride, d_geom, (int)t->n_cells, dc, N, (int)F, fd.d, fd.nq, fd.TPC, a0, fd.ncols,
+                          (double *)d_colpart, fd.stride, W, sc.flag);
     };
-    // lean kernel: every thread owns EB whole segments
-    const bool general = fd.nq % FU_EB != 0 || F % fd.d != 0 || getenv("AMOF_MSD_FUSED_GENERAL");
-    const bool constcell = t->n_cells == 1;
-    hipError_t e;
-#define AMOF_FUSED_L(LL)                                                                                                        \
-    (general ? (constcell ? go(msd_fused_general_kernel<LL, 512, true>) : go(msd_fused_general_kernel<LL, 512, false>))         \
-             : (constcell ? go(msd_fused_kernel<LL, 512, true, 1>) : go(msd_fused_kernel<LL, 512, false, 1>)))
-    e = fd.L == 7 ? AMOF_FUSED_L(7) : fd.L == 15 ? AMOF_FUSED_L(15) : fd.L == 24 ? AMOF_FUSED_L(24) : AMOF_FUSED_L(31);
-#undef AMOF_FUSED_L
+    const hipError_t e = with_value<7, 15, 24, 31>(fd.L, [&](auto L) {
+        return with_flag(t->n_cells == 1, [&](auto C) {
+            constexpr int LL = decltype(L)::value;
+            constexpr bool CONSTCELL = decltype(C)::value;
+            return general ? go(msd_fused_general_kernel<LL, 512, CONSTCELL>) : go(msd_fused_kernel<LL, 512, CONSTCELL, 1>);
+        });
+    });
     AMOF_HIP_TRY(ctx, e);
     timing_dom_end(ctx, 1);
     hipLaunchKernelGGL(msd_colreduce_kernel, dim3((unsigned)(S * W)), dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_colpart,
                        fd.stride, d_perm, d_spfirst, a0, W, d_out);
     AMOF_HIP_TRY(ctx, hipGetLastError());
-    *d_flag_out = (int32_t *)d_flag;
+    *d_flag_out = sc.flag;
+    return AMOF_OK;
+}
+
+// pass 1, pass 2 and the flag; answered = false: an entry could wrap again under the centre-of-mass step -- handed over to
+// the transposed forms
+int msd_fused_tier(MsdCall &c, bool &answered)
+{
+    amof_ctx *ctx = c.ctx;
+    void *d_csum;
+    double *d_RS = nullptr;
+    int32_t *d_flag = nullptr, evt = 0;
+    AMOF_TRY(ensure(ctx, SLOT_AUX2, (size_t)c.F() * 3 * sizeof(double), &d_csum));
+    AMOF_TRY(fused_pass1(ctx, c.t, c.pos_dev, c.d_geom, c.d_mass, c.a0, c.a1, c.plan.fd, (double *)d_csum, &d_RS));
+    AMOF_TRY(fused_pass2(ctx, c.t, c.pos_dev, c.d_geom, c.a0, c.plan.fd, c.plan.fused_general, c.W, (const double *)d_csum,
+                         c.total_mass, d_RS, c.d_perm, c.d_sfa, c.d_out, &d_flag));
+    AMOF_TRY(fetch(ctx, &evt, d_flag, sizeof evt));
+    AMOF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (not sync_stream: the staged tables stay where they are)
+    answered = evt == 0;
+    return AMOF_OK;
+}
+
+// ---- the transposed forms ----
+// the wrapped step columns in c.d_DT and, 2-pass fold, what the window kernels need to finish them in c.dcom
+int msd_columns_tier(MsdCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const int64_t N = t->n_atoms, F = c.F(), Fp = c.Fp();
+    const ColumnsIn in = {c.pos_dev, c.d_geom, c.hg.all_ortho, c.d_mass, c.total_mass, c.unwrap, c.remove_com, c.com_ext};
+    c.dcom = dcom_of(t, c.d_geom, Fp, nullptr);
+    if (c.plan.columns != MSD_COL_FOLD) return build_step_columns(ctx, t, in, c.a0, c.a1, &c.d_DT);
+    const int ntiles = (int)((N + TR_TA - 1) / TR_TA);
+    void *d_cpart, *d_aux;
+    AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)ntiles * (size_t)F * 3 * sizeof(double), &d_cpart));
+    AMOF_TRY(ensure(ctx, SLOT_AUX4, DcomScratch::bytes(Fp), &d_aux));
+    const DcomScratch sc = dcom_carve(d_aux, Fp);
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(sc.dcmax, 0, DcomScratch::zero_bytes, ctx->stream));
+    AMOF_TRY(build_step_columns(ctx, t, in, 0, N, &c.d_DT, (double *)d_cpart));
+    hipLaunchKernelGGL(com_finish_kernel, dim3((unsigned)((F + COMF_FRAMES - 1) / COMF_FRAMES)), dim3(MSD_THREADS), 0, ctx->stream,
+                       (const double *)d_cpart, ntiles, (int)F, Fp, c.total_mass, sc.dcT, sc.CT, sc.dcmax);
+    AMOF_HIP_TRY(ctx, hipGetLastError());
+    c.dcom = dcom_of(t, c.d_geom, Fp, &sc);
+    return AMOF_OK;
+}
+
+// LDS-resident series: stream, comb (with its further passes of 32 windows) or group -> d_part[group][W]
+int msd_window_tier(MsdCall &c, double *d_part)
+{
+    const MsdPlan &p = c.plan;
+    const hipStream_t stream = c.ctx->stream;
+    const int64_t Fp = c.Fp();
+    const int F = (int)c.F(), W = c.W;
+    const dim3 grid(c.n_groups()), block(MSD_THREADS);
+    const double *DT = c.d_DT;
+    hipError_t e = hipSuccess;
+    if (p.family == MSD_STREAM) {
+        e = with_value<7, 15, 23, 24, 31>(p.stream_L, [&](auto L) {
+            return with_flags(p.stream_T == 128, p.columns == MSD_COL_FOLD, [&](auto T128, auto FOLD) {
+                constexpr int T = decltype(T128)::value ? 128 : 256;
+                return launch_lds(msd_stream_kernel<decltype(L)::value, T, decltype(FOLD)::value>, grid, dim3(T), p.lds, stream, DT,
+                                  Fp, F, c.d_perm, c.d_groups, p.comb_d, W, W, d_part, c.dcom);
+            });
+        });
+    } else if (p.family == MSD_COMB) {
+        e = with_value<4, 8, 12, 16, 20, 24, 28, 32>(p.comb_WT, [&](auto B) {
+            constexpr int WT = decltype(B)::value;
+            auto go = [&](auto kern) {
+                return launch_lds(kern, grid, block, p.lds, stream, DT, Fp, F, c.d_perm, c.d_groups, p.comb_d, std::min(W, 32), W,
+                                  d_part, c.dcom);
+            };
+            return p.db ? go(msd_comb_db_kernel<WT>) : go(msd_comb_kernel<WT>);
+        });
+        for (size_t q = 0; q < p.comb_hi.size() && e == hipSuccess; q++) {
+            const CombPass &h = p.comb_hi[q];
+            e = with_value<8, 16, 32>(h.WT, [&](auto B) {
+                return launch_lds(msd_comb_hi_kernel<decltype(B)::value>, grid, block, (size_t)F * sizeof(double), stream, DT, Fp, F,
+                                  c.d_perm, c.d_groups, p.comb_d, h.w0, h.wn, W, d_part, c.dcom);
+            });
+        }
+    } else {
+        e = with_value<8, 32, 0>(p.WREG, [&](auto R) {
+            return launch_lds(msd_group_kernel<decltype(R)::value>, grid, block, p.lds, stream, DT, Fp, F, c.d_perm, c.d_groups,
+                              c.d_win, W, d_part, c.dcom);
+        });
+    }
+    AMOF_HIP_TRY(c.ctx, e);
+    return AMOF_OK;
+}
+
+// long series: every column prefix-summed in place, then the windows reduced from global memory -> d_part[group][W]
+int msd_global_tier(MsdCall &c, double *d_part)
+{
+    const MsdPlan &p = c.plan;
+    const hipStream_t stream = c.ctx->stream;
+    const int64_t Fp = c.Fp();
+    const int F = (int)c.F(), W = c.W;
+    hipLaunchKernelGGL(scan_column_kernel, dim3((unsigned)(3 * c.t->n_atoms)), dim3(MSD_THREADS), 0, stream, (const double *)c.d_DT,
+                       (const double *)nullptr, Fp, F, c.d_DT);
+    if (p.family == MSD_COMB_GLOBAL) {      // 32 windows per launch
+        for (int w0 = 0; w0 < W; w0 += 32) {
+            const hipError_t e = launch_lds(msd_comb_global_kernel<32>, dim3(c.n_groups()), dim3(MSD_THREADS), p.lds, stream,
+                                            (const double *)c.d_DT, Fp, F, c.d_perm, c.d_groups, p.comb_d, p.Rres, w0,
+                                            std::min(32, W - w0), W, d_part);
+            AMOF_HIP_TRY(c.ctx, e);
+        }
+    } else {
+        hipLaunchKernelGGL(msd_group_kernel_global, dim3(c.n_groups(), p.wchunks), dim3(MSD_THREADS), 0, stream,
+                           (const double *)c.d_DT, Fp, F, c.d_perm, c.d_groups, c.d_win, W, d_part);
+    }
+    AMOF_HIP_TRY(c.ctx, hipGetLastError());
+    return AMOF_OK;
+}
+
+// d_part[group][W] of the transposed forms (nullptr: the fused form has answered) reduced to the [S][W] sums in fixed order;
+// the sums to where the caller wants them: sumsq (host, overwritten) or sumsq_dev (device, accumulated into)
+int msd_finish(MsdCall &c, const double *d_part, double *sumsq, double *sumsq_dev)
+{
+    amof_ctx *ctx = c.ctx;
+    const size_t n = (size_t)c.t->n_species * (size_t)c.W;
+    if (d_part) {
+        hipLaunchKernelGGL(msd_reduce_kernel, dim3((unsigned)n), dim3(MSD_THREADS), 0, ctx->stream, d_part, c.d_sgf, c.W, c.d_out);
+        AMOF_HIP_TRY(ctx, hipGetLastError());
+    }
+    if (sumsq_dev) AMOF_TRY(add_into(ctx, sumsq_dev, (const double *)c.d_out, n));
+    timing_end(ctx);
+    if (sumsq) AMOF_TRY(fetch(ctx, sumsq, c.d_out, n * sizeof(double)));
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
     return AMOF_OK;
 }
 
@@ -1440,295 +1606,37 @@ static int msd_window_run(amof_ctx *ctx, const amof_traj *t, const int32_t *wind
                           int32_t remove_com, int64_t atom_begin, int64_t atom_end, const double *com_ext, double *sumsq,
                           double *sumsq_dev)
 {
-    AMOF_TRY(validate_traj(ctx, t, remove_com != 0));
+    AMOF_TRY(msd_check(ctx, t, windows, W, atom_begin, atom_end, remove_com != 0));
+    if (com_ext && unwrap) return fail(ctx, AMOF_EINVAL, "a precomputed centre of mass cannot be combined with unwrap");
     const int S = t->n_species;
     const int64_t N = t->n_atoms, F = t->n_frames;
-    if (W < 0 || (W > 0 && !windows) || (!sumsq && !sumsq_dev)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (atom_begin < 0 || atom_end > N || atom_begin > atom_end) return fail(ctx, AMOF_EINVAL, "bad atom range");
-    if (com_ext && unwrap) return fail(ctx, AMOF_EINVAL, "a precomputed centre of mass cannot be combined with unwrap");
-    for (int w = 0; w < W; w++)
-        if (windows[w] < 0 || (F > 0 && windows[w] >= F)) return fail(ctx, AMOF_EINVAL, "window %d out of range", windows[w]);
     if (sumsq)
         for (int k = 0; k < S * W; k++) sumsq[k] = 0.0;
     if (F == 0 || N == 0 || W == 0 || atom_begin == atom_end) return AMOF_OK;
     if (F > 0x7fffffffLL) return fail(ctx, AMOF_EINVAL, "too many frames");
-    const size_t lds_need = ((size_t)F + (size_t)W) * sizeof(double);
-    const bool lds_resident = lds_need <= 150 * 1024;   // whole time series + window sums fit in LDS
-
-    // geometry records with the FULL inverse (wrap_positions semantics)
-    HostGeom hg;
-    AMOF_TRY(build_geometry(ctx, t, hg));
-    std::vector<double> grec;
-    msd_geom_records(t, hg, grec);
-    // species-sorted groups of the selected atoms
-    std::vector<int32_t> perm;
-    std::vector<MsdGroup> groups;
-    std::vector<int32_t> sp_group_first(S + 1, 0);
-    for (int s = 0; s < S; s++) {
-        sp_group_first[s] = (int32_t)groups.size();
-        size_t first = perm.size();
-        for (int64_t i = atom_begin; i < atom_end; i++)
-            if (t->species[i] == s) perm.push_back((int32_t)i);
-        for (size_t off = first; off < perm.size(); off += MSD_GROUP) {
-            MsdGroup g;
-            g.start = (int32_t)off;
-            g.count = (int32_t)std::min<size_t>(MSD_GROUP, perm.size() - off);
-            g.species = s;
-            g._pad = 0;
-            groups.push_back(g);
-        }
-    }
-    sp_group_first[S] = (int32_t)groups.size();
-    std::vector<int32_t> sp_first_atom(S + 1, 0);       // species s owns perm[sp_first_atom[s] .. sp_first_atom[s + 1])
-    for (int s = 0; s < S; s++) sp_first_atom[s] = sp_group_first[s] < (int32_t)groups.size() ? groups[sp_group_first[s]].start : (int32_t)perm.size();
-    sp_first_atom[S] = (int32_t)perm.size();
-    double total_mass = 0.0;
-    if (remove_com)
-        for (int64_t i = 0; i < N; i++) total_mass += t->masses[i];
+    MsdCall c = {ctx, t, windows, (int)W, unwrap != 0, remove_com != 0, atom_begin, atom_end, com_ext};
+    AMOF_TRY(msd_tables(c));
+    c.plan = msd_select(F, N, (int)W, windows, c.unwrap, c.remove_com, com_ext != nullptr, c.hg.all_ortho, atom_begin, atom_end,
+                        (int64_t)c.n_groups(), MsdSwitches::from_env());
 
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
-    const double *pos_dev = nullptr;
-    AMOF_TRY(stage_positions(ctx, t, &pos_dev));
-    const int64_t Fp = (F + 31) / 32 * 32;
-    const size_t dt_bytes = (size_t)3 * N * Fp * sizeof(double);
-    const void *d_geom, *d_perm, *d_groups, *d_win, *d_mass = nullptr, *d_sgf, *d_sfa;
-    void *d_com = nullptr, *d_DT = nullptr, *d_UT = nullptr, *d_part = nullptr, *d_out;
-    // the call's small tables travel in ONE copy (a copy costs ~5 us of queue time however small: six of them were a tenth
-    // of the pipeline)
-    UploadPack pk;
-    const int i_geom = pk.add(grec.data(), grec.size() * sizeof(double));
-    const int i_perm = pk.add(perm.data(), perm.size() * sizeof(int32_t));
-    const int i_groups = pk.add(groups.data(), groups.size() * sizeof(MsdGroup));
-    const int i_win = pk.add(windows, (size_t)W * sizeof(int32_t));
-    const int i_sgf = pk.add(sp_group_first.data(), sp_group_first.size() * sizeof(int32_t));
-    const int i_sfa = pk.add(sp_first_atom.data(), sp_first_atom.size() * sizeof(int32_t));
-    const int i_mass = remove_com ? pk.add(t->masses, (size_t)N * sizeof(double)) : -1;
-    AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
-    d_geom = pk.ptr<double>(i_geom); d_perm = pk.ptr<int32_t>(i_perm); d_groups = pk.ptr<MsdGroup>(i_groups);
-    d_win = pk.ptr<int32_t>(i_win); d_sgf = pk.ptr<int32_t>(i_sgf); d_sfa = pk.ptr<int32_t>(i_sfa);
-    if (remove_com) {
-        d_mass = pk.ptr<double>(i_mass);
-        AMOF_TRY(ensure(ctx, SLOT_AUX2, (size_t)F * 3 * sizeof(double), &d_com));
-    }
+    AMOF_TRY(stage_positions(ctx, t, &c.pos_dev));
+    AMOF_TRY(msd_upload(c));
+    void *d_out, *d_part = nullptr;
     AMOF_TRY(ensure(ctx, SLOT_OUT0, (size_t)S * W * sizeof(double), &d_out));
-    // windows in arithmetic progression from 0 (the only thing WindowMsd produces): comb kernels
-    int comb_d = 0;
-    if (W >= 2 && W <= (lds_resident ? 128 : 256) && windows[0] == 0 && windows[1] > 0 && !getenv("AMOF_MSD_NOCOMB")) {
-        comb_d = windows[1];
-        for (int w = 0; w < W; w++)
-            if ((int64_t)windows[w] != (int64_t)w * comb_d) comb_d = 0;
+    c.d_out = (double *)d_out;
+    bool fused = false;
+    if (c.plan.fused) AMOF_TRY(msd_fused_tier(c, fused));
+    if (!fused) {
+        AMOF_TRY(ensure(ctx, SLOT_AUX5, (size_t)c.n_groups() * (size_t)W * sizeof(double), &d_part));
+        AMOF_TRY(msd_columns_tier(c));
+        timing_dom_begin(ctx, "msd_global");
+        AMOF_TRY(c.plan.resident ? msd_window_tier(c, (double *)d_part) : msd_global_tier(c, (double *)d_part));
+        timing_dom_end(ctx, 1);
     }
-    // fused form (no transposed copy: see msd_seg_kernel): diagonal cells, the whole system in one call (the centre of
-    // mass needs every atom; atom-sharded ranks go through amof_msd_shard_begin / _finish), centre of mass removed, no unwrap
-    FusedDims fd;
-    bool done = false;
-    if (!unwrap && remove_com && !com_ext && hg.all_ortho && atom_begin == 0 && atom_end == N && !getenv("AMOF_MSD_NOFUSED") &&
-        fused_dims(F, W, comb_d, atom_begin, atom_end, fd)) {
-        double *d_RS = nullptr;
-        int32_t *d_flag = nullptr, evt = 0;
-        AMOF_TRY(fused_pass1(ctx, t, pos_dev, (const double *)d_geom, (const double *)d_mass, atom_begin, atom_end, fd,
-                             (double *)d_com, &d_RS));
-        AMOF_TRY(fused_pass2(ctx, t, pos_dev, (const double *)d_geom, atom_begin, fd, (int)W, (const double *)d_com, total_mass, d_RS,
-                             (const int32_t *)d_perm, (const int32_t *)d_sfa, (double *)d_out, &d_flag));
-        AMOF_TRY(fetch(ctx, &evt, d_flag, sizeof evt));
-        AMOF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (not sync_stream: the staged tables stay where they are)
-        done = evt == 0;       // else: an entry could wrap again under the centre-of-mass step -- the transposed forms answer
-    }
-    if (!done) {
-    AMOF_TRY(ensure(ctx, SLOT_AUX3, dt_bytes, &d_DT));
-    AMOF_TRY(ensure(ctx, SLOT_AUX5, groups.size() * (size_t)W * sizeof(double), &d_part));
-
-    // transposition tile: 32 frames x 64 atoms, 1024 threads (two consecutive frames per thread).  Measured on the
-    // MI355X for the headline shape (profiles/r02/msd_transpose_shapes.txt): 0.52 ms = 4.5 TB/s of read + write; a
-    // flat copy of the same bytes (torch) takes 0.46 ms.  Four or eight frames per thread: 0.57 / 1.18 ms.
-    constexpr int TR_TA = 64;
-    auto transpose = [&](const double *com_dev, int64_t a0, int64_t a1, double *cpart) -> hipError_t {
-        constexpr int TF = 32, TA = TR_TA, TH = 1024;
-        auto go = [&](auto kern) -> hipError_t {
-            const size_t lds = (size_t)TF * (3 * TA + 1) * sizeof(double);
-            hipError_t e = allow_max_lds((const void *)kern);
-            if (e != hipSuccess) return e;
-            dim3 grid((unsigned)((a1 - a0 + TA - 1) / TA), (unsigned)((F + TF - 1) / TF));
-            hipLaunchKernelGGL(kern, grid, dim3(TH), lds, ctx->stream, pos_dev, com_dev, (const double *)d_geom,
-                               (int)t->n_cells, N, (int)F, Fp, a0, a1, (double *)d_DT, (const double *)d_mass, cpart);
-            return hipGetLastError();
-        };
-        return hg.all_ortho ? go(delta_transpose_kernel<TF, TA, TH, true>) : go(delta_transpose_kernel<TF, TA, TH, false>);
-    };
-    // 2-pass form (see the header): diagonal cells, the whole system in one call, the series LDS-resident
-    Dcom dcom = {nullptr, nullptr, nullptr, (const double *)d_geom, {0.0, 0.0, 0.0}, Fp, (int32_t)t->n_cells, 0};
-    // (the streaming window kernel subtracts C in its register scan: chunks of at most STREAM_CH entries per thread)
-    const bool stream = lds_resident && comb_d >= 64 && comb_d <= 256 && W <= 32 && (size_t)Fp * sizeof(double) <= 150 * 1024 &&
-                        !getenv("AMOF_MSD_NOSTREAM");
-    const int streamT = comb_d <= 128 ? 128 : 256;
-    const bool stream_regscan = (((F + streamT - 1) / streamT) | 1) <= STREAM_CH;
-    const bool fold = !unwrap && remove_com && !com_ext && hg.all_ortho && lds_resident && atom_begin == 0 && atom_end == N &&
-                      !(stream && !stream_regscan) && !getenv("AMOF_MSD_NOFOLD");
-    if (fold) {
-        const int ntiles = (int)((N + TR_TA - 1) / TR_TA);
-        void *d_cpart, *d_dcT;
-        AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)ntiles * (size_t)F * 3 * sizeof(double), &d_cpart));
-        // dc [3][Fp] | C [4][Fp] (row 3 = zeros) | max |dc| [3] (bits)
-        AMOF_TRY(ensure(ctx, SLOT_AUX4, (size_t)7 * Fp * sizeof(double) + 32, &d_dcT));
-        double *d_CT = (double *)d_dcT + (size_t)3 * Fp;
-        unsigned long long *d_dcmax = (unsigned long long *)(d_CT + (size_t)4 * Fp);
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_dcmax, 0, 3 * sizeof(unsigned long long), ctx->stream));
-        AMOF_HIP_TRY(ctx, transpose((const double *)nullptr, 0, N, (double *)d_cpart));
-        hipLaunchKernelGGL(com_finish_kernel, dim3((unsigned)((F + COMF_FRAMES - 1) / COMF_FRAMES)), dim3(MSD_THREADS), 0,
-                           ctx->stream, (const double *)d_cpart, ntiles, (int)F, Fp, total_mass, (double *)d_dcT, d_CT, d_dcmax);
-        AMOF_HIP_TRY(ctx, hipGetLastError());
-        dcom.dcT = (const double *)d_dcT;
-        dcom.CT = d_CT;
-        dcom.dcmax = d_dcmax;
-        for (int c = 0; c < 3; c++) {
-            double lmin = 1e300;
-            for (int64_t k = 0; k < t->n_cells; k++) lmin = std::min(lmin, fabs(t->cell[9 * k + 4 * c]));
-            dcom.lhalf[c] = t->pbc[c] ? lmin * (0.5 - 1e-6) : 1e300;       // (a non-periodic axis never wraps)
-        }
-    } else if (!unwrap) {
-        if (remove_com && !com_ext) {
-            hipLaunchKernelGGL(com_kernel, dim3((unsigned)F), dim3(MSD_THREADS), 0, ctx->stream, pos_dev,
-                               (const double *)d_mass, N, total_mass, (double *)d_com);
-        }
-        // only the atoms of this call's range are transposed (atom-sharded ranks each do their share)
-        AMOF_HIP_TRY(ctx, transpose(remove_com && com_ext ? com_ext : (const double *)d_com, atom_begin, atom_end, nullptr));
-    } else {
-        // the unwrapped centre of mass needs every atom: all columns are transposed and scanned
-        AMOF_TRY(ensure(ctx, SLOT_AUX4, dt_bytes, &d_UT));
-        AMOF_HIP_TRY(ctx, transpose((const double *)nullptr, 0, N, nullptr));
-        hipLaunchKernelGGL(scan_column_kernel, dim3((unsigned)(3 * N)), dim3(MSD_THREADS), 0, ctx->stream,
-                           (const double *)d_DT, pos_dev, Fp, (int)F, (double *)d_UT);
-        if (remove_com) {
-            const int nblk = (int)((N + COMT_BLK - 1) / COMT_BLK);
-            void *d_cpart;
-            AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)nblk * 3 * Fp * sizeof(double), &d_cpart));
-            hipLaunchKernelGGL(com_T_partial_kernel, dim3((unsigned)((F + MSD_THREADS - 1) / MSD_THREADS), 3, (unsigned)nblk),
-                               dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_UT, (const double *)d_mass, N, Fp,
-                               (int)F, (double *)d_cpart);
-            hipLaunchKernelGGL(com_T_final_kernel, dim3((unsigned)((F + MSD_THREADS - 1) / MSD_THREADS), 3),
-                               dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_cpart, nblk, Fp, (int)F, total_mass,
-                               (double *)d_com);
-        }
-        hipLaunchKernelGGL(delta_T_kernel, dim3((unsigned)(atom_end - atom_begin), (unsigned)((F + MSD_THREADS - 1) / MSD_THREADS)),
-                           dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_UT, (const double *)d_com,
-                           (const double *)d_geom, (int)t->n_cells, N, Fp, (int)F, atom_begin, (double *)d_DT);
-    }
-    AMOF_HIP_TRY(ctx, hipGetLastError());
-    timing_dom_begin(ctx, "msd_global");
-    if (lds_resident) {
-        auto launch = [&](auto kern) -> hipError_t {
-            hipError_t e = allow_max_lds((const void *)kern);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3((unsigned)groups.size()), dim3(MSD_THREADS), lds_need, ctx->stream,
-                               (const double *)d_DT, Fp, (int)F, (const int32_t *)d_perm, (const MsdGroup *)d_groups,
-                               (const int32_t *)d_win, (int)W, (double *)d_part, dcom);
-            return hipGetLastError();
-        };
-        // two column buffers (the next column streams in behind the arithmetic) when they fit twice per CU
-        const bool db = 2 * (size_t)Fp * sizeof(double) <= 80 * 1024 && !getenv("AMOF_MSD_NODB");
-        auto launch_comb = [&](auto kern, auto kern_db) -> hipError_t {
-            const size_t lds = db ? 2 * (size_t)Fp * sizeof(double) : (size_t)F * sizeof(double);
-            hipError_t e = db ? allow_max_lds((const void *)kern_db) : allow_max_lds((const void *)kern);
-            if (e != hipSuccess) return e;
-            if (db)
-                hipLaunchKernelGGL(kern_db, dim3((unsigned)groups.size()), dim3(MSD_THREADS), lds, ctx->stream,
-                                   (const double *)d_DT, Fp, (int)F, (const int32_t *)d_perm, (const MsdGroup *)d_groups,
-                                   comb_d, (int)std::min(W, 32), (int)W, (double *)d_part, dcom);
-            else
-                hipLaunchKernelGGL(kern, dim3((unsigned)groups.size()), dim3(MSD_THREADS), lds, ctx->stream,
-                                   (const double *)d_DT, Fp, (int)F, (const int32_t *)d_perm, (const MsdGroup *)d_groups,
-                                   comb_d, (int)std::min(W, 32), (int)W, (double *)d_part, dcom);
-            return hipGetLastError();
-        };
-        // windows 32 .. W-1 in further passes of up to 32 (each re-reads the columns)
-        auto launch_comb_hi = [&](auto kern, int w0, int wn) -> hipError_t {
-            const size_t lds = (size_t)F * sizeof(double);
-            hipError_t e = allow_max_lds((const void *)kern);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3((unsigned)groups.size()), dim3(MSD_THREADS), lds, ctx->stream,
-                               (const double *)d_DT, Fp, (int)F, (const int32_t *)d_perm, (const MsdGroup *)d_groups,
-                               comb_d, w0, wn, (int)W, (double *)d_part, dcom);
-            return hipGetLastError();
-        };
-        ctx->last_path = comb_d > 0 ? "msd_comb" : "msd_group";
-        hipError_t e;
-        // streaming comb kernel: one thread per residue class (window spacing 64 .. 256 frames, <= 32 windows)
-        auto launch_stream = [&](auto kern) -> hipError_t {
-            hipError_t e2 = allow_max_lds((const void *)kern);
-            if (e2 != hipSuccess) return e2;
-            hipLaunchKernelGGL(kern, dim3((unsigned)groups.size()), dim3(streamT), (size_t)Fp * sizeof(double), ctx->stream,
-                               (const double *)d_DT, Fp, (int)F, (const int32_t *)d_perm, (const MsdGroup *)d_groups,
-                               comb_d, (int)W, (int)W, (double *)d_part, dcom);
-            ctx->last_path = "msd_stream";
-            return hipGetLastError();
-        };
-#define AMOF_STREAM(L)                                                                                                     \
-    (fold ? (streamT == 128 ? launch_stream(msd_stream_kernel<L, 128, true>) : launch_stream(msd_stream_kernel<L, 256, true>))  \
-          : (streamT == 128 ? launch_stream(msd_stream_kernel<L, 128, false>) : launch_stream(msd_stream_kernel<L, 256, false>)))
-        if (stream && W <= 8) e = AMOF_STREAM(7);
-        else if (stream && W <= 16) e = AMOF_STREAM(15);
-        else if (stream && W <= 24) e = AMOF_STREAM(23);
-        else if (stream && W <= 25) e = AMOF_STREAM(24);
-        else if (stream) e = AMOF_STREAM(31);
-#undef AMOF_STREAM
-        else if (comb_d > 0 && W <= 4) e = launch_comb(msd_comb_kernel<4>, msd_comb_db_kernel<4>);
-        else if (comb_d > 0 && W <= 8) e = launch_comb(msd_comb_kernel<8>, msd_comb_db_kernel<8>);
-        else if (comb_d > 0 && W <= 12) e = launch_comb(msd_comb_kernel<12>, msd_comb_db_kernel<12>);
-        else if (comb_d > 0 && W <= 16) e = launch_comb(msd_comb_kernel<16>, msd_comb_db_kernel<16>);
-        else if (comb_d > 0 && W <= 20) e = launch_comb(msd_comb_kernel<20>, msd_comb_db_kernel<20>);
-        else if (comb_d > 0 && W <= 24) e = launch_comb(msd_comb_kernel<24>, msd_comb_db_kernel<24>);
-        else if (comb_d > 0 && W <= 28) e = launch_comb(msd_comb_kernel<28>, msd_comb_db_kernel<28>);
-        else if (comb_d > 0) {
-            e = launch_comb(msd_comb_kernel<32>, msd_comb_db_kernel<32>);
-            for (int w0 = 32; w0 < W && e == hipSuccess; w0 += 32) {
-                const int wn = std::min(32, (int)W - w0);
-                if (wn <= 8) e = launch_comb_hi(msd_comb_hi_kernel<8>, w0, wn);
-                else if (wn <= 16) e = launch_comb_hi(msd_comb_hi_kernel<16>, w0, wn);
-                else e = launch_comb_hi(msd_comb_hi_kernel<32>, w0, wn);
-            }
-        }
-        else if (W <= 8) e = launch(msd_group_kernel<8>);
-        else if (W <= 32) e = launch(msd_group_kernel<32>);
-        else e = launch(msd_group_kernel<0>);
-        AMOF_HIP_TRY(ctx, e);
-    } else {
-        // long trajectory: prefix-sum every column in place, then reduce the windows from global memory
-        hipLaunchKernelGGL(scan_column_kernel, dim3((unsigned)(3 * N)), dim3(MSD_THREADS), 0, ctx->stream,
-                           (const double *)d_DT, (const double *)nullptr, Fp, (int)F, (double *)d_DT);
-        const int64_t nq = comb_d > 0 ? (F + comb_d - 1) / comb_d : 0;
-        const int Rres = comb_d > 0 && nq > 0 ? (int)std::min<int64_t>(std::min<int64_t>(comb_d, 32), 16384 / nq) : 0;
-        if (Rres >= 1) {
-            // comb kernel on the scanned columns, 32 windows per launch
-            ctx->last_path = "msd_comb_global";
-            const size_t lds = (size_t)nq * Rres * sizeof(double);
-            AMOF_HIP_TRY(ctx, allow_max_lds((const void *)msd_comb_global_kernel<32>));
-            for (int w0 = 0; w0 < W; w0 += 32) {
-                hipLaunchKernelGGL(msd_comb_global_kernel<32>, dim3((unsigned)groups.size()), dim3(MSD_THREADS), lds,
-                                   ctx->stream, (const double *)d_DT, Fp, (int)F, (const int32_t *)d_perm,
-                                   (const MsdGroup *)d_groups, comb_d, Rres, w0, std::min(32, (int)W - w0), (int)W,
-                                   (double *)d_part);
-            }
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-        } else {
-        const unsigned wchunks = (unsigned)std::max<int64_t>(1, std::min<int64_t>(W, (4096 + (int64_t)groups.size() - 1) /
-                                                                                    (int64_t)groups.size()));
-        hipLaunchKernelGGL(msd_group_kernel_global, dim3((unsigned)groups.size(), std::min(wchunks, 65535u)),
-                           dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_DT, Fp, (int)F, (const int32_t *)d_perm,
-                           (const MsdGroup *)d_groups, (const int32_t *)d_win, (int)W, (double *)d_part);
-        AMOF_HIP_TRY(ctx, hipGetLastError());
-        }
-    }
-    timing_dom_end(ctx, 1);
-    hipLaunchKernelGGL(msd_reduce_kernel, dim3((unsigned)(S * W)), dim3(MSD_THREADS), 0, ctx->stream,
-                       (const double *)d_part, (const int32_t *)d_sgf, (int)W, (double *)d_out);
-    AMOF_HIP_TRY(ctx, hipGetLastError());
-    }   // (!done: the transposed forms)
-    if (sumsq_dev) AMOF_TRY(add_into(ctx, sumsq_dev, (const double *)d_out, (size_t)S * W));
-    timing_end(ctx);
-    if (sumsq)
-        AMOF_TRY(fetch(ctx, sumsq, d_out, (size_t)S * W * sizeof(double)));
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));
+    AMOF_TRY(msd_finish(c, (const double *)d_part, sumsq, sumsq_dev));
+    ctx->last_path = fused ? "msd_fused" : c.plan.path;
     return AMOF_OK;
 }
 
@@ -1759,63 +1667,21 @@ __global__ void com_from_csum_kernel(const double *__restrict__ csum, int n, dou
     if (i < n) com[i] = csum[i] / total_mass;
 }
 
-struct ShardTables {
-    std::vector<double> grec;
-    std::vector<int32_t> perm, sp_first;
-    const double *d_geom = nullptr, *d_mass = nullptr;
-    const int32_t *d_perm = nullptr, *d_sp_first = nullptr;
-    double total_mass = 0.0;
-    int comb_d = 0;
-    bool ortho = true;
-};
-
-// what both halves of a sharded call need on the device: geometry records, the species-sorted atoms of the range, masses
-int shard_tables(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W, int64_t a0, int64_t a1, ShardTables &st)
+int shard_check(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W, int64_t a0, int64_t a1)
 {
-    const int S = t->n_species;
-    const int64_t N = t->n_atoms;
-    HostGeom hg;
-    AMOF_TRY(build_geometry(ctx, t, hg));
-    st.ortho = hg.all_ortho;
-    msd_geom_records(t, hg, st.grec);
-    st.sp_first.assign(S + 1, 0);
-    for (int s = 0; s < S; s++) {
-        st.sp_first[s] = (int32_t)st.perm.size();
-        for (int64_t i = a0; i < a1; i++)
-            if (t->species[i] == s) st.perm.push_back((int32_t)i);
-    }
-    st.sp_first[S] = (int32_t)st.perm.size();
-    st.total_mass = 0.0;
-    for (int64_t i = 0; i < N; i++) st.total_mass += t->masses[i];
-    st.comb_d = 0;
-    if (W >= 2 && windows[0] == 0 && windows[1] > 0) {
-        st.comb_d = windows[1];
-        for (int w = 0; w < W; w++)
-            if ((int64_t)windows[w] != (int64_t)w * st.comb_d) st.comb_d = 0;
-    }
-    UploadPack pk;
-    const int i_geom = pk.add(st.grec.data(), st.grec.size() * sizeof(double));
-    const int i_perm = pk.add(st.perm.data(), st.perm.size() * sizeof(int32_t));
-    const int i_spf = pk.add(st.sp_first.data(), st.sp_first.size() * sizeof(int32_t));
-    const int i_mass = pk.add(t->masses, (size_t)N * sizeof(double));
-    AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
-    st.d_geom = pk.ptr<double>(i_geom);
-    st.d_perm = pk.ptr<int32_t>(i_perm);
-    st.d_sp_first = pk.ptr<int32_t>(i_spf);
-    st.d_mass = pk.ptr<double>(i_mass);
+    AMOF_TRY(msd_check(ctx, t, windows, W, a0, a1, true));
+    if (!t->pos_on_device) return fail(ctx, AMOF_EUNSUPPORTED, "the sharded form reads device-resident positions");
+    if (t->n_frames > 0x7fffffffLL) return fail(ctx, AMOF_EINVAL, "too many frames");
     return AMOF_OK;
 }
 
-int shard_check(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32_t W, int64_t a0, int64_t a1)
+// what both halves of a sharded call need on the device: the tables of a call with the centre of mass removed; comb_d: the
+// RAW window spacing (the caps and AMOF_MSD_NOCOMB of the one-call path do not apply here)
+int shard_tables(MsdCall &c, int &comb_d)
 {
-    AMOF_TRY(validate_traj(ctx, t, true));
-    const int64_t N = t->n_atoms, F = t->n_frames;
-    if (W < 0 || (W > 0 && !windows)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (a0 < 0 || a1 > N || a0 > a1) return fail(ctx, AMOF_EINVAL, "bad atom range");
-    if (!t->pos_on_device) return fail(ctx, AMOF_EUNSUPPORTED, "the sharded form reads device-resident positions");
-    if (F > 0x7fffffffLL) return fail(ctx, AMOF_EINVAL, "too many frames");
-    for (int w = 0; w < W; w++)
-        if (windows[w] < 0 || (F > 0 && windows[w] >= F)) return fail(ctx, AMOF_EINVAL, "window %d out of range", windows[w]);
+    AMOF_TRY(msd_tables(c));
+    AMOF_TRY(msd_upload(c));
+    comb_d = comb_spacing(c.windows, c.W);
     return AMOF_OK;
 }
 
@@ -1829,19 +1695,20 @@ extern "C" int amof_msd_shard_begin(amof_ctx *ctx, const amof_traj *t, const int
     AMOF_TRY(shard_check(ctx, t, windows, W, a0, a1));
     const int64_t F = t->n_frames;
     ctx->shard_ticket = 0;
-    ShardTables st;
+    MsdCall c = {ctx, t, windows, (int)W, false, true, a0, a1, nullptr};
     FusedDims fd;
+    int comb_d = 0;
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    AMOF_TRY(shard_tables(ctx, t, windows, W, a0, a1, st));
-    if (!st.ortho || getenv("AMOF_MSD_NOFUSED") || !fused_dims(F, W, st.comb_d, a0, std::max(a1, a0 + 1), fd))
+    AMOF_TRY(shard_tables(c, comb_d));
+    if (!c.hg.all_ortho || MsdSwitches::from_env().nofused || !fused_dims(F, W, comb_d, a0, std::max(a1, a0 + 1), fd))
         return fail(ctx, AMOF_EUNSUPPORTED, "the fused window-MSD form does not take this call (general cell, or windows that are "
                                             "not w * d with 16 <= d, W <= 32, ceil(F / d) <= %d)", FU_MAX_TPC * FU_EB);
     timing_begin(ctx);
     timing_dom_begin(ctx, "msd_fused");
     if (a1 > a0) {
         double *d_RS = nullptr;
-        AMOF_TRY(fused_dims(F, W, st.comb_d, a0, a1, fd) ? AMOF_OK : AMOF_EINVAL);
-        AMOF_TRY(fused_pass1(ctx, t, t->pos, st.d_geom, st.d_mass, a0, a1, fd, csum_dev, &d_RS));
+        AMOF_TRY(fused_dims(F, W, comb_d, a0, a1, fd) ? AMOF_OK : AMOF_EINVAL);
+        AMOF_TRY(fused_pass1(ctx, t, t->pos, c.d_geom, c.d_mass, a0, a1, fd, csum_dev, &d_RS));
     } else {
         AMOF_HIP_TRY(ctx, hipMemsetAsync(csum_dev, 0, (size_t)F * 3 * sizeof(double), ctx->stream));
     }
@@ -1850,7 +1717,7 @@ extern "C" int amof_msd_shard_begin(amof_ctx *ctx, const amof_traj *t, const int
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     ctx->shard_ticket = ctx->calls;       // (timing_begin counts the calls: a finish must be the NEXT call on this context)
     ctx->shard_key[0] = (int64_t)(intptr_t)t->pos; ctx->shard_key[1] = F; ctx->shard_key[2] = t->n_atoms;
-    ctx->shard_key[3] = a0; ctx->shard_key[4] = a1; ctx->shard_key[5] = st.comb_d; ctx->shard_key[6] = W;
+    ctx->shard_key[3] = a0; ctx->shard_key[4] = a1; ctx->shard_key[5] = comb_d; ctx->shard_key[6] = W;
     return AMOF_OK;
 }
 
@@ -1862,24 +1729,25 @@ extern "C" int amof_msd_shard_finish(amof_ctx *ctx, const amof_traj *t, const in
     AMOF_TRY(shard_check(ctx, t, windows, W, a0, a1));
     const int S = t->n_species;
     const int64_t F = t->n_frames;
-    ShardTables st;
+    MsdCall c = {ctx, t, windows, (int)W, false, true, a0, a1, nullptr};
     FusedDims fd;
+    int comb_d = 0;
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    AMOF_TRY(shard_tables(ctx, t, windows, W, a0, a1, st));
-    const int64_t key[7] = {(int64_t)(intptr_t)t->pos, F, t->n_atoms, a0, a1, st.comb_d, W};
+    AMOF_TRY(shard_tables(c, comb_d));
+    const int64_t key[7] = {(int64_t)(intptr_t)t->pos, F, t->n_atoms, a0, a1, comb_d, W};
     bool same = ctx->shard_ticket != 0 && ctx->shard_ticket == ctx->calls;
     for (int q = 0; q < 7; q++) same = same && key[q] == ctx->shard_key[q];
     ctx->shard_ticket = 0;
     if (!same) return fail(ctx, AMOF_EINVAL, "amof_msd_shard_finish must follow amof_msd_shard_begin of the same arguments on this context");
     if (a1 == a0 || W == 0) return AMOF_OK;
-    if (!fused_dims(F, W, st.comb_d, a0, a1, fd)) return fail(ctx, AMOF_EINVAL, "window list changed");
+    if (!fused_dims(F, W, comb_d, a0, a1, fd)) return fail(ctx, AMOF_EINVAL, "window list changed");
     timing_begin(ctx);
     void *d_RS, *d_out;
     AMOF_TRY(ensure(ctx, SLOT_AUX7, (size_t)fd.nq * (size_t)fd.stride * sizeof(double), &d_RS));      // (what begin left there)
     AMOF_TRY(ensure(ctx, SLOT_OUT0, (size_t)S * W * sizeof(double), &d_out));
     int32_t *d_flag = nullptr, evt = 0;
-    AMOF_TRY(fused_pass2(ctx, t, t->pos, st.d_geom, a0, fd, (int)W, csum_dev, st.total_mass, (double *)d_RS, st.d_perm, st.d_sp_first,
-                         (double *)d_out, &d_flag));
+    AMOF_TRY(fused_pass2(ctx, t, t->pos, c.d_geom, a0, fd, fused_general(fd, F, MsdSwitches::from_env()), (int)W, csum_dev,
+                         c.total_mass, (double *)d_RS, c.d_perm, c.d_sfa, (double *)d_out, &d_flag));
     AMOF_TRY(fetch(ctx, &evt, d_flag, sizeof evt));
     AMOF_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (evt) {
@@ -1887,7 +1755,7 @@ extern "C" int amof_msd_shard_finish(amof_ctx *ctx, const amof_traj *t, const in
         void *d_com;
         AMOF_TRY(ensure(ctx, SLOT_AUX9, (size_t)F * 3 * sizeof(double), &d_com));
         hipLaunchKernelGGL(com_from_csum_kernel, dim3((unsigned)((3 * F + 255) / 256)), dim3(256), 0, ctx->stream, csum_dev, (int)(3 * F),
-                           st.total_mass, (double *)d_com);
+                           c.total_mass, (double *)d_com);
         AMOF_HIP_TRY(ctx, hipGetLastError());
         AMOF_HIP_TRY(ctx, sync_stream(ctx));
         return msd_window_run(ctx, t, windows, W, 0, 1, a0, a1, (const double *)d_com, nullptr, sumsq_dev);
@@ -1897,6 +1765,7 @@ extern "C" int amof_msd_shard_finish(amof_ctx *ctx, const amof_traj *t, const in
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     return AMOF_OK;
 }
+
 
 extern "C" int amof_msd_com_dev(amof_ctx *ctx, const amof_traj *t, int64_t frame_begin, int64_t frame_end, double *com_dev)
 {

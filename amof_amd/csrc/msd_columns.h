@@ -1,6 +1,7 @@
 // The MSD's atom-major data path, shared by the window MSD (msd.hip) and the self Van Hove function (vanhove.hip):
 // wrap of the frame-to-frame steps (ase wrap_positions), centre of mass, transposition to atom-major columns
-// D_T[3N][Fp] and their prefix sums (the running positions u of amof_msd_window), with and without unwrap.
+// D_T[3N][Fp] and their prefix sums (the running positions u of amof_msd_window), with and without unwrap -- the kernels
+// and, behind them, the one host function that launches them for a call (build_step_columns).
 // Everything here has internal linkage: each translation unit that includes it gets its own copy of the kernels.
 #pragma once
 
@@ -339,6 +340,75 @@ inline void msd_geom_records(const amof_traj *t, const HostGeom &hg, std::vector
         for (int q = 0; q < 9; q++) grec[(size_t)k * MSD_GEOM + 9 + q] = hg.invfull[(size_t)k * 9 + q];
         for (int q = 0; q < 3; q++) grec[(size_t)k * MSD_GEOM + 18 + q] = t->pbc[q] ? 1.0 : 0.0;
     }
+}
+
+// ---- the wrapped step columns of a call, as amof_msd_window forms them ----
+// Transposition tile: 32 frames x 64 atoms, 1024 threads (two consecutive frames per thread).  Measured on the MI355X for
+// the headline shape (profiles/r02/msd_transpose_shapes.txt): 0.52 ms = 4.5 TB/s of read + write; a flat copy of the same
+// bytes (torch) takes 0.46 ms.  Four or eight frames per thread: 0.57 / 1.18 ms.
+constexpr int TR_TF = 32, TR_TA = 64, TR_TH = 1024;
+
+struct ColumnsIn {
+    const double *pos_dev;      // [F][N][3]
+    const double *d_geom;       // msd_geom_records on the device
+    bool all_ortho;
+    const double *d_mass;       // [N] (remove_com)
+    double total_mass;
+    bool unwrap, remove_com;
+    const double *com_ext;      // optional precomputed centre of mass, device [F][3] (not with unwrap)
+};
+
+// Leaves D_T[3a + c][Fp], the wrapped steps of the atoms [a0, a1), in SLOT_AUX3 (*d_DT_out: the slot, columns indexed by
+// the atom's own number).  Slots: AUX2 centre of mass, AUX4 the unwrapped columns U_T, AUX6 its partial sums.
+// cpart (2-pass fold): RAW wrapped steps -- no centre of mass is removed -- and the mass-weighted coordinate sums of every
+// tile of TR_TA atoms and frame go to cpart[tile][F][3].
+int build_step_columns(amof_ctx *ctx, const amof_traj *t, const ColumnsIn &in, int64_t a0, int64_t a1, double **d_DT_out,
+                       double *cpart = nullptr)
+{
+    const int64_t N = t->n_atoms, F = t->n_frames, Fp = (F + 31) / 32 * 32;
+    const size_t dt_bytes = (size_t)3 * N * Fp * sizeof(double);
+    const dim3 frames((unsigned)((F + MSD_THREADS - 1) / MSD_THREADS));
+    void *d_DT, *d_com = nullptr;
+    AMOF_TRY(ensure(ctx, SLOT_AUX3, dt_bytes, &d_DT));
+    if (in.remove_com && !cpart) AMOF_TRY(ensure(ctx, SLOT_AUX2, (size_t)F * 3 * sizeof(double), &d_com));
+    // only the atoms [b0, b1) are transposed (atom-sharded ranks each do their share)
+    auto transpose = [&](const double *com_dev, int64_t b0, int64_t b1) -> hipError_t {
+        const dim3 grid((unsigned)((b1 - b0 + TR_TA - 1) / TR_TA), (unsigned)((F + TR_TF - 1) / TR_TF));
+        return with_flag(in.all_ortho, [&](auto O) {
+            return launch_lds(delta_transpose_kernel<TR_TF, TR_TA, TR_TH, O()>, grid, dim3(TR_TH),
+                              (size_t)TR_TF * (3 * TR_TA + 1) * sizeof(double), ctx->stream, in.pos_dev, com_dev, in.d_geom,
+                              (int)t->n_cells, N, (int)F, Fp, b0, b1, (double *)d_DT, in.d_mass, cpart);
+        });
+    };
+    if (cpart) {
+        AMOF_HIP_TRY(ctx, transpose(nullptr, a0, a1));
+    } else if (!in.unwrap) {
+        if (in.remove_com && !in.com_ext)
+            hipLaunchKernelGGL(com_kernel, dim3((unsigned)F), dim3(MSD_THREADS), 0, ctx->stream, in.pos_dev, in.d_mass, N,
+                               in.total_mass, (double *)d_com);
+        AMOF_HIP_TRY(ctx, transpose(in.remove_com ? (in.com_ext ? in.com_ext : (const double *)d_com) : nullptr, a0, a1));
+    } else {
+        // the unwrapped centre of mass needs every atom: all columns are transposed and scanned from frame 0's positions
+        void *d_UT;
+        AMOF_TRY(ensure(ctx, SLOT_AUX4, dt_bytes, &d_UT));
+        AMOF_HIP_TRY(ctx, transpose(nullptr, 0, N));
+        hipLaunchKernelGGL(scan_column_kernel, dim3((unsigned)(3 * N)), dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_DT,
+                           in.pos_dev, Fp, (int)F, (double *)d_UT);
+        if (in.remove_com) {
+            const int nblk = (int)((N + COMT_BLK - 1) / COMT_BLK);
+            void *d_part;
+            AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)nblk * 3 * Fp * sizeof(double), &d_part));
+            hipLaunchKernelGGL(com_T_partial_kernel, dim3(frames.x, 3, (unsigned)nblk), dim3(MSD_THREADS), 0, ctx->stream,
+                               (const double *)d_UT, in.d_mass, N, Fp, (int)F, (double *)d_part);
+            hipLaunchKernelGGL(com_T_final_kernel, dim3(frames.x, 3), dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_part,
+                               nblk, Fp, (int)F, in.total_mass, (double *)d_com);
+        }
+        hipLaunchKernelGGL(delta_T_kernel, dim3((unsigned)(a1 - a0), frames.x), dim3(MSD_THREADS), 0, ctx->stream,
+                           (const double *)d_UT, (const double *)d_com, in.d_geom, (int)t->n_cells, N, Fp, (int)F, a0, (double *)d_DT);
+    }
+    AMOF_HIP_TRY(ctx, hipGetLastError());
+    *d_DT_out = (double *)d_DT;
+    return AMOF_OK;
 }
 
 }  // namespace

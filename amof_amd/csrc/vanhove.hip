@@ -1,6 +1,6 @@
 // Self Van Hove function and the moments of the non-Gaussian parameter (gfx950).
 //
-// Data path (all float64), the window MSD's transposed one (msd_columns.h):
+// Data path (all float64), the window MSD's transposed one (msd_columns.h: build_step_columns):
 //   pos --com_kernel--> com[F][3];  pos, com --delta_transpose_kernel--> D_T[3N][Fp] (wrapped steps, atom-major)
 //   D_T --scan_column_kernel (in place)--> U_T: the running positions u_i(k) of amof_msd_window
 //   (unwrap: every column transposed and scanned from frame 0's positions, centre of mass from the unwrapped columns,
@@ -21,6 +21,7 @@
 
 #include "amof_internal.h"
 #include "msd_columns.h"
+#include "msd_select.h"
 
 namespace amof {
 namespace {
@@ -33,20 +34,13 @@ constexpr size_t VH_LDS_BUDGET = 64 * 1024;     // u32 counters of a multi-lag t
 constexpr int64_t VH_ORIGINS = (int64_t)1 << 28;
 static_assert(VH_THREADS == MSD_THREADS, "block_sum reduces MSD_THREADS lanes");
 
-struct VhGroup {
-    int32_t start;    // into perm
-    int32_t count;    // atoms
-    int32_t species;
-    int32_t _pad;
-};
-
 // grid (group, lag tile, origin chunk).  Samples: origins k in [k_begin, k_end) of the chunk with k + m < F, m the
 // tile's windows.  r2 = (dx dx + dy dy) + dz dz (no fma: -ffp-contract=off), bin b = (int)(sqrt(r2) / dr) -- the
 // comparison q < nbins on the double quotient is the same test as b < nbins without converting a huge q.
 template <bool GLOBAL>
 __global__ __launch_bounds__(VH_THREADS) void vanhove_hist_kernel(const double *__restrict__ UT, int64_t Fp, int F,
                                                                   const int32_t *__restrict__ perm,
-                                                                  const VhGroup *__restrict__ groups, int n_groups,
+                                                                  const MsdGroup *__restrict__ groups, int n_groups,
                                                                   const int32_t *__restrict__ windows, int W, int lags_per_tile,
                                                                   int64_t k_chunk, double dr, int nbins,
                                                                   unsigned long long *__restrict__ counts,
@@ -56,7 +50,7 @@ __global__ __launch_bounds__(VH_THREADS) void vanhove_hist_kernel(const double *
     extern __shared__ __align__(16) unsigned char lds_raw[];
     uint32_t *hist = reinterpret_cast<uint32_t *>(lds_raw);     // [nl][nbins] (LDS variant)
     __shared__ double red[2 * (MSD_THREADS / 64)];
-    const VhGroup gr = groups[blockIdx.x];
+    const MsdGroup gr = groups[blockIdx.x];
     const int w0 = blockIdx.y * lags_per_tile;
     const int nl = min(lags_per_tile, W - w0);
     const int64_t k_begin = 1 + (int64_t)blockIdx.z * k_chunk;
@@ -181,19 +175,9 @@ int vanhove_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32
     std::vector<double> grec;
     msd_geom_records(t, hg, grec);
     // species-sorted groups of the selected atoms
-    std::vector<int32_t> perm;
-    std::vector<VhGroup> groups;
-    std::vector<int32_t> sp_group_first(S + 1, 0);
-    for (int s = 0; s < S; s++) {
-        sp_group_first[s] = (int32_t)groups.size();
-        const size_t first = perm.size();
-        for (int64_t i = atom_begin; i < atom_end; i++)
-            if (t->species[i] == s) perm.push_back((int32_t)i);
-        for (size_t off = first; off < perm.size(); off += VH_GROUP)
-            groups.push_back(VhGroup{(int32_t)off, (int32_t)std::min<size_t>(VH_GROUP, perm.size() - off), s, 0});
-    }
-    sp_group_first[S] = (int32_t)groups.size();
-    const int n_groups = (int)groups.size();
+    SpeciesGroups sg;
+    species_groups(t->species, atom_begin, atom_end, S, VH_GROUP, sg);
+    const int n_groups = (int)sg.groups.size();
     double total_mass = 0.0;
     if (remove_com)
         for (int64_t i = 0; i < N; i++) total_mass += t->masses[i];
@@ -215,21 +199,18 @@ int vanhove_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32
     const double *pos_dev = nullptr;
     AMOF_TRY(stage_positions(ctx, t, &pos_dev));
     const int64_t Fp = (F + 31) / 32 * 32;
-    const size_t dt_bytes = (size_t)3 * N * Fp * sizeof(double);
     UploadPack pk;
     const int i_geom = pk.add(grec.data(), grec.size() * sizeof(double));
-    const int i_perm = pk.add(perm.data(), perm.size() * sizeof(int32_t));
-    const int i_groups = pk.add(groups.data(), groups.size() * sizeof(VhGroup));
+    const int i_perm = pk.add(sg.perm.data(), sg.perm.size() * sizeof(int32_t));
+    const int i_groups = pk.add(sg.groups.data(), sg.groups.size() * sizeof(MsdGroup));
     const int i_win = pk.add(windows, (size_t)W * sizeof(int32_t));
-    const int i_sgf = pk.add(sp_group_first.data(), sp_group_first.size() * sizeof(int32_t));
+    const int i_sgf = pk.add(sg.group_first.data(), sg.group_first.size() * sizeof(int32_t));
     const int i_mass = remove_com ? pk.add(t->masses, (size_t)N * sizeof(double)) : -1;
     AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
     const double *d_geom = pk.ptr<double>(i_geom), *d_mass = remove_com ? pk.ptr<double>(i_mass) : nullptr;
     const int32_t *d_perm = pk.ptr<int32_t>(i_perm), *d_win = pk.ptr<int32_t>(i_win), *d_sgf = pk.ptr<int32_t>(i_sgf);
-    const VhGroup *d_groups = pk.ptr<VhGroup>(i_groups);
-    void *d_com = nullptr, *d_DT = nullptr, *d_UT = nullptr, *d_part = nullptr, *d_mom = nullptr, *d_cnt = nullptr;
-    if (remove_com) AMOF_TRY(ensure(ctx, SLOT_AUX2, (size_t)F * 3 * sizeof(double), &d_com));
-    AMOF_TRY(ensure(ctx, SLOT_AUX3, dt_bytes, &d_DT));
+    const MsdGroup *d_groups = pk.ptr<MsdGroup>(i_groups);
+    void *d_part = nullptr, *d_mom = nullptr, *d_cnt = nullptr;
     AMOF_TRY(ensure(ctx, SLOT_AUX5, (size_t)n_chunks * n_groups * W * 2 * sizeof(double), &d_part));
     AMOF_TRY(ensure(ctx, SLOT_OUT0, (size_t)S * W * 2 * sizeof(double), &d_mom));
     unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counts_dev), *ovf = reinterpret_cast<unsigned long long *>(overflow_dev);
@@ -241,47 +222,12 @@ int vanhove_run(amof_ctx *ctx, const amof_traj *t, const int32_t *windows, int32
         ovf = cnt + (size_t)S * W * nbins;
     }
 
-    // ---- the running positions u_i(k) of the call's atoms, as amof_msd_window forms them ----
-    auto transpose = [&](const double *com_dev, int64_t a0, int64_t a1) -> hipError_t {
-        constexpr int TF = 32, TA = 64, TH = 1024;
-        auto go = [&](auto kern) -> hipError_t {
-            const size_t lds = (size_t)TF * (3 * TA + 1) * sizeof(double);
-            hipError_t e = allow_max_lds((const void *)kern);
-            if (e != hipSuccess) return e;
-            dim3 grid((unsigned)((a1 - a0 + TA - 1) / TA), (unsigned)((F + TF - 1) / TF));
-            hipLaunchKernelGGL(kern, grid, dim3(TH), lds, ctx->stream, pos_dev, com_dev, d_geom, (int)t->n_cells, N, (int)F, Fp,
-                               a0, a1, (double *)d_DT, (const double *)nullptr, (double *)nullptr);
-            return hipGetLastError();
-        };
-        return hg.all_ortho ? go(delta_transpose_kernel<TF, TA, TH, true>) : go(delta_transpose_kernel<TF, TA, TH, false>);
-    };
-    double *range_cols = (double *)d_DT + (size_t)3 * atom_begin * Fp;
+    // ---- the running positions u_i(k) of the call's atoms, as amof_msd_window forms them: its step columns, scanned ----
+    const ColumnsIn cols = {pos_dev, d_geom, hg.all_ortho, d_mass, total_mass, unwrap != 0, remove_com != 0, com_ext};
+    double *d_DT = nullptr;
+    AMOF_TRY(build_step_columns(ctx, t, cols, atom_begin, atom_end, &d_DT));
+    double *range_cols = d_DT + (size_t)3 * atom_begin * Fp;
     const unsigned n_cols = (unsigned)(3 * (atom_end - atom_begin));
-    if (!unwrap) {
-        if (remove_com && !com_ext)
-            hipLaunchKernelGGL(com_kernel, dim3((unsigned)F), dim3(MSD_THREADS), 0, ctx->stream, pos_dev, d_mass, N, total_mass,
-                               (double *)d_com);
-        AMOF_HIP_TRY(ctx, transpose(remove_com ? (com_ext ? com_ext : (const double *)d_com) : nullptr, atom_begin, atom_end));
-    } else {
-        // the unwrapped centre of mass needs every atom: all columns are transposed and scanned from frame 0's positions
-        AMOF_TRY(ensure(ctx, SLOT_AUX4, dt_bytes, &d_UT));
-        AMOF_HIP_TRY(ctx, transpose(nullptr, 0, N));
-        hipLaunchKernelGGL(scan_column_kernel, dim3((unsigned)(3 * N)), dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_DT,
-                           pos_dev, Fp, (int)F, (double *)d_UT);
-        if (remove_com) {
-            const int nblk = (int)((N + COMT_BLK - 1) / COMT_BLK);
-            void *d_cpart;
-            AMOF_TRY(ensure(ctx, SLOT_AUX6, (size_t)nblk * 3 * Fp * sizeof(double), &d_cpart));
-            hipLaunchKernelGGL(com_T_partial_kernel, dim3((unsigned)((F + MSD_THREADS - 1) / MSD_THREADS), 3, (unsigned)nblk),
-                               dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_UT, d_mass, N, Fp, (int)F, (double *)d_cpart);
-            hipLaunchKernelGGL(com_T_final_kernel, dim3((unsigned)((F + MSD_THREADS - 1) / MSD_THREADS), 3), dim3(MSD_THREADS), 0,
-                               ctx->stream, (const double *)d_cpart, nblk, Fp, (int)F, total_mass, (double *)d_com);
-        }
-        hipLaunchKernelGGL(delta_T_kernel, dim3((unsigned)(atom_end - atom_begin), (unsigned)((F + MSD_THREADS - 1) / MSD_THREADS)),
-                           dim3(MSD_THREADS), 0, ctx->stream, (const double *)d_UT, (const double *)d_com, d_geom, (int)t->n_cells, N,
-                           Fp, (int)F, atom_begin, (double *)d_DT);
-    }
-    AMOF_HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(scan_column_kernel, dim3(n_cols), dim3(MSD_THREADS), 0, ctx->stream, (const double *)range_cols,
                        (const double *)nullptr, Fp, (int)F, range_cols);
     AMOF_HIP_TRY(ctx, hipGetLastError());

@@ -123,6 +123,78 @@ def rdf_path_case(kind):
     return random_walk(z, 4, 0.05, 34), 7.7, 770
 
 
+def _msd_case(F, n, diagonal, window, paths, unwrap=False, atom_range=None, hands_over=False):
+    return dict(F=F, n=n, diagonal=diagonal, window=np.asarray(window, dtype=np.int32), paths=paths, unwrap=unwrap,
+                atom_range=atom_range, hands_over=hands_over)
+
+
+def _comb_window(F, d, W):
+    return np.array([w * d for w in range(W) if w * d < F], dtype=np.int32)
+
+
+MSD_COMB_SHAPES = [(7, 1, 3), (50, 3, 16), (333, 7, 24), (333, 11, 25), (1000, 100, 5), (1000, 31, 32),
+                   (257, 13, 12), (90, 100, 1), (64, 2, 29), (1201, 50, 21),
+                   (333, 3, 40), (1000, 7, 64), (2000, 9, 100), (700, 5, 33), (900, 11, 70),
+                   # window spacings of 64 .. 256 frames: the streaming kernel (one thread per residue
+                   # class; whole blocks, ragged comb ends, combs shorter than one block, 128 / 256 threads)
+                   (5000, 100, 25), (3000, 64, 20), (2000, 128, 12), (2600, 129, 9), (4100, 256, 8),
+                   (999, 77, 13), (1530, 100, 15), (4999, 100, 32), (650, 65, 10), (3333, 90, 24)]
+MSD_FUSED_SHAPES = [(5000, 100, 25, 40), (1000, 100, 5, 9), (999, 77, 13, 30), (1530, 100, 15, 25),
+                    (4999, 100, 32, 12), (650, 65, 10, 100), (3333, 90, 24, 17), (64, 16, 4, 5),
+                    (700, 16, 32, 64), (1680, 16, 8, 3), (1675, 16, 8, 5),     # nq = 44, 105: up to 21 threads per column
+                    (2000, 128, 12, 65), (4100, 256, 8, 24), (330, 64, 3, 40), (2600, 129, 9, 8)]
+MSD_LONG_COMBS = [(100, 105), (1000, 10), (7, 250), (333, 31)]        # (d, W at most) on 21000 frames
+
+
+def msd_path_case(kind):
+    """key -> case of the window-MSD shapes whose kernel family the GPU tests assert (tests/test_gpu_paths.py,
+    test_gpu_msd_fused.py, test_gpu_edges.py) and the selection is pinned to on the CPU (tests/test_msd_select_cpu.py).
+    A case: F frames, n atoms, diagonal cell or not, the window list, unwrap, an atom range, and paths: the switches set
+    (AMOF_MSD_<NAME>, lower case here) -> amof_last_path.  "msd_fused" is the path of a call whose columns never come within
+    the centre-of-mass step of half the cell; a gas is handed over to the path of the same case with "nofused".  hands_over:
+    the GPU test's trajectory is such a gas, so where the selection tries the fused form first the path is the one behind it."""
+    out = {}
+    if kind == "comb":              # 9 atoms in a triclinic cell
+        for F, d, W in MSD_COMB_SHAPES:
+            window = _comb_window(F, d, W)
+            streams = 64 <= d <= 256 and 2 <= len(window) <= 32
+            paths = {(): "msd_stream" if streams else ("msd_comb" if len(window) >= 2 else "msd_group"), ("nocomb",): "msd_group"}
+            if streams:
+                paths[("nostream",)] = "msd_comb"
+            out[(F, d, W)] = _msd_case(F, 9, False, window, paths)
+    elif kind == "fused":           # diagonal cells, the whole system
+        for F, d, W, n in MSD_FUSED_SHAPES:
+            other = "msd_stream" if 64 <= d <= 256 else "msd_comb"
+            out[(F, d, W, n)] = _msd_case(F, n, True, _comb_window(F, d, W), {(): "msd_fused", ("nofused",): other})
+    elif kind == "fused_other":     # what the fused form does not take
+        out["general_cell"] = _msd_case(300, 272, False, np.arange(4) * 64, {(): "msd_stream"})
+        out["spacing_8"] = _msd_case(300, 12, True, np.arange(30) * 8, {(): "msd_comb"})
+        out["irregular"] = _msd_case(300, 12, True, [0, 3, 50, 161], {(): "msd_group"})
+        out["40_windows"] = _msd_case(300, 12, True, np.arange(40) * 5, {(): "msd_comb"})
+        out["107_segments"] = _msd_case(1700, 6, True, np.arange(8) * 16, {(): "msd_comb"})
+        out["atom_range"] = _msd_case(300, 12, True, np.arange(4) * 64, {(): "msd_stream"}, atom_range=(2, 9))
+    elif kind == "long":            # F + W beyond the LDS-resident limit (19 200), 6 atoms
+        for unwrap in (False, True):
+            out[("irregular", unwrap)] = _msd_case(21000, 6, True, [0, 1, 7, 500, 9999, 20000, 20999], {(): "msd_global"}, unwrap=unwrap,
+                                                   hands_over=True)
+            for d, W in MSD_LONG_COMBS:
+                out[(d, W, unwrap)] = _msd_case(21000, 6, True, _comb_window(21000, d, W),
+                                                {(): "msd_comb_global", ("nocomb",): "msd_global"}, unwrap=unwrap, hands_over=True)
+    elif kind == "two_pass":        # 330 frames of 40 atoms, constant or breathing diagonal cell
+        both = ("nofold", "nofused")
+        out["stream"] = _msd_case(330, 40, True, np.arange(0, 160, 64), {(): "msd_fused", ("nofused",): "msd_stream", both: "msd_stream"})
+        out["comb"] = _msd_case(330, 40, True, np.arange(0, 160, 8), {(): "msd_comb", both: "msd_comb"})
+        out["group"] = _msd_case(330, 40, True, [0, 3, 50, 161], {(): "msd_group", both: "msd_group"})
+    else:
+        assert kind == "headline"
+        out["headline"] = _msd_case(5000, 9792, True, _comb_window(5000, 100, 25), {(): "msd_fused", ("nofused",): "msd_stream"})
+    return out
+
+
+def msd_switch_env(switches):
+    return {"AMOF_MSD_" + s.upper(): "1" for s in switches}
+
+
 def device_walk(device, reps, n_frames, sigma, seed, base=None):
     """Synthetic ZIF-4 supercell trajectory generated directly in HBM (torch, float64): Gaussian random walk,
     sigma per frame and axis, wrapped each frame into the constant orthorhombic cell.  The headline workload of

@@ -336,24 +336,27 @@ def test_msd_long_trajectory_uses_global_path(hip_ctx):
     pos = np.cumsum(rng.normal(scale=0.2, size=(F, n, 3)), axis=0) + 4.0
     s = pos / np.diag(cell)
     packed = PackedTrajectory((s - np.floor(s)) * np.diag(cell), cell, [1, 1, 1, 8, 8, 30])
-    window = np.array([0, 1, 7, 500, 9999, 20000, 20999], dtype=np.int32)
+    cases = H.msd_path_case("long")         # (the same shapes pin the selection on the CPU: test_msd_select_cpu.py)
+    window = cases[("irregular", False)]["window"]
+    assert (F, n) == (cases[("irregular", False)]["F"], cases[("irregular", False)]["n"])
     for unwrap in (False, True):
         sumsq, kinds = hip_ctx.msd_window(packed, window, unwrap=unwrap)
-        assert hip_ctx.last_path() == "msd_global"
+        assert hip_ctx.last_path() == cases[("irregular", unwrap)]["paths"][()] == "msd_global"
         elements, ref = no.window_msd_fast(packed.pos, packed.cell, packed.numbers, packed.masses, window, unwrap=unwrap)
         for e, r in zip(elements, ref):
             got = sumsq[kinds.index(int(e))] / (packed.numbers == e).sum() / (F - window)
             np.testing.assert_allclose(got, r, rtol=1e-9, atol=1e-12)
     # evenly spaced windows on the same long trajectory: the comb kernel on globally scanned columns
-    for d, wmax in [(100, 105), (1000, 10), (7, 250), (333, 31)]:
-        wap = (np.arange(wmax) * d).astype(np.int32)
-        wap = wap[wap < F]
+    for d, wmax in H.MSD_LONG_COMBS:
+        wap = cases[(d, wmax, False)]["window"]
+        assert np.array_equal(wap, [w * d for w in range(wmax) if w * d < F])
         for unwrap in (False, True):
+            paths = cases[(d, wmax, unwrap)]["paths"]
             sumsq, kinds = hip_ctx.msd_window(packed, wap, unwrap=unwrap)
-            assert hip_ctx.last_path() == "msd_comb_global"
+            assert hip_ctx.last_path() == paths[()] == "msd_comb_global"
             with H_env(AMOF_MSD_NOCOMB="1"):
                 generic, _ = hip_ctx.msd_window(packed, wap, unwrap=unwrap)
-                assert hip_ctx.last_path() == "msd_global"
+                assert hip_ctx.last_path() == paths[("nocomb",)] == "msd_global"
             np.testing.assert_allclose(sumsq, generic, rtol=1e-11, atol=1e-12)
         elements, ref = no.window_msd_fast(packed.pos, packed.cell, packed.numbers, packed.masses, wap)
         sumsq, kinds = hip_ctx.msd_window(packed, wap)
@@ -406,14 +409,18 @@ def test_msd_two_pass_form_and_its_rare_columns(hip_ctx, jitter):
     cells = np.array([cell * (1 + jitter * rng.normal()) for _ in range(F)]) if jitter else cell
     gas = PackedTrajectory(rng.uniform(0, 1, (F, N, 3)) @ cell, cells, numbers)
     walk = H.random_walk(Frame(numbers, rng.uniform(0, 1, (N, 3)) @ cell, cell), F, 0.05, 3, cell_jitter=jitter, ortho=True)
+    cases = H.msd_path_case("two_pass")     # (the same shapes pin the selection on the CPU: test_msd_select_cpu.py)
+    assert all((c["F"], c["n"]) == (F, N) for c in cases.values())
     for packed in (gas, walk):
-        for window, want in ((np.arange(0, 160, 64), "msd_stream"), (np.arange(0, 160, 8), "msd_comb"),
-                             (np.array([0, 3, 50, 161]), "msd_group")):
-            window = window.astype(np.int32)
+        for name in ("stream", "comb", "group"):
+            window, paths = cases[name]["window"], cases[name]["paths"]
+            want = paths[("nofold", "nofused")]
+            assert want == "msd_" + name
             got, kinds = hip_ctx.msd_window(packed, window)
             # round 5: evenly spaced windows (spacing >= 16) of a diagonal cell go to the fused form first; the gas raises
             # its flag (entries that wrap again under the centre-of-mass step) and is answered by the forms below
-            fused = want == "msd_stream" and packed is walk
+            fused = paths[()] == "msd_fused" and packed is walk
+            assert (paths[()] == "msd_fused") == (name == "stream")
             assert hip_ctx.last_path() == ("msd_fused" if fused else want)
             if fused:
                 with H_env(AMOF_MSD_NOFUSED="1"):

@@ -50,27 +50,51 @@ def _check_oracle(packed, window, got, kinds, rtol=1e-9):
         np.testing.assert_allclose(g, r, rtol=rtol, atol=1e-12)
 
 
-@pytest.mark.parametrize("F,d,W,n", [(5000, 100, 25, 40), (1000, 100, 5, 9), (999, 77, 13, 30), (1530, 100, 15, 25),
-                                     (4999, 100, 32, 12), (650, 65, 10, 100), (3333, 90, 24, 17), (64, 16, 4, 5),
-                                     (700, 16, 32, 64), (1680, 16, 8, 3), (1675, 16, 8, 5),     # nq = 44, 105: up to 21 threads per column
-                                     (2000, 128, 12, 65), (4100, 256, 8, 24), (330, 64, 3, 40), (2600, 129, 9, 8)])
+@pytest.mark.parametrize("F,d,W,n", list(H.msd_path_case("fused")))
 def test_fused_form_equals_oracle_and_transposed_forms(hip_ctx, F, d, W, n):
     # (steps of 0.05 A: with a dozen atoms the centre of mass of the WRAPPED positions jumps by angstroms whenever a heavy atom
     #  crosses the box -- the reference subtracts exactly that, amof/msd.py:235-237 -- and a larger raw step could then
     #  wrap again under it: such calls are answered by the transposed forms, see the gas test below)
     cell = np.diag([9.0, 10.0, 11.0])
     packed = _walk(F, n, F * 131 + d, cell)
-    window = np.array([w * d for w in range(W) if w * d < F], dtype=np.int32)
+    case = H.msd_path_case("fused")[(F, d, W, n)]       # (the same shapes pin the selection on the CPU: test_msd_select_cpu.py)
+    window, paths = case["window"], case["paths"]
+    assert np.array_equal(window, [w * d for w in range(W) if w * d < F])
     got, kinds = hip_ctx.msd_window(packed, window)
-    assert hip_ctx.last_path() == "msd_fused", (F, d, W)
+    assert hip_ctx.last_path() == paths[()] == "msd_fused", (F, d, W)
     with _env(AMOF_MSD_NOFUSED="1"):
         old, _ = hip_ctx.msd_window(packed, window)
-        assert hip_ctx.last_path() != "msd_fused"
+        assert hip_ctx.last_path() == paths[("nofused",)] != "msd_fused"
     np.testing.assert_allclose(got, old, rtol=1e-11, atol=1e-9)
     _check_oracle(packed, window, got, kinds)
     # device-resident positions: the same bits
     dev, _ = hip_ctx.msd_window(packed.to_device(0), window)
     assert np.array_equal(dev, got)
+
+
+def test_general_fused_kernel_by_switch(hip_ctx):
+    F, d, W, n = 1000, 100, 5, 9                # whole segments, five per thread: the lean kernel by default
+    packed = _walk(F, n, F * 131 + d, np.diag([9.0, 10.0, 11.0]))
+    window = (np.arange(W) * d).astype(np.int32)
+    lean, _ = hip_ctx.msd_window(packed, window)
+    assert hip_ctx.last_path() == "msd_fused"
+    with _env(AMOF_MSD_FUSED_GENERAL="1"):
+        general, _ = hip_ctx.msd_window(packed, window)
+        assert hip_ctx.last_path() == "msd_fused"
+    np.testing.assert_allclose(general, lean, rtol=1e-11, atol=1e-9)
+
+
+def test_fused_pass_one_with_two_atoms_per_lane(hip_ctx):
+    F, d, W, n = 1600, 16, 8, 330               # 330 atoms x 100 segments = 33 000 >= 2 * 64 * 256; the last tile of 128 is ragged
+    packed = _walk(F, n, F * 131 + d, np.diag([9.0, 10.0, 11.0]))
+    window = (np.arange(W) * d).astype(np.int32)
+    got, kinds = hip_ctx.msd_window(packed, window)
+    assert hip_ctx.last_path() == "msd_fused"
+    with _env(AMOF_MSD_NOFUSED="1"):
+        old, _ = hip_ctx.msd_window(packed, window)
+        assert hip_ctx.last_path() == "msd_comb"
+    np.testing.assert_allclose(got, old, rtol=1e-11, atol=1e-9)
+    _check_oracle(packed, window, got, kinds)
 
 
 def test_fused_form_cell_per_frame_drift_and_open_axis(hip_ctx):
@@ -126,20 +150,22 @@ def test_gas_raises_the_flag_and_the_transposed_forms_answer(hip_ctx):
 
 
 def test_general_cells_and_other_windows_keep_their_kernels(hip_ctx):
+    cases = H.msd_path_case("fused_other")
     tri = H.random_walk(H.zif4_frame(), 300, 0.05, 4)                 # the fixture's lattice has off-diagonal terms
-    hip_ctx.msd_window(tri, (np.arange(4) * 64).astype(np.int32))
-    assert hip_ctx.last_path() == "msd_stream"
+    assert (tri.n_frames, tri.n_atoms) == (cases["general_cell"]["F"], cases["general_cell"]["n"])
+    hip_ctx.msd_window(tri, cases["general_cell"]["window"])
+    assert hip_ctx.last_path() == cases["general_cell"]["paths"][()] == "msd_stream"
     cell = np.diag([9.0, 10.0, 11.0])
     packed = _walk(300, 12, 1, cell)
-    for window, want in (((np.arange(30) * 8), "msd_comb"), (np.array([0, 3, 50, 161]), "msd_group"),
-                         ((np.arange(40) * 5), "msd_comb")):          # spacing < 16, irregular, more than 32 windows
-        hip_ctx.msd_window(packed, window.astype(np.int32))
-        assert hip_ctx.last_path() == want
+    for name in ("spacing_8", "irregular", "40_windows"):             # spacing < 16, irregular, more than 32 windows
+        hip_ctx.msd_window(packed, cases[name]["window"])
+        assert hip_ctx.last_path() == cases[name]["paths"][()] != "msd_fused"
     long = _walk(1700, 6, 2, cell)
-    hip_ctx.msd_window(long, (np.arange(8) * 16).astype(np.int32))
-    assert hip_ctx.last_path() == "msd_comb"                          # more than 105 segments per column
-    sub, _ = hip_ctx.msd_window(packed, (np.arange(4) * 64).astype(np.int32), atom_range=(2, 9))
-    assert hip_ctx.last_path() != "msd_fused"                        # (an atom range of one call: the centre of mass needs all atoms)
+    hip_ctx.msd_window(long, cases["107_segments"]["window"])
+    assert hip_ctx.last_path() == cases["107_segments"]["paths"][()] == "msd_comb"      # more than 105 segments per column
+    sub, _ = hip_ctx.msd_window(packed, cases["atom_range"]["window"], atom_range=cases["atom_range"]["atom_range"])
+    # (an atom range of one call: the centre of mass needs all atoms)
+    assert hip_ctx.last_path() == cases["atom_range"]["paths"][()] != "msd_fused"
 
 
 def test_sharded_halves_add_up_to_the_whole(hip_ctx):

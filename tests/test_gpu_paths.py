@@ -451,13 +451,7 @@ def test_rdf_pipelined_host_staging(hip_ctx):
     assert np.array_equal(hb, hr) and np.array_equal(ab, ar) and ar.sum() > 0
 
 
-@pytest.mark.parametrize("F,d,W", [(7, 1, 3), (50, 3, 16), (333, 7, 24), (333, 11, 25), (1000, 100, 5), (1000, 31, 32),
-                                   (257, 13, 12), (90, 100, 1), (64, 2, 29), (1201, 50, 21),
-                                   (333, 3, 40), (1000, 7, 64), (2000, 9, 100), (700, 5, 33), (900, 11, 70),
-                                   # window spacings of 64 .. 256 frames: the streaming kernel (one thread per residue
-                                   # class; whole blocks, ragged comb ends, combs shorter than one block, 128 / 256 threads)
-                                   (5000, 100, 25), (3000, 64, 20), (2000, 128, 12), (2600, 129, 9), (4100, 256, 8),
-                                   (999, 77, 13), (1530, 100, 15), (4999, 100, 32), (650, 65, 10), (3333, 90, 24)])
+@pytest.mark.parametrize("F,d,W", list(H.msd_path_case("comb")))
 def test_msd_comb_kernel_equals_generic_and_oracle(hip_ctx, F, d, W):
     # windows w*d: the comb kernel (every template bucket, ragged comb ends, F < d, the skipped origin)
     # against the generic LDS kernel and the numpy restatement
@@ -468,23 +462,83 @@ def test_msd_comb_kernel_equals_generic_and_oracle(hip_ctx, F, d, W):
     pos = np.cumsum(rng.normal(scale=0.25, size=(F, n, 3)), axis=0) + 4.0
     s = pos @ np.linalg.inv(cell)
     packed = PackedTrajectory((s - np.floor(s)) @ cell, cell, [1, 1, 1, 1, 8, 8, 30, 30, 30])
-    window = np.array([w * d for w in range(W) if w * d < F], dtype=np.int32)
+    case = H.msd_path_case("comb")[(F, d, W)]       # (the same shapes pin the selection on the CPU: test_msd_select_cpu.py)
+    window, paths = case["window"], case["paths"]
+    assert packed.n_atoms == case["n"] and np.array_equal(window, [w * d for w in range(W) if w * d < F])
     comb, kinds = hip_ctx.msd_window(packed, window)
-    streams = 64 <= d <= 256 and 2 <= len(window) <= 32
-    assert hip_ctx.last_path() == ("msd_stream" if streams else ("msd_comb" if len(window) >= 2 else "msd_group"))
-    if streams:
+    assert hip_ctx.last_path() == paths[()]
+    if ("nostream",) in paths:
+        assert paths[()] == "msd_stream"
         with _env(AMOF_MSD_NOSTREAM="1"):
             blockform, _ = hip_ctx.msd_window(packed, window)
-            assert hip_ctx.last_path() == "msd_comb"
+            assert hip_ctx.last_path() == paths[("nostream",)] == "msd_comb"
         np.testing.assert_allclose(comb, blockform, rtol=1e-12, atol=1e-12)
     with _env(AMOF_MSD_NOCOMB="1"):
         generic, _ = hip_ctx.msd_window(packed, window)
-        assert hip_ctx.last_path() == "msd_group"
+        assert hip_ctx.last_path() == paths[("nocomb",)] == "msd_group"
     np.testing.assert_allclose(comb, generic, rtol=1e-12, atol=1e-12)
     elements, ref = no.window_msd_fast(packed.pos, packed.cell, packed.numbers, packed.masses, window)
     for e, r in zip(elements, ref):
         got = comb[kinds.index(int(e))] / (packed.numbers == e).sum() / (F - window)
         np.testing.assert_allclose(got, r, rtol=1e-9, atol=1e-12)
+
+
+def _msd_walk6(F, seed, cell):
+    rng = np.random.default_rng(seed)
+    pos = np.cumsum(rng.normal(scale=0.25, size=(F, 6, 3)), axis=0) + 4.0
+    s = pos @ np.linalg.inv(cell)
+    return PackedTrajectory((s - np.floor(s)) @ cell, cell, [1, 1, 8, 8, 30, 30])
+
+
+def _msd_oracle(packed, window, got, kinds):
+    from oracle import numpy_oracle as no
+    elements, ref = no.window_msd_fast(packed.pos, packed.cell, packed.numbers, packed.masses, window)
+    for e, r in zip(elements, ref):
+        g = got[kinds.index(int(e))] / (packed.numbers == e).sum() / (packed.n_frames - window)
+        np.testing.assert_allclose(g, r, rtol=1e-9, atol=1e-12)
+
+
+TRICLINIC = np.array([[9.0, 0, 0], [1.0, 10.0, 0], [0.5, -0.7, 11.0]])
+
+
+def test_msd_comb_kernel_without_the_second_column_buffer(hip_ctx):
+    # 5200 frames: two column buffers (Fp * 16 bytes) exceed the 80 KiB the double-buffered comb kernel may take
+    window = (np.arange(12) * 8).astype(np.int32)
+    packed = _msd_walk6(5200, 5, TRICLINIC)
+    comb, kinds = hip_ctx.msd_window(packed, window)
+    assert hip_ctx.last_path() == "msd_comb"
+    with _env(AMOF_MSD_NOCOMB="1"):
+        generic, _ = hip_ctx.msd_window(packed, window)
+        assert hip_ctx.last_path() == "msd_group"
+    np.testing.assert_allclose(comb, generic, rtol=1e-12, atol=1e-12)
+    _msd_oracle(packed, window, comb, kinds)
+    # a short series, where the double buffer is the default: the single buffer by switch
+    short = _msd_walk6(300, 6, TRICLINIC)
+    double, _ = hip_ctx.msd_window(short, window)
+    assert hip_ctx.last_path() == "msd_comb"
+    with _env(AMOF_MSD_NODB="1"):
+        single, _ = hip_ctx.msd_window(short, window)
+        assert hip_ctx.last_path() == "msd_comb"
+    np.testing.assert_allclose(single, double, rtol=1e-12, atol=1e-12)
+
+
+def test_msd_stream_kernel_without_the_register_scan(hip_ctx):
+    # 5300 frames at 128 threads: chunks of 43 entries, one more than the register scan of the streaming kernel holds
+    window = (np.arange(8) * 100).astype(np.int32)
+    tri = _msd_walk6(5300, 7, TRICLINIC)
+    got, kinds = hip_ctx.msd_window(tri, window)
+    assert hip_ctx.last_path() == "msd_stream"
+    _msd_oracle(tri, window, got, kinds)
+    # diagonal cell: the 2-pass fold needs the register scan, so the columns come from the 3-pass form either way
+    diag = _msd_walk6(5300, 8, np.diag([9.0, 10.0, 11.0]))
+    with _env(AMOF_MSD_NOFUSED="1"):
+        got, kinds = hip_ctx.msd_window(diag, window)
+        assert hip_ctx.last_path() == "msd_stream"
+        with _env(AMOF_MSD_NOFOLD="1"):
+            three_pass, _ = hip_ctx.msd_window(diag, window)
+            assert hip_ctx.last_path() == "msd_stream"
+    np.testing.assert_allclose(got, three_pass, rtol=1e-11, atol=1e-9)
+    _msd_oracle(diag, window, got, kinds)
 
 
 def test_msd_device_side_merge_entry_points(hip_ctx):

@@ -99,6 +99,18 @@ def test_unwrap_with_face_crossings(hip_ctx, remove_com):
     assert hip_ctx.last_path() == "msd_vanhove"
 
 
+def test_wrapped_steps_without_the_centre_of_mass(hip_ctx):
+    # (the columns of the shared builder with neither unwrap nor a centre of mass, whole system and an atom range)
+    packed = _gas_walk(64, 100, np.diag([5.0, 6.0, 7.0]), [1] * 40 + [8] * 24, 0.6, 13)
+    windows = np.array([0, 1, 4, 10, 49], dtype=np.int32)
+    for atom_range in (None, (9, 52)):
+        got = hip_ctx.vanhove_window(packed, windows, 0.05, 120, remove_com=False, atom_range=atom_range)
+        want = ref.vanhove(packed, windows, 0.05, 120, remove_com=False, atom_range=atom_range)
+        sel = packed.numbers if atom_range is None else np.asarray(packed.numbers)[atom_range[0]:atom_range[1]]
+        _compare(got, want, len(packed), windows, sel)
+    assert hip_ctx.last_path() == "msd_vanhove"
+
+
 def test_ragged_shapes_and_a_single_atom_species(hip_ctx):
     # F prime, N not a multiple of the 8-atom workgroup block, one Zn atom, unsorted windows incl. the last frame
     numbers = [30] + [7] * 17 + [6] * 19

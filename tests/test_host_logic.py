@@ -277,6 +277,8 @@ def test_every_kernel_family_is_pinned_by_a_forced_path_test():
             emitted |= set(re.findall(r'timing_dom_begin\(ctx, "([a-z_0-9]+)"', src))
             for args in re.findall(r'timing_dom_begin\(ctx, ([^;]*)\);', src):
                 emitted |= set(re.findall(r'"([a-z_0-9]+)"', args))
+        elif fn == "msd_select.h":      # the window MSD's plan carries the string of its family (msd.hip: last_path = ... plan.path)
+            emitted |= set(re.findall(r'\bpath = "([a-z_0-9]+)"', open(os.path.join(csrc, fn)).read()))
     emitted = {p for p in emitted if re.match(r"(rdf|cn|bad|msd)_", p)}
     header = open(os.path.join(ROOT, "include", "amof_hip.h")).read()
     doc = header[header.index("kernel family that produced the result of the last call"):header.index("const char *amof_last_path")]
