@@ -38,6 +38,7 @@ EXPORTS = [
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
     "amof_bond_order", "amof_bond_order_dev", "amof_pore_field", "amof_pore_candidate_bound",
+    "amof_pore_access", "amof_pore_access_field",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
@@ -147,6 +148,9 @@ def load_library():
         lib.amof_bond_order_dev.argtypes = lib.amof_bond_order.argtypes
         lib.amof_pore_field.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, P, P, P, P, P]
         lib.amof_pore_candidate_bound.argtypes = [P, ctypes.c_double]
+        lib.amof_pore_access.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, ctypes.c_int32,
+                                         P, P, P, P, P, P, P, P]
+        lib.amof_pore_access_field.argtypes = [P, P, ctypes.c_int64, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P]
         lib.amof_pore_candidate_bound.restype = ctypes.c_double
         lib.amof_sq_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_double, ctypes.c_int32, P, P, P]
@@ -396,6 +400,12 @@ def _recip(packed, recip):
     recip = np.ascontiguousarray(reciprocal(packed.cell) if recip is None else recip, dtype=np.float64)
     assert recip.shape == (packed.cell.shape[0], 3, 3)
     return recip
+
+
+def _label_cap(labels, n_t, G):
+    """the library's cap on ``labels`` (4 GiB per frame, AMOF_ECAPACITY), raised before the array is allocated"""
+    if labels and 4 * n_t * G > 2 ** 32:
+        raise AmofError(AMOF_ECAPACITY, "labels of %d thresholds x %d points exceed the 4 GiB a frame may take" % (n_t, G))
 
 
 def _span(given, n):
@@ -830,6 +840,66 @@ class Context(Lane):
         return res + (field.reshape((F,) + tuple(int(x) for x in grid)),) if per_point else res
 
     @_locked
+    def pore_access(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, free_sphere=False,
+                    labels=False):
+        """``pore_field``'s results -- the same bits -- followed by ``access int64 [F][n_t][4]`` (accessible points, channels,
+        pockets, largest channel dimension of the void ``v >= thresholds[t]``), then, each only if asked for, ``free_sphere
+        f64 [F][2]`` (t* and Dif / 2; +inf: not resolved below dmax), ``field f64 [F][nx][ny][nz]`` (``per_point``) and
+        ``labels int32 [F][n_t][nx][ny][nz]`` (the smallest linear index of a point's periodic component, -1 outside the
+        void): ``amof_pore_access`` (include/amof_hip.h has the definitions)."""
+        th = self._traj(packed, frame_range)
+        radii = np.ascontiguousarray(radii, dtype=np.float64).reshape(th.S)
+        grid = _i32(grid).reshape(3)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        dr, dmax = float(dr), float(dmax)
+        if not (np.isfinite(dr) and dr > 0 and np.isfinite(dmax) and dmax > 0):
+            raise ValueError("dr and dmax must be finite and > 0")
+        nbins = int(np.rint(dmax / dr))
+        if nbins < 1 or (grid < 1).any() or int(grid[0]) * int(grid[1]) * int(grid[2]) > 2 ** 31 - 1:
+            raise ValueError("dmax / dr rounds to no bin, or a grid that is not 1 .. 2^31 - 1 points")
+        shape = tuple(int(x) for x in grid)
+        F, G = th.n_frames, shape[0] * shape[1] * shape[2]
+        _label_cap(labels, len(thr), G)
+        hist = np.zeros((F, nbins + 2), dtype=np.uint64)
+        counts = np.zeros((F, len(thr)), dtype=np.int64)
+        vmax, argmax = np.zeros(F, dtype=np.float64), np.zeros(F, dtype=np.int64)
+        access = np.zeros((F, len(thr), 4), dtype=np.int64)
+        free = np.zeros((F, 2), dtype=np.float64) if free_sphere else None
+        field = np.zeros((F, G), dtype=np.float64) if per_point else None
+        lab = np.zeros((F, len(thr), G), dtype=np.int32) if labels else None
+        self._check(self._lib.amof_pore_access(self._h, ctypes.byref(th.c), _ptr(radii), _ptr(grid), dr, dmax, _ptr(thr), len(thr),
+                                               int(bool(free_sphere)), _ptr(hist), _ptr(counts), _ptr(vmax), _ptr(argmax), _ptr(access),
+                                               _ptr(free), _ptr(field), _ptr(lab)))
+        res = (hist, counts, vmax, argmax, access)
+        res += (free,) if free_sphere else ()
+        res += (field.reshape((F,) + shape),) if per_point else ()
+        return res + ((lab.reshape((F, len(thr)) + shape),) if labels else ())
+
+    @_locked
+    def pore_access_field(self, field, pbc=(True, True, True), thresholds=(), free_sphere=False, labels=False):
+        """``(access int64 [F][n_t][4], free_sphere f64 [F][2] or None, labels int32 [F][n_t][nx][ny][nz] or None)`` of
+        ``amof_pore_access_field``: the periodic components of ``{field >= thresholds[t]}`` of a field ``[F][nx][ny][nz]`` the
+        caller supplies (finite; ``pbc``: which grid axes are periodic) -- ``Pore(per_point=True).field`` or any other.
+        Here t* (``free_sphere[:, 0]``) is the largest field value of any sign whose void has a channel, -inf without one."""
+        field = np.ascontiguousarray(field, dtype=np.float64)
+        if field.ndim != 4:
+            raise ValueError("field must be [F][nx][ny][nz]")
+        F, shape = field.shape[0], tuple(int(x) for x in field.shape[1:])
+        grid = _i32(shape)
+        G = shape[0] * shape[1] * shape[2]
+        if min(shape) < 1 or G > 2 ** 31 - 1:
+            raise ValueError("a grid that is not 1 .. 2^31 - 1 points")
+        per = _i32([1 if x else 0 for x in pbc]).reshape(3)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        _label_cap(labels, len(thr), G)
+        access = np.zeros((F, len(thr), 4), dtype=np.int64)
+        free = np.zeros((F, 2), dtype=np.float64) if free_sphere else None
+        lab = np.zeros((F, len(thr), G), dtype=np.int32) if labels else None
+        self._check(self._lib.amof_pore_access_field(self._h, _ptr(field), F, _ptr(grid), _ptr(per), _ptr(thr), len(thr),
+                                                     int(bool(free_sphere)), _ptr(access), _ptr(free), _ptr(lab)))
+        return access, free, (lab.reshape((F, len(thr)) + shape) if labels else None)
+
+    @_locked
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None, out=None):
         """``(counts [nbins] u64, sums [P][nbins] f64, beyond, kinds)`` of ``amof_sq_accumulate``: the vectors ``hkl``
         (int ``[K][3]``) of the frames ``frame_range[0], + frame_stride, ... < frame_range[1]``, P = S(S+1)/2 species
@@ -1067,6 +1137,16 @@ class MultiContext(object):
         return self._sharded("pore_field", packed, _span(frame_range, packed.n_frames), "frame_range",
                              ("cat",) * (4 + bool(per_point)), radii, grid, dr, dmax, thresholds, copy_frames=True,
                              per_point=per_point)
+
+    def pore_access(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, free_sphere=False,
+                    labels=False):
+        """frames sharded over the devices as ``pore_field``'s: every output is per frame, the rows concatenate"""
+        return self._sharded("pore_access", packed, _span(frame_range, packed.n_frames), "frame_range",
+                             ("cat",) * (5 + bool(free_sphere) + bool(per_point) + bool(labels)), radii, grid, dr, dmax, thresholds,
+                             copy_frames=True, per_point=per_point, free_sphere=free_sphere, labels=labels)
+
+    def pore_access_field(self, field, pbc=(True, True, True), thresholds=(), free_sphere=False, labels=False):
+        return self.ctxs[0].pore_access_field(field, pbc, thresholds, free_sphere=free_sphere, labels=labels)
 
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None):
         """frames sharded over the devices (whole strides per device; a device trajectory on another GPU is copied for the

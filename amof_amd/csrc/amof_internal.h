@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -411,6 +412,17 @@ struct StageSpans {
         }
     }
 };
+
+// amof_pore_field's tiers (pore.hip) for a caller that works on the field where it lies: with a hook, the field of every batch
+// of frames [fb, fb + nf) is kept in device memory ([nf][G]) and handed to `batch` on the context's stream, after the field
+// kernel and before the next batch overwrites it.  fixed_bytes: the hook's own scratch, taken off the batch budget.
+struct PoreFieldHook {
+    size_t fixed_bytes = 0;
+    std::function<int(int64_t fb, int64_t nf, const double *d_field, StageSpans &spans)> batch;
+};
+int pore_field_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
+                   const double *thresholds, int32_t n_t, uint64_t *hist, int64_t *counts, double *vmax, int64_t *argmax,
+                   double *field, PoreFieldHook *hook);
 
 // ---------------------------------------------------------------- LDS-DMA --
 typedef __attribute__((address_space(1))) const void *gptr_t;

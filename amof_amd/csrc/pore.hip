@@ -363,6 +363,7 @@ struct PoreCall {
     long long *d_argmax = nullptr;
     double *field_host = nullptr;
     int64_t batch_cap = 0;      // AMOF_PORE_BATCH (0: none)
+    PoreFieldHook *hook = nullptr;      // amof_pore_access: the batch's field stays on the device and is labelled there
 };
 
 static size_t pore_lds(const PoreArgs &a)
@@ -382,8 +383,9 @@ static hipError_t pore_launch(Kernel kern, dim3 grid, size_t lds, hipStream_t st
 // frames per batch: the partial table, the field (if asked for) and `per_frame` more bytes of scratch within 1 GiB
 static int64_t pore_batch(const PoreCall &c, int64_t nwg, size_t per_frame)
 {
-    per_frame += (size_t)nwg * (sizeof(double) + sizeof(int32_t)) + (c.field_host ? (size_t)c.G * sizeof(double) : 0);
-    int64_t FB = std::max<int64_t>(1, (int64_t)((size_t)1 << 30) / (int64_t)std::max<size_t>(1, per_frame));
+    per_frame += (size_t)nwg * (sizeof(double) + sizeof(int32_t)) + (c.field_host || c.hook ? (size_t)c.G * sizeof(double) : 0);
+    const size_t budget = ((size_t)1 << 30) - std::min<size_t>(c.hook ? c.hook->fixed_bytes : 0, (size_t)1 << 29);
+    int64_t FB = std::max<int64_t>(1, (int64_t)budget / (int64_t)std::max<size_t>(1, per_frame));
     FB = std::min<int64_t>(std::min<int64_t>(FB, 32768), c.t->n_frames);
     if (c.batch_cap > 0) FB = std::min(FB, c.batch_cap);
     return FB;
@@ -399,7 +401,7 @@ static int pore_batches(PoreCall &c, int64_t nwg, int64_t FB, Launch &&launch)
     void *d_pv, *d_pi, *d_field = nullptr;
     AMOF_TRY(ensure(ctx, SLOT_AUX2, (size_t)FB * nwg * sizeof(double), &d_pv));
     AMOF_TRY(ensure(ctx, SLOT_AUX3, (size_t)FB * nwg * sizeof(int32_t), &d_pi));
-    if (c.field_host) AMOF_TRY(ensure(ctx, SLOT_OUT1, (size_t)FB * (size_t)c.G * sizeof(double), &d_field));
+    if (c.field_host || c.hook) AMOF_TRY(ensure(ctx, SLOT_OUT1, (size_t)FB * (size_t)c.G * sizeof(double), &d_field));
     a.part_v = (double *)d_pv;
     a.part_i = (int32_t *)d_pi;
     a.field = (double *)d_field;
@@ -416,6 +418,7 @@ static int pore_batches(PoreCall &c, int64_t nwg, int64_t FB, Launch &&launch)
         AMOF_HIP_TRY(ctx, hipGetLastError());
         launches++;
         if (c.field_host) AMOF_TRY(fetch(ctx, c.field_host + (size_t)fb * (size_t)c.G, d_field, (size_t)nf * (size_t)c.G * sizeof(double)));
+        if (c.hook) AMOF_TRY(c.hook->batch(fb, nf, (const double *)d_field, *c.spans));
     }
     timing_dom_end(ctx, launches);
     return AMOF_OK;
@@ -556,14 +559,16 @@ extern "C" double amof_pore_candidate_bound(const double *cell, double rcut)
     return cell ? pore_candidate_bound(cell, rcut) : -1.0;
 }
 
-extern "C" int amof_pore_field(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
-                               const double *thresholds, int32_t n_t, uint64_t *hist, int64_t *counts, double *vmax, int64_t *argmax,
-                               double *field)
+// amof_pore_field; with a hook (amof_pore_access, pore_access.hip) every batch's field is kept in device memory and handed over
+int amof::pore_field_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
+                         const double *thresholds, int32_t n_t, uint64_t *hist, int64_t *counts, double *vmax, int64_t *argmax,
+                         double *field, PoreFieldHook *hook)
 {
     if (!ctx) return AMOF_EINVAL;
     PoreCall c;
     c.ctx = ctx;
     c.t = t;
+    c.hook = hook;
     int32_t nbins = 0;
     AMOF_TRY(pore_check(ctx, t, radii, grid, dr, dmax, thresholds, n_t, hist, counts, vmax, argmax, c.geom, nbins));
     const int64_t F = t->n_frames;
@@ -585,7 +590,7 @@ extern "C" int amof_pore_field(amof_ctx *ctx, const amof_traj *t, const double *
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
     AMOF_TRY(stager_begin(ctx, t, true, c.stage));
-    StageSpans spans(ctx);      // cell sort, field kernel
+    StageSpans spans(ctx);      // cell sort, field kernel, the hook's labelling kernels
     c.spans = &spans;
     UploadPack pk;
     const int i_geom = pk.add(c.geom.rec.data(), c.geom.rec.size() * sizeof(double));
@@ -635,4 +640,11 @@ extern "C" int amof_pore_field(amof_ctx *ctx, const amof_traj *t, const double *
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     spans.collect();
     return AMOF_OK;
+}
+
+extern "C" int amof_pore_field(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
+                               const double *thresholds, int32_t n_t, uint64_t *hist, int64_t *counts, double *vmax, int64_t *argmax,
+                               double *field)
+{
+    return pore_field_run(ctx, t, radii, grid, dr, dmax, thresholds, n_t, hist, counts, vmax, argmax, field, nullptr);
 }

@@ -15,8 +15,14 @@ the host keeps the divisions and the DataFrames.
 The reference's ``Pore`` (amof/pore/core.py) writes one CIF per frame and starts the external Zeo++ binary on it.  This
 class takes the reference's four arguments and Zeo++'s column names for the quantities it has, but it is NOT Zeo++: that
 uses a Voronoi network, Monte-Carlo sampling and an accessibility test; this is the deterministic grid version of the same
-geometric quantities, converging with the grid spacing.  Not computed: accessibility / percolation of the void (the volumes
-are accessible plus non-accessible), the probe-occupiable volume, surface areas, the Gelb-Gubbins pore size distribution.
+geometric quantities, converging with the grid spacing.
+
+``accessibility=True`` splits the probe-centre volume into its accessible and non-accessible part: the periodic connected
+components of {v >= rp} (6-neighbourhood of the grid) are labelled on the GPU (``amof_pore_access``,
+amof_amd/csrc/pore_access.hip); a component that winds around the cell is a channel and its points are accessible, one
+that does not is a pocket.  ``free_sphere=True`` adds the largest free sphere Df -- twice the largest v at which the void still
+has a channel -- and Dif, the largest included sphere along the channels of that void.  include/amof_hip.h has the
+definitions.  Not computed: surface areas, the probe-occupiable volume, the Gelb-Gubbins pore size distribution.
 """
 
 import logging
@@ -156,6 +162,37 @@ def assemble(counts, probe_counts, vmax, step, volume, mass, probes, grid, dr):
     return pd.DataFrame(data), hist
 
 
+def access_columns(access, probe_counts, volume, mass, probes, grid):
+    """the columns ``accessibility=True`` adds to ``.data``, from the library's integers: ``access [F][n_probes][4]`` (accessible
+    points, channels, pockets, largest channel dimension), ``probe_counts [F][n_probes]`` (points with v >= rp).  Per probe
+    rp: AV_Volume_fraction-rp = accessible / G, NAV_Volume_fraction-rp = (count - accessible) / G, each with its A^3 and cm^3/g
+    as the PCV columns (AV + NAV = PCV in counts), Channels-rp, Pockets-rp, Channel_dimension-rp (0 without a channel)."""
+    access = np.asarray(access, dtype=np.int64).reshape(-1, len(probes), 4)
+    F = access.shape[0]
+    probe_counts = np.asarray(probe_counts, dtype=np.int64).reshape(F, len(probes))
+    volume = np.asarray(volume, dtype=np.float64).reshape(F)
+    G = int(grid[0]) * int(grid[1]) * int(grid[2])
+    if (access[:, :, 0] > probe_counts).any() or (access < 0).any():
+        raise ValueError("more accessible points than points of the void")
+    cols = {}
+    for k, rp in enumerate(probes):
+        for name, count in (("AV", access[:, k, 0]), ("NAV", probe_counts[:, k] - access[:, k, 0])):
+            frac = count.astype(np.float64) / G
+            cols[name + "_Volume_fraction-" + probe_label(rp)] = frac
+            cols[name + "_A^3-" + probe_label(rp)] = frac * volume
+            cols[name + "_cm^3/g-" + probe_label(rp)] = frac * volume * AVOGADRO_A3 / float(mass)
+        cols["Channels-" + probe_label(rp)] = access[:, k, 1].copy()
+        cols["Pockets-" + probe_label(rp)] = access[:, k, 2].copy()
+        cols["Channel_dimension-" + probe_label(rp)] = access[:, k, 3].copy()
+    return cols
+
+
+def free_sphere_columns(free):
+    """``Df = 2 t*`` and ``Dif`` from ``free [F][2]`` (t*, Dif / 2; inf: not resolved below dmax, 0: no channel at all)"""
+    free = np.asarray(free, dtype=np.float64).reshape(-1, 2)
+    return {"Df": 2.0 * free[:, 0], "Dif": 2.0 * free[:, 1]}
+
+
 class Pore(Deferred):
     """
     Void fraction, cavity-size histogram and largest included sphere of every frame of a trajectory
@@ -169,6 +206,10 @@ class Pore(Deferred):
       .counts       u64 [F][nbins + 2]: grid points inside an atom, per bin of [0, dmax), overflow
       .di_position  [F][3]: where the largest included sphere sits
       per_point=True: .field float64 [F][nx][ny][nz], the distance itself (dmax where it is not below dmax)
+      accessibility=True: per probe radius AV_* / NAV_* (accessible / non-accessible probe-centre volume), Channels-rp,
+                    Pockets-rp, Channel_dimension-rp (``access_columns``); .access int64 [F][n_probes][4]; with per_point
+                    .labels int32 [F][n_probes][nx][ny][nz]: the smallest linear index of a point's component, -1 outside
+      free_sphere=True: Df, Dif (``free_sphere_columns``); .free_sphere [F][2]: t* and Dif / 2
     These are grid estimates of geometric quantities, not Zeo++'s numbers (see the module's docstring).
     """
 
@@ -180,7 +221,8 @@ class Pore(Deferred):
 
     @classmethod
     def from_trajectory(cls, trajectory, delta_Step=1, first_frame=0, parallel=False, *, probe_radius=(0.0, 1.2), spacing=0.2,
-                        grid=None, dr=0.05, dmax=None, radii=None, per_point=False, device=None, distributed=None):
+                        grid=None, dr=0.05, dmax=None, radii=None, per_point=False, device=None, distributed=None, accessibility=False,
+                        free_sphere=False):
         """
         Args:
             trajectory: list of ase.Atoms-like frames, a PackedTrajectory or an XyzStream
@@ -193,6 +235,9 @@ class Pore(Deferred):
                 radius above half the smallest perpendicular cell height raises ValueError
             radii: dict element -> Angstrom over the built-in Bondi table; an element in neither raises ValueError
             per_point: keep the field
+            accessibility: label the void of every probe radius and split its volume into accessible and non-accessible
+                (every periodic grid axis then needs at least 3 points)
+            free_sphere: the largest free sphere Df and Dif per frame (about log2 of the grid size labellings per frame)
             device: GPU index or list of indices (default: LOCAL_RANK or 0)
             distributed: None -> the ranks of an initialised torch.distributed group take contiguous shares of the frames;
                 False -> single process; 'local' -> the trajectory is this rank's own block of frames
@@ -200,11 +245,11 @@ class Pore(Deferred):
         pore = cls()
         step = _trajectory.construct_step(delta_Step=delta_Step, first_frame=first_frame, number_of_frames=len(trajectory))
         pore.compute_pore(trajectory, step, probe_radius, spacing, grid, dr, dmax, radii, per_point, device=device,
-                          distributed=distributed)
+                          distributed=distributed, accessibility=accessibility, free_sphere=free_sphere)
         return pore
 
     def compute_pore(self, trajectory, step, probe_radius=(0.0, 1.2), spacing=0.2, grid=None, dr=0.05, dmax=None, radii=None,
-                     per_point=False, device=None, distributed=None):
+                     per_point=False, device=None, distributed=None, accessibility=False, free_sphere=False):
         packed = _setup.pack(trajectory, device, keep_stream=True)
         logger.info("Start pore analysis for %s frames", len(packed))
         kinds, _ = _hip.packed_species(packed)
@@ -248,20 +293,36 @@ class Pore(Deferred):
         frame_range = st.shard(F)
         G = grid[0] * grid[1] * grid[2]
 
-        cols = nbins + 2 + n_t + 6
+        accessibility, free_sphere = bool(accessibility), bool(free_sphere)
+        labelled = accessibility or free_sphere
+        want_labels = accessibility and per_point
+        if labelled and any(p and n < 3 for p, n in zip(packed.pbc, grid)):
+            raise ValueError("accessibility / free_sphere: a periodic grid axis needs at least 3 points, the grid is %s" % (grid,))
+        base_cols = nbins + 2 + n_t + 6
+        cols = base_cols + (4 * n_t if labelled else 0) + (2 if free_sphere else 0)
 
         def finish_host(raw):
-            rows, field = raw
+            rows, field, labels = raw
             rows = np.asarray(rows, dtype=np.int64).reshape(-1, cols)
-            tail = rows[:, nbins + 2 + n_t:].copy()
+            tail = rows[:, nbins + 2 + n_t:base_cols].copy()
             self._assemble(rows[:, :nbins + 2].copy().view(np.uint64), rows[:, nbins + 2:nbins + 2 + n_t].copy(),
                            tail[:, 0].copy().view(np.float64), tail[:, 1].copy(), tail[:, 2].copy().view(np.float64),
                            tail[:, 3:].copy().view(np.float64), field, step, mass, probes, grid, dr, dmax, rs, kinds)
+            if labelled:
+                self._assemble_access(rows[:, base_cols:base_cols + 4 * n_t].copy().reshape(-1, n_t, 4),
+                                      rows[:, base_cols + 4 * n_t:].copy().view(np.float64) if free_sphere else None, labels,
+                                      accessibility, tail[:, 2].copy().view(np.float64), mass, probes, grid)
 
         def call(tr, frame_range=None):
             # one int64 row per frame -- histogram, probe counts, the bits of vmax, argmax, the bits of the cell volume and of
             # the position of vmax -- so that one gather merges the ranks
-            res = ctx.pore_field(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point)
+            if labelled:
+                res = list(ctx.pore_access(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point,
+                                           free_sphere=free_sphere, labels=want_labels))
+                more = [res[4].reshape(-1, 4 * n_t)] + ([res.pop(5).view(np.int64)] if free_sphere else [])
+                res = res[:4] + res[5:]
+            else:
+                res, more = ctx.pore_field(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point), []
             hist, counts, vmax, argmax = res[:4]
             f0, f1 = (0, len(vmax)) if frame_range is None else frame_range
             c = np.asarray(tr.cell, dtype=np.float64).reshape(-1, 3, 3)
@@ -269,14 +330,18 @@ class Pore(Deferred):
             volume = np.ascontiguousarray(np.abs(np.linalg.det(c)), dtype=np.float64).reshape(-1)
             where = np.ascontiguousarray(positions(argmax, c, grid), dtype=np.float64).reshape(-1, 3)
             rows = np.concatenate([hist.view(np.int64), counts, vmax.view(np.int64)[:, None], argmax[:, None],
-                                   volume.view(np.int64)[:, None], where.view(np.int64)], axis=1)
-            return rows, (res[4] if per_point else None)
+                                   volume.view(np.int64)[:, None], where.view(np.int64)] + more, axis=1)
+            return rows, (res[4] if per_point else None), (res[5] if want_labels else None)
 
         if _setup.streamed(st):
             def walk():
-                if per_point:
-                    return _setup.walk(source, call, ("cat", "cat"))
-                return _setup.walk(source, lambda batch: call(batch)[:1], ("cat",)) + (None,)
+                keep = [0] + ([1] if per_point else []) + ([2] if want_labels else [])
+
+                def kept(batch):
+                    res = call(batch)
+                    return tuple(res[k] for k in keep)
+                got = _setup.walk(source, kept, ("cat",) * len(keep))
+                return tuple(got[keep.index(k)] if k in keep else None for k in range(3))
 
             self._defer(ctx, walk, finish_host)
             return
@@ -284,17 +349,21 @@ class Pore(Deferred):
         def local():
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
             if F == 0:
-                return np.zeros((0, cols), dtype=np.int64), (np.zeros((0,) + grid) if per_point else None)
+                return (np.zeros((0, cols), dtype=np.int64), (np.zeros((0,) + grid) if per_point else None),
+                        (np.zeros((0, n_t) + grid, dtype=np.int32) if want_labels else None))
             return call(packed, frame_range)
 
         def finish(raw):
-            rows, field = raw
+            rows, field, labels = raw
             if sharded:
                 rows = _dist.all_gather_rows(rows, device=ctx.device)
                 if per_point:
                     field = _dist.all_gather_rows(field.reshape(-1, G).view(np.int64), device=ctx.device).view(np.float64)
                     field = field.reshape((-1,) + grid)
-            finish_host((rows, field))
+                if want_labels:
+                    labels = _dist.all_gather_rows(labels.reshape(-1, n_t * G).astype(np.int64), device=ctx.device)
+                    labels = labels.astype(np.int32).reshape((-1, n_t) + grid)
+            finish_host((rows, field, labels))
 
         self._defer(ctx, local, finish, collective=sharded)
 
@@ -314,6 +383,19 @@ class Pore(Deferred):
         if len(over):
             logger.warning("Pore: %d frame(s) have grid points farther than dmax = %g from every atomic surface (first: frame %d); "
                            "Di is inf there -- raise dmax", len(over), dmax, int(over[0]))
+
+    def _assemble_access(self, access, free, labels, accessibility, volume, mass, probes, grid):
+        """the columns of ``accessibility`` / ``free_sphere`` behind ``assemble``'s (``access_columns``, ``free_sphere_columns``)"""
+        cols = {}
+        if accessibility:
+            self.access = access
+            cols.update(access_columns(access, self.probe_counts, volume, mass, probes, grid))
+            if labels is not None:
+                self.labels = labels
+        if free is not None:
+            self.free_sphere = free
+            cols.update(free_sphere_columns(free))
+        self.data = pd.concat([self.data, pd.DataFrame(cols, index=self.data.index)], axis=1)
 
     def write_to_file(self, path_to_output):
         """writes ``.data`` to ``<path>.pore`` (feather)"""

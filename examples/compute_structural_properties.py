@@ -51,6 +51,7 @@ def main(out_dir):
 
     pore = Pore.from_trajectory(traj, spacing=0.25)      # (the reference runs Zeo++ here, :131; this is the grid estimate)
     print(pore.data[["Step", "Density", "PCV_Volume_fraction-0", "PCV_Volume_fraction-1.2", "Di"]].to_string())
+    # Pore.from_trajectory(traj, spacing=0.25, accessibility=True, free_sphere=True): AV_* / NAV_* per probe radius, Df, Dif
 
 
 if __name__ == "__main__":

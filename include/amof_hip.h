@@ -128,6 +128,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
  * after amof_pore_field: 2 the cell sort (0 on "pore_exact"), 3 the field kernels.
+ * after amof_pore_access / amof_pore_access_field: 4 the labelling (amof_pore_access: 2 and 3 as amof_pore_field).
  * Returns < 0 if unavailable. */
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which);
 /* number of launches of the dominant kernel in the last call */
@@ -165,7 +166,9 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        neighbours; also AMOF_ORDER_EXACT=1)
  *   pore field "pore_brick" (bricks of grid points against a cell list, float32 candidates, the near-minimal atoms
  *        re-evaluated in canonical float64), "pore_exact" (every atom per grid point in canonical float64: open axes,
- *        bricks too coarse for the cutoff or too full; also AMOF_PORE_EXACT=1) */
+ *        bricks too coarse for the cutoff or too full; also AMOF_PORE_EXACT=1)
+ *   pore labelling (amof_pore_access, amof_pore_access_field) "pore_label_tile" (tiles labelled in LDS, tile faces merged in
+ *        device memory), "pore_label_global" (every link merged in device memory; AMOF_PORE_LABEL_GLOBAL=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -454,7 +457,8 @@ int amof_bond_order_dev(amof_ctx *ctx, const amof_traj *traj, const double *cuto
  * fraction for a set of probe radii, the cavity-size histogram and the largest included sphere, per frame.
  * The reference's Pore (amof/pore.py) writes one CIF per frame and runs the external Zeo++ binary on it (Voronoi network,
  * Monte-Carlo sampling, accessibility test); this is the deterministic grid version of the same geometric quantities and
- * does not reproduce Zeo++'s numbers.  No accessibility / percolation test: the counts are of probe CENTRES that fit.
+ * does not reproduce Zeo++'s numbers.  The counts are of probe CENTRES that fit, accessible or not: amof_pore_access below
+ * splits them.
  *   grid n = (nx, ny, nz), G = nx ny nz <= 2^31 - 1.  Point (i, j, k), linear index (i ny + j) nz + k:
  *     f = (((double)i + 0.5) / (double)nx, ...),  p_c = (f_x C[0][c] + f_y C[1][c]) + f_z C[2][c]   (no fma; the grid spans
  *     the cell parallelepiped, also along non-periodic axes)
@@ -482,6 +486,54 @@ int amof_pore_field(amof_ctx *ctx, const amof_traj *traj, const double *radii /*
  * rcut = dmax + max_s radii[s] (amof_amd/csrc/pore_math.h): atoms whose float32 candidate is within 2 eps_c of the
  * candidate minimum are re-evaluated in float64.  Tests plant decisions inside it. */
 double amof_pore_candidate_bound(const double *cell /* host [9] */, double rcut);
+
+/*
+ * Accessibility of the void: which part of V(t) percolates through the periodic cell, and the free sphere.
+ * (The reference's Pore.compute_surface_volume reads AV_* / NAV_* from Zeo++ -vol; this is the grid version on the field
+ * above and does not reproduce Zeo++'s numbers.)  Definitions:
+ *   void       V(t) = { p : v(p) >= t }, the float64 compare of the (dmax-capped) field that `counts` uses
+ *   adjacency  two grid points whose indices differ by +-1 along exactly one grid axis (6-neighbourhood in index space; the
+ *              grid axes are the lattice vectors).  On a periodic axis index n_k - 1 is adjacent to index 0 of the next
+ *              image, on an open axis it is not.  A periodic axis needs n_k >= 3 (AMOF_EINVAL): with 1 or 2 points a point
+ *              meets itself or the same neighbour through both faces.
+ *   component  a connected component of V(t) in this periodic graph; its label is the smallest linear index
+ *              (i ny + j) nz + k among its points -- independent of launch order, batching, path and frame range
+ *   winding    of a closed path inside a component: + e_k for every time it leaves through the upper face of periodic axis
+ *              k, - e_k through the lower.  The winding vectors of a component form a lattice in Z^3; its rank (0 .. 3) is
+ *              the component's DIMENSION.  Dimension >= 1: a CHANNEL, its points are ACCESSIBLE; dimension 0: a POCKET (also
+ *              a component that crosses a face and comes back through the same face).
+ *   free sphere  t* = the largest field value t >= 0 for which V(t) has a channel: V(t*) has one, V(nextafter(t*, +inf))
+ *              has none.  Df = 2 t* (0 if V(0) has no channel, +inf if V(dmax) has one: not resolved, as for Di);
+ *              Dif = 2 max v over the channels of V(t*), +inf where that is the cap dmax, 0 where Df = 0.
+ * amof_pore_access: amof_pore_field (same tiers, same switches, same first outputs and field, bit for bit) with every batch's
+ * field kept in device memory and labelled there.
+ *   access [F][n_t][4]: accessible points, channels, pockets, largest channel dimension of V(thresholds[t])
+ *   free_sphere [F][2] (may be NULL when want_free == 0; AMOF_EINVAL otherwise): t* and Dif / 2
+ *   labels (optional) host int32 [F][n_t][G]: the component label of every point, -1 outside the void; at most 4 GiB per
+ *     frame (AMOF_ECAPACITY)
+ * amof_pore_access_field: the same labelling of a field the caller supplies (host [n_frames][G], finite), e.g. one kept from
+ * amof_pore_field or one that is no distance at all; pbc[3]: which grid axes are periodic.  Here t* is the largest field
+ * value of any sign with a channel and free_sphere is (-inf, -inf) where V(t) has no channel for any t.
+ * One labelling is a union-find over the grid points (amof_amd/csrc/pore_access.hip); the windings are resolved on the host
+ * from the links through the cell's faces (amof_amd/csrc/pore_access_math.h).  The free sphere takes ceil(log2(G + 1))
+ * labellings per frame at most (bisection over the sorted field) and one more.
+ * Paths (amof_last_path names the labelling): "pore_label_tile" (tiles of 8 x 8 x 32 points labelled in LDS, the links across
+ * tile faces merged in device memory), "pore_label_global" (every link merged in device memory; AMOF_PORE_LABEL_GLOBAL=1).
+ * Both give the same bits.  amof_last_kernel_seconds: which = 4 the labelling (device work and the host's share between
+ * its kernels); amof_last_kernel_launches: the labellings of the call.
+ * All outputs are overwritten (zeros after an error).  Errors: as amof_pore_field.
+ */
+int amof_pore_access(amof_ctx *ctx, const amof_traj *traj, const double *radii /* host [S] */, const int32_t *grid /* host [3] */,
+                     double dr, double dmax, const double *thresholds /* host [n_t] */, int32_t n_t, int32_t want_free,
+                     uint64_t *hist /* host [F][nbins + 2] */, int64_t *counts /* host [F][n_t] */, double *vmax /* host [F] */,
+                     int64_t *argmax /* host [F] */, int64_t *access /* host [F][n_t][4] */,
+                     double *free_sphere /* host [F][2] or NULL */, double *field /* host [F][G] or NULL */,
+                     int32_t *labels /* host [F][n_t][G] or NULL */);
+int amof_pore_access_field(amof_ctx *ctx, const double *field /* host [n_frames][G] */, int64_t n_frames,
+                           const int32_t *grid /* host [3] */, const int32_t *pbc /* host [3] */,
+                           const double *thresholds /* host [n_t] */, int32_t n_t, int32_t want_free,
+                           int64_t *access /* host [n_frames][n_t][4] */, double *free_sphere /* host [n_frames][2] or NULL */,
+                           int32_t *labels /* host [n_frames][n_t][G] or NULL */);
 
 /*
  * Static structure factor by direct summation over reciprocal-lattice vectors.
