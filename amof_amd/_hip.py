@@ -38,7 +38,7 @@ EXPORTS = [
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
     "amof_bond_order", "amof_bond_order_dev", "amof_pore_field", "amof_pore_candidate_bound",
-    "amof_pore_access", "amof_pore_access_field",
+    "amof_pore_access", "amof_pore_access_field", "amof_pore_psd", "amof_pore_psd_field", "amof_pore_cover_stats",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
@@ -151,6 +151,11 @@ def load_library():
         lib.amof_pore_access.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, ctypes.c_int32,
                                          P, P, P, P, P, P, P, P]
         lib.amof_pore_access_field.argtypes = [P, P, ctypes.c_int64, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P]
+        lib.amof_pore_psd.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                      P, P, P, P, P, P, P, P, P, P, P, P]
+        lib.amof_pore_psd_field.argtypes = [P, P, P, ctypes.c_int64, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32,
+                                            ctypes.c_int32, P, P, P, P]
+        lib.amof_pore_cover_stats.argtypes = [P, P]
         lib.amof_pore_candidate_bound.restype = ctypes.c_double
         lib.amof_sq_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_double, ctypes.c_int32, P, P, P]
@@ -900,6 +905,97 @@ class Context(Lane):
         return access, free, (lab.reshape((F, len(thr)) + shape) if labels else None)
 
     @_locked
+    def pore_psd(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, accessibility=False,
+                 free_sphere=False, labels=False):
+        """``amof_pore_psd``: the results of ``pore_field`` -- of ``pore_access`` with ``accessibility`` or ``free_sphere`` --
+        with the same optional outputs in the same order, the same bits, followed by ``psd_hist u64 [F][nbins + 2]`` (the
+        histogram of the covering radius ``w``: covered by no sphere, the bins of ``[0, dmax)``, ``w >= dmax``), ``po_counts
+        int64 [F][n_t]`` (points with ``w >= thresholds[t]``: the probe-occupiable volume), with ``accessibility`` ``po_access
+        int64 [F][n_t]`` (points covered from a channel of the void ``v >= thresholds[t]``) and with ``per_point`` ``cover f64
+        [F][nx][ny][nz]`` (``w`` itself).  include/amof_hip.h has the definitions."""
+        th = self._traj(packed, frame_range)
+        radii = np.ascontiguousarray(radii, dtype=np.float64).reshape(th.S)
+        grid = _i32(grid).reshape(3)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        dr, dmax = float(dr), float(dmax)
+        if not (np.isfinite(dr) and dr > 0 and np.isfinite(dmax) and dmax > 0):
+            raise ValueError("dr and dmax must be finite and > 0")
+        nbins = int(np.rint(dmax / dr))
+        if nbins < 1 or (grid < 1).any() or int(grid[0]) * int(grid[1]) * int(grid[2]) > 2 ** 31 - 1:
+            raise ValueError("dmax / dr rounds to no bin, or a grid that is not 1 .. 2^31 - 1 points")
+        shape = tuple(int(x) for x in grid)
+        F, G = th.n_frames, shape[0] * shape[1] * shape[2]
+        accessibility, free_sphere = bool(accessibility), bool(free_sphere)
+        labelled = accessibility or free_sphere
+        labels = bool(labels) and labelled
+        _label_cap(labels, len(thr), G)
+        hist = np.zeros((F, nbins + 2), dtype=np.uint64)
+        counts = np.zeros((F, len(thr)), dtype=np.int64)
+        vmax, argmax = np.zeros(F, dtype=np.float64), np.zeros(F, dtype=np.int64)
+        access = np.zeros((F, len(thr), 4), dtype=np.int64) if labelled else None
+        free = np.zeros((F, 2), dtype=np.float64) if free_sphere else None
+        field = np.zeros((F, G), dtype=np.float64) if per_point else None
+        lab = np.zeros((F, len(thr), G), dtype=np.int32) if labels else None
+        psd_hist = np.zeros((F, nbins + 2), dtype=np.uint64)
+        po_counts = np.zeros((F, len(thr)), dtype=np.int64)
+        po_access = np.zeros((F, len(thr)), dtype=np.int64) if accessibility else None
+        cover = np.zeros((F, G), dtype=np.float64) if per_point else None
+        self._check(self._lib.amof_pore_psd(self._h, ctypes.byref(th.c), _ptr(radii), _ptr(grid), dr, dmax, _ptr(thr), len(thr),
+                                            int(accessibility), int(free_sphere), _ptr(hist), _ptr(counts), _ptr(vmax), _ptr(argmax),
+                                            _ptr(access), _ptr(free), _ptr(field), _ptr(lab), _ptr(psd_hist), _ptr(po_counts),
+                                            _ptr(po_access), _ptr(cover)))
+        res = (hist, counts, vmax, argmax) + ((access,) if labelled else ())
+        res += (free,) if free_sphere else ()
+        res += (field.reshape((F,) + shape),) if per_point else ()
+        res += (lab.reshape((F, len(thr)) + shape),) if labels else ()
+        res += (psd_hist, po_counts) + ((po_access,) if accessibility else ())
+        return res + ((cover.reshape((F,) + shape),) if per_point else ())
+
+    @_locked
+    def pore_psd_field(self, field, cells, pbc, dr, dmax, thresholds=(), accessibility=False, per_point=False):
+        """``(psd_hist u64 [F][nbins + 2], po_counts int64 [F][n_t], po_access int64 [F][n_t] or None, cover f64
+        [F][nx][ny][nz] or None)`` of ``amof_pore_psd_field``: the covering radius of a field ``[F][nx][ny][nz]`` the caller
+        supplies (finite; no value above half the smallest periodic perpendicular height of its frame's cell), ``cells
+        [F][3][3]`` or one cell for all frames, ``pbc``: which grid axes are periodic."""
+        field = np.ascontiguousarray(field, dtype=np.float64)
+        if field.ndim != 4:
+            raise ValueError("field must be [F][nx][ny][nz]")
+        F, shape = field.shape[0], tuple(int(x) for x in field.shape[1:])
+        grid = _i32(shape)
+        G = shape[0] * shape[1] * shape[2]
+        if min(shape) < 1 or G > 2 ** 31 - 1:
+            raise ValueError("a grid that is not 1 .. 2^31 - 1 points")
+        cells = np.asarray(cells, dtype=np.float64).reshape(-1, 9)
+        if cells.shape[0] == 1:
+            cells = np.broadcast_to(cells, (F, 9))
+        if cells.shape[0] != F:
+            raise ValueError("cells must be one cell or one per frame")
+        cells = np.ascontiguousarray(cells)
+        dr, dmax = float(dr), float(dmax)
+        if not (np.isfinite(dr) and dr > 0 and np.isfinite(dmax) and dmax > 0) or int(np.rint(dmax / dr)) < 1:
+            raise ValueError("dr and dmax must be finite and > 0, dmax at least one bin")
+        nbins = int(np.rint(dmax / dr))
+        per = _i32([1 if x else 0 for x in pbc]).reshape(3)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        psd_hist = np.zeros((F, nbins + 2), dtype=np.uint64)
+        po_counts = np.zeros((F, len(thr)), dtype=np.int64)
+        po_access = np.zeros((F, len(thr)), dtype=np.int64) if accessibility else None
+        cover = np.zeros((F, G), dtype=np.float64) if per_point else None
+        self._check(self._lib.amof_pore_psd_field(self._h, _ptr(field), _ptr(cells), F, _ptr(grid), _ptr(per), dr, dmax, _ptr(thr),
+                                                  len(thr), int(bool(accessibility)), _ptr(psd_hist), _ptr(po_counts), _ptr(po_access),
+                                                  _ptr(cover)))
+        return psd_hist, po_counts, po_access, (cover.reshape((F,) + shape) if per_point else None)
+
+    def pore_cover_stats(self):
+        """``{"bricks", "source_bricks", "records"}`` summed over the full passes of the last ``pore_psd`` / ``pore_psd_field`` on
+        the "pore_cover_brick" path (``amof_pore_cover_stats``): divide by ``bricks`` for the means per destination brick"""
+        self.drain()
+        out = np.zeros(3, dtype=np.float64)
+        with self._lock:
+            self._check(self._lib.amof_pore_cover_stats(self._h, _ptr(out)))
+        return dict(zip(("bricks", "source_bricks", "records"), out.tolist()))
+
+    @_locked
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None, out=None):
         """``(counts [nbins] u64, sums [P][nbins] f64, beyond, kinds)`` of ``amof_sq_accumulate``: the vectors ``hkl``
         (int ``[K][3]``) of the frames ``frame_range[0], + frame_stride, ... < frame_range[1]``, P = S(S+1)/2 species
@@ -1147,6 +1243,18 @@ class MultiContext(object):
 
     def pore_access_field(self, field, pbc=(True, True, True), thresholds=(), free_sphere=False, labels=False):
         return self.ctxs[0].pore_access_field(field, pbc, thresholds, free_sphere=free_sphere, labels=labels)
+
+    def pore_psd(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, accessibility=False,
+                 free_sphere=False, labels=False):
+        """frames sharded over the devices as ``pore_access``'s: every output is per frame, the rows concatenate"""
+        labelled = bool(accessibility) or bool(free_sphere)
+        n = (4 + labelled + bool(free_sphere) + bool(per_point) + (bool(labels) and labelled) + 2 + bool(accessibility) + bool(per_point))
+        return self._sharded("pore_psd", packed, _span(frame_range, packed.n_frames), "frame_range", ("cat",) * n, radii, grid, dr,
+                             dmax, thresholds, copy_frames=True, per_point=per_point, accessibility=accessibility,
+                             free_sphere=free_sphere, labels=labels)
+
+    def pore_psd_field(self, field, cells, pbc, dr, dmax, thresholds=(), accessibility=False, per_point=False):
+        return self.ctxs[0].pore_psd_field(field, cells, pbc, dr, dmax, thresholds, accessibility=accessibility, per_point=per_point)
 
     def sq_accumulate(self, packed, hkl, dq, nbins, frame_range=None, frame_stride=1, recip=None):
         """frames sharded over the devices (whole strides per device; a device trajectory on another GPU is copied for the

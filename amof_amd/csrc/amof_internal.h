@@ -84,8 +84,11 @@ struct amof_ctx {
     int64_t shard_ticket = 0;     // `calls` right after a begin; 0 = none pending
     int64_t shard_key[7] = {0, 0, 0, 0, 0, 0, 0};
     // kernel seconds of the stages of the last amof_isf_accumulate[_dev]: rho table (with the quantisation), correlation, self;
-    // of the last amof_bond_survival[_dev]: lists, series, correlations (StageSpans)
-    double stage_seconds[3] = {-1.0, -1.0, -1.0};
+    // of the last amof_bond_survival[_dev]: lists, series, correlations (StageSpans); the fourth: amof_pore_psd's covering stage
+    double stage_seconds[4] = {-1.0, -1.0, -1.0, -1.0};
+    // of the last amof_pore_psd[_field], over the full passes on "pore_cover_brick": destination bricks, the source bricks they
+    // kept, the centre records they swept (amof_pore_cover_stats)
+    double cover_stats[3] = {0.0, 0.0, 0.0};
 };
 
 namespace amof {
@@ -373,7 +376,7 @@ void timing_end(amof_ctx *ctx);
 void timing_dom_begin(amof_ctx *ctx, const char *path);
 void timing_dom_end(amof_ctx *ctx, int64_t launches);
 
-// Event pairs around the stages of a call, for amof_last_kernel_seconds 2 .. 4 (ctx->stage_seconds).  A stage may be
+// Event pairs around the stages of a call, for amof_last_kernel_seconds 2 .. 5 (ctx->stage_seconds).  A stage may be
 // begun many times; end() closes the span begun last.  An event that cannot be created leaves its span out, silently.
 struct StageSpans {
     struct Span {
@@ -423,6 +426,23 @@ struct PoreFieldHook {
 int pore_field_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
                    const double *thresholds, int32_t n_t, uint64_t *hist, int64_t *counts, double *vmax, int64_t *argmax,
                    double *field, PoreFieldHook *hook);
+
+// amof_pore_access / amof_pore_access_field (pore_access.hip) for a caller that works beside the labelling (amof_pore_psd,
+// pore_cover.hip): `frame` runs before a frame's first labelling; `threshold` after threshold k of the frame is labelled --
+// parent[] then holds the periodic labels (-1 outside the void) and mark[root] < 0 for the root of every channel (channels:
+// whether there is one).  Both run on the context's stream, outside the labelling's span; fixed_bytes as PoreFieldHook's.
+struct PoreAccessHook {
+    size_t fixed_bytes = 0;
+    std::function<int(int64_t f, const double *d_field, StageSpans &spans)> frame;
+    std::function<int(int64_t f, int32_t k, const double *d_field, const int32_t *parent, const int32_t *mark, bool channels,
+                      StageSpans &spans)> threshold;
+};
+int pore_access_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
+                    const double *thresholds, int32_t n_t, int32_t want_free, uint64_t *hist, int64_t *counts, double *vmax,
+                    int64_t *argmax, int64_t *access, double *free_sphere, double *field, int32_t *labels, PoreAccessHook *hook);
+int pore_access_field_run(amof_ctx *ctx, const double *field, int64_t n_frames, const int32_t *grid, const int32_t *pbc,
+                          const double *thresholds, int32_t n_t, int32_t want_free, int64_t *access, double *free_sphere,
+                          int32_t *labels, PoreAccessHook *hook);
 
 // ---------------------------------------------------------------- LDS-DMA --
 typedef __attribute__((address_space(1))) const void *gptr_t;

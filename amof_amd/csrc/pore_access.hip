@@ -315,6 +315,7 @@ struct Labeller {
     size_t cub_bytes = 0;
     int64_t labellings = 0;
     std::vector<int2> h_links, h_list;
+    std::vector<int32_t> roots;                 // pa_mark_channels: lives until the copy queued from it has run
     std::vector<WrapLink> wrap;
     std::vector<PeriodicComponent> comps;       // of the last labelling: the periodic components with a wrap link
     WindingResolver resolver;
@@ -435,6 +436,23 @@ static bool pa_has_channel(const Labeller &lb)
     return false;
 }
 
+// after pa_periodic: size[root] = -1 for the root of every channel (any: whether there is one)
+static int pa_mark_channels(Labeller &lb, bool &any)
+{
+    amof_ctx *ctx = lb.ctx;
+    lb.roots.clear();
+    for (const PeriodicComponent &c : lb.comps)
+        if (c.dimension > 0) lb.roots.push_back(c.label);
+    any = !lb.roots.empty();
+    if (!any) return AMOF_OK;
+    void *d_roots;
+    AMOF_TRY(upload(ctx, SLOT_PERM, lb.roots.data(), lb.roots.size() * sizeof(int32_t), &d_roots));
+    hipLaunchKernelGGL(pa_mark_kernel, dim3(pa_blocks((int64_t)lb.roots.size())), dim3(PA_THREADS), 0, ctx->stream, lb.size,
+                       (const int32_t *)d_roots, (int)lb.roots.size());
+    AMOF_HIP_TRY(ctx, hipGetLastError());
+    return AMOF_OK;
+}
+
 // after pa_open: the wrap links merged, the periodic labels in parent[], access[4] = accessible points, channels, pockets,
 // largest dimension; labels (host [G] or null); chmax (or null): the largest field value over the channels (-inf without one)
 static int pa_periodic(Labeller &lb, const double *d_field, int64_t *access, int32_t *labels, double *chmax)
@@ -480,20 +498,14 @@ static int pa_periodic(Labeller &lb, const double *d_field, int64_t *access, int
     if (labels) AMOF_TRY(fetch(ctx, labels, lb.parent, (size_t)G * sizeof(int32_t)));
     if (chmax) {
         *chmax = -INFINITY;
-        std::vector<int32_t> roots;
-        for (const PeriodicComponent &c : lb.comps)
-            if (c.dimension > 0) roots.push_back(c.label);
-        if (!roots.empty()) {
-            void *d_roots;
-            AMOF_TRY(upload(ctx, SLOT_PERM, roots.data(), roots.size() * sizeof(int32_t), &d_roots));
-            hipLaunchKernelGGL(pa_mark_kernel, dim3(pa_blocks((int64_t)roots.size())), dim3(PA_THREADS), 0, ctx->stream, lb.size,
-                               (const int32_t *)d_roots, (int)roots.size());
-            AMOF_HIP_TRY(ctx, hipGetLastError());
+        bool any = false;
+        AMOF_TRY(pa_mark_channels(lb, any));
+        if (any) {
             hipLaunchKernelGGL(pa_chmax_kernel, dim3(pa_blocks(G)), dim3(PA_THREADS), 0, ctx->stream, d_field, (const int32_t *)lb.parent,
                                (const int32_t *)lb.size, G, (unsigned long long *)(lb.out + 2));
             AMOF_HIP_TRY(ctx, hipGetLastError());
             unsigned long long key = 0;
-            AMOF_TRY(fetch(ctx, &key, lb.out + 2, sizeof key));      // (synchronises: `roots` is consumed)
+            AMOF_TRY(fetch(ctx, &key, lb.out + 2, sizeof key));
             if (key) *chmax = pa_unkey(key);
         }
     }
@@ -545,15 +557,26 @@ static int pa_free_sphere(Labeller &lb, const double *d_field, double dmax, doub
     return AMOF_OK;
 }
 
-// every threshold of one frame whose field lies on the device, then its free sphere
+// every threshold of one frame whose field lies on the device, then its free sphere.  With a hook (amof_pore_psd): the hook's
+// work is no labelling, the span of stage 2 is closed around it.
 static int pa_frame(Labeller &lb, const double *d_field, const double *thresholds, int32_t n_t, int want_free, double dmax, int64_t *access,
-                    double *free_sphere, int32_t *labels)
+                    double *free_sphere, int32_t *labels, int64_t f, PoreAccessHook *hook, StageSpans &spans)
 {
+    if (hook && hook->frame) AMOF_TRY(hook->frame(f, d_field, spans));
+    spans.begin(2);
     for (int32_t k = 0; k < n_t; k++) {
         AMOF_TRY(pa_open(lb, d_field, thresholds[k]));
         AMOF_TRY(pa_periodic(lb, d_field, access + (size_t)k * 4, labels ? labels + (size_t)k * (size_t)lb.g.G : nullptr, nullptr));
+        if (hook && hook->threshold) {
+            bool any = false;
+            AMOF_TRY(pa_mark_channels(lb, any));
+            spans.end();
+            AMOF_TRY(hook->threshold(f, k, d_field, lb.parent, lb.size, any, spans));
+            spans.begin(2);
+        }
     }
     if (want_free) AMOF_TRY(pa_free_sphere(lb, d_field, dmax, free_sphere));
+    spans.end();
     return AMOF_OK;
 }
 
@@ -574,9 +597,9 @@ static int pa_check_outputs(amof_ctx *ctx, int64_t F, int64_t G, const double *t
 
 using namespace amof;
 
-extern "C" int amof_pore_access(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
-                                const double *thresholds, int32_t n_t, int32_t want_free, uint64_t *hist, int64_t *counts, double *vmax,
-                                int64_t *argmax, int64_t *access, double *free_sphere, double *field, int32_t *labels)
+int amof::pore_access_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
+                          const double *thresholds, int32_t n_t, int32_t want_free, uint64_t *hist, int64_t *counts, double *vmax,
+                          int64_t *argmax, int64_t *access, double *free_sphere, double *field, int32_t *labels, PoreAccessHook *ahook)
 {
     if (!ctx) return AMOF_EINVAL;
     if (!t || !grid) return fail(ctx, AMOF_EINVAL, "NULL argument");
@@ -590,17 +613,16 @@ extern "C" int amof_pore_access(amof_ctx *ctx, const amof_traj *t, const double 
     }
     Labeller lb;
     PoreFieldHook hook;
-    hook.fixed_bytes = pa_fixed_bytes(G, (int64_t)grid[1] * grid[2] + (int64_t)grid[0] * grid[2] + (int64_t)grid[0] * grid[1], want_free != 0);
+    hook.fixed_bytes = pa_fixed_bytes(G, (int64_t)grid[1] * grid[2] + (int64_t)grid[0] * grid[2] + (int64_t)grid[0] * grid[1], want_free != 0) +
+                       (ahook ? ahook->fixed_bytes : 0);
     bool ready = false;
     hook.batch = [&](int64_t fb, int64_t nf, const double *d_field, StageSpans &spans) -> int {
         if (!ready) AMOF_TRY(pa_setup(lb, ctx, grid, pbc, want_free != 0));
         ready = true;
-        spans.begin(2);
         for (int64_t f = fb; f < fb + nf; f++)
             AMOF_TRY(pa_frame(lb, d_field + (size_t)(f - fb) * (size_t)G, thresholds, n_t, want_free, dmax, access + (size_t)f * n_t * 4,
                               free_sphere ? free_sphere + (size_t)f * 2 : nullptr,
-                              labels ? labels + (size_t)f * (size_t)n_t * (size_t)G : nullptr));
-        spans.end();
+                              labels ? labels + (size_t)f * (size_t)n_t * (size_t)G : nullptr, f, ahook, spans));
         return AMOF_OK;
     };
     const int rc = pore_field_run(ctx, t, radii, grid, dr, dmax, thresholds, n_t, hist, counts, vmax, argmax, field, &hook);
@@ -616,9 +638,17 @@ extern "C" int amof_pore_access(amof_ctx *ctx, const amof_traj *t, const double 
     return AMOF_OK;
 }
 
-extern "C" int amof_pore_access_field(amof_ctx *ctx, const double *field, int64_t n_frames, const int32_t *grid, const int32_t *pbc,
-                                      const double *thresholds, int32_t n_t, int32_t want_free, int64_t *access, double *free_sphere,
-                                      int32_t *labels)
+extern "C" int amof_pore_access(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
+                                const double *thresholds, int32_t n_t, int32_t want_free, uint64_t *hist, int64_t *counts, double *vmax,
+                                int64_t *argmax, int64_t *access, double *free_sphere, double *field, int32_t *labels)
+{
+    return pore_access_run(ctx, t, radii, grid, dr, dmax, thresholds, n_t, want_free, hist, counts, vmax, argmax, access, free_sphere, field,
+                           labels, nullptr);
+}
+
+int amof::pore_access_field_run(amof_ctx *ctx, const double *field, int64_t n_frames, const int32_t *grid, const int32_t *pbc,
+                                const double *thresholds, int32_t n_t, int32_t want_free, int64_t *access, double *free_sphere,
+                                int32_t *labels, PoreAccessHook *ahook)
 {
     if (!ctx) return AMOF_EINVAL;
     if (!grid || !pbc || n_frames < 0 || (n_frames > 0 && !field)) return fail(ctx, AMOF_EINVAL, "NULL argument");
@@ -642,19 +672,25 @@ extern "C" int amof_pore_access_field(amof_ctx *ctx, const double *field, int64_
     timing_dom_begin(ctx, pa_path(lb));
     for (int64_t f = 0; f < F; f++) {
         AMOF_HIP_TRY(ctx, hipMemcpyAsync(d_field, field + (size_t)f * (size_t)G, (size_t)G * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        spans.begin(2);
         const int rc = pa_frame(lb, (const double *)d_field, thresholds, n_t, want_free, 0.0, access + (size_t)f * n_t * 4,
-                                free_sphere ? free_sphere + (size_t)f * 2 : nullptr, labels ? labels + (size_t)f * (size_t)n_t * (size_t)G : nullptr);
+                                free_sphere ? free_sphere + (size_t)f * 2 : nullptr, labels ? labels + (size_t)f * (size_t)n_t * (size_t)G : nullptr,
+                                f, ahook, spans);
         if (rc != AMOF_OK) {
             if (access) std::fill(access, access + (size_t)F * n_t * 4, (int64_t)0);
             if (free_sphere) std::fill(free_sphere, free_sphere + (size_t)F * 2, 0.0);
             return rc;
         }
-        spans.end();
     }
     timing_dom_end(ctx, lb.labellings);
     timing_end(ctx);
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     spans.collect();
     return AMOF_OK;
+}
+
+extern "C" int amof_pore_access_field(amof_ctx *ctx, const double *field, int64_t n_frames, const int32_t *grid, const int32_t *pbc,
+                                      const double *thresholds, int32_t n_t, int32_t want_free, int64_t *access, double *free_sphere,
+                                      int32_t *labels)
+{
+    return pore_access_field_run(ctx, field, n_frames, grid, pbc, thresholds, n_t, want_free, access, free_sphere, labels, nullptr);
 }

@@ -22,7 +22,18 @@ components of {v >= rp} (6-neighbourhood of the grid) are labelled on the GPU (`
 amof_amd/csrc/pore_access.hip); a component that winds around the cell is a channel and its points are accessible, one
 that does not is a pocket.  ``free_sphere=True`` adds the largest free sphere Df -- twice the largest v at which the void still
 has a channel -- and Dif, the largest included sphere along the channels of that void.  include/amof_hip.h has the
-definitions.  Not computed: surface areas, the probe-occupiable volume, the Gelb-Gubbins pore size distribution.
+definitions.
+
+``psd=True`` adds the Gelb-Gubbins pore size distribution and the probe-occupiable volume.  Both come from the covering radius
+
+    w(p) = max { v(c) : v(c) >= 0, |c - p| <= v(c) }        (c: the grid points; v(p) where no sphere covers p)
+
+the radius of the largest sphere that overlaps no atom and covers p (``amof_pore_psd``, amof_amd/csrc/pore_cover.hip).  The
+fraction of points with w >= r is the cumulative pore volume V(r) of Gelb and Gubbins, its histogram is - dV/dr, and
+#{w >= rp} / G is the volume a probe of radius rp occupies -- the whole probe sphere, the quantity helium or nitrogen pore
+volumes are compared with; the probe-centre volume above understates it by a surface layer rp thick.  With
+``accessibility`` the occupiable volume is split into the part covered from a channel (POAV) and the rest (PONAV).
+Not computed: surface areas.
 """
 
 import logging
@@ -187,6 +198,42 @@ def access_columns(access, probe_counts, volume, mass, probes, grid):
     return cols
 
 
+def psd_columns(psd_counts, po_counts, po_access, volume, mass, probes, grid, dr):
+    """``(columns, psd)`` of ``psd=True`` from the library's integers: ``psd_counts`` u64 ``[F][nbins + 2]`` (points covered by no
+    sphere, the bins of the covering radius w over [0, dmax), w >= dmax), ``po_counts [F][n_probes]`` (points with w >= rp),
+    ``po_access [F][n_probes]`` or None (points covered from a channel of the void v >= rp).
+      columns  per probe rp POV_Volume_fraction-rp = po_count / G with its A^3 and cm^3/g as the PCV columns; with ``po_access``
+               POAV_* = po_access / G and PONAV_* = (po_count - po_access) / G (POAV + PONAV = POV in counts)
+      psd      r (bin centres), density: the trajectory mean of count / (G dr), - dV/dr as a fraction of the cell volume per
+               Angstrom; cumulative: the trajectory mean of the fraction of points with w >= the bin's lower edge, summed from
+               the integers, the points with w >= dmax included -- it starts at the covered fraction and never rises"""
+    psd_counts = np.asarray(psd_counts, dtype=np.uint64)
+    F = psd_counts.shape[0]
+    nbins = psd_counts.shape[1] - 2
+    G = int(grid[0]) * int(grid[1]) * int(grid[2])
+    po_counts = np.asarray(po_counts, dtype=np.int64).reshape(F, len(probes))
+    volume = np.asarray(volume, dtype=np.float64).reshape(F)
+    kinds = [("POV", po_counts)]
+    if po_access is not None:
+        po_access = np.asarray(po_access, dtype=np.int64).reshape(F, len(probes))
+        if (po_access > po_counts).any() or (po_access < 0).any():
+            raise ValueError("more points covered from channels than covered at all")
+        kinds += [("POAV", po_access), ("PONAV", po_counts - po_access)]
+    cols = {}
+    for k, rp in enumerate(probes):
+        for name, count in kinds:
+            frac = count[:, k].astype(np.float64) / G
+            cols[name + "_Volume_fraction-" + probe_label(rp)] = frac
+            cols[name + "_A^3-" + probe_label(rp)] = frac * volume
+            cols[name + "_cm^3/g-" + probe_label(rp)] = frac * volume * AVOGADRO_A3 / float(mass)
+    ints = psd_counts[:, 1:].astype(np.int64)                   # the bins, then w >= dmax
+    above = ints[:, ::-1].cumsum(axis=1)[:, ::-1][:, :nbins]    # points with w >= the lower edge of bin b
+    psd = pd.DataFrame({"r": (np.arange(nbins) + 0.5) * float(dr),
+                        "density": (ints[:, :nbins].astype(np.float64) / (G * float(dr))).mean(axis=0) if F else np.full(nbins, np.nan),
+                        "cumulative": (above.astype(np.float64) / G).mean(axis=0) if F else np.full(nbins, np.nan)})
+    return cols, psd
+
+
 def free_sphere_columns(free):
     """``Df = 2 t*`` and ``Dif`` from ``free [F][2]`` (t*, Dif / 2; inf: not resolved below dmax, 0: no channel at all)"""
     free = np.asarray(free, dtype=np.float64).reshape(-1, 2)
@@ -210,6 +257,12 @@ class Pore(Deferred):
                     Pockets-rp, Channel_dimension-rp (``access_columns``); .access int64 [F][n_probes][4]; with per_point
                     .labels int32 [F][n_probes][nx][ny][nz]: the smallest linear index of a point's component, -1 outside
       free_sphere=True: Df, Dif (``free_sphere_columns``); .free_sphere [F][2]: t* and Dif / 2
+      psd=True:     per probe radius POV_* (probe-occupiable volume), with accessibility POAV_* / PONAV_* (``psd_columns``);
+                    .psd: r, density, cumulative -- the pore size distribution - dV/dr and V(r), trajectory means;
+                    .psd_counts u64 [F][nbins + 2], .po_counts int64 [F][n_probes], with accessibility .po_access; with
+                    per_point .cover float64 [F][nx][ny][nz], the covering radius.  In a frame with overflow points (the
+                    warning below) the covering radius is a lower bound where it reaches dmax: the POV columns stay valid for
+                    rp <= dmax, the distribution above dmax is not resolved.
     These are grid estimates of geometric quantities, not Zeo++'s numbers (see the module's docstring).
     """
 
@@ -222,7 +275,7 @@ class Pore(Deferred):
     @classmethod
     def from_trajectory(cls, trajectory, delta_Step=1, first_frame=0, parallel=False, *, probe_radius=(0.0, 1.2), spacing=0.2,
                         grid=None, dr=0.05, dmax=None, radii=None, per_point=False, device=None, distributed=None, accessibility=False,
-                        free_sphere=False):
+                        free_sphere=False, psd=False):
         """
         Args:
             trajectory: list of ase.Atoms-like frames, a PackedTrajectory or an XyzStream
@@ -238,6 +291,8 @@ class Pore(Deferred):
             accessibility: label the void of every probe radius and split its volume into accessible and non-accessible
                 (every periodic grid axis then needs at least 3 points)
             free_sphere: the largest free sphere Df and Dif per frame (about log2 of the grid size labellings per frame)
+            psd: the pore size distribution and the probe-occupiable volume of every probe radius (one more pass over the
+                field, about as heavy as the field itself; with accessibility one more per probe radius that has a channel)
             device: GPU index or list of indices (default: LOCAL_RANK or 0)
             distributed: None -> the ranks of an initialised torch.distributed group take contiguous shares of the frames;
                 False -> single process; 'local' -> the trajectory is this rank's own block of frames
@@ -245,11 +300,11 @@ class Pore(Deferred):
         pore = cls()
         step = _trajectory.construct_step(delta_Step=delta_Step, first_frame=first_frame, number_of_frames=len(trajectory))
         pore.compute_pore(trajectory, step, probe_radius, spacing, grid, dr, dmax, radii, per_point, device=device,
-                          distributed=distributed, accessibility=accessibility, free_sphere=free_sphere)
+                          distributed=distributed, accessibility=accessibility, free_sphere=free_sphere, psd=psd)
         return pore
 
     def compute_pore(self, trajectory, step, probe_radius=(0.0, 1.2), spacing=0.2, grid=None, dr=0.05, dmax=None, radii=None,
-                     per_point=False, device=None, distributed=None, accessibility=False, free_sphere=False):
+                     per_point=False, device=None, distributed=None, accessibility=False, free_sphere=False, psd=False):
         packed = _setup.pack(trajectory, device, keep_stream=True)
         logger.info("Start pore analysis for %s frames", len(packed))
         kinds, _ = _hip.packed_species(packed)
@@ -293,16 +348,18 @@ class Pore(Deferred):
         frame_range = st.shard(F)
         G = grid[0] * grid[1] * grid[2]
 
-        accessibility, free_sphere = bool(accessibility), bool(free_sphere)
+        accessibility, free_sphere, psd = bool(accessibility), bool(free_sphere), bool(psd)
         labelled = accessibility or free_sphere
         want_labels = accessibility and per_point
         if labelled and any(p and n < 3 for p, n in zip(packed.pbc, grid)):
             raise ValueError("accessibility / free_sphere: a periodic grid axis needs at least 3 points, the grid is %s" % (grid,))
         base_cols = nbins + 2 + n_t + 6
-        cols = base_cols + (4 * n_t if labelled else 0) + (2 if free_sphere else 0)
+        access_cols = base_cols + (4 * n_t if labelled else 0) + (2 if free_sphere else 0)
+        cols = access_cols + ((nbins + 2 + n_t + (n_t if accessibility else 0)) if psd else 0)
+        want_cover = psd and per_point
 
         def finish_host(raw):
-            rows, field, labels = raw
+            rows, field, labels, cover = raw
             rows = np.asarray(rows, dtype=np.int64).reshape(-1, cols)
             tail = rows[:, nbins + 2 + n_t:base_cols].copy()
             self._assemble(rows[:, :nbins + 2].copy().view(np.uint64), rows[:, nbins + 2:nbins + 2 + n_t].copy(),
@@ -310,19 +367,35 @@ class Pore(Deferred):
                            tail[:, 3:].copy().view(np.float64), field, step, mass, probes, grid, dr, dmax, rs, kinds)
             if labelled:
                 self._assemble_access(rows[:, base_cols:base_cols + 4 * n_t].copy().reshape(-1, n_t, 4),
-                                      rows[:, base_cols + 4 * n_t:].copy().view(np.float64) if free_sphere else None, labels,
+                                      rows[:, base_cols + 4 * n_t:access_cols].copy().view(np.float64) if free_sphere else None, labels,
                                       accessibility, tail[:, 2].copy().view(np.float64), mass, probes, grid)
+            if psd:
+                more = rows[:, access_cols:]
+                self._assemble_psd(more[:, :nbins + 2].copy().view(np.uint64), more[:, nbins + 2:nbins + 2 + n_t].copy(),
+                                   more[:, nbins + 2 + n_t:].copy() if accessibility else None, cover,
+                                   tail[:, 2].copy().view(np.float64), mass, probes, grid, dr)
 
         def call(tr, frame_range=None):
             # one int64 row per frame -- histogram, probe counts, the bits of vmax, argmax, the bits of the cell volume and of
             # the position of vmax -- so that one gather merges the ranks
-            if labelled:
+            last = []
+            if psd:
+                res = list(ctx.pore_psd(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point,
+                                        accessibility=accessibility, free_sphere=free_sphere, labels=want_labels))
+                n_last = 2 + accessibility + per_point
+                last, res = res[len(res) - n_last:], res[:len(res) - n_last]
+            elif labelled:
                 res = list(ctx.pore_access(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point,
                                            free_sphere=free_sphere, labels=want_labels))
+            if labelled:
                 more = [res[4].reshape(-1, 4 * n_t)] + ([res.pop(5).view(np.int64)] if free_sphere else [])
                 res = res[:4] + res[5:]
+            elif psd:
+                more = []
             else:
                 res, more = ctx.pore_field(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point), []
+            if psd:
+                more += [last[0].view(np.int64), last[1]] + ([last[2]] if accessibility else [])
             hist, counts, vmax, argmax = res[:4]
             f0, f1 = (0, len(vmax)) if frame_range is None else frame_range
             c = np.asarray(tr.cell, dtype=np.float64).reshape(-1, 3, 3)
@@ -331,17 +404,17 @@ class Pore(Deferred):
             where = np.ascontiguousarray(positions(argmax, c, grid), dtype=np.float64).reshape(-1, 3)
             rows = np.concatenate([hist.view(np.int64), counts, vmax.view(np.int64)[:, None], argmax[:, None],
                                    volume.view(np.int64)[:, None], where.view(np.int64)] + more, axis=1)
-            return rows, (res[4] if per_point else None), (res[5] if want_labels else None)
+            return rows, (res[4] if per_point else None), (res[5] if want_labels else None), (last[-1] if want_cover else None)
 
         if _setup.streamed(st):
             def walk():
-                keep = [0] + ([1] if per_point else []) + ([2] if want_labels else [])
+                keep = [0] + ([1] if per_point else []) + ([2] if want_labels else []) + ([3] if want_cover else [])
 
                 def kept(batch):
                     res = call(batch)
                     return tuple(res[k] for k in keep)
                 got = _setup.walk(source, kept, ("cat",) * len(keep))
-                return tuple(got[keep.index(k)] if k in keep else None for k in range(3))
+                return tuple(got[keep.index(k)] if k in keep else None for k in range(4))
 
             self._defer(ctx, walk, finish_host)
             return
@@ -350,11 +423,12 @@ class Pore(Deferred):
             # this rank's kernels (a lane job: amof_amd/_lazy.py)
             if F == 0:
                 return (np.zeros((0, cols), dtype=np.int64), (np.zeros((0,) + grid) if per_point else None),
-                        (np.zeros((0, n_t) + grid, dtype=np.int32) if want_labels else None))
+                        (np.zeros((0, n_t) + grid, dtype=np.int32) if want_labels else None),
+                        (np.zeros((0,) + grid) if want_cover else None))
             return call(packed, frame_range)
 
         def finish(raw):
-            rows, field, labels = raw
+            rows, field, labels, cover = raw
             if sharded:
                 rows = _dist.all_gather_rows(rows, device=ctx.device)
                 if per_point:
@@ -363,7 +437,10 @@ class Pore(Deferred):
                 if want_labels:
                     labels = _dist.all_gather_rows(labels.reshape(-1, n_t * G).astype(np.int64), device=ctx.device)
                     labels = labels.astype(np.int32).reshape((-1, n_t) + grid)
-            finish_host((rows, field, labels))
+                if want_cover:
+                    cover = _dist.all_gather_rows(cover.reshape(-1, G).view(np.int64), device=ctx.device).view(np.float64)
+                    cover = cover.reshape((-1,) + grid)
+            finish_host((rows, field, labels, cover))
 
         self._defer(ctx, local, finish, collective=sharded)
 
@@ -395,6 +472,16 @@ class Pore(Deferred):
         if free is not None:
             self.free_sphere = free
             cols.update(free_sphere_columns(free))
+        self.data = pd.concat([self.data, pd.DataFrame(cols, index=self.data.index)], axis=1)
+
+    def _assemble_psd(self, psd_counts, po_counts, po_access, cover, volume, mass, probes, grid, dr):
+        """the columns and the distribution of ``psd`` behind the others (``psd_columns``)"""
+        self.psd_counts, self.po_counts = psd_counts, po_counts
+        if po_access is not None:
+            self.po_access = po_access
+        if cover is not None:
+            self.cover = cover
+        cols, self.psd = psd_columns(psd_counts, po_counts, po_access, volume, mass, probes, grid, dr)
         self.data = pd.concat([self.data, pd.DataFrame(cols, index=self.data.index)], axis=1)
 
     def write_to_file(self, path_to_output):

@@ -129,6 +129,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
  * after amof_pore_field: 2 the cell sort (0 on "pore_exact"), 3 the field kernels.
  * after amof_pore_access / amof_pore_access_field: 4 the labelling (amof_pore_access: 2 and 3 as amof_pore_field).
+ * after amof_pore_psd / amof_pore_psd_field: 5 the covering stage (2 .. 4 as amof_pore_access where those stages ran).
  * Returns < 0 if unavailable. */
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which);
 /* number of launches of the dominant kernel in the last call */
@@ -168,7 +169,10 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        re-evaluated in canonical float64), "pore_exact" (every atom per grid point in canonical float64: open axes,
  *        bricks too coarse for the cutoff or too full; also AMOF_PORE_EXACT=1)
  *   pore labelling (amof_pore_access, amof_pore_access_field) "pore_label_tile" (tiles labelled in LDS, tile faces merged in
- *        device memory), "pore_label_global" (every link merged in device memory; AMOF_PORE_LABEL_GLOBAL=1) */
+ *        device memory), "pore_label_global" (every link merged in device memory; AMOF_PORE_LABEL_GLOBAL=1)
+ *   pore covering (amof_pore_psd, amof_pore_psd_field) "pore_cover_brick" (bricks of grid points gather the centres whose
+ *        sphere reaches them from the source bricks within reach), "pore_cover_exact" (every offset within reach per grid
+ *        point: a brick's list too short, a reach of too many bricks; also AMOF_PORE_COVER_EXACT=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -534,6 +538,69 @@ int amof_pore_access_field(amof_ctx *ctx, const double *field /* host [n_frames]
                            const double *thresholds /* host [n_t] */, int32_t n_t, int32_t want_free,
                            int64_t *access /* host [n_frames][n_t][4] */, double *free_sphere /* host [n_frames][2] or NULL */,
                            int32_t *labels /* host [n_frames][n_t][G] or NULL */);
+
+/*
+ * Covering radius of the pore field: the Gelb-Gubbins pore size distribution and the probe-occupiable volume.
+ * (The reference reads POAV / PONAV from Zeo++ -volpo and the distribution from -psd, amof/pore/pysimmzeopp.py; this is the
+ * grid version on the field above and does not reproduce Zeo++'s numbers.)  The cumulative pore volume V(r) is the volume of
+ * the points that a sphere of radius r, overlapping no atom, can cover; - dV/dr is the pore size distribution, and V(rp) the
+ * volume a probe of radius rp occupies -- the whole probe sphere, not only its centre.  Both are read off one field over the
+ * grid, the covering radius w.  Let v be the (dmax-capped) field of amof_pore_field on the grid n of a frame with cell C:
+ *   step vectors   A_k[c] = C[k][c] / (double)n_k
+ *   offset distance  of an integer offset D = (Di, Dj, Dk): s_c = ((double)Di A_0[c] + (double)Dj A_1[c]) + (double)Dk A_2[c],
+ *                  d2(D) = (s_x s_x + s_y s_y) + s_z s_z -- float64 in this order, no fma.  It depends on the offset and the
+ *                  frame's cell only, not on the point.
+ *   target point   p + D: the grid point whose indices are those of p plus D, modulo n_k on a periodic axis; on an open axis an
+ *                  offset that leaves the grid does not exist
+ *   covering       a centre c = p + D COVERS p iff v(c) >= 0 and d2(D) <= v(c) v(c) (float64 product and compare)
+ *   covering radius  w(p) = max { v(c) : c covers p }; w(p) = v(p) if no centre covers p.  A point with v(p) >= 0 covers
+ *                  itself through D = 0, so an uncovered point has w = v < 0.  The maximum of IEEE numbers does not depend on
+ *                  the order: w is bit-identical on every path, batching, frame range and rank.
+ *   one image at most  every value of v is at most dmax, which is at most half the smallest periodic perpendicular height: no
+ *                  sphere reaches p through more than one image of its centre.  amof_pore_psd_field enforces the same on the
+ *                  field it is given: max(field) > half the smallest periodic perpendicular height (1 + 1e-12) of the frame's
+ *                  cell is AMOF_EINVAL.
+ *   overflow       where v is capped at dmax, w is a lower bound; such frames are flagged as for the largest included sphere
+ *                  (hist[f][nbins + 1] > 0).
+ * Per frame:
+ *   psd_hist [F][nbins + 2]: [0] points with w < 0 (covered by no sphere); [1 + b] points with b = (int)(w / dr) for
+ *     0 <= w < dmax, b < nbins; [nbins + 1] the rest (w >= dmax).  A row sums to G; nbins and dr are the field histogram's.
+ *   po_counts [F][n_t]: points with w >= thresholds[t] -- the probe-occupiable volume in points, at least counts[f][t]
+ *   po_access [F][n_t] (want_access; AMOF_EINVAL if NULL then): points covered by at least one centre that lies in a CHANNEL
+ *     of V(thresholds[t]) -- the components and channels of amof_pore_access; every such centre has v >= thresholds[t].  At
+ *     most po_counts; po_counts - po_access, the points a probe reaches only from pockets, is the non-accessible occupiable
+ *     count, so that POAV + PONAV = POV holds in integers.
+ *   cover (optional, may be NULL) host [F][G]: w itself; at most 4 GiB per frame (AMOF_ECAPACITY)
+ * amof_pore_psd: amof_pore_field -- or, with want_access or want_free, amof_pore_access, whose `access` array is then
+ * required -- with the same tiers, switches and outputs, bit for bit, and every batch's field covered where it lies.
+ * amof_pore_psd_field: the same analysis of a field the caller supplies (host [n_frames][G], finite) with the cell of every
+ * frame (host [n_frames][9], rows = cell vectors); pbc[3]: which grid axes are periodic (want_access: at least 3 points each).
+ * Paths (amof_last_path): "pore_cover_brick" -- a workgroup owns a brick of 8 x 8 x 8 points, keeps the source bricks and of
+ * those the centres whose sphere reaches the brick's bounding sphere, and every lane sweeps these records for its points --
+ * and "pore_cover_exact" -- a lane per point walks every offset with d2 <= (the frame's largest v)^2; also
+ * AMOF_PORE_COVER_EXACT=1, a brick that keeps more than 2048 source bricks (the frame is then run again on the exact path;
+ * AMOF_PORE_COVER_SRC_CAP=n lowers that limit, for tests), a reach of more than 32768 source bricks.  Both
+ * decide with the canonical compare above and give the same bits.  amof_last_kernel_seconds: which = 5 the covering stage
+ * (2 .. 4 as amof_pore_access); amof_last_kernel_launches: its passes.  amof_pore_cover_stats: out3 = destination bricks,
+ * source bricks kept, centre records swept, summed over the full passes of the last call on "pore_cover_brick".
+ * All outputs are overwritten (zeros after an error).  Errors: as amof_pore_field.
+ */
+int amof_pore_psd(amof_ctx *ctx, const amof_traj *traj, const double *radii /* host [S] */, const int32_t *grid /* host [3] */,
+                  double dr, double dmax, const double *thresholds /* host [n_t] */, int32_t n_t, int32_t want_access,
+                  int32_t want_free, uint64_t *hist /* host [F][nbins + 2] */, int64_t *counts /* host [F][n_t] */,
+                  double *vmax /* host [F] */, int64_t *argmax /* host [F] */,
+                  int64_t *access /* host [F][n_t][4]; may be NULL without want_access and want_free */,
+                  double *free_sphere /* host [F][2] or NULL */, double *field /* host [F][G] or NULL */,
+                  int32_t *labels /* host [F][n_t][G] or NULL */, uint64_t *psd_hist /* host [F][nbins + 2] */,
+                  int64_t *po_counts /* host [F][n_t] */, int64_t *po_access /* host [F][n_t]; NULL unless want_access */,
+                  double *cover /* host [F][G] or NULL */);
+int amof_pore_psd_field(amof_ctx *ctx, const double *field /* host [n_frames][G] */, const double *cells /* host [n_frames][9] */,
+                        int64_t n_frames, const int32_t *grid /* host [3] */, const int32_t *pbc /* host [3] */, double dr,
+                        double dmax, const double *thresholds /* host [n_t] */, int32_t n_t, int32_t want_access,
+                        uint64_t *psd_hist /* host [n_frames][nbins + 2] */, int64_t *po_counts /* host [n_frames][n_t] */,
+                        int64_t *po_access /* host [n_frames][n_t]; NULL unless want_access */,
+                        double *cover /* host [n_frames][G] or NULL */);
+int amof_pore_cover_stats(const amof_ctx *ctx, double *out3 /* host [3] */);
 
 /*
  * Static structure factor by direct summation over reciprocal-lattice vectors.
