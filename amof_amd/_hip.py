@@ -5,6 +5,7 @@ If the shared library is missing, or no GPU is visible, the analysis classes
 raise -- they never silently compute somewhere else.
 """
 
+import collections
 import ctypes
 import os
 import threading
@@ -413,6 +414,28 @@ def _label_cap(labels, n_t, G):
         raise AmofError(AMOF_ECAPACITY, "labels of %d thresholds x %d points exceed the 4 GiB a frame may take" % (n_t, G))
 
 
+# the arrays of the Pore calls in the order of the tuples ``pore_field`` / ``pore_access`` / ``pore_psd`` return: name, the flag that
+# asks for it (None: always), its shape behind [F] (b: nbins + 2, t: n_t, g: the grid, C-contiguous [G] to the library), dtype
+_PORE = (("hist", None, "b", np.uint64), ("counts", None, "t", np.int64), ("vmax", None, "", np.float64), ("argmax", None, "", np.int64),
+         ("access", "labelled", "t4", np.int64), ("free_sphere", "free_sphere", "2", np.float64), ("field", "per_point", "g", np.float64),
+         ("labels", "labels", "tg", np.int32), ("psd_hist", "psd", "b", np.uint64), ("po_counts", "psd", "t", np.int64),
+         ("po_access", "po_access", "t", np.int64), ("cover", "cover", "g", np.float64))
+PoreResult = collections.namedtuple("PoreResult", [x[0] for x in _PORE], defaults=(None,) * len(_PORE))
+
+
+def pore_names(per_point=False, labelled=False, free_sphere=False, labels=False, psd=False, accessibility=False):
+    """which arrays a call with these flags returns, in the tuple's order (``labelled``: ``pore_access``, or ``pore_psd`` with
+    ``accessibility`` or ``free_sphere``)"""
+    flags = dict(locals(), po_access=psd and accessibility, cover=psd and per_point)
+    return tuple(name for name, flag, _, _ in _PORE if flag is None or flags[flag])
+
+
+def _pore_alloc(names, F, n_t, nbins, shape):
+    """zeroed arrays of these names as a ``PoreResult``"""
+    dims = {"b": (nbins + 2,), "t": (n_t,), "4": (4,), "2": (2,), "g": tuple(shape)}
+    return PoreResult(**{name: np.zeros((F,) + sum((dims[c] for c in dim), ()), dtype=kind) for name, _, dim, kind in _PORE if name in names})
+
+
 def _span(given, n):
     """a ``frame_range`` / ``atom_range`` argument as ``(lo, hi)``: all ``n`` by default"""
     return (0, n) if given is None else tuple(given)
@@ -816,42 +839,9 @@ class Context(Lane):
                        _ptr(hist), _ptr(hist_tet), _ptr(sums), _ptr(pa)))
         return (hist, hist_tet, sums, pa) if per_atom else (hist, hist_tet, sums)
 
-    @_locked
-    def pore_field(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False):
-        """``(hist u64 [F][nbins + 2], counts int64 [F][n_t], vmax f64 [F], argmax int64 [F][, field f64 [F][nx][ny][nz]])``
-        of ``amof_pore_field`` over the frames of ``frame_range``: per frame the histogram of the distance ``v`` of every
-        point of the grid ``grid = (nx, ny, nz)`` over the cell to the nearest atomic surface (``radii [S]`` in Angstrom,
-        in ``kinds`` order; row: inside an atom, ``nbins = rint(dmax / dr)`` bins of ``[0, dmax)``, overflow), the points
-        with ``v >= thresholds[t]``, the largest ``v`` and its linear grid index; ``per_point``: the field itself
-        (include/amof_hip.h)."""
-        th = self._traj(packed, frame_range)
-        radii = np.ascontiguousarray(radii, dtype=np.float64).reshape(th.S)
-        grid = _i32(grid).reshape(3)
-        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
-        dr, dmax = float(dr), float(dmax)
-        if not (np.isfinite(dr) and dr > 0 and np.isfinite(dmax) and dmax > 0):
-            raise ValueError("dr and dmax must be finite and > 0")
-        nbins = int(np.rint(dmax / dr))
-        if nbins < 1 or (grid < 1).any() or int(grid[0]) * int(grid[1]) * int(grid[2]) > 2 ** 31 - 1:
-            raise ValueError("dmax / dr rounds to no bin, or a grid that is not 1 .. 2^31 - 1 points")
-        F, G = th.n_frames, int(grid[0]) * int(grid[1]) * int(grid[2])
-        hist = np.zeros((F, nbins + 2), dtype=np.uint64)
-        counts = np.zeros((F, len(thr)), dtype=np.int64)
-        vmax, argmax = np.zeros(F, dtype=np.float64), np.zeros(F, dtype=np.int64)
-        field = np.zeros((F, G), dtype=np.float64) if per_point else None
-        self._check(self._lib.amof_pore_field(self._h, ctypes.byref(th.c), _ptr(radii), _ptr(grid), dr, dmax, _ptr(thr), len(thr),
-                                              _ptr(hist), _ptr(counts), _ptr(vmax), _ptr(argmax), _ptr(field)))
-        res = (hist, counts, vmax, argmax)
-        return res + (field.reshape((F,) + tuple(int(x) for x in grid)),) if per_point else res
-
-    @_locked
-    def pore_access(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, free_sphere=False,
-                    labels=False):
-        """``pore_field``'s results -- the same bits -- followed by ``access int64 [F][n_t][4]`` (accessible points, channels,
-        pockets, largest channel dimension of the void ``v >= thresholds[t]``), then, each only if asked for, ``free_sphere
-        f64 [F][2]`` (t* and Dif / 2; +inf: not resolved below dmax), ``field f64 [F][nx][ny][nz]`` (``per_point``) and
-        ``labels int32 [F][n_t][nx][ny][nz]`` (the smallest linear index of a point's periodic component, -1 outside the
-        void): ``amof_pore_access`` (include/amof_hip.h has the definitions)."""
+    def _pore_atoms(self, packed, radii, grid, dr, dmax, thresholds, frame_range, **flags):
+        """the three calls that take atoms -- ``amof_pore_field``, ``amof_pore_access`` (``labelled``), ``amof_pore_psd``
+        (``psd``) -- as a ``PoreResult``; ``flags``: ``pore_names``'"""
         th = self._traj(packed, frame_range)
         radii = np.ascontiguousarray(radii, dtype=np.float64).reshape(th.S)
         grid = _i32(grid).reshape(3)
@@ -863,22 +853,54 @@ class Context(Lane):
         if nbins < 1 or (grid < 1).any() or int(grid[0]) * int(grid[1]) * int(grid[2]) > 2 ** 31 - 1:
             raise ValueError("dmax / dr rounds to no bin, or a grid that is not 1 .. 2^31 - 1 points")
         shape = tuple(int(x) for x in grid)
-        F, G = th.n_frames, shape[0] * shape[1] * shape[2]
-        _label_cap(labels, len(thr), G)
-        hist = np.zeros((F, nbins + 2), dtype=np.uint64)
-        counts = np.zeros((F, len(thr)), dtype=np.int64)
-        vmax, argmax = np.zeros(F, dtype=np.float64), np.zeros(F, dtype=np.int64)
-        access = np.zeros((F, len(thr), 4), dtype=np.int64)
-        free = np.zeros((F, 2), dtype=np.float64) if free_sphere else None
-        field = np.zeros((F, G), dtype=np.float64) if per_point else None
-        lab = np.zeros((F, len(thr), G), dtype=np.int32) if labels else None
-        self._check(self._lib.amof_pore_access(self._h, ctypes.byref(th.c), _ptr(radii), _ptr(grid), dr, dmax, _ptr(thr), len(thr),
-                                               int(bool(free_sphere)), _ptr(hist), _ptr(counts), _ptr(vmax), _ptr(argmax), _ptr(access),
-                                               _ptr(free), _ptr(field), _ptr(lab)))
-        res = (hist, counts, vmax, argmax, access)
-        res += (free,) if free_sphere else ()
-        res += (field.reshape((F,) + shape),) if per_point else ()
-        return res + ((lab.reshape((F, len(thr)) + shape),) if labels else ())
+        _label_cap(flags.get("labels"), len(thr), shape[0] * shape[1] * shape[2])
+        r = _pore_alloc(pore_names(**flags), th.n_frames, len(thr), nbins, shape)
+        head = (self._h, ctypes.byref(th.c), _ptr(radii), _ptr(grid), dr, dmax, _ptr(thr), len(thr))
+        rows = (_ptr(r.hist), _ptr(r.counts), _ptr(r.vmax), _ptr(r.argmax))
+        more = (_ptr(r.access), _ptr(r.free_sphere), _ptr(r.field), _ptr(r.labels))
+        if flags.get("psd"):
+            rc = self._lib.amof_pore_psd(*head, int(bool(flags.get("accessibility"))), int(bool(flags.get("free_sphere"))), *rows, *more,
+                                         _ptr(r.psd_hist), _ptr(r.po_counts), _ptr(r.po_access), _ptr(r.cover))
+        elif flags.get("labelled"):
+            rc = self._lib.amof_pore_access(*head, int(bool(flags.get("free_sphere"))), *rows, *more)
+        else:
+            rc = self._lib.amof_pore_field(*head, *rows, _ptr(r.field))
+        self._check(rc)
+        return r
+
+    def _pore_given_field(self, field, pbc, thresholds):
+        """what the two calls on a supplied field ``[F][nx][ny][nz]`` share: ``(field, F, shape, grid, periodic, thresholds)``"""
+        field = np.ascontiguousarray(field, dtype=np.float64)
+        if field.ndim != 4:
+            raise ValueError("field must be [F][nx][ny][nz]")
+        F, shape = field.shape[0], tuple(int(x) for x in field.shape[1:])
+        if min(shape) < 1 or shape[0] * shape[1] * shape[2] > 2 ** 31 - 1:
+            raise ValueError("a grid that is not 1 .. 2^31 - 1 points")
+        per = _i32([1 if x else 0 for x in pbc]).reshape(3)
+        return field, F, shape, _i32(shape), per, np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+
+    @_locked
+    def pore_field(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False):
+        """``(hist u64 [F][nbins + 2], counts int64 [F][n_t], vmax f64 [F], argmax int64 [F][, field f64 [F][nx][ny][nz]])``
+        of ``amof_pore_field`` over the frames of ``frame_range``: per frame the histogram of the distance ``v`` of every
+        point of the grid ``grid = (nx, ny, nz)`` over the cell to the nearest atomic surface (``radii [S]`` in Angstrom,
+        in ``kinds`` order; row: inside an atom, ``nbins = rint(dmax / dr)`` bins of ``[0, dmax)``, overflow), the points
+        with ``v >= thresholds[t]``, the largest ``v`` and its linear grid index; ``per_point``: the field itself
+        (include/amof_hip.h)."""
+        r = self._pore_atoms(packed, radii, grid, dr, dmax, thresholds, frame_range, per_point=bool(per_point))
+        return tuple(x for x in r if x is not None)
+
+    @_locked
+    def pore_access(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, free_sphere=False,
+                    labels=False):
+        """``pore_field``'s results -- the same bits -- followed by ``access int64 [F][n_t][4]`` (accessible points, channels,
+        pockets, largest channel dimension of the void ``v >= thresholds[t]``), then, each only if asked for, ``free_sphere
+        f64 [F][2]`` (t* and Dif / 2; +inf: not resolved below dmax), ``field f64 [F][nx][ny][nz]`` (``per_point``) and
+        ``labels int32 [F][n_t][nx][ny][nz]`` (the smallest linear index of a point's periodic component, -1 outside the
+        void): ``amof_pore_access`` (include/amof_hip.h has the definitions)."""
+        r = self._pore_atoms(packed, radii, grid, dr, dmax, thresholds, frame_range, per_point=bool(per_point), labelled=True,
+                             free_sphere=bool(free_sphere), labels=bool(labels))
+        return tuple(x for x in r if x is not None)
 
     @_locked
     def pore_access_field(self, field, pbc=(True, True, True), thresholds=(), free_sphere=False, labels=False):
@@ -886,23 +908,12 @@ class Context(Lane):
         ``amof_pore_access_field``: the periodic components of ``{field >= thresholds[t]}`` of a field ``[F][nx][ny][nz]`` the
         caller supplies (finite; ``pbc``: which grid axes are periodic) -- ``Pore(per_point=True).field`` or any other.
         Here t* (``free_sphere[:, 0]``) is the largest field value of any sign whose void has a channel, -inf without one."""
-        field = np.ascontiguousarray(field, dtype=np.float64)
-        if field.ndim != 4:
-            raise ValueError("field must be [F][nx][ny][nz]")
-        F, shape = field.shape[0], tuple(int(x) for x in field.shape[1:])
-        grid = _i32(shape)
-        G = shape[0] * shape[1] * shape[2]
-        if min(shape) < 1 or G > 2 ** 31 - 1:
-            raise ValueError("a grid that is not 1 .. 2^31 - 1 points")
-        per = _i32([1 if x else 0 for x in pbc]).reshape(3)
-        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
-        _label_cap(labels, len(thr), G)
-        access = np.zeros((F, len(thr), 4), dtype=np.int64)
-        free = np.zeros((F, 2), dtype=np.float64) if free_sphere else None
-        lab = np.zeros((F, len(thr), G), dtype=np.int32) if labels else None
-        self._check(self._lib.amof_pore_access_field(self._h, _ptr(field), F, _ptr(grid), _ptr(per), _ptr(thr), len(thr),
-                                                     int(bool(free_sphere)), _ptr(access), _ptr(free), _ptr(lab)))
-        return access, free, (lab.reshape((F, len(thr)) + shape) if labels else None)
+        field, F, shape, grid, per, thr = self._pore_given_field(field, pbc, thresholds)
+        _label_cap(labels, len(thr), shape[0] * shape[1] * shape[2])
+        r = _pore_alloc(("access",) + ("free_sphere",) * bool(free_sphere) + ("labels",) * bool(labels), F, len(thr), 0, shape)
+        self._check(self._lib.amof_pore_access_field(self._h, _ptr(field), F, _ptr(grid), _ptr(per), _ptr(thr), len(thr), int(bool(free_sphere)),
+                                                     _ptr(r.access), _ptr(r.free_sphere), _ptr(r.labels)))
+        return r.access, r.free_sphere, r.labels
 
     @_locked
     def pore_psd(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, accessibility=False,
@@ -913,43 +924,10 @@ class Context(Lane):
         int64 [F][n_t]`` (points with ``w >= thresholds[t]``: the probe-occupiable volume), with ``accessibility`` ``po_access
         int64 [F][n_t]`` (points covered from a channel of the void ``v >= thresholds[t]``) and with ``per_point`` ``cover f64
         [F][nx][ny][nz]`` (``w`` itself).  include/amof_hip.h has the definitions."""
-        th = self._traj(packed, frame_range)
-        radii = np.ascontiguousarray(radii, dtype=np.float64).reshape(th.S)
-        grid = _i32(grid).reshape(3)
-        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
-        dr, dmax = float(dr), float(dmax)
-        if not (np.isfinite(dr) and dr > 0 and np.isfinite(dmax) and dmax > 0):
-            raise ValueError("dr and dmax must be finite and > 0")
-        nbins = int(np.rint(dmax / dr))
-        if nbins < 1 or (grid < 1).any() or int(grid[0]) * int(grid[1]) * int(grid[2]) > 2 ** 31 - 1:
-            raise ValueError("dmax / dr rounds to no bin, or a grid that is not 1 .. 2^31 - 1 points")
-        shape = tuple(int(x) for x in grid)
-        F, G = th.n_frames, shape[0] * shape[1] * shape[2]
-        accessibility, free_sphere = bool(accessibility), bool(free_sphere)
-        labelled = accessibility or free_sphere
-        labels = bool(labels) and labelled
-        _label_cap(labels, len(thr), G)
-        hist = np.zeros((F, nbins + 2), dtype=np.uint64)
-        counts = np.zeros((F, len(thr)), dtype=np.int64)
-        vmax, argmax = np.zeros(F, dtype=np.float64), np.zeros(F, dtype=np.int64)
-        access = np.zeros((F, len(thr), 4), dtype=np.int64) if labelled else None
-        free = np.zeros((F, 2), dtype=np.float64) if free_sphere else None
-        field = np.zeros((F, G), dtype=np.float64) if per_point else None
-        lab = np.zeros((F, len(thr), G), dtype=np.int32) if labels else None
-        psd_hist = np.zeros((F, nbins + 2), dtype=np.uint64)
-        po_counts = np.zeros((F, len(thr)), dtype=np.int64)
-        po_access = np.zeros((F, len(thr)), dtype=np.int64) if accessibility else None
-        cover = np.zeros((F, G), dtype=np.float64) if per_point else None
-        self._check(self._lib.amof_pore_psd(self._h, ctypes.byref(th.c), _ptr(radii), _ptr(grid), dr, dmax, _ptr(thr), len(thr),
-                                            int(accessibility), int(free_sphere), _ptr(hist), _ptr(counts), _ptr(vmax), _ptr(argmax),
-                                            _ptr(access), _ptr(free), _ptr(field), _ptr(lab), _ptr(psd_hist), _ptr(po_counts),
-                                            _ptr(po_access), _ptr(cover)))
-        res = (hist, counts, vmax, argmax) + ((access,) if labelled else ())
-        res += (free,) if free_sphere else ()
-        res += (field.reshape((F,) + shape),) if per_point else ()
-        res += (lab.reshape((F, len(thr)) + shape),) if labels else ()
-        res += (psd_hist, po_counts) + ((po_access,) if accessibility else ())
-        return res + ((cover.reshape((F,) + shape),) if per_point else ())
+        labelled = bool(accessibility or free_sphere)
+        r = self._pore_atoms(packed, radii, grid, dr, dmax, thresholds, frame_range, per_point=bool(per_point), labelled=labelled,
+                             free_sphere=bool(free_sphere), labels=bool(labels) and labelled, psd=True, accessibility=bool(accessibility))
+        return tuple(x for x in r if x is not None)
 
     @_locked
     def pore_psd_field(self, field, cells, pbc, dr, dmax, thresholds=(), accessibility=False, per_point=False):
@@ -957,14 +935,7 @@ class Context(Lane):
         [F][nx][ny][nz] or None)`` of ``amof_pore_psd_field``: the covering radius of a field ``[F][nx][ny][nz]`` the caller
         supplies (finite; no value above half the smallest periodic perpendicular height of its frame's cell), ``cells
         [F][3][3]`` or one cell for all frames, ``pbc``: which grid axes are periodic."""
-        field = np.ascontiguousarray(field, dtype=np.float64)
-        if field.ndim != 4:
-            raise ValueError("field must be [F][nx][ny][nz]")
-        F, shape = field.shape[0], tuple(int(x) for x in field.shape[1:])
-        grid = _i32(shape)
-        G = shape[0] * shape[1] * shape[2]
-        if min(shape) < 1 or G > 2 ** 31 - 1:
-            raise ValueError("a grid that is not 1 .. 2^31 - 1 points")
+        field, F, shape, grid, per, thr = self._pore_given_field(field, pbc, thresholds)
         cells = np.asarray(cells, dtype=np.float64).reshape(-1, 9)
         if cells.shape[0] == 1:
             cells = np.broadcast_to(cells, (F, 9))
@@ -974,17 +945,11 @@ class Context(Lane):
         dr, dmax = float(dr), float(dmax)
         if not (np.isfinite(dr) and dr > 0 and np.isfinite(dmax) and dmax > 0) or int(np.rint(dmax / dr)) < 1:
             raise ValueError("dr and dmax must be finite and > 0, dmax at least one bin")
-        nbins = int(np.rint(dmax / dr))
-        per = _i32([1 if x else 0 for x in pbc]).reshape(3)
-        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
-        psd_hist = np.zeros((F, nbins + 2), dtype=np.uint64)
-        po_counts = np.zeros((F, len(thr)), dtype=np.int64)
-        po_access = np.zeros((F, len(thr)), dtype=np.int64) if accessibility else None
-        cover = np.zeros((F, G), dtype=np.float64) if per_point else None
-        self._check(self._lib.amof_pore_psd_field(self._h, _ptr(field), _ptr(cells), F, _ptr(grid), _ptr(per), dr, dmax, _ptr(thr),
-                                                  len(thr), int(bool(accessibility)), _ptr(psd_hist), _ptr(po_counts), _ptr(po_access),
-                                                  _ptr(cover)))
-        return psd_hist, po_counts, po_access, (cover.reshape((F,) + shape) if per_point else None)
+        names = ("psd_hist", "po_counts") + ("po_access",) * bool(accessibility) + ("cover",) * bool(per_point)
+        r = _pore_alloc(names, F, len(thr), int(np.rint(dmax / dr)), shape)
+        self._check(self._lib.amof_pore_psd_field(self._h, _ptr(field), _ptr(cells), F, _ptr(grid), _ptr(per), dr, dmax, _ptr(thr), len(thr),
+                                                  int(bool(accessibility)), _ptr(r.psd_hist), _ptr(r.po_counts), _ptr(r.po_access), _ptr(r.cover)))
+        return r.psd_hist, r.po_counts, r.po_access, r.cover
 
     def pore_cover_stats(self):
         """``{"bricks", "source_bricks", "records"}`` summed over the full passes of the last ``pore_psd`` / ``pore_psd_field`` on
@@ -1231,8 +1196,7 @@ class MultiContext(object):
     def pore_field(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False):
         """frames sharded over the devices as ``cn_count``'s: every output is per frame, the rows concatenate"""
         return self._sharded("pore_field", packed, _span(frame_range, packed.n_frames), "frame_range",
-                             ("cat",) * (4 + bool(per_point)), radii, grid, dr, dmax, thresholds, copy_frames=True,
-                             per_point=per_point)
+                             ("cat",) * (4 + bool(per_point)), radii, grid, dr, dmax, thresholds, copy_frames=True, per_point=per_point)
 
     def pore_access(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, free_sphere=False,
                     labels=False):
@@ -1247,8 +1211,8 @@ class MultiContext(object):
     def pore_psd(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False, accessibility=False,
                  free_sphere=False, labels=False):
         """frames sharded over the devices as ``pore_access``'s: every output is per frame, the rows concatenate"""
-        labelled = bool(accessibility) or bool(free_sphere)
-        n = (4 + labelled + bool(free_sphere) + bool(per_point) + (bool(labels) and labelled) + 2 + bool(accessibility) + bool(per_point))
+        labelled = bool(accessibility or free_sphere)
+        n = len(pore_names(bool(per_point), labelled, bool(free_sphere), bool(labels) and labelled, True, bool(accessibility)))
         return self._sharded("pore_psd", packed, _span(frame_range, packed.n_frames), "frame_range", ("cat",) * n, radii, grid, dr,
                              dmax, thresholds, copy_frames=True, per_point=per_point, accessibility=accessibility,
                              free_sphere=free_sphere, labels=labels)

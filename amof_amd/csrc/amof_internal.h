@@ -6,7 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <functional>
+#include <algorithm>
 #include <map>
 #include <mutex>
 #include <string>
@@ -17,6 +17,7 @@
 #include "../../include/amof_hip.h"
 #include "guard_math.h"
 #include "lag_work.h"
+#include "pore_check.h"
 
 namespace amof {
 
@@ -416,33 +417,98 @@ struct StageSpans {
     }
 };
 
-// amof_pore_field's tiers (pore.hip) for a caller that works on the field where it lies: with a hook, the field of every batch
-// of frames [fb, fb + nf) is kept in device memory ([nf][G]) and handed to `batch` on the context's stream, after the field
-// kernel and before the next batch overwrites it.  fixed_bytes: the hook's own scratch, taken off the batch budget.
-struct PoreFieldHook {
-    size_t fixed_bytes = 0;
-    std::function<int(int64_t fb, int64_t nf, const double *d_field, StageSpans &spans)> batch;
-};
-int pore_field_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
-                   const double *thresholds, int32_t n_t, uint64_t *hist, int64_t *counts, double *vmax, int64_t *argmax,
-                   double *field, PoreFieldHook *hook);
+// ------------------------------------------------------------------ Pore --
+// The host scaffolding of amof_pore_field, amof_pore_access[_field] and amof_pore_psd[_field] (pore.hip, pore_access.hip,
+// pore_cover.hip).  Every entry point reads: check (pore_check.h), fill PoreOutputs, pick stages, run one field source, finish.
+inline int pore_refuse(amof_ctx *ctx, const pore_check::Verdict &v) { return v.code == AMOF_OK ? AMOF_OK : fail(ctx, v.code, "%s", v.text); }
 
-// amof_pore_access / amof_pore_access_field (pore_access.hip) for a caller that works beside the labelling (amof_pore_psd,
-// pore_cover.hip): `frame` runs before a frame's first labelling; `threshold` after threshold k of the frame is labelled --
-// parent[] then holds the periodic labels (-1 outside the void) and mark[root] < 0 for the root of every channel (channels:
-// whether there is one).  Both run on the context's stream, outside the labelling's span; fixed_bytes as PoreFieldHook's.
-struct PoreAccessHook {
-    size_t fixed_bytes = 0;
-    std::function<int(int64_t f, const double *d_field, StageSpans &spans)> frame;
-    std::function<int(int64_t f, int32_t k, const double *d_field, const int32_t *parent, const int32_t *mark, bool channels,
-                      StageSpans &spans)> threshold;
+// The caller's arrays as the entry point got them; one it did not ask for is nulled.  F, G, n_t and nbins stay 0 until the checks of
+// the arguments that size the arrays have passed.  zero() is the documented "zeros after an error": an entry point calls it once the
+// record is complete (without the per-point arrays: success overwrites them in full), the destructor again unless keep(AMOF_OK) ran.
+struct PoreOutputs {
+    uint64_t *hist = nullptr;           // [F][nbins + 2]
+    int64_t *counts = nullptr;          // [F][n_t]
+    double *vmax = nullptr;             // [F]
+    int64_t *argmax = nullptr;          // [F]
+    double *field = nullptr;            // [F][G]
+    int64_t *access = nullptr;          // [F][n_t][4]
+    double *free_sphere = nullptr;      // [F][2]
+    int32_t *labels = nullptr;          // [F][n_t][G]
+    uint64_t *psd_hist = nullptr;       // [F][nbins + 2]
+    int64_t *po_counts = nullptr, *po_access = nullptr;     // [F][n_t]
+    double *cover = nullptr;            // [F][G]
+    int64_t F = 0, G = 0;
+    int32_t nbins = 0, n_t = 0;
+    bool kept = false;
+    void sized(int64_t frames, const int32_t *grid, int32_t thresholds) { F = frames; G = (int64_t)grid[0] * grid[1] * grid[2]; n_t = thresholds; }
+    template <typename T> static void clear(T *p, size_t n) { if (p) std::fill(p, p + n, (T)0); }
+    void zero(bool per_point) const
+    {
+        if (F <= 0) return;
+        const size_t f = (size_t)F, g = per_point ? (size_t)G : 0, t = (size_t)n_t, row = nbins > 0 ? (size_t)nbins + 2 : 0;
+        clear(hist, f * row), clear(counts, f * t), clear(vmax, f), clear(argmax, f), clear(field, f * g);
+        clear(access, f * t * 4), clear(free_sphere, f * 2), clear(labels, f * t * g);
+        clear(psd_hist, f * row), clear(po_counts, f * t), clear(po_access, f * t), clear(cover, f * g);
+    }
+    int keep(int rc) { kept = rc == AMOF_OK; return rc; }
+    ~PoreOutputs() { if (!kept) zero(true); }       // (a return without keep() while F == 0 zeroes nothing)
+    PoreOutputs(const PoreOutputs &) = delete;      // (a copy would zero the caller's arrays when it dies)
+    PoreOutputs &operator=(const PoreOutputs &) = delete;
 };
-int pore_access_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
-                    const double *thresholds, int32_t n_t, int32_t want_free, uint64_t *hist, int64_t *counts, double *vmax,
-                    int64_t *argmax, int64_t *access, double *free_sphere, double *field, int32_t *labels, PoreAccessHook *hook);
-int pore_access_field_run(amof_ctx *ctx, const double *field, int64_t n_frames, const int32_t *grid, const int32_t *pbc,
-                          const double *thresholds, int32_t n_t, int32_t want_free, int64_t *access, double *free_sphere,
-                          int32_t *labels, PoreAccessHook *hook);
+
+// The arguments of an entry point: atoms (t, radii) or a field of the caller (field [n_frames][G]; cells [n_frames][9]: amof_pore_psd_field)
+struct PoreInputs {
+    const amof_traj *t;
+    const double *radii, *field, *cells;
+    int64_t n_frames;
+    const int32_t *grid, *pbc;      // pbc [3]: nonzero = periodic
+    double dr, dmax;
+    const double *thresholds;
+    int32_t n_t, want_access, want_free;
+};
+
+// What runs on every frame's field while it lies in device memory: the labelling (pore_access.hip) and the covering radius
+// (pore_cover.hip), each optional; both states belong to their files
+struct Labeller;
+struct CoverCall;
+size_t pore_label_fixed_bytes(const Labeller &lb);
+int pore_label_setup(Labeller &lb);
+int pore_label_frame(Labeller &lb, int64_t f, const double *d_field, CoverCall *cover, StageSpans &spans);
+void pore_label_report(const Labeller &lb);
+size_t pore_cover_fixed_bytes(const CoverCall &c);
+int pore_cover_setup(CoverCall &c);
+void pore_cover_restart(CoverCall &c);
+int pore_cover_frame(CoverCall &c, int64_t f, const double *d_field, StageSpans &spans);
+int pore_cover_threshold(CoverCall &c, int64_t f, int32_t k, const double *d_field, const int32_t *parent, const int32_t *mark, bool channels,
+                         StageSpans &spans);
+void pore_cover_report(const CoverCall &c);
+struct PoreStages {
+    Labeller *label = nullptr;
+    CoverCall *cover = nullptr;
+    bool cover_access = false;      // after every labelled threshold: the covering pass from that threshold's channels
+    size_t fixed_bytes() const { return (label ? pore_label_fixed_bytes(*label) : 0) + (cover ? pore_cover_fixed_bytes(*cover) : 0); }
+    int setup()
+    {
+        if (label) AMOF_TRY(pore_label_setup(*label));
+        return cover ? pore_cover_setup(*cover) : AMOF_OK;
+    }
+    // pore_brick gave up after its batches ran and pore_exact hands every frame over again: the covering stage's counters
+    // (launches, reported path, amof_pore_cover_stats) start over, the labeller's count of labellings goes on
+    void restart() { if (cover) pore_cover_restart(*cover); }
+    int frame(int64_t f, const double *d_field, StageSpans &spans)
+    {
+        if (cover) AMOF_TRY(pore_cover_frame(*cover, f, d_field, spans));
+        return label ? pore_label_frame(*label, f, d_field, cover_access ? cover : nullptr, spans) : AMOF_OK;
+    }
+    void report() const { if (label) pore_label_report(*label); if (cover) pore_cover_report(*cover); }
+};
+
+// the field from atoms: amof_pore_field's tiers and batches, the stages behind every batch (pore.hip)
+int pore_field_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, PoreStages *stages);
+// the field the caller supplies: frame by frame into device memory and through the stages; path: what the call reports meanwhile
+int pore_given_field_run(amof_ctx *ctx, const PoreInputs &in, const PoreOutputs &out, PoreStages &stages, const char *path);
+// the labelling stage on either source, beside a covering stage (amof_pore_psd[_field]) or without (cover null)
+int pore_access_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, CoverCall *cover);
 
 // ---------------------------------------------------------------- LDS-DMA --
 typedef __attribute__((address_space(1))) const void *gptr_t;

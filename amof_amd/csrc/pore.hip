@@ -363,7 +363,7 @@ struct PoreCall {
     long long *d_argmax = nullptr;
     double *field_host = nullptr;
     int64_t batch_cap = 0;      // AMOF_PORE_BATCH (0: none)
-    PoreFieldHook *hook = nullptr;      // amof_pore_access: the batch's field stays on the device and is labelled there
+    PoreStages *stages = nullptr;       // the batch's field stays on the device and goes through them frame by frame
 };
 
 static size_t pore_lds(const PoreArgs &a)
@@ -383,8 +383,8 @@ static hipError_t pore_launch(Kernel kern, dim3 grid, size_t lds, hipStream_t st
 // frames per batch: the partial table, the field (if asked for) and `per_frame` more bytes of scratch within 1 GiB
 static int64_t pore_batch(const PoreCall &c, int64_t nwg, size_t per_frame)
 {
-    per_frame += (size_t)nwg * (sizeof(double) + sizeof(int32_t)) + (c.field_host || c.hook ? (size_t)c.G * sizeof(double) : 0);
-    const size_t budget = ((size_t)1 << 30) - std::min<size_t>(c.hook ? c.hook->fixed_bytes : 0, (size_t)1 << 29);
+    per_frame += (size_t)nwg * (sizeof(double) + sizeof(int32_t)) + (c.field_host || c.stages ? (size_t)c.G * sizeof(double) : 0);
+    const size_t budget = ((size_t)1 << 30) - std::min<size_t>(c.stages ? c.stages->fixed_bytes() : 0, (size_t)1 << 29);
     int64_t FB = std::max<int64_t>(1, (int64_t)budget / (int64_t)std::max<size_t>(1, per_frame));
     FB = std::min<int64_t>(std::min<int64_t>(FB, 32768), c.t->n_frames);
     if (c.batch_cap > 0) FB = std::min(FB, c.batch_cap);
@@ -401,7 +401,7 @@ static int pore_batches(PoreCall &c, int64_t nwg, int64_t FB, Launch &&launch)
     void *d_pv, *d_pi, *d_field = nullptr;
     AMOF_TRY(ensure(ctx, SLOT_AUX2, (size_t)FB * nwg * sizeof(double), &d_pv));
     AMOF_TRY(ensure(ctx, SLOT_AUX3, (size_t)FB * nwg * sizeof(int32_t), &d_pi));
-    if (c.field_host || c.hook) AMOF_TRY(ensure(ctx, SLOT_OUT1, (size_t)FB * (size_t)c.G * sizeof(double), &d_field));
+    if (c.field_host || c.stages) AMOF_TRY(ensure(ctx, SLOT_OUT1, (size_t)FB * (size_t)c.G * sizeof(double), &d_field));
     a.part_v = (double *)d_pv;
     a.part_i = (int32_t *)d_pi;
     a.field = (double *)d_field;
@@ -418,7 +418,8 @@ static int pore_batches(PoreCall &c, int64_t nwg, int64_t FB, Launch &&launch)
         AMOF_HIP_TRY(ctx, hipGetLastError());
         launches++;
         if (c.field_host) AMOF_TRY(fetch(ctx, c.field_host + (size_t)fb * (size_t)c.G, d_field, (size_t)nf * (size_t)c.G * sizeof(double)));
-        if (c.hook) AMOF_TRY(c.hook->batch(fb, nf, (const double *)d_field, *c.spans));
+        for (int64_t f = fb; c.stages && f < fb + nf; f++)
+            AMOF_TRY(c.stages->frame(f, (const double *)d_field + (size_t)(f - fb) * (size_t)c.G, *c.spans));
     }
     timing_dom_end(ctx, launches);
     return AMOF_OK;
@@ -513,43 +514,6 @@ static int pore_brick_tier(PoreCall &c, double rcut, bool &done)
     return AMOF_OK;
 }
 
-static int pore_check(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
-                      const double *thresholds, int32_t n_t, const void *hist, const void *counts, const void *vmax, const void *argmax,
-                      HostGeom &geom, int32_t &nbins)
-{
-    AMOF_TRY(validate_traj(ctx, t, false));
-    if (!radii || !grid || n_t < 0 || (n_t > 0 && !thresholds)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (t->n_frames > 0 && (!hist || !vmax || !argmax || (n_t > 0 && !counts))) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    for (int k = 0; k < 3; k++)
-        if (grid[k] < 1) return fail(ctx, AMOF_EINVAL, "grid must be at least 1 x 1 x 1");
-    if ((int64_t)grid[0] * grid[1] > 0x7fffffffLL || (int64_t)grid[0] * grid[1] * (int64_t)grid[2] > 0x7fffffffLL)
-        return fail(ctx, AMOF_EINVAL, "the grid has more than 2^31 - 1 points");
-    if (!(dr > 0.0) || !isfinite(dr) || !(dmax > 0.0) || !isfinite(dmax)) return fail(ctx, AMOF_EINVAL, "dr and dmax must be finite and > 0");
-    const double nb = rint(dmax / dr);
-    if (!(nb >= 1.0)) return fail(ctx, AMOF_EINVAL, "dmax / dr rounds to no bin");
-    double rmax = 0.0;
-    for (int s = 0; s < t->n_species; s++) {
-        if (!(radii[s] >= 0.0) || !isfinite(radii[s])) return fail(ctx, AMOF_EINVAL, "radii must be finite and >= 0");
-        rmax = std::max(rmax, radii[s]);
-    }
-    for (int k = 0; k < n_t; k++)
-        if (!isfinite(thresholds[k])) return fail(ctx, AMOF_EINVAL, "thresholds must be finite");
-    if (nb + 2.0 + (double)n_t > (double)AMOF_PORE_MAX_WORDS)
-        return fail(ctx, AMOF_ECAPACITY, "nbins + 2 + n_thresholds exceeds %d", AMOF_PORE_MAX_WORDS);
-    nbins = (int32_t)nb;
-    if (t->n_frames == 0) return AMOF_OK;
-    AMOF_TRY(build_geometry(ctx, t, geom));
-    double hmin = INFINITY;         // smallest perpendicular height on a periodic axis
-    for (int64_t k = 0; k < t->n_cells; k++)
-        for (int x = 0; x < 3; x++)
-            if (t->pbc[x]) hmin = std::min(hmin, geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-    // (1e-12: the heights come out of an inverse; a cutoff of exactly half a height, as Pore's default dmax can be, passes)
-    if (dmax + rmax > 0.5 * hmin * (1.0 + 1e-12))
-        return fail(ctx, AMOF_EINVAL, "dmax + the largest radius = %g exceeds half the smallest cell height %g: one minimum image would not do",
-                    dmax + rmax, hmin);
-    return AMOF_OK;
-}
-
 }  // namespace amof
 
 using namespace amof;
@@ -559,43 +523,49 @@ extern "C" double amof_pore_candidate_bound(const double *cell, double rcut)
     return cell ? pore_candidate_bound(cell, rcut) : -1.0;
 }
 
-// amof_pore_field; with a hook (amof_pore_access, pore_access.hip) every batch's field is kept in device memory and handed over
-int amof::pore_field_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
-                         const double *thresholds, int32_t n_t, uint64_t *hist, int64_t *counts, double *vmax, int64_t *argmax,
-                         double *field, PoreFieldHook *hook)
+// ---- field source 1: atoms.  amof_pore_field; with stages every batch's field stays in device memory and goes through them
+int amof::pore_field_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, PoreStages *stages)
 {
     if (!ctx) return AMOF_EINVAL;
     PoreCall c;
     c.ctx = ctx;
-    c.t = t;
-    c.hook = hook;
-    int32_t nbins = 0;
-    AMOF_TRY(pore_check(ctx, t, radii, grid, dr, dmax, thresholds, n_t, hist, counts, vmax, argmax, c.geom, nbins));
-    const int64_t F = t->n_frames;
+    c.stages = stages;
+    const amof_traj *t = c.t = in.t;
+    double rmax = 0.0, nb = 0.0, hmin = INFINITY;       // hmin: the smallest perpendicular height on a periodic axis
+    AMOF_TRY(validate_traj(ctx, t, false));
+    AMOF_TRY(pore_refuse(ctx, pore_check::both_given(in.radii, in.grid)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::thresholds_given(in.thresholds, in.n_t)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::field_outputs(t->n_frames, in.n_t, out.hist, out.counts, out.vmax, out.argmax)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::grid(in.grid, nullptr)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::bin_width(in.dr, in.dmax, nb)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::radii(in.radii, t->n_species, rmax)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::thresholds_finite(in.thresholds, in.n_t)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::counter_words(nb, in.n_t, out.nbins)));
+    out.sized(t->n_frames, in.grid, in.n_t);        // (whatever refuses from here on leaves zeros)
+    const int64_t F = out.F;
     if (F == 0) return AMOF_OK;
+    AMOF_TRY(build_geometry(ctx, t, c.geom));
+    for (int64_t k = 0; k < t->n_cells; k++)
+        for (int x = 0; x < 3; x++)
+            if (t->pbc[x]) hmin = std::min(hmin, c.geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
+    AMOF_TRY(pore_refuse(ctx, pore_check::half_height_atoms(in.dmax, rmax, hmin)));
+    if (out.field) AMOF_TRY(pore_refuse(ctx, pore_check::per_point_cap(out.G, "field")));
     const int S = t->n_species;
-    c.G = (int64_t)grid[0] * grid[1] * grid[2];
-    if (field && (size_t)c.G * sizeof(double) > ((size_t)1 << 32))
-        return fail(ctx, AMOF_ECAPACITY, "a per-point field of %lld points per frame exceeds the 4 GiB a frame may take", (long long)c.G);
-    c.field_host = field;
+    const int32_t nbins = out.nbins, n_t = in.n_t;
+    c.G = out.G;
+    c.field_host = out.field;
     if (const char *be = getenv("AMOF_PORE_BATCH")) c.batch_cap = std::max(1, atoi(be));
-    // the outputs are overwritten: zeros first, so that a failing call leaves zeros
-    std::fill(hist, hist + (size_t)F * (nbins + 2), (uint64_t)0);
-    if (n_t > 0) std::fill(counts, counts + (size_t)F * n_t, (int64_t)0);
-    std::fill(vmax, vmax + F, 0.0);
-    std::fill(argmax, argmax + F, (int64_t)0);
-    double rmax = 0.0;
-    for (int s = 0; s < S; s++) rmax = std::max(rmax, radii[s]);
+    out.zero(false);
 
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
     AMOF_TRY(stager_begin(ctx, t, true, c.stage));
-    StageSpans spans(ctx);      // cell sort, field kernel, the hook's labelling kernels
+    StageSpans spans(ctx);      // cell sort, field kernel, the stages' kernels
     c.spans = &spans;
     UploadPack pk;
     const int i_geom = pk.add(c.geom.rec.data(), c.geom.rec.size() * sizeof(double));
-    const int i_rad = pk.add(radii, (size_t)S * sizeof(double));
-    const int i_thr = pk.add(thresholds, (size_t)n_t * sizeof(double));
+    const int i_rad = pk.add(in.radii, (size_t)S * sizeof(double));
+    const int i_thr = pk.add(in.thresholds, (size_t)n_t * sizeof(double));
     const int i_sp = pk.add(t->species, (size_t)t->n_atoms * sizeof(int32_t));
     AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
     const size_t hist_bytes = (size_t)F * (nbins + 2) * sizeof(uint64_t), cnt_bytes = (size_t)F * n_t * sizeof(int64_t);
@@ -614,31 +584,57 @@ int amof::pore_field_run(amof_ctx *ctx, const amof_traj *t, const double *radii,
     a.G = c.G;
     a.n_cells = (int32_t)t->n_cells;
     a.S = S;
-    for (int k = 0; k < 3; k++) a.n[k] = grid[k];
+    for (int k = 0; k < 3; k++) a.n[k] = in.grid[k];
     a.nbins = nbins;
     a.n_t = n_t;
-    a.dr = dr;
-    a.dmax = dmax;
+    a.dr = in.dr;
+    a.dmax = in.dmax;
     a.hist = (unsigned long long *)c.d_out;
     a.counts = (unsigned long long *)((unsigned char *)c.d_out + hist_bytes);
     c.d_vmax = (double *)((unsigned char *)c.d_out + hist_bytes + cnt_bytes);
     c.d_argmax = (long long *)(c.d_vmax + F);
     a.flags = (int32_t *)d_flags;
+    if (stages) AMOF_TRY(stages->setup());
 
     bool done = false;
     const char *ex = getenv("AMOF_PORE_EXACT");
-    if (!(ex && ex[0] == '1')) AMOF_TRY(pore_brick_tier(c, dmax + rmax, done));
+    if (!(ex && ex[0] == '1')) AMOF_TRY(pore_brick_tier(c, in.dmax + rmax, done));
     if (!done) {
+        if (stages) stages->restart();      // (nothing to take back where pore_brick never started)
         AMOF_TRY(stager_need(c.stage, F));
         AMOF_TRY(pore_exact_tier(c));
     }
     timing_end(ctx);
-    AMOF_TRY(fetch(ctx, hist, a.hist, hist_bytes));
-    AMOF_TRY(fetch(ctx, counts, a.counts, cnt_bytes));
-    AMOF_TRY(fetch(ctx, vmax, c.d_vmax, (size_t)F * sizeof(double)));
-    AMOF_TRY(fetch(ctx, argmax, c.d_argmax, (size_t)F * sizeof(long long)));
+    AMOF_TRY(fetch(ctx, out.hist, a.hist, hist_bytes));
+    AMOF_TRY(fetch(ctx, out.counts, a.counts, cnt_bytes));
+    AMOF_TRY(fetch(ctx, out.vmax, c.d_vmax, (size_t)F * sizeof(double)));
+    AMOF_TRY(fetch(ctx, out.argmax, c.d_argmax, (size_t)F * sizeof(long long)));
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     spans.collect();
+    if (stages) stages->report();
+    return AMOF_OK;
+}
+
+// ---- field source 2: a field the caller supplies (its arguments checked by the entry point)
+int amof::pore_given_field_run(amof_ctx *ctx, const PoreInputs &in, const PoreOutputs &out, PoreStages &stages, const char *path)
+{
+    const size_t G = (size_t)out.G;
+    AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    timing_begin(ctx);
+    AMOF_TRY(stages.setup());
+    void *d_field;
+    AMOF_TRY(ensure(ctx, SLOT_OUT1, G * sizeof(double), &d_field));
+    StageSpans spans(ctx);
+    timing_dom_begin(ctx, path);
+    for (int64_t f = 0; f < out.F; f++) {
+        AMOF_HIP_TRY(ctx, hipMemcpyAsync(d_field, in.field + (size_t)f * G, G * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        AMOF_TRY(stages.frame(f, (const double *)d_field, spans));
+    }
+    timing_dom_end(ctx, 0);
+    timing_end(ctx);
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
+    spans.collect();
+    stages.report();
     return AMOF_OK;
 }
 
@@ -646,5 +642,6 @@ extern "C" int amof_pore_field(amof_ctx *ctx, const amof_traj *t, const double *
                                const double *thresholds, int32_t n_t, uint64_t *hist, int64_t *counts, double *vmax, int64_t *argmax,
                                double *field)
 {
-    return pore_field_run(ctx, t, radii, grid, dr, dmax, thresholds, n_t, hist, counts, vmax, argmax, field, nullptr);
+    PoreOutputs out{hist, counts, vmax, argmax, field};
+    return out.keep(pore_field_run(ctx, PoreInputs{t, radii, nullptr, nullptr, 0, grid, nullptr, dr, dmax, thresholds, n_t, 0, 0}, out, nullptr));
 }

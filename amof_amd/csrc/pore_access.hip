@@ -306,6 +306,8 @@ struct Labeller {
     amof_ctx *ctx = nullptr;
     PaGrid g;               // n, pbc, G
     bool global = false;
+    const PoreInputs *in = nullptr;         // the call: thresholds [n_t], want_free
+    const PoreOutputs *arrays = nullptr;    // access, free_sphere, labels (access null: the rows are nobody's, amof_pore_psd_field)
     int64_t L = 0;          // slots of the link table
     int64_t cap = 0;        // entries of the component list
     int32_t *parent = nullptr, *size = nullptr, *out = nullptr;        // out: [0] components, [2..3] the u64 of pa_chmax_kernel
@@ -325,26 +327,10 @@ static unsigned pa_blocks(int64_t n) { return (unsigned)std::max<int64_t>(1, (n 
 
 static const char *pa_path(const Labeller &lb) { return lb.global ? "pore_label_global" : "pore_label_tile"; }
 
-static size_t pa_fixed_bytes(int64_t G, int64_t L, bool want_free)
+// what the call labels and where its answers go; no device work
+static void pa_plan(Labeller &lb, amof_ctx *ctx, const PoreInputs &in, const PoreOutputs &out)
 {
-    return (size_t)G * 8 + (size_t)(G / 2 + 2) * 8 + (size_t)L * 8 + (want_free ? (size_t)G * 20 : 0);
-}
-
-static int pa_check_grid(amof_ctx *ctx, const int32_t *grid, const int *pbc)
-{
-    for (int k = 0; k < 3; k++) {
-        if (grid[k] < 1) return fail(ctx, AMOF_EINVAL, "grid must be at least 1 x 1 x 1");
-        if (pbc[k] && grid[k] < 3)
-            return fail(ctx, AMOF_EINVAL, "periodic axis %d has %d grid points: a point would meet itself or one neighbour through both faces, "
-                                          "labelling needs 3", k, grid[k]);
-    }
-    if ((int64_t)grid[0] * grid[1] > 0x7fffffffLL || (int64_t)grid[0] * grid[1] * (int64_t)grid[2] > 0x7fffffffLL)
-        return fail(ctx, AMOF_EINVAL, "the grid has more than 2^31 - 1 points");
-    return AMOF_OK;
-}
-
-static int pa_setup(Labeller &lb, amof_ctx *ctx, const int32_t *grid, const int *pbc, bool want_free)
-{
+    const int32_t *grid = in.grid, *pbc = in.pbc;
     lb.ctx = ctx;
     memset(&lb.g, 0, sizeof lb.g);
     for (int k = 0; k < 3; k++) {
@@ -357,6 +343,25 @@ static int pa_setup(Labeller &lb, amof_ctx *ctx, const int32_t *grid, const int 
     lb.cap = lb.g.G / 2 + 2;        // (no two adjacent points are both roots of one-point components: at most ceil(G / 2) components)
     const char *gl = getenv("AMOF_PORE_LABEL_GLOBAL");
     lb.global = gl && gl[0] == '1';
+    lb.in = &in;
+    lb.arrays = &out;
+}
+
+size_t pore_label_fixed_bytes(const Labeller &lb)
+{
+    const int64_t G = lb.g.G;
+    return (size_t)G * 8 + (size_t)(G / 2 + 2) * 8 + (size_t)lb.L * 8 + (lb.in->want_free ? (size_t)G * 20 : 0);
+}
+
+void pore_label_report(const Labeller &lb)
+{
+    lb.ctx->last_path = pa_path(lb);
+    lb.ctx->dom_launches = lb.labellings;
+}
+
+int pore_label_setup(Labeller &lb)
+{
+    amof_ctx *ctx = lb.ctx;
     void *p;
     AMOF_TRY(ensure(ctx, SLOT_AUX0, (size_t)lb.g.G * sizeof(int32_t), &p));
     lb.parent = (int32_t *)p;
@@ -368,7 +373,7 @@ static int pa_setup(Labeller &lb, amof_ctx *ctx, const int32_t *grid, const int 
     lb.links = (int2 *)p;
     AMOF_TRY(ensure(ctx, SLOT_SELF, 4 * sizeof(int32_t), &p));
     lb.out = (int32_t *)p;
-    if (want_free) {
+    if (lb.in->want_free) {
         AMOF_TRY(ensure(ctx, SLOT_PAIRS, (size_t)lb.g.G * sizeof(double), &p));
         lb.sorted = (double *)p;
         lb.cub_bytes = 0;
@@ -557,39 +562,41 @@ static int pa_free_sphere(Labeller &lb, const double *d_field, double dmax, doub
     return AMOF_OK;
 }
 
-// every threshold of one frame whose field lies on the device, then its free sphere.  With a hook (amof_pore_psd): the hook's
-// work is no labelling, the span of stage 2 is closed around it.
-static int pa_frame(Labeller &lb, const double *d_field, const double *thresholds, int32_t n_t, int want_free, double dmax, int64_t *access,
-                    double *free_sphere, int32_t *labels, int64_t f, PoreAccessHook *hook, StageSpans &spans)
+// every threshold of frame f, whose field lies on the device, then its free sphere.  With a covering stage (want_access) every
+// threshold's channels are marked for its accessible pass: that is no labelling, the span of stage 2 is closed around it.
+int pore_label_frame(Labeller &lb, int64_t f, const double *d_field, CoverCall *cover, StageSpans &spans)
 {
-    if (hook && hook->frame) AMOF_TRY(hook->frame(f, d_field, spans));
+    const size_t G = (size_t)lb.g.G;
+    int64_t own[4];
     spans.begin(2);
-    for (int32_t k = 0; k < n_t; k++) {
-        AMOF_TRY(pa_open(lb, d_field, thresholds[k]));
-        AMOF_TRY(pa_periodic(lb, d_field, access + (size_t)k * 4, labels ? labels + (size_t)k * (size_t)lb.g.G : nullptr, nullptr));
-        if (hook && hook->threshold) {
+    for (int32_t k = 0; k < lb.in->n_t; k++) {
+        const size_t row = (size_t)f * (size_t)lb.in->n_t + (size_t)k;
+        AMOF_TRY(pa_open(lb, d_field, lb.in->thresholds[k]));
+        AMOF_TRY(pa_periodic(lb, d_field, lb.arrays->access ? lb.arrays->access + row * 4 : own,
+                             lb.arrays->labels ? lb.arrays->labels + row * G : nullptr, nullptr));
+        if (cover) {
             bool any = false;
             AMOF_TRY(pa_mark_channels(lb, any));
             spans.end();
-            AMOF_TRY(hook->threshold(f, k, d_field, lb.parent, lb.size, any, spans));
+            AMOF_TRY(pore_cover_threshold(*cover, f, k, d_field, lb.parent, lb.size, any, spans));
             spans.begin(2);
         }
     }
-    if (want_free) AMOF_TRY(pa_free_sphere(lb, d_field, dmax, free_sphere));
+    const double cap = lb.in->t ? lb.in->dmax : 0.0;        // (of the field from atoms; a supplied field has none)
+    if (lb.in->want_free) AMOF_TRY(pa_free_sphere(lb, d_field, cap, lb.arrays->free_sphere + (size_t)f * 2));
     spans.end();
     return AMOF_OK;
 }
 
-static int pa_check_outputs(amof_ctx *ctx, int64_t F, int64_t G, const double *thresholds, int32_t n_t, int want_free, const int64_t *access,
-                            const double *free_sphere, const int32_t *labels)
+// the labelling's checks, the same for both entry points (pore_check.h has the order); the record's sizes
+static int pa_check(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out)
 {
-    if (n_t < 0 || (n_t > 0 && !thresholds)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    for (int k = 0; k < n_t; k++)
-        if (!isfinite(thresholds[k])) return fail(ctx, AMOF_EINVAL, "thresholds must be finite");
-    if (F > 0 && n_t > 0 && !access) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (F > 0 && want_free && !free_sphere) return fail(ctx, AMOF_EINVAL, "want_free without a free_sphere array");
-    if (labels && (size_t)n_t * (size_t)G * sizeof(int32_t) > ((size_t)1 << 32))
-        return fail(ctx, AMOF_ECAPACITY, "labels of %d thresholds x %lld points exceed the 4 GiB a frame may take", n_t, (long long)G);
+    AMOF_TRY(pore_refuse(ctx, pore_check::grid(in.grid, in.pbc)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::thresholds_given(in.thresholds, in.n_t)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::thresholds_finite(in.thresholds, in.n_t)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::access_outputs(in.n_frames, in.n_t, in.want_free, out.access, out.free_sphere)));
+    if (out.labels) AMOF_TRY(pore_refuse(ctx, pore_check::labels_cap(in.n_t, (int64_t)in.grid[0] * in.grid[1] * in.grid[2])));
+    out.sized(in.n_frames, in.grid, in.n_t);
     return AMOF_OK;
 }
 
@@ -597,100 +604,38 @@ static int pa_check_outputs(amof_ctx *ctx, int64_t F, int64_t G, const double *t
 
 using namespace amof;
 
-int amof::pore_access_run(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
-                          const double *thresholds, int32_t n_t, int32_t want_free, uint64_t *hist, int64_t *counts, double *vmax,
-                          int64_t *argmax, int64_t *access, double *free_sphere, double *field, int32_t *labels, PoreAccessHook *ahook)
+int amof::pore_access_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, CoverCall *cover)
 {
-    if (!ctx) return AMOF_EINVAL;
-    if (!t || !grid) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    const int pbc[3] = {t->pbc[0], t->pbc[1], t->pbc[2]};
-    AMOF_TRY(pa_check_grid(ctx, grid, pbc));
-    const int64_t F = t->n_frames, G = (int64_t)grid[0] * grid[1] * grid[2];
-    AMOF_TRY(pa_check_outputs(ctx, F, G, thresholds, n_t, want_free, access, free_sphere, labels));
-    if (F > 0) {
-        if (access) std::fill(access, access + (size_t)F * n_t * 4, (int64_t)0);
-        if (free_sphere) std::fill(free_sphere, free_sphere + (size_t)F * 2, 0.0);
-    }
+    if (in.t) AMOF_TRY(pa_check(ctx, in, out));     // (the entry point of a supplied field has checked already)
     Labeller lb;
-    PoreFieldHook hook;
-    hook.fixed_bytes = pa_fixed_bytes(G, (int64_t)grid[1] * grid[2] + (int64_t)grid[0] * grid[2] + (int64_t)grid[0] * grid[1], want_free != 0) +
-                       (ahook ? ahook->fixed_bytes : 0);
-    bool ready = false;
-    hook.batch = [&](int64_t fb, int64_t nf, const double *d_field, StageSpans &spans) -> int {
-        if (!ready) AMOF_TRY(pa_setup(lb, ctx, grid, pbc, want_free != 0));
-        ready = true;
-        for (int64_t f = fb; f < fb + nf; f++)
-            AMOF_TRY(pa_frame(lb, d_field + (size_t)(f - fb) * (size_t)G, thresholds, n_t, want_free, dmax, access + (size_t)f * n_t * 4,
-                              free_sphere ? free_sphere + (size_t)f * 2 : nullptr,
-                              labels ? labels + (size_t)f * (size_t)n_t * (size_t)G : nullptr, f, ahook, spans));
-        return AMOF_OK;
-    };
-    const int rc = pore_field_run(ctx, t, radii, grid, dr, dmax, thresholds, n_t, hist, counts, vmax, argmax, field, &hook);
-    if (rc != AMOF_OK) {
-        if (F > 0 && access) std::fill(access, access + (size_t)F * n_t * 4, (int64_t)0);
-        if (F > 0 && free_sphere) std::fill(free_sphere, free_sphere + (size_t)F * 2, 0.0);
-        return rc;
-    }
-    if (ready) {
-        ctx->last_path = pa_path(lb);
-        ctx->dom_launches = lb.labellings;
-    }
-    return AMOF_OK;
+    pa_plan(lb, ctx, in, out);
+    PoreStages stages{&lb, cover, cover && in.want_access};
+    return in.t ? pore_field_run(ctx, in, out, &stages) : pore_given_field_run(ctx, in, out, stages, pa_path(lb));
 }
 
 extern "C" int amof_pore_access(amof_ctx *ctx, const amof_traj *t, const double *radii, const int32_t *grid, double dr, double dmax,
                                 const double *thresholds, int32_t n_t, int32_t want_free, uint64_t *hist, int64_t *counts, double *vmax,
                                 int64_t *argmax, int64_t *access, double *free_sphere, double *field, int32_t *labels)
 {
-    return pore_access_run(ctx, t, radii, grid, dr, dmax, thresholds, n_t, want_free, hist, counts, vmax, argmax, access, free_sphere, field,
-                           labels, nullptr);
-}
-
-int amof::pore_access_field_run(amof_ctx *ctx, const double *field, int64_t n_frames, const int32_t *grid, const int32_t *pbc,
-                                const double *thresholds, int32_t n_t, int32_t want_free, int64_t *access, double *free_sphere,
-                                int32_t *labels, PoreAccessHook *ahook)
-{
     if (!ctx) return AMOF_EINVAL;
-    if (!grid || !pbc || n_frames < 0 || (n_frames > 0 && !field)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    const int per[3] = {pbc[0], pbc[1], pbc[2]};
-    AMOF_TRY(pa_check_grid(ctx, grid, per));
-    const int64_t F = n_frames, G = (int64_t)grid[0] * grid[1] * grid[2];
-    AMOF_TRY(pa_check_outputs(ctx, F, G, thresholds, n_t, want_free, access, free_sphere, labels));
-    if (F == 0) return AMOF_OK;
-    for (size_t k = 0; k < (size_t)F * (size_t)G; k++)
-        if (!isfinite(field[k])) return fail(ctx, AMOF_EINVAL, "the field must be finite");
-    if (access) std::fill(access, access + (size_t)F * n_t * 4, (int64_t)0);
-    if (free_sphere) std::fill(free_sphere, free_sphere + (size_t)F * 2, 0.0);
-
-    AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    timing_begin(ctx);
-    Labeller lb;
-    AMOF_TRY(pa_setup(lb, ctx, grid, per, want_free != 0));
-    void *d_field;
-    AMOF_TRY(ensure(ctx, SLOT_OUT1, (size_t)G * sizeof(double), &d_field));
-    StageSpans spans(ctx);
-    timing_dom_begin(ctx, pa_path(lb));
-    for (int64_t f = 0; f < F; f++) {
-        AMOF_HIP_TRY(ctx, hipMemcpyAsync(d_field, field + (size_t)f * (size_t)G, (size_t)G * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        const int rc = pa_frame(lb, (const double *)d_field, thresholds, n_t, want_free, 0.0, access + (size_t)f * n_t * 4,
-                                free_sphere ? free_sphere + (size_t)f * 2 : nullptr, labels ? labels + (size_t)f * (size_t)n_t * (size_t)G : nullptr,
-                                f, ahook, spans);
-        if (rc != AMOF_OK) {
-            if (access) std::fill(access, access + (size_t)F * n_t * 4, (int64_t)0);
-            if (free_sphere) std::fill(free_sphere, free_sphere + (size_t)F * 2, 0.0);
-            return rc;
-        }
-    }
-    timing_dom_end(ctx, lb.labellings);
-    timing_end(ctx);
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    spans.collect();
-    return AMOF_OK;
+    PoreOutputs out{hist, counts, vmax, argmax, field, access, free_sphere, labels};
+    AMOF_TRY(pore_refuse(ctx, pore_check::both_given(t, grid)));
+    const int32_t pbc[3] = {t->pbc[0], t->pbc[1], t->pbc[2]};
+    return out.keep(pore_access_run(ctx, PoreInputs{t, radii, nullptr, nullptr, t->n_frames, grid, pbc, dr, dmax, thresholds, n_t, 0, want_free}, out, nullptr));
 }
 
 extern "C" int amof_pore_access_field(amof_ctx *ctx, const double *field, int64_t n_frames, const int32_t *grid, const int32_t *pbc,
                                       const double *thresholds, int32_t n_t, int32_t want_free, int64_t *access, double *free_sphere,
                                       int32_t *labels)
 {
-    return pore_access_field_run(ctx, field, n_frames, grid, pbc, thresholds, n_t, want_free, access, free_sphere, labels, nullptr);
+    if (!ctx) return AMOF_EINVAL;
+    PoreOutputs out{nullptr, nullptr, nullptr, nullptr, nullptr, access, free_sphere, labels};
+    const PoreInputs in{nullptr, nullptr, field, nullptr, n_frames, grid, pbc, 0.0, 0.0, thresholds, n_t, 0, want_free};
+    AMOF_TRY(pore_refuse(ctx, pore_check::given_field_inputs(grid, pbc, n_frames, field, false, nullptr)));
+    AMOF_TRY(pa_check(ctx, in, out));
+    if (n_frames == 0) return AMOF_OK;
+    double top;
+    AMOF_TRY(pore_refuse(ctx, pore_check::field_finite(field, (size_t)out.F * (size_t)out.G, top)));
+    out.zero(false);
+    return out.keep(pore_access_run(ctx, in, out, nullptr));
 }

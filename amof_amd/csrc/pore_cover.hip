@@ -371,10 +371,7 @@ struct CoverCall {
     int32_t src_cap = PC_SRC_CAP;       // AMOF_PORE_COVER_SRC_CAP=n (1 .. PC_SRC_CAP) shortens the brick list: the tests' way to the retry
     const double *cells = nullptr;      // host [n_cells][9]
     int64_t n_cells = 1;
-    // the caller's arrays
-    uint64_t *psd_hist = nullptr;
-    int64_t *po_counts = nullptr, *po_access = nullptr;
-    double *cover = nullptr;
+    const PoreOutputs *out = nullptr;   // the caller's arrays: psd_hist, po_counts, po_access, cover
     // device
     double *d_w = nullptr, *d_bmax = nullptr, *d_thr = nullptr;
     PcOffset *d_st = nullptr;
@@ -390,7 +387,7 @@ struct CoverCall {
     std::vector<PcOffset> h_st;
     std::vector<unsigned long long> h_out;
     // the call
-    int64_t last_frame = -1;
+    const double *thresholds = nullptr;
     int64_t launches = 0;
     bool used_exact = false;
     double stat_src = 0.0, stat_rec = 0.0, stat_bricks = 0.0;     // sums over the full passes on pore_cover_brick
@@ -426,9 +423,10 @@ static bool pc_geometry(const double *C, const int32_t *n, double *A, double *hs
     return true;
 }
 
-static int pc_setup(CoverCall &c, amof_ctx *ctx, const int32_t *grid, const int *pbc, int32_t nbins, int32_t n_t, double dr, double dmax,
-                    const double *thresholds)
+// what the call covers and where its answers go; no device work
+static void pc_plan(CoverCall &c, amof_ctx *ctx, const PoreInputs &in, const PoreOutputs &out)
 {
+    const int32_t *grid = in.grid, *pbc = in.pbc;
     c.ctx = ctx;
     c.G = 1;
     c.nbk = 1;
@@ -438,37 +436,54 @@ static int pc_setup(CoverCall &c, amof_ctx *ctx, const int32_t *grid, const int 
         c.G *= grid[k];
         c.nbk *= (grid[k] + PC_BRICK - 1) / PC_BRICK;
     }
-    c.nbins = nbins;
-    c.n_t = n_t;
-    c.dr = dr;
-    c.dmax = dmax;
+    c.nbins = out.nbins;
+    c.n_t = out.n_t;
+    c.dr = in.dr;
+    c.dmax = in.dmax;
+    c.thresholds = in.thresholds;
+    c.cells = in.t ? in.t->cell : in.cells;
+    c.n_cells = in.t ? in.t->n_cells : in.n_frames;
     const char *ex = getenv("AMOF_PORE_COVER_EXACT");
     c.force_exact = ex && ex[0] == '1';
     if (const char *cap = getenv("AMOF_PORE_COVER_SRC_CAP")) c.src_cap = std::min(PC_SRC_CAP, std::max(1, atoi(cap)));
-    c.words = nbins + 2 + n_t;
+    c.words = c.nbins + 2 + c.n_t;
+    c.out = &out;
+}
+
+int pore_cover_setup(CoverCall &c)
+{
+    amof_ctx *ctx = c.ctx;
     void *p;
     AMOF_TRY(ensure(ctx, SLOT_IMG, (size_t)c.G * sizeof(double), &p));
     c.d_w = (double *)p;
     AMOF_TRY(ensure(ctx, SLOT_NIMG, (size_t)c.nbk * sizeof(double), &p));
     c.d_bmax = (double *)p;
     // thresholds, then the counters of a frame
-    c.h_out.assign((size_t)n_t + c.words + 4, 0ull);
-    if (n_t > 0) memcpy(c.h_out.data(), thresholds, (size_t)n_t * sizeof(double));
+    c.h_out.assign((size_t)c.n_t + c.words + 4, 0ull);
+    if (c.n_t > 0) memcpy(c.h_out.data(), c.thresholds, (size_t)c.n_t * sizeof(double));
     AMOF_TRY(upload(ctx, SLOT_QSPEC, c.h_out.data(), c.h_out.size() * sizeof(unsigned long long), &p));
     c.d_thr = (double *)p;
-    c.d_out = (unsigned long long *)p + n_t;
+    c.d_out = (unsigned long long *)p + c.n_t;
     c.h_bmax.resize((size_t)c.nbk);
     return AMOF_OK;
 }
 
-static size_t pc_fixed_bytes(const int32_t *grid, const double *cell0, double dmax)
+// w, the brick maxima and the exact path's offset table, sized from the first cell
+size_t pore_cover_fixed_bytes(const CoverCall &c)
 {
-    const int64_t G = (int64_t)grid[0] * grid[1] * grid[2];
     double A[9], hstep[3], hd;
     double offsets = 1e6;
-    if (pc_geometry(cell0, grid, A, hstep, hd))
-        offsets = std::min(1e8, 8.0 * (dmax / hstep[0] + 1.0) * (dmax / hstep[1] + 1.0) * (dmax / hstep[2] + 1.0));
-    return (size_t)G * 8 + (size_t)(G / 64 + 64) * 8 + (size_t)offsets * sizeof(PcOffset);
+    if (pc_geometry(c.cells, c.n, A, hstep, hd))
+        offsets = std::min(1e8, 8.0 * (c.dmax / hstep[0] + 1.0) * (c.dmax / hstep[1] + 1.0) * (c.dmax / hstep[2] + 1.0));
+    return (size_t)c.G * 8 + (size_t)(c.G / 64 + 64) * 8 + (size_t)offsets * sizeof(PcOffset);
+}
+
+// the field tiers start over: so do the call's counters
+void pore_cover_restart(CoverCall &c)
+{
+    c.launches = 0;
+    c.used_exact = false;
+    c.stat_src = c.stat_rec = c.stat_bricks = 0.0;
 }
 
 // every offset with d2 <= vmax^2, for the frame at hand
@@ -545,17 +560,9 @@ static int pc_clear_out(CoverCall &c)
 }
 
 // w, its histogram and the occupiable counts of frame f, whose field lies on the device
-static int pc_frame(CoverCall &c, int64_t f, const double *d_field, StageSpans &spans)
+int pore_cover_frame(CoverCall &c, int64_t f, const double *d_field, StageSpans &spans)
 {
     amof_ctx *ctx = c.ctx;
-    if (f <= c.last_frame) {
-        // the field tiers start over (pore_brick gave up, pore_exact runs every batch again): so do the call's counters.  The
-        // covering stage's spans of the abandoned round stay in amof_last_kernel_seconds(5), as the field kernels' do in (3).
-        c.launches = 0;
-        c.used_exact = false;
-        c.stat_src = c.stat_rec = c.stat_bricks = 0.0;
-    }
-    c.last_frame = f;
     memset(&c.g, 0, sizeof c.g);
     c.g.src_cap = c.src_cap;
     if (!pc_geometry(c.cells + (size_t)(c.n_cells == 1 ? 0 : f) * 9, c.n, c.g.A, c.hstep, c.g.hd))
@@ -599,17 +606,17 @@ static int pc_frame(CoverCall &c, int64_t f, const double *d_field, StageSpans &
         c.stat_rec += (double)c.h_out[(size_t)c.words + 3];
         c.stat_bricks += (double)c.nbk;
     }
-    for (int x = 0; x < c.nbins + 2; x++) c.psd_hist[(size_t)f * (c.nbins + 2) + x] = (uint64_t)c.h_out[(size_t)x];
-    for (int t = 0; t < c.n_t; t++) c.po_counts[(size_t)f * c.n_t + t] = (int64_t)c.h_out[(size_t)c.nbins + 2 + t];
-    if (c.cover) AMOF_TRY(fetch(ctx, c.cover + (size_t)f * (size_t)c.G, c.d_w, (size_t)c.G * sizeof(double)));
+    for (int x = 0; x < c.nbins + 2; x++) c.out->psd_hist[(size_t)f * (c.nbins + 2) + x] = (uint64_t)c.h_out[(size_t)x];
+    for (int t = 0; t < c.n_t; t++) c.out->po_counts[(size_t)f * c.n_t + t] = (int64_t)c.h_out[(size_t)c.nbins + 2 + t];
+    if (c.out->cover) AMOF_TRY(fetch(ctx, c.out->cover + (size_t)f * (size_t)c.G, c.d_w, (size_t)c.G * sizeof(double)));
     return AMOF_OK;
 }
 
 // the points of frame f covered from a channel of V(thresholds[k])
-static int pc_threshold(CoverCall &c, int64_t f, int32_t k, const double *d_field, const int32_t *parent, const int32_t *mark, bool channels,
-                        StageSpans &spans)
+int pore_cover_threshold(CoverCall &c, int64_t f, int32_t k, const double *d_field, const int32_t *parent, const int32_t *mark, bool channels,
+                         StageSpans &spans)
 {
-    int64_t &out = c.po_access[(size_t)f * c.n_t + k];
+    int64_t &out = c.out->po_access[(size_t)f * c.n_t + k];
     out = 0;
     if (!channels) return AMOF_OK;
     // On the path of the frame's full pass.  The channels' centres are a subset of all centres: a destination brick keeps no
@@ -626,31 +633,22 @@ static int pc_threshold(CoverCall &c, int64_t f, int32_t k, const double *d_fiel
     return AMOF_OK;
 }
 
-static void pc_zero(int64_t F, int64_t G, int32_t nbins, int32_t n_t, uint64_t *psd_hist, int64_t *po_counts, int64_t *po_access, double *cover)
+// the checks both entry points share, in the order of pore_check.h; the record's sizes
+static int pc_check(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out)
 {
-    if (F <= 0) return;
-    if (psd_hist) std::fill(psd_hist, psd_hist + (size_t)F * (nbins + 2), (uint64_t)0);
-    if (po_counts && n_t > 0) std::fill(po_counts, po_counts + (size_t)F * n_t, (int64_t)0);
-    if (po_access && n_t > 0) std::fill(po_access, po_access + (size_t)F * n_t, (int64_t)0);
-    if (cover) std::fill(cover, cover + (size_t)F * (size_t)G, 0.0);
+    double nb = 0.0;
+    AMOF_TRY(pore_refuse(ctx, pore_check::thresholds_given(in.thresholds, in.n_t)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::bin_width(in.dr, in.dmax, nb)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::thresholds_finite(in.thresholds, in.n_t)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::counter_words(nb, in.n_t, out.nbins)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::grid(in.grid, nullptr)));
+    AMOF_TRY(pore_refuse(ctx, pore_check::psd_outputs(in.n_frames, in.n_t, out.psd_hist, out.po_counts)));
+    if (out.cover) AMOF_TRY(pore_refuse(ctx, pore_check::per_point_cap((int64_t)in.grid[0] * in.grid[1] * in.grid[2], "array")));
+    out.sized(in.n_frames, in.grid, in.n_t);
+    return pore_refuse(ctx, pore_check::po_access_given(out.F, in.n_t, in.want_access, out.po_access));
 }
 
-// dr, dmax and the counters as amof_pore_field checks them
-static int pc_check_bins(amof_ctx *ctx, double dr, double dmax, const double *thresholds, int32_t n_t, int32_t &nbins)
-{
-    if (n_t < 0 || (n_t > 0 && !thresholds)) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (!(dr > 0.0) || !isfinite(dr) || !(dmax > 0.0) || !isfinite(dmax)) return fail(ctx, AMOF_EINVAL, "dr and dmax must be finite and > 0");
-    const double nb = rint(dmax / dr);
-    if (!(nb >= 1.0)) return fail(ctx, AMOF_EINVAL, "dmax / dr rounds to no bin");
-    for (int k = 0; k < n_t; k++)
-        if (!isfinite(thresholds[k])) return fail(ctx, AMOF_EINVAL, "thresholds must be finite");
-    if (nb + 2.0 + (double)n_t > (double)AMOF_PORE_MAX_WORDS)
-        return fail(ctx, AMOF_ECAPACITY, "nbins + 2 + n_thresholds exceeds %d", AMOF_PORE_MAX_WORDS);
-    nbins = (int32_t)nb;
-    return AMOF_OK;
-}
-
-static void pc_finish(CoverCall &c)
+void pore_cover_report(const CoverCall &c)
 {
     c.ctx->last_path = c.used_exact ? "pore_cover_exact" : "pore_cover_brick";
     c.ctx->dom_launches = c.launches;
@@ -669,70 +667,17 @@ extern "C" int amof_pore_psd(amof_ctx *ctx, const amof_traj *t, const double *ra
                              uint64_t *psd_hist, int64_t *po_counts, int64_t *po_access, double *cover)
 {
     if (!ctx) return AMOF_EINVAL;
-    if (!t || !grid) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    const int64_t F = t->n_frames;
-    int32_t nbins = 0;
-    AMOF_TRY(pc_check_bins(ctx, dr, dmax, thresholds, n_t, nbins));
-    for (int k = 0; k < 3; k++)
-        if (grid[k] < 1) return fail(ctx, AMOF_EINVAL, "grid must be at least 1 x 1 x 1");
-    if ((int64_t)grid[0] * grid[1] > 0x7fffffffLL || (int64_t)grid[0] * grid[1] * (int64_t)grid[2] > 0x7fffffffLL)
-        return fail(ctx, AMOF_EINVAL, "the grid has more than 2^31 - 1 points");
-    const int64_t G = (int64_t)grid[0] * grid[1] * grid[2];
-    if (F > 0 && (!psd_hist || (n_t > 0 && !po_counts))) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (cover && (size_t)G * sizeof(double) > ((size_t)1 << 32))
-        return fail(ctx, AMOF_ECAPACITY, "a per-point array of %lld points per frame exceeds the 4 GiB a frame may take", (long long)G);
-    pc_zero(F, G, nbins, n_t, psd_hist, po_counts, want_access ? po_access : nullptr, cover);
-    if (F > 0 && n_t > 0 && want_access && !po_access) {
-        // (refused before the field tiers, which zero their outputs themselves, are reached)
-        if (hist) std::fill(hist, hist + (size_t)F * (nbins + 2), (uint64_t)0);
-        if (counts) std::fill(counts, counts + (size_t)F * n_t, (int64_t)0);
-        if (vmax) std::fill(vmax, vmax + F, 0.0);
-        if (argmax) std::fill(argmax, argmax + F, (int64_t)0);
-        if (access) std::fill(access, access + (size_t)F * n_t * 4, (int64_t)0);
-        if (free_sphere && want_free) std::fill(free_sphere, free_sphere + (size_t)F * 2, 0.0);
-        return fail(ctx, AMOF_EINVAL, "want_access without a po_access array");
-    }
-
+    const bool labelled = want_access || want_free;
+    PoreOutputs out{hist, counts, vmax, argmax, field, labelled ? access : nullptr, labelled ? free_sphere : nullptr, labelled ? labels : nullptr,
+                    psd_hist, po_counts, want_access ? po_access : nullptr, cover};     // (what the call does not ask for is not the record's)
+    AMOF_TRY(pore_refuse(ctx, pore_check::both_given(t, grid)));
+    const int32_t pbc[3] = {t->pbc[0], t->pbc[1], t->pbc[2]};
+    const PoreInputs in{t, radii, nullptr, nullptr, t->n_frames, grid, pbc, dr, dmax, thresholds, n_t, want_access, want_free};
+    AMOF_TRY(pc_check(ctx, in, out));
     CoverCall c;
-    c.psd_hist = psd_hist;
-    c.po_counts = po_counts;
-    c.po_access = po_access;
-    c.cover = cover;
-    c.cells = t->cell;
-    c.n_cells = t->n_cells;
-    const int pbc[3] = {t->pbc[0], t->pbc[1], t->pbc[2]};
-    bool ready = false;
-    auto frame = [&](int64_t f, const double *d_field, StageSpans &spans) -> int {
-        if (!ready) AMOF_TRY(pc_setup(c, ctx, grid, pbc, nbins, n_t, dr, dmax, thresholds));
-        ready = true;
-        return pc_frame(c, f, d_field, spans);
-    };
-    const size_t fixed = (F > 0 && t->cell) ? pc_fixed_bytes(grid, t->cell, dmax) : 0;
-    int rc;
-    if (want_access || want_free) {
-        PoreAccessHook hook;
-        hook.fixed_bytes = fixed;
-        hook.frame = frame;
-        if (want_access)
-            hook.threshold = [&](int64_t f, int32_t k, const double *d_field, const int32_t *parent, const int32_t *mark, bool channels,
-                                 StageSpans &spans) -> int { return pc_threshold(c, f, k, d_field, parent, mark, channels, spans); };
-        rc = pore_access_run(ctx, t, radii, grid, dr, dmax, thresholds, n_t, want_free, hist, counts, vmax, argmax, access, free_sphere, field,
-                             labels, &hook);
-    } else {
-        PoreFieldHook hook;
-        hook.fixed_bytes = fixed;
-        hook.batch = [&](int64_t fb, int64_t nf, const double *d_field, StageSpans &spans) -> int {
-            for (int64_t f = fb; f < fb + nf; f++) AMOF_TRY(frame(f, d_field + (size_t)(f - fb) * (size_t)G, spans));
-            return AMOF_OK;
-        };
-        rc = pore_field_run(ctx, t, radii, grid, dr, dmax, thresholds, n_t, hist, counts, vmax, argmax, field, &hook);
-    }
-    if (rc != AMOF_OK) {
-        pc_zero(F, G, nbins, n_t, psd_hist, po_counts, want_access ? po_access : nullptr, cover);
-        return rc;
-    }
-    if (ready) pc_finish(c);
-    return AMOF_OK;
+    pc_plan(c, ctx, in, out);
+    PoreStages stages{nullptr, &c};
+    return out.keep(labelled ? pore_access_run(ctx, in, out, &c) : pore_field_run(ctx, in, out, &stages));
 }
 
 extern "C" int amof_pore_psd_field(amof_ctx *ctx, const double *field, const double *cells, int64_t n_frames, const int32_t *grid,
@@ -740,84 +685,29 @@ extern "C" int amof_pore_psd_field(amof_ctx *ctx, const double *field, const dou
                                    uint64_t *psd_hist, int64_t *po_counts, int64_t *po_access, double *cover)
 {
     if (!ctx) return AMOF_EINVAL;
-    if (!grid || !pbc || n_frames < 0 || (n_frames > 0 && (!field || !cells))) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    const int64_t F = n_frames;
-    int32_t nbins = 0;
-    AMOF_TRY(pc_check_bins(ctx, dr, dmax, thresholds, n_t, nbins));
-    for (int k = 0; k < 3; k++)
-        if (grid[k] < 1) return fail(ctx, AMOF_EINVAL, "grid must be at least 1 x 1 x 1");
-    if ((int64_t)grid[0] * grid[1] > 0x7fffffffLL || (int64_t)grid[0] * grid[1] * (int64_t)grid[2] > 0x7fffffffLL)
-        return fail(ctx, AMOF_EINVAL, "the grid has more than 2^31 - 1 points");
-    const int64_t G = (int64_t)grid[0] * grid[1] * grid[2];
-    if (F > 0 && (!psd_hist || (n_t > 0 && !po_counts))) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (cover && (size_t)G * sizeof(double) > ((size_t)1 << 32))
-        return fail(ctx, AMOF_ECAPACITY, "a per-point array of %lld points per frame exceeds the 4 GiB a frame may take", (long long)G);
-    pc_zero(F, G, nbins, n_t, psd_hist, po_counts, po_access, cover);
-    if (F > 0 && n_t > 0 && want_access && !po_access) return fail(ctx, AMOF_EINVAL, "want_access without a po_access array");
-    if (F == 0) return AMOF_OK;
-    const int per[3] = {pbc[0] ? 1 : 0, pbc[1] ? 1 : 0, pbc[2] ? 1 : 0};
+    PoreOutputs out{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, psd_hist, po_counts, po_access, cover};
+    AMOF_TRY(pore_refuse(ctx, pore_check::given_field_inputs(grid, pbc, n_frames, field, true, cells)));
+    const int32_t per[3] = {pbc[0] ? 1 : 0, pbc[1] ? 1 : 0, pbc[2] ? 1 : 0};
+    const PoreInputs in{nullptr, nullptr, field, cells, n_frames, grid, per, dr, dmax, thresholds, n_t, want_access, 0};
+    AMOF_TRY(pc_check(ctx, in, out));
+    if (n_frames == 0) return AMOF_OK;
+    const size_t G = (size_t)out.G;
     // one image at most: no value above half the smallest periodic perpendicular height of its frame's cell
-    for (int64_t f = 0; f < F; f++) {
+    for (int64_t f = 0; f < n_frames; f++) {
         double A[9], hstep[3], hd;
         if (!pc_geometry(cells + (size_t)f * 9, grid, A, hstep, hd)) return fail(ctx, AMOF_ESINGULAR, "the cell of frame %lld is singular", (long long)f);
-        double hmin = INFINITY, top = -INFINITY;
+        double hmin = INFINITY, top;
         for (int k = 0; k < 3; k++)
             if (per[k]) hmin = std::min(hmin, hstep[k] * (double)grid[k]);
-        for (size_t x = (size_t)f * (size_t)G; x < (size_t)(f + 1) * (size_t)G; x++) {
-            if (!isfinite(field[x])) return fail(ctx, AMOF_EINVAL, "the field must be finite");
-            top = std::max(top, field[x]);
-        }
-        if (top > 0.5 * hmin * (1.0 + 1e-12))
-            return fail(ctx, AMOF_EINVAL, "the largest field value %g of frame %lld exceeds half the smallest periodic cell height %g: a sphere "
-                                          "would reach a point through two images", top, (long long)f, hmin);
+        AMOF_TRY(pore_refuse(ctx, pore_check::field_finite(field + (size_t)f * G, G, top)));
+        AMOF_TRY(pore_refuse(ctx, pore_check::half_height_field(top, f, hmin)));
     }
-
+    if (want_access) AMOF_TRY(pore_refuse(ctx, pore_check::grid(grid, per)));
     CoverCall c;
-    c.psd_hist = psd_hist;
-    c.po_counts = po_counts;
-    c.po_access = po_access;
-    c.cover = cover;
-    c.cells = cells;
-    c.n_cells = F;
-    int rc = AMOF_OK;
-    if (want_access) {
-        bool ready = false;
-        PoreAccessHook hook;
-        hook.fixed_bytes = pc_fixed_bytes(grid, cells, dmax);
-        hook.frame = [&](int64_t f, const double *d_field, StageSpans &spans) -> int {
-            if (!ready) AMOF_TRY(pc_setup(c, ctx, grid, per, nbins, n_t, dr, dmax, thresholds));
-            ready = true;
-            return pc_frame(c, f, d_field, spans);
-        };
-        hook.threshold = [&](int64_t f, int32_t k, const double *d_field, const int32_t *parent, const int32_t *mark, bool channels,
-                             StageSpans &spans) -> int { return pc_threshold(c, f, k, d_field, parent, mark, channels, spans); };
-        std::vector<int64_t> access((size_t)F * std::max(1, n_t) * 4);
-        rc = pore_access_field_run(ctx, field, F, grid, pbc, thresholds, n_t, 0, access.data(), nullptr, nullptr, &hook);
-    } else {
-        AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        timing_begin(ctx);
-        StageSpans spans(ctx);
-        rc = pc_setup(c, ctx, grid, per, nbins, n_t, dr, dmax, thresholds);
-        void *d_field = nullptr;
-        if (rc == AMOF_OK) rc = ensure(ctx, SLOT_OUT1, (size_t)G * sizeof(double), &d_field);
-        if (rc == AMOF_OK) timing_dom_begin(ctx, "pore_cover_brick");
-        for (int64_t f = 0; f < F && rc == AMOF_OK; f++) {
-            const hipError_t e = hipMemcpyAsync(d_field, field + (size_t)f * (size_t)G, (size_t)G * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
-            rc = e == hipSuccess ? pc_frame(c, f, (const double *)d_field, spans) : fail(ctx, AMOF_EHIP, "hipMemcpyAsync failed: %s", hipGetErrorString(e));
-        }
-        if (rc == AMOF_OK) {
-            timing_dom_end(ctx, c.launches);
-            timing_end(ctx);
-            if (sync_stream(ctx) != hipSuccess) rc = fail(ctx, AMOF_EHIP, "hipStreamSynchronize failed");
-            else spans.collect();
-        }
-    }
-    if (rc != AMOF_OK) {
-        pc_zero(F, G, nbins, n_t, psd_hist, po_counts, po_access, cover);
-        return rc;
-    }
-    pc_finish(c);
-    return AMOF_OK;
+    pc_plan(c, ctx, in, out);
+    out.zero(false);
+    PoreStages stages{nullptr, &c};
+    return out.keep(want_access ? pore_access_run(ctx, in, out, &c) : pore_given_field_run(ctx, in, out, stages, "pore_cover_brick"));
 }
 
 extern "C" int amof_pore_cover_stats(const amof_ctx *ctx, double *out3)

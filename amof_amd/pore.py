@@ -378,25 +378,23 @@ class Pore(Deferred):
         def call(tr, frame_range=None):
             # one int64 row per frame -- histogram, probe counts, the bits of vmax, argmax, the bits of the cell volume and of
             # the position of vmax -- so that one gather merges the ranks
-            last = []
+            flags = dict(per_point=per_point, labelled=labelled, free_sphere=free_sphere, labels=want_labels, psd=psd,
+                         accessibility=psd and accessibility)
             if psd:
-                res = list(ctx.pore_psd(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point,
-                                        accessibility=accessibility, free_sphere=free_sphere, labels=want_labels))
-                n_last = 2 + accessibility + per_point
-                last, res = res[len(res) - n_last:], res[:len(res) - n_last]
+                res = ctx.pore_psd(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point,
+                                   accessibility=accessibility, free_sphere=free_sphere, labels=want_labels)
             elif labelled:
-                res = list(ctx.pore_access(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point,
-                                           free_sphere=free_sphere, labels=want_labels))
-            if labelled:
-                more = [res[4].reshape(-1, 4 * n_t)] + ([res.pop(5).view(np.int64)] if free_sphere else [])
-                res = res[:4] + res[5:]
-            elif psd:
-                more = []
+                res = ctx.pore_access(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point,
+                                      free_sphere=free_sphere, labels=want_labels)
             else:
-                res, more = ctx.pore_field(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point), []
+                res = ctx.pore_field(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point)
+            r = _hip.PoreResult(**dict(zip(_hip.pore_names(**flags), res, strict=True)))       # (None: not asked for)
+            more = []
+            if labelled:
+                more += [r.access.reshape(-1, 4 * n_t)] + ([r.free_sphere.view(np.int64)] if free_sphere else [])
             if psd:
-                more += [last[0].view(np.int64), last[1]] + ([last[2]] if accessibility else [])
-            hist, counts, vmax, argmax = res[:4]
+                more += [r.psd_hist.view(np.int64), r.po_counts] + ([r.po_access] if accessibility else [])
+            hist, counts, vmax, argmax = r.hist, r.counts, r.vmax, r.argmax
             f0, f1 = (0, len(vmax)) if frame_range is None else frame_range
             c = np.asarray(tr.cell, dtype=np.float64).reshape(-1, 3, 3)
             c = np.broadcast_to(c, (f1 - f0, 3, 3)) if c.shape[0] == 1 else c[f0:f1]
@@ -404,7 +402,7 @@ class Pore(Deferred):
             where = np.ascontiguousarray(positions(argmax, c, grid), dtype=np.float64).reshape(-1, 3)
             rows = np.concatenate([hist.view(np.int64), counts, vmax.view(np.int64)[:, None], argmax[:, None],
                                    volume.view(np.int64)[:, None], where.view(np.int64)] + more, axis=1)
-            return rows, (res[4] if per_point else None), (res[5] if want_labels else None), (last[-1] if want_cover else None)
+            return rows, r.field, r.labels, r.cover
 
         if _setup.streamed(st):
             def walk():

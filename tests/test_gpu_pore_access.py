@@ -30,6 +30,11 @@ def _same(a, b):
                                     for x, y in zip(a, b))
 
 
+def _unzeroed(arrays):
+    """the names of the arrays a refusal left something in"""
+    return [k for k, v in arrays.items() if v.any()]
+
+
 # ---- 1. synthetic fields ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", acases.NAMES)
 def test_synthetic_topologies(hip_ctx, name):
@@ -168,6 +173,43 @@ def test_refusals_leave_the_context_usable(hip_ctx):
     assert rc == _hip.AMOF_ECAPACITY
     with pytest.raises(ValueError):
         hip_ctx.pore_access_field(np.full((1, 4, 4, 4), np.nan), acases.PBC, (0.0,))
+    # a refusal after the sizes are known leaves zeros in every array given ("zeros after an error", include/amof_hip.h)
+    lib, h, ptr = hip_ctx._lib, hip_ctx._h, _hip._ptr
+    th = hip_ctx._traj(c.packed)
+    F, G, far = th.n_frames, c.G, 6.0                   # dmax + R = 7.39 above half the smallest height, 7.15
+    nb = int(np.rint(far / c.dr))
+    grid3, thr3, radii = _hip._i32(c.grid), np.array(THRESHOLDS), np.ascontiguousarray(c.radii, dtype=np.float64)
+
+    def sevens():
+        return dict(hist=np.full((F, nb + 2), 7, dtype=np.uint64), counts=np.full((F, 3), 7, dtype=np.int64), vmax=np.full(F, 7.0),
+                    argmax=np.full(F, 7, dtype=np.int64), access=np.full((F, 3, 4), 7, dtype=np.int64), free=np.full((F, 2), 7.0),
+                    field=np.full((F, G), 7.0), labels=np.full((F, 3, G), 7, dtype=np.int32))
+
+    a = sevens()
+    rc = lib.amof_pore_field(h, ctypes.byref(th.c), ptr(radii), ptr(grid3), c.dr, far, ptr(thr3), 3, ptr(a["hist"]), ptr(a["counts"]),
+                             ptr(a["vmax"]), ptr(a["argmax"]), ptr(a["field"]))
+    assert rc == _hip.AMOF_EINVAL
+    assert _unzeroed({k: a[k] for k in ("hist", "counts", "vmax", "argmax", "field")}) == []
+    a = sevens()
+    rc = lib.amof_pore_access(h, ctypes.byref(th.c), ptr(radii), ptr(grid3), c.dr, far, ptr(thr3), 3, 1, ptr(a["hist"]), ptr(a["counts"]),
+                              ptr(a["vmax"]), ptr(a["argmax"]), ptr(a["access"]), ptr(a["free"]), ptr(a["field"]), ptr(a["labels"]))
+    assert rc == _hip.AMOF_EINVAL
+    with pytest.raises(ValueError, match="half the smallest cell height"):
+        hip_ctx._check(rc)
+    assert _unzeroed(a) == []
+    bad = ok.field.copy()
+    bad[0, 1, 2, 3] = np.nan
+    Gf = int(np.prod(ok.grid))
+    access, free, labels = np.full((1, 1, 4), 7, dtype=np.int64), np.full((1, 2), 7.0), np.full((1, 1, Gf), 7, dtype=np.int32)
+    rc = lib.amof_pore_access_field(h, ptr(bad), 1, ptr(grid), ptr(per), ptr(thr), 1, 1, ptr(access), ptr(free), ptr(labels))
+    assert rc == _hip.AMOF_EINVAL
+    assert _unzeroed(dict(access=access, free=free, labels=labels)) == []
+    # valid calls follow: the known answers
+    rows, _ = pore_cases.reference("rect")
+    hist, counts, _, _ = hip_ctx.pore_field(c.packed, c.radii, c.grid, c.dr, c.dmax, c.thresholds)
+    assert np.array_equal(hist, rows.rows) and np.array_equal(counts, rows.counts)
+    got = hip_ctx.pore_access(c.packed, c.radii, c.grid, c.dr, c.dmax, c.thresholds)
+    assert np.array_equal(got[0], rows.rows) and np.array_equal(got[1], rows.counts) and (got[4][:, :, 0] <= counts).all()
     want = acases.reference("helix")
     assert _same(hip_ctx.pore_access_field(ok.field, ok.pbc, ok.thresholds, free_sphere=True, labels=True), (want[0], want[2], want[1]))
 

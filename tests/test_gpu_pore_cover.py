@@ -14,7 +14,7 @@ from tests import pore_access_cases as acases
 from tests import pore_cases
 from tests import pore_cover_ref as ref
 from tests.test_gpu_bond import SHEARED, _device, _env
-from tests.test_gpu_pore_access import _restated, _same
+from tests.test_gpu_pore_access import _restated, _same, _unzeroed
 from tests.test_pore_cover_host import CUBE, restated_rows
 
 pytestmark = pytest.mark.gpu
@@ -165,6 +165,46 @@ def test_a_brick_list_too_short_sends_the_frame_to_the_exact_path(hip_ctx):
 
 
 # ---- 2. atoms ---------------------------------------------------------------------------------------------------------------
+# (what the test below printed when run against the library of the commit before the stage pipeline: the full call, and the
+# labelling-only call whose count holds both rounds)
+RESTART_REPORT = ("pore_cover_brick", 9, {"bricks": 36.0, "source_bricks": 1118.0, "records": 26334.0})
+RESTART_LABELLINGS = ("pore_label_tile", 90)
+
+
+def test_the_field_tiers_start_over_with_stages_attached(hip_ctx):
+    """an atom 2 x 10^4 cells away (the cell sort calls 10^4 too far and raises its flag): pore_brick runs every batch, the
+    labelling and the covering behind each, and is abandoned; pore_exact hands every frame to the stages once more.  Every
+    output is the one of the call that starts on pore_exact, and so is what the call reports: the covering stage's counters
+    start over with the tiers."""
+    from amof_amd.frames import PackedTrajectory
+    c = pore_cases.case("rect")
+    pos = np.array(c.packed.pos[:3], dtype=np.float64)
+    pos[1, 0, 0] += 2.0e4 * c.packed.cell.reshape(-1, 3, 3)[0, 0, 0]
+    far = PackedTrajectory(pos, c.packed.cell, c.packed.numbers)
+    args = (c.radii, c.grid, c.dr, c.dmax, THRESHOLDS)
+    kw = dict(per_point=True, accessibility=True, free_sphere=True, labels=True)
+    hip_ctx.pore_field(far, *args)
+    assert hip_ctx.last_path() == "pore_exact"                  # (pore_brick gave up on this input, through its own flag)
+    hip_ctx.pore_field(c.packed, *args)
+    assert hip_ctx.last_path() == "pore_brick"
+    seen = {}
+    for env in ({}, {"AMOF_PORE_EXACT": "1"}):
+        with _env(AMOF_PORE_BATCH="1", **env):
+            got = hip_ctx.pore_psd(far, *args, **kw)
+            seen[len(env)] = (got, hip_ctx.last_path(), hip_ctx.last_kernel_launches(), hip_ctx.pore_cover_stats())
+    assert len(seen[0][0]) == 12 and _same(seen[0][0], seen[1][0])
+    assert seen[0][1:] == seen[1][1:]
+    assert seen[0][1:] == RESTART_REPORT
+    # the labelling stage alone: its count of labellings goes on across the restart, both rounds are in it
+    count = {}
+    for env in ({}, {"AMOF_PORE_EXACT": "1"}):
+        with _env(AMOF_PORE_BATCH="1", **env):
+            got = hip_ctx.pore_access(far, *args, free_sphere=True)
+            count[len(env)] = (hip_ctx.last_path(), hip_ctx.last_kernel_launches())
+        assert _same(got, seen[0][0][:6])
+    assert count[0] == ("pore_label_tile", 2 * count[1][1]) and count[0] == RESTART_LABELLINGS, count
+
+
 @pytest.mark.parametrize("name", ["rect", "zif4", "sheared", "npt_sheared", "open", "planted"])
 def test_atoms_every_path_batching_residence_and_frame_range(hip_ctx, name):
     c = pore_cases.case(name)
@@ -297,6 +337,22 @@ def test_refusals_leave_zeros_and_the_context_usable(hip_ctx):
     assert rc == _hip.AMOF_EINVAL
     for a in (hist, counts, vmax, argmax, access, psd_hist, po):
         assert not a.any()
+    # every array given, refused after the sizes are known (dmax + R = 7.39 above half the smallest height, 7.15): zeros in all twelve
+    far = 6.0
+    nb6 = int(np.rint(far / c.dr))
+    a = dict(hist=np.full((F, nb6 + 2), 7, dtype=np.uint64), counts=np.full((F, 3), 7, dtype=np.int64), vmax=np.full(F, 7.0),
+             argmax=np.full(F, 7, dtype=np.int64), access=np.full((F, 3, 4), 7, dtype=np.int64), free=np.full((F, 2), 7.0),
+             field=np.full((F, G), 7.0), labels=np.full((F, 3, G), 7, dtype=np.int32), psd_hist=np.full((F, nb6 + 2), 7, dtype=np.uint64),
+             po=np.full((F, 3), 7, dtype=np.int64), po_access=np.full((F, 3), 7, dtype=np.int64), cover=np.full((F, G), 7.0))
+    rc = lib.amof_pore_psd(h, ctypes.byref(th.c), ptr(radii), ptr(grid3), c.dr, far, ptr(thr3), 3, 1, 1, *[ptr(v) for v in a.values()])
+    assert rc == _hip.AMOF_EINVAL
+    with pytest.raises(ValueError, match="half the smallest cell height"):
+        hip_ctx._check(rc)
+    assert _unzeroed(a) == []
+    # ... and a valid call follows: the restatement's integers on the library's field
+    got = hip_ctx.pore_psd(c.packed, c.radii, c.grid, c.dr, c.dmax, THRESHOLDS, per_point=True)
+    want = restated_rows(got[4], c.packed.cell, (True, True, True), c.dr, c.dmax, THRESHOLDS, False)
+    assert _same(got[5:7], want[:2]) and np.array_equal(got[7], want[3])
     # accessibility needs three points on a periodic axis, as the labelling does
     with pytest.raises(ValueError, match="periodic axis"):
         hip_ctx.pore_psd_field(np.ones((1, 2, 5, 5)), np.diag([4.0, 10.0, 10.0]), PBC, 0.25, 4.0, thr, accessibility=True)
