@@ -19,31 +19,21 @@
 // that no counter can overflow) and added with integer atomics -- LDS counters flushed to u64, or straight into global
 // memory (sq_bin_global) when (P + 1) nbins counters do not fit the LDS budget, or on request (AMOF_SQ_GLOBAL=1).  Integer
 // sums are independent of the order of the atomics, of the batching and of how frames are split across ranks.
+//
+// The rules behind every launch -- the constants, the species and hkl orders and the runs, the fixed-point scales, batches,
+// chunks, grids and LDS sizes -- are sq_plan.h's (host only, pinned by tests/test_sq_plan_cpu.py); the host code, after the
+// kernels, checks, stages, launches and fetches: one call record, one stage function each.
 #include <math.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <numeric>
 #include <vector>
 
 #include "amof_internal.h"
+#include "sq_plan.h"
 
 namespace amof {
 namespace {
-
-constexpr int SQ_THREADS = 256;
-constexpr int SQ_RUN = 16;                  // vectors per thread (registers: two f32 partials and two f64 sums each)
-constexpr int SQ_BLOCK = 64;                // atoms per f32 partial
-constexpr size_t SQ_LDS_BUDGET = 64 * 1024; // LDS counters of sq_bin_kernel (u64)
-constexpr size_t SQ_RHO_BUDGET = (size_t)512 << 20;   // bytes of rho per batch of frames
-constexpr int SQ_BIN_BLOCKS = 1024;         // workgroups of sq_bin_kernel (grid-stride over the samples)
-
-struct SqRun {
-    int32_t h, k, l0, n;    // vectors (h, k, l0 + r), r < n
-    int32_t start;          // into order[]: the callers' indices of the run's vectors
-    int32_t _pad[3];
-};
 
 // Q[b][i] = quantize_atom of atom perm[i] of frame frames[b] (components in cell-vector order)
 __global__ __launch_bounds__(256) void sq_quantize_kernel(const double *__restrict__ pos, const double *__restrict__ geom,
@@ -170,257 +160,6 @@ __global__ __launch_bounds__(SQ_THREADS) void sq_bin_kernel(const double *__rest
     }
 }
 
-// The largest number of vectors one bin can receive in one frame of ANY of the n_cells cells: every vector is counted in
-// each bin its |q| can reach.  |q_c| lies within delta |hkl| of |hkl . Rm|, Rm the mean reciprocal matrix and delta the
-// largest Frobenius norm of R_c - Rm (>= the spectral norm); a relative margin of 1e-9 covers the rounding of both.  One
-// pass over the vectors (a difference array over the bins): for a constant cell this is the per-bin count itself, give or
-// take a vector on a bin edge.
-int64_t sq_bin_capacity(const double *recip, int64_t n_cells, const int32_t *hkl, int32_t K, double dq, int32_t nbins)
-{
-    double Rm[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, delta = 0.0;
-    for (int64_t c = 0; c < n_cells; c++)
-        for (int i = 0; i < 9; i++) Rm[i] += recip[9 * c + i];
-    for (int i = 0; i < 9; i++) Rm[i] /= (double)std::max<int64_t>(n_cells, 1);
-    for (int64_t c = 0; c < n_cells; c++) {
-        double f2 = 0.0;
-        for (int i = 0; i < 9; i++) f2 += (recip[9 * c + i] - Rm[i]) * (recip[9 * c + i] - Rm[i]);
-        delta = std::max(delta, sqrt(f2));
-    }
-    std::vector<int64_t> diff((size_t)nbins + 1, 0);
-    for (int32_t m = 0; m < K; m++) {
-        const double h = hkl[3 * m], k = hkl[3 * m + 1], l = hkl[3 * m + 2];
-        const double qx = (h * Rm[0] + k * Rm[3]) + l * Rm[6];
-        const double qy = (h * Rm[1] + k * Rm[4]) + l * Rm[7];
-        const double qz = (h * Rm[2] + k * Rm[5]) + l * Rm[8];
-        const double qm = sqrt((qx * qx + qy * qy) + qz * qz), r = delta * sqrt((h * h + k * k) + l * l);
-        const double lo = (qm - r) * (1.0 - 1e-9) / dq, hi = (qm + r) * (1.0 + 1e-9) / dq;
-        if (!(lo < (double)nbins)) continue;                // beyond in every cell
-        const int32_t b0 = lo > 0.0 ? (int32_t)lo : 0;
-        const int32_t b1 = hi < (double)nbins ? (int32_t)hi : nbins - 1;
-        diff[b0]++;
-        diff[(size_t)b1 + 1]--;
-    }
-    int64_t run = 0, best = 0;
-    for (int32_t b = 0; b < nbins; b++) {
-        run += diff[b];
-        best = std::max(best, run);
-    }
-    return best;
-}
-
-// Per-pair fixed-point scale 2^s: the sum over the trajectory's frames (ANY selection of them) of |t_ab| + 1/2 in one bin
-// stays below 2^62 -- |t_ab| <= N_a N_b, and a bin receives at most F * sq_bin_capacity samples.  The scale depends on
-// the trajectory's frame count and cells, the vectors, the bins and the species counts only: frame ranges of one
-// trajectory add up exactly (and F(q, t) -- at most F samples of a vector per lag -- shares S(q)'s scale).
-int sq_scales(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K, double dq, int32_t nbins,
-              std::vector<int32_t> &sexp, std::vector<double> &scale)
-{
-    const int S = t->n_species, P = S * (S + 1) / 2;
-    const int64_t N = t->n_atoms, F = t->n_frames;
-    std::vector<int64_t> nsp(S, 0);
-    for (int64_t i = 0; i < N; i++) nsp[t->species[i]]++;
-    const int64_t cap = sq_bin_capacity(recip, t->n_cells, hkl, K, dq, nbins);
-    sexp.assign(P, 0);
-    scale.assign(P, 0.0);
-    int p = 0;
-    for (int a = 0; a < S; a++)
-        for (int c = a; c < S; c++, p++) {
-            const double bound = (double)std::max<int64_t>(F, 1) * (double)std::max<int64_t>(cap, 1) *
-                                 ((double)std::max<int64_t>(nsp[a], 1) * (double)std::max<int64_t>(nsp[c], 1) + 0.5);
-            int e;
-            frexp(bound, &e);               // bound < 2^e
-            sexp[p] = std::min(62 - e, 60);
-            scale[p] = ldexp(1.0, sexp[p]);
-            // the quantum 2^-s in S units (divided by sqrt(N_a N_b)) must not exceed 2^-20
-            const double nab = sqrt((double)std::max<int64_t>(nsp[a], 1) * (double)std::max<int64_t>(nsp[c], 1));
-            if (ldexp(1.0, -sexp[p]) / nab > ldexp(1.0, -20))
-                return fail(ctx, AMOF_ECAPACITY, "S(q): %lld frames x %lld vectors per bin x %lld x %lld atoms exceed the "
-                                                 "fixed-point range (quantum above 2^-20): use fewer frames per call, a "
-                                                 "smaller dq or fewer vectors per bin (max_points)",
-                            (long long)F, (long long)cap, (long long)nsp[a], (long long)nsp[c]);
-        }
-    return AMOF_OK;
-}
-
-struct SqPlan {
-    std::vector<int32_t> perm;          // atoms in species order (stable)
-    std::vector<int64_t> sp_first;      // [S + 1]
-    std::vector<SqRun> runs;
-    std::vector<int32_t> order;         // [K]: the callers' index of every sorted vector
-};
-
-int sq_plan(amof_ctx *ctx, const amof_traj *t, const int32_t *hkl, int32_t K, SqPlan &pl)
-{
-    const int S = t->n_species;
-    const int64_t N = t->n_atoms;
-    pl.sp_first.assign(S + 1, 0);
-    for (int64_t i = 0; i < N; i++) pl.sp_first[t->species[i] + 1]++;
-    for (int s = 0; s < S; s++) pl.sp_first[s + 1] += pl.sp_first[s];
-    pl.perm.resize(N);
-    std::vector<int64_t> cur(pl.sp_first.begin(), pl.sp_first.end() - 1);
-    for (int64_t i = 0; i < N; i++) pl.perm[cur[t->species[i]]++] = (int32_t)i;
-    for (int32_t m = 0; m < K; m++)
-        if (hkl[3 * m] == 0 && hkl[3 * m + 1] == 0 && hkl[3 * m + 2] == 0)
-            return fail(ctx, AMOF_EINVAL, "hkl %d is (0, 0, 0)", m);
-    // rows of consecutive l at fixed (h, k), cut into runs of at most SQ_RUN
-    pl.order.resize(K);
-    std::iota(pl.order.begin(), pl.order.end(), 0);
-    std::sort(pl.order.begin(), pl.order.end(), [&](int32_t x, int32_t y) {
-        const int32_t *a = hkl + 3 * x, *b = hkl + 3 * y;
-        if (a[0] != b[0]) return a[0] < b[0];
-        if (a[1] != b[1]) return a[1] < b[1];
-        if (a[2] != b[2]) return a[2] < b[2];
-        return x < y;
-    });
-    pl.runs.clear();
-    for (int32_t i = 0; i < K; i++) {
-        const int32_t *v = hkl + 3 * pl.order[i];
-        if (!pl.runs.empty()) {
-            SqRun &r = pl.runs.back();
-            if (r.n < SQ_RUN && r.h == v[0] && r.k == v[1] && (int64_t)r.l0 + r.n == (int64_t)v[2]) {
-                r.n++;
-                continue;
-            }
-        }
-        pl.runs.push_back(SqRun{v[0], v[1], v[2], 1, i, {0, 0, 0}});
-    }
-    return AMOF_OK;
-}
-
-int sq_check_traj(amof_ctx *ctx, const amof_traj *t, const int32_t *hkl, int32_t K)
-{
-    AMOF_TRY(validate_traj(ctx, t, false));
-    if (!t->pbc[0] || !t->pbc[1] || !t->pbc[2]) return fail(ctx, AMOF_EINVAL, "S(q) needs a cell periodic on all three axes");
-    if (K < 0 || (K > 0 && !hkl)) return fail(ctx, AMOF_EINVAL, "bad hkl list");
-    if (t->n_atoms > 0 && !t->species) return fail(ctx, AMOF_EINVAL, "NULL species");
-    return AMOF_OK;
-}
-
-// rho of the frames fsel[f0 .. f0 + nb) into d_rho [nb][K][S][2]
-int sq_rho_batch(amof_ctx *ctx, const amof_traj *t, const double *pos_dev, const double *d_geom, const int32_t *d_perm,
-                 const int64_t *d_spfirst, const SqRun *d_runs, int n_runs, const int32_t *d_order, int K,
-                 const int32_t *d_frames, int nb, uint4 *d_Q, int32_t *d_flag, double *d_rho)
-{
-    const int64_t N = t->n_atoms;
-    if (N > 0)
-        hipLaunchKernelGGL(sq_quantize_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream, pos_dev,
-                       d_geom, t->n_cells, d_perm, N, d_frames, d_Q, d_flag);
-    AMOF_HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(sq_rho_kernel, dim3((unsigned)((n_runs + SQ_THREADS - 1) / SQ_THREADS), (unsigned)nb), dim3(SQ_THREADS), 0,
-                       ctx->stream, (const uint4 *)d_Q, N, d_spfirst, t->n_species, d_runs, n_runs, d_order, K, d_rho);
-    AMOF_HIP_TRY(ctx, hipGetLastError());
-    return AMOF_OK;
-}
-
-// host outputs (counts, sums: f64, beyond -- overwritten) or device outputs (counts_dev, sums_dev: int64 fixed point,
-// beyond_dev -- added into; scale_log2 receives the pairs' exponents)
-int sq_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K, int64_t frame_begin,
-           int64_t frame_end, int64_t frame_stride, double dq, int32_t nbins, uint64_t *counts, double *sums, uint64_t *beyond,
-           uint64_t *counts_dev, int64_t *sums_dev, uint64_t *beyond_dev, int32_t *scale_log2)
-{
-    AMOF_TRY(sq_check_traj(ctx, t, hkl, K));
-    const int S = t->n_species, P = S * (S + 1) / 2;
-    const int64_t N = t->n_atoms, F = t->n_frames;
-    if (!recip && t->n_cells > 0) return fail(ctx, AMOF_EINVAL, "NULL recip");
-    if (frame_stride < 1 || frame_begin < 0 || frame_end > F || frame_begin > frame_end)
-        return fail(ctx, AMOF_EINVAL, "bad frame range");
-    if (!(dq > 0.0) || !isfinite(dq)) return fail(ctx, AMOF_EINVAL, "dq must be positive and finite");
-    if (nbins < 1) return fail(ctx, AMOF_EINVAL, "nbins must be >= 1");
-    for (int64_t c = 0; c < 9 * t->n_cells; c++)
-        if (!isfinite(recip[c])) return fail(ctx, AMOF_EINVAL, "recip is not finite");
-    if ((size_t)(P + 1) * (size_t)nbins > ((size_t)1 << 36)) return fail(ctx, AMOF_EINVAL, "histogram too large");
-    std::vector<int32_t> sexp;
-    std::vector<double> scale;
-    AMOF_TRY(sq_scales(ctx, t, recip, hkl, K, dq, nbins, sexp, scale));
-    if (scale_log2) std::copy(sexp.begin(), sexp.end(), scale_log2);
-    if (counts) {
-        std::fill(counts, counts + nbins, (uint64_t)0);
-        std::fill(sums, sums + (size_t)P * nbins, 0.0);
-        *beyond = 0;
-    }
-    std::vector<int32_t> fsel;
-    for (int64_t f = frame_begin; f < frame_end; f += frame_stride) fsel.push_back((int32_t)f);
-    if (fsel.empty() || K == 0) return AMOF_OK;
-
-    HostGeom hg;
-    AMOF_TRY(build_geometry(ctx, t, hg));
-    SqPlan pl;
-    AMOF_TRY(sq_plan(ctx, t, hkl, K, pl));
-    const size_t rho_frame = (size_t)K * S * 2 * sizeof(double);
-    const int nb_max = (int)std::max<size_t>(1, std::min<size_t>({SQ_RHO_BUDGET / rho_frame, fsel.size(), (size_t)65535}));
-    const size_t n_ctr = (size_t)(P + 1) * nbins + 1;
-    const bool global = n_ctr * sizeof(uint64_t) > SQ_LDS_BUDGET || getenv("AMOF_SQ_GLOBAL");
-
-    AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    timing_begin(ctx);
-    const double *pos_dev = nullptr;
-    AMOF_TRY(stage_positions(ctx, t, &pos_dev));
-    UploadPack pk;
-    const int i_geom = pk.add(hg.rec.data(), hg.rec.size() * sizeof(double));
-    const int i_perm = pk.add(pl.perm.data(), pl.perm.size() * sizeof(int32_t));
-    const int i_spf = pk.add(pl.sp_first.data(), pl.sp_first.size() * sizeof(int64_t));
-    const int i_runs = pk.add(pl.runs.data(), pl.runs.size() * sizeof(SqRun));
-    const int i_order = pk.add(pl.order.data(), pl.order.size() * sizeof(int32_t));
-    const int i_hkl = pk.add(hkl, (size_t)K * 3 * sizeof(int32_t));
-    const int i_recip = pk.add(recip, (size_t)t->n_cells * 9 * sizeof(double));
-    const int i_frames = pk.add(fsel.data(), fsel.size() * sizeof(int32_t));
-    const int i_scale = pk.add(scale.data(), scale.size() * sizeof(double));
-    AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
-    void *d_Q = nullptr, *d_rho = nullptr, *d_flag = nullptr, *d_ctr = nullptr;
-    AMOF_TRY(ensure(ctx, SLOT_AUX0, (size_t)nb_max * std::max<int64_t>(N, 1) * sizeof(uint4), &d_Q));
-    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)nb_max * rho_frame, &d_rho));
-    AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), ctx->stream));
-    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(counts_dev);
-    unsigned long long *sm = reinterpret_cast<unsigned long long *>(sums_dev);
-    unsigned long long *bey = reinterpret_cast<unsigned long long *>(beyond_dev);
-    if (counts) {       // host call: the counters start from zero in scratch
-        AMOF_TRY(ensure(ctx, SLOT_OUT1, n_ctr * sizeof(uint64_t), &d_ctr));
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, n_ctr * sizeof(uint64_t), ctx->stream));
-        cnt = (unsigned long long *)d_ctr;
-        sm = cnt + nbins;
-        bey = sm + (size_t)P * nbins;
-    }
-    if (!global) AMOF_HIP_TRY(ctx, allow_max_lds((const void *)sq_bin_kernel<false>));
-    const int n_runs = (int)pl.runs.size();
-    timing_dom_begin(ctx, global ? "sq_bin_global" : "sq");
-    int64_t launches = 0;
-    for (size_t f0 = 0; f0 < fsel.size(); f0 += nb_max) {
-        const int nb = (int)std::min<size_t>(nb_max, fsel.size() - f0);
-        const int32_t *d_frames = pk.ptr<int32_t>(i_frames) + f0;
-        AMOF_TRY(sq_rho_batch(ctx, t, pos_dev, pk.ptr<double>(i_geom), pk.ptr<int32_t>(i_perm), pk.ptr<int64_t>(i_spf),
-                              pk.ptr<SqRun>(i_runs), n_runs, pk.ptr<int32_t>(i_order), K, d_frames, nb, (uint4 *)d_Q,
-                              (int32_t *)d_flag, (double *)d_rho));
-        const int64_t samples = (int64_t)nb * K;
-        const unsigned blocks = (unsigned)std::min<int64_t>(SQ_BIN_BLOCKS, (samples + SQ_THREADS - 1) / SQ_THREADS);
-        if (global)
-            hipLaunchKernelGGL(sq_bin_kernel<true>, dim3(blocks), dim3(SQ_THREADS), 0, ctx->stream, (const double *)d_rho, nb, K, S,
-                               pk.ptr<int32_t>(i_hkl), pk.ptr<double>(i_recip), t->n_cells, d_frames, dq, (int)nbins,
-                               pk.ptr<double>(i_scale), cnt, sm, bey);
-        else
-            hipLaunchKernelGGL(sq_bin_kernel<false>, dim3(blocks), dim3(SQ_THREADS), n_ctr * sizeof(uint64_t), ctx->stream,
-                               (const double *)d_rho, nb, K, S, pk.ptr<int32_t>(i_hkl), pk.ptr<double>(i_recip), t->n_cells,
-                               d_frames, dq, (int)nbins, pk.ptr<double>(i_scale), cnt, sm, bey);
-        AMOF_HIP_TRY(ctx, hipGetLastError());
-        launches += 3;
-    }
-    timing_dom_end(ctx, launches);
-    timing_end(ctx);
-    int32_t flag = 0;
-    AMOF_TRY(fetch(ctx, &flag, d_flag, sizeof(int32_t)));
-    if (flag) return fail(ctx, AMOF_EINVAL, "positions lie more than 10^4 cells from the cell, or are not finite");
-    if (counts) {
-        std::vector<int64_t> raw((size_t)P * nbins);
-        AMOF_TRY(fetch(ctx, counts, cnt, (size_t)nbins * sizeof(uint64_t)));
-        AMOF_TRY(fetch(ctx, raw.data(), sm, raw.size() * sizeof(int64_t)));
-        AMOF_TRY(fetch(ctx, beyond, bey, sizeof(uint64_t)));
-        for (int p = 0; p < P; p++)
-            for (int b = 0; b < nbins; b++) sums[(size_t)p * nbins + b] = ldexp((double)raw[(size_t)p * nbins + b], -sexp[p]);
-    }
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    return AMOF_OK;
-}
-
 // ------------------------------------------------------------------------------------------------ F(q, t) --
 // Intermediate scattering function: the time correlation of the rho table (amof_isf_accumulate[_dev]).
 //
@@ -440,23 +179,6 @@ int sq_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t
 // (lane, lag, pair) and tile -- into per-lag LDS counter tiles ((1 + S^2) nbins u64 each; as many lags per pass as fit
 // ISF_LDS_BUDGET, flushed to global memory after each pass) or straight into global memory ("isf_global").  S > ISF_SMAX
 // takes a generic form of the same kernel (one atomic per sample, rows re-read through the caches).
-constexpr int ISF_THREADS = 256;
-constexpr int ISF_TILE = 4;                 // origins whose rows a lane holds in registers
-constexpr int ISF_SMAX = 4;                 // species counts with a register form
-constexpr int ISF_OPW = 64;                 // at most this many origins per workgroup
-constexpr size_t ISF_LDS_BUDGET = 64 * 1024;
-// rho table of one vector chunk: 1 GiB, twice S(q)'s batch.  The table is streamed (1 + W) times whatever its size, but a
-// thread of sq_rho_kernel owns a run of up to 16 vectors and a chunk is cut to whole waves of runs: on the headline shape
-// (5000 frames, 4 species: 320 KB per vector) 512 MB hold ~126 runs -- one whole wave, 13 launches with a tail each, the
-// table 14 % slower than S(q)'s -- where 1 GiB holds three.  Next to Q (16 N bytes per frame) a rank's scratch stays near
-// 2 GB there.  AMOF_ISF_RHO_BUDGET (bytes) overrides it (tests: several chunks on a small case).
-constexpr size_t ISF_RHO_BUDGET = (size_t)1 << 30;
-
-struct IsfEntry {
-    int32_t w, k;           // lag index, origin frame
-    int32_t sk, skm;        // slots of frames k and k + m in Q
-};
-
 struct IsfArgs {
     const double *rho;          // [slots][Kc][S][2]
     const int32_t *slot_of;     // [F]: slot of a frame in Q / rho (-1: not touched)
@@ -662,275 +384,449 @@ hipError_t isf_launch_corr(amof_ctx *ctx, const IsfArgs &a, dim3 grid, size_t ld
     }
 }
 
-// host outputs (counts, coh, selfs: f64, beyond -- overwritten) or device outputs (int64 fixed point / u64, added into;
-// scale_log2 receives the pairs' exponents).  want_self: the self part is computed (selfs / self_dev given)
-int isf_run(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K, const int32_t *windows,
-            int32_t W, int64_t stride, int64_t wb, int64_t we, double dq, int32_t nbins, bool want_self, uint64_t *counts,
-            double *coh, double *selfs, uint64_t *beyond, uint64_t *counts_dev, int64_t *coh_dev, int64_t *self_dev,
-            uint64_t *beyond_dev, int32_t *scale_log2)
-{
-    AMOF_TRY(sq_check_traj(ctx, t, hkl, K));
-    const int S = t->n_species, P = S * (S + 1) / 2;
-    const int64_t N = t->n_atoms, F = t->n_frames;
-    if (!recip && t->n_cells > 0) return fail(ctx, AMOF_EINVAL, "NULL recip");
-    AMOF_TRY(check_lag_args(ctx, windows, W, F, stride));
-    if (!(dq > 0.0) || !isfinite(dq)) return fail(ctx, AMOF_EINVAL, "dq must be positive and finite");
-    if (nbins < 1) return fail(ctx, AMOF_EINVAL, "nbins must be >= 1");
-    if (F > 0x7fffffffLL || N > 0x7fffffffLL) return fail(ctx, AMOF_EINVAL, "too many frames or atoms");
-    for (int64_t c = 0; c < 9 * t->n_cells; c++)
-        if (!isfinite(recip[c])) return fail(ctx, AMOF_EINVAL, "recip is not finite");
-    // this call's origin indices [o0, o1) of every lag (the lag-major work list of amof_vanhove_distinct)
-    static_assert(sizeof(LagRange) == sizeof(int2), "the kernels read the table as int2");
-    std::vector<LagRange> lagiv(std::max(W, 1), LagRange{0, 0});
-    const int64_t total = lag_work_ranges(windows, W, F, stride, wb, we, lagiv.data());
-    int64_t n_entries = 0;
-    for (int w = 0; w < W; w++) n_entries += lagiv[w].o1 - lagiv[w].o0;
-    if (wb < 0 || we > total || wb > we) return fail(ctx, AMOF_EINVAL, "work range [%lld, %lld) outside [0, %lld)", (long long)wb,
-                                                     (long long)we, (long long)total);
-    const size_t n_cnt = (size_t)W * nbins, n_coh = (size_t)S * S * n_cnt, n_self = want_self ? (size_t)S * n_cnt : 0;
-    if (n_coh > ((size_t)1 << 36)) return fail(ctx, AMOF_EINVAL, "histogram too large");
-    std::vector<int32_t> sexp;
-    std::vector<double> scale;
-    AMOF_TRY(sq_scales(ctx, t, recip, hkl, K, dq, nbins, sexp, scale));
-    if (scale_log2) std::copy(sexp.begin(), sexp.end(), scale_log2);
-    std::vector<double> scale2((size_t)S * S);
-    std::vector<int32_t> sexp2((size_t)S * S);
-    {
-        int p = 0;
-        for (int a = 0; a < S; a++)
-            for (int c = a; c < S; c++, p++) {
-                scale2[a * S + c] = scale2[c * S + a] = scale[p];
-                sexp2[a * S + c] = sexp2[c * S + a] = sexp[p];
-            }
-    }
-    if (counts) {
-        std::fill(counts, counts + n_cnt, (uint64_t)0);
-        std::fill(coh, coh + n_coh, 0.0);
-        if (selfs) std::fill(selfs, selfs + n_self, 0.0);
-        std::fill(beyond, beyond + W, (uint64_t)0);
-    }
-    if (n_entries == 0 || K == 0) return AMOF_OK;
-
-    // the frames the range touches, ascending: slot s of Q and of the rho table holds frame fsel[s]
-    std::vector<int32_t> slot_of(F, -1), fsel;
-    int omin = 0x7fffffff, omax = 0;
-    for (int w = 0; w < W; w++) {
-        if (lagiv[w].o0 >= lagiv[w].o1) continue;
-        omin = std::min(omin, lagiv[w].o0);
-        omax = std::max(omax, lagiv[w].o1);
-        for (int64_t o = lagiv[w].o0; o < lagiv[w].o1; o++) {
-            const int64_t k = lag_origin_frame(o, stride);
-            slot_of[k] = 0;
-            slot_of[k + windows[w]] = 0;
-        }
-    }
-    for (int64_t f = 0; f < F; f++)
-        if (slot_of[f] == 0) {
-            slot_of[f] = (int32_t)fsel.size();
-            fsel.push_back((int32_t)f);
-        }
-    const size_t slots = fsel.size();
-
+// --------------------------------------------------------------------------------------------- host code --
+// What every stage of a call needs, filled in this order: the arguments (the entry point), S .. F (sq_check_traj), the scales
+// (sq_call_scales), the plan (build_geometry, sq_call_plan), the device side (sq_stage).
+struct SqCall {
+    amof_ctx *ctx;
+    const amof_traj *t;
+    const double *recip;        // [n_cells][9]; NULL in amof_sq_modes, which bins nothing
+    const int32_t *hkl;
+    int32_t K;
+    double dq;
+    int32_t nbins;
+    int S = 0, P = 0;
+    int64_t N = 0, F = 0;
+    SqSwitches sw = SqSwitches::from_env();
+    SqScales sc;
     HostGeom hg;
-    AMOF_TRY(build_geometry(ctx, t, hg));
     SqPlan pl;
-    AMOF_TRY(sq_plan(ctx, t, hkl, K, pl));
-    // vector chunks: whole runs of the sorted list, at most kc_max vectors (at least one run)
-    size_t budget = ISF_RHO_BUDGET;
-    if (const char *e = getenv("AMOF_ISF_RHO_BUDGET")) {
-        const long long b = atoll(e);
-        if (b > 0) budget = (size_t)b;
-    }
-    const size_t vec_bytes = slots * (size_t)S * 2 * sizeof(double);
-    const size_t kc_max = std::max<size_t>(1, budget / vec_bytes);
-    struct Chunk { int r0, r1, v0, nv; };
-    std::vector<Chunk> chunks;
-    std::vector<int32_t> order_local(K);
-    const int n_runs_all = (int)pl.runs.size();
-    for (int r0 = 0; r0 < n_runs_all;) {
-        int r1 = r0, nv = 0;
-        while (r1 < n_runs_all && (r1 == r0 || (size_t)(nv + pl.runs[r1].n) <= kc_max)) nv += pl.runs[r1++].n;
-        // a thread of sq_rho_kernel owns a run: whole waves of runs, so that a chunk leaves no lane of its last wave idle
-        if (r1 < n_runs_all && r1 - r0 > 64)
-            while ((r1 - r0) % 64) nv -= pl.runs[--r1].n;
-        chunks.push_back(Chunk{r0, r1, pl.runs[r0].start, nv});
-        for (int i = 0; i < nv; i++) order_local[pl.runs[r0].start + i] = i;
-        r0 = r1;
-    }
-    int kc_top = 0;
-    for (const Chunk &c : chunks) kc_top = std::max(kc_top, c.nv);
+    const double *pos_dev = nullptr;
+    UploadPack pk;              // a form adds its own tables before sq_stage uploads everything at once
+    int i_geom = -1, i_perm = -1, i_spf = -1, i_runs = -1, i_order = -1, i_hkl = -1, i_recip = -1, i_frames = -1;
+    uint4 *d_Q = nullptr;       // SLOT_AUX0
+    double *d_rho = nullptr;    // SLOT_AUX1
+    int32_t *d_flag = nullptr;  // SLOT_FLAGS, zeroed
+    SqCall(amof_ctx *ctx_, const amof_traj *t_, const double *recip_, const int32_t *hkl_, int32_t K_, double dq_, int32_t nbins_)
+        : ctx(ctx_), t(t_), recip(recip_), hkl(hkl_), K(K_), dq(dq_), nbins(nbins_) {}
+};
 
-    const size_t tile_ctr = (size_t)(1 + S * S) * nbins;
-    const bool global = tile_ctr * sizeof(uint64_t) > ISF_LDS_BUDGET || getenv("AMOF_ISF_GLOBAL");
-    const int lags_per_pass = global ? W : (int)std::min<size_t>(W, ISF_LDS_BUDGET / (tile_ctr * sizeof(uint64_t)));
+// The caller's arrays.  Host form: counts, sums (F(q, t): coh), selfs, beyond -- f64, overwritten.  Device form: int64 fixed
+// point / u64, added into, and scale_log2 receives the pairs' exponents.  An entry point fills one of the two.
+struct SqOutputs {
+    uint64_t *counts = nullptr, *beyond = nullptr;
+    double *sums = nullptr, *selfs = nullptr;
+    uint64_t *counts_dev = nullptr, *beyond_dev = nullptr;
+    int64_t *sums_dev = nullptr, *self_dev = nullptr;
+    int32_t *scale_log2 = nullptr;
+    bool host() const { return counts != nullptr; }
+};
 
-    std::vector<IsfEntry> entries;
-    if (want_self) {
-        entries.reserve(n_entries);
-        for (int w = 0; w < W; w++)
-            for (int64_t o = lagiv[w].o0; o < lagiv[w].o1; o++) {
-                const int64_t k = lag_origin_frame(o, stride);
-                entries.push_back(IsfEntry{w, (int32_t)k, slot_of[k], slot_of[k + windows[w]]});
-            }
-    }
+int sq_check_traj(SqCall &c)
+{
+    const amof_traj *t = c.t;
+    AMOF_TRY(validate_traj(c.ctx, t, false));
+    if (!t->pbc[0] || !t->pbc[1] || !t->pbc[2]) return fail(c.ctx, AMOF_EINVAL, "S(q) needs a cell periodic on all three axes");
+    if (c.K < 0 || (c.K > 0 && !c.hkl)) return fail(c.ctx, AMOF_EINVAL, "bad hkl list");
+    if (t->n_atoms > 0 && !t->species) return fail(c.ctx, AMOF_EINVAL, "NULL species");
+    c.S = t->n_species;
+    c.P = c.S * (c.S + 1) / 2;
+    c.N = t->n_atoms;
+    c.F = t->n_frames;
+    return AMOF_OK;
+}
 
+// The arguments of amof_sq_accumulate[_dev] and amof_isf_accumulate[_dev]; range_check: the form's own frame or lag arguments,
+// in their place among the others
+template <typename RangeCheck>
+int sq_check(SqCall &c, bool isf, RangeCheck range_check)
+{
+    AMOF_TRY(sq_check_traj(c));
+    if (!c.recip && c.t->n_cells > 0) return fail(c.ctx, AMOF_EINVAL, "NULL recip");
+    AMOF_TRY(range_check());
+    if (!(c.dq > 0.0) || !isfinite(c.dq)) return fail(c.ctx, AMOF_EINVAL, "dq must be positive and finite");
+    if (c.nbins < 1) return fail(c.ctx, AMOF_EINVAL, "nbins must be >= 1");
+    if (isf && (c.F > 0x7fffffffLL || c.N > 0x7fffffffLL)) return fail(c.ctx, AMOF_EINVAL, "too many frames or atoms");
+    for (int64_t i = 0; i < 9 * c.t->n_cells; i++)
+        if (!isfinite(c.recip[i])) return fail(c.ctx, AMOF_EINVAL, "recip is not finite");
+    return AMOF_OK;
+}
+
+int sq_check_histogram(SqCall &c, size_t n_sums)
+{
+    return n_sums > ((size_t)1 << 36) ? fail(c.ctx, AMOF_EINVAL, "histogram too large") : AMOF_OK;
+}
+
+int sq_call_scales(SqCall &c, int32_t *scale_log2)
+{
+    if (sq_scales(c.t->species, c.N, c.S, c.F, c.recip, c.t->n_cells, c.hkl, c.K, c.dq, c.nbins, c.sc) >= 0)
+        return fail(c.ctx, AMOF_ECAPACITY, "S(q): %lld frames x %lld vectors per bin x %lld x %lld atoms exceed the "
+                                           "fixed-point range (quantum above 2^-20): use fewer frames per call, a "
+                                           "smaller dq or fewer vectors per bin (max_points)",
+                    (long long)c.F, (long long)c.sc.cap, (long long)c.sc.nsp[c.sc.bad_a], (long long)c.sc.nsp[c.sc.bad_c]);
+    if (scale_log2) std::copy(c.sc.sexp.begin(), c.sc.sexp.end(), scale_log2);
+    return AMOF_OK;
+}
+
+int sq_call_plan(SqCall &c)
+{
+    sq_species_order(c.t->species, c.N, c.S, c.pl);
+    const int32_t zero = sq_cut_runs(c.hkl, c.K, c.pl);
+    return zero >= 0 ? fail(c.ctx, AMOF_EINVAL, "hkl %d is (0, 0, 0)", zero) : AMOF_OK;
+}
+
+// Positions, ONE upload of the plan's tables, the frame list and whatever the form added to c.pk, then the scratch every form
+// has: Q for q_frames frames, the rho table, the flag (zeroed).  Opens the call's timing.
+int sq_stage(SqCall &c, const int32_t *frames, size_t n_frames, size_t q_frames, size_t rho_bytes)
+{
+    amof_ctx *ctx = c.ctx;
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
-    StageSpans spans(ctx);      // rho table (with the quantisation), correlation, self
-    const double *pos_dev = nullptr;
-    AMOF_TRY(stage_positions(ctx, t, &pos_dev));
-    UploadPack pk;
-    const int i_geom = pk.add(hg.rec.data(), hg.rec.size() * sizeof(double));
-    const int i_perm = pk.add(pl.perm.data(), pl.perm.size() * sizeof(int32_t));
-    const int i_spf = pk.add(pl.sp_first.data(), pl.sp_first.size() * sizeof(int64_t));
-    const int i_runs = pk.add(pl.runs.data(), pl.runs.size() * sizeof(SqRun));
-    const int i_order = pk.add(pl.order.data(), pl.order.size() * sizeof(int32_t));
-    const int i_olocal = pk.add(order_local.data(), order_local.size() * sizeof(int32_t));
-    const int i_hkl = pk.add(hkl, (size_t)K * 3 * sizeof(int32_t));
-    const int i_recip = pk.add(recip, (size_t)t->n_cells * 9 * sizeof(double));
-    const int i_frames = pk.add(fsel.data(), fsel.size() * sizeof(int32_t));
-    const int i_slot = pk.add(slot_of.data(), slot_of.size() * sizeof(int32_t));
-    const int i_scale2 = pk.add(scale2.data(), scale2.size() * sizeof(double));
-    const int i_win = pk.add(windows, (size_t)W * sizeof(int32_t));
-    const int i_iv = pk.add(lagiv.data(), lagiv.size() * sizeof(LagRange));
-    const int i_ent = pk.add(entries.data(), entries.size() * sizeof(IsfEntry));
+    AMOF_TRY(stage_positions(ctx, c.t, &c.pos_dev));
+    UploadPack &pk = c.pk;
+    c.i_geom = pk.add(c.hg.rec.data(), c.hg.rec.size() * sizeof(double));
+    c.i_perm = pk.add(c.pl.perm.data(), c.pl.perm.size() * sizeof(int32_t));
+    c.i_spf = pk.add(c.pl.sp_first.data(), c.pl.sp_first.size() * sizeof(int64_t));
+    c.i_runs = pk.add(c.pl.runs.data(), c.pl.runs.size() * sizeof(SqRun));
+    c.i_order = pk.add(c.pl.order.data(), c.pl.order.size() * sizeof(int32_t));
+    if (c.recip) {
+        c.i_hkl = pk.add(c.hkl, (size_t)c.K * 3 * sizeof(int32_t));
+        c.i_recip = pk.add(c.recip, (size_t)c.t->n_cells * 9 * sizeof(double));
+    }
+    c.i_frames = pk.add(frames, n_frames * sizeof(int32_t));
     AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
-    void *d_Q = nullptr, *d_rho = nullptr, *d_flag = nullptr, *d_ctr = nullptr;
-    AMOF_TRY(ensure(ctx, SLOT_AUX0, slots * (size_t)std::max<int64_t>(N, 1) * sizeof(uint4), &d_Q));
-    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)kc_top * vec_bytes, &d_rho));
+    void *d_Q = nullptr, *d_rho = nullptr, *d_flag = nullptr;
+    AMOF_TRY(ensure(ctx, SLOT_AUX0, q_frames * (size_t)std::max<int64_t>(c.N, 1) * sizeof(uint4), &d_Q));
+    AMOF_TRY(ensure(ctx, SLOT_AUX1, rho_bytes, &d_rho));
     AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag));
     AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), ctx->stream));
-    // the call's own counters, zeroed: [counts | coh | self | beyond]; the device form adds them into the caller's at the end
-    const size_t n_ctr = n_cnt + n_coh + n_self + (size_t)W;
-    AMOF_TRY(ensure(ctx, SLOT_OUT1, n_ctr * sizeof(uint64_t), &d_ctr));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, n_ctr * sizeof(uint64_t), ctx->stream));
-    unsigned long long *cnt = (unsigned long long *)d_ctr, *co = cnt + n_cnt, *se = co + n_coh, *bey = se + n_self;
+    c.d_Q = (uint4 *)d_Q;
+    c.d_rho = (double *)d_rho;
+    c.d_flag = (int32_t *)d_flag;
+    return AMOF_OK;
+}
 
-    // every touched frame is quantised once
-    spans.begin(0);
-    if (N > 0)
-        for (size_t s0 = 0; s0 < slots; s0 += 65535) {
-            const unsigned nb = (unsigned)std::min<size_t>(65535, slots - s0);
-            hipLaunchKernelGGL(sq_quantize_kernel, dim3((unsigned)((N + 255) / 256), nb), dim3(256), 0, ctx->stream, pos_dev,
-                               pk.ptr<double>(i_geom), t->n_cells, pk.ptr<int32_t>(i_perm), N, pk.ptr<int32_t>(i_frames) + s0,
-                               (uint4 *)d_Q + s0 * (size_t)N, (int32_t *)d_flag);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-        }
-    spans.end();
+// The two kernels below index the frame (slot, entry) by blockIdx.y, which ends at SQ_GRID_Y: the helpers cut a longer range
+// into several launches.  S(q)'s batches and the self part's never need it (nb_max, isf_self_batch); F(q, t) quantises every
+// touched frame and fills a chunk's table for all of them at once, and does.
+// Q_dst[s] = the quantised frame frames[f0 + s] of the uploaded frame list, s < n
+int sq_launch_quantize(SqCall &c, size_t f0, size_t n, uint4 *Q_dst)
+{
+    if (c.N == 0) return AMOF_OK;
+    for (size_t s0 = 0; s0 < n; s0 += SQ_GRID_Y) {
+        const unsigned nb = (unsigned)std::min<size_t>(SQ_GRID_Y, n - s0);
+        hipLaunchKernelGGL(sq_quantize_kernel, dim3((unsigned)((c.N + 255) / 256), nb), dim3(256), 0, c.ctx->stream, c.pos_dev,
+                           c.pk.ptr<double>(c.i_geom), c.t->n_cells, c.pk.ptr<int32_t>(c.i_perm), c.N,
+                           c.pk.ptr<int32_t>(c.i_frames) + f0 + s0, Q_dst + s0 * (size_t)c.N, c.d_flag);
+        AMOF_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    return AMOF_OK;
+}
 
-    IsfArgs a;
-    memset(&a, 0, sizeof a);
-    a.rho = (const double *)d_rho;
-    a.slot_of = pk.ptr<int32_t>(i_slot);
-    a.hkl = pk.ptr<int32_t>(i_hkl);
-    a.recip = pk.ptr<double>(i_recip);
-    a.scale2 = pk.ptr<double>(i_scale2);
-    a.windows = pk.ptr<int32_t>(i_win);
-    a.lagiv = pk.ptr<int2>(i_iv);
-    a.counts = cnt;
-    a.coh = co;
-    a.beyond = bey;
-    a.n_cells = t->n_cells;
-    a.stride = stride;
-    a.S = S;
-    a.W = W;
-    a.nbins = nbins;
-    a.omin = omin;
-    a.omax = omax;
-    a.lags_per_pass = lags_per_pass;
-    a.dq = dq;
-    const size_t lds = (size_t)lags_per_pass * tile_ctr * sizeof(uint64_t);
+// dst[s][d_order[..]][S][2] = rho of the coordinates src[s][N] (Q, or the self part's D), s < n, over the runs [r0, r0 + n_runs):
+// Kc vectors, numbered by d_order.  *launches (optional) counts the launches
+int sq_launch_rho(SqCall &c, const uint4 *src, size_t n, int r0, int n_runs, const int32_t *d_order, int Kc, double *dst,
+                  int64_t *launches = nullptr)
+{
+    for (size_t s0 = 0; s0 < n; s0 += SQ_GRID_Y) {
+        const unsigned nb = (unsigned)std::min<size_t>(SQ_GRID_Y, n - s0);
+        hipLaunchKernelGGL(sq_rho_kernel, dim3((unsigned)((n_runs + SQ_THREADS - 1) / SQ_THREADS), nb), dim3(SQ_THREADS), 0,
+                           c.ctx->stream, src + s0 * (size_t)c.N, c.N, c.pk.ptr<int64_t>(c.i_spf), c.S, c.pk.ptr<SqRun>(c.i_runs) + r0,
+                           n_runs, d_order, Kc, dst + s0 * (size_t)Kc * c.S * 2);
+        AMOF_HIP_TRY(c.ctx, hipGetLastError());
+        if (launches) ++*launches;
+    }
+    return AMOF_OK;
+}
 
-    timing_dom_begin(ctx, global ? "isf_global" : "isf");
+// rho of the frames frames[f0 .. f0 + nb) of the frame list, every vector: Q and the rho table from their starts
+int sq_rho_batch(SqCall &c, size_t f0, int nb)
+{
+    AMOF_TRY(sq_launch_quantize(c, f0, (size_t)nb, c.d_Q));
+    return sq_launch_rho(c, c.d_Q, (size_t)nb, 0, (int)c.pl.runs.size(), c.pk.ptr<int32_t>(c.i_order), c.K, c.d_rho);
+}
+
+// the quantiser's flag (complete on return: the stream is synchronised); timing_open: the call's timing ends before the error
+int sq_fetch_flag(SqCall &c, bool timing_open = false)
+{
+    int32_t flag = 0;
+    AMOF_TRY(fetch(c.ctx, &flag, c.d_flag, sizeof(int32_t)));
+    if (!flag) return AMOF_OK;
+    if (timing_open) timing_end(c.ctx);
+    return fail(c.ctx, AMOF_EINVAL, "positions lie more than 10^4 cells from the cell, or are not finite");
+}
+
+// fixed point to f64
+void sq_descale(const int64_t *raw, size_t n, int32_t sexp, double *out)
+{
+    for (size_t i = 0; i < n; i++) out[i] = ldexp((double)raw[i], -sexp);
+}
+
+// ---- S(q) ----
+// The host form counts in zeroed scratch and fetches; the device form adds straight into the caller's counters.
+int sq_run(SqCall &c, int64_t frame_begin, int64_t frame_end, int64_t frame_stride, const SqOutputs &out)
+{
+    amof_ctx *ctx = c.ctx;
+    AMOF_TRY(sq_check(c, false, [&] {
+        return frame_stride < 1 || frame_begin < 0 || frame_end > c.F || frame_begin > frame_end
+                   ? fail(ctx, AMOF_EINVAL, "bad frame range") : AMOF_OK;
+    }));
+    const int P = c.P, nbins = c.nbins;
+    AMOF_TRY(sq_check_histogram(c, (size_t)(P + 1) * (size_t)nbins));
+    AMOF_TRY(sq_call_scales(c, out.scale_log2));
+    if (out.host()) {
+        std::fill(out.counts, out.counts + nbins, (uint64_t)0);
+        std::fill(out.sums, out.sums + (size_t)P * nbins, 0.0);
+        *out.beyond = 0;
+    }
+    std::vector<int32_t> fsel;
+    for (int64_t f = frame_begin; f < frame_end; f += frame_stride) fsel.push_back((int32_t)f);
+    if (fsel.empty() || c.K == 0) return AMOF_OK;
+
+    AMOF_TRY(build_geometry(ctx, c.t, c.hg));
+    AMOF_TRY(sq_call_plan(c));
+    const SqBatchPlan bp = sq_batch_plan(c.K, c.S, nbins, fsel.size(), c.sw);
+    const int i_scale = c.pk.add(c.sc.scale.data(), c.sc.scale.size() * sizeof(double));
+    AMOF_TRY(sq_stage(c, fsel.data(), fsel.size(), (size_t)bp.nb_max, (size_t)bp.nb_max * bp.rho_frame));
+    unsigned long long *cnt = reinterpret_cast<unsigned long long *>(out.counts_dev);
+    unsigned long long *sm = reinterpret_cast<unsigned long long *>(out.sums_dev);
+    unsigned long long *bey = reinterpret_cast<unsigned long long *>(out.beyond_dev);
+    if (out.host()) {
+        void *d_ctr = nullptr;
+        AMOF_TRY(ensure(ctx, SLOT_OUT1, bp.n_ctr * sizeof(uint64_t), &d_ctr));
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, bp.n_ctr * sizeof(uint64_t), ctx->stream));
+        cnt = (unsigned long long *)d_ctr;
+        sm = cnt + nbins;
+        bey = sm + (size_t)P * nbins;
+    }
+    if (!bp.global) AMOF_HIP_TRY(ctx, allow_max_lds((const void *)sq_bin_kernel<false>));
+    timing_dom_begin(ctx, bp.path);
     int64_t launches = 0;
-    for (const Chunk &c : chunks) {
-        spans.begin(0);
-        const int n_runs = c.r1 - c.r0;
-        for (size_t s0 = 0; s0 < slots; s0 += 65535) {
-            const unsigned nb = (unsigned)std::min<size_t>(65535, slots - s0);
-            hipLaunchKernelGGL(sq_rho_kernel, dim3((unsigned)((n_runs + SQ_THREADS - 1) / SQ_THREADS), nb), dim3(SQ_THREADS), 0,
-                               ctx->stream, (const uint4 *)d_Q + s0 * (size_t)N, N, pk.ptr<int64_t>(i_spf), S,
-                               pk.ptr<SqRun>(i_runs) + c.r0, n_runs, pk.ptr<int32_t>(i_olocal), c.nv,
-                               (double *)d_rho + s0 * (size_t)c.nv * S * 2);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-            launches++;
-        }
-        spans.end();
-        spans.begin(1);
-        a.Kc = c.nv;
-        a.vec = pk.ptr<int32_t>(i_order) + c.v0;
-        const int vblocks = (c.nv + ISF_THREADS - 1) / ISF_THREADS;
-        const int64_t range = (int64_t)omax - omin;
-        // origins per workgroup: a multiple of the tile, enough workgroups to fill the GPU several times over
-        int64_t opw = std::min<int64_t>(ISF_OPW, std::max<int64_t>(ISF_TILE, range * vblocks / 2048 / ISF_TILE * ISF_TILE));
-        opw = std::max<int64_t>(opw, ((range + 65534) / 65535 + ISF_TILE - 1) / ISF_TILE * ISF_TILE);
-        a.opw = (int32_t)opw;
-        const dim3 grid((unsigned)vblocks, (unsigned)((range + opw - 1) / opw));
-        AMOF_HIP_TRY(ctx, global ? isf_launch_corr<true>(ctx, a, grid, 0) : isf_launch_corr<false>(ctx, a, grid, lds));
-        launches++;
-        spans.end();
+    for (size_t f0 = 0; f0 < fsel.size(); f0 += bp.nb_max) {
+        const int nb = (int)std::min<size_t>(bp.nb_max, fsel.size() - f0);
+        AMOF_TRY(sq_rho_batch(c, f0, nb));
+        AMOF_HIP_TRY(ctx, with_flag(bp.global, [&](auto G) {
+            hipLaunchKernelGGL(sq_bin_kernel<G()>, dim3(sq_sample_blocks(nb, c.K)), dim3(SQ_THREADS), bp.lds, ctx->stream,
+                               (const double *)c.d_rho, nb, c.K, c.S, c.pk.ptr<int32_t>(c.i_hkl), c.pk.ptr<double>(c.i_recip),
+                               c.t->n_cells, c.pk.ptr<int32_t>(c.i_frames) + f0, c.dq, (int)nbins, c.pk.ptr<double>(i_scale), cnt, sm,
+                               bey);
+            return hipGetLastError();
+        }));
+        launches += 3;
     }
     timing_dom_end(ctx, launches);
-
-    if (want_self) {
-        // batches of entries inside the same budget: D (16 N bytes) and rho_d (16 K S bytes) per entry
-        const size_t ent_bytes = (size_t)std::max<int64_t>(N, 1) * sizeof(uint4) + (size_t)K * S * 2 * sizeof(double);
-        const size_t nb_max = std::max<size_t>(1, std::min<size_t>({budget / ent_bytes, entries.size(), (size_t)65535}));
-        void *d_D = nullptr, *d_rd = nullptr;
-        AMOF_TRY(ensure(ctx, SLOT_AUX2, nb_max * (size_t)std::max<int64_t>(N, 1) * sizeof(uint4), &d_D));
-        AMOF_TRY(ensure(ctx, SLOT_AUX3, nb_max * (size_t)K * S * 2 * sizeof(double), &d_rd));
-        const int n_runs = (int)pl.runs.size();
-        spans.begin(2);
-        for (size_t e0 = 0; e0 < entries.size(); e0 += nb_max) {
-            const int nb = (int)std::min<size_t>(nb_max, entries.size() - e0);
-            const IsfEntry *d_ent = pk.ptr<IsfEntry>(i_ent) + e0;
-            if (N > 0)
-                hipLaunchKernelGGL(isf_diff_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream,
-                                   (const uint4 *)d_Q, N, d_ent, (uint4 *)d_D);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(sq_rho_kernel, dim3((unsigned)((n_runs + SQ_THREADS - 1) / SQ_THREADS), (unsigned)nb), dim3(SQ_THREADS),
-                               0, ctx->stream, (const uint4 *)d_D, N, pk.ptr<int64_t>(i_spf), S, pk.ptr<SqRun>(i_runs), n_runs,
-                               pk.ptr<int32_t>(i_order), K, (double *)d_rd);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-            const int64_t samples = (int64_t)nb * K;
-            const unsigned blocks = (unsigned)std::min<int64_t>(SQ_BIN_BLOCKS, (samples + SQ_THREADS - 1) / SQ_THREADS);
-            hipLaunchKernelGGL(isf_self_bin_kernel, dim3(blocks), dim3(SQ_THREADS), 0, ctx->stream, (const double *)d_rd, nb, K, S, W,
-                               d_ent, pk.ptr<int32_t>(i_hkl), pk.ptr<double>(i_recip), t->n_cells, dq, (int)nbins,
-                               pk.ptr<double>(i_scale2), se);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-        }
-        spans.end();
-    }
-    int32_t flag = 0;
-    AMOF_TRY(fetch(ctx, &flag, d_flag, sizeof(int32_t)));
-    if (flag) {
-        timing_end(ctx);
-        return fail(ctx, AMOF_EINVAL, "positions lie more than 10^4 cells from the cell, or are not finite");
-    }
-    if (counts_dev) {
-        // (the fixed-point sums are int64: two's complement, the same addition)
-        AMOF_TRY(add_into(ctx, counts_dev, (const uint64_t *)cnt, n_cnt));
-        AMOF_TRY(add_into(ctx, (uint64_t *)coh_dev, (const uint64_t *)co, n_coh));
-        if (want_self) AMOF_TRY(add_into(ctx, (uint64_t *)self_dev, (const uint64_t *)se, n_self));
-        AMOF_TRY(add_into(ctx, beyond_dev, (const uint64_t *)bey, (size_t)W));
-    }
     timing_end(ctx);
-    if (counts) {
-        std::vector<int64_t> raw(n_coh + n_self);
-        AMOF_TRY(fetch(ctx, counts, cnt, n_cnt * sizeof(uint64_t)));
-        AMOF_TRY(fetch(ctx, raw.data(), co, raw.size() * sizeof(int64_t)));
-        AMOF_TRY(fetch(ctx, beyond, bey, (size_t)W * sizeof(uint64_t)));
-        for (int x = 0; x < S * S; x++)
-            for (size_t i = 0; i < n_cnt; i++) coh[(size_t)x * n_cnt + i] = ldexp((double)raw[(size_t)x * n_cnt + i], -sexp2[x]);
-        if (want_self)
-            for (int s = 0; s < S; s++)
-                for (size_t i = 0; i < n_cnt; i++)
-                    selfs[(size_t)s * n_cnt + i] = ldexp((double)raw[n_coh + (size_t)s * n_cnt + i], -sexp2[s * S + s]);
+    AMOF_TRY(sq_fetch_flag(c));
+    if (out.host()) {
+        std::vector<int64_t> raw((size_t)P * nbins);
+        AMOF_TRY(fetch(ctx, out.counts, cnt, (size_t)nbins * sizeof(uint64_t)));
+        AMOF_TRY(fetch(ctx, raw.data(), sm, raw.size() * sizeof(int64_t)));
+        AMOF_TRY(fetch(ctx, out.beyond, bey, sizeof(uint64_t)));
+        for (int p = 0; p < P; p++) sq_descale(raw.data() + (size_t)p * nbins, (size_t)nbins, c.sc.sexp[p], out.sums + (size_t)p * nbins);
     }
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    spans.collect();
-    (void)P;
     return AMOF_OK;
+}
+
+// ---- F(q, t) ----
+// The call keeps its own zeroed counters [counts | coh | self | beyond] in either form: the host form fetches them, the device
+// form adds them into the caller's at the end (so a call that fails leaves the caller's untouched).
+struct IsfCall : SqCall {
+    const int32_t *windows = nullptr;
+    int32_t W = 0;
+    int64_t stride = 1;
+    bool want_self = false;     // the self part is computed (selfs / self_dev given)
+    std::vector<LagRange> lagiv;        // this call's origin indices of every lag (the lag-major work list of amof_vanhove_distinct)
+    size_t n_cnt = 0, n_coh = 0, n_self = 0;
+    std::vector<double> scale2;
+    std::vector<int32_t> sexp2;
+    IsfFrames fr;
+    IsfChunks ch;
+    IsfPass pass;
+    std::vector<IsfEntry> entries;
+    int i_olocal = -1, i_slot = -1, i_scale2 = -1, i_win = -1, i_iv = -1, i_ent = -1;
+    unsigned long long *cnt = nullptr, *co = nullptr, *se = nullptr, *bey = nullptr;
+    StageSpans spans;           // rho table (with the quantisation), correlation, self
+    IsfCall(amof_ctx *ctx_, const amof_traj *t_, const double *recip_, const int32_t *hkl_, int32_t K_, double dq_, int32_t nbins_)
+        : SqCall(ctx_, t_, recip_, hkl_, K_, dq_, nbins_), spans(ctx_) {}
+};
+
+void isf_plan(IsfCall &c)
+{
+    isf_touched_frames(c.lagiv.data(), c.windows, c.W, c.F, c.stride, c.fr);
+    isf_cut_chunks(c.pl.runs, c.K, c.fr.fsel.size(), c.S, c.sw.isf_rho_budget, c.ch);
+    c.pass = isf_pass_plan(c.S, c.nbins, c.W, c.sw);
+    if (c.want_self) isf_self_entries(c.lagiv.data(), c.windows, c.W, c.stride, c.fr, c.entries);
+}
+
+int isf_stage(IsfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    UploadPack &pk = c.pk;
+    c.i_olocal = pk.add(c.ch.order_local.data(), c.ch.order_local.size() * sizeof(int32_t));
+    c.i_slot = pk.add(c.fr.slot_of.data(), c.fr.slot_of.size() * sizeof(int32_t));
+    c.i_scale2 = pk.add(c.scale2.data(), c.scale2.size() * sizeof(double));
+    c.i_win = pk.add(c.windows, (size_t)c.W * sizeof(int32_t));
+    c.i_iv = pk.add(c.lagiv.data(), c.lagiv.size() * sizeof(LagRange));
+    c.i_ent = pk.add(c.entries.data(), c.entries.size() * sizeof(IsfEntry));
+    const size_t slots = c.fr.fsel.size();
+    AMOF_TRY(sq_stage(c, c.fr.fsel.data(), slots, slots, (size_t)c.ch.kc_top * c.ch.vec_bytes));
+    const size_t n_ctr = c.n_cnt + c.n_coh + c.n_self + (size_t)c.W;
+    void *d_ctr = nullptr;
+    AMOF_TRY(ensure(ctx, SLOT_OUT1, n_ctr * sizeof(uint64_t), &d_ctr));
+    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_ctr, 0, n_ctr * sizeof(uint64_t), ctx->stream));
+    c.cnt = (unsigned long long *)d_ctr;
+    c.co = c.cnt + c.n_cnt;
+    c.se = c.co + c.n_coh;
+    c.bey = c.se + c.n_self;
+    return AMOF_OK;
+}
+
+// every touched frame is quantised once
+int isf_quantise(IsfCall &c)
+{
+    c.spans.begin(0);
+    AMOF_TRY(sq_launch_quantize(c, 0, c.fr.fsel.size(), c.d_Q));
+    c.spans.end();
+    return AMOF_OK;
+}
+
+// per chunk of vectors: its rho table for every touched frame, then the correlation over all lags
+int isf_coherent(IsfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const UploadPack &pk = c.pk;
+    IsfArgs a;
+    memset(&a, 0, sizeof a);
+    a.rho = c.d_rho;
+    a.slot_of = pk.ptr<int32_t>(c.i_slot);
+    a.hkl = pk.ptr<int32_t>(c.i_hkl);
+    a.recip = pk.ptr<double>(c.i_recip);
+    a.scale2 = pk.ptr<double>(c.i_scale2);
+    a.windows = pk.ptr<int32_t>(c.i_win);
+    a.lagiv = pk.ptr<int2>(c.i_iv);
+    a.counts = c.cnt;
+    a.coh = c.co;
+    a.beyond = c.bey;
+    a.n_cells = c.t->n_cells;
+    a.stride = c.stride;
+    a.S = c.S;
+    a.W = c.W;
+    a.nbins = c.nbins;
+    a.omin = c.fr.omin;
+    a.omax = c.fr.omax;
+    a.lags_per_pass = c.pass.lags_per_pass;
+    a.dq = c.dq;
+    timing_dom_begin(ctx, c.pass.path);
+    int64_t launches = 0;
+    for (const IsfChunk &k : c.ch.chunks) {
+        c.spans.begin(0);
+        AMOF_TRY(sq_launch_rho(c, c.d_Q, c.fr.fsel.size(), k.r0, k.r1 - k.r0, pk.ptr<int32_t>(c.i_olocal), k.nv, c.d_rho, &launches));
+        c.spans.end();
+        c.spans.begin(1);
+        const IsfGrid g = isf_grid(k.nv, (int64_t)c.fr.omax - c.fr.omin);
+        a.Kc = k.nv;
+        a.vec = pk.ptr<int32_t>(c.i_order) + k.v0;
+        a.opw = g.opw;
+        const dim3 grid((unsigned)g.vblocks, g.gy);
+        AMOF_HIP_TRY(ctx, c.pass.global ? isf_launch_corr<true>(ctx, a, grid, 0) : isf_launch_corr<false>(ctx, a, grid, c.pass.lds));
+        launches++;
+        c.spans.end();
+    }
+    timing_dom_end(ctx, launches);
+    return AMOF_OK;
+}
+
+// per batch of (lag, origin) entries: the displacements D, their rho, the bins of the origin frames
+int isf_self(IsfCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const UploadPack &pk = c.pk;
+    const size_t nb_max = isf_self_batch(c.sw.isf_rho_budget, c.N, c.K, c.S, c.entries.size());
+    void *d_D = nullptr, *d_rd = nullptr;
+    AMOF_TRY(ensure(ctx, SLOT_AUX2, nb_max * (size_t)std::max<int64_t>(c.N, 1) * sizeof(uint4), &d_D));
+    AMOF_TRY(ensure(ctx, SLOT_AUX3, nb_max * (size_t)c.K * c.S * 2 * sizeof(double), &d_rd));
+    c.spans.begin(2);
+    for (size_t e0 = 0; e0 < c.entries.size(); e0 += nb_max) {
+        const int nb = (int)std::min<size_t>(nb_max, c.entries.size() - e0);
+        const IsfEntry *d_ent = pk.ptr<IsfEntry>(c.i_ent) + e0;
+        if (c.N > 0)
+            hipLaunchKernelGGL(isf_diff_kernel, dim3((unsigned)((c.N + 255) / 256), (unsigned)nb), dim3(256), 0, ctx->stream,
+                               (const uint4 *)c.d_Q, c.N, d_ent, (uint4 *)d_D);
+        AMOF_HIP_TRY(ctx, hipGetLastError());
+        AMOF_TRY(sq_launch_rho(c, (const uint4 *)d_D, (size_t)nb, 0, (int)c.pl.runs.size(), pk.ptr<int32_t>(c.i_order), c.K, (double *)d_rd));
+        hipLaunchKernelGGL(isf_self_bin_kernel, dim3(sq_sample_blocks(nb, c.K)), dim3(SQ_THREADS), 0, ctx->stream, (const double *)d_rd,
+                           nb, c.K, c.S, c.W, d_ent, pk.ptr<int32_t>(c.i_hkl), pk.ptr<double>(c.i_recip), c.t->n_cells, c.dq,
+                           (int)c.nbins, pk.ptr<double>(c.i_scale2), c.se);
+        AMOF_HIP_TRY(ctx, hipGetLastError());
+    }
+    c.spans.end();
+    return AMOF_OK;
+}
+
+// the flag; device form: the call's counters into the caller's; host form: fetched and descaled
+int isf_finish(IsfCall &c, const SqOutputs &out)
+{
+    amof_ctx *ctx = c.ctx;
+    const size_t n_cnt = c.n_cnt, n_coh = c.n_coh, n_self = c.n_self;
+    AMOF_TRY(sq_fetch_flag(c, true));
+    if (!out.host()) {
+        // (the fixed-point sums are int64: two's complement, the same addition)
+        AMOF_TRY(add_into(ctx, out.counts_dev, (const uint64_t *)c.cnt, n_cnt));
+        AMOF_TRY(add_into(ctx, (uint64_t *)out.sums_dev, (const uint64_t *)c.co, n_coh));
+        if (c.want_self) AMOF_TRY(add_into(ctx, (uint64_t *)out.self_dev, (const uint64_t *)c.se, n_self));
+        AMOF_TRY(add_into(ctx, out.beyond_dev, (const uint64_t *)c.bey, (size_t)c.W));
+    }
+    timing_end(ctx);
+    if (out.host()) {
+        std::vector<int64_t> raw(n_coh + n_self);
+        AMOF_TRY(fetch(ctx, out.counts, c.cnt, n_cnt * sizeof(uint64_t)));
+        AMOF_TRY(fetch(ctx, raw.data(), c.co, raw.size() * sizeof(int64_t)));
+        AMOF_TRY(fetch(ctx, out.beyond, c.bey, (size_t)c.W * sizeof(uint64_t)));
+        for (int x = 0; x < c.S * c.S; x++) sq_descale(raw.data() + (size_t)x * n_cnt, n_cnt, c.sexp2[x], out.sums + (size_t)x * n_cnt);
+        if (c.want_self)
+            for (int s = 0; s < c.S; s++)
+                sq_descale(raw.data() + n_coh + (size_t)s * n_cnt, n_cnt, c.sexp2[s * c.S + s], out.selfs + (size_t)s * n_cnt);
+    }
+    AMOF_HIP_TRY(ctx, sync_stream(ctx));
+    c.spans.collect();
+    return AMOF_OK;
+}
+
+int isf_run(IsfCall &c, int64_t wb, int64_t we, const SqOutputs &out)
+{
+    amof_ctx *ctx = c.ctx;
+    const int32_t W = c.W;
+    AMOF_TRY(sq_check(c, true, [&] { return check_lag_args(ctx, c.windows, W, c.F, c.stride); }));
+    static_assert(sizeof(LagRange) == sizeof(int2), "the kernels read the table as int2");
+    c.lagiv.assign(std::max(W, 1), LagRange{0, 0});
+    const int64_t total = lag_work_ranges(c.windows, W, c.F, c.stride, wb, we, c.lagiv.data());
+    int64_t n_entries = 0;
+    for (int w = 0; w < W; w++) n_entries += c.lagiv[w].o1 - c.lagiv[w].o0;
+    if (wb < 0 || we > total || wb > we) return fail(ctx, AMOF_EINVAL, "work range [%lld, %lld) outside [0, %lld)", (long long)wb,
+                                                     (long long)we, (long long)total);
+    c.n_cnt = (size_t)W * c.nbins;
+    c.n_coh = (size_t)c.S * c.S * c.n_cnt;
+    c.n_self = c.want_self ? (size_t)c.S * c.n_cnt : 0;
+    AMOF_TRY(sq_check_histogram(c, c.n_coh));
+    AMOF_TRY(sq_call_scales(c, out.scale_log2));
+    sq_expand_pairs(c.S, c.sc, c.scale2, c.sexp2);
+    if (out.host()) {
+        std::fill(out.counts, out.counts + c.n_cnt, (uint64_t)0);
+        std::fill(out.sums, out.sums + c.n_coh, 0.0);
+        if (out.selfs) std::fill(out.selfs, out.selfs + c.n_self, 0.0);
+        std::fill(out.beyond, out.beyond + W, (uint64_t)0);
+    }
+    if (n_entries == 0 || c.K == 0) return AMOF_OK;
+
+    AMOF_TRY(build_geometry(ctx, c.t, c.hg));
+    AMOF_TRY(sq_call_plan(c));
+    isf_plan(c);
+    AMOF_TRY(isf_stage(c));
+    AMOF_TRY(isf_quantise(c));
+    AMOF_TRY(isf_coherent(c));
+    if (c.want_self) AMOF_TRY(isf_self(c));
+    return isf_finish(c, out);
 }
 
 }  // namespace
@@ -944,8 +840,12 @@ extern "C" int amof_sq_accumulate(amof_ctx *ctx, const amof_traj *t, const doubl
 {
     if (!ctx) return AMOF_EINVAL;
     if (!counts || !sums || !beyond) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    return sq_run(ctx, t, recip, hkl, K, frame_begin, frame_end, frame_stride, dq, nbins, counts, sums, beyond, nullptr, nullptr,
-                  nullptr, nullptr);
+    SqCall c(ctx, t, recip, hkl, K, dq, nbins);
+    SqOutputs out;
+    out.counts = counts;
+    out.sums = sums;
+    out.beyond = beyond;
+    return sq_run(c, frame_begin, frame_end, frame_stride, out);
 }
 
 extern "C" int amof_sq_accumulate_dev(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K,
@@ -954,55 +854,38 @@ extern "C" int amof_sq_accumulate_dev(amof_ctx *ctx, const amof_traj *t, const d
 {
     if (!ctx) return AMOF_EINVAL;
     if (!counts_dev || !sums_dev || !beyond_dev || !scale_log2) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    return sq_run(ctx, t, recip, hkl, K, frame_begin, frame_end, frame_stride, dq, nbins, nullptr, nullptr, nullptr, counts_dev,
-                  sums_dev, beyond_dev, scale_log2);
+    SqCall c(ctx, t, recip, hkl, K, dq, nbins);
+    SqOutputs out;
+    out.counts_dev = counts_dev;
+    out.sums_dev = sums_dev;
+    out.beyond_dev = beyond_dev;
+    out.scale_log2 = scale_log2;
+    return sq_run(c, frame_begin, frame_end, frame_stride, out);
 }
 
 extern "C" int amof_sq_modes(amof_ctx *ctx, const amof_traj *t, int64_t frame, const int32_t *hkl, int32_t K, double *rho)
 {
     if (!ctx) return AMOF_EINVAL;
-    AMOF_TRY(sq_check_traj(ctx, t, hkl, K));
+    SqCall c(ctx, t, nullptr, hkl, K, 0.0, 0);
+    AMOF_TRY(sq_check_traj(c));
     if (!rho && K > 0) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (frame < 0 || frame >= t->n_frames) return fail(ctx, AMOF_EINVAL, "frame out of range");
-    const int S = t->n_species;
-    const int64_t N = t->n_atoms;
+    if (frame < 0 || frame >= c.F) return fail(ctx, AMOF_EINVAL, "frame out of range");
     if (K == 0) return AMOF_OK;
-    SqPlan pl;
-    AMOF_TRY(sq_plan(ctx, t, hkl, K, pl));
-    if (N == 0) {
-        std::fill(rho, rho + (size_t)K * S * 2, 0.0);
+    AMOF_TRY(sq_call_plan(c));
+    const size_t rho_bytes = (size_t)K * c.S * 2 * sizeof(double);
+    if (c.N == 0) {
+        std::fill(rho, rho + (size_t)K * c.S * 2, 0.0);
         return AMOF_OK;
     }
-    HostGeom hg;
-    AMOF_TRY(build_geometry(ctx, t, hg));
+    AMOF_TRY(build_geometry(ctx, t, c.hg));
     const int32_t fr = (int32_t)frame;
-    AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    timing_begin(ctx);
-    const double *pos_dev = nullptr;
-    AMOF_TRY(stage_positions(ctx, t, &pos_dev));
-    UploadPack pk;
-    const int i_geom = pk.add(hg.rec.data(), hg.rec.size() * sizeof(double));
-    const int i_perm = pk.add(pl.perm.data(), pl.perm.size() * sizeof(int32_t));
-    const int i_spf = pk.add(pl.sp_first.data(), pl.sp_first.size() * sizeof(int64_t));
-    const int i_runs = pk.add(pl.runs.data(), pl.runs.size() * sizeof(SqRun));
-    const int i_order = pk.add(pl.order.data(), pl.order.size() * sizeof(int32_t));
-    const int i_frames = pk.add(&fr, sizeof(int32_t));
-    AMOF_TRY(upload_pack(ctx, SLOT_GEOM, pk));
-    void *d_Q = nullptr, *d_rho = nullptr, *d_flag = nullptr;
-    AMOF_TRY(ensure(ctx, SLOT_AUX0, (size_t)N * sizeof(uint4), &d_Q));
-    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)K * S * 2 * sizeof(double), &d_rho));
-    AMOF_TRY(ensure(ctx, SLOT_FLAGS, sizeof(int32_t), &d_flag));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flag, 0, sizeof(int32_t), ctx->stream));
+    AMOF_TRY(sq_stage(c, &fr, 1, 1, rho_bytes));
     timing_dom_begin(ctx, "sq_modes");
-    AMOF_TRY(sq_rho_batch(ctx, t, pos_dev, pk.ptr<double>(i_geom), pk.ptr<int32_t>(i_perm), pk.ptr<int64_t>(i_spf),
-                          pk.ptr<SqRun>(i_runs), (int)pl.runs.size(), pk.ptr<int32_t>(i_order), K, pk.ptr<int32_t>(i_frames), 1,
-                          (uint4 *)d_Q, (int32_t *)d_flag, (double *)d_rho));
+    AMOF_TRY(sq_rho_batch(c, 0, 1));
     timing_dom_end(ctx, 2);
     timing_end(ctx);
-    int32_t flag = 0;
-    AMOF_TRY(fetch(ctx, &flag, d_flag, sizeof(int32_t)));
-    if (flag) return fail(ctx, AMOF_EINVAL, "positions lie more than 10^4 cells from the cell, or are not finite");
-    AMOF_TRY(fetch(ctx, rho, d_rho, (size_t)K * S * 2 * sizeof(double)));
+    AMOF_TRY(sq_fetch_flag(c));
+    AMOF_TRY(fetch(ctx, rho, c.d_rho, rho_bytes));
     AMOF_HIP_TRY(ctx, sync_stream(ctx));
     return AMOF_OK;
 }
@@ -1014,8 +897,17 @@ extern "C" int amof_isf_accumulate(amof_ctx *ctx, const amof_traj *t, const doub
 {
     if (!ctx) return AMOF_EINVAL;
     if (!counts || !coh || !beyond) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    return isf_run(ctx, t, recip, hkl, K, windows, n_windows, origin_stride, work_begin, work_end, dq, nbins, self_sums != nullptr,
-                   counts, coh, self_sums, beyond, nullptr, nullptr, nullptr, nullptr, nullptr);
+    IsfCall c(ctx, t, recip, hkl, K, dq, nbins);
+    c.windows = windows;
+    c.W = n_windows;
+    c.stride = origin_stride;
+    c.want_self = self_sums != nullptr;
+    SqOutputs out;
+    out.counts = counts;
+    out.sums = coh;
+    out.selfs = self_sums;
+    out.beyond = beyond;
+    return isf_run(c, work_begin, work_end, out);
 }
 
 extern "C" int amof_isf_accumulate_dev(amof_ctx *ctx, const amof_traj *t, const double *recip, const int32_t *hkl, int32_t K,
@@ -1025,6 +917,17 @@ extern "C" int amof_isf_accumulate_dev(amof_ctx *ctx, const amof_traj *t, const 
 {
     if (!ctx) return AMOF_EINVAL;
     if (!counts_dev || !coh_dev || !beyond_dev || !scale_log2) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    return isf_run(ctx, t, recip, hkl, K, windows, n_windows, origin_stride, work_begin, work_end, dq, nbins, self_dev != nullptr,
-                   nullptr, nullptr, nullptr, nullptr, counts_dev, coh_dev, self_dev, beyond_dev, scale_log2);
+    IsfCall c(ctx, t, recip, hkl, K, dq, nbins);
+    c.windows = windows;
+    c.W = n_windows;
+    c.stride = origin_stride;
+    c.want_self = self_dev != nullptr;
+    SqOutputs out;
+    out.counts_dev = counts_dev;
+    out.sums_dev = coh_dev;
+    out.self_dev = self_dev;
+    out.beyond_dev = beyond_dev;
+    out.scale_log2 = scale_log2;
+    return isf_run(c, work_begin, work_end, out);
 }
+
