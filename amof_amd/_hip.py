@@ -40,6 +40,7 @@ EXPORTS = [
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
     "amof_bond_order", "amof_bond_order_dev", "amof_pore_field", "amof_pore_candidate_bound",
     "amof_pore_access", "amof_pore_access_field", "amof_pore_psd", "amof_pore_psd_field", "amof_pore_cover_stats",
+    "amof_pore_surface", "amof_pore_surface_bound", "amof_pore_surface_stats",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
@@ -157,6 +158,10 @@ def load_library():
         lib.amof_pore_psd_field.argtypes = [P, P, P, ctypes.c_int64, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32,
                                             ctypes.c_int32, P, P, P, P]
         lib.amof_pore_cover_stats.argtypes = [P, P]
+        lib.amof_pore_surface.argtypes = lib.amof_pore_psd.argtypes + [ctypes.c_int32, P, ctypes.c_int32, P, P, P]
+        lib.amof_pore_surface_bound.argtypes = [P, ctypes.c_double]
+        lib.amof_pore_surface_bound.restype = ctypes.c_double
+        lib.amof_pore_surface_stats.argtypes = [P, P]
         lib.amof_pore_candidate_bound.restype = ctypes.c_double
         lib.amof_sq_accumulate.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                            ctypes.c_double, ctypes.c_int32, P, P, P]
@@ -184,6 +189,13 @@ def load_library():
             raise RuntimeError("libamofhip.so ABI version %d, expected %d" % (lib.amof_abi_version(), ABI_VERSION))
         _lib = lib
         return lib
+
+
+def pore_surface_bound(cell, reach):
+    """``amof_pore_surface_bound``: the bound (Angstrom) of the float32 compare of the "pore_surface_list" path for one cell
+    ``[3][3]`` and ``reach = the largest radius + the largest probe radius``"""
+    cell = np.ascontiguousarray(cell, dtype=np.float64).reshape(9)
+    return float(load_library().amof_pore_surface_bound(_ptr(cell), float(reach)))
 
 
 def isf_layout(S, W, nbins, self_part=True):
@@ -415,24 +427,27 @@ def _label_cap(labels, n_t, G):
 
 
 # the arrays of the Pore calls in the order of the tuples ``pore_field`` / ``pore_access`` / ``pore_psd`` return: name, the flag that
-# asks for it (None: always), its shape behind [F] (b: nbins + 2, t: n_t, g: the grid, C-contiguous [G] to the library), dtype
+# asks for it (None: always), its shape behind [F] (b: nbins + 2, t: n_t, g: the grid, C-contiguous [G] to the library, s: species,
+# n: atoms, m: directions), dtype
 _PORE = (("hist", None, "b", np.uint64), ("counts", None, "t", np.int64), ("vmax", None, "", np.float64), ("argmax", None, "", np.int64),
          ("access", "labelled", "t4", np.int64), ("free_sphere", "free_sphere", "2", np.float64), ("field", "per_point", "g", np.float64),
          ("labels", "labels", "tg", np.int32), ("psd_hist", "psd", "b", np.uint64), ("po_counts", "psd", "t", np.int64),
-         ("po_access", "po_access", "t", np.int64), ("cover", "cover", "g", np.float64))
+         ("po_access", "po_access", "t", np.int64), ("cover", "cover", "g", np.float64), ("exposed", "surface", "ts", np.int64),
+         ("exposed_access", "exposed_access", "ts", np.int64), ("samples", "samples", "tnm", np.uint8))
 PoreResult = collections.namedtuple("PoreResult", [x[0] for x in _PORE], defaults=(None,) * len(_PORE))
 
 
-def pore_names(per_point=False, labelled=False, free_sphere=False, labels=False, psd=False, accessibility=False):
-    """which arrays a call with these flags returns, in the tuple's order (``labelled``: ``pore_access``, or ``pore_psd`` with
-    ``accessibility`` or ``free_sphere``)"""
-    flags = dict(locals(), po_access=psd and accessibility, cover=psd and per_point)
+def pore_names(per_point=False, labelled=False, free_sphere=False, labels=False, psd=False, accessibility=False, surface=False):
+    """which arrays a call with these flags returns, in the tuple's order (``labelled``: ``pore_access``, or ``pore_psd`` /
+    ``pore_surface`` with ``accessibility`` or ``free_sphere``; ``surface``: ``pore_surface``)"""
+    flags = dict(locals(), po_access=psd and accessibility, cover=psd and per_point, exposed_access=surface and accessibility,
+                 samples=surface and per_point)
     return tuple(name for name, flag, _, _ in _PORE if flag is None or flags[flag])
 
 
-def _pore_alloc(names, F, n_t, nbins, shape):
+def _pore_alloc(names, F, n_t, nbins, shape, S=0, N=0, M=0):
     """zeroed arrays of these names as a ``PoreResult``"""
-    dims = {"b": (nbins + 2,), "t": (n_t,), "4": (4,), "2": (2,), "g": tuple(shape)}
+    dims = {"b": (nbins + 2,), "t": (n_t,), "4": (4,), "2": (2,), "g": tuple(shape), "s": (S,), "n": (N,), "m": (M,)}
     return PoreResult(**{name: np.zeros((F,) + sum((dims[c] for c in dim), ()), dtype=kind) for name, _, dim, kind in _PORE if name in names})
 
 
@@ -839,9 +854,9 @@ class Context(Lane):
                        _ptr(hist), _ptr(hist_tet), _ptr(sums), _ptr(pa)))
         return (hist, hist_tet, sums, pa) if per_atom else (hist, hist_tet, sums)
 
-    def _pore_atoms(self, packed, radii, grid, dr, dmax, thresholds, frame_range, **flags):
-        """the three calls that take atoms -- ``amof_pore_field``, ``amof_pore_access`` (``labelled``), ``amof_pore_psd``
-        (``psd``) -- as a ``PoreResult``; ``flags``: ``pore_names``'"""
+    def _pore_atoms(self, packed, radii, grid, dr, dmax, thresholds, frame_range, dirs=None, **flags):
+        """the four calls that take atoms -- ``amof_pore_field``, ``amof_pore_access`` (``labelled``), ``amof_pore_psd``
+        (``psd``), ``amof_pore_surface`` (``surface``, with ``dirs [M][3]``) -- as a ``PoreResult``; ``flags``: ``pore_names``'"""
         th = self._traj(packed, frame_range)
         radii = np.ascontiguousarray(radii, dtype=np.float64).reshape(th.S)
         grid = _i32(grid).reshape(3)
@@ -854,11 +869,25 @@ class Context(Lane):
             raise ValueError("dmax / dr rounds to no bin, or a grid that is not 1 .. 2^31 - 1 points")
         shape = tuple(int(x) for x in grid)
         _label_cap(flags.get("labels"), len(thr), shape[0] * shape[1] * shape[2])
-        r = _pore_alloc(pore_names(**flags), th.n_frames, len(thr), nbins, shape)
+        M = 0
+        if flags.get("surface"):
+            dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+            if dirs.ndim != 2 or dirs.shape[1] != 3:
+                raise ValueError("dirs must be [M][3]")
+            M = dirs.shape[0]
+            if flags.get("per_point") and len(thr) * int(th.n_atoms) * M > 2 ** 32:
+                raise AmofError(AMOF_ECAPACITY, "samples of %d thresholds x %d atoms x %d directions exceed the 4 GiB a frame may take"
+                                % (len(thr), int(th.n_atoms), M))
+        r = _pore_alloc(pore_names(**flags), th.n_frames, len(thr), nbins, shape, th.S, int(th.n_atoms), M)
         head = (self._h, ctypes.byref(th.c), _ptr(radii), _ptr(grid), dr, dmax, _ptr(thr), len(thr))
         rows = (_ptr(r.hist), _ptr(r.counts), _ptr(r.vmax), _ptr(r.argmax))
         more = (_ptr(r.access), _ptr(r.free_sphere), _ptr(r.field), _ptr(r.labels))
-        if flags.get("psd"):
+        if flags.get("surface"):
+            rc = self._lib.amof_pore_surface(*head, int(bool(flags.get("accessibility"))), int(bool(flags.get("free_sphere"))), *rows, *more,
+                                             _ptr(r.psd_hist), _ptr(r.po_counts), _ptr(r.po_access), _ptr(r.cover),
+                                             int(bool(flags.get("psd"))), _ptr(dirs), M, _ptr(r.exposed), _ptr(r.exposed_access),
+                                             _ptr(r.samples))
+        elif flags.get("psd"):
             rc = self._lib.amof_pore_psd(*head, int(bool(flags.get("accessibility"))), int(bool(flags.get("free_sphere"))), *rows, *more,
                                          _ptr(r.psd_hist), _ptr(r.po_counts), _ptr(r.po_access), _ptr(r.cover))
         elif flags.get("labelled"):
@@ -951,6 +980,31 @@ class Context(Lane):
                                                   int(bool(accessibility)), _ptr(r.psd_hist), _ptr(r.po_counts), _ptr(r.po_access), _ptr(r.cover)))
         return r.psd_hist, r.po_counts, r.po_access, r.cover
 
+    @_locked
+    def pore_surface(self, packed, radii, grid, dr, dmax, thresholds=(), dirs=None, frame_range=None, per_point=False,
+                     accessibility=False, free_sphere=False, labels=False, psd=False):
+        """``amof_pore_surface``: the results of ``pore_field`` -- of ``pore_access`` with ``accessibility`` or ``free_sphere``, of
+        ``pore_psd`` with ``psd`` -- with the same optional outputs in the same order, the same bits, followed by ``exposed int64
+        [F][n_t][S]`` (per species, the samples ``r_j + (R_j + rp) dirs[m]`` that lie in no other atom's sphere of radius
+        ``R_k + rp``), with ``accessibility`` ``exposed_access int64 [F][n_t][S]`` (of those, the samples with one of their 8
+        surrounding grid points in a channel of the void ``v >= rp``) and with ``per_point`` ``samples uint8 [F][n_t][N][M]`` (0
+        buried, 1 exposed, 2 exposed and accessible).  ``dirs [M][3]``: unit vectors (``amof_amd.pore.sphere_points``);
+        ``thresholds``: probe radii >= 0.  include/amof_hip.h has the definitions."""
+        labelled = bool(accessibility or free_sphere)
+        r = self._pore_atoms(packed, radii, grid, dr, dmax, thresholds, frame_range, dirs=dirs, per_point=bool(per_point),
+                             labelled=labelled, free_sphere=bool(free_sphere), labels=bool(labels) and labelled, psd=bool(psd),
+                             accessibility=bool(accessibility), surface=True)
+        return tuple(x for x in r if x is not None)
+
+    def pore_surface_stats(self):
+        """``{"atoms", "records", "samples", "redecisions", "early_exits"}`` summed over the launches of the last ``pore_surface``
+        that stayed on the "pore_surface_list" path (``amof_pore_surface_stats``)"""
+        self.drain()
+        out = np.zeros(5, dtype=np.float64)
+        with self._lock:
+            self._check(self._lib.amof_pore_surface_stats(self._h, _ptr(out)))
+        return dict(zip(("atoms", "records", "samples", "redecisions", "early_exits"), out.tolist()))
+
     def pore_cover_stats(self):
         """``{"bricks", "source_bricks", "records"}`` summed over the full passes of the last ``pore_psd`` / ``pore_psd_field`` on
         the "pore_cover_brick" path (``amof_pore_cover_stats``): divide by ``bricks`` for the means per destination brick"""
@@ -1024,14 +1078,17 @@ class Context(Lane):
         self._check(self._lib.amof_isf_accumulate(*args, _ptr(counts), _ptr(coh), _ptr(selfs), _ptr(beyond)))
         return counts, coh, selfs, beyond, th.kinds
 
-    def last_stage_seconds(self):
+    def last_stage_seconds(self, pore=False):
         """``{"rho", "corr", "self"}``: kernel seconds of the stages of the last ``isf_accumulate`` (amof_last_kernel_seconds
         2 .. 4; negative: the last call was not one).  After ``bond_survival`` the same three slots hold the bond lists, the
         bit series and the correlations; after ``bond_reorientation`` the bond lists, the bit series, and the vector table
-        with the reorientation sums; after ``bond_order`` the list stage and the order kernels (the third is 0)."""
+        with the reorientation sums; after ``bond_order`` the list stage and the order kernels (the third is 0).  After the Pore
+        calls the three slots hold the cell sort, the field kernels and the labelling; ``pore=True`` adds ``"cover"``, the covering
+        stage, and ``"surface"``, the surface stage (amof_last_kernel_seconds 5 and 6)."""
         self.drain()
+        names = ("rho", "corr", "self") + (("cover", "surface") if pore else ())
         with self._lock:
-            return {name: self._lib.amof_last_kernel_seconds(self._h, 2 + i) for i, name in enumerate(("rho", "corr", "self"))}
+            return {name: self._lib.amof_last_kernel_seconds(self._h, 2 + i) for i, name in enumerate(names)}
 
     @_locked
     def sq_modes(self, packed, hkl, frame=0):
@@ -1216,6 +1273,15 @@ class MultiContext(object):
         return self._sharded("pore_psd", packed, _span(frame_range, packed.n_frames), "frame_range", ("cat",) * n, radii, grid, dr,
                              dmax, thresholds, copy_frames=True, per_point=per_point, accessibility=accessibility,
                              free_sphere=free_sphere, labels=labels)
+
+    def pore_surface(self, packed, radii, grid, dr, dmax, thresholds=(), dirs=None, frame_range=None, per_point=False,
+                     accessibility=False, free_sphere=False, labels=False, psd=False):
+        """frames sharded over the devices as ``pore_psd``'s: every output is per frame, the rows concatenate"""
+        labelled = bool(accessibility or free_sphere)
+        n = len(pore_names(bool(per_point), labelled, bool(free_sphere), bool(labels) and labelled, bool(psd), bool(accessibility), True))
+        return self._sharded("pore_surface", packed, _span(frame_range, packed.n_frames), "frame_range", ("cat",) * n, radii, grid, dr,
+                             dmax, thresholds, copy_frames=True, dirs=dirs, per_point=per_point, accessibility=accessibility,
+                             free_sphere=free_sphere, labels=labels, psd=psd)
 
     def pore_psd_field(self, field, cells, pbc, dr, dmax, thresholds=(), accessibility=False, per_point=False):
         return self.ctxs[0].pore_psd_field(field, cells, pbc, dr, dmax, thresholds, accessibility=accessibility, per_point=per_point)

@@ -52,6 +52,12 @@ enum Slot {
     SLOT_OUT0,
     SLOT_OUT1,
     SLOT_FLAGS,
+    SLOT_SURF0,     // the surface stage (pore_surface.hip): cell-sorted records
+    SLOT_SURF1,     // its cell offsets
+    SLOT_SURF2,     // its keys
+    SLOT_SURF3,     // its cursors
+    SLOT_SURF4,     // directions, counters, flags
+    SLOT_SURF5,     // per-sample bytes of one (frame, threshold)
     SLOT_COUNT
 };
 
@@ -85,11 +91,15 @@ struct amof_ctx {
     int64_t shard_ticket = 0;     // `calls` right after a begin; 0 = none pending
     int64_t shard_key[7] = {0, 0, 0, 0, 0, 0, 0};
     // kernel seconds of the stages of the last amof_isf_accumulate[_dev]: rho table (with the quantisation), correlation, self;
-    // of the last amof_bond_survival[_dev]: lists, series, correlations (StageSpans); the fourth: amof_pore_psd's covering stage
-    double stage_seconds[4] = {-1.0, -1.0, -1.0, -1.0};
+    // of the last amof_bond_survival[_dev]: lists, series, correlations (StageSpans); the fourth: amof_pore_psd's covering stage;
+    // the fifth: amof_pore_surface's surface stage
+    double stage_seconds[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};
     // of the last amof_pore_psd[_field], over the full passes on "pore_cover_brick": destination bricks, the source bricks they
     // kept, the centre records they swept (amof_pore_cover_stats)
     double cover_stats[3] = {0.0, 0.0, 0.0};
+    // of the last amof_pore_surface, over its launches on "pore_surface_list": atoms swept, neighbour records kept, samples,
+    // float64 re-decisions, samples ended by the early exit (amof_pore_surface_stats)
+    double surface_stats[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
 };
 
 namespace amof {
@@ -377,7 +387,7 @@ void timing_end(amof_ctx *ctx);
 void timing_dom_begin(amof_ctx *ctx, const char *path);
 void timing_dom_end(amof_ctx *ctx, int64_t launches);
 
-// Event pairs around the stages of a call, for amof_last_kernel_seconds 2 .. 5 (ctx->stage_seconds).  A stage may be
+// Event pairs around the stages of a call, for amof_last_kernel_seconds 2 .. 6 (ctx->stage_seconds).  A stage may be
 // begun many times; end() closes the span begun last.  An event that cannot be created leaves its span out, silently.
 struct StageSpans {
     struct Span {
@@ -418,8 +428,8 @@ struct StageSpans {
 };
 
 // ------------------------------------------------------------------ Pore --
-// The host scaffolding of amof_pore_field, amof_pore_access[_field] and amof_pore_psd[_field] (pore.hip, pore_access.hip,
-// pore_cover.hip).  Every entry point reads: check (pore_check.h), fill PoreOutputs, pick stages, run one field source, finish.
+// The host scaffolding of amof_pore_field, amof_pore_access[_field], amof_pore_psd[_field] and amof_pore_surface (pore.hip,
+// pore_access.hip, pore_cover.hip, pore_surface.hip).  Every entry point reads: check (pore_check.h), fill PoreOutputs, pick stages, run one field source, finish.
 inline int pore_refuse(amof_ctx *ctx, const pore_check::Verdict &v) { return v.code == AMOF_OK ? AMOF_OK : fail(ctx, v.code, "%s", v.text); }
 
 // The caller's arrays as the entry point got them; one it did not ask for is nulled.  F, G, n_t and nbins stay 0 until the checks of
@@ -437,7 +447,10 @@ struct PoreOutputs {
     uint64_t *psd_hist = nullptr;       // [F][nbins + 2]
     int64_t *po_counts = nullptr, *po_access = nullptr;     // [F][n_t]
     double *cover = nullptr;            // [F][G]
+    int64_t *exposed = nullptr, *exposed_access = nullptr;  // [F][n_t][S]
+    uint8_t *samples = nullptr;         // [F][n_t][N][M]
     int64_t F = 0, G = 0;
+    int64_t S = 0, NM = 0;              // species, atoms x directions (amof_pore_surface alone sets them)
     int32_t nbins = 0, n_t = 0;
     bool kept = false;
     void sized(int64_t frames, const int32_t *grid, int32_t thresholds) { F = frames; G = (int64_t)grid[0] * grid[1] * grid[2]; n_t = thresholds; }
@@ -449,6 +462,7 @@ struct PoreOutputs {
         clear(hist, f * row), clear(counts, f * t), clear(vmax, f), clear(argmax, f), clear(field, f * g);
         clear(access, f * t * 4), clear(free_sphere, f * 2), clear(labels, f * t * g);
         clear(psd_hist, f * row), clear(po_counts, f * t), clear(po_access, f * t), clear(cover, f * g);
+        clear(exposed, f * t * (size_t)S), clear(exposed_access, f * t * (size_t)S), clear(samples, per_point ? f * t * (size_t)NM : 0);
     }
     int keep(int rc) { kept = rc == AMOF_OK; return rc; }
     ~PoreOutputs() { if (!kept) zero(true); }       // (a return without keep() while F == 0 zeroes nothing)
@@ -468,12 +482,28 @@ struct PoreInputs {
 };
 
 // What runs on every frame's field while it lies in device memory: the labelling (pore_access.hip) and the covering radius
-// (pore_cover.hip), each optional; both states belong to their files
+// (pore_cover.hip), each optional; both states belong to their files.  The surface stage (pore_surface.hip,
+// DESIGN.md 4.3e.3) reads no field: it runs where the frame's channel marks are at hand, per (frame, threshold).
 struct Labeller;
 struct CoverCall;
+struct SurfaceCall;
+// the device arrays of the call that the stages do not see otherwise: positions [F][N][3], geometry records, radii [S], species [N]
+struct PoreAtoms {
+    const double *pos, *geom, *radii;
+    const int32_t *species;
+    const HostGeom *host;
+    double rmax, hmin;
+};
+size_t pore_surface_fixed_bytes(const SurfaceCall &s);
+int pore_surface_setup(SurfaceCall &s, const PoreAtoms &atoms);
+void pore_surface_restart(SurfaceCall &s);
+// threshold k of frame f; parent / mark (or null): the periodic labels and the channel marks of V(thresholds[k]), channels:
+// whether there is one
+int pore_surface_threshold(SurfaceCall &s, int64_t f, int32_t k, const int32_t *parent, const int32_t *mark, bool channels, StageSpans &spans);
+void pore_surface_report(const SurfaceCall &s);
 size_t pore_label_fixed_bytes(const Labeller &lb);
 int pore_label_setup(Labeller &lb);
-int pore_label_frame(Labeller &lb, int64_t f, const double *d_field, CoverCall *cover, StageSpans &spans);
+int pore_label_frame(Labeller &lb, int64_t f, const double *d_field, CoverCall *cover, SurfaceCall *surface, StageSpans &spans);
 void pore_label_report(const Labeller &lb);
 size_t pore_cover_fixed_bytes(const CoverCall &c);
 int pore_cover_setup(CoverCall &c);
@@ -486,21 +516,29 @@ struct PoreStages {
     Labeller *label = nullptr;
     CoverCall *cover = nullptr;
     bool cover_access = false;      // after every labelled threshold: the covering pass from that threshold's channels
-    size_t fixed_bytes() const { return (label ? pore_label_fixed_bytes(*label) : 0) + (cover ? pore_cover_fixed_bytes(*cover) : 0); }
-    int setup()
+    SurfaceCall *surface = nullptr;
+    int32_t n_t = 0;                // thresholds of the call (the surface stage without a labeller walks them itself)
+    size_t fixed_bytes() const
+    {
+        return (label ? pore_label_fixed_bytes(*label) : 0) + (cover ? pore_cover_fixed_bytes(*cover) : 0) + (surface ? pore_surface_fixed_bytes(*surface) : 0);
+    }
+    int setup(const PoreAtoms *atoms = nullptr)
     {
         if (label) AMOF_TRY(pore_label_setup(*label));
-        return cover ? pore_cover_setup(*cover) : AMOF_OK;
+        if (cover) AMOF_TRY(pore_cover_setup(*cover));
+        return surface && atoms ? pore_surface_setup(*surface, *atoms) : AMOF_OK;
     }
     // pore_brick gave up after its batches ran and pore_exact hands every frame over again: the covering stage's counters
     // (launches, reported path, amof_pore_cover_stats) start over, the labeller's count of labellings goes on
-    void restart() { if (cover) pore_cover_restart(*cover); }
+    void restart() { if (cover) pore_cover_restart(*cover); if (surface) pore_surface_restart(*surface); }
     int frame(int64_t f, const double *d_field, StageSpans &spans)
     {
         if (cover) AMOF_TRY(pore_cover_frame(*cover, f, d_field, spans));
-        return label ? pore_label_frame(*label, f, d_field, cover_access ? cover : nullptr, spans) : AMOF_OK;
+        if (label) return pore_label_frame(*label, f, d_field, cover_access ? cover : nullptr, surface, spans);
+        for (int32_t k = 0; surface && k < n_t; k++) AMOF_TRY(pore_surface_threshold(*surface, f, k, nullptr, nullptr, false, spans));
+        return AMOF_OK;
     }
-    void report() const { if (label) pore_label_report(*label); if (cover) pore_cover_report(*cover); }
+    void report() const { if (label) pore_label_report(*label); if (cover) pore_cover_report(*cover); if (surface) pore_surface_report(*surface); }
 };
 
 // the field from atoms: amof_pore_field's tiers and batches, the stages behind every batch (pore.hip)
@@ -508,7 +546,9 @@ int pore_field_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, PoreSt
 // the field the caller supplies: frame by frame into device memory and through the stages; path: what the call reports meanwhile
 int pore_given_field_run(amof_ctx *ctx, const PoreInputs &in, const PoreOutputs &out, PoreStages &stages, const char *path);
 // the labelling stage on either source, beside a covering stage (amof_pore_psd[_field]) or without (cover null)
-int pore_access_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, CoverCall *cover);
+int pore_access_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, CoverCall *cover, SurfaceCall *surface = nullptr);
+// amof_pore_psd's stages behind the atoms' field -- the covering stage only with want_psd -- and the surface stage (pore_cover.hip)
+int pore_psd_surface_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, bool want_psd, SurfaceCall &surface);
 
 // ---------------------------------------------------------------- LDS-DMA --
 typedef __attribute__((address_space(1))) const void *gptr_t;

@@ -532,7 +532,7 @@ int amof_ctx_synchronize(amof_ctx *ctx)
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which)
 {
     if (!ctx || !ctx->ev_valid) return -1.0;
-    if (which >= 2 && which <= 5) return ctx->stage_seconds[which - 2];
+    if (which >= 2 && which <= 6) return ctx->stage_seconds[which - 2];
     float ms = 0.f;
     hipEvent_t a = which == 1 ? ctx->ev_dom0 : ctx->ev_all0;
     hipEvent_t b = which == 1 ? ctx->ev_dom1 : ctx->ev_all1;

@@ -594,7 +594,8 @@ int amof::pore_field_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, 
     c.d_vmax = (double *)((unsigned char *)c.d_out + hist_bytes + cnt_bytes);
     c.d_argmax = (long long *)(c.d_vmax + F);
     a.flags = (int32_t *)d_flags;
-    if (stages) AMOF_TRY(stages->setup());
+    const PoreAtoms atoms{a.pos, a.geom, a.radii, a.species, &c.geom, rmax, hmin};
+    if (stages) AMOF_TRY(stages->setup(&atoms));
 
     bool done = false;
     const char *ex = getenv("AMOF_PORE_EXACT");

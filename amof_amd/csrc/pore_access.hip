@@ -564,7 +564,8 @@ static int pa_free_sphere(Labeller &lb, const double *d_field, double dmax, doub
 
 // every threshold of frame f, whose field lies on the device, then its free sphere.  With a covering stage (want_access) every
 // threshold's channels are marked for its accessible pass: that is no labelling, the span of stage 2 is closed around it.
-int pore_label_frame(Labeller &lb, int64_t f, const double *d_field, CoverCall *cover, StageSpans &spans)
+// The surface stage (or null) runs at the same place, on the same marks.
+int pore_label_frame(Labeller &lb, int64_t f, const double *d_field, CoverCall *cover, SurfaceCall *surface, StageSpans &spans)
 {
     const size_t G = (size_t)lb.g.G;
     int64_t own[4];
@@ -574,11 +575,12 @@ int pore_label_frame(Labeller &lb, int64_t f, const double *d_field, CoverCall *
         AMOF_TRY(pa_open(lb, d_field, lb.in->thresholds[k]));
         AMOF_TRY(pa_periodic(lb, d_field, lb.arrays->access ? lb.arrays->access + row * 4 : own,
                              lb.arrays->labels ? lb.arrays->labels + row * G : nullptr, nullptr));
-        if (cover) {
+        if (cover || surface) {
             bool any = false;
             AMOF_TRY(pa_mark_channels(lb, any));
             spans.end();
-            AMOF_TRY(pore_cover_threshold(*cover, f, k, d_field, lb.parent, lb.size, any, spans));
+            if (cover) AMOF_TRY(pore_cover_threshold(*cover, f, k, d_field, lb.parent, lb.size, any, spans));
+            if (surface) AMOF_TRY(pore_surface_threshold(*surface, f, k, lb.parent, lb.size, any, spans));
             spans.begin(2);
         }
     }
@@ -604,12 +606,12 @@ static int pa_check(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out)
 
 using namespace amof;
 
-int amof::pore_access_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, CoverCall *cover)
+int amof::pore_access_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, CoverCall *cover, SurfaceCall *surface)
 {
     if (in.t) AMOF_TRY(pa_check(ctx, in, out));     // (the entry point of a supplied field has checked already)
     Labeller lb;
     pa_plan(lb, ctx, in, out);
-    PoreStages stages{&lb, cover, cover && in.want_access};
+    PoreStages stages{&lb, cover, cover && in.want_access, surface, in.n_t};
     return in.t ? pore_field_run(ctx, in, out, &stages) : pore_given_field_run(ctx, in, out, stages, pa_path(lb));
 }
 

@@ -1,5 +1,5 @@
-// The argument rules of the Pore family (amof_pore_field, amof_pore_access[_field], amof_pore_psd[_field]), each once, host-only
-// C++17 without HIP or amof_ctx (tests/native/pore_check_driver.cpp asks them directly).  A rule returns the AMOF_E* code and
+// The argument rules of the Pore family (amof_pore_field, amof_pore_access[_field], amof_pore_psd[_field], amof_pore_surface), each
+// once, host-only C++17 without HIP or amof_ctx (tests/native/pore_check_driver.cpp and pore_surface_driver.cpp ask them directly).  A rule returns the AMOF_E* code and
 // the message; the .hip files pass both on to fail() (pore_refuse, amof_internal.h) and decide none of this themselves.
 // The order of the checks per entry point (the first refusal wins; F = n_frames):
 //   amof_pore_field         validate_traj . both_given(radii, grid) . thresholds_given . field_outputs . grid . bin_width . radii . thresholds_finite .
@@ -11,6 +11,9 @@
 //                           psd_outputs . per_point_cap(cover) . po_access_given . then LABELLING (want_access or want_free) . amof_pore_field's
 //   amof_pore_psd_field     given_field_inputs(with cells) . COVERING . po_access_given . [F == 0: done] . per frame: singular
 //                           cell (pore_cover.hip has the step geometry), field_finite, half_height_field . want_access: grid(with pbc)
+//   amof_pore_surface       both_given(traj, grid) . SURFACE = direction_count . both_given(dirs, dirs) . directions . thresholds_given .
+//                           thresholds_finite . probes_not_negative . surface_outputs . samples_cap . then COVERING (want_psd) .
+//                           LABELLING (want_access or want_free) . amof_pore_field's . half_height_surface
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -128,6 +131,40 @@ inline Verdict labels_cap(int32_t n_t, int64_t G)
 {
     return refuse_if((size_t)n_t * (size_t)G * sizeof(int32_t) > ((size_t)1 << 32), AMOF_ECAPACITY,
                      "labels of %d thresholds x %lld points exceed the 4 GiB a frame may take", n_t, (long long)G);
+}
+// ---- the surface stage (amof_pore_surface): directions [M][3], 1 <= M <= 4096, unit vectors to 1e-12 in |u|^2; probe radii >= 0
+inline Verdict direction_count(int32_t n_dirs) { return refuse_if(n_dirs < 1 || n_dirs > 4096, AMOF_EINVAL, "n_dirs = %d: 1 .. 4096 directions", n_dirs); }
+inline Verdict directions(const double *dirs, int32_t n_dirs)
+{
+    for (int m = 0; m < n_dirs; m++) {
+        const double *u = dirs + 3 * (size_t)m;
+        const double q = (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+        if (!(fabs(q - 1.0) <= 1e-12)) return refuse_if(true, AMOF_EINVAL, "direction %d is no unit vector: |u|^2 - 1 = %g", m, q - 1.0);
+    }
+    return Verdict();
+}
+inline Verdict probes_not_negative(const double *thresholds, int32_t n_t)
+{
+    for (int k = 0; k < n_t; k++)
+        if (!(thresholds[k] >= 0.0)) return refuse_if(true, AMOF_EINVAL, "threshold %d = %g: the surface stage takes probe radii >= 0", k, thresholds[k]);
+    return Verdict();
+}
+inline Verdict surface_outputs(int64_t F, int32_t n_t, int32_t want_access, P exposed, P exposed_access)
+{
+    if (F > 0 && n_t > 0 && !exposed) return null_if(true);
+    return refuse_if(F > 0 && n_t > 0 && want_access && !exposed_access, AMOF_EINVAL, "want_access without an exposed_access array");
+}
+// the largest sample sphere: no other image of an atom may come closer to its own samples than the sphere's radius
+inline Verdict half_height_surface(double rmax, double tmax, double hmin)
+{
+    return refuse_if(above_half_height(rmax + tmax, hmin), AMOF_EINVAL, "the largest radius + the largest probe radius = %g exceeds half the "
+                                                                        "smallest cell height %g: a sample sphere would meet its own image",
+                     rmax + tmax, hmin);
+}
+inline Verdict samples_cap(int32_t n_t, int64_t n_atoms, int32_t n_dirs)
+{
+    return refuse_if((double)n_t * (double)n_atoms * (double)n_dirs > 4294967296.0, AMOF_ECAPACITY,
+                     "samples of %d thresholds x %lld atoms x %d directions exceed the 4 GiB a frame may take", n_t, (long long)n_atoms, n_dirs);
 }
 }  // namespace pore_check
 }  // namespace amof

@@ -680,6 +680,18 @@ extern "C" int amof_pore_psd(amof_ctx *ctx, const amof_traj *t, const double *ra
     return out.keep(labelled ? pore_access_run(ctx, in, out, &c) : pore_field_run(ctx, in, out, &stages));
 }
 
+int amof::pore_psd_surface_run(amof_ctx *ctx, const PoreInputs &in, PoreOutputs &out, bool want_psd, SurfaceCall &surface)
+{
+    const bool labelled = in.want_access || in.want_free;
+    CoverCall c;
+    if (want_psd) {
+        AMOF_TRY(pc_check(ctx, in, out));
+        pc_plan(c, ctx, in, out);
+    }
+    PoreStages stages{nullptr, want_psd ? &c : nullptr, false, &surface, in.n_t};
+    return labelled ? pore_access_run(ctx, in, out, want_psd ? &c : nullptr, &surface) : pore_field_run(ctx, in, out, &stages);
+}
+
 extern "C" int amof_pore_psd_field(amof_ctx *ctx, const double *field, const double *cells, int64_t n_frames, const int32_t *grid,
                                    const int32_t *pbc, double dr, double dmax, const double *thresholds, int32_t n_t, int32_t want_access,
                                    uint64_t *psd_hist, int64_t *po_counts, int64_t *po_access, double *cover)

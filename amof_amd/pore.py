@@ -33,7 +33,16 @@ fraction of points with w >= r is the cumulative pore volume V(r) of Gelb and Gu
 #{w >= rp} / G is the volume a probe of radius rp occupies -- the whole probe sphere, the quantity helium or nitrogen pore
 volumes are compared with; the probe-centre volume above understates it by a surface layer rp thick.  With
 ``accessibility`` the occupiable volume is split into the part covered from a channel (POAV) and the rest (PONAV).
-Not computed: surface areas.
+
+``surface=True`` adds the surface area by deterministic Shrake-Rupley sampling: every atom carries ``surface_points`` samples
+on its sphere of radius R_j + rp (``sphere_points``: a Fibonacci lattice, the same directions for every atom), a sample is
+exposed when it lies in no other atom's sphere of radius R_k + rp, and
+
+    SA(rp) = sum_s 4 pi (R_s + rp)^2 exposed_s / M          (rp = 0: the van der Waals surface)
+
+from the integers of ``amof_pore_surface`` (amof_amd/csrc/pore_surface.hip).  With ``accessibility`` an exposed sample is
+accessible when one of the 8 grid points around it lies in a channel of the void of that probe: ASA and NASA, a grid estimate
+that converges with the spacing.  Zeo++ samples the same spheres at random; these are not its numbers.
 """
 
 import logging
@@ -234,6 +243,59 @@ def psd_columns(psd_counts, po_counts, po_access, volume, mass, probes, grid, dr
     return cols, psd
 
 
+def sphere_points(M):
+    """``[M][3]`` unit vectors of the Fibonacci lattice: ``z_m = 1 - (2 m + 1) / M``, ``phi_m = m pi (3 - sqrt 5)``, ``u = (sqrt(1 -
+    z^2) cos phi, sqrt(1 - z^2) sin phi, z)`` -- uniform in z, the default directions of ``Pore(surface=True)``"""
+    M = int(M)
+    if not 1 <= M <= 4096:
+        raise ValueError("1 .. 4096 sphere points")
+    m = np.arange(M, dtype=np.float64)
+    z = 1.0 - (2.0 * m + 1.0) / M
+    phi = m * (np.pi * (3.0 - np.sqrt(5.0)))
+    r = np.sqrt(1.0 - z * z)
+    return np.ascontiguousarray(np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1))
+
+
+def surface_area(exposed, radii, rp, M):
+    """``[..]`` Angstrom^2 from exposed counts ``[..][S]``: ``sum_s ((4 pi) rho_s rho_s) exposed_s / M``, ``rho_s = radii[s] + rp``,
+    the species added in order"""
+    exposed = np.asarray(exposed, dtype=np.int64)
+    total = np.zeros(exposed.shape[:-1], dtype=np.float64)
+    for k, R in enumerate(np.asarray(radii, dtype=np.float64)):
+        rho = R + np.float64(rp)
+        total = total + ((4.0 * np.pi) * rho * rho) * exposed[..., k].astype(np.float64) / np.float64(M)
+    return total
+
+
+SURFACE_PER_GRAM = 6022.14076       # 1e-20 m^2 per Angstrom^2 x N_A: A^2 per cell and g/mol per cell  ->  m^2/g
+
+
+def surface_columns(exposed, exposed_access, radii, volume, mass, probes, M):
+    """the columns ``surface=True`` adds to ``.data``, from the library's integers: ``exposed [F][n_probes][S]`` (exposed samples
+    per species), ``exposed_access`` the same of the accessible ones, or None; ``radii [S]``, ``volume [F]`` (A^3), ``mass``
+    (g/mol per cell), ``M`` samples per atom.  Per probe rp: SA_A^2-rp (``surface_area``), SA_m^2/cm^3-rp = A^2 1e4 / V,
+    SA_m^2/g-rp = A^2 6022.14076 / mass; with ``exposed_access`` ASA_* of the accessible and NASA_* of exposed - accessible samples
+    (ASA + NASA = SA in counts)."""
+    exposed = np.asarray(exposed, dtype=np.int64)
+    F = exposed.shape[0]
+    exposed = exposed.reshape(F, len(probes), -1)
+    volume = np.asarray(volume, dtype=np.float64).reshape(F)
+    kinds = [("SA", exposed)]
+    if exposed_access is not None:
+        exposed_access = np.asarray(exposed_access, dtype=np.int64).reshape(exposed.shape)
+        if (exposed_access > exposed).any() or (exposed_access < 0).any():
+            raise ValueError("more accessible samples than exposed ones")
+        kinds += [("ASA", exposed_access), ("NASA", exposed - exposed_access)]
+    cols = {}
+    for k, rp in enumerate(probes):
+        for name, count in kinds:
+            area = surface_area(count[:, k], radii, rp, M)
+            cols[name + "_A^2-" + probe_label(rp)] = area
+            cols[name + "_m^2/cm^3-" + probe_label(rp)] = area * 1e4 / volume
+            cols[name + "_m^2/g-" + probe_label(rp)] = area * SURFACE_PER_GRAM / float(mass)
+    return cols
+
+
 def free_sphere_columns(free):
     """``Df = 2 t*`` and ``Dif`` from ``free [F][2]`` (t*, Dif / 2; inf: not resolved below dmax, 0: no channel at all)"""
     free = np.asarray(free, dtype=np.float64).reshape(-1, 2)
@@ -263,6 +325,10 @@ class Pore(Deferred):
                     per_point .cover float64 [F][nx][ny][nz], the covering radius.  In a frame with overflow points (the
                     warning below) the covering radius is a lower bound where it reaches dmax: the POV columns stay valid for
                     rp <= dmax, the distribution above dmax is not resolved.
+      surface=True: per probe radius SA_A^2-rp, SA_m^2/cm^3-rp, SA_m^2/g-rp, with accessibility ASA_* / NASA_*
+                    (``surface_columns``); .exposed int64 [F][n_probes][S], with accessibility .exposed_access;
+                    .surface_by_species: A^2 per element and probe radius; with per_point .surface_samples uint8
+                    [F][n_probes][N][M]: 0 buried, 1 exposed, 2 exposed and accessible
     These are grid estimates of geometric quantities, not Zeo++'s numbers (see the module's docstring).
     """
 
@@ -275,7 +341,7 @@ class Pore(Deferred):
     @classmethod
     def from_trajectory(cls, trajectory, delta_Step=1, first_frame=0, parallel=False, *, probe_radius=(0.0, 1.2), spacing=0.2,
                         grid=None, dr=0.05, dmax=None, radii=None, per_point=False, device=None, distributed=None, accessibility=False,
-                        free_sphere=False, psd=False):
+                        free_sphere=False, psd=False, surface=False, surface_points=256):
         """
         Args:
             trajectory: list of ase.Atoms-like frames, a PackedTrajectory or an XyzStream
@@ -293,6 +359,9 @@ class Pore(Deferred):
             free_sphere: the largest free sphere Df and Dif per frame (about log2 of the grid size labellings per frame)
             psd: the pore size distribution and the probe-occupiable volume of every probe radius (one more pass over the
                 field, about as heavy as the field itself; with accessibility one more per probe radius that has a channel)
+            surface: the surface area of every probe radius by Shrake-Rupley sampling, with accessibility its accessible and
+                non-accessible part; surface_points: samples per atom (1 .. 4096, ``sphere_points``).  The largest radius + the
+                largest probe radius above half the smallest perpendicular cell height raises ValueError
             device: GPU index or list of indices (default: LOCAL_RANK or 0)
             distributed: None -> the ranks of an initialised torch.distributed group take contiguous shares of the frames;
                 False -> single process; 'local' -> the trajectory is this rank's own block of frames
@@ -300,11 +369,13 @@ class Pore(Deferred):
         pore = cls()
         step = _trajectory.construct_step(delta_Step=delta_Step, first_frame=first_frame, number_of_frames=len(trajectory))
         pore.compute_pore(trajectory, step, probe_radius, spacing, grid, dr, dmax, radii, per_point, device=device,
-                          distributed=distributed, accessibility=accessibility, free_sphere=free_sphere, psd=psd)
+                          distributed=distributed, accessibility=accessibility, free_sphere=free_sphere, psd=psd, surface=surface,
+                          surface_points=surface_points)
         return pore
 
     def compute_pore(self, trajectory, step, probe_radius=(0.0, 1.2), spacing=0.2, grid=None, dr=0.05, dmax=None, radii=None,
-                     per_point=False, device=None, distributed=None, accessibility=False, free_sphere=False, psd=False):
+                     per_point=False, device=None, distributed=None, accessibility=False, free_sphere=False, psd=False, surface=False,
+                     surface_points=256):
         packed = _setup.pack(trajectory, device, keep_stream=True)
         logger.info("Start pore analysis for %s frames", len(packed))
         kinds, _ = _hip.packed_species(packed)
@@ -348,18 +419,25 @@ class Pore(Deferred):
         frame_range = st.shard(F)
         G = grid[0] * grid[1] * grid[2]
 
-        accessibility, free_sphere, psd = bool(accessibility), bool(free_sphere), bool(psd)
+        accessibility, free_sphere, psd, surface = bool(accessibility), bool(free_sphere), bool(psd), bool(surface)
+        dirs = sphere_points(surface_points) if surface else None
+        S, N, M = len(rs), len(packed.numbers), (len(dirs) if surface else 0)
+        if surface and F and rmax + max(probes + [0.0]) > half_height(cells, packed.pbc) * (1.0 + 1e-12):
+            raise ValueError("the largest radius + the largest probe radius = %g exceeds half the smallest cell height %g: a sample "
+                             "sphere would meet its own image" % (rmax + max(probes + [0.0]), 2.0 * half_height(cells, packed.pbc)))
         labelled = accessibility or free_sphere
         want_labels = accessibility and per_point
         if labelled and any(p and n < 3 for p, n in zip(packed.pbc, grid)):
             raise ValueError("accessibility / free_sphere: a periodic grid axis needs at least 3 points, the grid is %s" % (grid,))
         base_cols = nbins + 2 + n_t + 6
         access_cols = base_cols + (4 * n_t if labelled else 0) + (2 if free_sphere else 0)
-        cols = access_cols + ((nbins + 2 + n_t + (n_t if accessibility else 0)) if psd else 0)
+        psd_cols = access_cols + ((nbins + 2 + n_t + (n_t if accessibility else 0)) if psd else 0)
+        cols = psd_cols + (n_t * S * (2 if accessibility else 1) if surface else 0)
         want_cover = psd and per_point
+        want_samples = surface and per_point
 
         def finish_host(raw):
-            rows, field, labels, cover = raw
+            rows, field, labels, cover, samples = raw
             rows = np.asarray(rows, dtype=np.int64).reshape(-1, cols)
             tail = rows[:, nbins + 2 + n_t:base_cols].copy()
             self._assemble(rows[:, :nbins + 2].copy().view(np.uint64), rows[:, nbins + 2:nbins + 2 + n_t].copy(),
@@ -370,17 +448,24 @@ class Pore(Deferred):
                                       rows[:, base_cols + 4 * n_t:access_cols].copy().view(np.float64) if free_sphere else None, labels,
                                       accessibility, tail[:, 2].copy().view(np.float64), mass, probes, grid)
             if psd:
-                more = rows[:, access_cols:]
+                more = rows[:, access_cols:psd_cols]
                 self._assemble_psd(more[:, :nbins + 2].copy().view(np.uint64), more[:, nbins + 2:nbins + 2 + n_t].copy(),
                                    more[:, nbins + 2 + n_t:].copy() if accessibility else None, cover,
                                    tail[:, 2].copy().view(np.float64), mass, probes, grid, dr)
+            if surface:
+                more = rows[:, psd_cols:].copy().reshape(-1, 2 if accessibility else 1, n_t, S)
+                self._assemble_surface(more[:, 0], more[:, 1] if accessibility else None, samples, rs, kinds,
+                                       tail[:, 2].copy().view(np.float64), mass, probes, M)
 
         def call(tr, frame_range=None):
             # one int64 row per frame -- histogram, probe counts, the bits of vmax, argmax, the bits of the cell volume and of
             # the position of vmax -- so that one gather merges the ranks
             flags = dict(per_point=per_point, labelled=labelled, free_sphere=free_sphere, labels=want_labels, psd=psd,
-                         accessibility=psd and accessibility)
-            if psd:
+                         accessibility=(psd or surface) and accessibility, surface=surface)
+            if surface:
+                res = ctx.pore_surface(tr, rs, grid, dr, dmax, probes, dirs=dirs, frame_range=frame_range, per_point=per_point,
+                                       accessibility=accessibility, free_sphere=free_sphere, labels=want_labels, psd=psd)
+            elif psd:
                 res = ctx.pore_psd(tr, rs, grid, dr, dmax, probes, frame_range=frame_range, per_point=per_point,
                                    accessibility=accessibility, free_sphere=free_sphere, labels=want_labels)
             elif labelled:
@@ -394,6 +479,8 @@ class Pore(Deferred):
                 more += [r.access.reshape(-1, 4 * n_t)] + ([r.free_sphere.view(np.int64)] if free_sphere else [])
             if psd:
                 more += [r.psd_hist.view(np.int64), r.po_counts] + ([r.po_access] if accessibility else [])
+            if surface:
+                more += [r.exposed.reshape(-1, n_t * S)] + ([r.exposed_access.reshape(-1, n_t * S)] if accessibility else [])
             hist, counts, vmax, argmax = r.hist, r.counts, r.vmax, r.argmax
             f0, f1 = (0, len(vmax)) if frame_range is None else frame_range
             c = np.asarray(tr.cell, dtype=np.float64).reshape(-1, 3, 3)
@@ -402,17 +489,17 @@ class Pore(Deferred):
             where = np.ascontiguousarray(positions(argmax, c, grid), dtype=np.float64).reshape(-1, 3)
             rows = np.concatenate([hist.view(np.int64), counts, vmax.view(np.int64)[:, None], argmax[:, None],
                                    volume.view(np.int64)[:, None], where.view(np.int64)] + more, axis=1)
-            return rows, r.field, r.labels, r.cover
+            return rows, r.field, r.labels, r.cover, r.samples
 
         if _setup.streamed(st):
             def walk():
-                keep = [0] + ([1] if per_point else []) + ([2] if want_labels else []) + ([3] if want_cover else [])
+                keep = [0] + ([1] if per_point else []) + ([2] if want_labels else []) + ([3] if want_cover else []) + ([4] if want_samples else [])
 
                 def kept(batch):
                     res = call(batch)
                     return tuple(res[k] for k in keep)
                 got = _setup.walk(source, kept, ("cat",) * len(keep))
-                return tuple(got[keep.index(k)] if k in keep else None for k in range(4))
+                return tuple(got[keep.index(k)] if k in keep else None for k in range(5))
 
             self._defer(ctx, walk, finish_host)
             return
@@ -422,11 +509,12 @@ class Pore(Deferred):
             if F == 0:
                 return (np.zeros((0, cols), dtype=np.int64), (np.zeros((0,) + grid) if per_point else None),
                         (np.zeros((0, n_t) + grid, dtype=np.int32) if want_labels else None),
-                        (np.zeros((0,) + grid) if want_cover else None))
+                        (np.zeros((0,) + grid) if want_cover else None),
+                        (np.zeros((0, n_t, N, M), dtype=np.uint8) if want_samples else None))
             return call(packed, frame_range)
 
         def finish(raw):
-            rows, field, labels, cover = raw
+            rows, field, labels, cover, samples = raw
             if sharded:
                 rows = _dist.all_gather_rows(rows, device=ctx.device)
                 if per_point:
@@ -438,7 +526,10 @@ class Pore(Deferred):
                 if want_cover:
                     cover = _dist.all_gather_rows(cover.reshape(-1, G).view(np.int64), device=ctx.device).view(np.float64)
                     cover = cover.reshape((-1,) + grid)
-            finish_host((rows, field, labels, cover))
+                if want_samples:
+                    samples = _dist.all_gather_rows(samples.reshape(-1, n_t * N * M).astype(np.int64), device=ctx.device)
+                    samples = samples.astype(np.uint8).reshape((-1, n_t, N, M))
+            finish_host((rows, field, labels, cover, samples))
 
         self._defer(ctx, local, finish, collective=sharded)
 
@@ -480,6 +571,24 @@ class Pore(Deferred):
         if cover is not None:
             self.cover = cover
         cols, self.psd = psd_columns(psd_counts, po_counts, po_access, volume, mass, probes, grid, dr)
+        self.data = pd.concat([self.data, pd.DataFrame(cols, index=self.data.index)], axis=1)
+
+    def _assemble_surface(self, exposed, exposed_access, samples, radii, kinds, volume, mass, probes, M):
+        """the columns of ``surface`` behind the others (``surface_columns``), the areas per element"""
+        self.exposed = exposed
+        if exposed_access is not None:
+            self.exposed_access = exposed_access
+        if samples is not None:
+            self.surface_samples = samples
+        self.surface_points = M
+        by = {}
+        for s, z in enumerate(kinds):
+            only = np.zeros_like(exposed)
+            only[:, :, s] = exposed[:, :, s]
+            for k, rp in enumerate(probes):
+                by[_data.chemical_symbols[int(z)] + "-" + probe_label(rp)] = surface_area(only[:, k], radii, rp, M)
+        self.surface_by_species = pd.DataFrame(by, index=self.data.index)
+        cols = surface_columns(exposed, exposed_access, radii, volume, mass, probes, M)
         self.data = pd.concat([self.data, pd.DataFrame(cols, index=self.data.index)], axis=1)
 
     def write_to_file(self, path_to_output):

@@ -130,6 +130,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_pore_field: 2 the cell sort (0 on "pore_exact"), 3 the field kernels.
  * after amof_pore_access / amof_pore_access_field: 4 the labelling (amof_pore_access: 2 and 3 as amof_pore_field).
  * after amof_pore_psd / amof_pore_psd_field: 5 the covering stage (2 .. 4 as amof_pore_access where those stages ran).
+ * after amof_pore_surface: 6 the surface stage, its cell sorts included (2 .. 5 as amof_pore_psd where those stages ran).
  * Returns < 0 if unavailable. */
 double amof_last_kernel_seconds(const amof_ctx *ctx, int which);
 /* number of launches of the dominant kernel in the last call */
@@ -172,7 +173,10 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        device memory), "pore_label_global" (every link merged in device memory; AMOF_PORE_LABEL_GLOBAL=1)
  *   pore covering (amof_pore_psd, amof_pore_psd_field) "pore_cover_brick" (bricks of grid points gather the centres whose
  *        sphere reaches them from the source bricks within reach), "pore_cover_exact" (every offset within reach per grid
- *        point: a brick's list too short, a reach of too many bricks; also AMOF_PORE_COVER_EXACT=1) */
+ *        point: a brick's list too short, a reach of too many bricks; also AMOF_PORE_COVER_EXACT=1)
+ *   pore surface (amof_pore_surface) "pore_surface_list" (a wave per atom against its neighbour list, float32 compares, the
+ *        guard band re-decided in canonical float64), "pore_surface_exact" (every atom per sample in canonical float64: open
+ *        axes, a list too short; also AMOF_PORE_SURFACE_EXACT=1) */
 const char *amof_last_path(const amof_ctx *ctx);
 
 /*
@@ -601,6 +605,69 @@ int amof_pore_psd_field(amof_ctx *ctx, const double *field /* host [n_frames][G]
                         int64_t *po_access /* host [n_frames][n_t]; NULL unless want_access */,
                         double *cover /* host [n_frames][G] or NULL */);
 int amof_pore_cover_stats(const amof_ctx *ctx, double *out3 /* host [3] */);
+
+/*
+ * Surface area of the pore space: deterministic Shrake-Rupley sampling of the atoms' spheres.
+ * (The reference reads ASA / NASA from Zeo++ -sa, amof/pore/core.py get_surface_volume: Monte-Carlo samples on the same
+ * spheres, accessibility from a Voronoi network.  This is the deterministic version on a fixed table of directions, with
+ * accessibility from the grid's channels; it does not reproduce Zeo++'s numbers.)  Definitions:
+ *   directions  dirs, host float64 [M][3], 1 <= M <= 4096 (AMOF_EINVAL), every row a unit vector: | |u|^2 - 1 | <= 1e-12 with
+ *               |u|^2 = (u_x u_x + u_y u_y) + u_z u_z (AMOF_EINVAL).  The library computes no sine or cosine: the caller builds
+ *               the table (amof_amd.pore.sphere_points: the Fibonacci lattice).
+ *   samples     probe radius rp = thresholds[t] >= 0 (AMOF_EINVAL), atom j of species s: rho_j = radii[s] + rp in float64 and
+ *               s_c = r_jc + rho_j u_mc -- the product first, then the sum, no fma
+ *   exposed     sample (j, m) is exposed iff for every atom k != j (by atom index): d0 = r_k - s from the raw positions, the
+ *               canonical minimum image of it and d2 exactly as amof_cn_count and the field form them, and
+ *               sqrt(d2) - radii[s_k] >= rp -- the field's float64 compare.  A sample is exposed exactly when the field of all
+ *               OTHER atoms, evaluated at the sample, is >= rp.
+ *   one image   max_s radii[s] + max_t thresholds[t] must not exceed half the smallest perpendicular cell height on a periodic
+ *               axis (AMOF_EINVAL; relative slack 1e-12 as for the field): one minimum image per pair then suffices, and no
+ *               other image of j comes closer to its own sample than rho_j.
+ *   exposed [F][n_t][S]: exposed samples per species of the sampled atom.  Integers: paths, batches, frame ranges and ranks agree
+ *               bit for bit.  The host forms SA = sum_s 4 pi (radii[s] + rp)^2 exposed_s / M (Angstrom^2); rp = 0 is the van
+ *               der Waals surface.
+ *   accessible  (want_access) f = s C^-1, wrapped into [0, 1) on periodic axes; t_k = f_k n_k - 0.5, i_k = floor(t_k).  The 8
+ *               grid points (i_x + a, i_y + b, i_z + c), a, b, c in {0, 1}, are the sample's corners: indices modulo n_k on a
+ *               periodic axis, a corner outside the grid on an open axis is dropped.  An exposed sample is accessible iff at
+ *               least one corner belongs to a channel of V(rp) (amof_pore_access).  An exposed sample with no corner in a
+ *               channel -- also one in a crevice narrower than the grid -- counts as non-accessible: a grid estimate that
+ *               converges with the spacing.
+ *   exposed_access [F][n_t][S] (want_access; AMOF_EINVAL if NULL then): accessible samples; NASA = exposed - exposed_access
+ *   samples (optional, may be NULL) host uint8 [F][n_t][N][M], atoms in input order: 0 buried, 1 exposed, 2 exposed and
+ *               accessible; at most 4 GiB per frame (AMOF_ECAPACITY)
+ * amof_pore_surface: amof_pore_psd's arguments, stages, switches and outputs, bit for bit -- the covering stage only with
+ * want_psd (psd_hist, po_counts, po_access and cover may be NULL without it) -- and the surface stage per (frame, threshold):
+ * behind the labelling of that threshold where the call labels (want_access or want_free), on its own otherwise.
+ * Paths (amof_last_path): "pore_surface_list" -- a wave per atom of a cell-sorted frame gathers the atom's neighbour images as
+ * float32 records, its lanes sweep them per sample with a root-free float32 compare and re-decide in canonical float64 inside
+ * the guard band amof_pore_surface_bound -- and "pore_surface_exact" -- a lane per sample, every atom in canonical float64: open
+ * axes, AMOF_PORE_SURFACE_EXACT=1, a wave with more than 512 neighbour records (the launch is then run again on the exact
+ * path; AMOF_PORE_SURFACE_LIST_CAP=n lowers that limit, for tests).  Both give the same integers.  The list holds the records
+ * that bury a quarter of the atom's sphere or more in front, so that a buried sample ends sooner; AMOF_PORE_SURFACE_UNSORTED=1
+ * keeps the order of the gather (for measurements; the same integers).
+ * amof_last_kernel_seconds: which = 6 the surface stage; amof_last_kernel_launches: its launches.  amof_pore_surface_stats:
+ * out5 = atoms swept, neighbour records kept, samples, float64 re-decisions, samples ended before the end of their list, summed
+ * over the launches of the last call that stayed on "pore_surface_list".
+ * All outputs are overwritten (zeros after an error).  Errors: as amof_pore_field.
+ */
+int amof_pore_surface(amof_ctx *ctx, const amof_traj *traj, const double *radii /* host [S] */, const int32_t *grid /* host [3] */,
+                      double dr, double dmax, const double *thresholds /* host [n_t], >= 0 */, int32_t n_t, int32_t want_access,
+                      int32_t want_free, uint64_t *hist /* host [F][nbins + 2] */, int64_t *counts /* host [F][n_t] */,
+                      double *vmax /* host [F] */, int64_t *argmax /* host [F] */,
+                      int64_t *access /* host [F][n_t][4]; may be NULL without want_access and want_free */,
+                      double *free_sphere /* host [F][2] or NULL */, double *field /* host [F][G] or NULL */,
+                      int32_t *labels /* host [F][n_t][G] or NULL */, uint64_t *psd_hist /* host [F][nbins + 2]; NULL without want_psd */,
+                      int64_t *po_counts /* host [F][n_t]; NULL without want_psd */,
+                      int64_t *po_access /* host [F][n_t]; NULL unless want_psd and want_access */,
+                      double *cover /* host [F][G] or NULL */, int32_t want_psd, const double *dirs /* host [n_dirs][3] */,
+                      int32_t n_dirs, int64_t *exposed /* host [F][n_t][S] */,
+                      int64_t *exposed_access /* host [F][n_t][S]; NULL unless want_access */,
+                      uint8_t *samples /* host [F][n_t][N][n_dirs] or NULL */);
+/* the bound eps (Angstrom) of the float32 compare of "pore_surface_list" for a cell (rows = cell vectors) and
+ * reach = max_s radii[s] + max_t thresholds[t] (amof_amd/csrc/pore_surface_math.h): a sample closer than eps to a neighbour's
+ * sphere is re-decided in float64.  Tests plant decisions inside it. */
+double amof_pore_surface_bound(const double *cell /* host [9] */, double reach);
+int amof_pore_surface_stats(const amof_ctx *ctx, double *out5 /* host [5] */);
 
 /*
  * Static structure factor by direct summation over reciprocal-lattice vectors.
