@@ -5,8 +5,10 @@ lag/origin family has always used as aliases.)
 """
 
 import collections
+import threading
 
 from . import _hip
+from . import _lazy
 from . import atom as amatom
 from . import data as _data
 from . import dist as _dist
@@ -60,6 +62,17 @@ def begin_local(source):
     """first thing of a ``local()`` (the lane job of amof_amd/_lazy.py): the frames are there before the kernels start"""
     if getattr(source, "is_stream", False):
         source.read_all()
+
+
+def on_lane(ctx, fn):
+    """``fn()`` -- a device call a CONSTRUCTOR makes on its lane's context -- in lane order: behind the jobs the context has
+    queued, waited for here (what it raises is raised here).  A context is one queue of device calls and some calls come in
+    pairs that nothing may split (``msd_shard_begin`` / ``_finish``): a call from the constructor's thread would land among
+    the queued jobs wherever the timing puts it.  Called directly where there is no lane (a MultiContext), where the
+    classes run synchronously (``AMOF_ASYNC=0``: nothing is ever queued) and from the lane's own thread."""
+    if not hasattr(ctx, "submit") or not _lazy.async_enabled() or threading.get_ident() == ctx._lane_thread:
+        return fn()
+    return ctx.submit(fn).result()
 
 
 def streamed(st):

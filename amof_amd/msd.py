@@ -183,7 +183,13 @@ class WindowMsd(Msd, Deferred):
         return float(sumsq[0][0]) / n / (F - m)
 
     def compute_msd(self, trajectory, window, time, parallel=False, unwrap=False, device=None, distributed=None):
-        """compute the window MSD (reference amof/msd.py:207-268)"""
+        """compute the window MSD (reference amof/msd.py:207-268)
+
+        An atom-sharded run with device collectives makes a device call of its own before it returns (the first half of
+        the sharded form, or the centre of mass): it waits for the jobs already queued on the lane, so that the calls of
+        the lane's context keep the order of the program.  That holds for ONE constructing thread per device:
+        constructing sharded analyses on one device from several threads at once is not supported (another thread's job
+        could be queued between the two halves)."""
         packed = _setup.pack(trajectory, device)      # (read whole: a window couples frames half a trajectory apart)
         elements = packed.unique_numbers()
         if unwrap == True:  # noqa: E712  (the reference compares with ==)
@@ -203,19 +209,22 @@ class WindowMsd(Msd, Deferred):
             # the centre of mass of every frame, a sum over ALL atoms: each rank reads ITS atoms once and contributes their
             # mass-weighted coordinate sums per frame, ONE all-reduce of [F][3] (120 kB at 5000 frames) completes them, and
             # the rank's second pass finishes its atoms (amof_msd_shard_begin / _finish: 1 / world of the trajectory per rank
-            # and pass).  The first half and the all-reduce run here, in the calling thread -- collectives are issued in
-            # program order, never from a lane -- the second half on the lane.
+            # and pass).  The all-reduce runs here, in the calling thread -- collectives are issued in program order, never
+            # from a lane.  Both halves run in LANE order: the first behind the jobs the context has queued, waited for here
+            # (_setup.on_lane), the second submitted right after the all-reduce, so no other call of this context comes
+            # between them -- amof_msd_shard_finish must be the call after its begin.
             import torch
             csum = torch.empty((F, 3), dtype=torch.float64, device=torch.device("cuda", ctx.device))
             try:
-                ctx.msd_shard_begin(packed, window, atom_range, csum)
+                _setup.on_lane(ctx, lambda: ctx.msd_shard_begin(packed, window, atom_range, csum))
                 _dist.all_reduce_sum(csum)
             except _hip.Unsupported:
                 # general cells, irregular windows: the centre of mass frame-sharded into a zeroed table (x + 0 = x, exact),
                 # then the general kernels on the rank's atoms
                 csum = None
                 com = torch.zeros((F, 3), dtype=torch.float64, device=torch.device("cuda", ctx.device))
-                ctx.msd_com(packed, _dist.shard_range(F, rank, world), com)
+                frames = _dist.shard_range(F, rank, world)
+                _setup.on_lane(ctx, lambda: ctx.msd_com(packed, frames, com))
                 _dist.all_reduce_sum(com)
 
         def local():

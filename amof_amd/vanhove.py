@@ -137,10 +137,7 @@ class WindowVanHove(Deferred):
             import torch
             com = torch.zeros((F, 3), dtype=torch.float64, device=torch.device("cuda", ctx.device))
             frames = _dist.shard_range(F, rank, world)
-            if hasattr(ctx, "submit"):
-                ctx.submit(lambda: ctx.msd_com(packed, frames, com)).result()
-            else:
-                ctx.msd_com(packed, frames, com)
+            _setup.on_lane(ctx, lambda: ctx.msd_com(packed, frames, com))
             _dist.all_reduce_sum(com)
 
         S = len(_hip.packed_species(packed)[0])

@@ -17,6 +17,13 @@ class OracleContext(_hip.Lane):
         self.device = None
         self._lane_name = name
         self.calls = []
+        self.n_calls = 0            # every entry point counts, as `calls` of the C context does (csrc/msd.hip shard_ticket)
+        self._shard_ticket = 0      # n_calls right after a msd_shard_begin; 0: none pending
+        self._shard_key = None
+
+    def _call(self, name):
+        self.calls.append(name)
+        self.n_calls += 1
 
     def job_stats(self):
         return {"kernel_s_all": 0.0, "kernel_s_dominant": 0.0, "kernel_launches": 0, "path": self.calls[-1] if self.calls else ""}
@@ -29,34 +36,62 @@ class OracleContext(_hip.Lane):
 
     def rdf_accumulate(self, packed, rmax, nbins, frame_range=None, out=None):
         assert out is None
-        self.calls.append("rdf")
+        self._call("rdf")
         kinds, sp = _hip.packed_species(packed)
         pos, cell = self._frames(packed, frame_range)
         hist, vol = clib.rdf_hist(pos, cell, sp, len(kinds), rmax, nbins)
         return hist, vol, kinds
 
     def cn_count(self, packed, cutoff, sets, frame_range=None, per_atom=False):
-        self.calls.append("cn")
+        self._call("cn")
         kinds, sp = _hip.packed_species(packed)
         pos, cell = self._frames(packed, frame_range)
         return clib.cn_counts(pos, cell, sp, len(kinds), np.asarray(cutoff, dtype=np.float64), sets, per_atom=per_atom)
 
     def bad_hist(self, packed, cutoff, triples, edges, frame_range=None, out=None):
         assert out is None
-        self.calls.append("bad")
+        self._call("bad")
         kinds, sp = _hip.packed_species(packed)
         pos, cell = self._frames(packed, frame_range)
         return clib.bad_hist(pos, cell, sp, len(kinds), np.asarray(cutoff, dtype=np.float64), triples, np.asarray(edges))
 
     def bad_hist_by_cn(self, packed, cutoff, triples, edges, cn_max=16, frame_range=None):
-        self.calls.append("bad_by_cn")
+        self._call("bad_by_cn")
         kinds, sp = _hip.packed_species(packed)
         pos, cell = self._frames(packed, frame_range)
         return clib.bad_hist_by_cn(pos, cell, sp, len(kinds), np.asarray(cutoff, dtype=np.float64), triples, np.asarray(edges), cn_max)
 
     def msd_window(self, packed, windows, unwrap=False, remove_com=True, atom_range=None, com=None, out=None):
         assert com is None and out is None and remove_com
-        self.calls.append("msd")
+        self._call("msd")
+        return self._msd_sums(packed, windows, unwrap, atom_range)
+
+    def msd_shard_begin(self, packed, windows, atom_range, csum):
+        """first half of the atom-sharded form: the mass-weighted coordinate sums of the rank's atoms per frame into ``csum``
+        (a numpy ``[F][3]`` table here), and the C side's record of the pending pair (csrc/msd.hip amof_msd_shard_begin):
+        the ticket is the call count right after this call, the key its arguments"""
+        self._call("msd_shard_begin")
+        a0, a1 = atom_range
+        csum[...] = (packed.pos_host()[:, a0:a1] * packed.masses[None, a0:a1, None]).sum(axis=1)
+        self._shard_ticket = self.n_calls
+        self._shard_key = (id(packed), tuple(int(w) for w in windows), tuple(atom_range))
+        return csum
+
+    def msd_shard_finish(self, packed, windows, atom_range, csum, out):
+        """second half, with the C side's rule (amof_msd_shard_finish): it must be the NEXT call on this context after a
+        begin of the same arguments -- the ticket is cleared either way"""
+        same = self._shard_ticket != 0 and self._shard_ticket == self.n_calls
+        same = same and self._shard_key == (id(packed), tuple(int(w) for w in windows), tuple(atom_range))
+        self._shard_ticket = 0
+        self._call("msd_shard_finish")
+        if not same:
+            raise ValueError("msd_shard_finish must follow msd_shard_begin of the same arguments on this context")
+        sums, kinds = self._msd_sums(packed, windows, False, atom_range)
+        out += sums
+        return out, kinds
+
+    @staticmethod
+    def _msd_sums(packed, windows, unwrap, atom_range):
         kinds, _ = _hip.packed_species(packed)
         a0, a1 = (0, packed.n_atoms) if atom_range is None else atom_range
         mask = np.zeros(packed.n_atoms, dtype=bool)

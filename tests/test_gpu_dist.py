@@ -20,6 +20,9 @@ def _build():
 
 
 def _run_all(packed, distributed):
+    """the four classes on one trajectory.  It is a HOST trajectory and the MSD's windows are one frame apart, so the MSD
+    never takes its device-collective branch here (msd_shard_begin / _finish, or msd_com + msd_window(com, out)):
+    tests/test_gpu_msd_shard_class.py runs that branch through the class."""
     from amof_amd.rdf import Rdf
     from amof_amd.msd import WindowMsd
     from amof_amd.bad import Bad

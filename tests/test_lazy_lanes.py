@@ -149,6 +149,81 @@ def test_lane_runs_jobs_in_order_and_drain_waits():
     lane.close_lane()
 
 
+def _sharded_msd_pairs(lane, packed, first_half):
+    """What WindowMsd.compute_msd does on its lane's context in an atom-sharded run with device collectives
+    (amof_amd/msd.py), twice, with two window lists, behind a lane that is busy -- the first half through ``first_half(ctx,
+    fn)``, the all-reduce (one rank: nothing to add), the second half submitted -- and an unrelated job of another class
+    queued before each.  The stand-in's halves enforce the C side's rule: a finish is the next call after its begin.
+    Returns the futures of the second halves and the tables they add into."""
+    kinds, _ = _hip.packed_species(packed)
+    whole = (0, packed.n_atoms)
+    gate = threading.Event()
+    lane.submit(lambda: gate.wait(timeout=10))          # (frees itself whatever happens)
+    threading.Timer(1.0, gate.set).start()
+    futs, outs = [], []
+    for window in (np.array([0, 1, 2, 3], dtype=np.int32), np.array([0, 2], dtype=np.int32)):
+        lane.submit(lambda: lane.cn_count(packed, np.full((len(kinds), len(kinds)), 2.5), [(0, 1)]))
+        csum = np.empty((packed.n_frames, 3))
+        out = np.zeros((len(kinds), len(window)))
+        first_half(lane, lambda: lane.msd_shard_begin(packed, window, whole, csum))
+        # (all_reduce_sum(csum): in the calling thread, no call of the context)
+        futs.append(lane.submit(lambda w=window, c=csum, o=out: lane.msd_shard_finish(packed, w, whole, c, o)))
+        outs.append((window, csum, out))
+    gate.set()
+    lane.drain()
+    return futs, outs
+
+
+def test_sharded_msd_halves_are_not_split_by_what_the_lane_has_queued(lanes, traj):
+    """``_setup.on_lane`` runs the first half behind the queued jobs and waits, so every finish directly follows its begin:
+    both succeed, with the sums of the one-call form.  (With the first half called directly from this thread -- the next
+    test -- both finishes are refused.)"""
+    from amof_amd import _setup
+    lane = lanes[1]
+    futs, outs = _sharded_msd_pairs(lane, traj, _setup.on_lane)
+    assert lane.calls == ["cn", "msd_shard_begin", "msd_shard_finish"] * 2
+    for fut, (window, csum, out) in zip(futs, outs):
+        got, kinds = fut.result(timeout=10)
+        assert got is out
+        ref, _ = lane.msd_window(traj, window)
+        assert np.array_equal(out, ref) and out.any()
+        np.testing.assert_allclose(csum, (traj.pos_host() * traj.masses[None, :, None]).sum(axis=1), rtol=1e-14)
+    assert lane._jobs_finished == lane._jobs_submitted
+
+
+def test_the_stand_in_refuses_a_finish_that_does_not_follow_its_begin(lanes, traj, monkeypatch):
+    """the stand-in's rule is the C side's (tests/test_gpu_msd_fused.py::test_sharded_halves_add_up_to_the_whole): the same
+    sequence with the first half called from the constructing thread -- both begins run at once, the second replaces the
+    first's ticket and key, the queued jobs follow -- and each finish raises.  on_lane itself calls directly where the
+    classes run synchronously, where there is no lane, and from the lane's own thread."""
+    from amof_amd import _setup
+    lane = lanes[1]
+    futs, outs = _sharded_msd_pairs(lane, traj, lambda ctx, fn: fn())
+    assert lane.calls == ["msd_shard_begin", "msd_shard_begin", "cn", "msd_shard_finish", "cn", "msd_shard_finish"]
+    for fut, (_, _, out) in zip(futs, outs):
+        with pytest.raises(ValueError, match="must follow"):
+            fut.result(timeout=10)
+        assert not out.any()
+    # a finish right after its begin, but with other arguments
+    w = np.array([0, 1], dtype=np.int32)
+    out = np.zeros((4, 2))
+    lane.msd_shard_begin(traj, w, (0, 5), np.empty((traj.n_frames, 3)))
+    with pytest.raises(ValueError, match="must follow"):
+        lane.msd_shard_finish(traj, w, (0, 6), np.empty((traj.n_frames, 3)), out)
+    # where on_lane does not queue
+    here = threading.get_ident()
+    submitted = lane._jobs_submitted
+    monkeypatch.setenv("AMOF_ASYNC", "0")
+    assert _setup.on_lane(lane, threading.get_ident) == here
+    monkeypatch.setenv("AMOF_ASYNC", "1")
+    assert _setup.on_lane(object(), threading.get_ident) == here
+    assert lane._jobs_submitted == submitted
+    assert _setup.on_lane(lane, threading.get_ident) == lane._lane_thread != here
+    assert lane.submit(lambda: _setup.on_lane(lane, threading.get_ident)).result(timeout=10) == lane._lane_thread
+    with pytest.raises(_hip.Unsupported):       # what the call raises is raised to the constructor
+        _setup.on_lane(lane, lambda: (_ for _ in ()).throw(_hip.Unsupported(_hip.AMOF_EUNSUPPORTED, "general cell")))
+
+
 def test_a_following_lane_without_a_gpu_context_runs_at_once():
     """Lane.follow_leader is a GPU matter (amof_amd/_hip.py Context.follow_leader): the stand-in lanes of the CPU suite have
     no leader, count their jobs all the same, and run a job as soon as it is submitted"""
