@@ -6,6 +6,7 @@ Drop-in mirrors of the reference's hot-path classes (coudertlab/amof v1.1.0):
     amof.msd.WindowMsd            -> amof_amd.msd.WindowMsd
     amof.bad.Bad                  -> amof_amd.bad.Bad
     amof.cn.CoordinationNumber    -> amof_amd.cn.CoordinationNumber
+    amof.ring.Ring                -> amof_amd.ring.Ring           (primitive ring statistics on the GPU: no RINGS binary)
 
 Analyses beyond the reference:
 

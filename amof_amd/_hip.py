@@ -38,7 +38,7 @@ EXPORTS = [
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
-    "amof_bond_order", "amof_bond_order_dev", "amof_pore_field", "amof_pore_candidate_bound",
+    "amof_bond_order", "amof_bond_order_dev", "amof_ring_stats", "amof_ring_search_stats", "amof_pore_field", "amof_pore_candidate_bound",
     "amof_pore_access", "amof_pore_access_field", "amof_pore_psd", "amof_pore_psd_field", "amof_pore_cover_stats",
     "amof_pore_surface", "amof_pore_surface_bound", "amof_pore_surface_stats",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
@@ -148,6 +148,8 @@ def load_library():
         lib.amof_bond_reorientation_dev.argtypes = lib.amof_bond_reorientation.argtypes
         lib.amof_bond_order.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P]
         lib.amof_bond_order_dev.argtypes = lib.amof_bond_order.argtypes
+        lib.amof_ring_stats.argtypes = [P, TP, P, ctypes.c_int32, P, P, P, P]
+        lib.amof_ring_search_stats.argtypes = [P, P]
         lib.amof_pore_field.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, P, P, P, P, P]
         lib.amof_pore_candidate_bound.argtypes = [P, ctypes.c_double]
         lib.amof_pore_access.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, ctypes.c_int32,
@@ -854,6 +856,35 @@ class Context(Lane):
                        _ptr(hist), _ptr(hist_tet), _ptr(sums), _ptr(pa)))
         return (hist, hist_tet, sums, pa) if per_atom else (hist, hist_tet, sums)
 
+    @_locked
+    def ring_stats(self, packed, cutoff, max_size=32, frame_range=None, per_atom=False, neighbours=False):
+        """``(counts int64 [F][4][max_size + 1], truncated int64 [F] [, per_atom u32 [F][N][max_size + 1]] [, neighbours int32
+        [F][N][17]])`` of ``amof_ring_stats``: the primitive rings of up to ``max_size`` (3 .. 32) nodes of the bond graph of
+        every frame of ``frame_range``.  ``cutoff``: the symmetric matrix ``[S][S]`` (``atom.cutoff_matrix`` of a sorted-pair
+        dictionary; 0: never bonded).  Per frame and size n: the sum over the atoms of the rings through them (n times the
+        number of rings), the atoms on such a ring, the atoms whose smallest / largest ring it is; ``truncated``: the sources
+        whose search was cut off at depth ``max_size // 2`` (include/amof_hip.h)."""
+        th = self._traj(packed, frame_range)
+        cutoff = _cutoff(cutoff, th.S)
+        max_size = int(max_size)
+        W = max(max_size, 0) + 1
+        counts = np.zeros((th.n_frames, 4, W), dtype=np.int64)
+        truncated = np.zeros(th.n_frames, dtype=np.int64)
+        pa = np.zeros((th.n_frames, th.n_atoms, W), dtype=np.uint32) if per_atom else None
+        nb = np.zeros((th.n_frames, th.n_atoms, 17), dtype=np.int32) if neighbours else None
+        self._check(self._lib.amof_ring_stats(self._h, ctypes.byref(th.c), _ptr(cutoff), max_size, _ptr(counts), _ptr(truncated),
+                                              _ptr(pa), _ptr(nb)))
+        return (counts, truncated) + ((pa,) if per_atom else ()) + ((nb,) if neighbours else ())
+
+    def ring_search_stats(self):
+        """``{"sources", "candidates", "closed"}`` of the last ``ring_stats``: the sources searched, their candidates and the
+        candidates that closed at least one ring (``amof_ring_search_stats``)"""
+        self.drain()
+        out = np.zeros(3, dtype=np.float64)
+        with self._lock:
+            self._check(self._lib.amof_ring_search_stats(self._h, _ptr(out)))
+        return dict(zip(("sources", "candidates", "closed"), out.tolist()))
+
     def _pore_atoms(self, packed, radii, grid, dr, dmax, thresholds, frame_range, dirs=None, **flags):
         """the four calls that take atoms -- ``amof_pore_field``, ``amof_pore_access`` (``labelled``), ``amof_pore_psd``
         (``psd``), ``amof_pore_surface`` (``surface``, with ``dirs [M][3]``) -- as a ``PoreResult``; ``flags``: ``pore_names``'"""
@@ -1249,6 +1280,12 @@ class MultiContext(object):
         return self._sharded("bond_order", packed, _span(frame_range, packed.n_frames), "frame_range",
                              ("sum", "sum", "cat", "cat")[:3 + bool(per_atom)], cutoff, sets, l, nbins, nbins_tet,
                              copy_frames=True, per_atom=per_atom)
+
+    def ring_stats(self, packed, cutoff, max_size=32, frame_range=None, per_atom=False, neighbours=False):
+        """frames sharded over the devices as ``cn_count``'s: every output is per frame, the rows concatenate"""
+        return self._sharded("ring_stats", packed, _span(frame_range, packed.n_frames), "frame_range",
+                             ("cat",) * (2 + bool(per_atom) + bool(neighbours)), cutoff, max_size, copy_frames=True,
+                             per_atom=per_atom, neighbours=neighbours)
 
     def pore_field(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False):
         """frames sharded over the devices as ``cn_count``'s: every output is per frame, the rows concatenate"""

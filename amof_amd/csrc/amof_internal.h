@@ -100,6 +100,8 @@ struct amof_ctx {
     // of the last amof_pore_surface, over its launches on "pore_surface_list": atoms swept, neighbour records kept, samples,
     // float64 re-decisions, samples ended by the early exit (amof_pore_surface_stats)
     double surface_stats[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    // of the last amof_ring_stats: sources, candidates searched, candidates that closed a ring (amof_ring_search_stats)
+    double ring_stats[3] = {0.0, 0.0, 0.0};
 };
 
 namespace amof {

@@ -127,6 +127,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations;
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
+ * after amof_ring_stats: 2 the adjacency rows, 3 the breadth-first searches (distance table, candidates), 4 the ring search.
  * after amof_pore_field: 2 the cell sort (0 on "pore_exact"), 3 the field kernels.
  * after amof_pore_access / amof_pore_access_field: 4 the labelling (amof_pore_access: 2 and 3 as amof_pore_field).
  * after amof_pore_psd / amof_pore_psd_field: 5 the covering stage (2 .. 4 as amof_pore_access where those stages ran).
@@ -166,6 +167,8 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *   bond order "order_frame" (the neighbour rows of BAD's frame tier: whole frames or z-slabs in LDS), "order_exact"
  *        (canonical float64 arithmetic per pair: general and per-frame cells, open axes, centres with 17 .. 64
  *        neighbours; also AMOF_ORDER_EXACT=1)
+ *   ring statistics "ring_wave" (a wave per source: level row and path stacks in LDS, a candidate per lane), "ring_simple" (a
+ *        thread per source, private stacks, no LDS, no candidate buffer; AMOF_RING_SIMPLE=1)
  *   pore field "pore_brick" (bricks of grid points against a cell list, float32 candidates, the near-minimal atoms
  *        re-evaluated in canonical float64), "pore_exact" (every atom per grid point in canonical float64: open axes,
  *        bricks too coarse for the cutoff or too full; also AMOF_PORE_EXACT=1)
@@ -459,6 +462,46 @@ int amof_bond_order_dev(amof_ctx *ctx, const amof_traj *traj, const double *cuto
                         uint64_t *hist_dev /* device [n_sets][n_l][nbins], += */,
                         uint64_t *hist_tet_dev /* device [n_sets][nbins_tet], += */, int64_t *frame_sums /* host */,
                         int64_t *per_atom /* host or NULL */);
+
+/*
+ * Primitive ring statistics of the bond network, per frame.
+ * Replaces amof.ring.Ring (amof/ring/core.py), which writes every frame to a temporary directory and runs the external
+ * program RINGS on it with growing search depth; the counts are those of its primitive rings (RINGS-res-5.dat).
+ *   Graph of a frame: the N atoms; i != j are bonded iff j is a neighbour of i by amof_cn_count's decision -- the canonical
+ *   minimum image, strict sqrt(d2) < rc with rc = cutoff[species i][species j] (symmetric; 0 = never bonded).  A cutoff
+ *   above half the smallest perpendicular cell height on a periodic axis is refused (AMOF_EINVAL), as amof_bond_survival's:
+ *   a pair then has at most one bond and the graph is simple.  It is the QUOTIENT graph of the cell: a closed path that
+ *   winds around a small cell is a ring of it (RINGS does the same on a periodic box).
+ *   Primitive ring (Franzblau's shortest-path ring): a simple cycle R of n >= 3 nodes with dist_G(y, z) == dist_R(y, z)
+ *   for every pair of its nodes.  With K = max_size / 2, D[v][.] = the breadth-first levels from v truncated at K (u8):
+ *     size 2k:      an unordered pair of shortest paths v -> w, D[v][w] = k >= 2, that share v and w only
+ *     size 2k + 1:  shortest paths v -> w1 and v -> w2 of a bonded pair w1 < w2 at level k >= 1, that share v only
+ *   and in both every cross pair y = P1[a], z = P2[b] has D[y][z] == min(a + b, n - a - b).  Every primitive n-ring is found
+ *   once from each of its n nodes: c[v][n] = primitive n-rings through v, rings[n] = sum_v c[v][n] / n exactly.
+ *   max_size: 3 .. 32.  The counts at sizes <= n1 do not depend on max_size >= n1.
+ *   Outputs, over the frames of the call (the caller passes the frames of its range: a trajectory handle of them):
+ *     counts int64 [F][4][max_size + 1]: [0] sum_v c[v][n], [1] nodes with c[v][n] > 0, [2] nodes whose smallest ring size
+ *       is n, [3] nodes whose largest ring size is n
+ *     truncated int64 [F]: sources whose search still had unvisited neighbours at level K.  0: the frame has no primitive
+ *       ring of more than 2K + 1 nodes; otherwise larger rings cannot be excluded (RINGS: "potentially undiscovered")
+ *     per_atom (optional, may be NULL) u32 [F][N][max_size + 1]: c[v][n]
+ *     neighbours (optional, may be NULL) int32 [F][N][1 + 16]: the degree and the neighbours in ascending order, -1 behind
+ *   Capacities (AMOF_ECAPACITY, the message names the limit and the frame; nothing is truncated silently): N <= 65535,
+ *   at most 16 neighbours per atom, at most 1024 shortest paths from a source to an end node of a candidate
+ *   (AMOF_RING_MAX_PATHS=n overrides the last, for tests).
+ *   All outputs are integers and independent per frame: frame ranges concatenate bit for bit, and nothing depends on the
+ *   batching (AMOF_RING_TABLE_MB=n caps the distance tables D of a batch of frames, N^2 bytes each, default 1024; 0: one
+ *   frame per batch) or the path ("ring_wave"; AMOF_RING_SIMPLE=1: "ring_simple").
+ *   amof_last_kernel_seconds: which = 2 the adjacency rows, 3 the breadth-first searches, 4 the ring search.
+ *   amof_ring_search_stats: out[3] = sources, candidates searched, candidates that closed at least one ring, of the last call.
+ * The outputs are overwritten (zeros after an error).  Errors: AMOF_EINVAL (max_size, an asymmetric, negative or oversized
+ * cutoff, NULL argument), AMOF_ESINGULAR, AMOF_ECAPACITY, AMOF_ENOMEM, AMOF_EHIP.
+ */
+int amof_ring_stats(amof_ctx *ctx, const amof_traj *traj, const double *cutoff /* [S][S], symmetric */, int32_t max_size,
+                    int64_t *counts /* host [F][4][max_size + 1] */, int64_t *truncated /* host [F] */,
+                    uint32_t *per_atom /* host [F][N][max_size + 1] or NULL */,
+                    int32_t *neighbours /* host [F][N][1 + 16] or NULL */);
+int amof_ring_search_stats(const amof_ctx *ctx, double *out /* [3] */);
 
 /*
  * Pore geometry on a grid: the distance of every grid point to the nearest atomic surface, and from it the void
