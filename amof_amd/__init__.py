@@ -7,6 +7,9 @@ Drop-in mirrors of the reference's hot-path classes (coudertlab/amof v1.1.0):
     amof.bad.Bad                  -> amof_amd.bad.Bad
     amof.cn.CoordinationNumber    -> amof_amd.cn.CoordinationNumber
     amof.ring.Ring                -> amof_amd.ring.Ring           (primitive ring statistics on the GPU: no RINGS binary)
+    amof.coordination.reduce, ReducedTrajectory
+                                  -> amof_amd.fragment.Fragments  (building units as connected components of a bond graph,
+                                                                   their centres of mass as a trajectory; no zif.py chemistry)
 
 Analyses beyond the reference:
 

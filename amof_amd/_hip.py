@@ -38,7 +38,8 @@ EXPORTS = [
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
-    "amof_bond_order", "amof_bond_order_dev", "amof_ring_stats", "amof_ring_search_stats", "amof_pore_field", "amof_pore_candidate_bound",
+    "amof_bond_order", "amof_bond_order_dev", "amof_ring_stats", "amof_ring_search_stats", "amof_fragment_stats", "amof_fragment_round_stats",
+    "amof_pore_field", "amof_pore_candidate_bound",
     "amof_pore_access", "amof_pore_access_field", "amof_pore_psd", "amof_pore_psd_field", "amof_pore_cover_stats",
     "amof_pore_surface", "amof_pore_surface_bound", "amof_pore_surface_stats",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
@@ -150,6 +151,8 @@ def load_library():
         lib.amof_bond_order_dev.argtypes = lib.amof_bond_order.argtypes
         lib.amof_ring_stats.argtypes = [P, TP, P, ctypes.c_int32, P, P, P, P]
         lib.amof_ring_search_stats.argtypes = [P, P]
+        lib.amof_fragment_stats.argtypes = [P, TP, P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P, P, P, P, ctypes.c_int32]
+        lib.amof_fragment_round_stats.argtypes = [P, P]
         lib.amof_pore_field.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, P, P, P, P, P]
         lib.amof_pore_candidate_bound.argtypes = [P, ctypes.c_double]
         lib.amof_pore_access.argtypes = [P, TP, P, P, ctypes.c_double, ctypes.c_double, P, ctypes.c_int32, ctypes.c_int32,
@@ -885,6 +888,53 @@ class Context(Lane):
             self._check(self._lib.amof_ring_search_stats(self._h, _ptr(out)))
         return dict(zip(("sources", "candidates", "closed"), out.tolist()))
 
+    @_locked
+    def fragment_stats(self, packed, cutoff, link=None, ref_label=None, kinds=None, max_size=64, frame_range=None, per_atom=False,
+                       com=False):
+        """``(summary int64 [F][5], size_hist int64 [F][max_size + 2], census int64 [F][K + 1] [, links int64 [F][K + 1][K + 1]]
+        [, label int32 [F][N], shift int32 [F][N][3]] [, com f64 [F][M][3], frag_mass f64 [M]])`` of ``amof_fragment_stats``: the
+        connected components of the bond graph of ``cutoff`` (``[S][S]``, symmetric, 0: never bonded) in every frame of
+        ``frame_range``.  ``summary``: fragments, atoms of the largest, winding fragments, atoms whose label differs from
+        ``ref_label`` (-1 without it), link bonds inside one fragment.  ``link`` (a second matrix, no pair in common with
+        ``cutoff``) adds ``links``: ordered link bonds between fragments by the kinds of the two; ``kinds [K][S]``: the species-count
+        vectors the census looks for; ``per_atom`` adds the labels and shifts; ``com`` (needs ``ref_label``) the centres of mass of
+        the reference fragments -- NaN rows where the frame's partition differs or the fragment winds -- and their masses
+        (include/amof_hip.h)."""
+        th = self._traj(packed, frame_range)
+        cutoff = _cutoff(cutoff, th.S)
+        link = None if link is None else _cutoff(link, th.S)
+        kinds = np.zeros((0, th.S), dtype=np.int32) if kinds is None else _i32(kinds).reshape(-1, th.S)
+        K, max_size = len(kinds), int(max_size)
+        F, N = th.n_frames, th.n_atoms
+        M = 0
+        if ref_label is not None:
+            ref_label = _i32(ref_label).reshape(N)
+            M = int((ref_label == np.arange(N)).sum())
+        elif com:
+            raise ValueError("com needs ref_label")
+        summary = np.zeros((F, 5), dtype=np.int64)
+        hist = np.zeros((F, max(max_size, 0) + 2), dtype=np.int64)
+        census = np.zeros((F, K + 1), dtype=np.int64)
+        links = np.zeros((F, K + 1, K + 1), dtype=np.int64) if link is not None else None
+        label = np.zeros((F, N), dtype=np.int32) if per_atom else None
+        shift = np.zeros((F, N, 3), dtype=np.int32) if per_atom else None
+        centres = np.zeros((F, M, 3), dtype=np.float64) if com else None
+        mass = np.zeros(M, dtype=np.float64) if com else None
+        self._check(self._lib.amof_fragment_stats(self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(link), _ptr(ref_label),
+                                                  _ptr(kinds) if K else None, K, max_size, _ptr(summary), _ptr(hist), _ptr(census),
+                                                  _ptr(links), _ptr(label), _ptr(shift), _ptr(centres), _ptr(mass), M))
+        return ((summary, hist, census) + ((links,) if link is not None else ()) + ((label, shift) if per_atom else ())
+                + ((centres, mass) if com else ()))
+
+    def fragment_round_stats(self):
+        """``{"frames", "rounds", "max_rounds"}`` of the last ``fragment_stats``: the frames labelled, the labelling rounds summed
+        over them and the most rounds of one frame (``amof_fragment_round_stats``)"""
+        self.drain()
+        out = np.zeros(3, dtype=np.float64)
+        with self._lock:
+            self._check(self._lib.amof_fragment_round_stats(self._h, _ptr(out)))
+        return dict(zip(("frames", "rounds", "max_rounds"), out.tolist()))
+
     def _pore_atoms(self, packed, radii, grid, dr, dmax, thresholds, frame_range, dirs=None, **flags):
         """the four calls that take atoms -- ``amof_pore_field``, ``amof_pore_access`` (``labelled``), ``amof_pore_psd``
         (``psd``), ``amof_pore_surface`` (``surface``, with ``dirs [M][3]``) -- as a ``PoreResult``; ``flags``: ``pore_names``'"""
@@ -1286,6 +1336,14 @@ class MultiContext(object):
         return self._sharded("ring_stats", packed, _span(frame_range, packed.n_frames), "frame_range",
                              ("cat",) * (2 + bool(per_atom) + bool(neighbours)), cutoff, max_size, copy_frames=True,
                              per_atom=per_atom, neighbours=neighbours)
+
+    def fragment_stats(self, packed, cutoff, link=None, ref_label=None, kinds=None, max_size=64, frame_range=None, per_atom=False,
+                       com=False):
+        """frames sharded over the devices as ``ring_stats``': every output is per frame, the rows concatenate (the masses of the
+        reference fragments are the same on all)"""
+        rules = ("cat",) * (3 + (link is not None) + 2 * bool(per_atom)) + (("cat", "first") if com else ())
+        return self._sharded("fragment_stats", packed, _span(frame_range, packed.n_frames), "frame_range", rules, cutoff,
+                             copy_frames=True, link=link, ref_label=ref_label, kinds=kinds, max_size=max_size, per_atom=per_atom, com=com)
 
     def pore_field(self, packed, radii, grid, dr, dmax, thresholds=(), frame_range=None, per_point=False):
         """frames sharded over the devices as ``cn_count``'s: every output is per frame, the rows concatenate"""

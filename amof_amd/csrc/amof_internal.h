@@ -102,6 +102,9 @@ struct amof_ctx {
     double surface_stats[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     // of the last amof_ring_stats: sources, candidates searched, candidates that closed a ring (amof_ring_search_stats)
     double ring_stats[3] = {0.0, 0.0, 0.0};
+    // of the last amof_fragment_stats: frames labelled, labelling rounds summed over them, the most rounds of one frame
+    // (amof_fragment_round_stats)
+    double fragment_stats[3] = {0.0, 0.0, 0.0};
 };
 
 namespace amof {
@@ -594,5 +597,30 @@ __device__ __forceinline__ double norm2(double dx, double dy, double dz)
 {
     return fma(dz, dz, fma(dy, dy, dx * dx));
 }
+
+// first frame that met a refusal: *flag = 1 + frame unless a smaller one stands there (bounded: the value only falls)
+__device__ __forceinline__ void flag_frame(int32_t *flag, int f)
+{
+    int old = *flag;
+    while (old == 0 || old > f + 1) {
+        const int seen = atomicCAS(flag, old, f + 1);
+        if (seen == old) break;
+        old = seen;
+    }
+}
+
+// ------------------------------------------------------------- bond rows --
+// The sorted neighbour rows of the bond graph of frames [f0, f0 + nf) (ring.hip, ring_adjacency_kernel): adj [nf][N][16]
+// (-1 behind the neighbours), deg [nf][N]; *flag: flag_frame of the first frame with a 17th neighbour.  amof_ring_stats and
+// amof_fragment_stats take their rows from this one launch.
+struct BondRows {
+    const double *pos;          // [F][N][3] of the call
+    const double *geom;
+    const int32_t *species;     // [N]
+    const double *cutoff;       // [S][S]
+    int32_t *adj, *deg, *flag;
+    int32_t N, S, n_cells, f0, nf;
+};
+int launch_bond_rows(amof_ctx *ctx, const BondRows &rows, bool ortho);
 
 }  // namespace amof

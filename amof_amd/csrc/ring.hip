@@ -5,6 +5,7 @@
 //   ring_adjacency_kernel   a centre per thread against partner tiles of 256 atoms through LDS: pair_base<ORTHO>, strict
 //                           sqrt(d2) < rc of the species pair (amof_cn_count's decision), the partners in atom order, so the
 //                           rows [frame][N][RING_MAX_DEGREE] come out sorted; a 17th neighbour flags the frame
+//                           (launch_bond_rows, amof_internal.h: fragment.hip takes its rows from the same kernel)
 //   ring_bfs_kernel         a wave per (frame, source): visited bitmap and ONE queue in LDS (the two frontiers are two ranges of
 //                           it), levels <= K = nmax / 2 into the source's row of the u8 table D[frame][N][N] (preset to 255).
 //                           Then the wave walks the nodes it reached and counts (pass 0) or writes (pass 1) the source's
@@ -65,19 +66,8 @@ struct RingArgs {
     int32_t N, S, n_cells, f0, nf, nmax, K, cap;
 };
 
-// first frame that met a refusal: flags[which] = 1 + frame unless a smaller one stands there (bounded: the value only falls)
-__device__ __forceinline__ void flag_frame(int32_t *flag, int f)
-{
-    int old = *flag;
-    while (old == 0 || old > f + 1) {
-        const int seen = atomicCAS(flag, old, f + 1);
-        if (seen == old) break;
-        old = seen;
-    }
-}
-
 template <bool ORTHO>
-__global__ __launch_bounds__(RA_THREADS) void ring_adjacency_kernel(RingArgs a)
+__global__ __launch_bounds__(RA_THREADS) void ring_adjacency_kernel(BondRows a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char ra_smem[];
     double *rc = reinterpret_cast<double *>(ra_smem);               // [S][S]
@@ -119,8 +109,22 @@ __global__ __launch_bounds__(RA_THREADS) void ring_adjacency_kernel(RingArgs a)
     if (!has) return;
     for (int q = cnt; q < RING_MAX_DEGREE; q++) row[q] = -1;
     a.deg[(size_t)fb * a.N + ii] = min(cnt, RING_MAX_DEGREE);
-    if (cnt > RING_MAX_DEGREE) flag_frame(&a.flags[0], f);
+    if (cnt > RING_MAX_DEGREE) flag_frame(a.flag, f);
 }
+
+}  // namespace
+
+// the rows of frames [f0, f0 + nf) of a call, for amof_ring_stats and amof_fragment_stats (fragment.hip): the SAME kernel
+int launch_bond_rows(amof_ctx *ctx, const BondRows &rows, bool ortho)
+{
+    AMOF_HIP_TRY(ctx, with_flag(ortho, [&](auto O) {
+        return launch_lds(ring_adjacency_kernel<O()>, dim3((unsigned)((rows.N + RA_THREADS - 1) / RA_THREADS), (unsigned)rows.nf), dim3(RA_THREADS),
+                          (size_t)rows.S * rows.S * sizeof(double), ctx->stream, rows);
+    }));
+    return AMOF_OK;
+}
+
+namespace {
 
 // LDS of ring_bfs_kernel: 4 counters, the visited bitmap, the queue
 __host__ __device__ inline size_t bfs_bitmap_words(int N) { return ((size_t)N + 31) / 32; }
@@ -410,10 +414,8 @@ int ring_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, int32_t nm
         int32_t flags[2];
         // ---- adjacency ----
         spans.begin(0);
-        AMOF_HIP_TRY(ctx, with_flag(geom.all_ortho, [&](auto O) {
-            return launch_lds(ring_adjacency_kernel<O()>, dim3((unsigned)((N + RA_THREADS - 1) / RA_THREADS), (unsigned)nf), dim3(RA_THREADS),
-                              (size_t)S * S * sizeof(double), ctx->stream, a);
-        }));
+        AMOF_TRY(launch_bond_rows(ctx, BondRows{a.pos, a.geom, a.species, a.cutoff, a.adj, a.deg, &a.flags[0], a.N, a.S, a.n_cells, a.f0, nf},
+                                  geom.all_ortho));
         spans.end();
         AMOF_TRY(fetch(ctx, flags, a.flags, sizeof flags));
         if (flags[0])

@@ -128,6 +128,8 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
  * after amof_ring_stats: 2 the adjacency rows, 3 the breadth-first searches (distance table, candidates), 4 the ring search.
+ * after amof_fragment_stats: 2 the adjacency rows (the link rows included), 3 the labelling (bond images and rounds), 4 the
+ *   reduction with the census.
  * after amof_pore_field: 2 the cell sort (0 on "pore_exact"), 3 the field kernels.
  * after amof_pore_access / amof_pore_access_field: 4 the labelling (amof_pore_access: 2 and 3 as amof_pore_field).
  * after amof_pore_psd / amof_pore_psd_field: 5 the covering stage (2 .. 4 as amof_pore_access where those stages ran).
@@ -169,6 +171,9 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        neighbours; also AMOF_ORDER_EXACT=1)
  *   ring statistics "ring_wave" (a wave per source: level row and path stacks in LDS, a candidate per lane), "ring_simple" (a
  *        thread per source, private stacks, no LDS, no candidate buffer; AMOF_RING_SIMPLE=1)
+ *   fragments "fragment_frame" (a workgroup per frame, both generations of the label / shift records in LDS, a round per
+ *        barrier), "fragment_global" (a launch per round over the atoms of the batch, the records in device memory:
+ *        AMOF_FRAGMENT_GLOBAL=1, or 16 N bytes of records beyond the LDS of a CU)
  *   pore field "pore_brick" (bricks of grid points against a cell list, float32 candidates, the near-minimal atoms
  *        re-evaluated in canonical float64), "pore_exact" (every atom per grid point in canonical float64: open axes,
  *        bricks too coarse for the cutoff or too full; also AMOF_PORE_EXACT=1)
@@ -502,6 +507,63 @@ int amof_ring_stats(amof_ctx *ctx, const amof_traj *traj, const double *cutoff /
                     uint32_t *per_atom /* host [F][N][max_size + 1] or NULL */,
                     int32_t *neighbours /* host [F][N][1 + 16] or NULL */);
 int amof_ring_search_stats(const amof_ctx *ctx, double *out /* [3] */);
+
+/*
+ * Fragments: the connected components of a bond graph under periodic boundaries, per frame, and what makes them whole.
+ * Replaces the search underneath the reference's building-unit reduction (amof/coordination/reduce.py, core.py and
+ * ReducedTrajectory in amof/trajectory.py: pymatgen neighbour lists and networkx components, one frame at a time); its
+ * MOF-specific chemistry (zif.py) is not restated.
+ *   Bond graph G: amof_ring_stats' -- i != j bonded iff sqrt(d2) < cutoff[species i][species j] on the canonical minimum
+ *   image (strict; symmetric matrix; 0 = never bonded), cutoffs above half the smallest perpendicular cell height refused.
+ *   Fragment: a connected component of G.  Its ROOT is its smallest atom index; label[i] = the root of i's fragment.
+ *   Shift: shift[i] in Z^3 with shift[root] = 0 and, along a bond i-j, shift[j] = shift[i] + s_ij, where s_ij = -n_ij and
+ *   n_ij = rint((r_j - r_i) C^-1) is the lattice vector the canonical minimum image subtracts (the same products, fma order
+ *   and rint: amof_amd/csrc/fragment_math.h), so that r_j + shift[j] C is the image bonded to r_i + shift[i] C.
+ *   Winding: a fragment WINDS iff a bond of it violates that relation for the shifts found; it is then periodic and has no
+ *   centre.  The shifts of a fragment that does not wind do not depend on the path; those of a winding one are whatever the
+ *   relabelling rounds left (the same on both kernels) and mean nothing.
+ *   Centre of mass: sum m_i (r_i + shift[i] C) / sum m_i, not wrapped into the cell; int64 fixed-point sums at scale 2^40
+ *   per u A (two words per component), so the summation order does not matter.  Accepted: 0 < m_i < 512 u (AMOF_EINVAL
+ *   otherwise), |coordinate of a whole fragment's atom| < 65536 A (AMOF_ECAPACITY naming the frame).  For a fragment of n
+ *   atoms, mass M and largest atomic mass mmax whose atoms pass through magnitudes of at most X A:
+ *   |centre - exact| <= n (2^-41 + mmax X 2^-53) / M + 5 X 2^-53 A (derivation: fragment_math.h).
+ *   Link bonds (optional): a second matrix `link`, the same decision; it must not name a species pair `cutoff` names
+ *   (AMOF_EINVAL).  Link bonds never join fragments; they are counted between them.
+ *   ref_label (optional) [N]: a partition by roots (ref_label[i] = the smallest atom of i's class; AMOF_EINVAL otherwise),
+ *   e.g. the labels of a reference frame.  kinds (optional) [K][S]: species-count vectors; a fragment is OF KIND k iff its
+ *   species counts equal kinds[k] (the first such k), of kind K otherwise.
+ *   Outputs, over the frames of the call:
+ *     summary int64 [F][5]: fragments, atoms of the largest, winding fragments, atoms with label != ref_label (-1 without
+ *       ref_label), link bonds (unordered) whose two ends lie in one fragment (0 without link)
+ *     size_hist int64 [F][max_size + 2]: fragments by atom count 0 .. max_size; the last bin: larger ones
+ *     census int64 [F][K + 1]: fragments per kind; the last column: all others
+ *     links (optional) int64 [F][K + 1][K + 1]: ORDERED link bonds i -> j with label[i] != label[j], by the kind of i's
+ *       fragment and the kind of j's (every bond is counted once from each end; bonds, not distinct partner fragments)
+ *     label (optional) int32 [F][N], shift (optional) int32 [F][N][3]
+ *     com (optional, needs ref_label) f64 [F][M][3], frag_mass (optional, needs ref_label) f64 [M]: M = the number of
+ *       distinct roots of ref_label (the caller passes it; checked), row k = the k-th smallest root; frag_mass in ascending
+ *       atom order.  A frame whose partition differs from ref_label (summary column 3 != 0) has NaN rows, and so has a
+ *       fragment that winds.
+ *   Capacities (AMOF_ECAPACITY, the message names the limit and the first frame; nothing is truncated silently): N <= 65535,
+ *   at most 16 neighbours per atom (cutoff and link rows alike), a bond's image within 127 cells, a shift within 32767.
+ *   Every output is independent per frame: frame ranges concatenate bit for bit, and nothing depends on the batching
+ *   (AMOF_FRAGMENT_BATCH_MB=n caps the rows, records and scratch of a batch of frames, default 256; 0: one frame per batch) or
+ *   the path ("fragment_frame"; AMOF_FRAGMENT_GLOBAL=1, or 16 N bytes beyond the LDS of a workgroup -- AMOF_FRAGMENT_LDS_KB=n
+ *   lowers that limit, for tests: "fragment_global").
+ *   amof_last_kernel_seconds: which = 2 the adjacency rows, 3 the labelling, 4 the reduction with the census.
+ *   amof_fragment_round_stats: out[3] = frames, labelling rounds summed over them (a frame's rounds: one more than the
+ *   eccentricity of the root that takes longest), the most rounds of a frame, of the last call.
+ * The outputs are overwritten (zeros after an error).  Errors: AMOF_EINVAL, AMOF_ESINGULAR, AMOF_ECAPACITY, AMOF_ENOMEM,
+ * AMOF_EHIP.
+ */
+int amof_fragment_stats(amof_ctx *ctx, const amof_traj *traj, const double *cutoff /* [S][S], symmetric */,
+                        const double *link /* [S][S] or NULL */, const int32_t *ref_label /* [N] or NULL */,
+                        const int32_t *kinds /* [K][S] or NULL */, int32_t K, int32_t max_size,
+                        int64_t *summary /* host [F][5] */, int64_t *size_hist /* host [F][max_size + 2] */,
+                        int64_t *census /* host [F][K + 1] */, int64_t *links /* host [F][K + 1][K + 1] or NULL */,
+                        int32_t *label /* host [F][N] or NULL */, int32_t *shift /* host [F][N][3] or NULL */,
+                        double *com /* host [F][M][3] or NULL */, double *frag_mass /* host [M] or NULL */, int32_t M);
+int amof_fragment_round_stats(const amof_ctx *ctx, double *out /* [3] */);
 
 /*
  * Pore geometry on a grid: the distance of every grid point to the nearest atomic surface, and from it the void
