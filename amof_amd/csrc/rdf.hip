@@ -26,6 +26,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <tuple>
 #include <type_traits>
 #include <vector>
 
@@ -877,7 +878,9 @@ template <bool ORTHO, bool CULL, bool IMG = false, bool ZFK = false, int TRI = -
 //  memory instructions of the diagonal kernel -- and the ones with near tests in the fast path ran better at four workgroups
 //  and 128 VGPRs; since their slow path reads the partner's record from LDS again and the canonical fallback of a full queue
 //  exists once per quad loop instead of eight times, all of them fit: profiles/r04/tri_experiments.txt)
-__global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastArgs fa)
+// (PLAN: six -- its centres go from global memory straight to registers, and without the centre buffers six workgroups'
+//  LDS fits a CU at the headline's histogram: tile_lds, profiles/r13/tile_six.txt)
+__global__ __launch_bounds__(FAST_THREADS, PLAN ? 6 : 5) void rdf_tile_kernel_fast(RdfFastArgs fa)
 {
     // TRI >= 0: general cells in the orthogonalised lattice frame (fast_quad_tri; TRI % 5: near tests, TRI / 5: x wrap with the y term)
     static_assert(!ZFK || (ORTHO && !IMG) || TRI >= 0, "f32 slab coordinates: diagonal cells (no image queue) or TRI");
@@ -895,7 +898,7 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
     constexpr bool REACH = ORTHO && CULL && ZFK && !IMG && TRI < 0;
     // PLAN (REACH only): a step's partner window comes from its record of fa.plan (rdf_tile_plan_kernel: the window arithmetic
     // of tile_plan.h over the quantiser's slab table, once per step instead of ballots over sampled quads in every wave), and a
-    // step without a quad to visit is not run at all: no centres staged, no barrier; a frame without a live step stages no
+    // step without a quad to visit is not run at all: no centres loaded, no barrier; a frame without a live step stages no
     // tile J, a work item without one returns at once.  Chunks of at most 16 frames (the host launches the kernel without
     // a plan otherwise): the live steps of the chunk are one 64-bit mask.
     static_assert(!PLAN || REACH, "PLAN: the slab-culled diagonal-cell kernel on f32 slab coordinates");
@@ -908,15 +911,15 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
     constexpr int HALF = TRI == 10 ? 1 : (TRI == 11 ? -1 : 0);
     const RdfArgs &a = fa.a;
     extern __shared__ __align__(16) unsigned char lds_raw[];
-    // double-buffered tiles: J (512 entries) and the centre sub-tile (128 entries)
+    // double-buffered tiles: J (512 entries) and the centre sub-tile (128 entries; none with a plan: load_c)
     // (the histogram first: bin_count forms LDS byte addresses from the candidate's bits)
     unsigned *hist = reinterpret_cast<unsigned *>(lds_raw);                  // [nbins + trash], padded to 16 bytes
     uint4 *tqb = reinterpret_cast<uint4 *>(hist + ((fa.a.nbins + FAST_TRASH + 2 + 3) & ~3));      // [2][FAST_TILE]
-    uint4 *tcb = tqb + 2 * FAST_TILE;                                        // [2][FAST_SUB]
+    uint4 *tcb = tqb + 2 * FAST_TILE;                                        // [2][FAST_SUB]; PLAN: [0]
     // IMG: queue of the pairs that need the canonical evaluation (drained densely once per step), two counters
     // (two buffers: a step parks into one while the previous step's is drained; three counters so that one can be
     // reset a whole step away from its last reader and its next writer)
-    uint2 *nq_base = reinterpret_cast<uint2 *>(tcb + 2 * FAST_SUB);                             // [2][img_queue]
+    uint2 *nq_base = reinterpret_cast<uint2 *>(tcb + (PLAN ? 0 : 2 * FAST_SUB));                // [2][img_queue]
     const unsigned nq_cap = (unsigned)fa.img_queue;
     // (the three counters behind the queue, in the dynamic LDS like everything else: the kernel has NO static LDS, so that
     //  the dynamic part starts at LDS address 0 -- bin_count)
@@ -984,6 +987,16 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
             dma_1k(Qf + ti.start + sub * FAST_SUB + min(wave * 64 + lane, cnt - 1), tcb + cb * FAST_SUB + wave * 64);
     };
 
+    // PLAN: a lane's two centres of sub-tile `sub` of frame fl from the quantised frame (resident in the XCD's L2 by the chunk
+    // mapping) straight into registers, two 16-byte loads with the indices stage_c clamps: a record is read once per step and
+    // kept for the whole step, so a copy in LDS buys nothing, and without the centre buffers a sixth workgroup fits the CU
+    auto load_c = [&](int fl, int sub, uint4 &ra, uint4 &rb) {
+        const uint4 *__restrict__ Qc = reinterpret_cast<const uint4 *>(fa.Q + (size_t)fl * (size_t)a.N + ti.start + sub * FAST_SUB);
+        const int cnt = min(FAST_SUB, ti.count - sub * FAST_SUB);
+        ra = Qc[min(la, cnt - 1)];
+        rb = Qc[min(lb, cnt - 1)];
+    };
+
     // PLAN: bit 4 (fl - f0) + sub of `live` = that step is still to run; the records of this work item's chunk
     // (read through the constant address space, so that a step's record arrives by one scalar load that the step before
     //  issued: as an ordinary load it is a vector load, a wait and three v_readfirstlane behind every barrier)
@@ -1014,7 +1027,10 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
         fl = f0 + (bit >> 2); sub = bit & 3;
         rec_next = plan_c[bit];
     }
-    if (nsteps > 0) { stage_j(fl, 0); stage_c(fl, sub, 0); }
+    if (nsteps > 0) {
+        stage_j(fl, 0);
+        if constexpr (!PLAN) stage_c(fl, sub, 0);
+    }
     float sc[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     double sc64r[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     TriConst trc = {0.0f, 0.0f, 0.0f, 0.0f, 0u, 0u};
@@ -1033,7 +1049,7 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
         const bool has_a = la < cnti, has_b = lb < cnti;
         const int f = fa.f_base + fl;
         const double *__restrict__ p = a.pos + (size_t)f * (size_t)a.N * 3;
-        const uint4 *tq = tqb + jb * FAST_TILE, *tc = tcb + cbuf * FAST_SUB;
+        const uint4 *tq = tqb + jb * FAST_TILE, *tc = tcb + (PLAN ? 0 : cbuf * FAST_SUB);
         const int gi = a.n_cells == 1 ? 0 : f;
         const FrameScale *__restrict__ fs = fa.fs + gi;
         const double *__restrict__ g = a.geom + (size_t)gi * GEOM_STRIDE;
@@ -1069,8 +1085,12 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
             }
         }
         const double *sc64 = (ORTHO || TRI >= 0) ? sc64r : fs->sc64;
+        uint4 ca, cb;
         if constexpr (PLAN) {      // (the next step's record: its latency passes in the wait below)
             if (rest) rec_next = plan_c[bit_next];
+            // this step's centres likewise: no register is held across the quad loops for them (issued behind the last
+            // quad loop of the step before, they were 0.25 ms slower: profiles/r13/tile_six.txt)
+            load_c(fl, sub, ca, cb);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA for this step has landed
         __syncthreads();                                    // everyone's has; the previous step is fully consumed
@@ -1091,7 +1111,6 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
         uint2 *nq = nq_base + (fa.img_defer ? (size_t)(step & 1) * nq_cap : 0);
         // what the next step needs streams in behind the arithmetic
         if constexpr (PLAN) {
-            if (rest) stage_c(f0 + (bit_next >> 2), bit_next & 3, cbuf ^ 1);
             // the next frame with a live step (buffer jb^1: the frame before this one, consumed before this barrier)
             const unsigned long long later = rest & ~(0xfull << (4 * (fl - f0)));
             if (new_frame && later) stage_j(f0 + ((__ffsll((long long)later) - 1) >> 2), jb ^ 1);
@@ -1101,7 +1120,7 @@ __global__ __launch_bounds__(FAST_THREADS, 5) void rdf_tile_kernel_fast(RdfFastA
             if (step + 1 < nsteps) stage_c(fl_next, nsub_next, cbuf ^ 1);
             if (sub == 0 && fl + 1 < f1) stage_j(fl + 1, jb ^ 1);   // (buffer jb^1: frame fl-1, consumed before this barrier)
         }
-        const uint4 ca = tc[min(la, cnti - 1)], cb = tc[min(lb, cnti - 1)];
+        if constexpr (!PLAN) { ca = tc[min(la, cnti - 1)]; cb = tc[min(lb, cnti - 1)]; }
         const uint32_t uax = ca.x, uay = ca.y, uaz = ca.z, ida = ca.w;
         const uint32_t ubx = cb.x, uby = cb.y, ubz = cb.z, idb = cb.w;
         // Partner index range(s) to visit.  Tile J is slab-sorted along the stored .z axis, so
@@ -2367,7 +2386,28 @@ static hipError_t rdf_tile_launch(RdfCall &c, const RdfFastArgs &k, dim3 grid, s
 {
     const RdfSelect &sel = c.sel;
     const bool ortho = c.geom.all_ortho, cull = sel.cull;
-    auto launch = [&](auto kern) { return launch_lds<true>(kern, grid, dim3(FAST_THREADS), lds, c.ctx->stream, k); };
+    auto launch = [&](auto kern) {
+        const hipError_t e = launch_lds<true>(kern, grid, dim3(FAST_THREADS), lds, c.ctx->stream, k);
+        if (e != hipSuccess) return e;
+        // what the hardware grants: workgroups per CU of this variant at this LDS size, asked once per (variant, size,
+        // device); the planned kernels are built for six at the headline, and nothing depends on the answer
+        static std::mutex mu;
+        static std::map<std::tuple<const void *, size_t, int>, int> granted;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError();
+        std::lock_guard<std::mutex> lock(mu);
+        const auto key = std::make_tuple((const void *)kern, lds, dev);
+        if (!granted.count(key)) {
+            int n = 0;
+            const hipError_t eo = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, FAST_THREADS, lds);
+            if (eo != hipSuccess) return eo;
+            granted[key] = n;
+            if (c.sw.debug)
+                fprintf(stderr, "rdf_tile: %s%s%d bins, %zu bytes of LDS: %d workgroups per CU\n", plan ? "plan, " : "",
+                        plan && !c.sw.noahead ? "read-ahead, " : "", c.nbins, lds, n);
+        }
+        return hipSuccess;
+    };
     if (sel.tri.ok)
         return with_flag(cull, [&](auto C) {
             return with_count<12>(sel.tri.code, [&](auto K) { return launch(rdf_tile_kernel_fast<false, C(), false, true, K()>); });
@@ -2413,7 +2453,6 @@ static int rdf_tile_tier(RdfCall &c)
         k.nb_hi = sel.zf_thr.nb_hi;
         k.half_m_guard = sel.zf_thr.half_m_guard;
     }
-    const size_t lds = tile_lds(nbins, k.img_queue, k.img_defer);
     // rdf_tile_zf with slab culling runs from a plan of its steps (rdf_tile_kernel_fast, PLAN): the quantiser writes
     // its slab table, rdf_tile_plan_kernel the records.  Not for tables beyond the plan kernel's LDS or plans beyond
     // 256 MiB (systems far larger than a tile kernel's share).
@@ -2457,7 +2496,8 @@ static int rdf_tile_tier(RdfCall &c)
             k.plan = (const uint4 *)d_plan;
         }
         if (launches == 0) timing_dom_begin(ctx, tri ? "rdf_tile_tri" : sel.img ? "rdf_tile_img" : sel.zf ? "rdf_tile_zf" : "rdf_tile");
-        AMOF_HIP_TRY(ctx, rdf_tile_launch(c, k, grid, lds, plan));
+        // (a batch without a plan runs the kernel with centre buffers, at their size)
+        AMOF_HIP_TRY(ctx, rdf_tile_launch(c, k, grid, tile_lds(nbins, k.img_queue, k.img_defer, plan), plan));
         launches++;
     }
     timing_dom_end(ctx, launches);

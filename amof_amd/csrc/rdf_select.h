@@ -32,7 +32,7 @@ struct RdfSwitches {
     bool force_img = false;     // AMOF_RDF_FORCE_IMG (set): the image-aware variant on a plain case, never TRI
     bool notri = false;         // AMOF_RDF_NOTRI (set): never the general-cell variant in the orthogonalised frame
     bool nohalf = false;        // AMOF_RDF_NOHALF (set): TRI never with the exact-half x wrap (codes 10 / 11)
-    bool debug = false;         // AMOF_RDF_DEBUG (set): the TRI selection on stderr
+    bool debug = false;         // AMOF_RDF_DEBUG (set): the TRI selection and the tile kernel's granted workgroups per CU on stderr
     bool nocull = false;        // AMOF_RDF_NOCULL=1: tile kernels without slab culling
     bool nozf = false;          // AMOF_RDF_NOZF=1: diagonal cells without the f32 slab coordinates
     bool noreach = false;       // AMOF_RDF_NOREACH=1: every quad of a diagonal tile pair masked (rdf_tile_kernel_fast, REACH)
@@ -171,9 +171,11 @@ inline ParkedQueue parked_queue(double share)
     return q;
 }
 // dynamic LDS of the tile kernel: two partner tiles and centre sub-tiles, the histogram with its trash words, the queues
-inline size_t tile_lds(int nbins, int32_t queue, int32_t defer)
+// plan: a planned launch (rdf_tile_kernel_fast, PLAN) has no centre buffers -- 25 760 bytes at the headline's 2310 bins, six
+// workgroups in a CU's 160 KiB where 29 856 allow five
+inline size_t tile_lds(int nbins, int32_t queue, int32_t defer, bool plan = false)
 {
-    const size_t base = 2 * (FAST_TILE + FAST_SUB) * 16 + (size_t)((nbins + FAST_TRASH + 2 + 3) & ~3) * sizeof(unsigned);
+    const size_t base = 2 * (FAST_TILE + (plan ? 0 : FAST_SUB)) * 16 + (size_t)((nbins + FAST_TRASH + 2 + 3) & ~3) * sizeof(unsigned);
     return queue ? base + (defer ? 2 : 1) * (size_t)queue * 8 + 16 : base;
 }
 
