@@ -22,6 +22,8 @@ Analyses beyond the reference:
     amof_amd.bond_lifetime.BondLifetime           bond survival correlations C(t), S(t) for CoordinationNumber's sets
     amof_amd.bond_reorientation.BondReorientation reorientational correlations C1(t), C2(t) of the same sets' bond vectors
     amof_amd.bond_order.BondOrder                 Steinhardt q_l and tetrahedral order parameter of the same sets' shells
+    amof_amd.dihedral.Dihedral                    torsion-angle distributions of chains a-b-c-d of bonded atoms (also
+                                                  ``amof_amd.Dihedral``)
     amof_amd.pore.Pore                            void fraction, cavity-size histogram and largest included sphere on a grid
                                                   (the reference's Pore wraps the external Zeo++ binary: not its numbers)
 
@@ -32,3 +34,11 @@ ABI of ``include/amof_hip.h``; there is no CPU fallback.
 __version__ = "0.1.0"
 
 from .frames import Frame, PackedTrajectory, pack_trajectory  # noqa: F401
+
+
+def __getattr__(name):
+    # (on first use: the analysis modules import pandas)
+    if name == "Dihedral":
+        from .dihedral import Dihedral
+        return Dihedral
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

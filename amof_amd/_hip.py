@@ -38,7 +38,7 @@ EXPORTS = [
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
-    "amof_bond_order", "amof_bond_order_dev", "amof_ring_stats", "amof_ring_search_stats", "amof_fragment_stats", "amof_fragment_round_stats",
+    "amof_bond_order", "amof_bond_order_dev", "amof_dihedral_hist", "amof_dihedral_hist_dev", "amof_ring_stats", "amof_ring_search_stats", "amof_fragment_stats", "amof_fragment_round_stats",
     "amof_pore_field", "amof_pore_candidate_bound",
     "amof_pore_access", "amof_pore_access_field", "amof_pore_psd", "amof_pore_psd_field", "amof_pore_cover_stats",
     "amof_pore_surface", "amof_pore_surface_bound", "amof_pore_surface_stats",
@@ -149,6 +149,8 @@ def load_library():
         lib.amof_bond_reorientation_dev.argtypes = lib.amof_bond_reorientation.argtypes
         lib.amof_bond_order.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P]
         lib.amof_bond_order_dev.argtypes = lib.amof_bond_order.argtypes
+        lib.amof_dihedral_hist.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, P, P, P, P]
+        lib.amof_dihedral_hist_dev.argtypes = lib.amof_dihedral_hist.argtypes
         lib.amof_ring_stats.argtypes = [P, TP, P, ctypes.c_int32, P, P, P, P]
         lib.amof_ring_search_stats.argtypes = [P, P]
         lib.amof_fragment_stats.argtypes = [P, TP, P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P, P, P, P, P, P, ctypes.c_int32]
@@ -860,6 +862,37 @@ class Context(Lane):
         return (hist, hist_tet, sums, pa) if per_atom else (hist, hist_tet, sums)
 
     @_locked
+    def dihedral_hist(self, packed, cutoff, chains, edges, frame_range=None, out=None):
+        """``(hist u64 [T][nb], n_dihedrals u64 [T], n_undefined u64 [T], frame_sums int64 [F][T][3])`` of
+        ``amof_dihedral_hist``: the folded torsion angle (0 .. 180 degrees) of every chain a-b-c-d of bonded atoms whose
+        species match a pattern of ``chains`` (``[T][4]`` species indices, -1: any; a chain counts once per pattern, in
+        whichever direction it matches), binned with ``edges`` as ``bad_hist`` bins its angles; per frame and pattern the
+        defined chains, the undefined ones (a bond angle within about 1e-6 rad of straight) and the sum of
+        ``llrint(cos(phi) 2^40)`` (include/amof_hip.h).  ``cutoff``: the symmetric matrix ``[S][S]`` as ``ring_stats``'.
+
+        ``out``: optional triple of torch CUDA int64 tensors ``([T][nb], [T], [T])`` the counts are ADDED into on the
+        device (they stay resident for an RCCL merge); they are returned in place of the arrays."""
+        th = self._traj(packed, frame_range)
+        cutoff = _cutoff(cutoff, th.S)
+        chains = _i32(chains).reshape(-1, 4)
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        T, nb = len(chains), len(edges) - 1
+        sums = np.zeros((th.n_frames, T, 3), dtype=np.int64)
+        if out is not None:
+            hist, n_def, n_undef = out
+            for x, n in ((hist, T * nb), (n_def, T), (n_undef, T)):
+                self._check_out(x, n)
+            self._order_after_torch()
+            fn = self._lib.amof_dihedral_hist_dev
+        else:
+            hist = np.zeros((T, nb), dtype=np.uint64)
+            n_def, n_undef = np.zeros(T, dtype=np.uint64), np.zeros(T, dtype=np.uint64)
+            fn = self._lib.amof_dihedral_hist
+        self._check(fn(self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(chains), T, _ptr(edges), nb, _ptr(hist), _ptr(n_def),
+                       _ptr(n_undef), _ptr(sums)))
+        return hist, n_def, n_undef, sums
+
+    @_locked
     def ring_stats(self, packed, cutoff, max_size=32, frame_range=None, per_atom=False, neighbours=False):
         """``(counts int64 [F][4][max_size + 1], truncated int64 [F] [, per_atom u32 [F][N][max_size + 1]] [, neighbours int32
         [F][N][17]])`` of ``amof_ring_stats``: the primitive rings of up to ``max_size`` (3 .. 32) nodes of the bond graph of
@@ -1163,7 +1196,8 @@ class Context(Lane):
         """``{"rho", "corr", "self"}``: kernel seconds of the stages of the last ``isf_accumulate`` (amof_last_kernel_seconds
         2 .. 4; negative: the last call was not one).  After ``bond_survival`` the same three slots hold the bond lists, the
         bit series and the correlations; after ``bond_reorientation`` the bond lists, the bit series, and the vector table
-        with the reorientation sums; after ``bond_order`` the list stage and the order kernels (the third is 0).  After the Pore
+        with the reorientation sums; after ``bond_order`` the list stage and the order kernels, after ``dihedral_hist`` the
+        list stage (or the adjacency rows) and the dihedral kernels (the third is 0).  After the Pore
         calls the three slots hold the cell sort, the field kernels and the labelling; ``pore=True`` adds ``"cover"``, the covering
         stage, and ``"surface"``, the surface stage (amof_last_kernel_seconds 5 and 6)."""
         self.drain()
@@ -1330,6 +1364,12 @@ class MultiContext(object):
         return self._sharded("bond_order", packed, _span(frame_range, packed.n_frames), "frame_range",
                              ("sum", "sum", "cat", "cat")[:3 + bool(per_atom)], cutoff, sets, l, nbins, nbins_tet,
                              copy_frames=True, per_atom=per_atom)
+
+    def dihedral_hist(self, packed, cutoff, chains, edges, frame_range=None, out=None):
+        """frames sharded over the devices as ``cn_count``'s: the rows concatenate, the counts add up exactly"""
+        assert out is None, "device-resident accumulation is a single-context feature"
+        return self._sharded("dihedral_hist", packed, _span(frame_range, packed.n_frames), "frame_range",
+                             ("sum", "sum", "sum", "cat"), cutoff, chains, edges, copy_frames=True)
 
     def ring_stats(self, packed, cutoff, max_size=32, frame_range=None, per_atom=False, neighbours=False):
         """frames sharded over the devices as ``cn_count``'s: every output is per frame, the rows concatenate"""

@@ -127,6 +127,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations;
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
+ * after amof_dihedral_hist[_dev]: 2 the list stage (the adjacency rows on "dihedral_exact"), 3 the dihedral kernels.
  * after amof_ring_stats: 2 the adjacency rows, 3 the breadth-first searches (distance table, candidates), 4 the ring search.
  * after amof_fragment_stats: 2 the adjacency rows (the link rows included), 3 the labelling (bond images and rounds), 4 the
  *   reduction with the census.
@@ -467,6 +468,53 @@ int amof_bond_order_dev(amof_ctx *ctx, const amof_traj *traj, const double *cuto
                         uint64_t *hist_dev /* device [n_sets][n_l][nbins], += */,
                         uint64_t *hist_tet_dev /* device [n_sets][nbins_tet], += */, int64_t *frame_sums /* host */,
                         int64_t *per_atom /* host or NULL */);
+
+/*
+ * Dihedral (torsion) angle distributions of chains a-b-c-d of bonded atoms.
+ * Replaces nothing in the reference (its static analyses stop at three bodies: amof/rdf.py, amof/bad.py); the angle AROUND a
+ * bond is what the rotation of a linker about its Zn-N bond, the planarity of a ring and the conformation of a chain are.
+ *   Bond graph: i != j are bonded iff j is a neighbour of i by amof_cn_count's decision -- the canonical minimum image, strict
+ *   sqrt(d2) < rc with rc = cutoff[species i][species j] (symmetric; 0 = never bonded): the graph of amof_ring_stats, whatever
+ *   the patterns name.  As amof_bond_order, a cutoff above half the smallest perpendicular cell height on a periodic axis is
+ *   refused (AMOF_EINVAL): a neighbour is one image.  An atom with more than 16 neighbours returns AMOF_ECAPACITY (the message
+ *   names the frame), a bonded pair of coincident atoms AMOF_EANGLE (as amof_bad_hist).
+ *   Chains: an unordered central bond {b, c}, a neighbour a of b and a neighbour d of c, with a != c, d != b and a != d BY ATOM
+ *   INDEX (the quotient-graph convention of amof_ring_stats: three-membered rings are dropped, and so is a chain that returns
+ *   to an image of its first atom around a small cell).  Every chain is visited once, from the end with b < c.
+ *   chains[t] = (A, B, C, D), species indices, -1 = any.  A chain counts ONCE for pattern t iff the pattern matches its species
+ *   read as a-b-c-d or as d-c-b-a: A-B-C-D and D-C-B-A give the same column, palindromes and wildcards never count twice.
+ *   1 <= n_chains <= 32.
+ *   Angle: with the canonical unit vectors u1 = u(b -> a), u2 = u(b -> c), u3 = u(c -> d) -- v / sqrt(vx vx + vy vy + vz vz) of
+ *   the canonical minimum-image vectors, as BAD; u(c -> b) == -u(b -> c) exactly -- in float64, no fma, in this order:
+ *     n1 = u2 x u1,  n2 = u2 x u3        x = (u2y * wz) - (u2z * wy),  y = (u2z * wx) - (u2x * wz),  z = (u2x * wy) - (u2y * wx)
+ *     s1 = (n1x*n1x + n1y*n1y) + n1z*n1z,  s2 = (n2x*n2x + n2y*n2y) + n2z*n2z
+ *     s1 < 2^-40 or s2 < 2^-40: the chain is UNDEFINED (a bond angle within about 1e-6 rad of straight): counted, not binned
+ *     c = ((n1x*n2x + n1y*n2y) + n1z*n2z) / sqrt(s1 * s2), clipped to [-1, 1]
+ *     phi = (180 / pi) * acos(c) in [0, 180], acos being the fixed algorithm of amof_bad_hist (fdlibm's)
+ *   The sign of the torsion is folded away (0: cis, 180: trans).
+ *   Bins: edges[nb + 1], strictly increasing, used as amof_bad_hist's: bin k holds edges[k] <= phi < edges[k + 1], the last
+ *   bin is right-closed.
+ *   Outputs, over the frames of the call, all integers:
+ *     hist [n_chains][nb]; n_dihedrals [n_chains]: the defined chains; n_undefined [n_chains]
+ *     frame_sums int64 [F][n_chains][3]: the defined chains, the undefined chains, sum of llrint(c * 2^40) over the defined ones
+ *       (<cos phi> of a frame and pattern = [2] / 2^40 / [0])
+ *   Frame ranges concatenate / add up bit for bit, and nothing depends on launch geometry, batching or the path
+ *   ("dihedral_frame": the neighbour rows of BAD's frame tier with the partner's index in every entry; "dihedral_exact": index
+ *   rows of amof_ring_stats' adjacency kernel, the unit vectors recomputed, any cell; AMOF_DIHEDRAL_EXACT=1 forces it;
+ *   AMOF_DIHEDRAL_ROWS_MB=n caps the scratch of the neighbour rows -- more, smaller frame batches; 0: one frame per batch).
+ *   amof_last_kernel_seconds: which = 2 the list stage (the adjacency rows on "dihedral_exact"), 3 the dihedral kernels.
+ * The host form overwrites hist, n_dihedrals, n_undefined and frame_sums (zeros after an error).  The _dev form ADDS hist,
+ * n_dihedrals and n_undefined into device buffers (frame-sharded ranks all-reduce them next); frame_sums stays a host buffer.
+ * Errors: AMOF_EINVAL, AMOF_EANGLE, AMOF_ECAPACITY, AMOF_ESINGULAR, AMOF_ENOMEM, AMOF_EHIP.
+ */
+int amof_dihedral_hist(amof_ctx *ctx, const amof_traj *traj, const double *cutoff /* [S][S], symmetric */,
+                       const int32_t *chains /* [n_chains][4] */, int32_t n_chains, const double *edges /* host [nb + 1] */,
+                       int32_t nb, uint64_t *hist /* host [n_chains][nb] */, uint64_t *n_dihedrals /* host [n_chains] */,
+                       uint64_t *n_undefined /* host [n_chains] */, int64_t *frame_sums /* host [F][n_chains][3] */);
+int amof_dihedral_hist_dev(amof_ctx *ctx, const amof_traj *traj, const double *cutoff, const int32_t *chains, int32_t n_chains,
+                           const double *edges, int32_t nb, uint64_t *hist_dev /* device [n_chains][nb], += */,
+                           uint64_t *n_dihedrals_dev /* device [n_chains], += */,
+                           uint64_t *n_undefined_dev /* device [n_chains], += */, int64_t *frame_sums /* host */);
 
 /*
  * Primitive ring statistics of the bond network, per frame.
