@@ -834,8 +834,14 @@ int amof_pore_surface_stats(const amof_ctx *ctx, double *out5 /* host [5] */);
  *     rho_a = sum over the atoms j of species a of exp(2 pi i phi_j / 2^32), phi_j = h ux_j + k uy_j + l uz_j (mod 2^32)
  *       with u = the atom's fractional coordinates * 2^32, folded into the cell (the fast paths' quantisation): the
  *       phase is exact for any cell and for unwrapped input; one f32 v_sin / v_cos per term, f32 partials over <= 64
- *       atoms folded into f64 (the tests hold every S column within 1e-5 max(1, |S|) of a float64 restatement; no
- *       separate ulp measurement of v_sin / v_cos was made).
+ *       atoms folded into f64 (the tests hold every S column within 1e-5 max(1, |S|) of a float64 restatement).
+ *       Measured on the MI355X against the exact phase (tests/test_gpu_sq_accuracy.py: test_single_terms), the error of
+ *       one term, int-to-float conversion included, is at most 2.980 x 2^-24 for cos and 2.931 x 2^-24 for sin over
+ *       2 x 262 144 swept phases, and 1.017 / 0.814 x 2^-24 over 2 x 128 planted ones (powers of two and their
+ *       neighbours, eighths of a revolution, +-1/2); the tests' constant is TERM_ERR = 2^-21, the smallest power of
+ *       two at least twice the largest.  rho_a then lies within n TERM_ERR + acc(n) of the exact sum per component, n
+ *       the atoms of the species and acc(n) = 2^-24 sum over the partials of (m (m + 1) / 2 - 1), m <= 64 their
+ *       lengths: 1.94e-6 per atom at worst, which keeps a fully coherent (Bragg) peak of S within 5e-6 |S|.
  *     counts[b] += 1;  for every unordered pair p = (a, c), a <= c, in the order (0,0), (0,1) .. (0,S-1), (1,1) ..:
  *     sums[p][b] += t_ac = Re rho_a Re rho_c + Im rho_a Im rho_c.
  *   Each t is rounded to an integer multiple of 2^-s_p and added as int64 (integer atomics: the result is independent of
