@@ -1,4 +1,4 @@
-// arccos of the angle kernels (nbr.hip: BAD, the dihedral kernels) and of the CPU driver tests/native/dihedral_driver.cpp.
+// arccos of the angle kernels (nbr.hip: BAD; dihedral.hip) and of the CPU driver tests/native/dihedral_driver.cpp.
 // numpy.arccos (what ase.geometry.get_angles calls) is a different routine on different CPUs and the device library's acos a
 // third one; they differ in the last place for a few percent of the arguments, which bins an angle that sits on a histogram
 // edge (exact lattices) differently.  Every angle here goes through ONE published algorithm instead -- fdlibm's acos:

@@ -54,6 +54,7 @@
 #include <vector>
 
 #include "amof_internal.h"
+#include "nbr_check.h"
 
 namespace amof {
 namespace {
@@ -548,10 +549,8 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
         return fail(ctx, AMOF_EINVAL, "atom range [%lld, %lld) outside [0, %lld)", (long long)atom_begin, (long long)atom_end, (long long)N);
     if (F > 0x7fffff00LL - 64) return fail(ctx, AMOF_EINVAL, "too many frames");
     for (int s = 0; s < n_sets; s++) {
-        if (sets[2 * s] < 0 || sets[2 * s] >= S || sets[2 * s + 1] < 0 || sets[2 * s + 1] >= S)
-            return fail(ctx, AMOF_EINVAL, "set %d names a species outside 0..%d", s, S - 1);
-        const double rc = cutoff[sets[2 * s] * S + sets[2 * s + 1]];
-        if (!(rc >= 0.0) || !isfinite(rc)) return fail(ctx, AMOF_EINVAL, "cutoff of set %d must be finite and not negative", s);
+        AMOF_TRY(pore_refuse(ctx, nbr_check::bond_set_species(sets, s, S)));
+        AMOF_TRY(pore_refuse(ctx, nbr_check::bond_set_cutoff(cutoff[sets[2 * s] * S + sets[2 * s + 1]], s)));
     }
     const size_t csize = (size_t)n_sets * W * 3;
     if (counts) std::fill(counts, counts + csize, (uint64_t)0);
@@ -575,16 +574,9 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
 
     HostGeom geom;
     AMOF_TRY(build_geometry(ctx, t, geom));
-    double hmin = INFINITY;         // smallest perpendicular height on a periodic axis
-    for (int64_t k = 0; k < t->n_cells; k++)
-        for (int x = 0; x < 3; x++)
-            if (t->pbc[x]) hmin = std::min(hmin, geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-    for (int s = 0; s < n_sets; s++) {
-        const double rc = cutoff[sets[2 * s] * S + sets[2 * s + 1]];
-        if (rc > 0.5 * hmin)
-            return fail(ctx, AMOF_EINVAL, "cutoff %g of set %d exceeds half the smallest cell height %g: a pair could be bonded twice",
-                        rc, s, hmin);
-    }
+    const double hmin = nbr_check::min_periodic_height(t->pbc, geom.rec.data(), t->n_cells);
+    for (int s = 0; s < n_sets; s++)
+        AMOF_TRY(pore_refuse(ctx, nbr_check::half_height_set(cutoff[sets[2 * s] * S + sets[2 * s + 1]], s, hmin, "a pair could be bonded twice")));
     HostTiles tiles;
     build_tiles(t, BL_THREADS, tiles);
     const std::vector<int64_t> &sp_first = tiles.sp_first;

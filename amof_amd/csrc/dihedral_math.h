@@ -1,5 +1,5 @@
 // Dihedral (torsion) angle of a chain a-b-c-d of bonded atoms: the arithmetic and the pattern match that both GPU kernels
-// (nbr.hip: "dihedral_frame", "dihedral_exact") and the CPU driver (tests/native/dihedral_driver.cpp) compile.  Plain scalars
+// (dihedral.hip: "dihedral_frame", "dihedral_exact") and the CPU driver (tests/native/dihedral_driver.cpp) compile.  Plain scalars
 // and pointers, no HIP types; -ffp-contract=off everywhere.  Definition: include/amof_hip.h (amof_dihedral_hist), DESIGN.md 4.3.
 //
 // Chain.  An unordered central bond {b, c}, a neighbour a of b and a neighbour d of c with a != c, d != b and a != d by atom

@@ -39,6 +39,7 @@
 
 #include "amof_internal.h"
 #include "fragment_math.h"
+#include "nbr_check.h"
 
 static_assert(FRAG_MAX_DEGREE == 16, "the rows are ring_adjacency_kernel's: RING_MAX_DEGREE");
 
@@ -276,15 +277,9 @@ int fragment_run(amof_ctx *ctx, const amof_traj *t, const FragInputs &in, const 
     const int64_t N = t->n_atoms, F = t->n_frames;
     HostGeom geom;
     AMOF_TRY(build_geometry(ctx, t, geom));
-    double hmin = INFINITY;         // smallest perpendicular height on a periodic axis
-    for (int64_t k = 0; k < t->n_cells; k++)
-        for (int x = 0; x < 3; x++)
-            if (t->pbc[x]) hmin = std::min(hmin, geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-    for (int k = 0; k < S * S; k++) {
-        const double rc = std::max(in.cutoff[k], in.link ? in.link[k] : 0.0);
-        if (rc > 0.5 * hmin)
-            return fail(ctx, AMOF_EINVAL, "cutoff %g exceeds half the smallest cell height %g: a pair could be bonded twice", rc, hmin);
-    }
+    const double hmin = nbr_check::min_periodic_height(t->pbc, geom.rec.data(), t->n_cells);
+    for (int k = 0; k < S * S; k++)
+        AMOF_TRY(pore_refuse(ctx, nbr_check::half_height(std::max(in.cutoff[k], in.link ? in.link[k] : 0.0), hmin)));
 
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     int lds_cap = 0;
@@ -479,17 +474,6 @@ int fragment_run(amof_ctx *ctx, const amof_traj *t, const FragInputs &in, const 
     return AMOF_OK;
 }
 
-int check_matrix(amof_ctx *ctx, const double *m, int S, const char *what)
-{
-    for (int x = 0; x < S; x++)
-        for (int y = 0; y < S; y++) {
-            const double rc = m[x * S + y];
-            if (!(rc >= 0.0) || !isfinite(rc)) return fail(ctx, AMOF_EINVAL, "%s must be finite and >= 0", what);
-            if (rc != m[y * S + x]) return fail(ctx, AMOF_EINVAL, "the %s matrix must be symmetric", what);
-        }
-    return AMOF_OK;
-}
-
 }  // namespace
 }  // namespace amof
 
@@ -512,9 +496,9 @@ extern "C" int amof_fragment_stats(amof_ctx *ctx, const amof_traj *t, const doub
     out.zero();     // the outputs are overwritten: zeros first, so that a failing call leaves zeros
     const int S = t->n_species;
     const int64_t N = t->n_atoms;
-    AMOF_TRY(check_matrix(ctx, cutoff, S, "cutoff"));
+    AMOF_TRY(pore_refuse(ctx, nbr_check::bond_matrix(cutoff, S, "cutoff")));
     if (link) {
-        AMOF_TRY(check_matrix(ctx, link, S, "link"));
+        AMOF_TRY(pore_refuse(ctx, nbr_check::bond_matrix(link, S, "link")));
         for (int k = 0; k < S * S; k++)
             if (link[k] > 0.0 && cutoff[k] > 0.0) return fail(ctx, AMOF_EINVAL, "a species pair is named by the cutoff and by the link matrix");
     }

@@ -9,6 +9,9 @@
 // sorted by species into tiles (as for the RDF) and a centre tile is compared
 // with the tiles of its partner species only, staged through LDS and read by
 // broadcast.  All results are integer counts (exact, order independent).
+//
+// The list stage of the frame tier (lists_frame_kernel, frame_lists_tier) also serves the bond order parameters (order.hip)
+// and the dihedrals (dihedral.hip); nbr_rows.h has what they share with this file.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -19,63 +22,13 @@
 
 #include "amof_internal.h"
 #include "angle_math.h"
-#include "dihedral_math.h"
-#include "ring_search.h"
+#include "nbr_rows.h"
 
 namespace amof {
 
+static_assert(GEOM_STRIDE == nbr_check::GEOM_REC, "min_periodic_height reads build_geometry's records");
 constexpr int CN_TILE = 256;
-constexpr int BAD_TILE = 64;
-
-struct NbrArgs {
-    const double *pos;
-    const double *geom;
-    const double *img;
-    const int32_t *nimg;
-    const int32_t *perm;
-    const Tile *tiles;
-    const int32_t *sp_first_tile;  // [S]
-    const int32_t *sp_ntiles;      // [S]
-    const double *cutoff;          // [S][S]
-    const int4 *work;              // (set/triple index, centre tile, A, B)
-    int64_t N;
-    int32_t F;
-    int32_t n_cells;
-    int32_t frames_per_chunk;
-    int32_t S;
-    int32_t max_img;
-    int32_t n_sets;
-    // CN outputs
-    unsigned long long *sums;  // [F][n_sets]
-    int32_t *per_atom;         // [F][n_sets][N] or null
-    // BAD
-    const double *edges;       // [nb+1]
-    int32_t nb;
-    unsigned long long *hist;  // [T][nb]
-    unsigned long long *n_angles;
-    int32_t *flags;            // [0] zero-length vector, [1] neighbour overflow, [2] largest neighbour count (count pass)
-    int32_t cn_max;            // > 0: histograms keyed by the centre's neighbour count (BadByCn)
-    // big-list pass of bad_kernel (centres with more than AMOF_MAX_NEIGHBOURS neighbours): the unit vectors live in
-    // global scratch, [workgroup][3][ncap][BAD_TILE] doubles, instead of LDS
-    double *nbuf;
-    int32_t ncap;
-    int32_t count_only;        // 1: only find the largest neighbour count (flags[2])
-    int32_t global_hist;       // 1: more angle bins than LDS holds -- count with global atomics
-    double edge_step;          // > 0: edges[k] == (double)k * edge_step exactly (hist_bin recomputes them); 0: read the table
-    // Transposed neighbour lists (fast BAD kernels).  When both triples B-A-B and A-B-A of a species pair are asked
-    // for, only the side with FEWER centres is searched; every pair it finds is also appended to the list of its
-    // partner, and the angles around the other species' centres are formed from those lists (bad_transposed_kernel)
-    // instead of a second search -- in ZIF-4 every N has one Zn neighbour and no angle at all, yet searching from the
-    // 2304 N cost as much as the whole Zn-centred triple.  The neighbour test is symmetric (same fixed-point
-    // differences negated, same canonical arithmetic), so the lists are the ones the search would have found.
-    const int32_t *tr_off;     // [T] first slot of the derived triple's centres, for a searched triple; -1: none (or null)
-    const int32_t *inv_rank;   // [N] position of an atom inside its species segment
-    uint32_t *tcount;          // [frames of the batch][tr_total]
-    uint32_t *tlist;           // [frames of the batch][tr_total][TR_CAP] partner atom indices
-    int32_t tr_total;
-};
-
-constexpr int TR_CAP = 16;     // = NBRF_NLIST: a fuller centre sends the call to the exact kernels either way
+constexpr int TR_CAP = 16;    // = NBRF_NLIST: a fuller centre sends the call to the exact kernels either way
 
 // ------------------------------------------------------------------- CN ----
 template <bool ORTHO, bool EXTRA>
@@ -431,8 +384,6 @@ __device__ __forceinline__ void cell_neighbours(const NbrFastArgs &fa, const QAt
     }
 }
 
-constexpr int NBRF_TILE = 256;
-constexpr int NBRF_NLIST = 16;     // neighbours per centre bad_fast_kernel keeps in LDS (more: big-list pass of the exact kernel)
 constexpr int NBRF_UVCAP = 768;    // unit vectors per centre tile and frame held in LDS for the flattened angle phase
 // (sized for three workgroups per CU at 3600 angle bins: 18 KB unit vectors -- the partner tile aliases them --
 //  + 16 KB lists + 14 KB histogram + 3.5 KB tables = 52.8 KB)
@@ -884,15 +835,6 @@ __global__ __launch_bounds__(NBRW_THREADS, (PT == 8 && !COMPACT) ? 4 : 8) void c
     }
 }
 
-// ase.geometry.get_angles on two canonical minimum-image vectors (normalise, dot, clip, acos)
-__device__ __forceinline__ bool unit_vec(double x, double y, double z, double &ux, double &uy, double &uz)
-{
-    const double nv = sqrt(x * x + y * y + z * z);
-    if (!(nv > 0.0)) return false;
-    ux = x / nv; uy = y / nv; uz = z / nv;
-    return true;
-}
-
 // One lane = one centre atom for the neighbour search (as in cn_fast_kernel); the angles are then formed by the
 // whole workgroup over FLATTENED work lists, because per-lane loops leave most lanes idle (in ZIF-4 every N has one
 // Zn neighbour and no angle, every Zn has four N and six angles) and chain dependent gathers (the old per-lane loop:
@@ -1175,22 +1117,10 @@ __global__ __launch_bounds__(256) void bad_transposed_kernel(NbrFastArgs fa, con
 //                       numpy.histogram edges) into an LDS histogram.  No gathers, no barriers inside the loop.
 // The 17 triples the reference asks for with three cutoffs (amof/bad.py:126-131: every ordered species pair + X) share
 // three sorts and three LDS searches.
-constexpr int NBRL_CAP = NBRF_NLIST;      // a fuller centre sends the call to the exact kernels, as in bad_fast_kernel
-constexpr int NBRL_EW = 4;                // doubles per row entry: (ux, uy, uz, partner or 0.0) -- one aligned 32-byte sector per unit vector
 constexpr int NBRW_HITS = 4096;           // pairs lists_frame_kernel buffers in LDS: 256 per wave, flushed by the wave itself once it
                                           // holds more than 64 -- its next 64 tasks may then add 128 (two neighbours per centre and
                                           // ROW of cells) and 64 more (third neighbours) before the call falls back to the exact kernels
 constexpr int NBRW_HITS_WAVE = NBRW_HITS / (NBRW_THREADS / 64);
-
-struct NbrListArgs {
-    const int32_t *region_of;  // [S][S] first row of the ordered pair (centre species, partner species); -1: not kept
-    const int32_t *inv_rank;   // [N] rank of an atom inside its species
-    uint32_t *count;           // [frames of the batch][R]
-    double *rows;              // [NBRL_CAP][frames of the batch * R][NBRL_EW] unit vectors centre -> neighbour, slot-major: the
-                               // k-th neighbours of consecutive centres are neighbours in memory (dense writes, coalesced reads)
-    size_t plane;              // frames of the batch * R
-    int32_t R;
-};
 
 #ifdef NBR_PHASE_STAMPS
 __device__ unsigned long long nbr_phase_ticks[16][5];   // [entry][sort, search, unit vectors, counts, workgroups] (diagnostic build only)
@@ -1644,616 +1574,14 @@ __global__ __launch_bounds__(NBRM_THREADS) void bad_rows_merged_kernel(NbrArgs a
     else flush(hist_x, nangx, it.tx[0], it.tx[1]);
 }
 
-// --------------------------------------------------------------- bond order ----
-// Steinhardt q_l and the tetrahedral order parameter q_tet of every centre of a set (A, B), from the unit vectors to its
-// neighbours alone (include/amof_hip.h, amof_bond_order).  By the addition theorem of the spherical harmonics
-//     q_l^2 = (n + 2 sum_{j<k} P_l(cos theta_jk)) / n^2,
-// so a centre needs the cosines BAD forms and a Legendre recurrence, no spherical harmonic.  Every term is rounded to a
-// fixed-point grid of 2^-40 (ORDER_E) and summed in int64: the sums are exact, order independent and the same on every
-// path.  order_pair and order_centre are the ONE statement of the arithmetic both tiers call.
-// Resources (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): order_rows_kernel 95 VGPRs, order_kernel<true / false> 84,
-// 0 bytes of scratch per lane and no VGPR spill in either; the compiler parks 20 / 17 SGPRs in VGPR lanes, as it does for
-// bad_rows_kernel.  No inline assembly.
-constexpr int ORDER_E = 40;
-constexpr int ORDER_MAX_L = 4;              // values of l per call
-constexpr int ORDER_L_TOP = 12;             // each in 1 .. 12
-constexpr int ORDER_CAP = 64;               // neighbours of a centre (more: AMOF_ECAPACITY); n 2^E + 2 T_l < 2^53 up to here
-constexpr int ORDER_EXACT_LDS_BINS = 15360; // u32 bins beside the exact kernel's 96 KB of unit vectors
-
-struct OrderArgs {
-    int32_t n_l, l_top;             // l_top = the largest l asked for
-    int32_t l[ORDER_MAX_L];         // (0: unused)
-    int32_t nbins, nbins_tet;
-    int32_t global_hist;            // 1: more bins than LDS holds -- u64 global atomics
-    int32_t lane_sums;              // 1: per-lane atomics for the frame sums even where a wave shares one frame (measurements)
-    int32_t cols;                   // 4 + n_l + 1 columns of frame_sums
-    unsigned long long *hist;       // [n_sets][n_l][nbins]
-    unsigned long long *hist_tet;   // [n_sets][nbins_tet]
-    unsigned long long *frame_sums; // [F][n_sets][cols] (int64, two's complement)
-    long long *per_atom;            // [F][n_sets][N][2 + n_l] or null
-};
-
-struct OrderSums {
-    long long T[ORDER_MAX_L];       // sum over pairs of llrint(P_l(c) 2^E)
-    long long U;                    // sum over pairs of llrint((c + 1/3)^2 2^E)
-};
-
-// one unordered pair of neighbours: BAD's clipped cosine (same expression, no contraction), the Bonnet recurrence in float64
-__device__ __forceinline__ void order_pair(const OrderArgs &o, double ax, double ay, double az, double bx, double by, double bz,
-                                           OrderSums &s)
-{
-    double c = ax * bx + ay * by + az * bz;
-    if (c > 1.0) c = 1.0;
-    if (c < -1.0) c = -1.0;
-    double pm = 1.0, p = c;
-    for (int m = 1;; m++) {
-#pragma unroll
-        for (int q = 0; q < ORDER_MAX_L; q++)
-            if (o.l[q] == m) s.T[q] += llrint(p * 0x1p40);
-        if (m >= o.l_top) break;
-        const double pn = (((double)(2 * m + 1) * c) * p - (double)m * pm) / (double)(m + 1);
-        pm = p;
-        p = pn;
-    }
-    const double t = c + 1.0 / 3.0;
-    s.U += llrint(t * t * 0x1p40);
-}
-
-// what a centre adds to its frame's sums: v[0..3] = n, n >= 1, n == 4, n (n - 1) / 2; ql[q] = llrint(q_l 2^30); qt = llrint(q_tet 2^30)
-struct OrderRow {
-    long long v[4];
-    long long ql[ORDER_MAX_L];
-    long long qt;
-};
-
-// a centre with n neighbours (0: none, or no centre at all) and its sums: the bins (lh: the workgroup's LDS histogram,
-// [n_l][nbins] then [nbins_tet]; null: global atomics) and its row of the frame sums
-__device__ __forceinline__ OrderRow order_centre(const OrderArgs &o, int set, int n, const OrderSums &s, unsigned *lh)
-{
-    OrderRow r;
-    r.v[0] = n; r.v[1] = n >= 1 ? 1 : 0; r.v[2] = n == 4 ? 1 : 0; r.v[3] = (long long)n * (n - 1) / 2;
-    r.qt = 0;
-#pragma unroll
-    for (int q = 0; q < ORDER_MAX_L; q++) {
-        r.ql[q] = 0;
-        if (n < 1 || q >= o.n_l) continue;
-        long long Q = ((long long)n << ORDER_E) + 2 * s.T[q];
-        if (Q < 0) Q = 0;
-        const double ql = sqrt((double)Q * 0x1p-40) / (double)n;
-        const int b = max(0, min((int)(ql * (double)o.nbins), o.nbins - 1));
-        if (lh) atomicAdd(&lh[q * o.nbins + b], 1u);
-        else atomicAdd(&o.hist[((size_t)set * o.n_l + q) * o.nbins + b], 1ull);
-        r.ql[q] = llrint(ql * 0x1p30);
-    }
-    if (n == 4) {
-        const double qt = 1.0 - 0.375 * ((double)s.U * 0x1p-40);
-        const int b = max(0, min((int)((qt + 3.0) * 0.25 * (double)o.nbins_tet), o.nbins_tet - 1));
-        if (lh) atomicAdd(&lh[o.n_l * o.nbins + b], 1u);
-        else atomicAdd(&o.hist_tet[(size_t)set * o.nbins_tet + b], 1ull);
-        r.qt = llrint(qt * 0x1p30);
-    }
-    return r;
-}
-
-// (n, T_l ..., U) of one centre
-__device__ __forceinline__ void order_per_atom(const NbrArgs &a, const OrderArgs &o, int f, int set, int64_t atom, int n,
-                                               const OrderSums &s)
-{
-    long long *pa = o.per_atom + (((size_t)f * a.n_sets + set) * (size_t)a.N + (size_t)atom) * (size_t)(2 + o.n_l);
-    pa[0] = n;
-#pragma unroll
-    for (int q = 0; q < ORDER_MAX_L; q++)
-        if (q < o.n_l) pa[1 + q] = s.T[q];
-    pa[1 + o.n_l] = s.U;
-}
-
-// The rows of a wave's centres into frame_sums (called by all 64 lanes; f < 0: the lane has no centre).  A wave whose
-// centres share one frame adds them up first -- one atomic per column; otherwise every lane adds its own row.
-__device__ __forceinline__ void order_frame_sums(const OrderArgs &o, int n_sets, int f, int set, const OrderRow &r)
-{
-    const int f0 = __shfl(f, 0, 64);
-    const bool shared = !o.lane_sums && __all(f == f0 || f < 0);
-    const int lane = threadIdx.x & 63;
-    auto column = [&](long long x, int col) {
-        if (shared) {
-            for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-            if (lane == 0 && f0 >= 0 && x) atomicAdd(&o.frame_sums[((size_t)f0 * n_sets + set) * o.cols + col], (unsigned long long)x);
-        } else if (f >= 0 && x) {
-            atomicAdd(&o.frame_sums[((size_t)f * n_sets + set) * o.cols + col], (unsigned long long)x);
-        }
-    };
-#pragma unroll
-    for (int k = 0; k < 4; k++) column(f >= 0 ? r.v[k] : 0, k);
-#pragma unroll
-    for (int q = 0; q < ORDER_MAX_L; q++)
-        if (q < o.n_l) column(f >= 0 ? r.ql[q] : 0, 4 + q);
-    column(f >= 0 ? r.qt : 0, 4 + o.n_l);
-}
-
-// the workgroup's LDS histogram into the global ones: one u64 atomic per non-empty bin
-__device__ __forceinline__ void order_flush_hist(const OrderArgs &o, int set, const unsigned *lh, int threads)
-{
-    const int nq = o.n_l * o.nbins, nh = nq + o.nbins_tet;
-    for (int k = threadIdx.x; k < nh; k += threads) {
-        const unsigned v = lh[k];
-        if (!v) continue;
-        if (k < nq) atomicAdd(&o.hist[(size_t)set * nq + k], (unsigned long long)v);
-        else atomicAdd(&o.hist_tet[(size_t)set * o.nbins_tet + (k - nq)], (unsigned long long)v);
-    }
-}
-
-// per_atom before any kernel: (n, T_l ..., U) = (0, 0 ..., 0) for the atoms of a set's centre species (a set without a
-// cutoff or without partners has no kernel work: its centres keep these), n = -1 for all others
-__global__ __launch_bounds__(256) void order_init_kernel(long long *__restrict__ pa, const int32_t *__restrict__ species,
-                                                         const int32_t *__restrict__ set_a, int n_sets, int64_t N, int width, size_t total)
-{
-    for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < total; k += (size_t)gridDim.x * 256) {
-        const size_t cell = k / (size_t)width;
-        const int col = (int)(k - cell * (size_t)width);
-        const int64_t atom = (int64_t)(cell % (size_t)N);
-        const int set = (int)((cell / (size_t)N) % (size_t)n_sets);
-        pa[k] = (col == 0 && species[atom] != set_a[set]) ? -1ll : 0ll;
-    }
-}
-
-// Frame tier: work item (blockIdx.y) = (set, centre species, partner species, -); blockIdx.x strides over the tiles of 256
-// (frame, centre) pairs of the batch, a lane owns its centre (as bad_rows_kernel); n <= 4 keeps the vectors in registers
-__global__ __launch_bounds__(NBRF_TILE) void order_rows_kernel(NbrArgs a, NbrListArgs la, OrderArgs o, const int4 *__restrict__ aw,
-                                                               const int64_t *__restrict__ sp_first, int f_base, int nf)
-{
-    extern __shared__ unsigned order_lh[];          // [n_l][nbins] | [nbins_tet] unless the counts go straight to global memory
-    const int tid = threadIdx.x;
-    const int4 w = aw[blockIdx.y];
-    const int set = w.x, sa = w.y, sb = w.z;
-    const int reg = la.region_of[sa * a.S + sb];
-    const int64_t seg = sp_first[sa];
-    const uint32_t nA = (uint32_t)(sp_first[sa + 1] - seg);
-    const uint32_t total = (uint32_t)nf * nA;                             // (< 2^31: the host sizes the frame batch)
-    const uint32_t tiles = (total + NBRF_TILE - 1) / NBRF_TILE;
-    unsigned *lh = o.global_hist ? nullptr : order_lh;
-    if (lh)
-        for (int k = tid; k < o.n_l * o.nbins + o.nbins_tet; k += NBRF_TILE) lh[k] = 0u;
-    __syncthreads();
-    const size_t step = la.plane * (NBRL_EW / 2);
-    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const uint32_t flat = tile * (uint32_t)NBRF_TILE + tid;
-        const bool has = flat < total;
-        const uint32_t fl = has ? flat / nA : 0u, r = has ? flat - fl * nA : 0u;
-        const size_t cbase = (size_t)fl * la.R + r + (size_t)reg;
-        int n = has ? (int)la.count[cbase] : 0;
-        if (n > NBRL_CAP) { a.flags[1] = 1; n = 0; }        // (as bad_rows_kernel: a fuller centre -> the exact kernel)
-        OrderSums s;
-#pragma unroll
-        for (int q = 0; q < ORDER_MAX_L; q++) s.T[q] = 0;
-        s.U = 0;
-        const double2 *__restrict__ e0 = reinterpret_cast<const double2 *>(la.rows + cbase * NBRL_EW);
-        if (n >= 2 && n <= 4) {
-            const double2 v0a = e0[0], v0b = e0[1], v1a = e0[step], v1b = e0[step + 1];
-            order_pair(o, v0a.x, v0a.y, v0b.x, v1a.x, v1a.y, v1b.x, s);
-            if (n > 2) {
-                const double2 v2a = e0[2 * step], v2b = e0[2 * step + 1];
-                order_pair(o, v0a.x, v0a.y, v0b.x, v2a.x, v2a.y, v2b.x, s);
-                order_pair(o, v1a.x, v1a.y, v1b.x, v2a.x, v2a.y, v2b.x, s);
-                if (n > 3) {
-                    const double2 v3a = e0[3 * step], v3b = e0[3 * step + 1];
-                    order_pair(o, v0a.x, v0a.y, v0b.x, v3a.x, v3a.y, v3b.x, s);
-                    order_pair(o, v1a.x, v1a.y, v1b.x, v3a.x, v3a.y, v3b.x, s);
-                    order_pair(o, v2a.x, v2a.y, v2b.x, v3a.x, v3a.y, v3b.x, s);
-                }
-            }
-        } else if (n > 4) {
-            for (int u = 0; u + 1 < n; u++) {
-                const double2 a01 = e0[u * step], a2 = e0[u * step + 1];
-                for (int v = u + 1; v < n; v++) {
-                    const double2 b01 = e0[v * step], b2 = e0[v * step + 1];
-                    order_pair(o, a01.x, a01.y, a2.x, b01.x, b01.y, b2.x, s);
-                }
-            }
-        }
-        const int f = has ? f_base + (int)fl : -1;
-        const OrderRow row = order_centre(o, set, n, s, lh);
-        if (o.per_atom && has) order_per_atom(a, o, f, set, a.perm[seg + r], n, s);
-        order_frame_sums(o, a.n_sets, f, set, row);
-    }
-    __syncthreads();
-    if (lh) order_flush_hist(o, set, lh, NBRF_TILE);
-}
-
-// Exact tier: bad_kernel<ORTHO, false>'s structure -- a lane per centre of a tile of 64, partner tiles staged through LDS,
-// the canonical minimum image (pair_base) and the strict sqrt(d2) < rc of amof_cn_count, the unit vectors [slot][lane] in
-// LDS, ORDER_CAP slots (96 KB).  Any cell, open axes, atoms anywhere.
-template <bool ORTHO>
-__global__ __launch_bounds__(BAD_TILE) void order_kernel(NbrArgs a, OrderArgs o)
-{
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    double *ux = reinterpret_cast<double *>(lds_raw);
-    double *uy = ux + ORDER_CAP * BAD_TILE;
-    double *uz = uy + ORDER_CAP * BAD_TILE;
-    double *tjx = uz + ORDER_CAP * BAD_TILE;
-    double *tjy = tjx + BAD_TILE;
-    double *tjz = tjy + BAD_TILE;
-    int *tja = reinterpret_cast<int *>(tjz + BAD_TILE);
-    unsigned *lh = o.global_hist ? nullptr : reinterpret_cast<unsigned *>(tja + BAD_TILE);
-
-    const int tid = threadIdx.x;
-    const int4 w = a.work[blockIdx.x];          // (set, centre tile, A, B)
-    const int set = w.x, A = w.z, B = w.w;
-    const Tile ti = a.tiles[w.y];
-    const double rc = a.cutoff[A * a.S + B];
-    const int64_t ai = tid < ti.count ? a.perm[ti.start + tid] : -1;
-    const int f0 = blockIdx.y * a.frames_per_chunk;
-    const int f1 = min(f0 + a.frames_per_chunk, a.F);
-    const int tb0 = a.sp_first_tile[B], tb1 = tb0 + a.sp_ntiles[B];
-    if (lh)
-        for (int k = tid; k < o.n_l * o.nbins + o.nbins_tet; k += BAD_TILE) lh[k] = 0u;
-    __syncthreads();
-
-    for (int f = f0; f < f1; f++) {
-        const double *__restrict__ p = a.pos + (size_t)f * (size_t)a.N * 3;
-        const double *__restrict__ g = a.geom + (size_t)(a.n_cells == 1 ? 0 : f) * GEOM_STRIDE;
-        double xi = 0.0, yi = 0.0, zi = 0.0;
-        if (ai >= 0) {
-            xi = p[ai * 3 + 0];
-            yi = p[ai * 3 + 1];
-            zi = p[ai * 3 + 2];
-        }
-        int n = 0;
-        if (rc > 0.0) {
-            for (int tb = tb0; tb < tb1; tb++) {
-                // partner tiles hold up to 256 atoms: stage them 64 at a time
-                const Tile tj = a.tiles[tb];
-                for (int base = 0; base < tj.count; base += BAD_TILE) {
-                    const int cntj = min(BAD_TILE, tj.count - base);
-                    __syncthreads();
-                    if (tid < cntj) {
-                        const int64_t aj = a.perm[tj.start + base + tid];
-                        tjx[tid] = p[aj * 3 + 0];
-                        tjy[tid] = p[aj * 3 + 1];
-                        tjz[tid] = p[aj * 3 + 2];
-                        tja[tid] = (int)aj;
-                    }
-                    __syncthreads();
-                    if (ai < 0) continue;
-                    for (int j = 0; j < cntj; j++) {
-                        if (tja[j] == (int)ai) continue;
-                        double dx, dy, dz;
-                        pair_base<ORTHO>(g, tjx[j] - xi, tjy[j] - yi, tjz[j] - zi, dx, dy, dz);
-                        if (!(sqrt(norm2(dx, dy, dz)) < rc)) continue;
-                        double qx = 0.0, qy = 0.0, qz = 0.0;
-                        if (!unit_vec(dx, dy, dz, qx, qy, qz)) a.flags[0] = 1;       // (the call fails: results are discarded)
-                        if (n < ORDER_CAP) {
-                            ux[n * BAD_TILE + tid] = qx;
-                            uy[n * BAD_TILE + tid] = qy;
-                            uz[n * BAD_TILE + tid] = qz;
-                        } else {
-                            a.flags[1] = 1;                                          // (AMOF_ECAPACITY)
-                        }
-                        n++;
-                    }
-                }
-            }
-        }
-        const int nn = min(n, ORDER_CAP);
-        OrderSums s;
-#pragma unroll
-        for (int q = 0; q < ORDER_MAX_L; q++) s.T[q] = 0;
-        s.U = 0;
-        for (int u = 0; u + 1 < nn; u++) {
-            const double ax = ux[u * BAD_TILE + tid], ay = uy[u * BAD_TILE + tid], az = uz[u * BAD_TILE + tid];
-            for (int v = u + 1; v < nn; v++)
-                order_pair(o, ax, ay, az, ux[v * BAD_TILE + tid], uy[v * BAD_TILE + tid], uz[v * BAD_TILE + tid], s);
-        }
-        const OrderRow row = order_centre(o, set, ai >= 0 ? nn : 0, s, lh);
-        if (o.per_atom && ai >= 0) order_per_atom(a, o, f, set, ai, nn, s);
-        order_frame_sums(o, a.n_sets, ai >= 0 ? f : -1, set, row);
-    }
-    __syncthreads();
-    if (lh) order_flush_hist(o, set, lh, BAD_TILE);
-}
-
-// ------------------------------------------------------------------ dihedral ----
-// Torsion angle of every chain a-b-c-d of bonded atoms (include/amof_hip.h, amof_dihedral_hist; dihedral_math.h states the
-// arithmetic and the pattern match once, for both kernels and the CPU driver).  A lane owns a (frame, atom b), walks the
-// central bonds to partners c > b and forms every (a, d); which patterns count a species 4-tuple comes from a host-built table
-// of masks (S^4 <= DIHEDRAL_TABLE_MAX words) or from the loop over the patterns.  Every output is an integer.
-//   dihedral_rows_kernel   "dihedral_frame": the unit vectors and partner indices from the neighbour rows of the list stage
-//                          (lists_frame_kernel<.., IDS = true>); c's rows through region_of and inv_rank
-//   dihedral_exact_kernel  "dihedral_exact": index rows from launch_bond_rows, the unit vectors recomputed from the positions
-//                          (pair_base<ORTHO>, unit_vec: the bits the rows hold)
-// Histogram: one per workgroup in LDS ([T][nb] u32; global u64 atomics when it does not fit).  Frame sums: the lanes of a wave
-// whose frame is the wave's first lane's add into the wave's own 3 T LDS words, which the wave then sends with one global
-// atomic per nonzero word (a tile of 256 (frame, atom) pairs spans two frames at most unless N < 256); a lane of another
-// frame adds to global memory itself.
-static_assert(NBRL_CAP == RING_MAX_DEGREE, "both paths refuse the same atoms");
-constexpr int DIH_WAVES = NBRF_TILE / 64;
-
-struct DihedralArgs {
-    const int32_t *chains;          // [T][4] species indices, -1: any
-    const uint32_t *table;          // [S^4] pattern masks of the species 4-tuples, or null (chain_mask per chain)
-    const int32_t *species;         // [N]
-    const double *edges;            // [nb + 1]
-    double edge_step;               // as NbrArgs::edge_step
-    int32_t T, nb, global_hist;
-    unsigned long long *hist;       // [T][nb]
-    unsigned long long *frame_sums; // [F][T][3] (int64, two's complement): defined, undefined, sum of llrint(c 2^40)
-    const int32_t *adj, *deg;       // exact kernel: the batch's index rows [nf][N][16], [nf][N]
-};
-
-struct DihedralLane {
-    unsigned *lh;                   // the workgroup's histogram, or null
-    unsigned long long *ws;         // the wave's frame sums [T][3]
-    double e0, en, inv_w;
-    int f;
-    bool in_wave;                   // the lane's frame is the wave's: sums into ws
-};
-
-__device__ __forceinline__ uint32_t dihedral_mask(const DihedralArgs &d, int S, int sa, int sb, int sc, int sd)
-{
-    return d.table ? d.table[((sa * S + sb) * S + sc) * S + sd] : dihedral::chain_mask(d.chains, d.T, sa, sb, sc, sd);
-}
-
-// one chain for the patterns of `mask` (not 0)
-__device__ __forceinline__ void dihedral_count(const DihedralArgs &d, const DihedralLane &ln, uint32_t mask, double u1x, double u1y,
-                                               double u1z, double u2x, double u2y, double u2z, double u3x, double u3y, double u3z)
-{
-    double c;
-    const bool defined = dihedral::chain_cos(u1x, u1y, u1z, u2x, u2y, u2z, u3x, u3y, u3z, c);
-    int k = -1;
-    long long term = 0;
-    if (defined) {
-        k = hist_bin(d.edges, d.nb, dihedral::angle_deg(c), ln.e0, ln.en, ln.inv_w, d.edge_step);
-        term = dihedral::cos_term(c);
-    }
-    while (mask) {
-        const int t = __ffs((int)mask) - 1;
-        mask &= mask - 1u;
-        if (k >= 0) {
-            if (ln.lh) atomicAdd(&ln.lh[t * d.nb + k], 1u);
-            else atomicAdd(&d.hist[(size_t)t * d.nb + k], 1ull);
-        }
-        if (ln.in_wave) {
-            atomicAdd(&ln.ws[3 * t + (defined ? 0 : 1)], 1ull);
-            if (term) atomicAdd(&ln.ws[3 * t + 2], (unsigned long long)term);
-        } else {
-            unsigned long long *fs = d.frame_sums + ((size_t)ln.f * d.T + t) * 3;
-            atomicAdd(&fs[defined ? 0 : 1], 1ull);
-            if (term) atomicAdd(&fs[2], (unsigned long long)term);
-        }
-    }
-}
-
-// the wave's LDS sums into frame f0's row (called by all 64 lanes after their chains; f0 < 0: the wave had no atom)
-__device__ __forceinline__ void dihedral_wave_flush(const DihedralArgs &d, unsigned long long *ws, int f0)
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (a wave's LDS operations execute in order: its sums are in place)
-    if (f0 < 0) return;
-    for (int e = (int)(threadIdx.x & 63); e < 3 * d.T; e += 64) {
-        const unsigned long long v = ws[e];
-        if (!v) continue;
-        atomicAdd(&d.frame_sums[(size_t)f0 * d.T * 3 + e], v);
-        ws[e] = 0ull;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-
-// LDS of both kernels: [DIH_WAVES][T][3] u64, then the histogram; the lane's record
-__device__ __forceinline__ DihedralLane dihedral_begin(const DihedralArgs &d, unsigned long long *lds)
-{
-    const int tid = threadIdx.x;
-    DihedralLane ln;
-    ln.ws = lds + (tid >> 6) * 3 * d.T;
-    ln.lh = d.global_hist ? nullptr : reinterpret_cast<unsigned *>(lds + DIH_WAVES * 3 * d.T);
-    for (int k = tid; k < DIH_WAVES * 3 * d.T; k += NBRF_TILE) lds[k] = 0ull;
-    if (ln.lh)
-        for (int k = tid; k < d.T * d.nb; k += NBRF_TILE) ln.lh[k] = 0u;
-    ln.e0 = d.edges[0];
-    ln.en = d.edges[d.nb];
-    ln.inv_w = (double)d.nb / (ln.en - ln.e0);
-    ln.f = -1;
-    ln.in_wave = false;
-    __syncthreads();
-    return ln;
-}
-
-__device__ __forceinline__ void dihedral_end(const DihedralArgs &d, const DihedralLane &ln)
-{
-    __syncthreads();
-    if (!ln.lh) return;
-    for (int k = threadIdx.x; k < d.T * d.nb; k += NBRF_TILE) {
-        const unsigned v = ln.lh[k];
-        if (v) atomicAdd(&d.hist[k], (unsigned long long)v);
-    }
-}
-
-// blockIdx.x strides over the tiles of 256 (frame, atom) pairs of the batch, the atoms in species order (perm): the lanes of
-// a wave mostly share a species, and with it their rows' regions and their trip counts
-__global__ __launch_bounds__(NBRF_TILE) void dihedral_rows_kernel(NbrArgs a, NbrListArgs la, DihedralArgs d, const int64_t *__restrict__ sp_first,
-                                                                  int f_base, int nf)
-{
-    extern __shared__ unsigned long long dihedral_lds[];
-    DihedralLane ln = dihedral_begin(d, dihedral_lds);
-    const int S = a.S;
-    const uint32_t N = (uint32_t)a.N;
-    const uint32_t total = (uint32_t)nf * N;                              // (< 2^31: the host sizes the frame batch)
-    const uint32_t tiles = (total + NBRF_TILE - 1) / NBRF_TILE;
-    // slot k of row r of the batch's frame fl: (ux, uy, uz, partner); a row's count (the list stage's global counters of
-    // shared partners run past the capacity: flags[1] is set then)
-    auto entry = [&](size_t row, int k) { return reinterpret_cast<const double2 *>(la.rows + ((size_t)k * la.plane + row) * NBRL_EW); };
-    auto count = [&](size_t row) { return (int)min(la.count[row], (uint32_t)NBRL_CAP); };
-    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const uint32_t flat = tile * (uint32_t)NBRF_TILE + threadIdx.x;
-        const bool has = flat < total;
-        const uint32_t fl = has ? flat / N : 0u, x = has ? flat - fl * N : 0u;
-        ln.f = has ? f_base + (int)fl : -1;
-        const int f0 = __shfl(ln.f, 0, 64);
-        ln.in_wave = ln.f == f0;
-        if (has) {
-            const int b = a.perm[x], sb = d.species[b];
-            const size_t fbase = (size_t)fl * la.R;
-            const size_t brow = fbase + (size_t)(x - (uint32_t)sp_first[sb]);       // + region: b's row for a partner species
-            int degree = 0;
-            for (int s = 0; s < S; s++) {
-                const int reg = la.region_of[sb * S + s];
-                if (reg >= 0) degree += count(brow + reg);
-            }
-            if (degree > NBRL_CAP) a.flags[1] = 1;          // (the exact tier names the frame)
-            for (int sc = 0; sc < S && degree >= 2 && degree <= NBRL_CAP; sc++) {
-                const int reg_bc = la.region_of[sb * S + sc];
-                if (reg_bc < 0) continue;
-                const int n_bc = count(brow + reg_bc);
-                for (int kc = 0; kc < n_bc; kc++) {
-                    const double2 *ec = entry(brow + reg_bc, kc);
-                    const double2 c01 = ec[0], c23 = ec[1];
-                    const int c = (int)__double_as_longlong(c23.y);
-                    if (c <= b) continue;                   // (the chain is visited from its other end)
-                    const size_t crow = fbase + (size_t)la.inv_rank[c];
-                    for (int sa = 0; sa < S; sa++) {
-                        const int reg_ba = la.region_of[sb * S + sa];
-                        if (reg_ba < 0) continue;
-                        const int n_ba = count(brow + reg_ba);
-                        for (int sd = 0; sd < S && n_ba > 0; sd++) {
-                            const int reg_cd = la.region_of[sc * S + sd];
-                            if (reg_cd < 0) continue;
-                            const uint32_t mask = dihedral_mask(d, S, sa, sb, sc, sd);
-                            if (!mask) continue;
-                            const int n_cd = count(crow + reg_cd);
-                            for (int ka = 0; ka < n_ba; ka++) {
-                                const double2 *ea = entry(brow + reg_ba, ka);
-                                const double2 a01 = ea[0], a23 = ea[1];
-                                const int at = (int)__double_as_longlong(a23.y);
-                                if (at == c) continue;
-                                for (int kd = 0; kd < n_cd; kd++) {
-                                    const double2 *ed = entry(crow + reg_cd, kd);
-                                    const double2 d01 = ed[0], d23 = ed[1];
-                                    const int dt = (int)__double_as_longlong(d23.y);
-                                    if (dt == b || dt == at) continue;
-                                    dihedral_count(d, ln, mask, a01.x, a01.y, a23.x, c01.x, c01.y, c23.x, d01.x, d01.y, d23.x);
-                                }
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        dihedral_wave_flush(d, ln.ws, f0);
-    }
-    dihedral_end(d, ln);
-}
-
-// the same chains from the index rows of launch_bond_rows (ascending, any cell); a lane owns (frame, atom b), b in atom order
-template <bool ORTHO>
-__global__ __launch_bounds__(NBRF_TILE) void dihedral_exact_kernel(NbrArgs a, DihedralArgs d, int f_base, int nf)
-{
-    extern __shared__ unsigned long long dihedral_lds[];
-    DihedralLane ln = dihedral_begin(d, dihedral_lds);
-    const int S = a.S;
-    const uint32_t N = (uint32_t)a.N;
-    const uint32_t total = (uint32_t)nf * N;                              // (< 2^31: the host sizes the frame batch)
-    const uint32_t tiles = (total + NBRF_TILE - 1) / NBRF_TILE;
-    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-        const uint32_t flat = tile * (uint32_t)NBRF_TILE + threadIdx.x;
-        const bool has = flat < total;
-        const uint32_t fl = has ? flat / N : 0u;
-        const int b = has ? (int)(flat - fl * N) : 0;
-        ln.f = has ? f_base + (int)fl : -1;
-        const int f0 = __shfl(ln.f, 0, 64);
-        ln.in_wave = ln.f == f0;
-        if (has) {
-            const double *__restrict__ p = a.pos + (size_t)ln.f * (size_t)a.N * 3;
-            const double *__restrict__ g = a.geom + (size_t)(a.n_cells == 1 ? 0 : ln.f) * GEOM_STRIDE;
-            // the canonical unit vector from atom i to its neighbour j: what the list stage writes into i's row
-            auto unit = [&](int i, int j, double &ux, double &uy, double &uz) {
-                double vx, vy, vz;
-                pair_base<ORTHO>(g, p[(size_t)j * 3] - p[(size_t)i * 3], p[(size_t)j * 3 + 1] - p[(size_t)i * 3 + 1],
-                                 p[(size_t)j * 3 + 2] - p[(size_t)i * 3 + 2], vx, vy, vz);
-                ux = uy = uz = 0.0;
-                if (!unit_vec(vx, vy, vz, ux, uy, uz)) a.flags[0] = 1;     // (the call fails: results are discarded)
-            };
-            const int32_t *__restrict__ brow = d.adj + ((size_t)fl * N + (size_t)b) * RING_MAX_DEGREE;
-            const int n_b = d.deg[(size_t)fl * N + (size_t)b], sb = d.species[b];
-            for (int j = 0; j < n_b; j++) {         // (every bond of the frame is seen here, whether a chain runs through it or not)
-                double ux, uy, uz;
-                unit(b, brow[j], ux, uy, uz);
-            }
-            for (int jc = 0; jc < n_b && n_b >= 2; jc++) {
-                const int c = brow[jc];
-                if (c <= b) continue;               // (the chain is visited from its other end)
-                const int32_t *__restrict__ crow = d.adj + ((size_t)fl * N + (size_t)c) * RING_MAX_DEGREE;
-                const int n_c = d.deg[(size_t)fl * N + (size_t)c], sc = d.species[c];
-                double u2x, u2y, u2z;
-                unit(b, c, u2x, u2y, u2z);
-                for (int ja = 0; ja < n_b; ja++) {
-                    const int at = brow[ja];
-                    if (at == c) continue;
-                    const int sa = d.species[at];
-                    double u1x, u1y, u1z;
-                    unit(b, at, u1x, u1y, u1z);
-                    for (int jd = 0; jd < n_c; jd++) {
-                        const int dt = crow[jd];
-                        if (dt == b || dt == at) continue;
-                        const uint32_t mask = dihedral_mask(d, S, sa, sb, sc, d.species[dt]);
-                        if (!mask) continue;
-                        double u3x, u3y, u3z;
-                        unit(c, dt, u3x, u3y, u3z);
-                        dihedral_count(d, ln, mask, u1x, u1y, u1z, u2x, u2y, u2z, u3x, u3y, u3z);
-                    }
-                }
-            }
-        }
-        dihedral_wave_flush(d, ln.ws, f0);
-    }
-    dihedral_end(d, ln);
-}
-
-// n_dihedrals[t], n_undefined[t] = the frame sums' first two columns over the frames of the call: totals [2][T]
-__global__ __launch_bounds__(256) void dihedral_totals_kernel(const unsigned long long *__restrict__ fs, unsigned long long *__restrict__ totals,
-                                                              int64_t F, int T)
-{
-    __shared__ unsigned long long part[2][256];
-    const int t = blockIdx.x, tid = threadIdx.x;
-    unsigned long long n0 = 0ull, n1 = 0ull;
-    for (int64_t f = tid; f < F; f += 256) {
-        n0 += fs[((size_t)f * T + t) * 3];
-        n1 += fs[((size_t)f * T + t) * 3 + 1];
-    }
-    part[0][tid] = n0;
-    part[1][tid] = n1;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) {
-            part[0][tid] += part[0][tid + off];
-            part[1][tid] += part[1][tid + off];
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        totals[t] = part[0][0];
-        totals[T + t] = part[1][0];
-    }
-}
-
 // ------------------------------------------------------------ host side ----
-struct NbrSetup {
-    HostGeom geom;
-    std::vector<double> img;
-    std::vector<int32_t> nimg;
-    int max_img = 0;
-    HostTiles tiles;
-    NbrArgs a;
-    Stager stage;
-};
-
-static int nbr_setup(amof_ctx *ctx, const amof_traj *t, const double *cutoff, int tile, NbrSetup &s)
+int nbr_setup(amof_ctx *ctx, const amof_traj *t, const double *cutoff, int tile, NbrSetup &s)
 {
     const int S = t->n_species;
+    AMOF_TRY(pore_refuse(ctx, nbr_check::values_not_negative(cutoff, S * S, "cutoff")));
+    AMOF_TRY(pore_refuse(ctx, nbr_check::symmetric(cutoff, S)));
     double R = 0.0;
-    for (int k = 0; k < S * S; k++) {
-        if (!(cutoff[k] >= 0.0) || !isfinite(cutoff[k])) return fail(ctx, AMOF_EINVAL, "cutoff must be finite and >= 0");
-        R = std::max(R, cutoff[k]);
-    }
-    for (int x = 0; x < S; x++)
-        for (int y = 0; y < S; y++)
-            if (cutoff[x * S + y] != cutoff[y * S + x]) return fail(ctx, AMOF_EINVAL, "cutoff matrix must be symmetric");
+    for (int k = 0; k < S * S; k++) R = std::max(R, cutoff[k]);
     AMOF_TRY(build_geometry(ctx, t, s.geom));
     AMOF_TRY(build_images(ctx, t, s.geom, R, s.img, s.nimg, s.max_img));
     build_tiles(t, tile, s.tiles);
@@ -2290,7 +1618,7 @@ static int nbr_setup(amof_ctx *ctx, const amof_traj *t, const double *cutoff, in
     return AMOF_OK;
 }
 
-static void pick_chunks(int64_t F, size_t nwork, int32_t &fpc, unsigned &chunks)
+void pick_chunks(int64_t F, size_t nwork, int32_t &fpc, unsigned &chunks)
 {
     int64_t want = (4 * 2048 + (int64_t)nwork - 1) / (int64_t)std::max<size_t>(1, nwork);
     int64_t f = std::max<int64_t>(1, F / std::max<int64_t>(1, want));
@@ -2768,7 +2096,6 @@ static int frame_batch_buffers(amof_ctx *ctx, const amof_traj *t, NbrFrame &nw, 
 // The frame tier's batches (CN, BAD and the bond order parameters), after frame_batch_buffers: FB0 frames first when the
 // input is staged lazily, doubling up to FB.  launch(nfr) queues one batch's kernels; qflag says whether an atom lay absurdly
 // far from the cell.  user: whose path name amof_last_path reports.
-enum FrameUser { FRAME_CN, FRAME_BAD, FRAME_ORDER, FRAME_DIHEDRAL };
 template <typename Launch>
 static int frame_batches(amof_ctx *ctx, const amof_traj *t, NbrSetup &st, NbrFrame &nw, int64_t FB, FrameUser user, Launch &&launch,
                          int32_t &qflag)
@@ -2814,14 +2141,6 @@ static hipError_t frame_dispatch(const NbrFrame &nw, F &&f)
     });
 }
 
-// ---- what the tiers of one call share: first tier to last, each runs unless one before it is done ----
-struct NbrCall {
-    amof_ctx *ctx;
-    const amof_traj *t;
-    const double *cutoff;
-    NbrSetup st;
-    bool done = false;
-};
 struct CnCall : NbrCall {
     const int32_t *sets;
     int32_t n_sets;
@@ -2948,7 +2267,8 @@ static int cn_exact_tier(CnCall &c)
 }
 
 // ---- the list stage of the frame tier: one sort + LDS search per species pair into neighbour rows (lists_frame_kernel).
-// BAD forms its angles from the rows, the bond order parameters their Legendre sums: both plan, commit and run it here.
+// BAD forms its angles from the rows, the bond order parameters (order.hip) their Legendre sums, the dihedrals (dihedral.hip) their
+// chains: all three go through frame_lists_tier below, which plans, commits and runs it.
 struct FrameLists {
     NbrFrame nw;
     std::vector<int32_t> region_of;     // [S][S] first row of the ordered pair (centre species, partner species); -1: not kept
@@ -3070,138 +2390,32 @@ static int frame_lists_run(NbrCall &c, FrameLists &L, FrameUser user, StageSpans
     return frame_batches(ctx, c.t, c.st, nw, L.FB, user, batch, qflag);
 }
 
-struct BadCall : NbrCall {
-    const int32_t *triples;
-    int32_t T, nb, cn_max;
-    // every pass accumulates into scratch; the caller's buffers only ever receive a complete, valid result
-    void *d_hs = nullptr, *d_flags = nullptr;
-    size_t hs_words = 0;
-    size_t lds_bins = 0;        // histogram bins a workgroup keeps in LDS (0: more bins than LDS holds, global atomics)
-    size_t KC = 1;              // histogram slots per triple
-    int read_flags(int32_t (&fl)[4])
-    {
-        AMOF_TRY(fetch(ctx, fl, d_flags, sizeof fl));
-        AMOF_HIP_TRY(ctx, sync_stream(ctx));
-        return AMOF_OK;
-    }
-    int clear_scratch()
-    {
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_hs, 0, hs_words * sizeof(unsigned long long), ctx->stream));
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
-        return AMOF_OK;
-    }
-};
-
-// whole-frame-in-LDS tier: one sort + LDS search per species pair into neighbour rows, every triple from the rows
-static int bad_frame_tier(BadCall &c)
+// The whole stage for one call (nbr_rows.h): prepare, plan, the two ways out before anything is uploaded, commit, run.
+int frame_lists_tier(HistCall &c, const ListsRequest &rq, const RowsConsumer &consume, ListsOutcome &outcome, int32_t &qflag,
+                     const RowsTables &tables)
 {
-    amof_ctx *ctx = c.ctx;
     const amof_traj *t = c.t;
-    const double *cutoff = c.cutoff;
-    NbrSetup &st = c.st;
-    NbrArgs &a = st.a;
-    const int S = t->n_species, T = c.T;
     FrameLists L;
     NbrFrame &nw = L.nw;
-    AMOF_TRY(nbr_frame_prepare(t, cutoff, st, nw));
-    if (getenv("AMOF_BAD_NOTRANSPOSE")) nw.ok = false;      // (names the two-search gather kernels)
-    auto live_pair = [&](int x, int y) { return cutoff[x * S + y] > 0.0 && st.tiles.nsp[x] > 0 && st.tiles.nsp[y] > 0; };
-    std::vector<char> needed((size_t)S * S, 0);
-    std::vector<int4> awork;
-    for (int k = 0; k < T && nw.ok; k++) {
-        const int A = c.triples[2 * k], B = c.triples[2 * k + 1];
-        for (int sa = 0; sa < S; sa++) {
-            if (!(A < 0 || sa == A)) continue;
-            bool live = false;
-            for (int sb = 0; sb < S; sb++)
-                if ((B < 0 || sb == B) && live_pair(sa, sb)) { needed[(size_t)sa * S + sb] = 1; live = true; }
-            if (live) awork.push_back(make_int4(k, sa, B, 0));
-        }
-    }
-    frame_lists_plan(c, needed, L);
-    const std::vector<int32_t> &region_of = L.region_of;
-    const int64_t R = L.R;
-    if (nw.ok && awork.empty()) {
-        c.done = true;          // no triple has a centre with a cutoff to any of its partners: no angle
+    outcome = LISTS_NOT_APPLICABLE;
+    qflag = 0;
+    AMOF_TRY(nbr_frame_prepare(t, c.cutoff, c.st, nw));
+    frame_lists_plan(c, rq.needed, L);
+    if (!nw.ok) return AMOF_OK;
+    if (std::find(rq.needed.begin(), rq.needed.end(), (char)1) == rq.needed.end()) {
+        outcome = LISTS_NOTHING;
         return AMOF_OK;
     }
-    if (!(nw.ok && R > 0 && R < (1ll << 30) && t->n_frames > 0)) return AMOF_OK;
-    // merged angle passes: one per centre species, every angle computed once (histograms in LDS; BadByCn keys, more
-    // bins than LDS holds, a centre species with more than three partner species or a triple named twice keep
-    // the pass per triple)
-    std::vector<MergedItem> merged;
-    size_t lds_merged = 0;
-    if (c.cn_max == 0 && !a.global_hist && !getenv("AMOF_BAD_NOMERGE")) {
-        auto find_triple = [&](int A, int B, bool &twice) {
-            int found = -1;
-            for (int k = 0; k < T; k++)
-                if (c.triples[2 * k] == A && c.triples[2 * k + 1] == B) { if (found >= 0) twice = true; else found = k; }
-            return found;
-        };
-        bool usable = true, twice = false;
-        for (int sa = 0; sa < S && usable; sa++) {
-            MergedItem mi{};
-            mi.sa = sa;
-            for (int q = 0; q < 3; q++) { mi.reg[q] = 0; mi.tb[q][0] = mi.tb[q][1] = -1; }
-            for (int sb = 0; sb < S && usable; sb++) {
-                if (region_of[(size_t)sa * S + sb] < 0) continue;
-                if (mi.n_reg == 3) { usable = false; break; }
-                mi.reg[mi.n_reg] = region_of[(size_t)sa * S + sb];
-                mi.tb[mi.n_reg][0] = find_triple(sa, sb, twice);
-                mi.tb[mi.n_reg][1] = find_triple(-1, sb, twice);
-                mi.n_reg++;
-            }
-            mi.tx[0] = find_triple(sa, -1, twice);
-            mi.tx[1] = find_triple(-1, -1, twice);
-            if (mi.n_reg == 0) continue;
-            bool any = mi.tx[0] >= 0 || mi.tx[1] >= 0;
-            for (int q = 0; q < mi.n_reg; q++) any = any || mi.tb[q][0] >= 0 || mi.tb[q][1] >= 0;
-            if (!any) continue;
-            lds_merged = std::max(lds_merged, (size_t)(mi.n_reg + (mi.n_reg > 1 ? 1 : 0)) * c.lds_bins * sizeof(unsigned));
-            merged.push_back(mi);
-        }
-        // (worth it when it saves passes: two triples over one species pair are two passes either way, and the pass
-        //  per triple keeps a centre's vectors in registers)
-        if (!usable || twice || lds_merged > 60 * 1024 || merged.size() >= awork.size()) merged.clear();
-    }
-    // the angle work at the head of the list stage's table; the merged items beside it
-    const int i_merged = nw.pk.add(merged.data(), merged.size() * sizeof(MergedItem));
-    AMOF_TRY(frame_lists_commit(c, L, reinterpret_cast<const int32_t *>(awork.data()), 4 * awork.size(), "AMOF_BAD_ROWS_MB"));
-    const MergedItem *d_merged = nw.pk.ptr<MergedItem>(i_merged);
-    const int4 *d_aw = (const int4 *)L.d_head;
-    const NbrListArgs &la = L.la;
-    const size_t lds_rows = c.lds_bins * sizeof(unsigned);
-    auto angles = [&](int64_t nfr) -> int {
-        hipError_t e;
-        if (!merged.empty()) {
-            // one pass per centre species: about 1024 workgroups of 512 lanes in all
-            int64_t widest_m = 0;
-            for (const MergedItem &mi : merged)
-                widest_m = std::max<int64_t>(widest_m, (nfr * st.tiles.nsp[(size_t)mi.sa] + NBRM_THREADS - 1) / NBRM_THREADS);
-            const int64_t gm = std::max<int64_t>(1, std::min<int64_t>(widest_m, (1024 + (int64_t)merged.size() - 1) / (int64_t)merged.size()));
-            const dim3 mgrid((unsigned)gm, (unsigned)merged.size());
-            e = with_flag(nw.ortho, [&](auto O) {
-                return launch_lds(bad_rows_merged_kernel<O()>, mgrid, dim3(NBRM_THREADS), lds_merged, ctx->stream, a, la, d_merged,
-                                  nw.d_spfirst, (int)nfr);
-            });
-            AMOF_HIP_TRY(ctx, e);
-            return AMOF_OK;
-        }
-        // angle kernel: about eight workgroups per CU in all work items together, each striding over the tiles of its own
-        int64_t widest = 0;
-        for (const int4 &w : awork) widest = std::max<int64_t>(widest, (nfr * st.tiles.nsp[(size_t)w.y] + NBRF_TILE - 1) / NBRF_TILE);
-        // (every workgroup ends with one global atomic per non-empty bin of its histogram, all on the same few
-        //  addresses: 16 384 workgroups spent more time there than on the angles)
-        const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(widest, (2048 + (int64_t)awork.size() - 1) / (int64_t)awork.size()));
-        const dim3 agrid((unsigned)gx, (unsigned)awork.size());
-        e = with_flag(nw.ortho, [&](auto O) {
-            return launch_lds(bad_rows_kernel<O()>, agrid, dim3(NBRF_TILE), lds_rows, ctx->stream, a, la, d_aw, nw.d_spfirst, (int)nfr);
-        });
-        AMOF_HIP_TRY(ctx, e);
-        return AMOF_OK;
+    if (!(L.R > 0 && L.R < (1ll << 30) && t->n_frames > 0)) return AMOF_OK;
+    if (tables) tables(L.region_of, nw.pk);
+    AMOF_TRY(frame_lists_commit(c, L, rq.head, rq.head_words, rq.rows_env, rq.zero_is_one_frame));
+    RowsBatch b{L.la, L.d_head, nw.d_spfirst, &nw.pk, 0, 0, nw.ortho};
+    auto batch = [&](int64_t nfr) -> int {
+        b.f_base = (int)nw.fr.f_base;
+        b.nfr = (int)nfr;
+        return consume(b);
     };
-    int32_t qflag;
-    AMOF_TRY(frame_lists_run(c, L, FRAME_BAD, nullptr, angles, qflag));
+    AMOF_TRY(frame_lists_run(c, L, rq.user, c.spans, batch, qflag));
 #ifdef NBR_PHASE_STAMPS
     {
         unsigned long long ph[16][5];
@@ -3216,13 +2430,121 @@ static int bad_frame_tier(BadCall &c)
         hipMemcpyToSymbol(HIP_SYMBOL(nbr_phase_ticks), ph, sizeof ph);
     }
 #endif
-    int32_t flags[4];
-    AMOF_TRY(c.read_flags(flags));
-    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-    // atoms absurdly far from the cell, or a centre with more than NBRL_CAP neighbours: the gather / exact kernels
-    if (qflag || flags[1]) return c.clear_scratch();
-    c.done = true;
+    outcome = LISTS_RAN;
     return AMOF_OK;
+}
+
+struct BadCall : HistCall {
+    const int32_t *triples;
+    int32_t T, nb, cn_max;
+    size_t lds_bins = 0;        // histogram bins a workgroup keeps in LDS (0: more bins than LDS holds, global atomics)
+    size_t KC = 1;              // histogram slots per triple
+};
+
+// whole-frame-in-LDS tier: one sort + LDS search per species pair into neighbour rows, every triple from the rows
+static int bad_frame_tier(BadCall &c)
+{
+    amof_ctx *ctx = c.ctx;
+    const amof_traj *t = c.t;
+    const double *cutoff = c.cutoff;
+    NbrSetup &st = c.st;
+    NbrArgs &a = st.a;
+    const int S = t->n_species, T = c.T;
+    if (getenv("AMOF_BAD_NOTRANSPOSE")) return AMOF_OK;     // (names the two-search gather kernels)
+    auto live_pair = [&](int x, int y) { return cutoff[x * S + y] > 0.0 && st.tiles.nsp[x] > 0 && st.tiles.nsp[y] > 0; };
+    std::vector<char> needed((size_t)S * S, 0);
+    std::vector<int4> awork;
+    for (int k = 0; k < T; k++) {
+        const int A = c.triples[2 * k], B = c.triples[2 * k + 1];
+        for (int sa = 0; sa < S; sa++) {
+            if (!(A < 0 || sa == A)) continue;
+            bool live = false;
+            for (int sb = 0; sb < S; sb++)
+                if ((B < 0 || sb == B) && live_pair(sa, sb)) { needed[(size_t)sa * S + sb] = 1; live = true; }
+            if (live) awork.push_back(make_int4(k, sa, B, 0));
+        }
+    }
+    // (no triple with a centre that has a cutoff to any of its partners: nothing is needed, and there is no angle)
+    //
+    // merged angle passes: one per centre species, every angle computed once (histograms in LDS; BadByCn keys, more
+    // bins than LDS holds, a centre species with more than three partner species or a triple named twice keep
+    // the pass per triple).  The angle work goes at the head of the list stage's table, the merged items beside it.
+    std::vector<MergedItem> merged;
+    size_t lds_merged = 0;
+    int i_merged = -1;
+    auto merge = [&](const std::vector<int32_t> &region_of, UploadPack &pk) {
+        if (c.cn_max == 0 && !a.global_hist && !getenv("AMOF_BAD_NOMERGE")) {
+            auto find_triple = [&](int A, int B, bool &twice) {
+                int found = -1;
+                for (int k = 0; k < T; k++)
+                    if (c.triples[2 * k] == A && c.triples[2 * k + 1] == B) { if (found >= 0) twice = true; else found = k; }
+                return found;
+            };
+            bool usable = true, twice = false;
+            for (int sa = 0; sa < S && usable; sa++) {
+                MergedItem mi{};
+                mi.sa = sa;
+                for (int q = 0; q < 3; q++) { mi.reg[q] = 0; mi.tb[q][0] = mi.tb[q][1] = -1; }
+                for (int sb = 0; sb < S && usable; sb++) {
+                    if (region_of[(size_t)sa * S + sb] < 0) continue;
+                    if (mi.n_reg == 3) { usable = false; break; }
+                    mi.reg[mi.n_reg] = region_of[(size_t)sa * S + sb];
+                    mi.tb[mi.n_reg][0] = find_triple(sa, sb, twice);
+                    mi.tb[mi.n_reg][1] = find_triple(-1, sb, twice);
+                    mi.n_reg++;
+                }
+                mi.tx[0] = find_triple(sa, -1, twice);
+                mi.tx[1] = find_triple(-1, -1, twice);
+                if (mi.n_reg == 0) continue;
+                bool any = mi.tx[0] >= 0 || mi.tx[1] >= 0;
+                for (int q = 0; q < mi.n_reg; q++) any = any || mi.tb[q][0] >= 0 || mi.tb[q][1] >= 0;
+                if (!any) continue;
+                lds_merged = std::max(lds_merged, (size_t)(mi.n_reg + (mi.n_reg > 1 ? 1 : 0)) * c.lds_bins * sizeof(unsigned));
+                merged.push_back(mi);
+            }
+            // (worth it when it saves passes: two triples over one species pair are two passes either way, and the pass
+            //  per triple keeps a centre's vectors in registers)
+            if (!usable || twice || lds_merged > 60 * 1024 || merged.size() >= awork.size()) merged.clear();
+        }
+        i_merged = pk.add(merged.data(), merged.size() * sizeof(MergedItem));
+    };
+    const size_t lds_rows = c.lds_bins * sizeof(unsigned);
+    auto angles = [&](const RowsBatch &b) -> int {
+        const int64_t nfr = b.nfr;
+        const NbrListArgs &la = b.la;
+        hipError_t e;
+        if (!merged.empty()) {
+            // one pass per centre species: about 1024 workgroups of 512 lanes in all
+            int64_t widest_m = 0;
+            for (const MergedItem &mi : merged)
+                widest_m = std::max<int64_t>(widest_m, (nfr * st.tiles.nsp[(size_t)mi.sa] + NBRM_THREADS - 1) / NBRM_THREADS);
+            const int64_t gm = std::max<int64_t>(1, std::min<int64_t>(widest_m, (1024 + (int64_t)merged.size() - 1) / (int64_t)merged.size()));
+            const dim3 mgrid((unsigned)gm, (unsigned)merged.size());
+            e = with_flag(b.ortho, [&](auto O) {
+                return launch_lds(bad_rows_merged_kernel<O()>, mgrid, dim3(NBRM_THREADS), lds_merged, ctx->stream, a, la,
+                                  b.pk->ptr<MergedItem>(i_merged), b.sp_first, (int)nfr);
+            });
+            AMOF_HIP_TRY(ctx, e);
+            return AMOF_OK;
+        }
+        // angle kernel: about eight workgroups per CU in all work items together, each striding over the tiles of its own
+        int64_t widest = 0;
+        for (const int4 &w : awork) widest = std::max<int64_t>(widest, (nfr * st.tiles.nsp[(size_t)w.y] + NBRF_TILE - 1) / NBRF_TILE);
+        // (every workgroup ends with one global atomic per non-empty bin of its histogram, all on the same few
+        //  addresses: 16 384 workgroups spent more time there than on the angles)
+        const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(widest, (2048 + (int64_t)awork.size() - 1) / (int64_t)awork.size()));
+        const dim3 agrid((unsigned)gx, (unsigned)awork.size());
+        e = with_flag(b.ortho, [&](auto O) {
+            return launch_lds(bad_rows_kernel<O()>, agrid, dim3(NBRF_TILE), lds_rows, ctx->stream, a, la, (const int4 *)b.head, b.sp_first, (int)nfr);
+        });
+        AMOF_HIP_TRY(ctx, e);
+        return AMOF_OK;
+    };
+    const ListsRequest rq{needed, reinterpret_cast<const int32_t *>(awork.data()), 4 * awork.size(), "AMOF_BAD_ROWS_MB", false, FRAME_BAD};
+    ListsOutcome outcome;
+    int32_t qflag;
+    AMOF_TRY(frame_lists_tier(c, rq, angles, outcome, qflag, merge));
+    return frame_lists_finish(c, outcome, qflag);     // (after a reset the gather / exact kernels answer)
 }
 
 // gathered cell list or slab list, one search per centre tile of a triple; of two triples B-A-B / A-B-A over one species
@@ -3334,7 +2656,7 @@ static int bad_gather_tier(BadCall &c)
     // atoms absurdly far from the cell: redo with the exact kernel.  A centre with more than NBRF_NLIST neighbours: the
     // exact kernel with its AMOF_MAX_NEIGHBOURS-deep LDS lists comes next (dense systems with 17..32 neighbours stay in
     // LDS); only if that overflows too, the big-list pass
-    if (qflag || flags[1]) return c.clear_scratch();
+    if (qflag || flags[1]) return c.reset_outputs();
     c.done = true;
     return AMOF_OK;
 }
@@ -3372,7 +2694,7 @@ static int bad_exact_tier(BadCall &c)
     AMOF_TRY(c.read_flags(flags));
     if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
     if (!flags[1]) return AMOF_OK;
-    AMOF_TRY(c.clear_scratch());
+    AMOF_TRY(c.reset_outputs());
     // Big-list pass.  The reference has no limit on the neighbours of a centre (amof/bad.py:87-100): find the
     // largest neighbour count with a counting pass of the exact kernel, then run that kernel once more with its
     // per-centre lists of unit vectors in global scratch, [workgroup][3][cap][BAD_TILE] doubles.
@@ -3392,7 +2714,7 @@ static int bad_exact_tier(BadCall &c)
     AMOF_TRY(ensure(ctx, SLOT_AUX8, per_wg * work.size() * (size_t)nchunks, &d_nbuf));
     a.nbuf = (double *)d_nbuf;
     a.ncap = (int32_t)cap;
-    AMOF_TRY(c.clear_scratch());
+    AMOF_TRY(c.reset_outputs());
     timing_dom_begin(ctx, "bad_exact_biglist");
     AMOF_HIP_TRY(ctx, launch_exact(dim3((unsigned)work.size(), (unsigned)nchunks)));
     timing_dom_end(ctx, 1);
@@ -3406,26 +2728,14 @@ static int bad_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, cons
                    int32_t T, const double *edges, int32_t nb, unsigned long long *hist_dev,
                    unsigned long long *nang_dev, int32_t cn_max = 0)
 {
-    BadCall c{{ctx, t, cutoff}, triples, T, nb, cn_max};
+    BadCall c{{{ctx, t, cutoff}}, triples, T, nb, cn_max};
     AMOF_TRY(nbr_setup(ctx, t, cutoff, BAD_TILE, c.st));
     void *d_edges;
     AMOF_TRY(upload(ctx, SLOT_AUX3, edges, (size_t)(nb + 1) * sizeof(double), &d_edges));
-    AMOF_TRY(ensure(ctx, SLOT_FLAGS, 4 * sizeof(int32_t), &c.d_flags));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(c.d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
     NbrArgs &a = c.st.a;
     a.edges = (const double *)d_edges;
     a.nb = nb;
-    a.edge_step = 0.0;
-    if (edges[0] == 0.0 && !getenv("AMOF_BAD_EDGE_TABLE")) {
-        volatile double step = edges[1];
-        bool uniform = true;
-        for (int k = 0; k <= nb && uniform; k++) {
-            volatile double e = (double)k * step;      // (one IEEE multiplication, as numpy and the kernels do it)
-            uniform = e == edges[k];
-        }
-        if (uniform) a.edge_step = step;
-    }
-    a.flags = (int32_t *)c.d_flags;
+    a.edge_step = getenv("AMOF_BAD_EDGE_TABLE") ? 0.0 : nbr_check::uniform_edge_step(edges, nb);
     a.cn_max = cn_max;
     a.nbuf = nullptr;
     a.ncap = 0;
@@ -3434,8 +2744,8 @@ static int bad_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, cons
     c.lds_bins = a.global_hist ? 0 : (size_t)nb;
     c.KC = (size_t)(cn_max > 0 ? cn_max + 1 : 1);
     c.hs_words = (size_t)T * c.KC * nb + (size_t)T * c.KC;
-    AMOF_TRY(ensure(ctx, SLOT_AUX7, c.hs_words * sizeof(unsigned long long), &c.d_hs));
-    AMOF_HIP_TRY(ctx, hipMemsetAsync(c.d_hs, 0, c.hs_words * sizeof(unsigned long long), ctx->stream));
+    AMOF_TRY(c.alloc_outputs());
+    AMOF_TRY(c.reset_outputs());
     a.hist = (unsigned long long *)c.d_hs;
     a.n_angles = a.hist + (size_t)T * c.KC * nb;
     AMOF_TRY(bad_frame_tier(c));
@@ -3452,447 +2762,6 @@ static int bad_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, cons
     return AMOF_OK;
 }
 
-// ------------------------------------------------------------ bond order: host side ----
-struct OrderCall : NbrCall {
-    const int32_t *sets;
-    int32_t n_sets;
-    OrderArgs o;
-    size_t words = 0;           // histogram words of a set: n_l nbins + nbins_tet
-    // every tier accumulates into the call's own buffers; the caller's only ever receive a complete, valid result
-    void *d_hs = nullptr, *d_flags = nullptr, *d_fs = nullptr, *d_pa = nullptr;
-    size_t hs_words = 0, fs_bytes = 0, pa_words = 0;
-    const int32_t *d_species = nullptr, *d_set_a = nullptr;
-    StageSpans *spans = nullptr;
-    int read_flags(int32_t (&fl)[4])
-    {
-        AMOF_TRY(fetch(ctx, fl, d_flags, sizeof fl));
-        AMOF_HIP_TRY(ctx, sync_stream(ctx));
-        return AMOF_OK;
-    }
-    int reset_outputs()         // the outputs as before the first tier
-    {
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_hs, 0, hs_words * sizeof(unsigned long long), ctx->stream));
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_fs, 0, fs_bytes, ctx->stream));
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
-        if (d_pa) {
-            const unsigned blocks = (unsigned)std::min<size_t>((pa_words + 255) / 256, 8192);
-            hipLaunchKernelGGL(order_init_kernel, dim3(blocks), dim3(256), 0, ctx->stream, (long long *)d_pa, d_species, d_set_a,
-                               (int)n_sets, (int64_t)t->n_atoms, 2 + o.n_l, pa_words);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-        }
-        return AMOF_OK;
-    }
-};
-
-// whole-frame-in-LDS tier: BAD's list stage (one sort + LDS search per species pair into neighbour rows), every set from its rows
-static int order_frame_tier(OrderCall &c)
-{
-    amof_ctx *ctx = c.ctx;
-    const amof_traj *t = c.t;
-    NbrSetup &st = c.st;
-    const int S = t->n_species;
-    FrameLists L;
-    NbrFrame &nw = L.nw;
-    AMOF_TRY(nbr_frame_prepare(t, c.cutoff, st, nw));
-    std::vector<char> needed((size_t)S * S, 0);
-    std::vector<int4> awork;
-    for (int s2 = 0; s2 < c.n_sets && nw.ok; s2++) {
-        const int A = c.sets[2 * s2], B = c.sets[2 * s2 + 1];
-        if (!(c.cutoff[A * S + B] > 0.0) || st.tiles.nsp[A] == 0 || st.tiles.nsp[B] == 0) continue;     // (no centre has a neighbour)
-        needed[(size_t)A * S + B] = 1;
-        awork.push_back(make_int4(s2, A, B, 0));
-    }
-    frame_lists_plan(c, needed, L);
-    if (nw.ok && awork.empty()) {
-        c.done = true;
-        return AMOF_OK;
-    }
-    if (!(nw.ok && L.R > 0 && L.R < (1ll << 30) && t->n_frames > 0)) return AMOF_OK;
-    AMOF_TRY(frame_lists_commit(c, L, reinterpret_cast<const int32_t *>(awork.data()), 4 * awork.size(), "AMOF_ORDER_ROWS_MB", true));
-    const int4 *d_aw = (const int4 *)L.d_head;
-    c.o.global_hist = c.words > (size_t)AMOF_MAX_LDS_BINS ? 1 : 0;
-    const size_t lds = c.o.global_hist ? 0 : c.words * sizeof(unsigned);
-    auto order = [&](int64_t nfr) -> int {
-        // about eight workgroups per CU in all work items together, each striding over the tiles of its own (as bad_rows_kernel)
-        int64_t widest = 0;
-        for (const int4 &w : awork) widest = std::max<int64_t>(widest, (nfr * st.tiles.nsp[(size_t)w.y] + NBRF_TILE - 1) / NBRF_TILE);
-        const int64_t gx = std::max<int64_t>(1, std::min<int64_t>(widest, (2048 + (int64_t)awork.size() - 1) / (int64_t)awork.size()));
-        const dim3 grid((unsigned)gx, (unsigned)awork.size());
-        AMOF_HIP_TRY(ctx, launch_lds(order_rows_kernel, grid, dim3(NBRF_TILE), lds, ctx->stream, st.a, L.la, c.o, d_aw, nw.d_spfirst,
-                                     (int)nw.fr.f_base, (int)nfr));
-        return AMOF_OK;
-    };
-    int32_t qflag;
-    AMOF_TRY(frame_lists_run(c, L, FRAME_ORDER, c.spans, order, qflag));
-    int32_t flags[4];
-    AMOF_TRY(c.read_flags(flags));
-    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-    // atoms absurdly far from the cell, or a centre with more than NBRL_CAP neighbours: the exact kernel
-    if (qflag || flags[1]) return c.reset_outputs();
-    c.done = true;
-    return AMOF_OK;
-}
-
-// exact kernel: every tile of centres of a set against every partner, canonical float64 arithmetic
-static int order_exact_tier(OrderCall &c)
-{
-    amof_ctx *ctx = c.ctx;
-    const amof_traj *t = c.t;
-    NbrSetup &st = c.st;
-    NbrArgs &a = st.a;
-    std::vector<int4> work;
-    for (int s = 0; s < c.n_sets; s++) {
-        const int A = c.sets[2 * s], B = c.sets[2 * s + 1];
-        for (int k = 0; k < st.tiles.sp_ntiles[A]; k++) work.push_back(make_int4(s, st.tiles.sp_first_tile[A] + k, A, B));
-    }
-    if (work.empty() || t->n_frames <= 0) return AMOF_OK;
-    void *d_work;
-    AMOF_TRY(upload(ctx, SLOT_PAIRS, work.data(), work.size() * sizeof(int4), &d_work));
-    a.work = (const int4 *)d_work;
-    c.o.global_hist = c.words > (size_t)ORDER_EXACT_LDS_BINS ? 1 : 0;
-    const size_t lds = (size_t)(3 * ORDER_CAP * BAD_TILE + 3 * BAD_TILE) * sizeof(double) + BAD_TILE * sizeof(int) +
-                       (c.o.global_hist ? 0 : c.words * sizeof(unsigned));
-    unsigned chunks;
-    pick_chunks(t->n_frames, work.size(), a.frames_per_chunk, chunks);
-    timing_dom_begin(ctx, "order_exact");
-    if (c.spans) c.spans->begin(1);
-    const hipError_t e = with_flag(st.geom.all_ortho, [&](auto O) {
-        return launch_lds(order_kernel<O()>, dim3((unsigned)work.size(), chunks), dim3(BAD_TILE), lds, ctx->stream, a, c.o);
-    });
-    AMOF_HIP_TRY(ctx, e);
-    if (c.spans) c.spans->end();
-    timing_dom_end(ctx, 1);
-    int32_t flags[4];
-    AMOF_TRY(c.read_flags(flags));
-    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-    if (flags[1]) return fail(ctx, AMOF_ECAPACITY, "a centre has more than %d neighbours", ORDER_CAP);
-    c.done = true;
-    return AMOF_OK;
-}
-
-static int order_check(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets, const int32_t *l,
-                       int32_t n_l, int32_t nbins, int32_t nbins_tet, const void *hist, const void *hist_tet, const void *frame_sums)
-{
-    AMOF_TRY(validate_traj(ctx, t, false));
-    if (!cutoff || n_sets < 0 || (n_sets > 0 && !sets) || !l) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (n_l < 1 || n_l > ORDER_MAX_L) return fail(ctx, AMOF_EINVAL, "n_l must be 1..%d", ORDER_MAX_L);
-    for (int q = 0; q < n_l; q++)
-        if (l[q] < 1 || l[q] > ORDER_L_TOP) return fail(ctx, AMOF_EINVAL, "l must be 1..%d", ORDER_L_TOP);
-    if (nbins < 1 || nbins > (1 << 24) || nbins_tet < 1 || nbins_tet > (1 << 24)) return fail(ctx, AMOF_EINVAL, "nbins, nbins_tet must be 1..2^24");
-    if (n_sets > 0 && (!hist || !hist_tet || (t->n_frames > 0 && !frame_sums))) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    const int S = t->n_species;
-    for (int s = 0; s < n_sets; s++)
-        if (sets[2 * s] < 0 || sets[2 * s] >= S || sets[2 * s + 1] < 0 || sets[2 * s + 1] >= S)
-            return fail(ctx, AMOF_EINVAL, "set %d names a species out of range", s);
-    for (int k = 0; k < S * S; k++)
-        if (!(cutoff[k] >= 0.0) || !isfinite(cutoff[k])) return fail(ctx, AMOF_EINVAL, "cutoff must be finite and >= 0");
-    if (n_sets == 0 || t->n_frames == 0) return AMOF_OK;
-    HostGeom geom;
-    AMOF_TRY(build_geometry(ctx, t, geom));
-    double hmin = INFINITY;         // smallest perpendicular height on a periodic axis
-    for (int64_t k = 0; k < t->n_cells; k++)
-        for (int x = 0; x < 3; x++)
-            if (t->pbc[x]) hmin = std::min(hmin, geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-    for (int s = 0; s < n_sets; s++) {
-        const double rc = cutoff[sets[2 * s] * S + sets[2 * s + 1]];
-        if (rc > 0.5 * hmin)
-            return fail(ctx, AMOF_EINVAL, "cutoff %g of set %d exceeds half the smallest cell height %g: a neighbour could be counted twice",
-                        rc, s, hmin);
-    }
-    return AMOF_OK;
-}
-
-// hist_dev / hist_tet_dev: device buffers to add into, or null (the call's own device buffers are then read back into
-// hist_host / hist_tet_host); frame_sums and per_atom: host
-static int order_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets, const int32_t *l,
-                     int32_t n_l, int32_t nbins, int32_t nbins_tet, uint64_t *hist_dev, uint64_t *hist_tet_dev, uint64_t *hist_host,
-                     uint64_t *hist_tet_host, int64_t *frame_sums, int64_t *per_atom)
-{
-    if (n_sets == 0 || t->n_frames == 0) return AMOF_OK;
-    OrderCall c{{ctx, t, cutoff}, sets, n_sets};
-    AMOF_TRY(nbr_setup(ctx, t, cutoff, BAD_TILE, c.st));
-    StageSpans spans(ctx);      // list stage, order kernels
-    c.spans = &spans;
-    OrderArgs &o = c.o;
-    memset(&o, 0, sizeof o);
-    o.n_l = n_l;
-    for (int q = 0; q < n_l; q++) {
-        o.l[q] = l[q];
-        o.l_top = std::max(o.l_top, l[q]);
-    }
-    o.nbins = nbins;
-    o.nbins_tet = nbins_tet;
-    o.cols = 4 + n_l + 1;
-    const char *sv = getenv("AMOF_ORDER_SUMS");
-    o.lane_sums = sv && !strcmp(sv, "lane") ? 1 : 0;
-    c.words = (size_t)n_l * nbins + (size_t)nbins_tet;
-    const size_t hq = (size_t)n_sets * n_l * nbins, ht = (size_t)n_sets * nbins_tet;
-    c.hs_words = hq + ht;
-    c.fs_bytes = (size_t)t->n_frames * n_sets * o.cols * sizeof(int64_t);
-    AMOF_TRY(ensure(ctx, SLOT_FLAGS, 4 * sizeof(int32_t), &c.d_flags));
-    AMOF_TRY(ensure(ctx, SLOT_AUX7, c.hs_words * sizeof(unsigned long long), &c.d_hs));
-    AMOF_TRY(ensure(ctx, SLOT_OUT0, c.fs_bytes, &c.d_fs));
-    if (per_atom) {
-        c.pa_words = (size_t)t->n_frames * n_sets * (size_t)t->n_atoms * (size_t)(2 + n_l);
-        AMOF_TRY(ensure(ctx, SLOT_OUT1, c.pa_words * sizeof(int64_t), &c.d_pa));
-        std::vector<int32_t> set_a((size_t)n_sets);
-        for (int s = 0; s < n_sets; s++) set_a[(size_t)s] = sets[2 * s];
-        UploadPack pk;
-        const int i_sp = pk.add(t->species, (size_t)t->n_atoms * sizeof(int32_t));
-        const int i_sa = pk.add(set_a.data(), set_a.size() * sizeof(int32_t));
-        AMOF_TRY(upload_pack(ctx, SLOT_AUX3, pk));
-        AMOF_HIP_TRY(ctx, sync_stream(ctx));        // (set_a leaves scope)
-        c.d_species = pk.ptr<int32_t>(i_sp);
-        c.d_set_a = pk.ptr<int32_t>(i_sa);
-    }
-    o.hist = (unsigned long long *)c.d_hs;
-    o.hist_tet = o.hist + hq;
-    o.frame_sums = (unsigned long long *)c.d_fs;
-    o.per_atom = (long long *)c.d_pa;
-    NbrArgs &a = c.st.a;
-    a.n_sets = n_sets;
-    a.flags = (int32_t *)c.d_flags;
-    AMOF_TRY(c.reset_outputs());
-    const char *ex = getenv("AMOF_ORDER_EXACT");
-    if (!(ex && ex[0] == '1')) AMOF_TRY(order_frame_tier(c));
-    AMOF_TRY(stager_need(c.st.stage, t->n_frames));   // (no-op unless the frame tier was skipped)
-    if (!c.done) AMOF_TRY(order_exact_tier(c));
-    // complete and valid: to the caller
-    if (hist_dev) {
-        AMOF_TRY(add_into(ctx, hist_dev, (const uint64_t *)o.hist, hq));
-        AMOF_TRY(add_into(ctx, hist_tet_dev, (const uint64_t *)o.hist_tet, ht));
-    }
-    timing_end(ctx);
-    if (!hist_dev) {
-        AMOF_TRY(fetch(ctx, hist_host, o.hist, hq * sizeof(uint64_t)));
-        AMOF_TRY(fetch(ctx, hist_tet_host, o.hist_tet, ht * sizeof(uint64_t)));
-    }
-    AMOF_TRY(fetch(ctx, frame_sums, c.d_fs, c.fs_bytes));
-    if (per_atom) AMOF_TRY(fetch(ctx, per_atom, c.d_pa, c.pa_words * sizeof(int64_t)));
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    spans.collect();
-    return AMOF_OK;
-}
-
-// ------------------------------------------------------------ dihedral: host side ----
-struct DihedralCall : NbrCall {
-    DihedralArgs d;
-    // every tier accumulates into the call's own buffers; the caller's only ever receive a complete, valid result
-    void *d_hs = nullptr, *d_flags = nullptr, *d_fs = nullptr;
-    size_t hist_words = 0, hs_words = 0, fs_bytes = 0;
-    size_t lds_words = 0;       // u32 words of a workgroup's LDS with the histogram in it
-    StageSpans *spans = nullptr;
-    int read_flags(int32_t (&fl)[4])
-    {
-        AMOF_TRY(fetch(ctx, fl, d_flags, sizeof fl));
-        AMOF_HIP_TRY(ctx, sync_stream(ctx));
-        return AMOF_OK;
-    }
-    int reset_outputs()         // the outputs as before the first tier
-    {
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_hs, 0, hs_words * sizeof(unsigned long long), ctx->stream));
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_fs, 0, fs_bytes, ctx->stream));
-        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_flags, 0, 4 * sizeof(int32_t), ctx->stream));
-        return AMOF_OK;
-    }
-    // dynamic LDS of either kernel (the wave sums, then the histogram unless it goes to global memory) and its grid
-    size_t lds_bytes() const { return (size_t)DIH_WAVES * 3 * d.T * sizeof(unsigned long long) + (d.global_hist ? 0 : hist_words * sizeof(unsigned)); }
-    dim3 grid(int64_t nfr) const
-    {
-        const int64_t tiles = (nfr * t->n_atoms + NBRF_TILE - 1) / NBRF_TILE;
-        return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>(tiles, 2048)));
-    }
-};
-
-// whole-frame-in-LDS tier: BAD's list stage with the partner's index in every row entry, every chain from the rows
-static int dihedral_frame_tier(DihedralCall &c)
-{
-    amof_ctx *ctx = c.ctx;
-    const amof_traj *t = c.t;
-    NbrSetup &st = c.st;
-    const int S = t->n_species;
-    FrameLists L;
-    NbrFrame &nw = L.nw;
-    AMOF_TRY(nbr_frame_prepare(t, c.cutoff, st, nw));
-    std::vector<char> needed((size_t)S * S, 0);
-    bool any = false;
-    for (int x = 0; x < S && nw.ok; x++)
-        for (int y = 0; y < S; y++)
-            if (c.cutoff[x * S + y] > 0.0 && st.tiles.nsp[x] > 0 && st.tiles.nsp[y] > 0) needed[(size_t)x * S + y] = 1, any = true;
-    frame_lists_plan(c, needed, L);
-    if (nw.ok && !any) {
-        c.done = true;          // no bond: no chain
-        return AMOF_OK;
-    }
-    if (!(nw.ok && L.R > 0 && L.R < (1ll << 30) && t->n_frames > 0)) return AMOF_OK;
-    AMOF_TRY(frame_lists_commit(c, L, nullptr, 0, "AMOF_DIHEDRAL_ROWS_MB", true));
-    auto chains = [&](int64_t nfr) -> int {
-        AMOF_HIP_TRY(ctx, launch_lds(dihedral_rows_kernel, c.grid(nfr), dim3(NBRF_TILE), c.lds_bytes(), ctx->stream, st.a, L.la, c.d,
-                                     nw.d_spfirst, (int)nw.fr.f_base, (int)nfr));
-        return AMOF_OK;
-    };
-    int32_t qflag;
-    AMOF_TRY(frame_lists_run(c, L, FRAME_DIHEDRAL, c.spans, chains, qflag));
-    int32_t flags[4];
-    AMOF_TRY(c.read_flags(flags));
-    if (flags[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-    // atoms absurdly far from the cell, or an atom with more than NBRL_CAP neighbours: the exact kernel (which names the frame)
-    if (qflag || flags[1]) return c.reset_outputs();
-    c.done = true;
-    return AMOF_OK;
-}
-
-// index rows of every frame from the adjacency kernel, the unit vectors recomputed per chain: any cell
-static int dihedral_exact_tier(DihedralCall &c)
-{
-    amof_ctx *ctx = c.ctx;
-    const amof_traj *t = c.t;
-    NbrSetup &st = c.st;
-    const int64_t N = t->n_atoms, F = t->n_frames;
-    if (N <= 0 || F <= 0) return AMOF_OK;
-    // rows of a batch: at most 256 MB, and a flat (frame, atom) index below 2^31
-    int64_t batch = std::max<int64_t>(1, ((int64_t)256 << 20) / (N * (RING_MAX_DEGREE + 1) * (int64_t)sizeof(int32_t)));
-    batch = std::min<int64_t>(std::min<int64_t>(batch, F), std::max<int64_t>(1, 0x7fffff00ll / N));
-    if (const char *mb = getenv("AMOF_DIHEDRAL_ROWS_MB"))
-        if (atoi(mb) <= 0) batch = 1;
-    void *d_adj, *d_deg;
-    AMOF_TRY(ensure(ctx, SLOT_AUX0, (size_t)batch * (size_t)N * RING_MAX_DEGREE * sizeof(int32_t), &d_adj));
-    AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)batch * (size_t)N * sizeof(int32_t), &d_deg));
-    c.d.adj = (const int32_t *)d_adj;
-    c.d.deg = (const int32_t *)d_deg;
-    int32_t *flags = (int32_t *)c.d_flags;
-    timing_dom_begin(ctx, "dihedral_exact");
-    int64_t launches = 0;
-    for (int64_t f0 = 0; f0 < F; f0 += batch) {
-        const int nf = (int)std::min<int64_t>(batch, F - f0);
-        if (c.spans) c.spans->begin(0);
-        AMOF_TRY(launch_bond_rows(ctx, BondRows{st.a.pos, st.a.geom, c.d.species, st.a.cutoff, (int32_t *)d_adj, (int32_t *)d_deg, &flags[2],
-                                                (int32_t)N, t->n_species, (int32_t)t->n_cells, (int32_t)f0, nf}, st.geom.all_ortho));
-        if (c.spans) { c.spans->end(); c.spans->begin(1); }
-        const hipError_t e = with_flag(st.geom.all_ortho, [&](auto O) {
-            return launch_lds(dihedral_exact_kernel<O()>, c.grid(nf), dim3(NBRF_TILE), c.lds_bytes(), ctx->stream, st.a, c.d, (int)f0, nf);
-        });
-        AMOF_HIP_TRY(ctx, e);
-        if (c.spans) c.spans->end();
-        launches++;
-    }
-    timing_dom_end(ctx, launches);
-    int32_t fl[4];
-    AMOF_TRY(c.read_flags(fl));
-    if (fl[2]) return fail(ctx, AMOF_ECAPACITY, "frame %d: an atom has more than %d neighbours", fl[2] - 1, NBRL_CAP);
-    if (fl[0]) return fail(ctx, AMOF_EANGLE, "Undefined angle");
-    c.done = true;
-    return AMOF_OK;
-}
-
-static int dihedral_check(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *chains, int32_t T, const double *edges,
-                          int32_t nb, const void *hist, const void *n_dihedrals, const void *n_undefined, const void *frame_sums)
-{
-    AMOF_TRY(validate_traj(ctx, t, false));
-    if (!cutoff || !chains || !edges || !hist || !n_dihedrals || !n_undefined || (t->n_frames > 0 && !frame_sums))
-        return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (T < 1 || T > DIHEDRAL_MAX_CHAINS) return fail(ctx, AMOF_EINVAL, "n_chains must be 1..%d", DIHEDRAL_MAX_CHAINS);
-    if (nb <= 0 || nb > (1 << 24)) return fail(ctx, AMOF_EINVAL, "nb must be 1..2^24");
-    for (int k = 0; k < nb; k++)
-        if (!(edges[k + 1] > edges[k])) return fail(ctx, AMOF_EINVAL, "edges must increase strictly");
-    const int S = t->n_species;
-    for (int k = 0; k < 4 * T; k++)
-        if (chains[k] < -1 || chains[k] >= S) return fail(ctx, AMOF_EINVAL, "chain %d names a species out of range", k / 4);
-    for (int x = 0; x < S; x++)
-        for (int y = 0; y < S; y++) {
-            const double rc = cutoff[x * S + y];
-            if (!(rc >= 0.0) || !isfinite(rc)) return fail(ctx, AMOF_EINVAL, "cutoff must be finite and >= 0");
-            if (rc != cutoff[y * S + x]) return fail(ctx, AMOF_EINVAL, "the cutoff matrix must be symmetric");
-        }
-    if (t->n_frames == 0 || t->n_atoms == 0) return AMOF_OK;
-    HostGeom geom;
-    AMOF_TRY(build_geometry(ctx, t, geom));
-    double hmin = INFINITY;         // smallest perpendicular height on a periodic axis
-    for (int64_t k = 0; k < t->n_cells; k++)
-        for (int x = 0; x < 3; x++)
-            if (t->pbc[x]) hmin = std::min(hmin, geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-    for (int k = 0; k < S * S; k++)
-        if (cutoff[k] > 0.5 * hmin)
-            return fail(ctx, AMOF_EINVAL, "cutoff %g exceeds half the smallest cell height %g: a pair could be bonded twice", cutoff[k], hmin);
-    return AMOF_OK;
-}
-
-// dev[3]: device buffers (hist, n_dihedrals, n_undefined) to add into, or null (the call's own are then read back into host[3])
-static int dihedral_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *chains, int32_t T, const double *edges,
-                        int32_t nb, uint64_t *const dev[3], uint64_t *const host[3], int64_t *frame_sums)
-{
-    if (t->n_frames == 0 || t->n_atoms == 0) return AMOF_OK;
-    const int S = t->n_species;
-    DihedralCall c{{ctx, t, cutoff}};
-    AMOF_TRY(nbr_setup(ctx, t, c.cutoff, BAD_TILE, c.st));
-    StageSpans spans(ctx);      // list stage (or adjacency), dihedral kernels
-    c.spans = &spans;
-    DihedralArgs &d = c.d;
-    memset(&d, 0, sizeof d);
-    d.T = T;
-    d.nb = nb;
-    // one table: chains | masks of the species 4-tuples | species | edges
-    const size_t tuples = (size_t)S * S * S * S;
-    std::vector<uint32_t> table;
-    if (tuples <= DIHEDRAL_TABLE_MAX && !getenv("AMOF_DIHEDRAL_NO_TABLE")) {
-        table.resize(tuples);
-        for (size_t k = 0; k < tuples; k++)
-            table[k] = dihedral::chain_mask(chains, T, (int)(k / ((size_t)S * S * S)), (int)(k / ((size_t)S * S) % S), (int)(k / S % S), (int)(k % S));
-    }
-    UploadPack pk;
-    const int i_edges = pk.add(edges, (size_t)(nb + 1) * sizeof(double));
-    const int i_chains = pk.add(chains, (size_t)4 * T * sizeof(int32_t));
-    const int i_species = pk.add(t->species, (size_t)t->n_atoms * sizeof(int32_t));
-    const int i_table = table.empty() ? -1 : pk.add(table.data(), table.size() * sizeof(uint32_t));
-    AMOF_TRY(upload_pack(ctx, SLOT_AUX3, pk));
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));        // (an early return below must not free `table` under the copy)
-    d.edges = pk.ptr<double>(i_edges);
-    d.chains = pk.ptr<int32_t>(i_chains);
-    d.species = pk.ptr<int32_t>(i_species);
-    d.table = i_table >= 0 ? pk.ptr<uint32_t>(i_table) : nullptr;
-    d.edge_step = 0.0;
-    if (edges[0] == 0.0 && !getenv("AMOF_BAD_EDGE_TABLE")) {
-        volatile double step = edges[1];
-        bool uniform = true;
-        for (int k = 0; k <= nb && uniform; k++) {
-            volatile double e = (double)k * step;      // (one IEEE multiplication, as numpy and the kernels do it)
-            uniform = e == edges[k];
-        }
-        if (uniform) d.edge_step = step;
-    }
-    c.hist_words = (size_t)T * nb;
-    c.hs_words = c.hist_words + 2 * (size_t)T;
-    c.fs_bytes = (size_t)t->n_frames * T * 3 * sizeof(int64_t);
-    d.global_hist = c.hist_words + (size_t)DIH_WAVES * 3 * T * 2 > (size_t)AMOF_MAX_LDS_BINS ? 1 : 0;
-    AMOF_TRY(ensure(ctx, SLOT_FLAGS, 4 * sizeof(int32_t), &c.d_flags));
-    AMOF_TRY(ensure(ctx, SLOT_AUX7, c.hs_words * sizeof(unsigned long long), &c.d_hs));
-    AMOF_TRY(ensure(ctx, SLOT_OUT0, c.fs_bytes, &c.d_fs));
-    d.hist = (unsigned long long *)c.d_hs;
-    d.frame_sums = (unsigned long long *)c.d_fs;
-    unsigned long long *totals = d.hist + c.hist_words;
-    c.st.a.flags = (int32_t *)c.d_flags;
-    AMOF_TRY(c.reset_outputs());
-    const char *ex = getenv("AMOF_DIHEDRAL_EXACT");
-    if (!(ex && ex[0] == '1')) AMOF_TRY(dihedral_frame_tier(c));
-    AMOF_TRY(stager_need(c.st.stage, t->n_frames));   // (no-op unless the frame tier was skipped)
-    if (!c.done) AMOF_TRY(dihedral_exact_tier(c));
-    hipLaunchKernelGGL(dihedral_totals_kernel, dim3((unsigned)T), dim3(256), 0, ctx->stream, (const unsigned long long *)d.frame_sums, totals,
-                       (int64_t)t->n_frames, (int)T);
-    AMOF_HIP_TRY(ctx, hipGetLastError());
-    // complete and valid: to the caller
-    const uint64_t *own[3] = {(const uint64_t *)d.hist, (const uint64_t *)totals, (const uint64_t *)totals + T};
-    const size_t words[3] = {c.hist_words, (size_t)T, (size_t)T};
-    if (dev)
-        for (int k = 0; k < 3; k++) AMOF_TRY(add_into(ctx, dev[k], own[k], words[k]));
-    timing_end(ctx);
-    if (!dev)
-        for (int k = 0; k < 3; k++) AMOF_TRY(fetch(ctx, host[k], own[k], words[k] * sizeof(uint64_t)));
-    AMOF_TRY(fetch(ctx, frame_sums, c.d_fs, c.fs_bytes));
-    AMOF_HIP_TRY(ctx, sync_stream(ctx));
-    spans.collect();
-    return AMOF_OK;
-}
-
 }  // namespace amof
 
 using namespace amof;
@@ -3903,10 +2772,7 @@ extern "C" int amof_cn_count(amof_ctx *ctx, const amof_traj *t, const double *cu
     if (!ctx) return AMOF_EINVAL;
     AMOF_TRY(validate_traj(ctx, t, false));
     if (!cutoff || n_sets < 0 || (n_sets > 0 && (!sets || !sums))) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    const int S = t->n_species;
-    for (int s = 0; s < n_sets; s++)
-        if (sets[2 * s] < 0 || sets[2 * s] >= S || sets[2 * s + 1] < 0 || sets[2 * s + 1] >= S)
-            return fail(ctx, AMOF_EINVAL, "set %d names a species out of range", s);
+    AMOF_TRY(pore_refuse(ctx, nbr_check::sets_in_range(sets, n_sets, t->n_species)));
     if (n_sets == 0 || t->n_frames == 0) return AMOF_OK;
     CnCall c{{ctx, t, cutoff}, sets, n_sets, per_atom != nullptr};
     AMOF_TRY(nbr_setup(ctx, t, cutoff, CN_TILE, c.st));
@@ -3938,14 +2804,9 @@ static int bad_check(amof_ctx *ctx, const amof_traj *t, const double *cutoff, co
 {
     AMOF_TRY(validate_traj(ctx, t, false));
     if (!cutoff || T < 0 || (T > 0 && !triples) || !edges || !hist || !nang) return fail(ctx, AMOF_EINVAL, "NULL argument");
-    if (nb <= 0) return fail(ctx, AMOF_EINVAL, "nb must be positive");
-    for (int k = 0; k < nb; k++)
-        if (!(edges[k + 1] > edges[k])) return fail(ctx, AMOF_EINVAL, "edges must increase strictly");
-    for (int k = 0; k < T; k++)
-        for (int c = 0; c < 2; c++)
-            if (triples[2 * k + c] < -1 || triples[2 * k + c] >= t->n_species)
-                return fail(ctx, AMOF_EINVAL, "triple %d names a species out of range", k);
-    return AMOF_OK;
+    AMOF_TRY(pore_refuse(ctx, nbr_check::bad_bins(nb)));
+    AMOF_TRY(pore_refuse(ctx, nbr_check::edges_increase(edges, nb)));
+    return pore_refuse(ctx, nbr_check::triples_in_range(triples, T, t->n_species));
 }
 
 extern "C" int amof_bad_hist_dev(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *triples,
@@ -3992,75 +2853,6 @@ extern "C" int amof_bad_hist_by_cn(amof_ctx *ctx, const amof_traj *t, const doub
 {
     if (!ctx) return AMOF_EINVAL;
     AMOF_TRY(bad_check(ctx, t, cutoff, triples, T, edges, nb, hist, n_angles));
-    if (cn_max < 1 || cn_max > 65535) return fail(ctx, AMOF_EINVAL, "cn_max must be 1..65535");
+    AMOF_TRY(pore_refuse(ctx, nbr_check::cn_max_range(cn_max)));
     return bad_hist_host(ctx, t, cutoff, triples, T, edges, nb, cn_max, hist, n_angles);
-}
-
-extern "C" int amof_bond_order(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets,
-                               const int32_t *l, int32_t n_l, int32_t nbins, int32_t nbins_tet, uint64_t *hist, uint64_t *hist_tet,
-                               int64_t *frame_sums, int64_t *per_atom)
-{
-    if (!ctx) return AMOF_EINVAL;
-    AMOF_TRY(order_check(ctx, t, cutoff, sets, n_sets, l, n_l, nbins, nbins_tet, hist, hist_tet, frame_sums));
-    // the host form overwrites: zeros first, so that a failing call leaves zeros
-    if (n_sets > 0) {
-        std::fill(hist, hist + (size_t)n_sets * n_l * nbins, (uint64_t)0);
-        std::fill(hist_tet, hist_tet + (size_t)n_sets * nbins_tet, (uint64_t)0);
-        if (t->n_frames > 0) std::fill(frame_sums, frame_sums + (size_t)t->n_frames * n_sets * (4 + n_l + 1), (int64_t)0);
-        if (per_atom) std::fill(per_atom, per_atom + (size_t)t->n_frames * n_sets * (size_t)t->n_atoms * (2 + n_l), (int64_t)0);
-    }
-    return order_run(ctx, t, cutoff, sets, n_sets, l, n_l, nbins, nbins_tet, nullptr, nullptr, hist, hist_tet, frame_sums, per_atom);
-}
-
-extern "C" int amof_bond_order_dev(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *sets, int32_t n_sets,
-                                   const int32_t *l, int32_t n_l, int32_t nbins, int32_t nbins_tet, uint64_t *hist_dev,
-                                   uint64_t *hist_tet_dev, int64_t *frame_sums, int64_t *per_atom)
-{
-    if (!ctx) return AMOF_EINVAL;
-    AMOF_TRY(order_check(ctx, t, cutoff, sets, n_sets, l, n_l, nbins, nbins_tet, hist_dev, hist_tet_dev, frame_sums));
-    if (n_sets > 0 && t->n_frames > 0) {
-        std::fill(frame_sums, frame_sums + (size_t)t->n_frames * n_sets * (4 + n_l + 1), (int64_t)0);
-        if (per_atom) std::fill(per_atom, per_atom + (size_t)t->n_frames * n_sets * (size_t)t->n_atoms * (2 + n_l), (int64_t)0);
-    }
-    return order_run(ctx, t, cutoff, sets, n_sets, l, n_l, nbins, nbins_tet, hist_dev, hist_tet_dev, nullptr, nullptr, frame_sums, per_atom);
-}
-
-extern "C" int amof_dihedral_hist(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *chains, int32_t n_chains,
-                                  const double *edges, int32_t nb, uint64_t *hist, uint64_t *n_dihedrals, uint64_t *n_undefined,
-                                  int64_t *frame_sums)
-{
-    if (!ctx) return AMOF_EINVAL;
-    // the host form overwrites: zeros first, so that a failing call leaves zeros
-    const bool sized = t && n_chains >= 1 && n_chains <= DIHEDRAL_MAX_CHAINS && nb > 0 && nb <= (1 << 24);
-    if (sized && hist) std::fill(hist, hist + (size_t)n_chains * nb, (uint64_t)0);
-    if (sized && n_dihedrals) std::fill(n_dihedrals, n_dihedrals + n_chains, (uint64_t)0);
-    if (sized && n_undefined) std::fill(n_undefined, n_undefined + n_chains, (uint64_t)0);
-    if (sized && frame_sums && t->n_frames > 0) std::fill(frame_sums, frame_sums + (size_t)t->n_frames * n_chains * 3, (int64_t)0);
-    AMOF_TRY(dihedral_check(ctx, t, cutoff, chains, n_chains, edges, nb, hist, n_dihedrals, n_undefined, frame_sums));
-    uint64_t *const host[3] = {hist, n_dihedrals, n_undefined};
-    const int rc = dihedral_run(ctx, t, cutoff, chains, n_chains, edges, nb, nullptr, host, frame_sums);
-    if (rc != AMOF_OK) {
-        (void)sync_stream(ctx);
-        std::fill(hist, hist + (size_t)n_chains * nb, (uint64_t)0);
-        std::fill(n_dihedrals, n_dihedrals + n_chains, (uint64_t)0);
-        std::fill(n_undefined, n_undefined + n_chains, (uint64_t)0);
-        std::fill(frame_sums, frame_sums + (size_t)t->n_frames * n_chains * 3, (int64_t)0);
-    }
-    return rc;
-}
-
-extern "C" int amof_dihedral_hist_dev(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int32_t *chains, int32_t n_chains,
-                                      const double *edges, int32_t nb, uint64_t *hist_dev, uint64_t *n_dihedrals_dev,
-                                      uint64_t *n_undefined_dev, int64_t *frame_sums)
-{
-    if (!ctx) return AMOF_EINVAL;
-    AMOF_TRY(dihedral_check(ctx, t, cutoff, chains, n_chains, edges, nb, hist_dev, n_dihedrals_dev, n_undefined_dev, frame_sums));
-    if (t->n_frames > 0) std::fill(frame_sums, frame_sums + (size_t)t->n_frames * n_chains * 3, (int64_t)0);
-    uint64_t *const dev[3] = {hist_dev, n_dihedrals_dev, n_undefined_dev};
-    const int rc = dihedral_run(ctx, t, cutoff, chains, n_chains, edges, nb, dev, nullptr, frame_sums);
-    if (rc != AMOF_OK && t->n_frames > 0) {
-        (void)sync_stream(ctx);
-        std::fill(frame_sums, frame_sums + (size_t)t->n_frames * n_chains * 3, (int64_t)0);
-    }
-    return rc;
 }

@@ -36,6 +36,7 @@
 #include <string.h>
 
 #include "amof_internal.h"
+#include "nbr_check.h"
 #include "ring_search.h"
 
 namespace amof {
@@ -335,13 +336,8 @@ int ring_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, int32_t nm
     const int W = nmax + 1;
     HostGeom geom;
     AMOF_TRY(build_geometry(ctx, t, geom));
-    double hmin = INFINITY;         // smallest perpendicular height on a periodic axis
-    for (int64_t k = 0; k < t->n_cells; k++)
-        for (int x = 0; x < 3; x++)
-            if (t->pbc[x]) hmin = std::min(hmin, geom.rec[(size_t)k * GEOM_STRIDE + 18 + x]);
-    for (int k = 0; k < S * S; k++)
-        if (cutoff[k] > 0.5 * hmin)
-            return fail(ctx, AMOF_EINVAL, "cutoff %g exceeds half the smallest cell height %g: a pair could be bonded twice", cutoff[k], hmin);
+    const double hmin = nbr_check::min_periodic_height(t->pbc, geom.rec.data(), t->n_cells);
+    for (int k = 0; k < S * S; k++) AMOF_TRY(pore_refuse(ctx, nbr_check::half_height(cutoff[k], hmin)));
 
     const bool simple = env_int("AMOF_RING_SIMPLE", 0) == 1;
     const char *path = simple ? "ring_simple" : "ring_wave";
@@ -495,13 +491,7 @@ extern "C" int amof_ring_stats(amof_ctx *ctx, const amof_traj *t, const double *
     if (!cutoff || (t->n_frames > 0 && (!counts || !truncated))) return fail(ctx, AMOF_EINVAL, "NULL argument");
     const RingOutputs out{counts, truncated, per_atom, neighbours, t->n_frames, t->n_atoms, max_size + 1};
     out.zero();     // the outputs are overwritten: zeros first, so that a failing call leaves zeros
-    const int S = t->n_species;
-    for (int x = 0; x < S; x++)
-        for (int y = 0; y < S; y++) {
-            const double rc = cutoff[x * S + y];
-            if (!(rc >= 0.0) || !isfinite(rc)) return fail(ctx, AMOF_EINVAL, "cutoff must be finite and >= 0");
-            if (rc != cutoff[y * S + x]) return fail(ctx, AMOF_EINVAL, "the cutoff matrix must be symmetric");
-        }
+    AMOF_TRY(pore_refuse(ctx, nbr_check::bond_matrix(cutoff, t->n_species, "cutoff")));
     if (t->n_atoms > RING_MAX_ATOMS) return fail(ctx, AMOF_ECAPACITY, "%lld atoms: more than the %d a path of u16 node ids can name", (long long)t->n_atoms, RING_MAX_ATOMS);
     if (t->n_frames == 0 || t->n_atoms == 0) return AMOF_OK;
     const int rc = ring_run(ctx, t, cutoff, max_size, out);

@@ -24,6 +24,7 @@ ONE_FRAME = {"AMOF_ORDER_ROWS_MB": "0"}         # a frame per batch of neighbour
 LANE_SUMS = {"AMOF_ORDER_SUMS": "lane"}         # the frame sums by per-lane atomics
 NB, NT = cases.NBINS, cases.NBINS_TET
 EDGES = np.arange(0, 182, 2.0)
+L2 = (4, 6)
 
 
 def _frame_tier_applies(hip_ctx, packed, rcm, sets):
@@ -162,6 +163,33 @@ def test_centres_with_17_to_64_neighbours_and_the_capacity(hip_ctx):
     # the context works afterwards
     assert _same(hip_ctx.bond_order(cases.case("cluster").packed, *_abi(cases.case("cluster").packed, [(30, 7, 3.0)]),
                                     (4, 6, 12), NB, NT), (hist, hist_tet, sums))
+
+
+def test_no_set_with_a_live_pair_is_nothing_to_do(hip_ctx):
+    """Two sets without a cutoff beside a species pair (N-N) that has one and that no set names: the list stage applies and finds
+    nothing to do, no kernel of either tier runs (the path name stays the call's before), and the outputs are the exact
+    kernel's and the restatement's -- no neighbour anywhere, zeros in the centres' rows, -1 off the centre species.
+    2 frames of 64 atoms."""
+    from tests import test_gpu_bond as B
+    packed = B._walk(B.DIAG, B._numbers4(64), 2, 21)
+    named = [(30, 30, 0.0), (1, 30, 0.0)]
+    _, sets = _abi(packed, named)
+    rcm, nn = _abi(packed, named + [(7, 7, 3.0)])
+    hip_ctx.cn_count(packed, rcm, nn[2:])
+    before = hip_ctx.last_path()
+    assert before.startswith("cn_")
+    got = hip_ctx.bond_order(packed, rcm, sets, L2, NB, NT, per_atom=True)
+    assert hip_ctx.last_path() == before
+    with _env(**EXACT):
+        exact = hip_ctx.bond_order(packed, rcm, sets, L2, NB, NT, per_atom=True)
+        assert hip_ctx.last_path() == "order_exact"
+    assert _same(got, exact)
+    ref.check(got[3], ref.order(packed.pos, packed.cell, packed.numbers, named, L2, pbc=tuple(packed.pbc)))
+    assert _same(ref.from_per_atom(got[3], len(L2), NB, NT), got[:3])
+    assert not got[0].any() and not got[1].any() and not got[2].any()
+    zn, h = packed.numbers == 30, packed.numbers == 1
+    assert zn.any() and h.any() and np.all(got[3][:, 0][:, zn] == 0) and np.all(got[3][:, 1][:, h] == 0)
+    assert np.all(got[3][:, 0][:, ~zn][..., 0] == -1) and np.all(got[3][:, 1][:, ~h][..., 0] == -1)
 
 
 def test_coincident_bonded_pair_is_an_error_and_leaves_zeros(hip_ctx):

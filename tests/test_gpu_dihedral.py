@@ -156,6 +156,63 @@ def test_bad_and_bond_order_read_rows_a_dihedral_call_wrote(hip_ctx):
     assert hip_ctx.last_path() == "order_exact" and _same(frame, exact)
 
 
+def _two_planted_frames(pbc=(True, True, True)):
+    """the planted chains of 35 and 100 degrees as the two frames of one trajectory of four atoms"""
+    a, b = cases.planted(35.0), cases.planted(100.0)
+    return PackedTrajectory(np.concatenate([a.pos_host(), b.pos_host()]), a.cell, a.numbers, pbc=pbc)
+
+
+def test_an_open_axis_leaves_the_call_to_the_exact_kernel(hip_ctx):
+    """the list stage wants three periodic axes: with y open the frame tier does not apply and the call reaches dihedral_exact
+    unforced -- the restatement's integers, the chain still bonded across the periodic face x"""
+    c = cases.Case()
+    c.packed, c.cutoff, c.chains, c.dphi = _two_planted_frames((True, False, True)), cases.PLANTED_CUT, cases.PLANTED_CHAINS, cases.PLANTED_DPHI
+    got = _run(hip_ctx, c, {}, "dihedral_exact")
+    assert _same(got, _run(hip_ctx, c, EXACT, "dihedral_exact"))
+    ref.check(got, ref.trajectory(c.packed, c.cutoff, cases.patterns(c)[1], cases.abi_arguments(c)[2]))
+    assert got[3][:, 0, 0].tolist() == [1, 1] and got[0][0, cases.PLANTED_BIN[35.0]] == 1 and got[0][0, cases.PLANTED_BIN[100.0]] == 1
+    periodic = cases.Case()
+    periodic.packed, periodic.cutoff, periodic.chains, periodic.dphi = _two_planted_frames(), c.cutoff, c.chains, c.dphi
+    assert _same(got, _run(hip_ctx, periodic, {}, "dihedral_frame"))
+
+
+def test_no_bonded_pair_is_nothing_to_do(hip_ctx):
+    """The only cutoff belongs to a species without atoms (one species more than the kinds present, through the C ABI): the list
+    stage applies and finds nothing to do, no kernel of either tier runs (the path name stays the call's before), and the
+    outputs are zeros, as the exact kernel and the restatement without a bond give them.  2 frames of 4 atoms."""
+    import ctypes
+    c = cases.Case()
+    c.packed, c.cutoff, c.chains, c.dphi = _two_planted_frames(), cases.PLANTED_CUT, ['X-X-X-X', 'H-C-N-Zn'], cases.PLANTED_DPHI
+    rcm4, idx, edges = cases.abi_arguments(c)
+    S, T, nb = 4, len(idx), len(edges) - 1
+    rcm = np.zeros((S + 1, S + 1))
+    rcm[0, S] = rcm[S, 0] = 1.3
+    idx, edges = np.ascontiguousarray(idx, dtype=np.int32), np.ascontiguousarray(edges)
+
+    def call(env):
+        outs = [np.full((T, nb), 7, dtype=np.uint64), np.full(T, 7, dtype=np.uint64), np.full(T, 7, dtype=np.uint64),
+                np.full((2, T, 3), 7, dtype=np.int64)]
+        hip_ctx.drain()
+        with _env(**env), hip_ctx._lock:
+            th = hip_ctx._traj(c.packed)
+            assert th.c.n_species == S
+            th.c.n_species = S + 1
+            rc = hip_ctx._lib.amof_dihedral_hist(hip_ctx._h, ctypes.byref(th.c), _hip._ptr(rcm), _hip._ptr(idx), T, _hip._ptr(edges), nb,
+                                                 *[_hip._ptr(x) for x in outs])
+        assert rc == _hip.AMOF_OK
+        return outs
+
+    hip_ctx.cn_count(c.packed, rcm4, [(1, 2)])          # (another family's path name: C-N within 1.7)
+    before = hip_ctx.last_path()
+    assert before.startswith("cn_")
+    got = call({})
+    assert hip_ctx.last_path() == before
+    exact = call(EXACT)
+    assert hip_ctx.last_path() == "dihedral_exact"
+    assert _same(got, exact) and not any(x.any() for x in got)
+    ref.check(got, ref.trajectory(c.packed, {'C-N': 0.0}, cases.patterns(c)[1], edges))
+
+
 @pytest.mark.parametrize("env", [{}, EXACT])
 def test_error_paths(hip_ctx, env):
     # a 17th neighbour: the capacity, naming the frame, on either path
