@@ -15,6 +15,7 @@ Analyses beyond the reference:
 
     amof_amd.vanhove.WindowVanHove                self Van Hove function, non-Gaussian parameter
     amof_amd.vanhove_distinct.DistinctVanHove     distinct Van Hove function G_d(r, t) on the same lags
+    amof_amd.vacf.VelocityAutocorrelation         velocity autocorrelation function, vibrational density of states
     amof_amd.structure_factor.StructureFactor     static structure factor S(q) by direct summation over the
                                                   reciprocal lattice (density_modes: rho_a(k) of one frame)
     amof_amd.intermediate_scattering.IntermediateScattering

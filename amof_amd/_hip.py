@@ -37,6 +37,7 @@ EXPORTS = [
     "amof_bad_hist_by_cn",
     "amof_msd_window", "amof_msd_window_dev", "amof_msd_com_dev", "amof_msd_shard_begin", "amof_msd_shard_finish", "amof_msd_direct",
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
+    "amof_vacf_window", "amof_vacf_window_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
     "amof_bond_order", "amof_bond_order_dev", "amof_dihedral_hist", "amof_dihedral_hist_dev", "amof_ring_stats", "amof_ring_search_stats", "amof_fragment_stats", "amof_fragment_round_stats",
     "amof_pore_field", "amof_pore_candidate_bound",
@@ -139,6 +140,10 @@ def load_library():
                                             ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P]
         lib.amof_vanhove_window_dev.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P]
+        lib.amof_vacf_window.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                         ctypes.c_int64, P]
+        lib.amof_vacf_window_dev.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64,
+                                             ctypes.c_int64, P, P]
         lib.amof_vanhove_distinct.argtypes = [P, TP, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                               ctypes.c_double, ctypes.c_int32, P]
         lib.amof_vanhove_distinct_dev.argtypes = lib.amof_vanhove_distinct.argtypes
@@ -763,6 +768,33 @@ class Context(Lane):
         return out + (th.kinds,)
 
     @_locked
+    def vacf_window(self, packed, windows, origin_stride=1, velocities=False, remove_com=True, atom_range=None, com=None, out=None):
+        """``(sums [S][W] f64, kinds)``: the raw velocity-autocorrelation sums of ``amof_vacf_window`` -- over the atoms of
+        ``atom_range``, the three coordinates and the origins of every lag, of x(k) x(k + m); x: the wrapped steps of
+        ``msd_window`` (Angstrom), or with ``velocities`` the trajectory's own values minus the frame's mass-weighted mean.
+
+        ``out``: optional torch CUDA f64 tensor ``[S][W]`` the sums are ADDED into on the device (stays resident for the
+        ranks' all-reduce); ``com``: optional torch CUDA f64 ``[F][3]`` precomputed centre of mass (``msd_com``)."""
+        th = self._traj(packed)
+        windows = _i32(windows)
+        a0, a1 = _span(atom_range, th.n_atoms)
+        args = (self._h, ctypes.byref(th.c), _ptr(windows), len(windows), int(origin_stride), 1 if velocities else 0,
+                1 if remove_com else 0, int(a0), int(a1))
+        if out is not None or com is not None:
+            import torch
+            if out is None:
+                out = torch.zeros((th.S, len(windows)), dtype=torch.float64, device=torch.device("cuda", self.device))
+            self._check_out(out, th.S * len(windows))
+            if com is not None:
+                self._check_out(com, 3 * th.n_frames)
+            self._order_after_torch()
+            self._check(self._lib.amof_vacf_window_dev(*args, _ptr(com), _ptr(out)))
+            return out, th.kinds
+        out = np.zeros((th.S, len(windows)), dtype=np.float64)
+        self._check(self._lib.amof_vacf_window(*args, _ptr(out)))
+        return out, th.kinds
+
+    @_locked
     def vanhove_distinct(self, packed, windows, rmax, nbins, origin_stride=1, work_range=None, out=None):
         """``(hist [S][S][W][nbins] u64, kinds)``: the distinct Van Hove counts of ``amof_vanhove_distinct`` for the entries
         ``work_range`` (default: all) of the lag-major (lag, origin) work list (amof_amd.lags.work_list).
@@ -1339,6 +1371,11 @@ class MultiContext(object):
         """atoms sharded over the devices; the integer counts add up exactly, the moments up to float64 summation order"""
         return self._sharded("vanhove_window", packed, _span(atom_range, packed.n_atoms), "atom_range",
                              ("sum", "sum", "sum", "first"), windows, dr, nbins, unwrap=unwrap, remove_com=remove_com)
+
+    def vacf_window(self, packed, windows, origin_stride=1, velocities=False, remove_com=True, atom_range=None):
+        """atoms sharded over the devices; the sums add up to float64 summation order"""
+        return self._sharded("vacf_window", packed, _span(atom_range, packed.n_atoms), "atom_range", ("sum", "first"), windows,
+                             origin_stride=origin_stride, velocities=velocities, remove_com=remove_com)
 
     def vanhove_distinct(self, packed, windows, rmax, nbins, origin_stride=1, work_range=None):
         """the (lag, origin) work list sharded over the devices: the integer counts add up exactly"""

@@ -127,6 +127,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations;
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
+ * after amof_vacf_window[_dev]: 2 the columns, 3 the correlation kernel with its reduction.
  * after amof_dihedral_hist[_dev]: 2 the list stage (the adjacency rows on "dihedral_exact"), 3 the dihedral kernels.
  * after amof_ring_stats: 2 the adjacency rows, 3 the breadth-first searches (distance table, candidates), 4 the ring search.
  * after amof_fragment_stats: 2 the adjacency rows (the link rows included), 3 the labelling (bond images and rounds), 4 the
@@ -154,6 +155,9 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        "msd_global" (series too long for LDS), "msd_direct", "msd_com" (amof_msd_com_dev alone)
  *   Van Hove "msd_vanhove" (u32 counters in LDS, lag tiles), "msd_vanhove_global" (u64 counters in global memory: more than
  *        AMOF_MAX_LDS_BINS bins, or AMOF_VANHOVE_GLOBAL=1)
+ *   VACF "vacf_lds" (every lag from 0, origin stride 1: a column and a zero tail in LDS, consecutive lags per lane),
+ *        "vacf_general" (a thread per block of atoms and lag on the columns in device memory: any window list, any origin
+ *        stride, series beyond the LDS; also AMOF_VACF_GENERAL=1)
  *   S(q) "sq" (counters in LDS), "sq_bin_global" (counters in global memory: (P + 1) nbins beyond the LDS budget, or
  *        AMOF_SQ_GLOBAL=1), "sq_modes" (amof_sq_modes)
  *   distinct Van Hove "rdf_distinct_tile" (constant diagonal cell, all axes periodic, one image in reach: quantised frames,
@@ -333,6 +337,35 @@ int amof_vanhove_window_dev(amof_ctx *ctx, const amof_traj *traj, const int32_t 
                             int32_t remove_com, int64_t atom_begin, int64_t atom_end, double dr, int32_t nbins,
                             const double *com_dev /* device [F][3] or NULL */, uint64_t *counts_dev /* device [S][W][nbins], += */,
                             uint64_t *overflow_dev /* device [S][W], += */, double *moments_dev /* device [S][W][2], += */);
+
+/*
+ * Velocity autocorrelation sums (window form).
+ * Replaces nothing the reference computes (the reference has no velocity analysis).
+ *   Samples x_ic(k), coordinate c of atom i:
+ *     velocity_mode == 0: the wrapped step of atom i from frame k - 1 to frame k, k = 1 .. F - 1, exactly as amof_msd_window
+ *       forms it without unwrap (the earlier frame's cell; remove_com as there).  The caller divides by the timestep.
+ *     velocity_mode != 0: traj's "positions" are velocities; x(k) = frame k's value minus, with remove_com, the mass-weighted
+ *       mean of the frame over ALL atoms.  No wrap; the cell is ignored.
+ *   Lags m = windows[w] and their origins k = 1, 1 + s, ... <= F - m - 1 (s = origin_stride >= 1): amof_vanhove_distinct's rule
+ *   (stated there); sample 0 is never used.
+ *     sums[s*W + w] = sum over atoms i of species s in [atom_begin, atom_end), c and the origins k of lag w of
+ *                     x_ic(k) * x_ic(k + m)
+ *   Order of summation: the atoms of a species in blocks of 8 (in atom order), one accumulator per block and lag updated with
+ *   fma over the block's columns (atom, then c) and k ascending; the blocks of a species added in order.  No float atomics: two
+ *   identical calls give identical bits, and so do the two kernels ("vacf_lds", "vacf_general": amof_last_path).
+ *   amof_last_kernel_seconds: which = 2 the columns, 3 the correlation with its reduction.
+ * The host form overwrites sums.  Errors: AMOF_EINVAL (bad window, stride, range, NULL argument), AMOF_ENOMEM, AMOF_EHIP,
+ * AMOF_ENODEVICE.
+ */
+int amof_vacf_window(amof_ctx *ctx, const amof_traj *traj, const int32_t *windows /* host [W] */, int32_t n_windows,
+                     int64_t origin_stride, int32_t velocity_mode, int32_t remove_com, int64_t atom_begin, int64_t atom_end,
+                     double *sums /* host [S][W] */);
+/* The same with the sums ADDED into a device buffer (atom-sharded ranks all-reduce it next) and, optionally, the per-frame
+ * centre of mass -- in velocity mode the per-frame mean velocity -- handed in (com_dev: device [F][3] from amof_msd_com_dev,
+ * NULL = computed here from all atoms). */
+int amof_vacf_window_dev(amof_ctx *ctx, const amof_traj *traj, const int32_t *windows, int32_t n_windows,
+                         int64_t origin_stride, int32_t velocity_mode, int32_t remove_com, int64_t atom_begin, int64_t atom_end,
+                         const double *com_dev /* device [F][3] or NULL */, double *sums_dev /* device [S][W], += */);
 
 /*
  * Distinct Van Hove function: pair-distance histograms between two frames of a trajectory.
