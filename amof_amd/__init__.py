@@ -16,6 +16,9 @@ Analyses beyond the reference:
     amof_amd.vanhove.WindowVanHove                self Van Hove function, non-Gaussian parameter
     amof_amd.vanhove_distinct.DistinctVanHove     distinct Van Hove function G_d(r, t) on the same lags
     amof_amd.vacf.VelocityAutocorrelation         velocity autocorrelation function, vibrational density of states
+    amof_amd.current_correlation.CurrentCorrelation
+                                                  longitudinal and transverse current correlations C_L(q, t), C_T(q, t), their
+                                                  spectra, dispersion and sound velocities (also ``amof_amd.CurrentCorrelation``)
     amof_amd.structure_factor.StructureFactor     static structure factor S(q) by direct summation over the
                                                   reciprocal lattice (density_modes: rho_a(k) of one frame)
     amof_amd.intermediate_scattering.IntermediateScattering
@@ -42,4 +45,7 @@ def __getattr__(name):
     if name == "Dihedral":
         from .dihedral import Dihedral
         return Dihedral
+    if name == "CurrentCorrelation":
+        from .current_correlation import CurrentCorrelation
+        return CurrentCorrelation
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -44,6 +44,7 @@ EXPORTS = [
     "amof_pore_access", "amof_pore_access_field", "amof_pore_psd", "amof_pore_psd_field", "amof_pore_cover_stats",
     "amof_pore_surface", "amof_pore_surface_bound", "amof_pore_surface_stats",
     "amof_sq_accumulate", "amof_sq_accumulate_dev", "amof_sq_modes", "amof_isf_accumulate", "amof_isf_accumulate_dev",
+    "amof_current_modes", "amof_current_accumulate", "amof_current_accumulate_dev",
     "amof_xyz_scan", "amof_xyz_read", "amof_xyz_open", "amof_xyz_read_frames", "amof_xyz_close", "amof_cp2k_cell_read", "amof_ingest_last_error",
     "amof_pack_frames", "amof_frames_checksum",
 ]
@@ -184,6 +185,10 @@ def load_library():
                                             ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P]
         lib.amof_isf_accumulate_dev.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64,
                                                 ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P, P]
+        lib.amof_current_modes.argtypes = [P, TP, TP, ctypes.c_int64, ctypes.c_int32, P, ctypes.c_int32, P]
+        lib.amof_current_accumulate.argtypes = [P, TP, TP, ctypes.c_int32, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int64,
+                                                ctypes.c_int64, ctypes.c_int64, ctypes.c_double, ctypes.c_int32, P, P, P, P, P, P]
+        lib.amof_current_accumulate_dev.argtypes = lib.amof_current_accumulate.argtypes
         lib.amof_xyz_scan.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]
         lib.amof_xyz_read.argtypes = [ctypes.c_char_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                       P, P, P, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]
@@ -216,6 +221,15 @@ def isf_layout(S, W, nbins, self_part=True):
     n = W * nbins
     lay = {"counts": 0, "beyond": n, "coh": n + W, "self": n + W + S * S * n}
     lay["size"] = lay["self"] + (S * n if self_part else 0)
+    return lay
+
+
+def current_layout(S, W, nbins):
+    """word offsets of the one int64 tensor ``Context.current_accumulate(out=...)`` adds into: ``counts [W][nbins]``,
+    ``beyond [W]``, ``long [S][S][W][nbins]``, ``trans [S][S][W][nbins]``, and its ``size``"""
+    n = W * nbins
+    lay = {"counts": 0, "beyond": n, "long": n + W, "trans": n + W + S * S * n}
+    lay["size"] = lay["trans"] + S * S * n
     return lay
 
 
@@ -1223,6 +1237,69 @@ class Context(Lane):
         beyond = np.zeros(W, dtype=np.uint64)
         self._check(self._lib.amof_isf_accumulate(*args, _ptr(counts), _ptr(coh), _ptr(selfs), _ptr(beyond)))
         return counts, coh, selfs, beyond, th.kinds
+
+    def _velocity_traj(self, packed, velocities):
+        """``(handle or None, pointer or None)`` of the velocity trajectory of ``amof_current_*``: the same frames and atoms
+        as ``packed``; only its array is read"""
+        if velocities is None:
+            return None, None
+        if velocities.n_frames != packed.n_frames or velocities.n_atoms != packed.n_atoms:
+            raise ValueError("velocities: other frames or atoms than the positions")
+        vh = self._traj(velocities)
+        return vh, ctypes.byref(vh.c)
+
+    @_locked
+    def current_modes(self, packed, hkl, frame=1, velocities=None, remove_com=True):
+        """``(j [K][S][3] complex128, kinds)``: j_a(k) of the sample on frame ``frame`` >= 1 for the vectors ``hkl``
+        (``amof_current_modes``), in Angstrom per frame (``velocities``, a PackedTrajectory of velocities: its units)"""
+        th = self._traj(packed)
+        vh, vp = self._velocity_traj(packed, velocities)
+        hkl = _hkl(hkl)
+        j = np.zeros((len(hkl), th.S, 3, 2), dtype=np.float64)
+        self._check(self._lib.amof_current_modes(self._h, ctypes.byref(th.c), vp, int(frame), 1 if remove_com else 0, _ptr(hkl),
+                                                 len(hkl), _ptr(j)))
+        return j[..., 0] + 1j * j[..., 1], th.kinds
+
+    @_locked
+    def current_accumulate(self, packed, hkl, windows, dq, nbins, origin_stride=1, work_range=None, velocities=None,
+                           remove_com=True, recip=None, out=None):
+        """``(counts [W][nbins] u64, long [S][S][W][nbins] f64, trans [S][S][W][nbins] f64, beyond [W] u64, scale_log2 [P],
+        vmax, kinds)`` of ``amof_current_accumulate``: the current correlations of the vectors ``hkl`` over the entries
+        ``work_range`` (default: all) of the lag-major (lag, origin) work list; ``[a][c]``: species a at the origin, c at the
+        origin + lag.  ``velocities``: a PackedTrajectory of velocities for the same frames (default: finite differences).
+
+        ``out``: optional torch CUDA int64 tensor of ``current_layout(S, W, nbins)["size"]`` words (counts, beyond, fixed-point
+        long and trans) the results are ADDED into on the device; returns ``(out, scale_log2, vmax, kinds)`` then."""
+        th = self._traj(packed)
+        vh, vp = self._velocity_traj(packed, velocities)
+        hkl, windows, recip = _hkl(hkl), _i32(windows), _recip(packed, recip)
+        S, W, nbins = th.S, len(windows), int(nbins)
+        if work_range is None:
+            work_range = _whole_work_list(th.n_frames, windows, origin_stride)
+        scale = np.zeros(S * (S + 1) // 2, dtype=np.int32)
+        vmax = np.zeros(1, dtype=np.float64)
+        args = (self._h, ctypes.byref(th.c), vp, 1 if remove_com else 0, _ptr(recip), _ptr(hkl), len(hkl), _ptr(windows), W,
+                int(origin_stride), int(work_range[0]), int(work_range[1]), float(dq), nbins)
+        if out is not None:
+            lay = current_layout(S, W, nbins)
+            self._check_out(out, lay["size"])
+            part = [ctypes.c_void_p(out.data_ptr() + 8 * lay[k]) for k in ("counts", "long", "trans", "beyond")]
+            self._order_after_torch()
+            self._check(self._lib.amof_current_accumulate_dev(*args, part[0], part[1], part[2], part[3], _ptr(scale), _ptr(vmax)))
+            return out, scale, float(vmax[0]), th.kinds
+        counts = np.zeros((W, nbins), dtype=np.uint64)
+        lng = np.zeros((S, S, W, nbins), dtype=np.float64)
+        trn = np.zeros((S, S, W, nbins), dtype=np.float64)
+        beyond = np.zeros(W, dtype=np.uint64)
+        self._check(self._lib.amof_current_accumulate(*args, _ptr(counts), _ptr(lng), _ptr(trn), _ptr(beyond), _ptr(scale), _ptr(vmax)))
+        return counts, lng, trn, beyond, scale, float(vmax[0]), th.kinds
+
+    def last_current_stage_seconds(self):
+        """``{"records", "table", "corr"}``: kernel seconds of the stages of the last ``current_accumulate``
+        (amof_last_kernel_seconds 2 .. 4)"""
+        self.drain()
+        with self._lock:
+            return {name: self._lib.amof_last_kernel_seconds(self._h, 2 + i) for i, name in enumerate(("records", "table", "corr"))}
 
     def last_stage_seconds(self, pore=False):
         """``{"rho", "corr", "self"}``: kernel seconds of the stages of the last ``isf_accumulate`` (amof_last_kernel_seconds

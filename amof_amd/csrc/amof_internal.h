@@ -91,6 +91,7 @@ struct amof_ctx {
     int64_t shard_ticket = 0;     // `calls` right after a begin; 0 = none pending
     int64_t shard_key[7] = {0, 0, 0, 0, 0, 0, 0};
     // kernel seconds of the stages of the last amof_isf_accumulate[_dev]: rho table (with the quantisation), correlation, self;
+    // of the last amof_current_accumulate[_dev]: records, table, correlation;
     // of the last amof_bond_survival[_dev]: lists, series, correlations (StageSpans); the fourth: amof_pore_psd's covering stage;
     // the fifth: amof_pore_surface's surface stage
     double stage_seconds[5] = {-1.0, -1.0, -1.0, -1.0, -1.0};

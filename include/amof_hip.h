@@ -128,6 +128,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
  * after amof_vacf_window[_dev]: 2 the columns, 3 the correlation kernel with its reduction.
+ * after amof_current_accumulate[_dev]: 2 the records (means and vmax included), 3 the table, 4 the correlation kernel.
  * after amof_dihedral_hist[_dev]: 2 the list stage (the adjacency rows on "dihedral_exact"), 3 the dihedral kernels.
  * after amof_ring_stats: 2 the adjacency rows, 3 the breadth-first searches (distance table, candidates), 4 the ring search.
  * after amof_fragment_stats: 2 the adjacency rows (the link rows included), 3 the labelling (bond images and rounds), 4 the
@@ -949,6 +950,65 @@ int amof_isf_accumulate_dev(amof_ctx *ctx, const amof_traj *traj, const double *
                             int64_t *coh_dev /* device [S][S][W][nbins], += */,
                             int64_t *self_dev /* device [S][W][nbins] or NULL, += */, uint64_t *beyond_dev /* device [W], += */,
                             int32_t *scale_log2 /* host [P] */);
+
+/*
+ * Current correlation functions C_L(q, t) and C_T(q, t): the time correlation of the particle current
+ *   j_a(k, t) = sum over the atoms j of species a of v_j(t) exp(i k . r_j(t))
+ * on reciprocal-lattice vectors, projected along (longitudinal) and across (transverse) k.  The collective counterpart of
+ * amof_vacf_window; replaces nothing the reference computes.  Cells must be periodic on all three axes.  recip, hkl, dq,
+ * nbins, the lags, origins and the work list: as amof_isf_accumulate.  The library works in Angstrom per frame (velocity
+ * mode: the input's units); the caller divides by the timestep.
+ *   Sample of atom j on frame f >= 1 (a sample of the positions mode lives on the half step f - 1/2):
+ *     positions mode (vel == NULL): d = the signed int32 reading of Q_j(f) - Q_j(f - 1) per fractional component (u32
+ *       wrap-around arithmetic on quantize_atom's coordinates, each frame in its own cell: the device of the self part of
+ *       F(q, t)); s = (double)d * 2^-32; v_c = fma(s_z, C[2][c], fma(s_y, C[1][c], s_x * C[0][c])) with C the cell of frame
+ *       f.  Phase position: p = Q_j(f - 1) + (uint32)(d >> 1) per component (arithmetic shift), the midpoint.
+ *     velocity mode (vel: a second amof_traj whose pos holds velocities [F][N][3] of the same frames and atoms; nothing else
+ *       of it is read): v = vel[f][j], p = Q_j(f).
+ *     remove_com != 0: the mass-weighted mean sample of the frame, sum_j m_j v_j / sum_j m_j (float64, a fixed order, no
+ *       float atomics: identical calls, identical bits), is subtracted.  Then w = (float)v per component.
+ *   Modes: j_a(f; hkl)[c] = sum_j w_j[c] exp(2 pi i phi_j / 2^32), phi_j = h p_x + k p_y + l p_z (mod 2^32: the exact
+ *     phase).  Per (atom, vector): x = (float)(int32)phi * 2^-32, v_cos_f32 / v_sin_f32 of x once, six fmaf with w into f32
+ *     partials over at most 64 atoms of the species (stable species order), the partials folded into float64 in a fixed
+ *     order.  Identical calls give identical bits; the result does not depend on how the vectors are cut into runs or chunks.
+ *   Projection (float64, no fma), per frame with ITS reciprocal matrix R: q = (h R0 + k R1) + l R2 per component,
+ *     n = sqrt((qx qx + qy qy) + qz qz), k^ = q / n;  L_a = (k^x j_x + k^y j_y) + k^z j_z for the real and for the imaginary
+ *     parts;  T_a[c] = j_a[c] - k^[c] L_a likewise.
+ *   Sums, per work entry (w, k), vector and ORDERED species pair (a at the origin k, c at k + m): the bin b and beyond[w]
+ *     from frame k as in amof_isf_accumulate; counts[w][b] += 1;
+ *       t_L = Re L_a(k) Re L_c(k + m) + Im L_a(k) Im L_c(k + m)
+ *       t_T = ((Tx.Tx') + (Ty.Ty')) + (Tz.Tz'),  each (T.T') = Re T Re T' + Im T Im T'   (no factor 1/2)
+ *       long[a][c][w][b] += rint(t_L * 2^s_p),  trans[a][c][w][b] += rint(t_T * 2^s_p)  as int64 (integer atomics).
+ *   Scale: vmax = the largest |w| component over ALL frames 1 .. F - 1 of the trajectory (an exact maximum, whatever the
+ *     work range: ranks and work ranges arrive at the same exponents); per unordered pair p = {a, c}, 2^s_p is the largest
+ *     power of two with F C (N_a N_c + 1/2) 3 vmax^2 2^s_p < 2^62 (amof_sq_accumulate's bound times 3 vmax^2), C its bin
+ *     capacity: the sums stay below 2^62 + F C / 2 < 2^63.  vmax == 0:
+ *     zero sums, scale_log2 == 0.  AMOF_ECAPACITY when 2^-s_p > 2^-20 * 3 vmax^2 sqrt(N_a N_c).
+ *   The table of a chunk of vectors ([frames touched][K_c][S][3][2] float64) is kept within 1 GiB
+ *   (AMOF_CURRENT_RHO_BUDGET, bytes, overrides).  AMOF_CURRENT_GLOBAL=1: counters in global memory ("current_global").
+ * amof_current_modes: j of one frame >= 1, written out: j[((m*S + a)*3 + c)*2 + 0 / 1].
+ * The host form overwrites counts, long_sums, trans_sums (float64: int64 * 2^-s) and beyond; both forms write scale_log2
+ * (host [P], amof_sq_accumulate's pair order) and *vmax.  amof_last_kernel_seconds: 2 the records (means and vmax included),
+ * 3 the table, 4 the correlation.
+ * Errors: as amof_isf_accumulate, plus AMOF_EINVAL for velocities of another shape, not finite or beyond float32, missing
+ * masses with remove_com, and a frame < 1 in amof_current_modes.
+ */
+int amof_current_modes(amof_ctx *ctx, const amof_traj *traj, const amof_traj *vel_or_NULL, int64_t frame, int32_t remove_com,
+                       const int32_t *hkl /* host [K][3] */, int32_t K, double *j /* host [K][S][3][2] */);
+int amof_current_accumulate(amof_ctx *ctx, const amof_traj *traj, const amof_traj *vel_or_NULL, int32_t remove_com,
+                            const double *recip /* host [n_cells][3][3] */, const int32_t *hkl /* host [K][3] */, int32_t K,
+                            const int32_t *windows /* host [W] */, int32_t n_windows, int64_t origin_stride, int64_t work_begin,
+                            int64_t work_end, double dq, int32_t nbins, uint64_t *counts /* host [W][nbins] */,
+                            double *long_sums /* host [S][S][W][nbins] */, double *trans_sums /* host [S][S][W][nbins] */,
+                            uint64_t *beyond /* host [W] */, int32_t *scale_log2 /* host [P] */, double *vmax /* host [1] */);
+/* The same with the results ADDED into device buffers (int64 fixed point: value = sum * 2^-scale_log2[p]): ranks that share
+ * the work list all-reduce them next. */
+int amof_current_accumulate_dev(amof_ctx *ctx, const amof_traj *traj, const amof_traj *vel_or_NULL, int32_t remove_com,
+                                const double *recip, const int32_t *hkl, int32_t K, const int32_t *windows, int32_t n_windows,
+                                int64_t origin_stride, int64_t work_begin, int64_t work_end, double dq, int32_t nbins,
+                                uint64_t *counts_dev /* device [W][nbins], += */, int64_t *long_dev /* device [S][S][W][nbins], += */,
+                                int64_t *trans_dev /* device [S][S][W][nbins], += */, uint64_t *beyond_dev /* device [W], += */,
+                                int32_t *scale_log2 /* host [P] */, double *vmax /* host [1] */);
 
 /*
  * Direct MSD with running unwrap, orthogonal cells only (deprecated in the reference).
