@@ -215,22 +215,29 @@ def pore_surface_bound(cell, reach):
     return float(load_library().amof_pore_surface_bound(_ptr(cell), float(reach)))
 
 
-def isf_layout(S, W, nbins, self_part=True):
-    """word offsets of the one int64 tensor ``Context.isf_accumulate(out=...)`` adds into: ``counts [W][nbins]``, ``beyond
-    [W]``, ``coh [S][S][W][nbins]``, ``self [S][W][nbins]`` (absent without ``self_part``), and its ``size``"""
+def lag_layout(S, W, nbins, blocks):
+    """word offsets of the one int64 tensor a lag analysis adds into: ``counts [W][nbins]``, ``beyond [W]``, then every
+    ``(name, rows)`` of ``blocks`` as ``[rows][W][nbins]`` in order (rows = 0: the name keeps its place and takes no word),
+    and its ``size``"""
     n = W * nbins
-    lay = {"counts": 0, "beyond": n, "coh": n + W, "self": n + W + S * S * n}
-    lay["size"] = lay["self"] + (S * n if self_part else 0)
+    lay = {"counts": 0, "beyond": n}
+    at = n + W
+    for name, rows in blocks:
+        lay[name] = at
+        at += rows * n
+    lay["size"] = at
     return lay
+
+
+def isf_layout(S, W, nbins, self_part=True):
+    """``lag_layout`` of ``Context.isf_accumulate(out=...)``: ``coh [S][S][W][nbins]``, ``self [S][W][nbins]`` (absent without
+    ``self_part``)"""
+    return lag_layout(S, W, nbins, (("coh", S * S), ("self", S if self_part else 0)))
 
 
 def current_layout(S, W, nbins):
-    """word offsets of the one int64 tensor ``Context.current_accumulate(out=...)`` adds into: ``counts [W][nbins]``,
-    ``beyond [W]``, ``long [S][S][W][nbins]``, ``trans [S][S][W][nbins]``, and its ``size``"""
-    n = W * nbins
-    lay = {"counts": 0, "beyond": n, "long": n + W, "trans": n + W + S * S * n}
-    lay["size"] = lay["trans"] + S * S * n
-    return lay
+    """``lag_layout`` of ``Context.current_accumulate(out=...)``: ``long [S][S][W][nbins]``, ``trans [S][S][W][nbins]``"""
+    return lag_layout(S, W, nbins, (("long", S * S), ("trans", S * S)))
 
 
 def reciprocal(cell):
@@ -1204,6 +1211,17 @@ class Context(Lane):
         self._check(self._lib.amof_sq_accumulate(*args, _ptr(counts), _ptr(sums), _ptr(beyond)))
         return counts, sums, int(beyond[0]), th.kinds
 
+    def _lag_args(self, th, packed, hkl, windows, dq, nbins, origin_stride, work_range, recip, extra=()):
+        """what ``amof_isf_accumulate`` and ``amof_current_accumulate`` take alike: ``(W, args, held)`` -- args the argument
+        tuple up to ``nbins``, ``extra`` behind the trajectory; held: the arrays args points into (hkl, windows, recip)"""
+        hkl, windows, recip = _hkl(hkl), _i32(windows), _recip(packed, recip)
+        if work_range is None:
+            work_range = _whole_work_list(th.n_frames, windows, origin_stride)
+        args = (self._h, ctypes.byref(th.c)) + tuple(extra) + (
+            _ptr(recip), _ptr(hkl), len(hkl), _ptr(windows), len(windows), int(origin_stride), int(work_range[0]),
+            int(work_range[1]), float(dq), int(nbins))
+        return len(windows), args, (hkl, windows, recip)
+
     @_locked
     def isf_accumulate(self, packed, hkl, windows, dq, nbins, origin_stride=1, work_range=None, self_part=True, recip=None,
                        out=None):
@@ -1216,12 +1234,8 @@ class Context(Lane):
         fixed-point coh, fixed-point self) the results are ADDED into on the device; returns ``(out, scale_log2, kinds)``
         then, with coh[a][c] = ``coh * 2**-scale_log2[p]``, p the unordered pair of ``sq_accumulate``'s order."""
         th = self._traj(packed)
-        hkl, windows, recip = _hkl(hkl), _i32(windows), _recip(packed, recip)
-        S, W, nbins = th.S, len(windows), int(nbins)
-        if work_range is None:
-            work_range = _whole_work_list(th.n_frames, windows, origin_stride)
-        args = (self._h, ctypes.byref(th.c), _ptr(recip), _ptr(hkl), len(hkl), _ptr(windows), W, int(origin_stride),
-                int(work_range[0]), int(work_range[1]), float(dq), nbins)
+        W, args, held = self._lag_args(th, packed, hkl, windows, dq, nbins, origin_stride, work_range, recip)
+        S, nbins = th.S, int(nbins)
         if out is not None:
             lay = isf_layout(S, W, nbins, self_part)
             self._check_out(out, lay["size"])
@@ -1272,14 +1286,11 @@ class Context(Lane):
         long and trans) the results are ADDED into on the device; returns ``(out, scale_log2, vmax, kinds)`` then."""
         th = self._traj(packed)
         vh, vp = self._velocity_traj(packed, velocities)
-        hkl, windows, recip = _hkl(hkl), _i32(windows), _recip(packed, recip)
-        S, W, nbins = th.S, len(windows), int(nbins)
-        if work_range is None:
-            work_range = _whole_work_list(th.n_frames, windows, origin_stride)
+        W, args, held = self._lag_args(th, packed, hkl, windows, dq, nbins, origin_stride, work_range, recip,
+                                       extra=(vp, 1 if remove_com else 0))
+        S, nbins = th.S, int(nbins)
         scale = np.zeros(S * (S + 1) // 2, dtype=np.int32)
         vmax = np.zeros(1, dtype=np.float64)
-        args = (self._h, ctypes.byref(th.c), vp, 1 if remove_com else 0, _ptr(recip), _ptr(hkl), len(hkl), _ptr(windows), W,
-                int(origin_stride), int(work_range[0]), int(work_range[1]), float(dq), nbins)
         if out is not None:
             lay = current_layout(S, W, nbins)
             self._check_out(out, lay["size"])

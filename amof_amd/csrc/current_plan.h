@@ -1,5 +1,5 @@
-// The host decisions of the current correlation functions C_L(q, t) and C_T(q, t) (sq.hip, amof_current_*): the runs a
-// thread of current_rho_kernel owns, the fixed-point scales, the vector chunks, the counter tiles and the grid of
+// The host decisions of the current correlation functions C_L(q, t) and C_T(q, t) (current.hip, amof_current_*): the runs a
+// thread of current_rho_kernel owns, the fixed-point scales, the vector chunks and the counter tiles of
 // current_corr_kernel -- and the constants those decisions share with the kernels.  Everything else (species order, bin
 // capacity, touched frames, the work list) is sq_plan.h's and lag_work.h's, unchanged.  Host only (no HIP dependency: the
 // CPU test suite compiles it with g++, tests/test_current_plan_cpu.py through tests/native/current_plan_driver.cpp).
@@ -16,10 +16,10 @@ namespace amof {
 // 6: 125, 4 waves; 8: 163, 3 waves.  4 keeps five waves in flight for the two transcendentals per vector and amortises the
 // three integer multiplies and the two scalar record loads of an atom over four vectors.
 constexpr int CUR_RUN = 4;
-constexpr int CUR_THREADS = 256;            // current_rho_kernel and current_corr_kernel
-constexpr int CUR_SMAX = 4;                 // species counts whose 2 S^2 sums current_corr_kernel keeps in registers
-constexpr int CUR_OPW = 64;                 // at most this many origins per workgroup
-constexpr size_t CUR_LDS_BUDGET = 64 * 1024;
+constexpr int CUR_THREADS = LAG_THREADS;    // current_rho_kernel and current_corr_kernel
+constexpr int CUR_SMAX = LAG_SMAX;          // species counts whose 2 S^2 sums current_corr_kernel keeps in registers
+constexpr int CUR_OPW = LAG_OPW;
+constexpr size_t CUR_LDS_BUDGET = LAG_LDS_BUDGET;
 constexpr size_t CUR_RHO_BUDGET = (size_t)1 << 30;      // bytes of the table [slots][K_c][S][6] f64 of one vector chunk
 
 struct CurSwitches {
@@ -99,42 +99,14 @@ inline void current_cut_chunks(const std::vector<SqRun> &runs, int32_t K, size_t
     isf_cut_chunks(runs, K, slots, 3 * S, budget, ch);
 }
 
-// current_corr_kernel's counters: per-lag LDS tiles (counts, S^2 longitudinal and S^2 transverse sums per bin), as many lags
-// per pass as fit, or global memory
-struct CurPass {
-    size_t tile_ctr = 0;
-    bool global = false;
-    int lags_per_pass = 0;
-    size_t lds = 0;
-    const char *path = "";
-};
-inline CurPass current_pass_plan(int S, int32_t nbins, int W, const CurSwitches &sw)
+// current_corr_kernel's counters: sq_plan.h's rule with two sums per pair (longitudinal and transverse).  Its grid is
+// lag_grid's with an origin tile of 1: a lane walks its origins lag by lag
+using CurPass = LagPass;
+using CurGrid = LagGrid;
+inline LagPass current_pass_plan(int S, int32_t nbins, int W, const CurSwitches &sw)
 {
-    CurPass p;
-    p.tile_ctr = (size_t)(1 + 2 * S * S) * nbins;
-    p.global = p.tile_ctr * sizeof(uint64_t) > CUR_LDS_BUDGET || sw.global;
-    p.lags_per_pass = p.global ? W : (int)std::min<size_t>(W, CUR_LDS_BUDGET / (p.tile_ctr * sizeof(uint64_t)));
-    p.lds = (size_t)p.lags_per_pass * p.tile_ctr * sizeof(uint64_t);
-    p.path = p.global ? "current_global" : "current";
-    return p;
+    return lag_pass_plan(2, S, nbins, W, sw.global, "current", "current_global");
 }
-
-// current_corr_kernel's grid over a chunk of nv vectors and `range` origin indices: enough workgroups to fill the GPU several
-// times over, at most CUR_OPW origins each, and no more than 65535 of them along y
-struct CurGrid {
-    int vblocks;
-    int32_t opw;
-    unsigned gy;
-};
-inline CurGrid current_grid(int nv, int64_t range)
-{
-    CurGrid g;
-    g.vblocks = (nv + CUR_THREADS - 1) / CUR_THREADS;
-    int64_t opw = std::min<int64_t>(CUR_OPW, std::max<int64_t>(1, range * g.vblocks / 2048));
-    opw = std::max<int64_t>(opw, (range + 65534) / 65535);
-    g.opw = (int32_t)opw;
-    g.gy = (unsigned)((range + opw - 1) / opw);
-    return g;
-}
+inline LagGrid current_grid(int nv, int64_t range) { return lag_grid(nv, range, 1); }
 
 }  // namespace amof

@@ -1,4 +1,4 @@
-// The lag/origin work list of the dynamics family (vanhove_distinct.hip, sq.hip's F(q, t), bond.hip), host side (no HIP
+// The lag/origin work list of the dynamics family (vanhove_distinct.hip, isf.hip, current.hip, bond.hip), host side (no HIP
 // dependency: the CPU test suite compiles it with g++, tests/test_lag_work_cpu.py).  Included by amof_internal.h.
 //
 // Lag m = windows[w] has the origins k = 1 + stride o, o = 0 .. n(m) - 1, i.e. every stride-th frame from 1 up to

@@ -1,6 +1,7 @@
-// The host decisions of S(q), density_modes and F(q, t) (sq.hip): the species and hkl orders and the runs a thread of
-// sq_rho_kernel owns, the fixed-point scales, the S(q) frame batch, the frames an F(q, t) call touches, its vector chunks,
-// counter tiles, grids and self-part batches -- and the constants those decisions share with the kernels.  Host only (no HIP
+// The host decisions of S(q) and density_modes (sq.hip) and of F(q, t) (isf.hip): the species and hkl orders and the runs a
+// thread of sq_rho_kernel owns, the fixed-point scales, the S(q) frame batch, the frames a lag call touches, its vector
+// chunks and self-part batches, the counter tiles and the grid of a lag correlation kernel (F(q, t)'s and, through
+// current_plan.h, C(q, t)'s: one rule each) -- and the constants those decisions share with the kernels.  Host only (no HIP
 // dependency, no amof_ctx: the CPU test suite compiles it with g++, tests/test_sq_plan_cpu.py through
 // tests/native/sq_plan_driver.cpp).
 #pragma once
@@ -26,11 +27,15 @@ constexpr size_t SQ_RHO_BUDGET = (size_t)512 << 20;   // bytes of rho per batch 
 constexpr int SQ_BIN_BLOCKS = 1024;         // workgroups of sq_bin_kernel (grid-stride over the samples)
 constexpr size_t SQ_GRID_Y = 65535;         // frames (slots, entries) one launch of a kernel indexed by blockIdx.y can take
 
-constexpr int ISF_THREADS = 256;
+// the lag correlation kernels (isf_corr_kernel, current_corr_kernel): one launch shape, one counter budget
+constexpr int LAG_THREADS = 256;
+constexpr int LAG_SMAX = 4;                 // species counts with a register form
+constexpr int LAG_OPW = 64;                 // at most this many origins per workgroup
+constexpr size_t LAG_LDS_BUDGET = 64 * 1024;
+
+constexpr int ISF_THREADS = LAG_THREADS;
 constexpr int ISF_TILE = 4;                 // origins whose rows a lane holds in registers
-constexpr int ISF_SMAX = 4;                 // species counts with a register form
-constexpr int ISF_OPW = 64;                 // at most this many origins per workgroup
-constexpr size_t ISF_LDS_BUDGET = 64 * 1024;
+constexpr int ISF_SMAX = LAG_SMAX;
 // rho table of one vector chunk: 1 GiB, twice S(q)'s batch.  The table is streamed (1 + W) times whatever its size, but a
 // thread of sq_rho_kernel owns a run of up to 16 vectors and a chunk is cut to whole waves of runs: on the headline shape
 // (5000 frames, 4 species: 320 KB per vector) 512 MB hold ~126 runs -- one whole wave, 13 launches with a tail each, the
@@ -316,42 +321,53 @@ inline void isf_cut_chunks(const std::vector<SqRun> &runs, int32_t K, size_t slo
     for (const IsfChunk &c : ch.chunks) ch.kc_top = std::max(ch.kc_top, c.nv);
 }
 
-// isf_corr_kernel's counters: per-lag LDS tiles, as many lags per pass as fit, or global memory
-struct IsfPass {
-    size_t tile_ctr = 0;        // counters of one lag: counts and S^2 sums
+// The counters of a lag correlation kernel (isf_corr_kernel, current_corr_kernel): per-lag LDS tiles of counts and
+// sums_per_pair S^2 sums per bin, as many lags per pass as fit the budget, or global memory (a tile beyond the budget, or
+// force_global); the two names are the paths the call reports
+struct LagPass {
+    size_t tile_ctr = 0;        // counters of one lag
     bool global = false;
     int lags_per_pass = 0;
     size_t lds = 0;
     const char *path = "";
 };
-inline IsfPass isf_pass_plan(int S, int32_t nbins, int W, const SqSwitches &sw)
+inline LagPass lag_pass_plan(int sums_per_pair, int S, int32_t nbins, int W, bool force_global, const char *lds_path,
+                             const char *global_path)
 {
-    IsfPass p;
-    p.tile_ctr = (size_t)(1 + S * S) * nbins;
-    p.global = p.tile_ctr * sizeof(uint64_t) > ISF_LDS_BUDGET || sw.isf_global;
-    p.lags_per_pass = p.global ? W : (int)std::min<size_t>(W, ISF_LDS_BUDGET / (p.tile_ctr * sizeof(uint64_t)));
+    LagPass p;
+    p.tile_ctr = (size_t)(1 + sums_per_pair * S * S) * nbins;
+    p.global = p.tile_ctr * sizeof(uint64_t) > LAG_LDS_BUDGET || force_global;
+    p.lags_per_pass = p.global ? W : (int)std::min<size_t>(W, LAG_LDS_BUDGET / (p.tile_ctr * sizeof(uint64_t)));
     p.lds = (size_t)p.lags_per_pass * p.tile_ctr * sizeof(uint64_t);
-    p.path = p.global ? "isf_global" : "isf";
+    p.path = p.global ? global_path : lds_path;
     return p;
 }
+using IsfPass = LagPass;        // isf_corr_kernel's: one sum per pair
+inline LagPass isf_pass_plan(int S, int32_t nbins, int W, const SqSwitches &sw)
+{
+    return lag_pass_plan(1, S, nbins, W, sw.isf_global, "isf", "isf_global");
+}
 
-// isf_corr_kernel's grid over a chunk of nv vectors and `range` origin indices.  Origins per workgroup: a multiple of the
-// tile, enough workgroups to fill the GPU several times over, and no more than 65535 of them along y.
-struct IsfGrid {
+// The grid of a lag correlation kernel over a chunk of nv vectors and `range` origin indices.  Origins per workgroup: a
+// multiple of the origin tile a lane holds in registers (ISF_TILE; 1: none), enough workgroups to fill the GPU several times
+// over, at most LAG_OPW origins each, and no more than 65535 workgroups along y.
+struct LagGrid {
     int vblocks;
     int32_t opw;
     unsigned gy;
 };
-inline IsfGrid isf_grid(int nv, int64_t range)
+inline LagGrid lag_grid(int nv, int64_t range, int tile)
 {
-    IsfGrid g;
-    g.vblocks = (nv + ISF_THREADS - 1) / ISF_THREADS;
-    int64_t opw = std::min<int64_t>(ISF_OPW, std::max<int64_t>(ISF_TILE, range * g.vblocks / 2048 / ISF_TILE * ISF_TILE));
-    opw = std::max<int64_t>(opw, ((range + 65534) / 65535 + ISF_TILE - 1) / ISF_TILE * ISF_TILE);
+    LagGrid g;
+    g.vblocks = (nv + LAG_THREADS - 1) / LAG_THREADS;
+    int64_t opw = std::min<int64_t>(LAG_OPW, std::max<int64_t>(tile, range * g.vblocks / 2048 / tile * tile));
+    opw = std::max<int64_t>(opw, ((range + 65534) / 65535 + tile - 1) / tile * tile);
     g.opw = (int32_t)opw;
     g.gy = (unsigned)((range + opw - 1) / opw);
     return g;
 }
+using IsfGrid = LagGrid;        // isf_corr_kernel's: origins ISF_TILE at a time
+inline LagGrid isf_grid(int nv, int64_t range) { return lag_grid(nv, range, ISF_TILE); }
 
 // self part: batches of entries inside the same budget -- D (16 N bytes) and rho_d (16 K S bytes) per entry
 inline size_t isf_self_batch(size_t budget, int64_t N, int32_t K, int S, size_t n_entries)

@@ -6,7 +6,7 @@ current j_a(k, t) = sum_j v_j(t) exp(i k . r_j(t)) on the reciprocal-lattice vec
 C_L(q, omega) and C_T(q, omega) carry the acoustic dispersion; the slopes of their maxima at small q are the longitudinal and
 transverse sound velocities, and with the density the longitudinal, shear and bulk moduli -- an independent route to the
 mechanical numbers of a trajectory.  The modes and the correlation run in the HIP kernels behind ``amof_current_accumulate``
-(amof_amd/csrc/sq.hip; exact u32 phases, int64 fixed-point sums); the host keeps the choice of vectors, the normalisation, the
+(amof_amd/csrc/current.hip; exact u32 phases, int64 fixed-point sums); the host keeps the choice of vectors, the normalisation, the
 Fourier transform and the DataFrames.  The reference has no such analysis.
 """
 
@@ -19,11 +19,10 @@ from ._lazy import Deferred, EmptyUntilComputed
 
 from . import _hip
 from . import data as _data
-from . import dist as _dist
+from . import lag_q
 from . import lags
 from .files import path as _path
 from .frames import PackedTrajectory
-from .structure_factor import enumerate_hkl, n_bins, pair_index
 
 logger = logging.getLogger(__name__)
 
@@ -83,22 +82,7 @@ def combine(counts, long_sums, trans_sums, w, species_n, time, dq, timestep=1):
                          "q": np.tile(np.arange(nbins, dtype=np.float64) * dq, W), "L": L.reshape(-1), "T": T.reshape(-1)})
 
 
-def normalise(data, window):
-    """``data`` divided, lag by lag, by its own t = 0 rows (every column but Time and q)"""
-    window = np.asarray(window)
-    zero = np.flatnonzero(window == 0)
-    if not len(zero):
-        raise ValueError("normalised() needs lag 0 among the windows")
-    W = len(window)
-    nbins = len(data) // W if W else 0
-    out = data.copy()
-    for name in data.columns:
-        if name in ("Time", "q"):
-            continue
-        v = data[name].to_numpy(dtype=np.float64).reshape(W, nbins)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            out[name] = (v / v[zero[0]][None, :]).reshape(-1)
-    return out
+normalise = lag_q.normalise
 
 
 def lag_spacing(time):
@@ -205,81 +189,36 @@ class CurrentCorrelation(Deferred):
 
     def compute_current(self, trajectory, window, time, timestep=1, dq=0.02, qmax=2.0, max_points=None, seed=0, origin_stride=1,
                         remove_com=True, velocities=None, device=None, distributed=None):
-        dq, qmax = float(dq), float(qmax)
-        if not dq > 0:
-            raise ValueError("dq must be positive")
-        nbins = n_bins(qmax, dq)
-        if nbins < 1:
-            raise ValueError("qmax // dq gives no bin")
-        origin_stride = lags.check_origin_stride(origin_stride)
-        packed = lags.pack(trajectory, device)
-        if not all(bool(x) for x in packed.pbc):
-            raise ValueError("C(q, t) needs a cell periodic on all three axes")
-        vel = None
-        if velocities is not None:
+        def pack_velocities(packed):
+            if velocities is None:
+                return None
             if isinstance(velocities, np.ndarray) or _hip._is_torch_tensor(velocities):
-                vel = PackedTrajectory(velocities, packed.cell, packed.numbers)
+                v = PackedTrajectory(velocities, packed.cell, packed.numbers)
             else:
-                vel = lags.pack(velocities, device)
-            if vel.n_frames != packed.n_frames or vel.n_atoms != packed.n_atoms:
+                v = lags.pack(velocities, device)
+            if v.n_frames != packed.n_frames or v.n_atoms != packed.n_atoms:
                 raise ValueError("velocities: other frames or atoms than the positions")
-        window = np.asarray(window, dtype=np.int32)
-        F = len(packed)
-        if len(window) and (window.min() < 0 or window.max() >= max(F, 1)):
-            raise ValueError("lag outside [0, n_frames)")
-        frames = np.arange(1, max(1, F), origin_stride)
-        cells = packed.cell if packed.cell.shape[0] == 1 else packed.cell[frames]
-        hkl = enumerate_hkl(cells, qmax, dq=dq, max_points=max_points, seed=seed)
-        elements = packed.unique_numbers()
-        n_orig = lags.n_origins(F, window, origin_stride)
-        total = int(n_orig.sum())
-        logger.info("Start computing C(q, t) at %s times, %s vectors, %s bins, %s (lag, origin) pairs", len(window), len(hkl),
-                    nbins, total)
+            return v
 
-        st = lags.setup(packed, device, distributed)
-        ctx, merge = st.ctx, st.merge
-        work = _dist.shard_range(total, st.rank, st.world) if merge else (0, total)
-        S = len(_hip.packed_species(packed)[0])
-        W = len(window)
-        lay = _hip.current_layout(S, W, nbins)
+        s = lag_q.setup("C(q, t)", logger, trajectory, window, dq, qmax, max_points, seed, origin_stride, device, distributed,
+                        after_pack=pack_velocities)
+        vel = s.own
+        ctx, merge = s.st.ctx, s.st.merge
+        lay = _hip.current_layout(s.S, s.W, s.nbins)
 
         def local():
-            # this rank's kernels (a lane job: amof_amd/_lazy.py)
-            lags.begin_local(st.source)
-            flat = None
-            if merge:
-                # integer fixed-point sums at a scale every rank arrives at: the shares add up exactly.  ONE int64 tensor
-                import torch
-                flat = torch.zeros(lay["size"], dtype=torch.int64, device=torch.device("cuda", ctx.device))
-            try:
-                return ctx.current_accumulate(packed, hkl, window, dq, nbins, origin_stride=origin_stride, work_range=work,
-                                              velocities=vel, remove_com=remove_com, out=flat)
-            except _hip.AmofError as e:
-                if e.code != _hip.AMOF_ECAPACITY:
-                    raise
-                raise ValueError("C(q, t): %s.  Remedies: fewer vectors per bin (max_points) or a larger dq; origin_stride "
-                                 "does not help (the scale is set by the trajectory's frame count)" % e) from e
+            return lag_q.local("C(q, t)", s, lay, lambda flat: ctx.current_accumulate(
+                s.packed, s.hkl, s.window, s.dq, s.nbins, origin_stride=s.origin_stride, work_range=s.work, velocities=vel,
+                remove_com=remove_com, out=flat))
 
         def finish(raw):
             if merge:
                 flat, scale, vmax, kinds = raw
-                if st.on_device:
-                    _dist.all_reduce_sum(flat)          # (in HBM)
-                    flat = flat.cpu().numpy()
-                else:
-                    flat = _dist.all_reduce_sum(flat.cpu().numpy(), device=ctx.device)
-                n = W * nbins
-                counts = flat[lay["counts"]:lay["counts"] + n].reshape(W, nbins).view(np.uint64)
-                beyond = flat[lay["beyond"]:lay["beyond"] + W].view(np.uint64)
-                pidx = pair_index(S)
-                exp2 = np.array([[scale[pidx[(min(a, c), max(a, c))]] for c in range(S)] for a in range(S)], dtype=np.int64)
-                lng = np.ldexp(flat[lay["long"]:lay["long"] + S * S * n].reshape(S, S, W, nbins).astype(np.float64),
-                               -exp2[:, :, None, None])
-                trn = np.ldexp(flat[lay["trans"]:lay["trans"] + S * S * n].reshape(S, S, W, nbins).astype(np.float64),
-                               -exp2[:, :, None, None])
+                m = lag_q.Merged(s, lay, flat, scale)
+                counts, beyond, lng, trn = m.counts, m.beyond, m.block("long"), m.block("trans")
             else:
                 counts, lng, trn, beyond, scale, vmax, kinds = raw
-            self._assemble(counts, lng, trn, beyond, kinds, hkl, packed, elements, n_orig, window, time, dq, timestep,
+            self._assemble(counts, lng, trn, beyond, kinds, s.hkl, s.packed, s.elements, s.n_orig, s.window, time, s.dq, timestep,
                            vel is not None, vmax)
 
         self._defer(ctx, local, finish, collective=merge)

@@ -4,7 +4,7 @@
 the lags of ``WindowMsd`` it correlates rho_a(k, t0) with rho_c(k, t0 + t) on the reciprocal-lattice vectors
 ``StructureFactor`` sums over and bins the products by |k|.  At t = 0 the coherent part is S(q); its decay at the first sharp
 diffraction peak is the structural relaxation time.  The self part is the phase sum of every atom's own displacement.  The
-correlation runs in the HIP kernels behind ``amof_isf_accumulate`` (amof_amd/csrc/sq.hip; exact u32 phases, int64
+correlation runs in the HIP kernels behind ``amof_isf_accumulate`` (amof_amd/csrc/isf.hip; exact u32 phases, int64
 fixed-point sums); the host keeps the choice of vectors, the origin bookkeeping, the normalisation and the DataFrame.  The
 reference has no such analysis.
 """
@@ -18,10 +18,9 @@ from ._lazy import Deferred, EmptyUntilComputed
 
 from . import _hip
 from . import data as _data
-from . import dist as _dist
+from . import lag_q
 from . import lags
 from .files import path as _path
-from .structure_factor import enumerate_hkl, n_bins, pair_index
 
 logger = logging.getLogger(__name__)
 
@@ -66,22 +65,7 @@ def assemble(counts, coh, self_sums, kinds, elements, species_counts, time, dq):
     return pd.DataFrame(cols)
 
 
-def normalise(data, window):
-    """``data`` divided, lag by lag, by its own t = 0 rows (every column but Time and q): F(q, t) / F(q, 0)"""
-    window = np.asarray(window)
-    zero = np.flatnonzero(window == 0)
-    if not len(zero):
-        raise ValueError("normalised() needs lag 0 among the windows")
-    W = len(window)
-    nbins = len(data) // W if W else 0
-    out = data.copy()
-    for name in data.columns:
-        if name in ("Time", "q"):
-            continue
-        v = data[name].to_numpy(dtype=np.float64).reshape(W, nbins)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            out[name] = (v / v[zero[0]][None, :]).reshape(-1)
-    return out
+normalise = lag_q.normalise
 
 
 class IntermediateScattering(Deferred):
@@ -134,78 +118,25 @@ class IntermediateScattering(Deferred):
 
     def compute_isf(self, trajectory, window, time, dq=0.02, qmax=5.0, max_points=None, seed=0, origin_stride=1, self_part=True,
                     device=None, distributed=None):
-        dq, qmax = float(dq), float(qmax)
-        if not dq > 0:
-            raise ValueError("dq must be positive")
-        nbins = n_bins(qmax, dq)
-        if nbins < 1:
-            raise ValueError("qmax // dq gives no bin")
-        origin_stride = lags.check_origin_stride(origin_stride)
-        packed = lags.pack(trajectory, device)
-        if not all(bool(x) for x in packed.pbc):
-            raise ValueError("F(q, t) needs a cell periodic on all three axes")
-        window = np.asarray(window, dtype=np.int32)
-        F = len(packed)
-        if len(window) and (window.min() < 0 or window.max() >= max(F, 1)):
-            raise ValueError("lag outside [0, n_frames)")
-        # the origins of lag 0 (a superset of every lag's): StructureFactor(first_frame=1, frame_stride=s)'s frames
-        frames = np.arange(1, max(1, F), origin_stride)
-        cells = packed.cell if packed.cell.shape[0] == 1 else packed.cell[frames]
-        hkl = enumerate_hkl(cells, qmax, dq=dq, max_points=max_points, seed=seed)
-        elements = packed.unique_numbers()
-        n_orig = lags.n_origins(F, window, origin_stride)
-        total = int(n_orig.sum())
-        logger.info("Start computing F(q, t) at %s times, %s vectors, %s bins, %s (lag, origin) pairs", len(window), len(hkl),
-                    nbins, total)
-
-        st = lags.setup(packed, device, distributed)
-        ctx, merge = st.ctx, st.merge
-        work = _dist.shard_range(total, st.rank, st.world) if merge else (0, total)
-        S = len(_hip.packed_species(packed)[0])
-        W = len(window)
-        lay = _hip.isf_layout(S, W, nbins, self_part)
+        s = lag_q.setup("F(q, t)", logger, trajectory, window, dq, qmax, max_points, seed, origin_stride, device, distributed)
+        ctx, merge = s.st.ctx, s.st.merge
+        lay = _hip.isf_layout(s.S, s.W, s.nbins, self_part)
 
         def local():
-            # this rank's kernels (a lane job: amof_amd/_lazy.py)
-            lags.begin_local(st.source)
-            flat = None
-            if merge:
-                # integer fixed-point sums: the ranks' shares add up exactly, whatever the split.  Counts, beyond, coh
-                # and self in ONE int64 tensor: one all-reduce
-                import torch
-                flat = torch.zeros(lay["size"], dtype=torch.int64, device=torch.device("cuda", ctx.device))
-            try:
-                return ctx.isf_accumulate(packed, hkl, window, dq, nbins, origin_stride=origin_stride, work_range=work,
-                                          self_part=self_part, out=flat)
-            except _hip.AmofError as e:
-                if e.code != _hip.AMOF_ECAPACITY:
-                    raise
-                # (no chunks of frames here: they would cut the lags)
-                raise ValueError("F(q, t): %s.  Remedies: fewer vectors per bin (max_points) or a larger dq; origin_stride "
-                                 "does not help (the scale is set by the trajectory's frame count)" % e) from e
+            return lag_q.local("F(q, t)", s, lay, lambda flat: ctx.isf_accumulate(
+                s.packed, s.hkl, s.window, s.dq, s.nbins, origin_stride=s.origin_stride, work_range=s.work, self_part=self_part,
+                out=flat))
 
         def finish(raw):
             if merge:
+                # counts, beyond, coh and self in ONE int64 tensor: one all-reduce
                 flat, scale, kinds = raw
-                if st.on_device:
-                    _dist.all_reduce_sum(flat)          # (in HBM)
-                    flat = flat.cpu().numpy()
-                else:
-                    flat = _dist.all_reduce_sum(flat.cpu().numpy(), device=ctx.device)
-                n = W * nbins
-                counts = flat[lay["counts"]:lay["counts"] + n].reshape(W, nbins).view(np.uint64)
-                beyond = flat[lay["beyond"]:lay["beyond"] + W].view(np.uint64)
-                pidx = pair_index(S)
-                exp2 = np.array([[scale[pidx[(min(a, c), max(a, c))]] for c in range(S)] for a in range(S)], dtype=np.int64)
-                coh = np.ldexp(flat[lay["coh"]:lay["coh"] + S * S * n].reshape(S, S, W, nbins).astype(np.float64),
-                               -exp2[:, :, None, None])
-                selfs = None
-                if self_part:
-                    selfs = np.ldexp(flat[lay["self"]:lay["self"] + S * n].reshape(S, W, nbins).astype(np.float64),
-                                     -np.diag(exp2)[:, None, None])
+                m = lag_q.Merged(s, lay, flat, scale)
+                counts, beyond, coh = m.counts, m.beyond, m.block("coh")
+                selfs = m.block("self", diagonal=True) if self_part else None
             else:
                 counts, coh, selfs, beyond, kinds = raw
-            self._assemble(counts, coh, selfs, beyond, kinds, hkl, packed, elements, n_orig, window, time, dq)
+            self._assemble(counts, coh, selfs, beyond, kinds, s.hkl, s.packed, s.elements, s.n_orig, s.window, time, s.dq)
 
         self._defer(ctx, local, finish, collective=merge)
 

@@ -1,5 +1,6 @@
-"""The lag/origin family's shared host side: ``DistinctVanHove``, ``IntermediateScattering``, ``BondLifetime``,
-``BondReorientation`` (and the windows of ``WindowVanHove``).
+"""The lag/origin family's shared host side: ``DistinctVanHove``, ``IntermediateScattering``, ``CurrentCorrelation`` (what
+those two share beyond this is amof_amd/lag_q.py), ``BondLifetime``, ``BondReorientation`` (and the windows of
+``WindowVanHove``).
 
 Lags m are the windows of ``WindowMsd``; the origins of lag m are the frames k = 1, 1 + s, 1 + 2s, ... <= F - m - 1 (s =
 ``origin_stride``).  The work list is every (lag, origin) pair, lag-major, origins ascending; ranks and devices take

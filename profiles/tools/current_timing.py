@@ -6,6 +6,7 @@ built), alternating, with the other tree's own run-to-run spread as the noise.  
 Writes a markdown report and prints one JSON line.
 
     python profiles/tools/current_timing.py [--frames 200] [--calls 5] [--parent-tree DIR] [--out profiles/current/current_timing.md]
+    python profiles/tools/current_timing.py --parent-tree DIR --stage-report profiles/current/lag_scaffold_timing.md [--rounds 4]
 """
 
 import argparse
@@ -74,12 +75,40 @@ def current(frames, calls):
     return out
 
 
-def _child(tree, frames, calls):
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--baseline-only", "--tree", tree, "--frames", str(frames),
+def _child(tree, frames, calls, mode="--baseline-only"):
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), mode, "--tree", tree, "--frames", str(frames),
                         "--calls", str(calls)], capture_output=True, text=True, timeout=900)
     if r.returncode != 0:
-        raise RuntimeError("baseline run in %s failed: %s" % (tree, r.stderr[-1500:]))
+        raise RuntimeError("%s run in %s failed: %s" % (mode, tree, r.stderr[-1500:]))
     return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+STAGES = (("C(q, t) records", "records"), ("C(q, t) table", "table"), ("C(q, t) correlation", "corr"), ("C(q, t) all kernels", "all"),
+          ("F(q, t) table", "isf_rho"), ("F(q, t) correlation", "isf_corr"), ("F(q, t) all kernels", "isf_all"))
+
+
+def stage_report(parent, this, calls, path):
+    """the stages of both lag analyses, dense lags, this tree against the parent: inside the parent's own spread or not"""
+    sh = this[0]["shape"]
+    ms = lambda x: "%.3f" % (1e3 * x)
+    lines = ["# F(q, t) and C(q, t): stage timings, this tree against the parent commit", "",
+             "%d atoms, %d species, %d frames (device resident), %d vectors, every lag up to %d; alternating runs in fresh processes, "
+             "device events, kernel milliseconds (medians of %d warm calls each); `profiles/tools/current_timing.py --stage-report`.  "
+             "Spread = min .. max of the parent's own repeated runs." % (sh["atoms"], sh["species"], sh["frames"], sh["vectors"],
+                                                                         this[0]["dense"]["lags"], calls), "",
+             "| stage | parent runs ms | this tree runs ms | parent spread | difference of medians | inside the spread |",
+             "|---|---|---|---|---|---|"]
+    verdict = {}
+    for label, k in STAGES:
+        p, t = [r["dense"][k] for r in parent], [r["dense"][k] for r in this]
+        verdict[k] = min(p) <= med(t) <= max(p)
+        lines.append("| %s | %s | %s | %.1f %% | %+.1f %% | %s |" % (label, ", ".join(ms(x) for x in p), ", ".join(ms(x) for x in t),
+                                                                    100 * (max(p) - min(p)) / med(p), 100 * (med(t) - med(p)) / med(p),
+                                                                    "yes" if verdict[k] else "no"))
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    return verdict
 
 
 def report(out, path):
@@ -120,6 +149,9 @@ def main():
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--tree", default=HERE, help="the source tree whose package is timed")
     ap.add_argument("--baseline-only", action="store_true")
+    ap.add_argument("--stages-only", action="store_true", help="print the stage timings of --tree as one JSON line")
+    ap.add_argument("--stage-report", default=None, metavar="FILE", help="with --parent-tree: the stages of F(q, t) and C(q, t) in "
+                    "both trees, alternating, as a markdown table")
     ap.add_argument("--parent-tree", default=None, help="a built checkout of the parent commit: the existing analyses are timed in both")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--vgprs", type=int, default=88, help="VGPRs of current_rho_kernel from the compiler's resource report")
@@ -128,6 +160,16 @@ def main():
     sys.path.insert(0, os.path.abspath(args.tree))
     if args.baseline_only:
         print(json.dumps(baseline(args.frames, args.calls)))
+        return
+    if args.stages_only:
+        print(json.dumps(current(args.frames, args.calls)))
+        return
+    if args.stage_report:
+        parent, this = [], []
+        for _ in range(args.rounds):
+            parent.append(_child(args.parent_tree, args.frames, args.calls, "--stages-only"))
+            this.append(_child(HERE, args.frames, args.calls, "--stages-only"))
+        print(json.dumps({"inside_parent_spread": stage_report(parent, this, args.calls, args.stage_report), "parent": parent, "this": this}))
         return
     out = current(args.frames, args.calls)
     import re

@@ -1,4 +1,4 @@
-"""The derived error budget of the current modes j_a(k) (amof_current_modes, current_rho_kernel in amof_amd/csrc/sq.hip)
+"""The derived error budget of the current modes j_a(k) (amof_current_modes, current_rho_kernel in amof_amd/csrc/current.hip)
 against the exact-phase reference tests/current_ref.py, built as tests/sq_exact_ref.budget is.  Test infrastructure only;
 needs no GPU.
 

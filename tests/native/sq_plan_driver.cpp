@@ -12,6 +12,8 @@
 //   "P S nbins W isf_global"              -> tile_ctr global lags_per_pass lds path
 //   "G nv range"                          -> vblocks opw gy
 //   "F budget N K S n_entries"            -> isf_self_batch
+//   "Q sums S nbins W global"             -> tile_ctr global lags_per_pass lds path of lag_pass_plan itself (paths "lds" / "glob")
+//   "L nv range tile"                     -> vblocks opw gy of lag_grid itself
 #include <stdio.h>
 
 #include <vector>
@@ -175,7 +177,7 @@ int main()
             rc = chunks_line();
         } else if (tag == 'P') {
             int S, nbins, W, glob;
-            if (scanf("%d %d %d %d", &S, &nbins, &W, &glob) != 4 || S < 1 || nbins < 1 || W < 1) return 1;
+            if (scanf("%d %d %d %d", &S, &nbins, &W, &glob) != 4 || S < 1 || nbins < 1 || W < 0) return 1;
             SqSwitches sw;
             sw.isf_global = glob != 0;
             const IsfPass p = isf_pass_plan(S, nbins, W, sw);
@@ -185,6 +187,17 @@ int main()
             long long range;
             if (scanf("%d %lld", &nv, &range) != 2 || nv < 1 || range < 1) return 1;
             const IsfGrid g = isf_grid(nv, range);
+            printf("%d %d %u\n", g.vblocks, g.opw, g.gy);
+        } else if (tag == 'Q') {
+            int sums, S, nbins, W, glob;
+            if (scanf("%d %d %d %d %d", &sums, &S, &nbins, &W, &glob) != 5 || sums < 1 || S < 1 || nbins < 1 || W < 0) return 1;
+            const LagPass p = lag_pass_plan(sums, S, nbins, W, glob != 0, "lds", "glob");
+            printf("%zu %d %d %zu %s\n", p.tile_ctr, p.global, p.lags_per_pass, p.lds, p.path);
+        } else if (tag == 'L') {
+            int nv, tile;
+            long long range;
+            if (scanf("%d %lld %d", &nv, &range, &tile) != 3 || nv < 1 || range < 1 || tile < 1) return 1;
+            const LagGrid g = lag_grid(nv, range, tile);
             printf("%d %d %u\n", g.vblocks, g.opw, g.gy);
         } else if (tag == 'F') {
             long long budget, N, n_entries;

@@ -300,3 +300,26 @@ def test_a_stream_is_kept_or_read_whole_and_never_merged(lanes, traj, tmp_path, 
         with pytest.raises(ValueError, match=text):
             make()
     assert lanes[0].calls == [] and lanes[1].calls == []
+
+
+def test_one_layout_of_the_merged_tensor_of_the_lag_analyses():
+    """``_hip.lag_layout``: counts, beyond, then the named blocks tile [0, size) without gap or overlap; ``isf_layout`` and
+    ``current_layout`` are two calls of it and return what they always did"""
+    for S in (1, 3):
+        for W in (1, 4):
+            for nbins in (1, 7):
+                n = W * nbins
+                for lay, blocks in ((_hip.isf_layout(S, W, nbins, True), (("coh", S * S), ("self", S))),
+                                    (_hip.isf_layout(S, W, nbins, False), (("coh", S * S), ("self", 0))),
+                                    (_hip.current_layout(S, W, nbins), (("long", S * S), ("trans", S * S)))):
+                    assert lay == _hip.lag_layout(S, W, nbins, blocks)
+                    assert set(lay) == {"counts", "beyond", "size"} | {name for name, _ in blocks}
+                    spans = [(lay["counts"], n), (lay["beyond"], W)] + [(lay[name], rows * n) for name, rows in blocks]
+                    at = 0
+                    for start, words in spans:      # in the order of the offsets: each block starts where the last one ended
+                        assert start == at
+                        at += words
+                    assert at == lay["size"]
+    assert _hip.isf_layout(3, 4, 7, True) == {"counts": 0, "beyond": 28, "coh": 32, "self": 284, "size": 368}
+    assert _hip.isf_layout(3, 4, 7, False) == {"counts": 0, "beyond": 28, "coh": 32, "self": 284, "size": 284}
+    assert _hip.current_layout(3, 4, 7) == {"counts": 0, "beyond": 28, "long": 32, "trans": 284, "size": 536}

@@ -474,6 +474,45 @@ def test_self_batch_size(driver):
     assert got[:2] == [GRID_Y, GRID_Y] and got[3] == 1 and got[4] == 1 and got[5] == 7 and 1 < got[2] < 30000
 
 
+def test_one_pass_plan_and_one_grid_rule_serve_both_correlation_kernels(driver, tmp):
+    """lag_pass_plan and lag_grid (sq_plan.h), asked directly and through F(q, t)'s driver line (one sum per pair, origin tile
+    ISF_TILE) and C(q, t)'s (two sums per pair, tile 1): all three against the rule restated once"""
+    out = str(tmp / "current_plan_driver")
+    r = subprocess.run(["g++", "-std=c++17", "-ffp-contract=off", "-O1", os.path.join(ROOT, "tests", "native", "current_plan_driver.cpp"),
+                        "-o", out], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    forms = ((driver, True, 1, ISF_TILE, "isf"), (out, False, 2, 1, "current"))
+
+    def grid(nv, rng_, tile):
+        vblocks = -(-nv // ISF_THREADS)
+        opw = min(ISF_OPW, max(tile, rng_ * vblocks // 2048 // tile * tile))
+        opw = max(opw, -(-(-(-rng_ // GRID_Y)) // tile) * tile)
+        return [vblocks, opw, -(-rng_ // opw)]
+
+    cases = [(nv, r) for nv in (1, 255, 256, 257, 70000) for r in (1, 3, 4, 5, 63, 64, 65, 1000, GRID_Y * 64 + 1)]
+    for exe, keep, _, tile, _ in forms:
+        direct = _ask(driver, ["L %d %d %d" % (c + (tile,)) for c in cases])      # lag_grid itself
+        for (nv, rng_), w, d in zip(cases, _ask(exe, ["G %d %d" % c for c in cases], keep=keep), direct):
+            got = [int(x) for x in w]
+            assert got == grid(nv, rng_, tile) and w == d, (tile, nv, rng_)
+            assert got[2] <= GRID_Y and got[2] * got[1] >= rng_ and got[1] % tile == 0, (tile, nv, rng_)
+
+    cases = [(S, nbins, W, 0) for S in (1, 2, 4, 5) for nbins in (1, 100, 911, 912, 8192) for W in (0, 1, 7, 300)]
+    seen = set()
+    for exe, keep, sums, _, name in forms:
+        direct = _ask(driver, ["Q %d %d %d %d %d" % ((sums,) + c) for c in cases])   # lag_pass_plan itself
+        for (S, nbins, W, g), w, d in zip(cases, _ask(exe, ["P %d %d %d %d" % c for c in cases], keep=keep), direct):
+            tile = (1 + sums * S * S) * nbins
+            glob = tile * 8 > LDS_BUDGET
+            lpp = W if glob else min(W, LDS_BUDGET // (tile * 8))
+            assert [int(x) for x in w[:4]] == [tile, int(glob), lpp, lpp * tile * 8] and w[4] == (name + "_global" if glob else name), (name, S, nbins, W)
+            assert w[:4] == d[:4] and d[4] == ("glob" if glob else "lds"), (name, S, nbins, W)
+            assert glob or int(w[3]) <= 65536, (name, S, nbins, W)
+            assert glob or W < 1 or int(w[2]) >= 1, (name, S, nbins, W)
+            seen.add((name, glob, lpp < W))
+    assert seen == {(n, g, c) for n in ("isf", "current") for g, c in ((False, False), (False, True), (True, False))}
+
+
 def test_driver_under_sanitizers(driver, tmp):
     san = _build(tmp, ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "sq_plan_driver_san")
     if not ALL_LINES:                # (run alone: the tests above have not asked their questions yet)
