@@ -25,6 +25,7 @@ Analyses beyond the reference:
                                                   intermediate scattering function F(q, t), coherent and self
     amof_amd.bond_lifetime.BondLifetime           bond survival correlations C(t), S(t) for CoordinationNumber's sets
     amof_amd.bond_reorientation.BondReorientation reorientational correlations C1(t), C2(t) of the same sets' bond vectors
+    amof_amd.lindemann.Lindemann                  Lindemann index (bond-length fluctuation) of the same sets per block of frames
     amof_amd.bond_order.BondOrder                 Steinhardt q_l and tetrahedral order parameter of the same sets' shells
     amof_amd.dihedral.Dihedral                    torsion-angle distributions of chains a-b-c-d of bonded atoms (also
                                                   ``amof_amd.Dihedral``)

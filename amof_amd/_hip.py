@@ -39,6 +39,7 @@ EXPORTS = [
     "amof_vanhove_window", "amof_vanhove_window_dev", "amof_vanhove_distinct", "amof_vanhove_distinct_dev",
     "amof_vacf_window", "amof_vacf_window_dev",
     "amof_bond_survival", "amof_bond_survival_dev", "amof_bond_reorientation", "amof_bond_reorientation_dev",
+    "amof_lindemann", "amof_lindemann_dev",
     "amof_bond_order", "amof_bond_order_dev", "amof_dihedral_hist", "amof_dihedral_hist_dev", "amof_ring_stats", "amof_ring_search_stats", "amof_fragment_stats", "amof_fragment_round_stats",
     "amof_pore_field", "amof_pore_candidate_bound",
     "amof_pore_access", "amof_pore_access_field", "amof_pore_psd", "amof_pore_psd_field", "amof_pore_cover_stats",
@@ -153,6 +154,9 @@ def load_library():
         lib.amof_bond_survival_dev.argtypes = lib.amof_bond_survival.argtypes
         lib.amof_bond_reorientation.argtypes = lib.amof_bond_survival.argtypes + [P]
         lib.amof_bond_reorientation_dev.argtypes = lib.amof_bond_reorientation.argtypes
+        lib.amof_lindemann.argtypes = [P, TP, P, P, ctypes.c_int32, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.c_double, ctypes.c_int64, ctypes.c_int64, P, P, P, P]
+        lib.amof_lindemann_dev.argtypes = lib.amof_lindemann.argtypes
         lib.amof_bond_order.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P, P]
         lib.amof_bond_order_dev.argtypes = lib.amof_bond_order.argtypes
         lib.amof_dihedral_hist.argtypes = [P, TP, P, P, ctypes.c_int32, P, ctypes.c_int32, P, P, P, P]
@@ -884,6 +888,43 @@ class Context(Lane):
         return sums, scale
 
     @_locked
+    def lindemann(self, packed, cutoff, sets, block, block_stride, nbins, ddelta, select=0, atom_range=None, per_atom=False, out=None):
+        """``(sums int64 [nb][n_sets][2], hist u64 [nb][n_sets][nbins], scale_log2 int32 [n_sets] [, per_atom int64
+        [nb][n_sets][N][2]])`` of ``amof_lindemann``: per block of ``block`` frames (block b starts at frame ``b *
+        block_stride``) and set (A, B), the pairs bonded at the block's first frame (``select=0``) or at frame 0 (``select=1``)
+        and the sum over them of ``llrint(delta 2^e)``, delta = the relative root-mean-square fluctuation of the pair's
+        minimum-image distance over the block; the histogram of delta in bins of ``ddelta`` (the last takes everything above);
+        per centre atom the same two numbers, for the centres ``atom_range`` (default: all).  ``cutoff``, ``sets``: as
+        ``cn_count``.
+
+        ``out``: optional pair of torch CUDA int64 tensors ``([nb][n_sets][2], [nb][n_sets][nbins])`` the sums and the
+        histogram are ADDED into on the device (they stay resident for an RCCL merge); they are returned in place of the
+        arrays."""
+        th = self._traj(packed)
+        cutoff, sets = _cutoff(cutoff, th.S), _pairs(sets)
+        a0, a1 = _span(atom_range, th.n_atoms)
+        block, block_stride, nbins, n_sets = int(block), int(block_stride), int(nbins), len(sets)
+        if block < 2 or block > th.n_frames or block_stride < 1 or nbins < 1:
+            raise ValueError("lindemann: block %d outside 2..%d frames, block_stride %d < 1 or nbins %d < 1"
+                             % (block, th.n_frames, block_stride, nbins))
+        nb = (th.n_frames - block) // block_stride + 1
+        scale = np.zeros(n_sets, dtype=np.int32)
+        pa = np.zeros((nb, n_sets, th.n_atoms, 2), dtype=np.int64) if per_atom else None
+        if out is not None:
+            sums, hist = out
+            self._check_out(sums, nb * n_sets * 2)
+            self._check_out(hist, nb * n_sets * nbins)
+            self._order_after_torch()
+            fn = self._lib.amof_lindemann_dev
+        else:
+            sums = np.zeros((nb, n_sets, 2), dtype=np.int64)
+            hist = np.zeros((nb, n_sets, nbins), dtype=np.uint64)
+            fn = self._lib.amof_lindemann
+        self._check(fn(self._h, ctypes.byref(th.c), _ptr(cutoff), _ptr(sets), n_sets, block, block_stride, int(select), nbins,
+                       float(ddelta), int(a0), int(a1), _ptr(sums), _ptr(hist), _ptr(pa), _ptr(scale)))
+        return (sums, hist, scale, pa) if per_atom else (sums, hist, scale)
+
+    @_locked
     def bond_order(self, packed, cutoff, sets, l, nbins, nbins_tet, frame_range=None, per_atom=False, out=None):
         """``(hist u64 [n_sets][n_l][nbins], hist_tet u64 [n_sets][nbins_tet], frame_sums int64 [F][n_sets][4 + n_l + 1]
         [, per_atom int64 [F][n_sets][N][2 + n_l]])`` of ``amof_bond_order``: the Steinhardt q_l (``l``: up to four values in
@@ -1316,7 +1357,8 @@ class Context(Lane):
         """``{"rho", "corr", "self"}``: kernel seconds of the stages of the last ``isf_accumulate`` (amof_last_kernel_seconds
         2 .. 4; negative: the last call was not one).  After ``bond_survival`` the same three slots hold the bond lists, the
         bit series and the correlations; after ``bond_reorientation`` the bond lists, the bit series, and the vector table
-        with the reorientation sums; after ``bond_order`` the list stage and the order kernels, after ``dihedral_hist`` the
+        with the reorientation sums; after ``lindemann`` the pair lists, the moments and the reduction; after ``bond_order``
+        the list stage and the order kernels, after ``dihedral_hist`` the
         list stage (or the adjacency rows) and the dihedral kernels (the third is 0).  After the Pore
         calls the three slots hold the cell sort, the field kernels and the labelling; ``pore=True`` adds ``"cover"``, the covering
         stage, and ``"surface"``, the surface stage (amof_last_kernel_seconds 5 and 6)."""
@@ -1482,6 +1524,14 @@ class MultiContext(object):
         """the centre atoms sharded over the devices: the integer sums add up exactly; the scale is the same on all"""
         return self._sharded("bond_reorientation", packed, _span(atom_range, packed.n_atoms), "atom_range", ("sum", "first"),
                              cutoff, sets, windows, origin_stride=origin_stride)
+
+    def lindemann(self, packed, cutoff, sets, block, block_stride, nbins, ddelta, select=0, atom_range=None, per_atom=False, out=None):
+        """the centre atoms sharded over the devices: the integer sums, histograms and per-atom rows (disjoint between the
+        shards) add up exactly; the scale is the same on all"""
+        assert out is None, "device-resident accumulation is a single-context feature"
+        return self._sharded("lindemann", packed, _span(atom_range, packed.n_atoms), "atom_range",
+                             ("sum", "sum", "first", "sum")[:3 + bool(per_atom)], cutoff, sets, block, block_stride, nbins, ddelta,
+                             select=select, per_atom=per_atom)
 
     def bond_order(self, packed, cutoff, sets, l, nbins, nbins_tet, frame_range=None, per_atom=False, out=None):
         """frames sharded over the devices as ``cn_count``'s: the rows concatenate, the histograms add up exactly"""

@@ -12,7 +12,9 @@
 //                        a pair that is never bonded only carries an all-zero series -- into a bitmap [centre][partner
 //                        rank]; bond_rowcount_kernel + a host prefix sum + bond_compact_kernel turn it into the table of
 //                        pairs (i, j), sorted and free of duplicates by construction; the table is built
-//                        for groups of whole rows of at most 2^25 pairs (256 MB; AMOF_BOND_PAIR_BUDGET, in pairs, overrides)
+//                        for groups of whole rows of at most 2^25 pairs (256 MB; AMOF_BOND_PAIR_BUDGET, in pairs, overrides).
+//                        The stage is bond_pair_groups (bond_pairs.h), which lindemann.hip calls too: the list kernel walks the
+//                        frames first + stride o, with first = 1 for the analyses of this file.
 //   bond_series_kernel   a lane owns a pair, a wave 64 pairs and one u64 word: 64 frames in a row, frame f's decision into
 //                        bit f & 63.  The pairs are sorted by centre, so the lanes of a wave read neighbouring atoms of one
 //                        frame.  (bond_series_frames_kernel, AMOF_BOND_LAYOUT=frames: a lane owns a frame, the word is the
@@ -54,12 +56,13 @@
 #include <vector>
 
 #include "amof_internal.h"
+#include "bond_pairs.h"
 #include "nbr_check.h"
 
 namespace amof {
 namespace {
 
-constexpr int BL_THREADS = 256;         // bond_list_kernel: a centre per thread, partner tiles of 256 atoms
+constexpr int BL_THREADS = BOND_LIST_TILE;      // bond_list_kernel: a centre per thread, partner tiles of 256 atoms
 constexpr int BS_THREADS = 256;         // series kernels: four waves, four words
 constexpr int BC_THREADS = 256;         // bond_corr_kernel: 64 pairs x four word ranges
 constexpr int BC_LAGS = 2048;           // lags per launch of bond_corr_kernel
@@ -73,7 +76,7 @@ struct BondListArgs {
     const double *geom;
     const int32_t *perm;
     unsigned *bitmap;           // [rows][wpr]
-    int64_t N, stride;
+    int64_t N, first, stride;   // the frames first + stride o, o < n_origins (the bond analyses: first = 1)
     int32_t n_cells, n_origins, opc;
     int32_t seg_a, rows;        // centres perm[seg_a .. seg_a + rows)
     int32_t seg_b, nb;          // partners perm[seg_b .. seg_b + nb)
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(BL_THREADS) void bond_list_kernel(BondListArgs a)
     unsigned *__restrict__ brow = a.bitmap + (size_t)(has ? row : 0) * a.wpr;
     const int o0 = blockIdx.y * a.opc, o1 = min(o0 + a.opc, a.n_origins);
     for (int o = o0; o < o1; o++) {
-        const int64_t f = 1 + a.stride * o;
+        const int64_t f = a.first + a.stride * o;
         const double *__restrict__ p = a.pos + (size_t)f * (size_t)a.N * 3;
         const double *__restrict__ g = a.geom + (size_t)(a.n_cells == 1 ? 0 : f) * GEOM_STRIDE;
         const double xi = p[ai * 3 + 0], yi = p[ai * 3 + 1], zi = p[ai * 3 + 2];
@@ -154,6 +157,115 @@ __global__ __launch_bounds__(256) void bond_compact_kernel(const unsigned *__res
         }
     }
 }
+
+}  // namespace
+
+size_t bond_pair_budget()
+{
+    if (const char *e = getenv("AMOF_BOND_PAIR_BUDGET")) {
+        const long long v = atoll(e);
+        if (v > 0) return (size_t)v;
+    }
+    return BOND_PAIR_BYTES / sizeof(int2);
+}
+
+// the pair-table stage (bond_pairs.h): pieces of centres, groups of whole rows, each(table, pairs) per group
+int bond_pair_groups(const BondPairCall &c, int s, int A, int B, double rc, int64_t atom_begin, int64_t atom_end,
+                     const std::function<int(const int2 *, size_t)> &each)
+{
+    amof_ctx *ctx = c.ctx;
+    StageSpans &spans = *c.spans;
+    const HostTiles &tiles = *c.tiles;
+    const std::vector<int64_t> &sp_first = tiles.sp_first;
+    const int64_t nA = tiles.nsp[(size_t)A], nB = tiles.nsp[(size_t)B];
+    if (!(rc > 0.0) || nA == 0 || nB == 0) return AMOF_OK;
+    // centres of the atom range: the species segment of perm is ascending in the atom index
+    const int32_t *seg = tiles.perm.data() + sp_first[(size_t)A];
+    const int64_t a0 = std::lower_bound(seg, seg + nA, (int32_t)atom_begin) - seg;
+    const int64_t a1 = std::lower_bound(seg, seg + nA, (int32_t)std::min<int64_t>(atom_end, 0x7fffffffLL)) - seg;
+    if (a0 >= a1) return AMOF_OK;
+    const int wpr = (int)((nB + 31) / 32);
+    const int64_t rows_max = std::max<int64_t>(1, (int64_t)(BOND_BITMAP_BYTES / 4) / wpr);
+    const int64_t n_origins = c.n_origins;
+    for (int64_t c0 = a0; c0 < a1; c0 += rows_max) {
+        const int rows = (int)std::min<int64_t>(rows_max, a1 - c0);
+        // ---- the pairs bonded at any origin ----
+        spans.begin(0);
+        void *d_bitmap = nullptr, *d_rowcnt = nullptr;
+        const size_t bm_bytes = (size_t)rows * wpr * sizeof(unsigned);
+        AMOF_TRY(ensure(ctx, SLOT_AUX0, bm_bytes, &d_bitmap));
+        AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)rows * sizeof(unsigned), &d_rowcnt));
+        AMOF_HIP_TRY(ctx, hipMemsetAsync(d_bitmap, 0, bm_bytes, ctx->stream));
+        BondListArgs la;
+        memset(&la, 0, sizeof la);
+        la.pos = c.pos_dev;
+        la.geom = c.d_geom;
+        la.perm = c.d_perm;
+        la.bitmap = (unsigned *)d_bitmap;
+        la.N = c.N;
+        la.first = c.first_frame;
+        la.stride = c.stride;
+        la.n_cells = c.n_cells;
+        la.n_origins = (int32_t)n_origins;
+        la.seg_a = (int32_t)(sp_first[(size_t)A] + c0);
+        la.rows = rows;
+        la.seg_b = (int32_t)sp_first[(size_t)B];
+        la.nb = (int32_t)nB;
+        la.self_off = A == B ? (int32_t)c0 : INT32_MIN / 2;
+        la.wpr = wpr;
+        la.rc2_hi = rc * rc * (1.0 + 1e-9);
+        const int row_tiles = (rows + BL_THREADS - 1) / BL_THREADS;
+        // origins per workgroup: enough workgroups to fill the GPU several times over, at most 65535 in y
+        int64_t opc = std::max<int64_t>(1, std::min<int64_t>(16, n_origins * row_tiles / 2048));
+        opc = std::max<int64_t>(opc, (n_origins + 65534) / 65535);
+        la.opc = (int32_t)opc;
+        const dim3 lgrid((unsigned)row_tiles, (unsigned)((n_origins + opc - 1) / opc));
+        if (c.ortho) hipLaunchKernelGGL(bond_list_kernel<true>, lgrid, dim3(BL_THREADS), 0, ctx->stream, la);
+        else hipLaunchKernelGGL(bond_list_kernel<false>, lgrid, dim3(BL_THREADS), 0, ctx->stream, la);
+        AMOF_HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(bond_rowcount_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream,
+                           (const unsigned *)d_bitmap, rows, wpr, (unsigned *)d_rowcnt);
+        AMOF_HIP_TRY(ctx, hipGetLastError());
+        std::vector<unsigned> rowcnt((size_t)rows);
+        AMOF_TRY(fetch(ctx, rowcnt.data(), d_rowcnt, (size_t)rows * sizeof(unsigned)));
+        spans.end();
+        if (getenv("AMOF_BOND_REPORT")) {
+            size_t total = 0;
+            for (unsigned n : rowcnt) total += n;
+            fprintf(stderr, "amof_bond: set %d centres [%lld, %lld) of its species: %zu pairs\n", s, (long long)c0,
+                    (long long)(c0 + rows), total);
+        }
+        // the pair table is bounded like the bitmap: groups of whole rows of at most pair_max pairs (one row, which has
+        // fewer than 2^31, where a single row holds more)
+        for (int r0 = 0; r0 < rows;) {
+            std::vector<unsigned> rowoff;
+            size_t P = 0;
+            int r1 = r0;
+            while (r1 < rows && (r1 == r0 || P + rowcnt[(size_t)r1] <= c.pair_max)) {
+                rowoff.push_back((unsigned)P);
+                P += rowcnt[(size_t)r1++];
+            }
+            const int gr0 = r0, grows = r1 - r0;
+            r0 = r1;
+            if (P == 0) continue;
+            spans.begin(0);
+            void *d_rowoff = nullptr, *d_pairs = nullptr;
+            AMOF_TRY(upload(ctx, SLOT_AUX2, rowoff.data(), (size_t)grows * sizeof(unsigned), &d_rowoff));
+            AMOF_TRY(ensure(ctx, SLOT_AUX3, P * sizeof(int2), &d_pairs));
+            hipLaunchKernelGGL(bond_compact_kernel, dim3((unsigned)((grows + 255) / 256)), dim3(256), 0, ctx->stream,
+                               (const unsigned *)d_bitmap, gr0, grows, wpr, (const unsigned *)d_rowoff, c.d_perm, la.seg_a, la.seg_b,
+                               (int2 *)d_pairs);
+            AMOF_HIP_TRY(ctx, hipGetLastError());
+            spans.end();
+            // rowoff dies with this iteration: a copy too big for the staging ring has consumed it when upload returns, one
+            // through the ring was copied there at once
+            AMOF_TRY(each((const int2 *)d_pairs, P));
+        }
+    }
+    return AMOF_OK;
+}
+
+namespace {
 
 struct BondSeriesArgs {
     const double *pos;
@@ -579,7 +691,6 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
         AMOF_TRY(pore_refuse(ctx, nbr_check::half_height_set(cutoff[sets[2 * s] * S + sets[2 * s + 1]], s, hmin, "a pair could be bonded twice")));
     HostTiles tiles;
     build_tiles(t, BL_THREADS, tiles);
-    const std::vector<int64_t> &sp_first = tiles.sp_first;
 
     // sorted distinct lags and where every window finds its own
     std::vector<int32_t> lags(windows, windows + W);
@@ -604,11 +715,6 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
     const char *env_layout = getenv("AMOF_BOND_LAYOUT");
     const bool by_frames = env_layout && !strcmp(env_layout, "frames");
     const bool ortho = geom.all_ortho;
-    size_t pair_max = BOND_PAIR_BYTES / sizeof(int2);
-    if (const char *e = getenv("AMOF_BOND_PAIR_BUDGET")) {
-        const long long v = atoll(e);
-        if (v > 0) pair_max = (size_t)v;
-    }
 
     AMOF_HIP_TRY(ctx, hipSetDevice(ctx->device));
     timing_begin(ctx);
@@ -655,19 +761,24 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
     }
     int64_t series_launches = 0;
     ctx->last_path = series_path;
+    BondPairCall pc;
+    pc.ctx = ctx;
+    pc.spans = &spans;
+    pc.pos_dev = pos_dev;
+    pc.d_geom = pk.ptr<double>(i_geom);
+    pc.d_perm = pk.ptr<int32_t>(i_perm);
+    pc.tiles = &tiles;
+    pc.N = N;
+    pc.n_cells = (int32_t)t->n_cells;
+    pc.ortho = ortho;
+    pc.first_frame = 1;
+    pc.stride = stride;
+    pc.n_origins = n_origins;
+    pc.pair_max = bond_pair_budget();
 
     for (int s = 0; s < n_sets; s++) {
         const int A = sets[2 * s], B = sets[2 * s + 1];
         const double rc = cutoff[A * S + B];
-        const int64_t nA = tiles.nsp[(size_t)A], nB = tiles.nsp[(size_t)B];
-        if (!(rc > 0.0) || nA == 0 || nB == 0) continue;
-        // centres of the atom range: the species segment of perm is ascending in the atom index
-        const int32_t *seg = tiles.perm.data() + sp_first[(size_t)A];
-        const int64_t a0 = std::lower_bound(seg, seg + nA, (int32_t)atom_begin) - seg;
-        const int64_t a1 = std::lower_bound(seg, seg + nA, (int32_t)std::min<int64_t>(atom_end, 0x7fffffffLL)) - seg;
-        if (a0 >= a1) continue;
-        const int wpr = (int)((nB + 31) / 32);
-        const int64_t rows_max = std::max<int64_t>(1, (int64_t)(BOND_BITMAP_BYTES / 4) / wpr);
         sa.rc = rc;
         if (fast) {
             const float rcf = (float)rc;
@@ -676,172 +787,101 @@ int bond_run(amof_ctx *ctx, const amof_traj *t, const double *cutoff, const int3
             sa.r_in = rcf - g;
             sa.r_out = rcf + g;
         }
-        for (int64_t c0 = a0; c0 < a1; c0 += rows_max) {
-            const int rows = (int)std::min<int64_t>(rows_max, a1 - c0);
-            // ---- the pairs bonded at any origin ----
-            spans.begin(0);
-            void *d_bitmap = nullptr, *d_rowcnt = nullptr;
-            const size_t bm_bytes = (size_t)rows * wpr * sizeof(unsigned);
-            AMOF_TRY(ensure(ctx, SLOT_AUX0, bm_bytes, &d_bitmap));
-            AMOF_TRY(ensure(ctx, SLOT_AUX1, (size_t)rows * sizeof(unsigned), &d_rowcnt));
-            AMOF_HIP_TRY(ctx, hipMemsetAsync(d_bitmap, 0, bm_bytes, ctx->stream));
-            BondListArgs la;
-            memset(&la, 0, sizeof la);
-            la.pos = pos_dev;
-            la.geom = pk.ptr<double>(i_geom);
-            la.perm = pk.ptr<int32_t>(i_perm);
-            la.bitmap = (unsigned *)d_bitmap;
-            la.N = N;
-            la.stride = stride;
-            la.n_cells = (int32_t)t->n_cells;
-            la.n_origins = (int32_t)n_origins;
-            la.seg_a = (int32_t)(sp_first[(size_t)A] + c0);
-            la.rows = rows;
-            la.seg_b = (int32_t)sp_first[(size_t)B];
-            la.nb = (int32_t)nB;
-            la.self_off = A == B ? (int32_t)c0 : INT32_MIN / 2;
-            la.wpr = wpr;
-            la.rc2_hi = rc * rc * (1.0 + 1e-9);
-            const int row_tiles = (rows + BL_THREADS - 1) / BL_THREADS;
-            // origins per workgroup: enough workgroups to fill the GPU several times over, at most 65535 in y
-            int64_t opc = std::max<int64_t>(1, std::min<int64_t>(16, n_origins * row_tiles / 2048));
-            opc = std::max<int64_t>(opc, (n_origins + 65534) / 65535);
-            la.opc = (int32_t)opc;
-            const dim3 lgrid((unsigned)row_tiles, (unsigned)((n_origins + opc - 1) / opc));
-            if (ortho) hipLaunchKernelGGL(bond_list_kernel<true>, lgrid, dim3(BL_THREADS), 0, ctx->stream, la);
-            else hipLaunchKernelGGL(bond_list_kernel<false>, lgrid, dim3(BL_THREADS), 0, ctx->stream, la);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-            hipLaunchKernelGGL(bond_rowcount_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ctx->stream,
-                               (const unsigned *)d_bitmap, rows, wpr, (unsigned *)d_rowcnt);
-            AMOF_HIP_TRY(ctx, hipGetLastError());
-            std::vector<unsigned> rowcnt((size_t)rows);
-            AMOF_TRY(fetch(ctx, rowcnt.data(), d_rowcnt, (size_t)rows * sizeof(unsigned)));
-            spans.end();
-            if (getenv("AMOF_BOND_REPORT")) {
-                size_t total = 0;
-                for (unsigned n : rowcnt) total += n;
-                fprintf(stderr, "amof_bond: set %d centres [%lld, %lld) of its species: %zu pairs\n", s, (long long)c0,
-                        (long long)(c0 + rows), total);
-            }
-            // the pair table is bounded like the bitmap: groups of whole rows of at most pair_max pairs (one row, which has
-            // fewer than 2^31, where a single row holds more)
-            for (int r0 = 0; r0 < rows;) {
-                std::vector<unsigned> rowoff;
-                size_t P = 0;
-                int r1 = r0;
-                while (r1 < rows && (r1 == r0 || P + rowcnt[(size_t)r1] <= pair_max)) {
-                    rowoff.push_back((unsigned)P);
-                    P += rowcnt[(size_t)r1++];
-                }
-                const int gr0 = r0, grows = r1 - r0;
-                r0 = r1;
-                if (P == 0) continue;
-                spans.begin(0);
-                void *d_rowoff = nullptr, *d_pairs = nullptr;
-                AMOF_TRY(upload(ctx, SLOT_AUX2, rowoff.data(), (size_t)grows * sizeof(unsigned), &d_rowoff));
-                AMOF_TRY(ensure(ctx, SLOT_AUX3, P * sizeof(int2), &d_pairs));
-                hipLaunchKernelGGL(bond_compact_kernel, dim3((unsigned)((grows + 255) / 256)), dim3(256), 0, ctx->stream,
-                                   (const unsigned *)d_bitmap, gr0, grows, wpr, (const unsigned *)d_rowoff, pk.ptr<int32_t>(i_perm),
-                                   la.seg_a, la.seg_b, (int2 *)d_pairs);
+        AMOF_TRY(bond_pair_groups(pc, s, A, B, rc, atom_begin, atom_end, [&](const int2 *d_pairs, size_t P) -> int {
+            // ---- series and correlations, a chunk of pairs at a time ----
+            size_t pc_max = std::max<size_t>(64, std::min<size_t>((size_t)65535 * 4, BOND_WORDS_BYTES / 8 / (size_t)nwords) / 64 * 64);
+            if (ro) pc_max = std::max<size_t>(64, std::min<size_t>(pc_max, BOND_VEC_BYTES / 24 / (size_t)F) / 64 * 64);
+            for (size_t p0 = 0; p0 < P; p0 += pc_max) {
+                const int Pc = (int)std::min(pc_max, P - p0);
+                void *d_words = nullptr;
+                AMOF_TRY(ensure(ctx, SLOT_AUX4, (size_t)nwords * Pc * sizeof(uint64_t), &d_words));
+                sa.pairs = (const int2 *)d_pairs + p0;
+                sa.words = (unsigned long long *)d_words;
+                sa.P = Pc;
+                spans.begin(1);
+                if (series_launches == 0) timing_dom_begin(ctx, series_path);
+                auto launch = [&](auto lanes, auto frames) {
+                    if (by_frames)
+                        hipLaunchKernelGGL(frames, dim3((unsigned)((nwords + 3) / 4), (unsigned)((Pc + 3) / 4)), dim3(BS_THREADS), 0,
+                                           ctx->stream, sa);
+                    else
+                        hipLaunchKernelGGL(lanes, dim3((unsigned)((nwords + 3) / 4), (unsigned)((Pc + 63) / 64)), dim3(BS_THREADS), 0,
+                                           ctx->stream, sa);
+                };
+                if (fast) launch(bond_series_kernel<true, true>, bond_series_frames_kernel<true, true>);
+                else if (ortho) launch(bond_series_kernel<false, true>, bond_series_frames_kernel<false, true>);
+                else launch(bond_series_kernel<false, false>, bond_series_frames_kernel<false, false>);
                 AMOF_HIP_TRY(ctx, hipGetLastError());
+                series_launches++;
+                timing_dom_end(ctx, series_launches);
                 spans.end();
-                // rowoff dies with this iteration: a copy too big for the staging ring has consumed it when upload returns, one
-                // through the ring was copied there at once
 
-                // ---- series and correlations, a chunk of pairs at a time ----
-                size_t pc_max = std::max<size_t>(64, std::min<size_t>((size_t)65535 * 4, BOND_WORDS_BYTES / 8 / (size_t)nwords) / 64 * 64);
-                if (ro) pc_max = std::max<size_t>(64, std::min<size_t>(pc_max, BOND_VEC_BYTES / 24 / (size_t)F) / 64 * 64);
-                for (size_t p0 = 0; p0 < P; p0 += pc_max) {
-                    const int Pc = (int)std::min(pc_max, P - p0);
-                    void *d_words = nullptr;
-                    AMOF_TRY(ensure(ctx, SLOT_AUX4, (size_t)nwords * Pc * sizeof(uint64_t), &d_words));
-                    sa.pairs = (const int2 *)d_pairs + p0;
-                    sa.words = (unsigned long long *)d_words;
-                    sa.P = Pc;
-                    spans.begin(1);
-                    if (series_launches == 0) timing_dom_begin(ctx, series_path);
-                    auto launch = [&](auto lanes, auto frames) {
-                        if (by_frames)
-                            hipLaunchKernelGGL(frames, dim3((unsigned)((nwords + 3) / 4), (unsigned)((Pc + 3) / 4)), dim3(BS_THREADS), 0,
-                                               ctx->stream, sa);
-                        else
-                            hipLaunchKernelGGL(lanes, dim3((unsigned)((nwords + 3) / 4), (unsigned)((Pc + 63) / 64)), dim3(BS_THREADS), 0,
-                                               ctx->stream, sa);
-                    };
-                    if (fast) launch(bond_series_kernel<true, true>, bond_series_frames_kernel<true, true>);
-                    else if (ortho) launch(bond_series_kernel<false, true>, bond_series_frames_kernel<false, true>);
-                    else launch(bond_series_kernel<false, false>, bond_series_frames_kernel<false, false>);
-                    AMOF_HIP_TRY(ctx, hipGetLastError());
-                    series_launches++;
-                    timing_dom_end(ctx, series_launches);
-                    spans.end();
-
-                    // ---- correlations of the chunk: the survival counters, or the vector table and the reorientation sums ----
-                    spans.begin(2);
-                    // word ranges: four per workgroup; more workgroups while the pairs alone do not fill the GPU; BC_LAGS lags
-                    // per launch (both kernels: 28 B of LDS per lag)
-                    auto launch_lags = [&](auto kernel, auto &args) -> int {
-                        const int pblocks = (Pc + 63) / 64;
-                        const int ysplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((nwords + 3) / 4, 64), 2048 / pblocks));
-                        AMOF_HIP_TRY(ctx, allow_max_lds((const void *)kernel));
-                        for (int w0 = 0; w0 < Wu; w0 += BC_LAGS) {
-                            args.w0 = w0;
-                            args.w1 = std::min(w0 + BC_LAGS, Wu);
-                            const size_t lds = (size_t)(args.w1 - args.w0) * (3 * sizeof(uint64_t) + sizeof(int32_t));
-                            hipLaunchKernelGGL(kernel, dim3((unsigned)pblocks, (unsigned)ysplit), dim3(BC_THREADS), lds, ctx->stream, args);
-                            AMOF_HIP_TRY(ctx, hipGetLastError());
-                        }
-                        return AMOF_OK;
-                    };
-                    if (ro) {
-                        void *d_tab = nullptr;
-                        AMOF_TRY(ensure(ctx, SLOT_AUX5, (size_t)F * 3 * Pc * sizeof(double), &d_tab));
-                        BondVecArgs va;
-                        memset(&va, 0, sizeof va);
-                        va.pos = pos_dev;
-                        va.geom = sa.geom;
-                        va.pairs = sa.pairs;
-                        va.tab = (double *)d_tab;
-                        va.N = N;
-                        va.F = (int32_t)F;
-                        va.P = Pc;
-                        va.nwords = nwords;
-                        va.n_cells = (int32_t)t->n_cells;
-                        const dim3 vgrid((unsigned)((nwords + 3) / 4), (unsigned)((Pc + 63) / 64));
-                        if (ortho) hipLaunchKernelGGL(bond_vector_kernel<true>, vgrid, dim3(BS_THREADS), 0, ctx->stream, va);
-                        else hipLaunchKernelGGL(bond_vector_kernel<false>, vgrid, dim3(BS_THREADS), 0, ctx->stream, va);
+                // ---- correlations of the chunk: the survival counters, or the vector table and the reorientation sums ----
+                spans.begin(2);
+                // word ranges: four per workgroup; more workgroups while the pairs alone do not fill the GPU; BC_LAGS lags
+                // per launch (both kernels: 28 B of LDS per lag)
+                auto launch_lags = [&](auto kernel, auto &args) -> int {
+                    const int pblocks = (Pc + 63) / 64;
+                    const int ysplit = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>((nwords + 3) / 4, 64), 2048 / pblocks));
+                    AMOF_HIP_TRY(ctx, allow_max_lds((const void *)kernel));
+                    for (int w0 = 0; w0 < Wu; w0 += BC_LAGS) {
+                        args.w0 = w0;
+                        args.w1 = std::min(w0 + BC_LAGS, Wu);
+                        const size_t lds = (size_t)(args.w1 - args.w0) * (3 * sizeof(uint64_t) + sizeof(int32_t));
+                        hipLaunchKernelGGL(kernel, dim3((unsigned)pblocks, (unsigned)ysplit), dim3(BC_THREADS), lds, ctx->stream, args);
                         AMOF_HIP_TRY(ctx, hipGetLastError());
-                        BondReorArgs ra;
-                        memset(&ra, 0, sizeof ra);
-                        ra.words = (const unsigned long long *)d_words;
-                        ra.obase = pk.ptr<unsigned long long>(i_obase);
-                        ra.lags = pk.ptr<int32_t>(i_lags);
-                        ra.tab = (const double *)d_tab;
-                        ra.G = (unsigned long long *)d_G + (size_t)s * 3 * Wu;
-                        ra.flag = (int32_t *)d_flag;
-                        ra.F = (int32_t)F;
-                        ra.P = Pc;
-                        ra.nwords = nwords;
-                        ra.Wu = Wu;
-                        ra.scale = ldexp(1.0, ro->scale_log2[s]);
-                        AMOF_TRY(launch_lags(bond_reorient_kernel, ra));
-                    } else {
-                        BondCorrArgs ca;
-                        memset(&ca, 0, sizeof ca);
-                        ca.words = (const unsigned long long *)d_words;
-                        ca.obase = pk.ptr<unsigned long long>(i_obase);
-                        ca.lags = pk.ptr<int32_t>(i_lags);
-                        ca.G = (unsigned long long *)d_G + (size_t)s * 3 * Wu;
-                        ca.F = (int32_t)F;
-                        ca.P = Pc;
-                        ca.nwords = nwords;
-                        ca.Wu = Wu;
-                        AMOF_TRY(launch_lags(bond_corr_kernel, ca));
                     }
-                    spans.end();
+                    return AMOF_OK;
+                };
+                if (ro) {
+                    void *d_tab = nullptr;
+                    AMOF_TRY(ensure(ctx, SLOT_AUX5, (size_t)F * 3 * Pc * sizeof(double), &d_tab));
+                    BondVecArgs va;
+                    memset(&va, 0, sizeof va);
+                    va.pos = pos_dev;
+                    va.geom = sa.geom;
+                    va.pairs = sa.pairs;
+                    va.tab = (double *)d_tab;
+                    va.N = N;
+                    va.F = (int32_t)F;
+                    va.P = Pc;
+                    va.nwords = nwords;
+                    va.n_cells = (int32_t)t->n_cells;
+                    const dim3 vgrid((unsigned)((nwords + 3) / 4), (unsigned)((Pc + 63) / 64));
+                    if (ortho) hipLaunchKernelGGL(bond_vector_kernel<true>, vgrid, dim3(BS_THREADS), 0, ctx->stream, va);
+                    else hipLaunchKernelGGL(bond_vector_kernel<false>, vgrid, dim3(BS_THREADS), 0, ctx->stream, va);
+                    AMOF_HIP_TRY(ctx, hipGetLastError());
+                    BondReorArgs ra;
+                    memset(&ra, 0, sizeof ra);
+                    ra.words = (const unsigned long long *)d_words;
+                    ra.obase = pk.ptr<unsigned long long>(i_obase);
+                    ra.lags = pk.ptr<int32_t>(i_lags);
+                    ra.tab = (const double *)d_tab;
+                    ra.G = (unsigned long long *)d_G + (size_t)s * 3 * Wu;
+                    ra.flag = (int32_t *)d_flag;
+                    ra.F = (int32_t)F;
+                    ra.P = Pc;
+                    ra.nwords = nwords;
+                    ra.Wu = Wu;
+                    ra.scale = ldexp(1.0, ro->scale_log2[s]);
+                    AMOF_TRY(launch_lags(bond_reorient_kernel, ra));
+                } else {
+                    BondCorrArgs ca;
+                    memset(&ca, 0, sizeof ca);
+                    ca.words = (const unsigned long long *)d_words;
+                    ca.obase = pk.ptr<unsigned long long>(i_obase);
+                    ca.lags = pk.ptr<int32_t>(i_lags);
+                    ca.G = (unsigned long long *)d_G + (size_t)s * 3 * Wu;
+                    ca.F = (int32_t)F;
+                    ca.P = Pc;
+                    ca.nwords = nwords;
+                    ca.Wu = Wu;
+                    AMOF_TRY(launch_lags(bond_corr_kernel, ca));
                 }
+                spans.end();
             }
-        }
+            return AMOF_OK;
+        }));
     }
     if (ro) {
         // a zero-length vector among the terms: an error return; the host out holds the zeros it was given above, the device

@@ -126,6 +126,7 @@ int amof_ctx_debug_poison(amof_ctx *ctx, int byte);
  * which = 2 the rho table (quantisation included), 3 the correlation kernel, 4 the self part (0 if not asked for);
  * after amof_bond_survival[_dev]: 2 the bond lists, 3 the bit series, 4 the correlations;
  * after amof_bond_reorientation[_dev]: 2 the bond lists, 3 the bit series, 4 the vector table and the reorientation sums.
+ * after amof_lindemann[_dev]: 2 the pair lists, 3 the moments, 4 the reduction (0 on "lindemann_simple").
  * after amof_bond_order[_dev]: 2 the list stage, 3 the order kernels.
  * after amof_vacf_window[_dev]: 2 the columns, 3 the correlation kernel with its reduction.
  * after amof_current_accumulate[_dev]: 2 the records (means and vmax included), 3 the table, 4 the correlation kernel.
@@ -172,6 +173,8 @@ int64_t amof_last_kernel_launches(const amof_ctx *ctx);
  *        and per-frame cells, open axes; also AMOF_BOND_EXACT=1)
  *   bond reorientation "bond_reorient" (the bond indicator decided as "bond_series"), "bond_reorient_exact" (as
  *        "bond_series_exact"); the bond vectors are the canonical float64 ones on both
+ *   Lindemann index "lindemann_chunk" (a lane per pair, block and chunk of 64 frames, the partial sums added in chunk order by
+ *        a second kernel), "lindemann_simple" (a lane per pair and block walks every frame; AMOF_LINDEMANN_SIMPLE=1)
  *   bond order "order_frame" (the neighbour rows of BAD's frame tier: whole frames or z-slabs in LDS), "order_exact"
  *        (canonical float64 arithmetic per pair: general and per-frame cells, open axes, centres with 17 .. 64
  *        neighbours; also AMOF_ORDER_EXACT=1)
@@ -455,6 +458,62 @@ int amof_bond_reorientation_dev(amof_ctx *ctx, const amof_traj *traj, const doub
                                 const int32_t *windows, int32_t n_windows, int64_t origin_stride, int64_t atom_begin,
                                 int64_t atom_end, int64_t *out_dev /* device [n_sets][W][3], += */,
                                 int32_t *scale_log2 /* host [n_sets] */);
+
+/*
+ * Lindemann index: how much does the LENGTH of a neighbour pair fluctuate?  delta = sqrt(<d^2> - <d>^2) / <d> per pair, over
+ * blocks of frames: the melting criterion (a glass stays below about 0.1, a liquid does not).  Replaces nothing in the
+ * reference, whose neighbour analyses (amof/cn.py) count bonds per frame and follow no pair through time.
+ *   Blocks.  F frames, a block length B = block (2 <= B <= F) and a block stride S = block_stride >= 1 give
+ *     nb = (F - B) / S + 1 blocks (integer division); block b covers the frames [b S, b S + B).  Frame 0 is used: this is no
+ *     lag analysis, and the origin rule of the lag family (origins from frame 1) does not apply.  Frames behind the last block
+ *     are not used.
+ *   cutoff, sets, h_ij(f): amof_cn_count's and amof_bond_survival's -- strict sqrt(d2) < rc on the canonical minimum image
+ *      in frame f's cell and pbc, decided by the canonical float64 arithmetic (one decision per pair and block: there
+ *     is no f32 form).  A cutoff of a set above half the smallest perpendicular cell height on a periodic axis is refused
+ *     (AMOF_EINVAL), as for amof_bond_survival; a zero cutoff gives an empty set.
+ *   Pairs of a block: the ordered pairs (i of species A, j of species B, i != j, atom_begin <= i < atom_end) with
+ *     select = 0 ("block")  h_ij(b S) = 1: the bonds that exist at the block's first frame;
+ *     select = 1 ("first")  h_ij(0) = 1, in every block: a fixed population, whose delta keeps growing as the initial network
+ *                           dissolves.
+ *   Distance.  d_ij(f) = sqrt(norm2(pair_base(r_j - r_i))): the canonical minimum-image distance in frame f's own cell and pbc.
+ *     A pair that drifts beyond half the cell is measured to its nearest image: delta of such a pair only means "large".
+ *   Moments, in a fixed order.  With c = d(first frame of the block) and e_f = d_f - c:
+ *     chunks of 64 block-relative frames [64 k, 64 k + 64); inside a chunk, frames ascending from p1 = p2 = 0:
+ *       p1 += e,  p2 = fma(e, e, p2);
+ *     S1, S2 = the chunk partials added in ascending k, from 0;
+ *     m1 = S1 / B,  mean = c + m1,  var = max(0, S2 / B - m1 * m1),  delta = var == 0 ? 0 : sqrt(var) / mean.
+ *     This order is part of the ABI: every kernel and every launch geometry gives the same bits.
+ *   Outputs, all integers:
+ *     sums[(b*n_sets + s)*2 + 0] = number of pairs of block b and set s
+ *     sums[(b*n_sets + s)*2 + 1] = sum over them of llrint(delta_ij 2^e_s)                      int64
+ *     scale_log2[s] = e_s = min(40, 62 - bit_length(n_A n_B ceil(sqrt(B)))), n_A and n_B the atoms of the set's species in the
+ *       whole trajectory (the coefficient of variation of B non-negative numbers is at most sqrt(B - 1)): it depends on the
+ *       trajectory, the set and B only.  e_s < 20 is refused (AMOF_EINVAL).
+ *     hist[(b*n_sets + s)*nbins + k]: pairs with k = min((int)(delta / ddelta), nbins - 1); the last bin takes everything above
+ *     per_atom (optional, may be NULL) int64 [nb][n_sets][N][2]: the pairs of centre i and their sum of llrint(delta_ij 2^e_s);
+ *       zero rows where the atom has no pair
+ *     Ranges of centres add up bit for bit, and nothing depends on launch order, on how the library chunks pairs, centres,
+ *     blocks and frames, or on the path.
+ *   Paths (amof_last_path): "lindemann_chunk" -- a lane per (pair, block, chunk of 64 frames) writes the chunk's partial sums,
+ *     a second kernel adds them in chunk order; "lindemann_simple" (AMOF_LINDEMANN_SIMPLE=1) -- a lane per (pair, block) walks
+ *     every frame in the same order: the cross-check inside the binary.  Scratch is bounded: the pair table as
+ *     amof_bond_survival's (AMOF_BOND_PAIR_BUDGET), the partial sums of a chunk of pairs and blocks <= 256 MB
+ *     (64 pairs and one block at least).
+ *   amof_last_kernel_seconds: which = 2 the pair lists, 3 the moments, 4 the reduction; 1 spans the moments launches.
+ * The host form overwrites sums, hist and per_atom (zeros after an error).  The _dev form ADDS sums and hist into device
+ * buffers (ranks that share the centres all-reduce them next; untouched after an error); per_atom and scale_log2 stay host
+ * arrays.  Errors: AMOF_EINVAL (block, block_stride, select, nbins, ddelta, atom range, set, cutoff, NULL argument),
+ * AMOF_ESINGULAR, AMOF_ENOMEM, AMOF_EHIP, AMOF_ENODEVICE.
+ */
+int amof_lindemann(amof_ctx *ctx, const amof_traj *traj, const double *cutoff /* [S][S], as amof_cn_count */,
+                   const int32_t *sets /* [n_sets][2] */, int32_t n_sets, int64_t block, int64_t block_stride, int32_t select,
+                   int32_t nbins, double ddelta, int64_t atom_begin, int64_t atom_end, int64_t *sums /* host [nb][n_sets][2] */,
+                   uint64_t *hist /* host [nb][n_sets][nbins] */, int64_t *per_atom /* host [nb][n_sets][N][2] or NULL */,
+                   int32_t *scale_log2 /* host [n_sets] */);
+int amof_lindemann_dev(amof_ctx *ctx, const amof_traj *traj, const double *cutoff, const int32_t *sets, int32_t n_sets, int64_t block,
+                       int64_t block_stride, int32_t select, int32_t nbins, double ddelta, int64_t atom_begin, int64_t atom_end,
+                       int64_t *sums_dev /* device [nb][n_sets][2], += */, uint64_t *hist_dev /* device [nb][n_sets][nbins], += */,
+                       int64_t *per_atom /* host or NULL */, int32_t *scale_log2 /* host [n_sets] */);
 
 /*
  * Bond order parameters of neighbour shells: Steinhardt q_l and the tetrahedral order parameter q_tet per centre atom.
