@@ -104,6 +104,26 @@ inline double fast_guard_zf(int nbins, double hb, double gfrac)
     return 1.1 * u * qmax * (3.5 + extra + 1.56);
 }
 
+// ZF form with the saturating tail (rdf_sat_math.h; the planned f32-slab slice): the chain runs in units of C = the lane's
+// clamp value and is scaled back behind the root, q' = fl(Q C + fl(1 + g)).  What changes against fast_guard_zf:
+//   c3, c4        fl(s^2 / C^2) from the f64 scales: one rounding, as sc[3], sc[4] have -- the x, y terms keep their 7u.
+//   dz'           fl(Z_j' k + n_i), k = fl(1 / C) = (1 + d) / C with |d| <= u, n_i = fl(-Z_i' k): the partner's product is not
+//                 rounded (fma), the centre's is, so  |C dz' - Z| <= A' + 2u |Z|,  A' = A + u |Z_i'| <= u Hb (G / 2^32 + 3/32 + 1/128)
+//                 (|Z_i'| <= Hb / 32: the centre lies within half the sub-tile span of z0); squared and summed: 5u on Z^2.
+//   t             |C^2 t - T| <= u T (7 - 2 zeta) + 2 |Z| A'   (zeta = Z^2 / T; the clamp changes nothing below t = 1)
+//   Q C           relative error u (3.5 - zeta + 1.56) with v_sqrt_f32's 1.56 u, C exact
+//   q'            one rounding of a value below q + 2: u (q + 2); the constant fl(1 + g), g < 1/4: 1.25 u
+//   |q' - (q + 1 + g)| <= u q (6.06 - zeta) + A' sqrt(zeta) + 3.25 u
+// over zeta in [0, 1] and q <= qmax = nbins + 1, with a = A' / (u qmax):  <= u qmax (6.06 + a^2 / 4) + 3.25 u  (a <= 2; else
+// 5.06 + a).  10 % margin.  Returns the bound in bins (without the fixed-point grid term g_m).
+inline double fast_guard_zf_sat(int nbins, double hb, double gfrac)
+{
+    const double u = 1.0 / 16777216.0, qmax = (double)nbins + 1.0;
+    const double a = hb * (gfrac + 3.0 / 32 + 1.0 / 128) / qmax;
+    const double extra = a <= 2.0 ? a * a / 4.0 : a - 1.0;
+    return 1.1 * u * (qmax * (3.5 + 1.0 + extra + 1.56) + 3.25);
+}
+
 // TRI form of the tile kernel (general cells, rdf.hip tri_q): the pair vector in the orthogonalised lattice frame,
 //   X = L00 (ix + c10 iy), Y = L11 iy, Z from f32 slab coordinates as in the ZF form (or L22 iz on the integer path),
 // ix, iy the u32 differences of the FOLDED coordinates.  The x term: two conversions, the constant c10 and the fma leave

@@ -32,6 +32,7 @@
 
 #include "amof_internal.h"
 #include "rdf_select.h"
+#include "rdf_sat_math.h"
 
 namespace amof {
 
@@ -232,6 +233,9 @@ struct RdfFastArgs {
     int32_t noreach;         // rdf_tile_zf with slab culling: 1 = every quad of a diagonal tile pair masked (AMOF_RDF_NOREACH)
     int32_t plan_noskip;     // PLAN: 1 = steps without a quad to visit are run all the same (AMOF_RDF_PLAN_NOSKIP: measurements)
     const uint4 *plan;       // PLAN: [pairs][nf][4] one TilePlanRecord per step, pair-major (rdf_tile_plan_kernel, tile_plan.h)
+    float sat_one_p_guard;   // SAT (rdf_sat_math.h): 1 + g rounded to nearest (that rounding is a term of g) and 2 g rounded UP,
+                             // g the bound of the saturating chain (sat_thresholds)
+    float sat_two_guard;
 };
 
 constexpr int FAST_THREADS = 256;
@@ -302,13 +306,15 @@ __device__ __forceinline__ double medium_t(const double *sc, int ix, int iy, int
 // loads from the kernel-argument segment, which the empty statement keeps there) and the two words of `late`; g, p and qseg are
 // not used.  As three pointers made at the head of every step they were carried through the quad loops in spilled scalar
 // registers (profiles/r14/tile_step_state.txt).
+// SAT (with PROV; rdf_sat_math.h): q is q' = q~ + g + 1 and `hist` the histogram one word up.  The edge is rint(q' - (1 + g)),
+// and the provisional count is taken back at the word the fast path used: the same fma and mask on the same q', not (int)q.
 struct LateRefs {
     int fl;          // frame of the step, relative to the batch
     int j_start;     // first atom of tile J in the species-sorted frame
 };
 typedef const RdfFastArgs __attribute__((address_space(4))) *rdf_kernarg_t;
 
-template <bool ORTHO, bool ZF = false, bool PROV = false, bool LATE = false>
+template <bool ORTHO, bool ZF = false, bool PROV = false, bool LATE = false, bool SAT = false>
 __device__ __forceinline__ void rdf_pair_refine(unsigned *hist, const RdfFastArgs &fa,
                                                 const double *sc64, const double *__restrict__ g,
                                                 float q, uint32_t uix, uint32_t uiy, uint32_t uiz, uint4 qj,
@@ -316,8 +322,9 @@ __device__ __forceinline__ void rdf_pair_refine(unsigned *hist, const RdfFastArg
                                                 const QAtom *__restrict__ qseg = nullptr, int j = 0, const LateRefs *late = nullptr)
 {
     const int ix = (int)(qj.x - uix), iy = (int)(qj.y - uiy), iz = (int)(qj.z - uiz);
+    static_assert(!SAT || PROV, "SAT: the always-add scheme");
     const double T = medium_t<ORTHO>(sc64, ix, iy, iz);
-    const float ef = rintf(q);
+    const float ef = rintf(SAT ? q - fa.sat_one_p_guard : q);
     const double e = (double)ef;
     // T >= (e + g_m)^2  <=>  D = T - e^2 >= 2 e g_m + g_m^2 =: band (D is exact: e^2 is an integer below 2^24 and T
     // - e^2 fits the significand); T < (e - g_m)^2 is implied by D < -band (stricter by 2 g_m^2: a few more level-3 pairs)
@@ -327,7 +334,10 @@ __device__ __forceinline__ void rdf_pair_refine(unsigned *hist, const RdfFastArg
     if (D >= band) b = ei;
     else if (D < -band && ei > 0) b = ei - 1;
     if (PROV) {
-        const int cand = (int)q;                       // (q < nbins + 1/2 here: never clamped)
+        const int cand = SAT ? (int)(sat_offset(q) >> 2) - 1 : (int)q;     // (a flagged candidate sits within the guard of an integer, so it
+                                                                           //  is not the clamp value: !SAT (int)q is its word; SAT: the word may be a
+                                                                           //  trash word -- an out-of-range q~ below the lane's C near an integer, as
+                                                                           //  !SAT between nbins + 1/2 and clampv -- inside the allocation either way)
         if (b == cand) return;                         // the provisional count was right
         atomicAdd(&hist[cand], 0xffffffffu);           // (u32 counters wrap; the sum is what is flushed)
     }
@@ -420,13 +430,30 @@ __device__ __forceinline__ void bin_count(unsigned *hist, float q)
     __hip_atomic_fetch_add(p, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
-template <bool ORTHO, bool IMG = false, bool ZF = false, bool AA = false>
+// SAT (the planned f32-slab slice; rdf_sat_math.h): qj.w holds dz' = (z_j - z_i) / C already, half_m_guard carries 2 g and nb_hi
+// 1 + g; q comes back as q' = q~ + g + 1.  No v_med3_f32 and no v_add_f32: 16 instructions per pair instead of 17
+// (profiles/r15/tile_sat.txt).  A masked slot takes the saturated value 1 behind the clamp -- what +inf in front of it gives.
+// (The two words travel in the parameters the clamped tail uses for 1/2 - g and nbins + g, which SAT has no use for, and are
+//  named below; clampv is not read.)  Flagged here, harmlessly, are also: a coincident pair (Q = 0: fract(q') = g; the clamped
+// tail raises it to 1/4 and leaves it in bin 0, where the refinement puts it too) and an out-of-range candidate below the
+// lane's C that sits near an integer (its provisional count is in a trash word; the refinement takes it back and adds nothing).
+template <bool ORTHO, bool IMG = false, bool ZF = false, bool AA = false, bool SAT = false>
 __device__ __forceinline__ bool fast_bin(unsigned *hist, const float *sc, bool live, float half_m_guard,
                                          float nb_hi, uint32_t uix, uint32_t uiy, uint32_t uiz, uint4 qj,
                                          float &q, const float *near_f = nullptr, bool *near = nullptr,
-                                         float zif = 0.0f, float clampv = 0.0f, bool live_all = false)
+                                         float zif = 0.0f, float clampv = 0.0f, bool live_all = false, const SatLane *sat = nullptr)
 {
+    static_assert(!SAT || (ZF && AA && !IMG), "SAT: the always-add tail on f32 slab coordinates");
     const int ix = (int)(qj.x - uix), iy = (int)(qj.y - uiy), iz = (int)(qj.z - uiz);
+    if constexpr (SAT) {
+        float t = sat_t(ix, iy, __uint_as_float(qj.w), sat->c3, sat->c4);
+        if (!live_all) t = live ? t : 1.0f;
+        const float two_guard = half_m_guard, one_p_guard = nb_hi;
+        q = sat_candidate(__builtin_amdgcn_sqrtf(t), sat->C, one_p_guard);
+        const bool unsafe = sat_unsafe(q, two_guard);
+        bin_count(hist, q);
+        return unsafe;
+    }
     if (IMG) {
         // on the converted differences the candidate needs anyway: one compare per axis (thresholds rounded down, see
         // the kernel; axes that are clear of their half height carry +inf)
@@ -441,7 +468,8 @@ __device__ __forceinline__ bool fast_bin(unsigned *hist, const float *sc, bool l
         // compares, five scalar instructions and a skip branch per pair) were what the loop waited for.  Every lane
         // adds to the candidate bin of min(q, clampv): clampv = nbins + 1/2 + (lane mod 32) sends out-of-range (and
         // dead: q = inf) pairs to 32 trash words behind the histogram with a "safe" fractional part, so that `unsafe`
-        // is exactly "in range and within the guard of a bin edge"; such a pair has been counted provisionally and
+        // is "within the guard of a bin edge, and in range or between nbins + 1/2 and the lane's clampv" (the latter: a
+        // count in a trash word, taken back for nothing); such a pair has been counted provisionally and
         // rdf_pair_refine<PROV> takes that count back before it adds the exact one.
         if (!live_all) q = live ? q : __builtin_inff();
         q = clamp_candidate(q, clampv);
@@ -523,8 +551,9 @@ __device__ __forceinline__ void pre_drain(PreRec *r)
                  : "memory");
     asm volatile("" : "+v"(r[0].xy), "+v"(r[0].s), "+v"(r[1].xy), "+v"(r[1].s), "+v"(r[2].xy), "+v"(r[2].s), "+v"(r[3].xy), "+v"(r[3].s));
 }
+// SAT (rdf_sat_math.h): zaf, zbf arrive as -z / C (sat_centre), and the slab word of a difference record is dz'
 template <bool ORTHO, bool DIAG, bool TAIL, bool IMG = false, bool ZF = false, bool ZFK = false, bool AA = false, bool PARK = false,
-          bool SLIM = false, int PRE = 0, bool LATE = false>
+          bool SLIM = false, int PRE = 0, bool LATE = false, bool SAT = false>
 __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa, const double *sc64,
                                           const double *__restrict__ g, const float *sc, const uint4 *tq,
                                           int j0, int cntj, bool has_a, bool has_b, int ia, int ib,
@@ -535,8 +564,9 @@ __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa,
                                           unsigned *nq_count = nullptr, unsigned nq_cap = 0,
                                           float zaf = 0.0f, float zbf = 0.0f, const QAtom *__restrict__ qseg = nullptr,
                                           float clampv = 0.0f, LaneQueue *lq = nullptr, PreRec *pre = nullptr, unsigned pre_addr = 0u,
-                                          const LateRefs *late = nullptr)
+                                          const LateRefs *late = nullptr, const SatLane *sat = nullptr)
 {
+    static_assert(!SAT || (ZF && SLIM && PARK && LATE), "SAT: the planned f32-slab slice");
     // ZF: this step uses the f32 slab coordinates; ZFK: the kernel is a ZF kernel (the .w of the LDS copies may have
     // been overwritten by an earlier step of the frame: atom indices always come from the quantised frame)
     // four partner atoms per trip, read by broadcast before any LDS atomic
@@ -564,8 +594,13 @@ __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa,
                 constexpr int U = decltype(uc)::value;
                 if constexpr (PRE == 1) pre_wait<12>(pre[U]);
                 const uint32_t qx = pre[U].xy.x, qy = pre[U].xy.y, qs = pre[U].s;
+                if constexpr (SAT) {
+                    da = make_uint4(qx - uax, qy - uay, 0u, __float_as_uint(sat_dz(__uint_as_float(qs), sat->invC, zaf)));
+                    db = make_uint4(qx - ubx, qy - uby, 0u, __float_as_uint(sat_dz(__uint_as_float(qs), sat->invC, zbf)));
+                } else {
                 da = make_uint4(qx - uax, qy - uay, ZF ? 0u : qs - uaz, ZF ? __float_as_uint(__uint_as_float(qs) - zaf) : 0u);
                 db = make_uint4(qx - ubx, qy - uby, ZF ? 0u : qs - ubz, ZF ? __float_as_uint(__uint_as_float(qs) - zbf) : 0u);
+                }
                 if constexpr (PRE == 1) {
                     // (the differences exist before the read overwrites the record: volatile statements keep their order)
                     if constexpr (ZF) asm volatile("" : "+v"(da.x), "+v"(da.y), "+v"(da.w), "+v"(db.x), "+v"(db.y), "+v"(db.w));
@@ -577,10 +612,21 @@ __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa,
             else if (u == 1) diffs(std::integral_constant<int, 1>{});
             else if (u == 2) diffs(std::integral_constant<int, 2>{});
             else diffs(std::integral_constant<int, 3>{});
-            na[u] = fast_bin<ORTHO, IMG, ZF, AA>(hist, sc, la, half_m_guard, nb_hi, 0u, 0u, 0u, da, qa[u], near_f, &ma, 0.0f,
-                                                 clampv, ZF && !DIAG && !TAIL);
-            nb[u] = fast_bin<ORTHO, IMG, ZF, AA>(hist, sc, lb, half_m_guard, nb_hi, 0u, 0u, 0u, db, qb[u], near_f, &mb, 0.0f,
-                                                 clampv, ZF && !DIAG && !TAIL);
+            na[u] = fast_bin<ORTHO, IMG, ZF, AA, SAT>(hist, sc, la, half_m_guard, nb_hi, 0u, 0u, 0u, da, qa[u], near_f, &ma, 0.0f,
+                                                      clampv, ZF && !DIAG && !TAIL, sat);
+            nb[u] = fast_bin<ORTHO, IMG, ZF, AA, SAT>(hist, sc, lb, half_m_guard, nb_hi, 0u, 0u, 0u, db, qb[u], near_f, &mb, 0.0f,
+                                                      clampv, ZF && !DIAG && !TAIL, sat);
+            continue;
+        }
+        if constexpr (SAT) {
+            // (the records come from LDS here, AMOF_RDF_NOAHEAD=1: the slab word is made as the read-ahead form makes it)
+            uint4 ra = qj[u], rb = qj[u];
+            ra.w = __float_as_uint(sat_dz(__uint_as_float(qj[u].w), sat->invC, zaf));
+            rb.w = __float_as_uint(sat_dz(__uint_as_float(qj[u].w), sat->invC, zbf));
+            na[u] = fast_bin<ORTHO, IMG, ZF, AA, SAT>(hist, sc, la, half_m_guard, nb_hi, uax, uay, uaz, ra, qa[u], near_f, &ma, 0.0f,
+                                                      clampv, ZF && !DIAG && !TAIL, sat);
+            nb[u] = fast_bin<ORTHO, IMG, ZF, AA, SAT>(hist, sc, lb, half_m_guard, nb_hi, ubx, uby, ubz, rb, qb[u], near_f, &mb, 0.0f,
+                                                      clampv, ZF && !DIAG && !TAIL, sat);
             continue;
         }
         // (ZF: centres that do not exist carry an infinite slab coordinate, so only DIAG / TAIL need a live mask)
@@ -617,7 +663,7 @@ __device__ __forceinline__ void fast_quad(unsigned *hist, const RdfFastArgs &fa,
                             const bool cb = (k & 1) != 0;
                             const float qv = cb ? (u == 0 ? qb[0] : u == 1 ? qb[1] : u == 2 ? qb[2] : qb[3])
                                                 : (u == 0 ? qa[0] : u == 1 ? qa[1] : u == 2 ? qa[2] : qa[3]);
-                            rdf_pair_refine<ORTHO, ZFK, AA, LATE>(hist, fa, sc64, g, qv, cb ? ubx : uax, cb ? uby : uay, cb ? ubz : uaz,
+                            rdf_pair_refine<ORTHO, ZFK, AA, LATE, SAT>(hist, fa, sc64, g, qv, cb ? ubx : uax, cb ? uby : uay, cb ? ubz : uaz,
                                                                   tq[j0 + u], p, cb ? idb : ida, qseg, j0 + u, late);
                         }
                     }
@@ -909,7 +955,8 @@ __device__ __forceinline__ void dma_1k(const QAtom *src_lane, uint4 *dst_wave)
 // (the body: rdf_tile_body.inc)
 // KIND (PLAN only): the grid slice.  1 = this workgroup runs the steps its records flag ZF (f32 slab coordinates) and no others,
 // 2 = the steps in integer form and no others; every step of the plan belongs to exactly one of the two, and integer histograms add.
-template <int AHEAD, int KIND>
+// SAT: the kernel's LDS histogram has the saturating tail's layout, and slice 1 runs that tail (rdf_sat_math.h)
+template <int AHEAD, int KIND, bool SAT>
 __device__ __forceinline__ void rdf_tile_slice(const RdfFastArgs &fa)
 {
     constexpr bool ORTHO = true, CULL = true, IMG = false, ZFK = true, PLAN = true;
@@ -929,14 +976,15 @@ __device__ __forceinline__ void rdf_tile_slice(const RdfFastArgs &fa)
 // is dispatched first: its few long work items run beside the others from the start.  As a launch of their own behind the
 // others they took 2.5 ms of an otherwise idle GPU (profiles/r14/tile_step_state.txt).  Which form a step takes depends
 // on the frame's slab table, so both slices always cover the whole grid.
-template <bool ORTHO, bool CULL, bool IMG = false, bool ZFK = false, int TRI = -1, bool PLAN = false, int AHEAD = 0>
+template <bool ORTHO, bool CULL, bool IMG = false, bool ZFK = false, int TRI = -1, bool PLAN = false, int AHEAD = 0, bool SAT = false>
 __global__ __launch_bounds__(FAST_THREADS, PLAN ? 6 : 5) void rdf_tile_kernel_fast(RdfFastArgs fa)
 {
     if constexpr (PLAN) {
         static_assert(ORTHO && CULL && !IMG && ZFK && TRI < 0, "PLAN: the slab-culled diagonal-cell kernel on f32 slab coordinates");
-        if (blockIdx.z == 0) rdf_tile_slice<AHEAD, 2>(fa);
-        else rdf_tile_slice<AHEAD, 1>(fa);
+        if (blockIdx.z == 0) rdf_tile_slice<AHEAD, 2, SAT>(fa);
+        else rdf_tile_slice<AHEAD, 1, SAT>(fa);
     } else {
+        static_assert(!SAT, "SAT: the plan variant");
         constexpr int KIND = 0;
 #include "rdf_tile_body.inc"
     }
@@ -1899,7 +1947,7 @@ static int rdf_tri_args(RdfCall &c, RdfFastArgs &k, const double **d_fold)
 
 // one launch of the tile kernel's selected variant.  TRI: one instantiation per code (near tests x x wrap); ZF: a list of
 // four (planned with / without the records read a quad ahead, culled, unculled)
-static hipError_t rdf_tile_launch(RdfCall &c, const RdfFastArgs &k, dim3 grid, size_t lds, bool plan)
+static hipError_t rdf_tile_launch(RdfCall &c, const RdfFastArgs &k, dim3 grid, size_t lds, bool plan, bool sat)
 {
     const RdfSelect &sel = c.sel;
     const bool ortho = c.geom.all_ortho, cull = sel.cull;
@@ -1920,8 +1968,8 @@ static hipError_t rdf_tile_launch(RdfCall &c, const RdfFastArgs &k, dim3 grid, s
             if (eo != hipSuccess) return eo;
             granted[key] = n;
             if (c.sw.debug)
-                fprintf(stderr, "rdf_tile: %s%s%d bins, %zu bytes of LDS: %d workgroups per CU\n", plan ? "plan, " : "",
-                        plan && !c.sw.noahead ? "read-ahead, " : "", c.nbins, lds, n);
+                fprintf(stderr, "rdf_tile: %s%s%s%d bins, %zu bytes of LDS: %d workgroups per CU\n", plan ? "plan, " : "",
+                        plan && !c.sw.noahead ? "read-ahead, " : "", sat ? "saturating tail, " : "", c.nbins, lds, n);
         }
         return hipSuccess;
     };
@@ -1931,7 +1979,9 @@ static hipError_t rdf_tile_launch(RdfCall &c, const RdfFastArgs &k, dim3 grid, s
         });
     if (sel.img) return with_flags(ortho, cull, [&](auto O, auto C) { return launch(rdf_tile_kernel_fast<O(), C(), true>); });
     if (sel.zf)
-        return plan && !c.sw.noahead ? launch(rdf_tile_kernel_fast<true, true, false, true, -1, true, 1>)
+        return sat && !c.sw.noahead  ? launch(rdf_tile_kernel_fast<true, true, false, true, -1, true, 1, true>)
+               : sat                 ? launch(rdf_tile_kernel_fast<true, true, false, true, -1, true, 0, true>)
+               : plan && !c.sw.noahead ? launch(rdf_tile_kernel_fast<true, true, false, true, -1, true, 1>)
                : plan                ? launch(rdf_tile_kernel_fast<true, true, false, true, -1, true>)
                : cull                ? launch(rdf_tile_kernel_fast<true, true, false, true>)
                                      : launch(rdf_tile_kernel_fast<true, false, false, true>);
@@ -1969,6 +2019,8 @@ static int rdf_tile_tier(RdfCall &c)
     } else if (sel.zf) {
         k.nb_hi = sel.zf_thr.nb_hi;
         k.half_m_guard = sel.zf_thr.half_m_guard;
+        k.sat_one_p_guard = sel.sat_thr.one_p_guard;
+        k.sat_two_guard = sel.sat_thr.two_guard;
     }
     // rdf_tile_zf with slab culling runs from a plan of its steps (rdf_tile_kernel_fast, PLAN): the quantiser writes
     // its slab table, rdf_tile_plan_kernel the records.  Not for tables beyond the plan kernel's LDS or plans beyond
@@ -2015,8 +2067,10 @@ static int rdf_tile_tier(RdfCall &c)
         if (launches == 0) timing_dom_begin(ctx, tri ? "rdf_tile_tri" : sel.img ? "rdf_tile_img" : sel.zf ? "rdf_tile_zf" : "rdf_tile");
         // (a batch without a plan runs the kernel with centre buffers, at their size; a planned one has two z slices: the
         //  steps in integer form and the steps on f32 slab coordinates, rdf_tile_kernel_fast)
+        // (the saturating tail of the f32-slab slice: planned launches only, AMOF_RDF_NOSAT=1 keeps the clamped one)
+        const bool sat = plan && sel.sat;
         if (plan) grid.z = 2;
-        AMOF_HIP_TRY(ctx, rdf_tile_launch(c, k, grid, tile_lds(nbins, k.img_queue, k.img_defer, plan), plan));
+        AMOF_HIP_TRY(ctx, rdf_tile_launch(c, k, grid, tile_lds(nbins, k.img_queue, k.img_defer, plan, sat), plan, sat));
         launches++;
     }
     timing_dom_end(ctx, launches);

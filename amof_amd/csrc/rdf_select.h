@@ -39,6 +39,7 @@ struct RdfSwitches {
     bool plan_noskip = false;   // AMOF_RDF_PLAN_NOSKIP=1: planned steps without a quad to visit are run all the same
     bool noplan = false;        // AMOF_RDF_NOPLAN=1: rdf_tile_zf searches the sampled quads in every step, no plan
     bool noahead = false;       // AMOF_RDF_NOAHEAD=1: planned kernel without the partner records read a quad ahead
+    bool nosat = false;         // AMOF_RDF_NOSAT=1: planned kernel's f32-slab slice with the clamped tail, not the saturating one
     bool notail = false;        // AMOF_RDF_NOTAIL (set): XCD mapping without the one-frame rows behind the chunks
     bool nocell = false;        // AMOF_RDF_NOCELL (set): never the 3-D cell-list kernel
     bool force_cell = false;    // AMOF_RDF_FORCE_CELL (set): the cell-list kernel wherever it is correct
@@ -65,6 +66,7 @@ struct RdfSwitches {
         s.cell_gather = set("AMOF_RDF_CELL_GATHER"); s.norange = set("AMOF_RDF_NORANGE"); s.force_range = set("AMOF_RDF_FORCE_RANGE");
         s.nocull = one("AMOF_RDF_NOCULL"); s.nozf = one("AMOF_RDF_NOZF"); s.noreach = one("AMOF_RDF_NOREACH");
         s.plan_noskip = one("AMOF_RDF_PLAN_NOSKIP"); s.noplan = one("AMOF_RDF_NOPLAN"); s.noahead = one("AMOF_RDF_NOAHEAD");
+        s.nosat = one("AMOF_RDF_NOSAT");
         s.batch = num("AMOF_RDF_BATCH"); s.fpc = num("AMOF_RDF_FPC"); s.cell_fpc = num("AMOF_RDF_CELL_FPC");
         s.cell_cpw = num("AMOF_RDF_CELL_CPW");
         return s;
@@ -155,6 +157,18 @@ inline GuardThresholds guard_thresholds(int nbins, double guard)
     return g;
 }
 
+// the saturating tail (rdf_sat_math.h): q' = q~ + g + 1 is flagged when fract(q') < 2 g
+struct SatThresholds {
+    float one_p_guard;      // 1 + guard rounded to nearest (its rounding error is a term of the bound: fast_guard_zf_sat)
+    float two_guard;        // 2 guard rounded UP
+};
+inline SatThresholds sat_thresholds(double guard)
+{
+    SatThresholds g = {(float)(1.0 + guard), (float)(2.0 * guard)};
+    if ((double)g.two_guard < 2.0 * guard) g.two_guard = nextafterf(g.two_guard, INFINITY);
+    return g;
+}
+
 // Parked pairs of the IMG / TRI variants; share: expected share of a step's 128 x 512 pairs that is parked.  Small shares:
 // two buffers of >= 96 entries, evaluated a step later -- small enough for five workgroups per CU and no extra barrier;
 // larger shares: one buffer of 1024, evaluated at the end of the step.
@@ -173,9 +187,11 @@ inline ParkedQueue parked_queue(double share)
 // dynamic LDS of the tile kernel: two partner tiles and centre sub-tiles, the histogram with its trash words, the queues
 // plan: a planned launch (rdf_tile_kernel_fast, PLAN) has no centre buffers -- 25 760 bytes at the headline's 2310 bins, six
 // workgroups in a CU's 160 KiB where 29 856 allow five
-inline size_t tile_lds(int nbins, int32_t queue, int32_t defer, bool plan = false)
+// sat: the saturating tail's histogram sits one word up (word 0 is a pad) -- 25 776 bytes at 2310 bins, still six workgroups
+inline size_t tile_lds(int nbins, int32_t queue, int32_t defer, bool plan = false, bool sat = false)
 {
-    const size_t base = 2 * (FAST_TILE + (plan ? 0 : FAST_SUB)) * 16 + (size_t)((nbins + FAST_TRASH + 2 + 3) & ~3) * sizeof(unsigned);
+    const size_t base = 2 * (FAST_TILE + (plan ? 0 : FAST_SUB)) * 16 +
+                        (size_t)((nbins + FAST_TRASH + 2 + (sat ? 1 : 0) + 3) & ~3) * sizeof(unsigned);
     return queue ? base + (defer ? 2 : 1) * (size_t)queue * 8 + 16 : base;
 }
 
@@ -196,6 +212,9 @@ struct RdfSelect {
     GuardThresholds thr = {0.f, 0.f};
     bool zf = false;            // diagonal cells: slab-axis difference from f32 coordinates
     GuardThresholds zf_thr = {0.f, 0.f};
+    bool sat = false;           // the planned f32-slab slice runs the saturating tail (needs zf and cull; the plan is the tier's choice)
+    double guard_zf_sat = 0.0;  // its candidate's error bound g (bins), grid term included
+    SatThresholds sat_thr = {0.f, 0.f};
     bool cell = false;          // 3-D cell list
     int nk[3] = {0, 0, 0};
     bool range = false;         // two-level cell list
@@ -305,6 +324,10 @@ inline RdfSelect rdf_select(const double *cells, const double *heights, int64_t 
         const double guard_zf = fast_guard_zf(nbins, hb, gfrac) + s.guard_m;
         if (!(guard_zf < 0.25)) s.zf = false;
         s.zf_thr = guard_thresholds(nbins, guard_zf);
+        // the planned slice's saturating tail: its chain has its own roundings, hence its own guard
+        s.guard_zf_sat = fast_guard_zf_sat(nbins, hb, gfrac) + s.guard_m;
+        s.sat = s.zf && s.cull && !sw.nosat && s.guard_zf_sat < 0.25;
+        s.sat_thr = sat_thresholds(s.guard_zf_sat);
     }
     // ---- 3-D cell list for cutoffs far below the cell size (cell kernel) ----
     s.cell = s.plain && S <= 16 && N < (1ll << RDF_CELL_ATOM_BITS) && N >= 64 && !sw.nocell;

@@ -2,7 +2,7 @@
 // without a plan, and as the device function of one grid slice of the planned variants (rdf_tile_slice).  One text, because
 // the planned slices are the same kernel with parts compiled out; two places, because a device function that takes the
 // arguments by reference is not compiled like the kernel that owns them, and the variants without a plan stay as they are.
-// In scope: the template parameters ORTHO, CULL, IMG, ZFK, TRI, PLAN, AHEAD, KIND and the arguments `fa`.
+// In scope: the template parameters ORTHO, CULL, IMG, ZFK, TRI, PLAN, AHEAD, KIND, SAT and the arguments `fa`.
     // TRI >= 0: general cells in the orthogonalised lattice frame (fast_quad_tri; TRI % 5: near tests, TRI / 5: x wrap with the y term)
     static_assert(!ZFK || (ORTHO && !IMG) || TRI >= 0, "f32 slab coordinates: diagonal cells (no image queue) or TRI");
     static_assert(TRI < 0 || (!ORTHO && !IMG && ZFK), "TRI: general cells, f32 slab coordinates, its own queue");
@@ -30,6 +30,10 @@
     // in integer form and no others; every step of the plan belongs to exactly one of the two, and integer histograms add
     // (rdf_tile_kernel_fast: the grid's two z slices)
     static_assert((KIND != 0) == PLAN, "KIND: the plan variant");
+    // SAT (PLAN only): the histogram sits one word up in LDS (both slices: one launch, one LDS size), and the slice on f32 slab
+    // coordinates runs the saturating tail (SATS; rdf_sat_math.h, fast_bin<SAT>): no per-pair clamp, no centring of the edge test
+    static_assert(!SAT || PLAN, "SAT: the plan variant");
+    constexpr bool SATS = SAT && KIND == 1;
     // TRI = 10 / 11: near mode 4 with the exact-half x wrap, c10 = + 1/2 / - 1/2 (tri_q_twin)
     constexpr int NEAR = TRI >= 10 ? 4 : (TRI >= 0 ? TRI % 5 : 0);
     constexpr bool XW = TRI >= 5;
@@ -38,8 +42,11 @@
     extern __shared__ __align__(16) unsigned char lds_raw[];
     // double-buffered tiles: J (512 entries) and the centre sub-tile (128 entries; none with a plan: load_c)
     // (the histogram first: bin_count forms LDS byte addresses from the candidate's bits)
-    unsigned *hist = reinterpret_cast<unsigned *>(lds_raw);                  // [nbins + trash], padded to 16 bytes
-    uint4 *tqb = reinterpret_cast<uint4 *>(hist + ((fa.a.nbins + FAST_TRASH + 2 + 3) & ~3));      // [2][FAST_TILE]
+    // (SATS: word 0 is a pad, bin b is word b + 1 -- the address of a candidate q' >= 1 is 4 floor(q') -- and every pointer to
+    //  the histogram but bin_count's own arithmetic is `hist`: the zeroing loop, the refinements and the flush follow by themselves)
+    unsigned *hist0 = reinterpret_cast<unsigned *>(lds_raw);                 // [nbins + trash (+ pad)], padded to 16 bytes
+    unsigned *hist = hist0 + (SATS ? 1 : 0);
+    uint4 *tqb = reinterpret_cast<uint4 *>(hist0 + ((fa.a.nbins + FAST_TRASH + 2 + (SAT ? 1 : 0) + 3) & ~3));      // [2][FAST_TILE]
     uint4 *tcb = tqb + 2 * FAST_TILE;                                        // [2][FAST_SUB]; PLAN: [0]
     // IMG: queue of the pairs that need the canonical evaluation (drained densely once per step), two counters
     // (two buffers: a step parks into one while the previous step's is drained; three counters so that one can be
@@ -87,8 +94,12 @@
     // and the LDS histogram is flushed once for everything.
     const int nsub = (ti.count + FAST_SUB - 1) / FAST_SUB;
     const int la = 2 * lane, lb = la + 1;                          // local indices in the sub-tile
-    const float half_m_guard = fa.half_m_guard;
-    const float nb_hi = fa.nb_hi;
+    // (SATS: the two words of the pair loops are the edge test's 2 g and the candidate's addend 1 + g -- in the scalar
+    //  registers and the parameters of fast_quad / fast_bin that the clamped tail uses for 1/2 - g and nbins + g, named there;
+    //  clampv is dead in that slice: its place is taken by sat.C)
+    const float half_m_guard = SATS ? fa.sat_two_guard : fa.half_m_guard;
+    const float nb_hi = SATS ? fa.sat_one_p_guard : fa.nb_hi;
+    SatLane sat = {0.0f, 0.0f, 0.0f, 0.0f};      // SATS: the lane's clamp value C, 1 / C and the in-plane scales over C^2
     const float clampv = (float)nbins + 0.5f + (float)(lane & (FAST_TRASH - 1));   // see fast_bin<AA>
     int cntj = tj.count;
     int cntj4 = (cntj + 3) & ~3;
@@ -190,7 +201,7 @@
                          "+s"(own_mul), "+s"(own_add), "+s"(f0));
             cntj4 = (cntj + 3) & ~3;
             full = cntj & ~3;
-            tqb = reinterpret_cast<uint4 *>(hist + ((nb_lds + FAST_TRASH + 2 + 3) & ~3));      // (the LDS layout at the top of the kernel)
+            tqb = reinterpret_cast<uint4 *>(hist0 + ((nb_lds + FAST_TRASH + 2 + (SAT ? 1 : 0) + 3) & ~3));      // (the LDS layout at the top of the kernel)
         }
         if (PLAN && new_frame) { if (fl_j >= 0) jbp = __builtin_amdgcn_readfirstlane(jbp ^ 1); fl_j = fl; }
         const unsigned long long rest = live & (live - 1ull);          // PLAN: the live steps behind this one
@@ -227,6 +238,7 @@
 #pragma unroll
                 for (int k = 0; k < 3; k++) sc64r[k] = uniform_f64(fs->sc64[k]);
             }
+            if constexpr (SATS) sat = sat_lane(nb_lds, lane, sc64r[0], sc64r[1]);
             if (TRI >= 0) {     // L00, L10, L11, L22 of the level-2 form (rdf_pair_refine_tri): a load at the head of every visit would cost its latency
                 sc64r[0] = uniform_f64(fs->sc64[0]); sc64r[3] = uniform_f64(fs->sc64[3]);
                 sc64r[4] = uniform_f64(fs->sc64[4]); sc64r[8] = uniform_f64(fs->sc64[8]);
@@ -426,6 +438,7 @@
             }
             zaf = has_a ? (float)((double)(int)(uaz - z0) * cz) : __builtin_inff();
             zbf = has_b ? (float)((double)(int)(ubz - z0) * cz) : __builtin_inff();
+            if constexpr (SATS) { zaf = sat_centre(zaf, sat.invC); zbf = sat_centre(zbf, sat.invC); }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
         const QAtom *__restrict__ qseg = PLAN ? nullptr : fa.Q + (size_t)fl * (size_t)a.N + tj.start;
@@ -480,41 +493,41 @@
                         if (j0 >= qe) continue;
                         pre_prime<ZF>(pre, tq_addr + 16u * (unsigned)j0, uax, uay, uaz, ubx, uby, ubz);
                         for (; j0 < own_end; j0 += 16)
-                            fast_quad<ORTHO, true, true, IMG, ZF, ZFK, AA, PARK, true, 1, PLAN>(hist, fa, sc64, g, sc, tq, j0, cntj, ha, hb, ia, ib,
+                            fast_quad<ORTHO, true, true, IMG, ZF, ZFK, AA, PARK, true, 1, PLAN, SATS && ZF>(hist, fa, sc64, g, sc, tq, j0, cntj, ha, hb, ia, ib,
                                                                                 half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
                                                                                 idb, p, near_f, gi, nq, nullptr, nq_cap, zaf,
                                                                                 zbf, qseg, clampv, &lq, pre,
-                                                                                tq_addr + 16u * (unsigned)(j0 + 16 < qe ? j0 + 16 : j0), &late);
+                                                                                tq_addr + 16u * (unsigned)(j0 + 16 < qe ? j0 + 16 : j0), &late, &sat);
                         for (; j0 < qe_plain; j0 += 16)
-                            fast_quad<ORTHO, false, false, IMG, ZF, ZFK, AA, PARK, true, 1, PLAN>(hist, fa, sc64, g, sc, tq, j0, cntj, ha, hb, ia, ib,
+                            fast_quad<ORTHO, false, false, IMG, ZF, ZFK, AA, PARK, true, 1, PLAN, SATS && ZF>(hist, fa, sc64, g, sc, tq, j0, cntj, ha, hb, ia, ib,
                                                                                   half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
                                                                                   idb, p, near_f, gi, nq, nullptr, nq_cap,
                                                                                   zaf, zbf, qseg, clampv, &lq, pre,
-                                                                                  tq_addr + 16u * (unsigned)(j0 + 16 < qe ? j0 + 16 : j0), &late);
+                                                                                  tq_addr + 16u * (unsigned)(j0 + 16 < qe ? j0 + 16 : j0), &late, &sat);
                         if (j0 == full && j0 < qe && full < cntj)
-                            fast_quad<ORTHO, false, true, IMG, ZF, ZFK, AA, PARK, true, 2, PLAN>(hist, fa, sc64, g, sc, tq, full, cntj, ha, hb, ia, ib,
+                            fast_quad<ORTHO, false, true, IMG, ZF, ZFK, AA, PARK, true, 2, PLAN, SATS && ZF>(hist, fa, sc64, g, sc, tq, full, cntj, ha, hb, ia, ib,
                                                                                  half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
                                                                                  idb, p, near_f, gi, nq, nullptr, nq_cap, zaf,
-                                                                                 zbf, qseg, clampv, &lq, pre, 0u, &late);
+                                                                                 zbf, qseg, clampv, &lq, pre, 0u, &late, &sat);
                         else
                             pre_drain(pre);
                         continue;
                     }
                     for (; j0 < own_end; j0 += 16)
-                        fast_quad<ORTHO, true, true, IMG, ZF, ZFK, AA, PARK, true, 0, PLAN>(hist, fa, sc64, g, sc, tq, j0, cntj, ha, hb, ia, ib,
+                        fast_quad<ORTHO, true, true, IMG, ZF, ZFK, AA, PARK, true, 0, PLAN, SATS && ZF>(hist, fa, sc64, g, sc, tq, j0, cntj, ha, hb, ia, ib,
                                                                          half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
                                                                          idb, p, near_f, gi, nq, nullptr, nq_cap, zaf,
-                                                                         zbf, qseg, clampv, &lq, nullptr, 0u, &late);
+                                                                         zbf, qseg, clampv, &lq, nullptr, 0u, &late, &sat);
                     for (; j0 < qe_plain; j0 += 16)
-                        fast_quad<ORTHO, false, false, IMG, ZF, ZFK, AA, PARK, true, 0, PLAN>(hist, fa, sc64, g, sc, tq, j0, cntj, ha, hb, ia, ib,
+                        fast_quad<ORTHO, false, false, IMG, ZF, ZFK, AA, PARK, true, 0, PLAN, SATS && ZF>(hist, fa, sc64, g, sc, tq, j0, cntj, ha, hb, ia, ib,
                                                                            half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
                                                                            idb, p, near_f, gi, nq, nullptr, nq_cap,
-                                                                           zaf, zbf, qseg, clampv, &lq, nullptr, 0u, &late);
+                                                                           zaf, zbf, qseg, clampv, &lq, nullptr, 0u, &late, &sat);
                     if (j0 == full && j0 < qe && full < cntj)
-                        fast_quad<ORTHO, false, true, IMG, ZF, ZFK, AA, PARK, true, 0, PLAN>(hist, fa, sc64, g, sc, tq, full, cntj, ha, hb, ia, ib,
+                        fast_quad<ORTHO, false, true, IMG, ZF, ZFK, AA, PARK, true, 0, PLAN, SATS && ZF>(hist, fa, sc64, g, sc, tq, full, cntj, ha, hb, ia, ib,
                                                                           half_m_guard, nb_hi, uax, uay, uaz, ida, ubx, uby, ubz,
                                                                           idb, p, near_f, gi, nq, nullptr, nq_cap, zaf,
-                                                                          zbf, qseg, clampv, &lq, nullptr, 0u, &late);
+                                                                          zbf, qseg, clampv, &lq, nullptr, 0u, &late, &sat);
                     continue;
                 }
                 if (diag) {
@@ -559,7 +572,7 @@
                     const int j = (int)(code >> 1);
                     const bool isb = (code & 1u) != 0u;
                     const uint4 qr = tq[j];
-                    rdf_pair_refine<ORTHO, ZFK, AA, PLAN>(hist, fa, sc64, g, qk, isb ? ubx : uax, isb ? uby : uay, isb ? ubz : uaz, qr, p,
+                    rdf_pair_refine<ORTHO, ZFK, AA, PLAN, SATS>(hist, fa, sc64, g, qk, isb ? ubx : uax, isb ? uby : uay, isb ? ubz : uaz, qr, p,
                                                           isb ? idb : ida, qseg, j, &late);
                 }
             }
